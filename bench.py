@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the stereo-pair -> disparity-map path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, config).  --full adds
+everything else: the instrumented second pass (step spreads, stage times, roofline, traffic / VALU figures) and the CPU
+baseline.  --dump-outputs DIR writes the maps of the last timed step (what PairPipeline.results() hands a caller) as
+DIR/<name>.npy in float32; inputs are seeded, so two builds run with the same arguments can be compared map for map.
 
 A step = one synthetic 1242x375 stereo pair at D=192 through the whole path: guidance statistics, the
 fused single-kernel aggregation (cost build -> integral -> box -> a,b -> integral -> box -> q per strip,
@@ -18,9 +23,9 @@ boundaries inside the C-ABI (smx_set_timing(2) / smx_stage_times).  The events r
 steps: every event record costs a bubble on the queue, and 11 of them per 0.9 ms step would take ~9 % off `value`;
 the timed region of the contract (value, ms_per_step) has no event in it.  `operator` repeats the figure for
 the whole smx_dev_aggregate_wta_pair call (key presets, guidance statistics, walker, WTA pass), which is what the
-lines of rounds 1-3 reported as `frac`.
-cpu_baseline: the CPU oracle (port of the reference kernels, 1 thread) timed on this box's host
-cores on the same pair -- a reported baseline, not the target.
+lines of rounds 1-3 reported as `frac`.  (--full only)
+cpu_baseline (--full only): the CPU oracle (port of the reference kernels, 1 thread) timed on the host cores of
+the machine that runs the benchmark, same pair -- a reported baseline, not the target.
 """
 import argparse
 import json
@@ -34,6 +39,23 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 ALGO_BYTES_PER_CELL = 8.0
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20            # pixels kept per map when the whole maps would exceed the budget
+DUMP_SAMPLE_SEED = 12345
+
+
+def dump_outputs(out_dir, maps):
+    """maps: name -> (h, w) numpy array.  Writes float32 copies; over the budget, the same seeded pixel sample of every map."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(maps.values())).size
+    idx = None
+    if len(maps) * (n * 4 + 128) > DUMP_BUDGET_BYTES:     # (128: the .npy header)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    for name, a in maps.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a if idx is None else a.reshape(-1)[idx])
 
 
 def main():
@@ -58,7 +80,16 @@ def main():
                     help="torch.distributed backend of the N > 1 exchange step: nccl = RCCL over xGMI, one GPU per rank (what the "
                          "scaling run uses); gloo = the SAME control flow with the keys staged through host memory, ranks may "
                          "share a GPU (rehearsal of the N > 1 path on a one-GPU box; not a performance number)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the instrumented second pass over the K steps (step spreads, stage times, "
+                         "roofline, traffic / VALU figures) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step as DIR/<name>.npy (float32); above "
+                         f"{DUMP_BUDGET_BYTES // 10**6} MB a fixed seeded sample of pixels, flat indices in "
+                         "DIR/sample_index.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -153,8 +184,6 @@ def main():
         step()
     fence()
     pipe.check_status()       # a timed-out hand-off would invalidate everything that follows
-    import ctypes as C
-    from stereo_matching_cuda_amd import _lib
 
     # ---- the timed region of the contract: exactly K steps between two fences, nothing but the hot path in it (an event
     # record costs a bubble of 5-20 us on this queue: per-step and per-stage events would take ~9 % off a 0.9 ms step)
@@ -171,76 +200,9 @@ def main():
         dt = float(t.item())
     chunk, walker_launches = pipe.last_chunk()      # what `slices_in_flight` came to in the timed steps
 
-    # ---- the same K steps again, instrumented: HIP events around every step and call (torch, current stream) and around
-    # every stage inside the C-ABI (smx_set_timing(2): events on the stream the kernels are launched on, no
-    # synchronisation).  Spreads, the walker's launch duration and the roofline come from this pass.
-    events = []
-    smx.check(smx.lib().smx_set_timing(2))
-    fence()
-    t0i = time.perf_counter()
-    for _ in range(args.steps):
-        step(events)
-    fence()
-    dti = time.perf_counter() - t0i
-    stage = _lib.StageMs()
-    stage_rc = smx.lib().smx_stage_times(C.byref(stage))
-    smx.check(smx.lib().smx_set_timing(0))
-    pipe.check_status()
-
-    def spread(v):
-        v = sorted(v)
-        return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "mean": sum(v) / len(v)} if v else None
-
-    agg_ms = [e0.elapsed_time(e1) for _, e0, e1, _ in events]
-    step_ms = [es.elapsed_time(ee) for es, _, _, ee in events]
-    agg_avg_s = (sum(agg_ms) / max(1, len(agg_ms))) * 1e-3
-    cells_per_call = 2.0 * w * h * local_slices   # left + right volume
-    operator_achieved = ALGO_BYTES_PER_CELL * cells_per_call / agg_avg_s / 1e9 if agg_avg_s > 0 else 0.0
-    # the walker kernel alone: its launches between the stage events of the C-ABI, summed over the timed region
-    # (chunked workspaces: several launches per call, each over its share of the cells)
-    ncalls = max(1, stage.calls) if stage_rc == 0 else 0
-    if stage_rc == 0 and (stage.calls != args.steps or stage.dropped):
-        # (the C-ABI keeps at most 32768 stage marks: a longer instrumented pass would average a truncated set)
-        print(f"bench.py: stage events of {stage.calls} calls for {args.steps} steps, {stage.dropped} marks dropped -- stage "
-              "times cover only the recorded ones", file=sys.stderr)
-    walk_avg_s = stage.aggregation / ncalls * 1e-3 if ncalls else 0.0
-    achieved = ALGO_BYTES_PER_CELL * cells_per_call / walk_avg_s / 1e9 if walk_avg_s > 0 else operator_achieved
-
-    # HBM bytes of one aggregation call from the committed PMC profile of this same command
-    # (tools/pmc.sh + tools/traffic.py; FETCH_SIZE/WRITE_SIZE in separate passes, gfx950 x2 fetch
-    # correction calibrated on a kernel with a known byte count).  Only valid for the profiled config.
-    traffic = None
-    traffic_src = None
-    tname = {"kitti": "r05_traffic.json", "motorcycle": "r05_motorcycle_traffic.json",
-             "4k": "r05_4k_traffic.json"}.get(args.workload) if args.mode == "exact" else None
-    tpath = os.path.join(ROOT, "profiles", tname) if tname else None
-    if world == 1 and tpath and args.slices_in_flight is None and args.source == "images" and os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            # the profile belongs to one build of the library: a stale file is not quoted
-            if tj.get("library") != smx.lib().smx_version().decode():
-                raise KeyError("library")
-            traffic = float(tj["walker_hbm_bytes"])
-            traffic_src = (f"profiles/{tname}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command in "
-                           "separate passes, (2*FETCH_SIZE + WRITE_SIZE)*1024 of the walker kernel per launch "
-                           "(tools/gpu_suite.sh, tools/traffic.py); an UPPER bound: the x2 FETCH_SIZE rule of the "
-                           "guide over-counts narrow loads")
-        except (ValueError, KeyError):
-            traffic = None
-
-    # VALU issue capacity the walker launch used: its dynamic instruction count (committed PMC profile of this build and
-    # workload) x the SIMD cycles of its instruction mix / (LIVE launch duration x clock x SIMDs)  -- tools/valu.py
-    valu_frac = None
-    vpath = os.path.join(ROOT, "profiles", "r05_valu.json")
-    if world == 1 and args.workload == "kitti" and args.mode == "exact" and args.source == "images" and walk_avg_s > 0 \
-            and os.path.exists(vpath):
-        try:
-            vj = json.load(open(vpath))
-            if vj.get("library") == smx.lib().smx_version().decode():
-                valu_frac = (float(vj["walker_valu_instructions_per_launch"]) * float(vj["simd_cycles_per_valu_instruction"])
-                             / (walk_avg_s * float(vj["shader_clock_ghz"]) * 1e9 * float(vj["simds"])))
-        except (ValueError, KeyError):
-            valu_frac = None
+    # ---- the maps of the last timed step, before anything else runs on the pipeline (every rank holds the merged maps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe.results())
 
     result = {
         "metric": "disparity MPix/s (stereo pair -> L+R disparity + occlusion-filled map)"
@@ -266,42 +228,120 @@ def main():
                    "backend": args.backend if world > 1 else None,
                    "slices_in_flight": chunk, "walker_launches_per_call": walker_launches,
                    "library": smx.lib().smx_version().decode()},
-        "instrumented_pass": {
-            "what": "the same K steps run a second time with HIP events around every step, call and stage; `step_ms`, "
-                    "`roofline.avg_launch_ms`, `stage_ms_per_call` and `operator.call_ms` are from this pass (events cost "
-                    "bubbles, so its steps are slower than the timed region's)",
-            "ms_per_step": dti / args.steps * 1e3,
-        },
-        "step_ms": spread(step_ms),
-        "roofline": {
-            "bound": "hbm",
-            "scope": "walker_kernel",     # frac / achieved / avg_launch_ms: the dominant KERNEL (rounds 1-3 quoted the whole call: `operator`)
-            "kernel": "fused guided-filter aggregation walker, both views per launch (k_v5_walk; k_v4_walk where the comb "
-                      "walker does not apply)",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            # which wall the kernel is nearer to: share of the chip's VALU issue capacity the launch used (null where no PMC
-            # profile of this build and workload is committed).  The kernel is bound by neither: dependent chains per wave.
-            "valu_frac": valu_frac,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "avg_launch_ms": walk_avg_s * 1e3,
-            "algorithmic_bytes_per_launch": ALGO_BYTES_PER_CELL * cells_per_call,
-            "stage_ms_per_call": ({k: getattr(stage, k) / ncalls for k in ("guidance", "aggregation", "wta", "finish")}
-                                  if ncalls else None),
-            "operator": {
-                "what": "the whole smx_dev_aggregate_wta_pair call (guidance statistics, walker, WTA pass): the `frac` of "
-                        "the round 1-3 lines",
-                "call_ms": spread(agg_ms),
-                "achieved": operator_achieved,
-                "frac": operator_achieved / HBM_PEAK_GBS,
-            },
-        },
     }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        import ctypes as C
+        from stereo_matching_cuda_amd import _lib
+
+        # ---- the same K steps again, instrumented: HIP events around every step and call (torch, current stream) and around
+        # every stage inside the C-ABI (smx_set_timing(2): events on the stream the kernels are launched on, no
+        # synchronisation).  Spreads, the walker's launch duration and the roofline come from this pass.
+        events = []
+        smx.check(smx.lib().smx_set_timing(2))
+        fence()
+        t0i = time.perf_counter()
+        for _ in range(args.steps):
+            step(events)
+        fence()
+        dti = time.perf_counter() - t0i
+        stage = _lib.StageMs()
+        stage_rc = smx.lib().smx_stage_times(C.byref(stage))
+        smx.check(smx.lib().smx_set_timing(0))
+        pipe.check_status()
+
+        def spread(v):
+            v = sorted(v)
+            return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "mean": sum(v) / len(v)} if v else None
+
+        agg_ms = [e0.elapsed_time(e1) for _, e0, e1, _ in events]
+        step_ms = [es.elapsed_time(ee) for es, _, _, ee in events]
+        agg_avg_s = (sum(agg_ms) / max(1, len(agg_ms))) * 1e-3
+        cells_per_call = 2.0 * w * h * local_slices   # left + right volume
+        operator_achieved = ALGO_BYTES_PER_CELL * cells_per_call / agg_avg_s / 1e9 if agg_avg_s > 0 else 0.0
+        # the walker kernel alone: its launches between the stage events of the C-ABI, summed over the timed region
+        # (chunked workspaces: several launches per call, each over its share of the cells)
+        ncalls = max(1, stage.calls) if stage_rc == 0 else 0
+        if stage_rc == 0 and (stage.calls != args.steps or stage.dropped):
+            # (the C-ABI keeps at most 32768 stage marks: a longer instrumented pass would average a truncated set)
+            print(f"bench.py: stage events of {stage.calls} calls for {args.steps} steps, {stage.dropped} marks dropped -- stage "
+                  "times cover only the recorded ones", file=sys.stderr)
+        walk_avg_s = stage.aggregation / ncalls * 1e-3 if ncalls else 0.0
+        achieved = ALGO_BYTES_PER_CELL * cells_per_call / walk_avg_s / 1e9 if walk_avg_s > 0 else operator_achieved
+
+        # HBM bytes of one aggregation call from the committed PMC profile of this same command
+        # (tools/pmc.sh + tools/traffic.py; FETCH_SIZE/WRITE_SIZE in separate passes, gfx950 x2 fetch
+        # correction calibrated on a kernel with a known byte count).  Only valid for the profiled config.
+        traffic = None
+        traffic_src = None
+        tname = {"kitti": "r05_traffic.json", "motorcycle": "r05_motorcycle_traffic.json",
+                 "4k": "r05_4k_traffic.json"}.get(args.workload) if args.mode == "exact" else None
+        tpath = os.path.join(ROOT, "profiles", tname) if tname else None
+        if world == 1 and tpath and args.slices_in_flight is None and args.source == "images" and os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                # the profile belongs to one build of the library: a stale file is not quoted
+                if tj.get("library") != smx.lib().smx_version().decode():
+                    raise KeyError("library")
+                traffic = float(tj["walker_hbm_bytes"])
+                traffic_src = (f"profiles/{tname}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command in "
+                               "separate passes, (2*FETCH_SIZE + WRITE_SIZE)*1024 of the walker kernel per launch "
+                               "(tools/gpu_suite.sh, tools/traffic.py); an UPPER bound: the gfx950 x2 FETCH_SIZE "
+                               "correction over-counts narrow loads")
+            except (ValueError, KeyError):
+                traffic = None
+
+        # VALU issue capacity the walker launch used: its dynamic instruction count (committed PMC profile of this build and
+        # workload) x the SIMD cycles of its instruction mix / (LIVE launch duration x clock x SIMDs)  -- tools/valu.py
+        valu_frac = None
+        vpath = os.path.join(ROOT, "profiles", "r05_valu.json")
+        if world == 1 and args.workload == "kitti" and args.mode == "exact" and args.source == "images" and walk_avg_s > 0 \
+                and os.path.exists(vpath):
+            try:
+                vj = json.load(open(vpath))
+                if vj.get("library") == smx.lib().smx_version().decode():
+                    valu_frac = (float(vj["walker_valu_instructions_per_launch"]) * float(vj["simd_cycles_per_valu_instruction"])
+                                 / (walk_avg_s * float(vj["shader_clock_ghz"]) * 1e9 * float(vj["simds"])))
+            except (ValueError, KeyError):
+                valu_frac = None
+
+        result.update({
+            "instrumented_pass": {
+                "what": "the same K steps run a second time with HIP events around every step, call and stage; `step_ms`, "
+                        "`roofline.avg_launch_ms`, `stage_ms_per_call` and `operator.call_ms` are from this pass (events cost "
+                        "bubbles, so its steps are slower than the timed region's)",
+                "ms_per_step": dti / args.steps * 1e3,
+            },
+            "step_ms": spread(step_ms),
+            "roofline": {
+                "bound": "hbm",
+                "scope": "walker_kernel",     # frac / achieved / avg_launch_ms: the dominant KERNEL (rounds 1-3 quoted the whole call: `operator`)
+                "kernel": "fused guided-filter aggregation walker, both views per launch (k_v5_walk; k_v4_walk where the comb "
+                          "walker does not apply)",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                # which wall the kernel is nearer to: share of the chip's VALU issue capacity the launch used (null where no PMC
+                # profile of this build and workload is committed).  The kernel is bound by neither: dependent chains per wave.
+                "valu_frac": valu_frac,
+                "traffic": traffic,
+                "traffic_source": traffic_src,
+                "avg_launch_ms": walk_avg_s * 1e3,
+                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_CELL * cells_per_call,
+                "stage_ms_per_call": ({k: getattr(stage, k) / ncalls for k in ("guidance", "aggregation", "wta", "finish")}
+                                      if ncalls else None),
+                "operator": {
+                    "what": "the whole smx_dev_aggregate_wta_pair call (guidance statistics, walker, WTA pass): the `frac` of "
+                            "the round 1-3 lines",
+                    "call_ms": spread(agg_ms),
+                    "achieved": operator_achieved,
+                    "frac": operator_achieved / HBM_PEAK_GBS,
+                },
+            },
+        })
+
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         oracle.build()
         try:

@@ -4,7 +4,7 @@
 TAG=$1; WL=$2; STEPS=${3:-3}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 $R/bench.py --workload $WL --steps $STEPS --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 500 python3 $R/bench.py --full --workload $WL --steps $STEPS --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --workload $WL --steps $STEPS --warmup 1 --no-cpu-baseline > $O/kt.log 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 500 rocprofv3 --pmc $C --output-format csv -d $O/pmc_$C -- python3 $R/bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_$C.log 2>&1

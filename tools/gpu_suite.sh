@@ -11,7 +11,7 @@ else
 fi
 tail -5 $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 python3 $R/bench.py --steps 20 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 200 python3 $R/bench.py --full --steps 20 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --no-cpu-baseline --steps 10 > $O/kt.log 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 200 rocprofv3 --pmc $C --output-format csv -d $O/pmc_$C -- python3 $R/bench.py --no-cpu-baseline --steps 5 > $O/pmc_$C.log 2>&1
