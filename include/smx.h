@@ -171,9 +171,10 @@ int smx_dev_integral(const float* d_in, float* d_out, int w, int h, int nplanes,
  * hand-off records, control words.  The first 256 bytes hold the call's status word
  * (smx_dev_agg_status).  Fewer slices in flight than s_end - s_begin only means more launches. */
 size_t smx_agg_workspace_bytes(int w, int h, int nslices);
-/* The same for the path that `p` will run in auto mode: with radius <= 9 the fused walker needs ONE plane per slice in
- * flight (plus its hand-off records), about a quarter of the radius-agnostic bound above, which has to cover the five
- * planes per slice of the multi-kernel path (radius > 9, or smx_set_agg_path(1)).  At 3840x2160 this is what lets all 512
+/* The same for the path that `p` will run in auto mode: where a fused walker runs (radius <= 9, thresholds within the
+ * sentinel bound below) it needs ONE plane per slice in flight (plus its hand-off records), about a quarter of the
+ * parameter-agnostic bound above, which has to cover the five planes per slice of the multi-kernel path (radius > 9,
+ * larger thresholds, or smx_set_agg_path(1)).  At 3840x2160 this is what lets all 512
  * slices of a volume go out in one launch inside 64 GB. */
 size_t smx_agg_workspace_bytes_for(const smx_params* p, int w, int h, int nslices);
 
@@ -228,10 +229,12 @@ int smx_dev_agg_fallback(const void* d_workspace, int* ring_walker_reran);
 
 /* Aggregation implementation of the calling THREAD's smx_dev_* and host-pointer stage calls (a persistent
  * context carries its own, smx_ctx_set_agg_path; it starts with the creating thread's):
- *   0 = auto: the fused single-kernel aggregation when radius <= 9, else the multi-kernel path; the fused call
- *       picks the comb walker (smx_agg_v5.hip: radius 9, costs built from the images) or the ring walker
+ *   0 = auto: the fused single-kernel aggregation when radius <= 9 and -- where the costs are built from the images --
+ *       th_color <= 59745 and th_grad <= 59872 (the cost of a partner outside the image comes from a sentinel cell of
+ *       60000 that must saturate both truncations), else the multi-kernel path; the fused call picks the comb walker
+ *       (smx_agg_v5.hip: radius 9, costs built from the images, th_color <= 59744) or the ring walker
  *       (smx_agg_v4.hip: any radius <= 9, materialised cost volumes)
- *   1 = force multi-kernel            2 = force fused (error if radius > 9), walker chosen as in auto
+ *   1 = force multi-kernel            2 = force fused (error where no walker applies), walker chosen as in auto
  *   3 = fused, ring walker forced     5 = fused, comb walker forced (error where it does not apply)
  *   4 = FAST, NOT bit-exact; reported separately, never a default.  Where the comb walker applies: the same sums in the
  *       same order, window means by multiplication with the rounded reciprocal of the area instead of the exact division

@@ -79,7 +79,8 @@ __device__ __forceinline__ uint8_t mean_to_u8(float m) {   // flToChOnGPU guided
 
 // p = (1-alpha)*min(|I1 - I2|, 7) + alpha*min(|g1 - g2|, 2) and I1*p  (costVolume.cu:187,
 // guidedFilter.cu:209).  The halves convert exactly, so the f32 operations equal the reference's; the
-// sentinel 60000 of an out-of-range partner saturates both terms = the border constant (:184).
+// sentinel 60000 of an out-of-range partner saturates both terms = the border constant (:184) -- for thresholds up to
+// 59745 / 59872, the nearest a cell comes to it (larger ones run the multi-kernel path: agg_path_for).
 // The two differences and the two products as packed instructions, the two selects as v_min_f32 (no operand is
 // ever a NaN: the inputs are finite halves, so min(|d|, th) == (|d| < th ? |d| : th)).
 __device__ __forceinline__ f2 cost_pair(fg_t q1, fg_t q2, const CostConst& cc) {

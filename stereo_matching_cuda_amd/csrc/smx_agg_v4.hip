@@ -1303,6 +1303,17 @@ void v4_geometry(int* ow, int* bh) { *ow = v4::OW; *bh = v4::BH; }
 
 bool v4_supported(const smx_params* p) { return p->radius >= 0 && p->radius <= v4::RMAX; }
 
+// Both walkers build the cost of a partner outside the image from the sentinel cell (60000, 60000) of k_v4_guid_rows and rely
+// on min(|d|, threshold) saturating to the threshold there, so that the cost is the border constant of costVolume.cu:184.  In
+// the ring walker's f32 differences the nearest a pixel value (0 .. 255) and a derivative (multiples of 0.5 in [-127.5, 127.5])
+// come to the sentinel is |255 - 60000| = 59745 and |127.5 - 60000| = 59872.5: larger thresholds would not saturate (the comb
+// walker's bounds, in packed halves, are tighter: v5_supported).  The multi-kernel path uses the border constant itself.
+constexpr int RING_TH_COLOR_MAX = 59745, RING_TH_GRAD_MAX = 59872;
+
+static bool ring_applies(const smx_params* p, bool use_cost) {
+    return v4_supported(p) && (use_cost || (p->th_color <= RING_TH_COLOR_MAX && p->th_grad <= RING_TH_GRAD_MAX));
+}
+
 constexpr size_t V4_CTRL_BYTES = 256;   // ticket (zeroed with the flags before every launch)
 
 static size_t v4_flag_bytes_k(int K, int nsv) { return align_up(V4_CTRL_BYTES + (size_t)nsv * K * sizeof(unsigned), 256); }
@@ -1380,6 +1391,41 @@ size_t v5_fix_bytes(int w, int h, int nviews) {
     return 2 * align_up(L.fg * 4, 256) + (size_t)nviews * (align_up(L.plane * 8, 256) + align_up(permb * 5 * 16, 256) + align_up(permb * 20, 256));
 }
 
+// The comb walker (smx_agg_v5.hip) serves radius 9 with eps >= 1; with costs built from the images, default-like cost
+// parameters (v5_supported); with materialised cost volumes, planes of at least one 16-byte quad (the kernel checks the values).
+// It addresses both image planes, the guidance planes and their comb-ordered copies through ONE buffer descriptor with 32-bit
+// offsets, 0x80000000 marking "outside": the whole region must stay below 2 GiB (v5_fix_bytes: the terms of the carving).
+static bool v5_applies(const smx_params* p, int w, int h, int nviews, bool use_cost) {
+    return v5_fix_bytes(w, h, nviews) < 0x80000000ull &&
+           (use_cost ? v5_supported_cost(p) && (size_t)w * h >= 4 : v5_supported(p));
+}
+
+// The one decision of which aggregation a call runs (smx_dev_aggregate_wta, the pair entries, the context, the workspace size):
+// 1 the multi-kernel path, 2 the ring walker, 4 FAST, 5 the comb walker; 0, with *why set, where the forced path does not apply.
+// forced is the caller's smx_set_agg_path value: 0 auto, 1 multi-kernel, 2 fused (walker chosen here), 3 ring walker, 4 FAST,
+// 5 comb walker.  Pure host arithmetic (no GPU needed: smx_debug_agg_path).
+int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, int forced, const char** why) {
+    *why = nullptr;
+    if (forced == 1) return 1;
+    if (!ring_applies(p, use_cost)) {
+        if (forced == 0) return 1;
+        *why = !v4_supported(p) ? "radius > 9"
+                                : "th_color > 59745 or th_grad > 59872 (the sentinel cell of an out-of-range partner would not "
+                                  "saturate the truncation: only the multi-kernel path gives the border cost there)";
+        return 0;
+    }
+    const bool comb = v5_applies(p, w, h, nviews, use_cost);
+    if (forced == 5 && !comb) {
+        *why = "the comb walker does not apply (radius 9, eps in [1, 1e30), default-like cost parameters where the costs are "
+               "built from the images -- thresholds exact in fp16, th_color <= 59744, th_grad <= 59872 --, planes within "
+               "its 2 GiB descriptor)";
+        return 0;
+    }
+    if (forced == 3) return 2;
+    if (forced == 4) return 4;
+    return comb ? 5 : 2;
+}
+
 // Aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses d_guide[v]
 // as guidance; its cost slices are d_cost[v] (materialised, slice s at (s - s_begin)*w*h) or, when
 // d_cost[v] == NULL, are built on the fly against d_guide[v ^ 1] (nviews == 2) / d_other[0].
@@ -1395,22 +1441,17 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
     // The comb walker (smx_agg_v5.hip) serves the hot case: radius 9, costs built from the images, exact mode.
     // opt.walker: 0 = choose, 4 = the ring walker of this file.  Both share this orchestration: image planes, guidance
     // statistics, chunking, WTA pass; only the strip / band geometry and the records differ.
-    // The comb walker addresses both image planes, the guidance planes and their comb-ordered copies through ONE buffer
-    // descriptor with 32-bit offsets, 0x80000000 marking "outside": the whole region must stay below 2 GiB
-    // (v5_fix_bytes: the same terms the carving below uses).
-    const bool v5_fits = v5_fix_bytes(w, h, nviews) < 0x80000000ull;
+    // (Where each walker applies: v5_applies, agg_path_for.)
     // Materialised cost volumes (the reference's calling convention, guidedFilter.cu:198-200) run on the comb walker too
     // (round 5): its cost wave loads the costs and CHECKS them -- +0 or a normal number in [2^-60, 2^60] is what its exactness
     // argument covers.  A violation cannot come back to the host of an asynchronous call, so the ring walker, which takes
     // any input, is queued behind it with a device-side gate (`only_if`): it does nothing unless the comb walker raised the
     // second status word, and the two WTA passes are gated the other way round.  Cost: two empty launches and a memset.
-    const bool use_v5 = opt.walker != 4 && v5_fits &&
-                        (use_cost ? v5_supported_cost(p) && (size_t)w * h >= 4 : v5_supported(p));
+    const bool use_v5 = opt.walker != 4 && v5_applies(p, w, h, nviews, use_cost);
     const bool fallback4 = use_v5 && use_cost;
-    if (opt.walker == 5 && !use_v5)
-        return fail(SMX_E_ARG, "aggregate_v4: the comb walker does not apply (radius 9, eps >= 1, default-like cost parameters where "
-                               "the costs are built from the images, planes of %d x %d within its 2 GiB descriptor: %s)", w, h,
-                    v5_fits ? "yes" : "no");
+    // (the entry points' decision once more: neither walker runs where agg_path_for would not send the call to it)
+    const char* why = nullptr;
+    if (!agg_path_for(p, w, h, nviews, use_cost, opt.walker == 5 ? 5 : 3, &why)) return fail(SMX_E_ARG, "aggregate_v4: %s", why);
     if (info) { *info = AggInfo(); info->walker_used = use_v5 ? 5 : 4; }
     const V4Layout L4 = L;      // the ring walker's geometry (the queued fall-back uses it)
     if (use_v5) {

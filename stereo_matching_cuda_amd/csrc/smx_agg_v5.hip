@@ -196,7 +196,8 @@ __device__ __forceinline__ f2 div_ca_m(f2 e, f2 q, f2 ca) { f2 m; asm("v_pk_fma_
 // halves: pixel values are the integers 0 .. 255 and derivatives multiples of 0.5 in [-127.5, 127.5] (k_v4_prep), so the
 // difference of two cells is EXACT in fp16 and min(|d|, threshold) -- thresholds exact in fp16: v5_supported -- is the very
 // number the reference's f32 arithmetic gets (costVolume.cu:187).  Against the sentinel 60000 of a partner outside the image
-// the difference rounds but stays finite and far above either threshold.  v_fma_mix_f32 with a +0 addend is the
+// the difference rounds but stays finite, at least 59744 (pixel values) / 59872 (derivatives): v5_supported keeps the
+// thresholds at or below those, so the truncation saturates and the cost is the border constant (:184).  v_fma_mix_f32 with a +0 addend is the
 // correctly rounded product of a half and a float (no product here is negative), so the two weighted terms, their sum
 // and I * p round exactly where the reference's do.
 __device__ __forceinline__ unsigned cost_trunc_h2(unsigned q1, unsigned q2, unsigned th2) {
@@ -1442,8 +1443,11 @@ bool v5_supported(const smx_params* p) {
     const float t1 = c.oma * m1, t2 = c.alpha * m2;
     auto ok = [](float t) { return t == 0.0f || t >= 0x1p-60f; };
     if (!(ok(t1) && ok(t2))) return false;
-    // the pipelined form truncates in packed halves: thresholds exact (and finite) in fp16
-    if (!((float)(_Float16)c.th_color == c.th_color && (float)(_Float16)c.th_grad == c.th_grad && c.th_color < 60000.0f && c.th_grad < 60000.0f))
+    // the pipelined form truncates in packed halves: thresholds exact (and finite) in fp16, and small enough that the sentinel
+    // 60000 of a partner outside the image saturates both truncations (the cost there must be the border constant,
+    // costVolume.cu:184): the nearest a cell comes to it is RN16(60000 - 255) = 59744 and RN16(60000 - 127.5) = 59872
+    if (!((float)(_Float16)c.th_color == c.th_color && (float)(_Float16)c.th_grad == c.th_grad && c.th_color <= 59744.0f &&
+          c.th_grad <= 59872.0f))
         return false;
     return true;
 }

@@ -51,7 +51,7 @@ static thread_local int g_keys_fresh = 0;    // smx_set_keys_fresh
 static thread_local AggInfo g_last_info;     // smx_last_agg_chunk
 
 // smx_agg_v4.hip (host orchestration of both fused walkers)
-bool v4_supported(const smx_params* p);
+int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, int forced, const char** why);
 size_t v4_workspace_bytes(int w, int h, int nslices);
 int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
                  const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
@@ -66,7 +66,7 @@ bool v5_supported(const smx_params* p);
 void v5_geometry(int* ow, int* bh);
 void v5_slots(int h, int K, int* bands, int* q_last, int* period);
 
-// the fused aggregation; reports the path that ran: 2 = ring walker, 4 = FAST, 5 = comb walker
+// the fused aggregation of the path agg_path_for chose (2 = ring walker, 4 = FAST, 5 = comb walker); reports it
 static int aggregate_fused(int path, const smx_params* p, int nviews, const uint8_t* const* d_guide,
                            const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
                            const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
@@ -79,7 +79,7 @@ static int aggregate_fused(int path, const smx_params* p, int nviews, const uint
     AggOpts opt;
     opt.keys_fresh = g_keys_fresh != 0;
     opt.fast = path == 4;
-    opt.walker = path == 3 ? 4 : path == 5 ? 5 : 0;
+    opt.walker = path == 2 ? 4 : path == 5 ? 5 : 0;
     opt.max_chunk = g_max_chunk;
     AggInfo info;
     int rc = aggregate_v4(p, nviews, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys, d_mean_u8,
@@ -87,7 +87,7 @@ static int aggregate_fused(int path, const smx_params* p, int nviews, const uint
     if (rc) return rc;
     g_last_info = info;
     if (launches) *launches = info.launches;
-    g_last_path = path == 4 ? 4 : (info.walker_used == 5 ? 5 : 2);
+    g_last_path = path;
     return SMX_OK;
 }
 
@@ -225,9 +225,10 @@ size_t smx_agg_workspace_bytes(int w, int h, int nslices) {
 
 size_t smx_agg_workspace_bytes_for(const smx_params* p, int w, int h, int nslices) {
     if (!p || w < 1 || h < 1 || nslices < 1) return 0;
-    // radius <= 9 runs a fused walker (unless the multi-kernel path is forced: smx_set_agg_path(1) callers size with
-    // smx_agg_workspace_bytes): image / guidance planes, per slice ONE q plane + the hand-off records
-    if (v4_supported(p)) return v4_workspace_bytes(w, h, nslices);
+    // where a fused walker runs for costs built from the images (agg_path_for; forced paths aside: smx_set_agg_path(1) callers
+    // size with smx_agg_workspace_bytes): image / guidance planes, per slice ONE q plane + the hand-off records
+    const char* why = nullptr;
+    if (agg_path_for(p, w, h, 2, false, 0, &why) != 1) return v4_workspace_bytes(w, h, nslices);
     return smx_agg_workspace_bytes(w, h, nslices);
 }
 
@@ -260,6 +261,18 @@ int smx_last_agg_chunk(int* slices_per_launch, int* walker_launches) {
 __attribute__((visibility("default"))) int smx_debug_v5_fix_bytes(int w, int h, int nviews, uint64_t* bytes) {
     SMX_ARG(bytes && w >= 2 && h >= 1 && (nviews == 1 || nviews == 2));
     *bytes = (uint64_t)v5_fix_bytes(w, h, nviews);
+    return SMX_OK;
+}
+
+// (dev / test hook, not in smx.h: the aggregation a call with these arguments runs -- agg_path_for, the decision every entry
+// takes: 1 multi-kernel, 2 ring walker, 4 FAST, 5 comb walker; SMX_E_ARG where the forced path does not apply)
+__attribute__((visibility("default"))) int smx_debug_agg_path(const smx_params* p, int w, int h, int nviews, int use_cost,
+                                                              int forced, int* path) {
+    SMX_ARG(p && path && w >= 2 && h >= 1 && (nviews == 1 || nviews == 2) && forced >= 0 && forced <= 5 && p->radius >= 0);
+    const char* why = nullptr;
+    const int r = agg_path_for(p, w, h, nviews, use_cost != 0, forced, &why);
+    if (!r) return fail(SMX_E_ARG, "smx_debug_agg_path: fused path %d forced but %s", forced, why);
+    *path = r;
     return SMX_OK;
 }
 
@@ -392,13 +405,13 @@ int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uin
     { int rcd = check_same_device(d_workspace, "smx_dev_aggregate_wta"); if (rcd) return rcd; }
     hipStream_t st = (hipStream_t)stream;
     stage_mark(ST_BEGIN, st);
-    // fused path: radius <= 9; cost built on the fly or read from d_cost
-    const bool can_fuse = v4_supported(p);
-    if (g_agg_path >= 2 && !can_fuse)
-        return fail(SMX_E_ARG, "smx_dev_aggregate_wta: fused path forced but radius > 9");
-    if (can_fuse && g_agg_path != 1) {
+    // fused path (agg_path_for); cost built on the fly or read from d_cost
+    const char* why = nullptr;
+    const int path = agg_path_for(p, w, h, 1, d_cost != nullptr, g_agg_path, &why);
+    if (!path) return fail(SMX_E_ARG, "smx_dev_aggregate_wta: fused path %d forced but %s", g_agg_path, why);
+    if (path != 1) {
         g_launches = 0;
-        int rc2 = aggregate_fused(g_agg_path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
+        int rc2 = aggregate_fused(path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
                                &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches);
         if (rc2) return rc2;
         return SMX_OK;
@@ -479,7 +492,10 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
     stage_mark(ST_BEGIN, st);
     const int64_t n = (int64_t)w * h;
     const int64_t vol = n * (s_end - s_begin);
-    if (v4_supported(p) && g_agg_path != 1) {
+    const char* why = nullptr;
+    const int path = agg_path_for(p, w, h, 2, d_cost_l != nullptr, g_agg_path, &why);
+    if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", who, g_agg_path, why);
+    if (path != 1) {
         const uint8_t* guide[2] = {d_left, d_right};
         const uint8_t* other[2] = {d_right, d_left};
         const float* cost[2] = {d_cost_l, d_cost_r};
@@ -488,13 +504,12 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
         uint8_t* mean[2] = {d_mean_u8, d_mean_u8 ? d_mean_u8 + n : nullptr};
         float* agg[2] = {d_agg, d_agg ? d_agg + vol : nullptr};
         g_launches = 0;
-        int rc2 = aggregate_fused(g_agg_path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
+        int rc2 = aggregate_fused(path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
                                d_mean_u8 ? mean : nullptr, d_agg ? agg : nullptr, d_workspace,
                                workspace_bytes, st, &g_launches);
         if (rc2) return rc2;
         return SMX_OK;
     }
-    if (g_agg_path >= 2) return fail(SMX_E_ARG, "%s: fused path forced but radius > 9", who);
     int rc = smx_dev_aggregate_wta(p, d_left, d_right, d_cost_l, w, h, dminl, s_begin, s_end, d_keys,
                                    d_mean_u8, d_agg, d_workspace, workspace_bytes, stream);
     if (rc) return rc;
@@ -755,8 +770,9 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     int rc;
     const int64_t nn = (int64_t)n;
     int64_t* keysL = c->keys.as<int64_t>(); int64_t* keysR = keysL + n;
-    if (c->agg_path >= 2 && !v4_supported(p))
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair: fused path forced but radius > 9");
+    const char* why = nullptr;
+    const int path = agg_path_for(p, w, h, 2, want_cost, c->agg_path, &why);
+    if (!path) return fail(SMX_E_ARG, "smx_ctx_stereo_pair: fused path %d forced but %s", c->agg_path, why);
     struct Nest { Nest() { g_in_ctx += 2; } ~Nest() { g_in_ctx -= 2; } } nest;     // (nested smx_dev_* calls do not restart the stage marks)
     // cost volumes are materialised only when the caller asks for them (main.cu:80-82) and then feed
     // the aggregation like in the reference; otherwise the slices are built on the fly inside it.
@@ -766,7 +782,7 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     }
     if ((rc = smx_dev_init_keys(keysL, 2 * nn, st))) return rc;
     // main.cu:133-134, both views per kernel launch
-    if (v4_supported(p) && c->agg_path != 1) {
+    if (path != 1) {
         const uint8_t* guide[2] = {dL, dR};
         const uint8_t* other[2] = {dR, dL};
         const float* cost[2] = {c->costL.as<float>(), c->costR.as<float>()};
@@ -775,7 +791,7 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
         uint8_t* mv[2] = {mean, mean + n};
         float* av[2] = {c->aggLR.as<float>(), want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr};
         g_launches = 0;
-        if ((rc = aggregate_fused(c->agg_path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
+        if ((rc = aggregate_fused(path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
                                   want_agg ? av : nullptr, c->ws.p, c->ws_bytes, st, &g_launches)))
             return rc;
     } else {

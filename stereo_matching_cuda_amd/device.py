@@ -36,10 +36,10 @@ class PairPipeline:
         self.params = params if params is not None else _lib.default_params()
         local = max(1, self.s_end - self.s_begin)
         sif = local if slices_in_flight is None else max(1, min(local, int(slices_in_flight)))
-        # workspace of the path these parameters run (the fused walker: one plane per slice in flight); a forced
-        # multi-kernel path (smx_set_agg_path(1)) needs the radius-agnostic bound
-        multi = multi_kernel or self.params.radius > 9
-        need = (lambda n: self.lib.smx_agg_workspace_bytes(self.w, self.h, n)) if multi else \
+        # workspace of the path these parameters run (smx_agg_workspace_bytes_for follows the library's choice: a fused
+        # walker, one plane per slice in flight, or the multi-kernel path); a forced multi-kernel path
+        # (smx_set_agg_path(1)) needs the parameter-agnostic bound
+        need = (lambda n: self.lib.smx_agg_workspace_bytes(self.w, self.h, n)) if multi_kernel else \
                (lambda n: self.lib.smx_agg_workspace_bytes_for(C.byref(self.params), self.w, self.h, n))
         while sif > 1 and 2 * need(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
