@@ -3,7 +3,8 @@
  *          (libsmx_hip.so, built from stereo_matching_cuda_amd/csrc/).
  *
  * This is the drop-in boundary for the one hot path of hamza1030/stereo_matching_cuda:
- *   gray -> cost volume -> guided-filter aggregation + winner-take-all -> LR check -> fill.
+ *   gray -> cost volume -> guided-filter aggregation + winner-take-all -> LR check -> fill,
+ * and, beyond the reference, an optional weighted-median refinement of the filled map (smx_weighted_median).
  * Every entry point cites the reference host function it replaces (paths relative to the
  * reference's stereo_matching_cuda/ directory).  Plain pointers and sizes only.
  *
@@ -285,6 +286,44 @@ int smx_dev_fill_occlusion(float* d_disp, int w, int h, float vMin, void* stream
 int smx_dev_finish_pair(const smx_params* p, const int64_t* d_keys, int w, int h, int dminl, int dminr,
                         int dOcclusion, float vMin, float* d_best, float* d_dmap, float* d_occlusion,
                         float* d_filled, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Weighted-median refinement (not a stage of the reference; opt-in, after fill_occlusion)
+ * ---------------------------------------------------------------------------------- */
+
+/* The bilateral weighted median of Hosni et al. (Fast Cost-Volume Filtering, CVPR 2011 / PAMI 2013) that removes the
+ * horizontal streaks of the scan-line fill.  Defaults: radius 9, sigma_s 9.0, sigma_c 25.5 (0.1 on a [0, 1] intensity
+ * scale).  Valid: 1 <= radius <= 15, sigma_s and sigma_c finite and > 0. */
+typedef struct smx_wmf_params {
+    int radius;       /* window (2*radius+1)^2, clipped to the image (no padding) */
+    double sigma_s;   /* spatial */
+    double sigma_c;   /* range (gray levels) */
+} smx_wmf_params;
+void smx_default_wmf_params(smx_wmf_params* p);
+
+/* The integer weight tables, computed on the host in double (works without a GPU):
+ *   spatial[k] = floor(1023 * exp(-k / sigma_s^2) + 0.5)   k = dx^2 + dy^2 = 0 .. 2*radius^2
+ *   range[t]   = floor(1023 * exp(-t^2 / sigma_c^2) + 0.5) t = |guide(p) - guide(q)| = 0 .. 255
+ * The weight of sample q for output pixel p is w(p, q) = spatial[dx^2 + dy^2] * range[t] (< 2^20), so a window's sum
+ * is below 2^30 and every sum is exact in any order. */
+int smx_wmf_weights(const smx_wmf_params* p, uint16_t* spatial, uint16_t* range);
+
+/* out = weighted median of disp guided by `guide` (u8 gray of the view the map belongs to), labels [dmin, dmin+size_d).
+ *   samples:  the pixels q of the window centred on p, clipped to the image; q counts only if disp[q] is an integer in
+ *             [dmin, dmin + size_d) (-0.0 is the integer 0; NaN, +-inf, fractions, labels out of range and the LR-check
+ *             marker dmin - 100 count for nothing)
+ *   result:   (float)(dmin + k*), k* the SMALLEST k with 2 * cum(k) >= total, where total = sum of the weights of the
+ *             counting samples and cum(k) = the sum over those with label <= dmin + k; if total == 0, disp[p]
+ *   select:   NULL filters every pixel; otherwise pixel i is filtered iff (int)select[i] < dmin (select[i] truncated
+ *             toward zero; NaN and +-inf select nothing) -- fill_occlusion's test, so passing the pair's occlusion map
+ *             filters exactly the pixels the LR check invalidated.  Pixels that are not filtered are copied bit for bit.
+ * out must not be disp (SMX_E_ARG).  1 <= size_d <= 4096, dmin + size_d <= INT_MAX; any width (rows are not staged whole).
+ * smx_weighted_median: host pointers, synchronous.  smx_dev_weighted_median: device pointers, one kernel launch on
+ * `stream`, no allocation, no synchronisation, no workspace (graph-capturable). */
+int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const float* disp, const float* select,
+                        float* out, int w, int h, int dmin, int size_d);
+int smx_dev_weighted_median(const smx_wmf_params* p, const uint8_t* d_guide, const float* d_disp,
+                            const float* d_select, float* d_out, int w, int h, int dmin, int size_d, void* stream);
 
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);

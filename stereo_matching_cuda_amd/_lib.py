@@ -33,6 +33,11 @@ class Params(C.Structure):
                 ("radius", C.c_int), ("eps", C.c_double), ("d_lr", C.c_int)]
 
 
+class WmfParams(C.Structure):
+    """smx_wmf_params: the weighted-median refinement (not a stage of the reference)."""
+    _fields_ = [("radius", C.c_int), ("sigma_s", C.c_double), ("sigma_c", C.c_double)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -55,6 +60,7 @@ def build(verbose=False):
 _vp, _i, _i64, _f, _sz, _u64, _u32 = (C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t,
                                       C.c_uint64, C.c_uint32)
 _PP = C.POINTER(Params)
+_WP = C.POINTER(WmfParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -104,6 +110,10 @@ SIGNATURES = {
     "smx_set_timing": (_i, [_i]),
     "smx_last_agg_ms": (_i, [C.POINTER(_f), C.POINTER(_i)]),
     "smx_stage_times": (_i, [C.POINTER(StageMs)]),
+    "smx_default_wmf_params": (None, [_WP]),
+    "smx_wmf_weights": (_i, [_WP, _vp, _vp]),
+    "smx_weighted_median": (_i, [_WP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_dev_weighted_median": (_i, [_WP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None
@@ -157,4 +167,10 @@ def check(rc):
 def default_params():
     p = Params()
     lib().smx_default_params(C.byref(p))
+    return p
+
+
+def default_wmf_params():
+    p = WmfParams()
+    lib().smx_default_wmf_params(C.byref(p))
     return p

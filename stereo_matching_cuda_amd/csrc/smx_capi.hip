@@ -1,5 +1,7 @@
 // smx_capi.hip -- the C-ABI of include/smx.h: argument checks, workspace carving, stage
 // orchestration, and the host-pointer wrappers that mirror the reference's per-stage functions.
+#include <limits.h>
+#include <math.h>
 #include <string.h>
 
 #include <new>
@@ -138,7 +140,7 @@ void smx_default_params(smx_params* p) {
 
 const char* smx_last_error(void) { return g_err.c_str(); }
 
-const char* smx_version(void) { return "smx-hip gfx950 0.9 (comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker; WTA winner in the float domain; guidance in three launches; two 512-thread workgroups per CU)"; }
+const char* smx_version(void) { return "smx-hip gfx950 0.10 (weighted-median refinement of the filled map: smx_weighted_median; comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker; WTA winner in the float domain; guidance in three launches; two 512-thread workgroups per CU)"; }
 
 int smx_device_count(void) {
     int n = 0;
@@ -657,6 +659,61 @@ int smx_fill_occlusion(float* disparity, int w, int h, float vMin) {
     if (rc) return rc;
     SMX_HIP(hipDeviceSynchronize());
     SMX_HIP(hipMemcpy(disparity, d.p, bytes, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
+// ---- weighted-median refinement (not in the reference; smx_wmf.hip) ----------------------------------
+void smx_default_wmf_params(smx_wmf_params* p) {
+    if (!p) return;
+    p->radius = 9; p->sigma_s = 9.0; p->sigma_c = 25.5;
+}
+
+static bool wmf_params_ok(const smx_wmf_params* p) {
+    return p && p->radius >= 1 && p->radius <= 15 && isfinite(p->sigma_s) && p->sigma_s > 0 && isfinite(p->sigma_c) &&
+           p->sigma_c > 0;
+}
+
+int smx_wmf_weights(const smx_wmf_params* p, uint16_t* spatial, uint16_t* range) {
+    SMX_ARG(wmf_params_ok(p) && spatial && range);
+    const double ss = p->sigma_s * p->sigma_s, sc = p->sigma_c * p->sigma_c;
+    // (k = 0 / t = 0 directly: a sigma whose square underflows would make 0 / 0 of them)
+    for (int k = 0; k <= 2 * p->radius * p->radius; ++k)
+        spatial[k] = k == 0 ? 1023 : (uint16_t)floor(1023.0 * exp(-(double)k / ss) + 0.5);
+    for (int t = 0; t < 256; ++t)
+        range[t] = t == 0 ? 1023 : (uint16_t)floor(1023.0 * exp(-(double)t * t / sc) + 0.5);
+    return SMX_OK;
+}
+
+int smx_dev_weighted_median(const smx_wmf_params* p, const uint8_t* d_guide, const float* d_disp,
+                            const float* d_select, float* d_out, int w, int h, int dmin, int size_d, void* stream) {
+    SMX_ARG(wmf_params_ok(p) && d_guide && d_disp && d_out && w >= 1 && h >= 1);
+    SMX_ARG(size_d >= 1 && size_d <= 4096 && (long long)dmin + size_d <= INT_MAX);
+    SMX_ARG((const void*)d_out != (const void*)d_disp);
+    uint16_t ws[2 * 15 * 15 + 1], wc[256];
+    smx_wmf_weights(p, ws, wc);
+    return launch_weighted_median(p->radius, ws, wc, d_guide, d_disp, d_select, d_out, w, h, dmin, size_d,
+                                  (hipStream_t)stream);
+}
+
+int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const float* disp, const float* select,
+                        float* out, int w, int h, int dmin, int size_d) {
+    SMX_ARG(wmf_params_ok(p) && guide && disp && out && w >= 1 && h >= 1);
+    SMX_ARG(size_d >= 1 && size_d <= 4096 && (long long)dmin + size_d <= INT_MAX);
+    SMX_ARG((const void*)out != (const void*)disp);
+    const size_t n = (size_t)w * h, bytes = n * sizeof(float);
+    DevBuf dG, dD, dS, dO;
+    SMX_HIP(dG.alloc(n));
+    SMX_HIP(dD.alloc(bytes));
+    SMX_HIP(dO.alloc(bytes));
+    if (select) SMX_HIP(dS.alloc(bytes));
+    SMX_HIP(hipMemcpy(dG.p, guide, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(dD.p, disp, bytes, hipMemcpyHostToDevice));
+    if (select) SMX_HIP(hipMemcpy(dS.p, select, bytes, hipMemcpyHostToDevice));
+    int rc = smx_dev_weighted_median(p, dG.as<uint8_t>(), dD.as<float>(), select ? dS.as<float>() : nullptr,
+                                     dO.as<float>(), w, h, dmin, size_d, nullptr);
+    if (rc) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(hipMemcpy(out, dO.p, bytes, hipMemcpyDeviceToHost));
     return SMX_OK;
 }
 

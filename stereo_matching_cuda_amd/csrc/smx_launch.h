@@ -28,4 +28,8 @@ int launch_filter(const smx_params* p, const uint8_t* I, uint8_t* mean, float* v
 bool finish_pair_row_supported(int w);
 int launch_finish_pair_row(const smx_params* p, const int64_t* keys, int w, int h, int dminl, int dminr, int dOcc,
                            float vMin, float* best, float* dmap, float* occlusion, float* filled, hipStream_t st);
+// smx_wmf.hip: weighted median (ws: spatial weights [0 .. 2 r^2], wc: range weights [0 .. 255])
+int wmf_bucket_shift(int size_d);
+int launch_weighted_median(int radius, const uint16_t* ws, const uint16_t* wc, const uint8_t* guide, const float* disp,
+                           const float* select, float* out, int w, int h, int dmin, int size_d, hipStream_t st);
 }  // namespace smx

@@ -24,7 +24,13 @@ class PairPipeline:
     current stream, whatever device is current in the calling thread."""
 
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
-                 slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False):
+                 slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
+                 wmf=None, wmf_params=None):
+        """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
+        the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
+        filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched."""
+        if wmf not in (None, "occluded", "all"):
+            raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
         self.lib = _lib.lib()
         self.w, self.h, self.size_d = int(w), int(h), int(size_d)
         self.n = self.w * self.h
@@ -57,6 +63,10 @@ class PairPipeline:
         self.occlusion = torch.empty((self.h, self.w), **f)
         self.filled = torch.empty((self.h, self.w), **f)
         self.agg = (torch.empty((2, local, self.h, self.w), **f) if want_agg else None)
+        self.wmf = wmf
+        self.wmf_params = (wmf_params if wmf_params is not None else _lib.default_wmf_params()) if wmf else None
+        self.refined = torch.empty((self.h, self.w), **f) if wmf else None
+        self._guide = None            # left image of the last aggregation: the guide of the refinement
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -84,6 +94,7 @@ class PairPipeline:
     def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r):
         """Both views per launch from materialised cost volumes of this rank's slices (smx_dev_aggregate_wta_pair_cost):
         the reference's data flow, read p + write q."""
+        self._guide = gray_l
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
@@ -109,6 +120,7 @@ class PairPipeline:
 
     def aggregate_pair(self, gray_l, gray_r):
         """Both views per kernel launch (smx_dev_aggregate_wta_pair)."""
+        self._guide = gray_l
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
@@ -125,6 +137,8 @@ class PairPipeline:
 
     def aggregate_view(self, view, guide, other, cost=None):
         dmin = self.dminl if view == 0 else self.dminr
+        if view == 0:
+            self._guide = guide
         agg = self.agg[view] if self.agg is not None else None
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
@@ -151,6 +165,19 @@ class PairPipeline:
             _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                              self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                              _dp(self.occlusion), _dp(self.filled), st))
+        if self.wmf:
+            self.refine()
+
+    def refine(self):
+        """The weighted median of the filled left map, guided by the left image the last aggregate() saw, into
+        self.refined (smx_dev_weighted_median; labels dminl .. dminl + size_d - 1)."""
+        if self._guide is None:
+            raise RuntimeError("refine() needs the left image: run an aggregation first")
+        with self._on_device():
+            sel = self.occlusion if self.wmf == "occluded" else None
+            _lib.check(self.lib.smx_dev_weighted_median(C.byref(self.wmf_params), _dp(self._guide), _dp(self.filled),
+                                                        _dp(sel), _dp(self.refined), self.w, self.h, self.dminl,
+                                                        self.size_d, self._stream()))
 
     def finish_per_call(self):
         """The same through the per-stage entry points (the reference's call sequence, seven launches)."""
@@ -186,4 +213,6 @@ class PairPipeline:
              "occlusion": c(self.occlusion), "filled": c(self.filled)}
         if self.agg is not None:
             r["aggl"], r["aggr"] = c(self.agg[0]), c(self.agg[1])
+        if self.wmf:
+            r["refined"] = c(self.refined)
         return r

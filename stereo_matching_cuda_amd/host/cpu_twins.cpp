@@ -14,6 +14,7 @@
 #include "integral.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "wmf.cuh"
 
 using std::vector;
 
@@ -217,4 +218,51 @@ void fill_occlusionOnCPU(float* disparity, const int w, const int h, const float
             r[x] = left > right ? left : right;
         }
     }
+}
+
+// ---- wmf.cuh (not in the reference) ----------------------------------------------------------
+// The weighted median of include/smx.h pixel by pixel: weight tables from the formula in double, one label histogram
+// per window, the smallest label whose cumulative weight reaches half the total.
+void weighted_medianOnCPU(const unsigned char* guide, const float* disparity, const float* select, float* out,
+                          const int w, const int h, int dmin, int size_d, const smx_wmf_params& p) {
+    const int R = p.radius;
+    vector<uint32_t> ws(2 * R * R + 1), wc(256), hist(size_d, 0);
+    for (int k = 0; k <= 2 * R * R; ++k)
+        ws[k] = k == 0 ? 1023 : (uint32_t)std::floor(1023.0 * std::exp(-(double)k / (p.sigma_s * p.sigma_s)) + 0.5);
+    for (int t = 0; t < 256; ++t)
+        wc[t] = t == 0 ? 1023 : (uint32_t)std::floor(1023.0 * std::exp(-(double)t * t / (p.sigma_c * p.sigma_c)) + 0.5);
+    auto label = [&](float v) -> int {          // v - dmin for an integer v in range, else -1 (counts for nothing)
+        if (!(std::fabs(v) < 2147483648.0f)) return -1;
+        const int iv = (int)v;
+        if ((float)iv != v) return -1;
+        const long long k = (long long)iv - dmin;
+        return (k >= 0 && k < size_d) ? (int)k : -1;
+    };
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t i = (size_t)y * w + x;
+            out[i] = disparity[i];
+            if (select) {
+                const float s = select[i];
+                if (!std::isfinite(s) || !(std::trunc((double)s) < (double)dmin)) continue;
+            }
+            uint32_t total = 0;
+            for (int qy = std::max(0, y - R); qy <= std::min(h - 1, y + R); ++qy)
+                for (int qx = std::max(0, x - R); qx <= std::min(w - 1, x + R); ++qx) {
+                    const size_t j = (size_t)qy * w + qx;
+                    const int k = label(disparity[j]);
+                    if (k < 0) continue;
+                    const int t = std::abs((int)guide[i] - (int)guide[j]);
+                    const uint32_t wt = ws[(qx - x) * (qx - x) + (qy - y) * (qy - y)] * wc[t];
+                    hist[k] += wt;
+                    total += wt;
+                }
+            uint32_t cum = 0;
+            bool found = false;
+            for (int k = 0; k < size_d; ++k) {
+                cum += hist[k];
+                hist[k] = 0;
+                if (!found && total && 2 * cum >= total) { out[i] = (float)(dmin + k); found = true; }
+            }
+        }
 }

@@ -18,6 +18,10 @@
 //                     exact path -- kept as a measured point, never a default
 //   --pfm FILE        filled left disparity (positive pixels) as a Middlebury-style PFM
 //   --png16 FILE      filled left disparity as a KITTI-style 16-bit PNG (disparity * 256)
+//   --wmf MODE        weighted-median refinement of the filled left map after the fill (smx_weighted_median, default
+//                     parameters; Hosni et al.'s last step, not in the reference), on every path: MODE `occluded`
+//                     filters the pixels the LR check invalidated, `all` every pixel.  Writes occlu_mapl_wmf.png
+//                     beside the 12 images, and --pfm / --png16 then hold the refined map
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -43,6 +47,7 @@
 #include "png_io.h"
 #include "rgb_to_grayscale.cuh"
 #include "winner_take_all.cuh"
+#include "wmf.cuh"
 
 namespace {
 
@@ -83,6 +88,7 @@ struct Options {
     std::vector<std::string> positional;
     bool fused = false, host_compare = false, fast = false;
     std::string pfm, png16;
+    std::string wmf;         // "" = no refinement, else "occluded" or "all"
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
     bool pipeline = false;
@@ -103,6 +109,13 @@ Options parse(int argc, char** argv) {
         else if (a == "--fast") o.fast = true;
         else if (a == "--pfm") value(o.pfm);
         else if (a == "--png16") value(o.png16);
+        else if (a == "--wmf") {
+            value(o.wmf);
+            if (o.ok && o.wmf != "occluded" && o.wmf != "all") {
+                std::fprintf(stderr, "--wmf needs `occluded` or `all`, not `%s`\n", o.wmf.c_str());
+                o.ok = false;
+            }
+        }
         else if (a == "--ngpu") { std::string v; value(v); o.ngpu = std::atoi(v.c_str()); }
         else if (a == "--pipeline") o.pipeline = true;
         else if (a == "--pairs") { std::string v; value(v); o.pairs = std::atoi(v.c_str()); }
@@ -279,6 +292,14 @@ int main(int argc, char** argv) {
             if (ok) std::cout << "Occlusion ok!" << std::endl;
         }
     }
+    // not in the reference: the weighted-median refinement of the filled left map (guide: the left gray image)
+    std::vector<float> refined;
+    if (!opt.wmf.empty()) {
+        std::cout << "weighted median ..." << std::endl;
+        refined.resize(n);
+        weighted_median(gray[0], filled.data(), opt.wmf == "occluded" ? occlusion.data() : nullptr, refined.data(), w, h,
+                        d_lo, size_d, host_compare);
+    }
     const double duration = (std::clock() - t_begin) / (double)CLOCKS_PER_SEC;
 
     std::cout << "writing images ..." << std::endl;
@@ -299,16 +320,21 @@ int main(int argc, char** argv) {
         const std::vector<unsigned char> img = normalise_like_reference(o.data, (size_t)n);
         if (!smx_png_write((outdir + "/" + o.name).c_str(), w, h, 1, img.data())) ++write_failures;
     }
-    // disparity outputs in dataset conventions: positive pixel offsets of the filled left map
+    if (!refined.empty()) {
+        const std::vector<unsigned char> img = normalise_like_reference(refined.data(), (size_t)n);
+        if (!smx_png_write((outdir + "/occlu_mapl_wmf.png").c_str(), w, h, 1, img.data())) ++write_failures;
+    }
+    // disparity outputs in dataset conventions: positive pixel offsets of the filled left map (the refined one with --wmf)
+    const float* final_map = refined.empty() ? filled.data() : refined.data();
     if (!opt.pfm.empty()) {
         std::vector<float> d(n);
-        for (int i = 0; i < n; ++i) d[i] = -filled[i];
+        for (int i = 0; i < n; ++i) d[i] = -final_map[i];
         if (!smx_pfm_write(opt.pfm.c_str(), w, h, d.data())) ++write_failures;
     }
     if (!opt.png16.empty()) {
         std::vector<unsigned short> d(n);
         for (int i = 0; i < n; ++i) {
-            const float v = -filled[i] * 256.0f;
+            const float v = -final_map[i] * 256.0f;
             d[i] = (unsigned short)(v < 0.0f ? 0.0f : (v > 65535.0f ? 65535.0f : v));
         }
         if (!smx_png_write_gray16(opt.png16.c_str(), w, h, d.data())) ++write_failures;

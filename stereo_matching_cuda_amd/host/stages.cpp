@@ -6,6 +6,7 @@
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "wmf.cuh"
 
 #include <vector>
 
@@ -116,4 +117,17 @@ void fill_occlusion(float* disparity, const int w, const int h, const float vMin
 // filter.cu:117-207: dead code in the reference (never called from main.cu); a standalone device op here.
 void filter(unsigned char* image, int width, int height, unsigned char* mean, float* var, bool) {
     CHECK(smx_filter(&smx_config().params, image, width, height, mean, var));
+}
+
+// not in the reference: the weighted-median refinement behind fill_occlusion (smx_main --wmf), default parameters
+void weighted_median(unsigned char* guide, float* disparity, float* select, float* out, const int w, const int h,
+                     int dmin, int size_d, bool host_gpu_compare) {
+    smx_wmf_params p;
+    smx_default_wmf_params(&p);
+    CHECK(smx_weighted_median(&p, guide, disparity, select, out, w, h, dmin, size_d));
+    if (host_gpu_compare) {
+        std::vector<float> twin((size_t)w * h);
+        weighted_medianOnCPU(guide, disparity, select, twin.data(), w, h, dmin, size_d, p);
+        if (check_errors(twin.data(), out, w * h)) cout << "Weighted median ok!" << endl;
+    }
 }

@@ -126,6 +126,34 @@ def fill_occlusion(disparity, v_min):
     return d
 
 
+def weighted_median(guide, disparity, dmin, size_d, select=None, params=None):
+    """Weighted-median refinement of a disparity map (include/smx.h smx_weighted_median; not a stage of the reference).
+    guide: (h, w) u8 gray of the view the map belongs to; labels [dmin, dmin + size_d); select: None filters every pixel,
+    else the pixels with (int)select < dmin (pass the pair's occlusion map for the LR-invalidated ones).  Returns a new
+    (h, w) float32 array."""
+    g, d = _c(guide, np.uint8), _c(disparity, np.float32)
+    if g.ndim != 2 or d.shape != g.shape:
+        raise ValueError("weighted_median expects an (h, w) uint8 guide and an (h, w) float32 map")
+    s = None if select is None else _c(select, np.float32)
+    if s is not None and s.shape != g.shape:
+        raise ValueError("select must have the map's shape")
+    h, w = g.shape
+    out = np.empty((h, w), np.float32)
+    p = params if params is not None else _lib.default_wmf_params()
+    _lib.check(_lib.lib().smx_weighted_median(C.byref(p), _ptr(g), _ptr(d), _ptr(s), _ptr(out), w, h, int(dmin),
+                                              int(size_d)))
+    return out
+
+
+def wmf_weights(params=None):
+    """(spatial[0 .. 2 r^2], range[0 .. 255]) uint16 weight tables of the weighted median (smx_wmf_weights)."""
+    p = params if params is not None else _lib.default_wmf_params()
+    spatial = np.zeros(2 * max(p.radius, 0) ** 2 + 1, np.uint16)
+    rng = np.zeros(256, np.uint16)
+    _lib.check(_lib.lib().smx_wmf_weights(C.byref(p), _ptr(spatial), _ptr(rng)))
+    return spatial, rng
+
+
 def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, want_agg=False,
                 params=None):
     """main.cu:65-155 on two gray images, device-resident between the stages."""
