@@ -7,7 +7,7 @@
 // each): while one of them sits in a latency-bound phase (the sequential scans) the others fill the SIMDs, which
 // is what the one-workgroup-per-CU predecessor (smx_agg_v3.hip) could not do.  Two LDS rings of RR = 36 rows x 83
 // columns x 2 components hold the integral images of stage 1 (p, I*p) and stage 2 (a, b): a band of box means
-// needs BH + 2R + 1 rows.  (BH = 32 with two workgroups per CU also builds: -DSMX_V4_BH=32, 3 % slower.)
+// needs BH + 2R + 1 rows.  (BH = 32 with two workgroups per CU was 3 % slower.)
 //
 // Exactness: every prefix sum keeps the reference's order (sequential left -> right in a row, then
 // sequential top -> bottom in a column; integral.cu:82-86, 124-128), the box mean its tap order
@@ -64,16 +64,12 @@ constexpr int ROWF = OFF1 + NCOLP;      // 172
 static_assert(NCOLP >= TWMAX && NCOLP % 4 == 0 && OFF1 % 4 == 0 && OFF1 >= NCOLP, "planar ring row");
 constexpr int NT = 512;
 constexpr int NWAVE = NT / 64;
-// Band height: 32 rows (rings of 52 rows, 72 KB of LDS, two workgroups per CU) or 16 rows (rings of 36 rows,
-// 50 KB, three workgroups per CU, fewer idle rows at the bottom of a strip)
-#ifndef SMX_V4_BH
-#define SMX_V4_BH 16
-#endif
-constexpr int BH = SMX_V4_BH;           // band height
+// Band height 16: rings of 36 rows, 50 KB of LDS, three workgroups per CU, fewer idle rows at the bottom of a strip
+// than with 32 (rings of 52 rows, 72 KB, two workgroups per CU)
+constexpr int BH = 16;                  // band height
 constexpr int RPW = BH / NWAVE;         // rows of a band per wave in the LANE = COLUMN phases
 constexpr int RR = BH + 2 * RMAX + 2;   // ring rows: a band of box means needs BH + 2R + 1 rows
-constexpr int WG_PER_CU = BH == 32 ? 2 : 3;
-static_assert(BH == 32 || BH == 16, "band height");
+constexpr int WG_PER_CU = 3;
 static_assert(RR % 4 == 0 && RR % RPW == 0 && BH % RPW == 0 && RPW % 2 == 0,
               "groups of four (column scan) and of RPW (box, cost) consecutive ring rows never wrap");
 
@@ -135,9 +131,6 @@ struct GuidArgs {
 constexpr int GR_NT = 256;
 constexpr int GR_MAXROWS = 8;
 __host__ __device__ inline int gr_wpad(int w) { return ((w + 127) & ~127) + 4; }
-#ifndef SMX_GR_WHATIF
-#define SMX_GR_WHATIF 0     // diagnostic builds (WRONG results): 1 no scan, 2 no S stores, 4 no image planes, 8 no pixel loads
-#endif
 __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int h, int rows) {
     extern __shared__ __attribute__((aligned(16))) float gr_lds[];
     const int tid = threadIdx.x, view = blockIdx.y, y0 = blockIdx.x * rows;
@@ -163,7 +156,6 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
         for (int k = 0; k < 16; ++k) {
             const int e = min(e0 + k * GR_NT + tid, total - 1);
             const int r = e / wr, x = e - r * wr;
-            if (SMX_GR_WHATIF & 8) v[k] = (float)(e & 255); else
             v[k] = 1.0f * (float)(int)Iu[(size_t)min(y0 + r, h - 1) * w + min(x, w - 1)];     // chToFlOnGPU guidedFilter.cu:442-449
         }
 #pragma unroll
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
     // ---- k_v4_prep's part II: the padded (value, x-derivative) rows out of the pixel values in LDS (x_derivativeOnGPU
     // costVolume.cu:358-381: (I[x-1] - I[x+1]) / 2, one-sided at the image edges; integers <= 255: exact whichever way formed).
     // (From global memory, a cell per loop trip, this part cost 5 us: its byte loads were waited for trip by trip.)
-    if (view < ga.nimg && !(SMX_GR_WHATIF & 4)) {
+    if (view < ga.nimg) {
         fg_t* __restrict__ FGo = ga.prep.FG[view];
         const int nr = min(rows, h - y0);
         for (int e = tid; e < nr * wp; e += GR_NT) {
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
     if (view >= ga.nviews) return;          // (an image that is only the other view's partner: no statistics)
     __syncthreads();                        // (the scan below overwrites the pixel values in place)
     // (2) columns behind the image hold copies of the last pixel; their sums are never stored
-    if (tid < 2 * rows && !(SMX_GR_WHATIF & 1)) {
+    if (tid < 2 * rows) {
         float* row = gr_lds + tid * wpad;                     // tid = plane * rows + row
         float acc = -0.0f;                                    // exact additive identity
         f4 c[16], n[16];
@@ -230,7 +222,7 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
     }
     __syncthreads();
     for (int r = 0; r < rows; ++r) {
-        if (y0 + r >= h || (SMX_GR_WHATIF & 2)) break;
+        if (y0 + r >= h) break;
         float* d0 = S0 + (size_t)(y0 + r) * w;
         float* d1 = S1 + (size_t)(y0 + r) * w;
         for (int x = tid; x < w; x += GR_NT) {
@@ -306,62 +298,6 @@ constexpr int QTH = NT - 64 * QW0;                // threads that hold quads
 constexpr int NQR = BH / 16;                      // quads per quad-holding thread: rows r, r + 16, ..
 static_assert(NQ * 4 <= NCOLP && NQ <= 4 * (NWAVE - QW0), "one wave-instruction covers 16 rows x 4 quads");
 
-// Diagnostic build only (-DSMX_V4_STAMPS=<item>): every wave of one work item records the shader clock
-// at its phase boundaries; the product build contains no stamp.
-#ifdef SMX_V4_STAMPS
-constexpr int STAMP_W = 12;             // stamps per iteration
-constexpr int STAMP_SLOTS = STAMP_W * 40;
-__device__ unsigned long long g_stamps[NWAVE * STAMP_SLOTS];
-#define V4_STAMP(n)                                                                          \
-    do {                                                                                     \
-        if (item == SMX_V4_STAMPS && lane == 0 && i * STAMP_W + (n) < STAMP_SLOTS)            \
-            g_stamps[wave * STAMP_SLOTS + i * STAMP_W + (n)] = __builtin_amdgcn_s_memtime();  \
-    } while (0)
-#elif defined(SMX_V4_MARK)
-#define V4_STAMP(n) asm volatile("; V4_MARK " #n)      // (to find the phases in the ISA listing)
-#else
-#define V4_STAMP(n) ((void)0)
-#endif
-// Diagnostic build only (-DSMX_V4_DUMP=<item> -DSMX_V4_DUMP_IT=<iteration> -DSMX_V4_DUMP_PH=<0..3: behind the
-// barrier that ends W / R / C / X>): both LDS rings of one work item at one point -> global memory
-#ifdef SMX_V4_DUMP
-__device__ float g_dump[2 * RR * ROWF];
-#define V4_DUMP(ph)                                                                               \
-    do {                                                                                          \
-        if (item == SMX_V4_DUMP && i == SMX_V4_DUMP_IT && (ph) == SMX_V4_DUMP_PH) {                \
-            for (int e_ = tid; e_ < RR * ROWF; e_ += NT) {                                         \
-                g_dump[e_] = ring1[e_];                                                            \
-                g_dump[RR * ROWF + e_] = ring2[e_];                                                \
-            }                                                                                     \
-            wg_barrier();                                                                         \
-        }                                                                                         \
-    } while (0)
-#else
-#define V4_DUMP(ph) ((void)0)
-#endif
-#ifdef SMX_V4_ITEMLOG
-constexpr int ITEMLOG_MAX = 1 << 16;
-__device__ unsigned long long g_itemlog[3 * ITEMLOG_MAX];
-#endif
-
-// Hand-in hysteresis (experiment, default off): an item that has caught up with its left neighbour meets the slow
-// hand-in -- poll, barrier, exposed cross-XCD load -- in every iteration; with SLACK > 0 it waits once until the
-// neighbour is SLACK records ahead.  Measured on KITTI (1242x375, D=192): SLACK 0 / 2 / 3 / 5 / 8 -> 1.266 / 1.274 /
-// 1.274 / 1.279 / 1.280 ms per pair: the slow hand-in is not what a caught-up item loses time on.
-#ifndef SMX_V4_SLACK
-#define SMX_V4_SLACK 0
-#endif
-constexpr unsigned SLACK = SMX_V4_SLACK;
-// Diagnostic build only (-DSMX_V4_WHATIF=<bits>): leaves parts of the work out (WRONG results) to see what
-// the kernel time is sensitive to.  1: no q stores / guidance loads in X; 2: box taps not read from LDS;
-// 4: no cost evaluation; 8: no column scans; 16: no row scans; 32: no stage-1 cost loads; 64: no box at all;
-// 128: no exact-division check; 256: no division; 512: no stage-1 box; 1024: no stage-2 box; 2048: no hand-off
-// between strips; 4096: the row-scan wave never waits for the neighbour's record
-#ifndef SMX_V4_WHATIF
-#define SMX_V4_WHATIF 0
-#endif
-constexpr int WHATIF = SMX_V4_WHATIF;
-
 // one ds_read_b64 the compiler cannot pair into a ds_read2_b64 (which takes four times the LDS cycles of two
 // ds_read_b64 for the same bytes); the caller waits with lds_wait16() before the first use
 #define LDS_RD64(dst, addr, imm) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
@@ -414,11 +350,11 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
     // row-scan lanes: each 32-lane group (the unit of LDS banking for dword accesses) takes half of the rows
     // with both components, lanes 0-15 / 16-31 = first / second component: 16 distinct even + 16 distinct
     // odd banks (row stride 170 dwords = 10 mod 32)
-    // BH = 32: wave 0 scans stage 1, wave 1 stage 2; BH = 16: wave 0 scans both, lanes 32.. = stage 2
-    auto srow_of = [&]() { const int l = opaque(lane); return BH == 32 ? (l & 15) + 16 * (l >> 5) : (l & 15); };
+    // wave 0 scans both stages, lanes 32.. = stage 2
+    auto srow_of = [&]() { return opaque(lane) & 15; };
     auto scomp_of = [&]() { return (opaque(lane) >> 4) & 1; };
-    auto sstage_of = [&]() { return BH == 32 ? wave : (opaque(lane) >> 5); };
-    constexpr int NRSW = BH == 32 ? 2 : 1;      // row-scan waves
+    auto sstage_of = [&]() { return opaque(lane) >> 5; };
+    constexpr int NRSW = 1;                     // row-scan waves
     // this thread's two stage-1 input quads (waves QW0..): row of the band, first ring column
     // One wave-instruction covers 16 rows x 4 quads: the LDS writes of a 16-lane group then go to 16 different
     // rows (row stride 170 dwords = 10 mod 32: conflict-free), the global loads to 64-byte runs of 16 rows.
@@ -436,12 +372,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         wg_barrier();
         const int item = s_item;
         if (item >= A.nitems) break;
-#ifdef SMX_V4_ITEMLOG
-        if (tid == 0 && item < ITEMLOG_MAX) {
-            g_itemlog[3 * item] = __builtin_amdgcn_s_memrealtime();
-            g_itemlog[3 * item + 2] = blockIdx.x;
-        }
-#endif
         const int k = item / nsv;
         const int sv = item - k * nsv;
         const int view = sv / A.nslices;
@@ -450,7 +380,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         const int xs = k * OW;
         const int cs1 = xs - R - 1;             // image column of ring-1 column 0
         const int cs2 = xs - HW;                // image column of ring-2 column 0
-        const bool pred = k > 0 && !(WHATIF & 2048), succ = k + 1 < K && !(WHATIF & 2048);   // (2048: no hand-off between strips)
+        const bool pred = k > 0, succ = k + 1 < K;
         const int d = V.d0 + slice;
         unsigned* const myflag = A.flags + (size_t)sv * K + k;
         const size_t recs = (size_t)NI * REC_F2;      // float2 per (parity, slice-view)
@@ -652,11 +582,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
             rr = rr >= RR ? rr - RR : rr;
             // the unit holds the carries (p, I p) / (a, b) of rows 2k, 2k+1
             const float c01 = scomp ? hreg.y : hreg.x, c23 = scomp ? hreg.w : hreg.z;
-            float acc = (pred && !(WHATIF & 4096)) ? ((srow & 1) ? c23 : c01) : -0.0f;   // (4096: wave 0 never waits for the record)
-#ifdef SMX_V4_STAMPS
-            asm volatile("" : "+v"(acc));
-            V4_STAMP(11);
-#endif
+            float acc = pred ? ((srow & 1) ? c23 : c01) : -0.0f;
             float* row = (st == 0 ? ring1 : ring2) + rr * ROWF + scomp * OFF1;   // column c of this component: row[c]
             float* const co = (float*)&cout[st][srow] + scomp;
             // NG groups of four columns from group G0, unrolled; the reads run two groups ahead of the adds.
@@ -844,7 +770,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         auto box2_fast = [&](const float* ring, int obf, int half, f2* m) {
             const int ob0 = obf + 2 * half * ROWF;
             f2 s11[2], s10[2], s01[2], s00[2], val[2];
-            if (RT == RMAX && !(WHATIF & 2)) {
+            if (RT == RMAX) {
                 static_assert(HWMAX + OFF1 < 256, "ds_read2_b32 offsets");
                 // top tap rows: HW ring rows above, each wrapped on its own
                 int ot0 = ob0 - HW * ROWF;
@@ -869,12 +795,8 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                     ot = ot < 0 ? ot + RR * ROWF : ot;
                     const float* pb = ring + ob0 + t * ROWF + lane;
                     const float* pt = ring + ot + lane;
-                    if (WHATIF & 2) {
-                        s11[t] = s10[t] = s01[t] = s00[t] = (f2){(float)(ob0 + lane), 2.0f + ot};
-                    } else {
-                        s11[t] = cell(pb + HW); s10[t] = cell(pb);
-                        s01[t] = cell(pt + HW); s00[t] = cell(pt);
-                    }
+                    s11[t] = cell(pb + HW); s10[t] = cell(pb);
+                    s01[t] = cell(pt + HW); s00[t] = cell(pt);
                 }
             }
             // (the two rows' dependent chains interleaved: a packed instruction that reads the result of the one in
@@ -883,20 +805,16 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
             v0 = v0 - s01[0]; v1 = v1 - s01[1];
             v0 = v0 + s00[0]; v1 = v1 + s00[1];
             val[0] = v0; val[1] = v1;
-            if (WHATIF & 256) {
-                m[0] = v0; m[1] = v1;
-            } else {
-                const f2 d2 = {area_full, area_full}, r2 = {ra_full, ra_full};
-                f2 q0 = v0 * r2, q1 = v1 * r2;
-                f2 e0 = __builtin_elementwise_fma(-q0, d2, v0), e1 = __builtin_elementwise_fma(-q1, d2, v1);
-                m[0] = __builtin_elementwise_fma(e0, r2, q0);
-                m[1] = __builtin_elementwise_fma(e1, r2, q1);
-            }
+            const f2 d2 = {area_full, area_full}, r2 = {ra_full, ra_full};
+            f2 q0 = v0 * r2, q1 = v1 * r2;
+            f2 e0 = __builtin_elementwise_fma(-q0, d2, v0), e1 = __builtin_elementwise_fma(-q1, d2, v1);
+            m[0] = __builtin_elementwise_fma(e0, r2, q0);
+            m[1] = __builtin_elementwise_fma(e1, r2, q1);
             // smallest / largest magnitude of the four sums: v_min3 + v_min, v_max3 + v_max
             const float amin = fminf(fminf(fminf(fabsf(val[0].x), fabsf(val[0].y)), fabsf(val[1].x)), fabsf(val[1].y));
             const float amax = fmaxf(fmaxf(fmaxf(fabsf(val[0].x), fabsf(val[0].y)), fabsf(val[1].x)), fabsf(val[1].y));
             // tiny, zero, infinite window sums (a NaN sum gives a NaN mean on either path)
-            if (!(WHATIF & 128) && __any(!(amin >= 0x1p-100f) || !(amax < __builtin_inff()))) {
+            if (__any(!(amin >= 0x1p-100f) || !(amax < __builtin_inff()))) {
                 asm volatile("; exact-division slow path");   // keep this a real (rare) wave-uniform branch
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -951,7 +869,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         bool qok[RPW];
         // (interior: every row exists and every lane's column is its own -- no predicate, no clamp)
         auto store_q = [&](int iq, bool interior) {
-            if (WHATIF & 1) return;
             const unsigned vq = vq_of();
             const int yq0 = BH * (iq - 1) - 2 * R + RPW * wave;
             unsigned vo[RPW];
@@ -974,7 +891,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         issue_cost(0);
         issue_guid(0);
         if (pred) {
-            if (tid == 0) spin_pred(1u + SLACK);
+            if (tid == 0) spin_pred(1u);
             wg_barrier();
             seen = s_seen;
         }
@@ -987,7 +904,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         int ob1 = RPW * wave * ROWF, ob2 = ob1;
         for (int i = 0; i < NI; ++i) {
             // ------------------------------------ W(i) --------------------------------------------------
-            V4_STAMP(0);
             {
                 if (q_on) {
 #pragma unroll
@@ -1016,7 +932,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                 }
                 if (pred && !have_pref) {
                     // the neighbour had not published record i when this item looked: wait for it now
-                    if (tid == 0) spin_pred((unsigned)i + 1u + SLACK);
+                    if (tid == 0) spin_pred((unsigned)i + 1u);
                     wg_barrier();
                     seen = s_seen;
                     fetch_rec(i);
@@ -1029,17 +945,14 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                     ((float*)&cin_fast[st][srow])[scomp] = (srow & 1) ? c23 : c01;
                 }
             }
-            if (!(WHATIF & 32)) issue_cost(i + 1);      // lands under the row scans (rows clamped: harmless behind the last iteration)
-            V4_STAMP(1);
+            issue_cost(i + 1);      // lands under the row scans (rows clamped: harmless behind the last iteration)
             wg_barrier();
-            V4_STAMP(2);
-            V4_DUMP(0);
             // ------------------------------------ R(i) --------------------------------------------------
             // the scans are dependent chains on the critical path of the iteration: let them win the issue
             // arbitration against the waves (of this and the other workgroup) that share their SIMDs
             if (!FAST && wave < NRSW) {
                 __builtin_amdgcn_s_setprio(3);
-                if (!(WHATIF & 16)) rowscans(i, rb, rbp);
+                rowscans(i, rb, rbp);
                 __builtin_amdgcn_s_setprio(0);
             } else {
                 if (wave == NWAVE - 1 && lane == 0) {
@@ -1049,7 +962,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                     if (i == NI - 1)
                         s_next = (int)__hip_atomic_fetch_add((gu32*)A.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                if (!(WHATIF & 4)) eval_cost();
+                eval_cost();
                 // the left neighbour's last 2R+1 columns of the stage-2 integral of band i-1 -> ring 2 (nobody
                 // touches these columns before X(i))
                 if (pred && hu_halo && i >= 1 && hu_in) {
@@ -1068,47 +981,24 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                 drain_vmem();
             }
             if (FAST) rowscans_fast(i, rb, rbp);
-            V4_STAMP(3);
             wg_barrier();
-            V4_STAMP(4);
-            V4_DUMP(1);
             // ------------------------------------ C(i) --------------------------------------------------
             if (succ && tid == NT - 1 && i >= 1) flag_store(myflag, (unsigned)i);
             // one dword (column, component) of a ring row per lane, lane-linear along the row
             if (wave < 3) {
                 __builtin_amdgcn_s_setprio(3);
                 const int cidx1 = 64 * wave + opaque(lane);                      // stage 1: every dword of a row
-                if (cidx1 < ROWF && !(WHATIF & 8)) colscan(ring1, cidx1, rb, BH * i, Sc);
+                if (cidx1 < ROWF) colscan(ring1, cidx1, rb, BH * i, Sc);
                 __builtin_amdgcn_s_setprio(0);
             } else if (wave < 5) {
                 __builtin_amdgcn_s_setprio(3);
                 const int cidx2 = OFF1 * (wave - 3) + HW + opaque(lane);         // stage 2: the new columns of either plane
-                if (i >= 1 && !(WHATIF & 8)) colscan(ring2, cidx2, rbp, BH * (i - 1) - R, Sc);
+                if (i >= 1) colscan(ring2, cidx2, rbp, BH * (i - 1) - R, Sc);
                 __builtin_amdgcn_s_setprio(0);
             }
-            V4_STAMP(5);
             wg_barrier();
-            V4_STAMP(6);
-            V4_DUMP(2);
             // ------------------------------------ X(i) --------------------------------------------------
             seen = s_seen;
-            V4_STAMP(8);
-#ifdef SMX_V4_EXTRA_SALU
-            {   // sensitivity experiment: SMX_V4_EXTRA_SALU dependent scalar adds per wave and iteration
-                int dummy = i;
-#pragma unroll
-                for (int z = 0; z < SMX_V4_EXTRA_SALU; ++z) asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy));
-                asm volatile("" :: "s"(dummy));
-            }
-#endif
-#ifdef SMX_V4_EXTRA_VALU
-            {
-                int dummy = lane;
-#pragma unroll
-                for (int z = 0; z < SMX_V4_EXTRA_VALU; ++z) asm volatile("v_add_u32 %0, %0, 1" : "+v"(dummy));
-                asm volatile("" :: "v"(dummy));
-            }
-#endif
             // Order of the phase: everything that consumes a value loaded in the previous iteration comes before
             // the first global access of this one.  (The compiler cannot count loads across the loop edge: the
             // first such use behind a new access waits for ALL outstanding accesses, the new one included.)
@@ -1127,10 +1017,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                 const int ya0 = BH * i - R + RPW * wave;
                 f2 m[RPW];
                 bool ok[RPW];
-                if (WHATIF & (64 | 512)) {
-#pragma unroll
-                    for (int t = 0; t < RPW; ++t) m[t] = (f2){1.0f + lane, 2.0f};
-                } else if ((unsigned)(i - f1_lo) < f1_n) {
+                if ((unsigned)(i - f1_lo) < f1_n) {
                     box4_fast(ring1, ob1, m);
                 } else {
                     box4_gen(ring1, 0, mkgeo(xs + opaque(lane), cs1), xint1, ya0, m, ok);
@@ -1144,7 +1031,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                     abreg[t] = (f2){ak, bk};
                 }
             }
-            V4_STAMP(9);
             const int yq0 = BH * (i - 1) - 2 * R + RPW * wave;
 #pragma unroll
             for (int t = 0; t < RPW; ++t) { qout[t] = 0.0f; qok[t] = false; }
@@ -1152,10 +1038,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
             if (i >= 1) {
                 // box means of stage 2 -> q rows [BH (i-1) - 2R, BH i - 2R)
                 f2 m[RPW];
-                if (WHATIF & (64 | 1024)) {
-#pragma unroll
-                    for (int t = 0; t < RPW; ++t) m[t] = (f2){1.0f + lane, 2.0f};
-                } else if (fast2) {
+                if (fast2) {
                     box4_fast(ring2, ob2, m);
 #pragma unroll
                     for (int t = 0; t < RPW; ++t) qok[t] = true;
@@ -1169,10 +1052,9 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                     qout[t] = tq + m[t].y;
                 }
             }
-            V4_STAMP(10);
             __builtin_amdgcn_sched_barrier(0);
             // ---- the global accesses of the phase: q rows, record i, the loads of iteration i+1 ----
-            if (i >= 1) store_q(i, fast2 && !(WHATIF & (64 | 1024)));
+            if (i >= 1) store_q(i, fast2);
             if (succ && (hu_halo || hu_carry)) {
                 // record i: row carries of this iteration's row scans, last 2R+1 columns of the stage-2 integral
                 f4 hov;
@@ -1186,8 +1068,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
                 st16_sc1(r_out, (unsigned)((i * REC_F2) * 8) + rec_voff, hov);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!(WHATIF & 1)) issue_guid(i + 1);      // (rows are clamped into the image: harmless behind the last iteration)
-            V4_STAMP(7);
+            issue_guid(i + 1);      // (rows are clamped into the image: harmless behind the last iteration)
             wg_barrier();
             rbp = rb;
             rb += BH;
@@ -1203,9 +1084,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
             if (succ) flag_store(myflag, FLAG_DONE);
             s_item = s_next;
         }
-#ifdef SMX_V4_ITEMLOG
-        if (tid == 0 && item < ITEMLOG_MAX) g_itemlog[3 * item + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
     }
 }
 
@@ -1340,10 +1218,7 @@ static int launch_walk4(const v4::Args& a, hipStream_t st) {
     int dev = 0, ncu = 256;
     SMX_HIP(hipGetDevice(&dev));
     SMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    int per_cu = v4::WG_PER_CU;                          // persistent: WG_PER_CU workgroups per CU
-    static const int env_per_cu = env_int_once("SMX_V4_WG_PER_CU", 0);   // experiments: fewer workgroups per CU
-    if (env_per_cu >= 1 && env_per_cu <= v4::WG_PER_CU) per_cu = env_per_cu;
-    const int slots = per_cu * ncu;
+    const int slots = v4::WG_PER_CU * ncu;               // persistent: WG_PER_CU workgroups per CU
     const int grid = a.nitems < slots ? a.nitems : slots;
     if (a.R == v4::RMAX)
         hipLaunchKernelGGL((v4::k_v4_walk<SRC, v4::RMAX, FAST>), dim3((unsigned)grid), dim3(v4::NT), 0, st, a);
@@ -1352,28 +1227,6 @@ static int launch_walk4(const v4::Args& a, hipStream_t st) {
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }
-
-#ifdef SMX_V4_ITEMLOG
-extern "C" __attribute__((visibility("default"))) int smx_debug_read_itemlog(unsigned long long* out, int n) {
-    const int m = 3 * v4::ITEMLOG_MAX;
-    SMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(v4::g_itemlog), sizeof(unsigned long long) * (n < m ? n : m)));
-    return SMX_OK;
-}
-#endif
-#ifdef SMX_V4_DUMP
-extern "C" __attribute__((visibility("default"))) int smx_debug_read_dump(float* out, int n) {
-    const int m = 2 * v4::RR * v4::ROWF;
-    SMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(v4::g_dump), sizeof(float) * (n < m ? n : m)));
-    return m;
-}
-#endif
-#ifdef SMX_V4_STAMPS
-extern "C" __attribute__((visibility("default"))) int smx_debug_read_stamps(unsigned long long* out, int n) {
-    const int m = v4::NWAVE * v4::STAMP_SLOTS;
-    SMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(v4::g_stamps), sizeof(unsigned long long) * (n < m ? n : m)));
-    return m;
-}
-#endif
 
 // status words of the last fused aggregation that used this workspace: [0] != 0: a hand-off wait timed out;
 // [1] != 0: the comb walker met cost values outside its exactness argument and the queued ring walker redid the chunk
@@ -1617,8 +1470,7 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
                 b.d0[v] = a.v[vv].d0;
             }
             b.w = w; b.h = h; b.K = L.K; b.NI = L.NI;
-            static const int env_no_overlap = env_int_once("SMX_V5_NO_OVERLAP", 0);     // (A/B runs: a period of the whole item)
-            b.P = env_no_overlap ? ((v5::bands(h) + 3) & ~1) : v5::period(h, L.K);
+            b.P = v5::period(h, L.K);
             b.nslices = a.nslices; b.nsv = a.nsv; b.nitems = a.nitems;
             b.hand = (float*)hand; b.flags = a.flags; b.ticket = a.ticket; b.status = a.status;
             b.src_cost = use_cost ? 1 : 0;
@@ -1634,20 +1486,15 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
             }
             b.fast = fast ? 1 : 0;
             {
-                // Role priorities (smx_agg_v5.hip PRIO_*).  Measured in rounds 4 and 5 (tools/prio_ab*.sh, profiles/r05_prio_*):
-                // they are worth 2-7 % on every launch whose aggregated planes stay within a few GB -- KITTI geometry up to
-                // 1 500 slices (5.7 GB of q), Motorcycle / 4K geometry with few slices, every aspect ratio at KITTI's volume --
-                // and cost 0.4-4.8 % on 4K (34 GB of q per launch); Motorcycle (15 GB) came out at -3.8 %, +3.0 % and -1.7 % on
-                // three boxes.  The counters of the losing case (profiles/r05_prio_pmc_motorcycle.txt): identical instruction
-                // counts, vector-memory operations 32 % longer in flight, 30 % more cycles in s_waitcnt.  What in a large q
-                // footprint does that is not established (address translation of 512 workgroups streaming into planes 27-33 MB
-                // apart is the suspect); the rule is therefore stated in the variable the effect follows: the q bytes of the
-                // launch.  SMX_V5_PRIO=0/1 (read once per process) overrides it for A/B runs.
+                // Role priorities (smx_agg_v5.hip PRIO_*) only while the launch's q planes stay below 6 GB.  Measured in rounds 4
+                // and 5 (profiles/r05_prio_*): worth 2-7 % on KITTI geometry up to 1 500 slices (5.7 GB of q), on Motorcycle / 4K
+                // geometry with few slices and on every aspect ratio at KITTI's volume; 0.4-4.8 % slower on 4K (34 GB of q per
+                // launch), and -3.8 %, +3.0 % and -1.7 % on Motorcycle (15 GB) on three boxes.  The losing case has identical
+                // instruction counts but vector-memory operations 32 % longer in flight (profiles/r05_prio_pmc_motorcycle.txt);
+                // its cause is not established, so the rule follows the variable the effect follows: the q bytes of the launch.
                 constexpr double PRIO_MAX_Q_BYTES = 6e9;
                 const double q_bytes = (double)a.nsv * (double)qplane * 4.0;
                 b.prio = q_bytes < PRIO_MAX_Q_BYTES ? 1 : 0;
-                static const int env_prio = env_int_once("SMX_V5_PRIO", -1);     // (A/B runs)
-                if (env_prio >= 0) b.prio = env_prio != 0;
             }
             b.qperm = own_q ? 1 : 0;
             b.q_plane = qplane;

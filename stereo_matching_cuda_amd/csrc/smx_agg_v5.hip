@@ -51,6 +51,7 @@
 
 #include "smx_agg_dev.h"
 #include "smx_agg_v5.h"
+#include "smx_v5_diag.h"
 
 namespace smx {
 namespace v5 {
@@ -83,78 +84,12 @@ static_assert(P1 % 64 == 0 && P1 >= SW && RS >= P1 + SW && RS % 4 == 0, "tile ro
 constexpr int NHU = BH * 10, NCU = BH / 2;
 static_assert(REC_U == NHU + NCU, "record layout");
 
-// Diagnostic build only (-DSMX_V5_STAMPS=<item>): every wave of one work item records the shader clock at the
-// start and end of its work in the W, R and X phases (the gaps are barrier waits); the product build has no stamp.
-#ifdef SMX_V5_STAMPS
-constexpr int STAMP_W = 12;     // 0..5: slot phases; 6..10: after each of the five row pairs (comb waves) / quarters of the scan / cost batches
-constexpr int STAMP_SLOTS = STAMP_W * 48;
-// (the stamps are those of ONE workgroup -- SMX_V5_STAMPS mod 512 -- over 48 global slots from STAMP_G0: its items overlap)
-#ifndef SMX_V5_STAMP_G0
-#define SMX_V5_STAMP_G0 30
-#endif
-constexpr int STAMP_G0 = SMX_V5_STAMP_G0;
-__device__ unsigned long long g_stamps[10 * STAMP_SLOTS];
-#define V5_STAMP(n)                                                                          \
-    do {                                                                                     \
-        if ((int)blockIdx.x == SMX_V5_STAMPS % 512 && lane == 0 && i >= STAMP_G0 && (i - STAMP_G0) * STAMP_W + (n) < STAMP_SLOTS) \
-            g_stamps[wave * STAMP_SLOTS + (i - STAMP_G0) * STAMP_W + (n)] = __builtin_amdgcn_s_memtime();  \
-    } while (0)
-#else
-#define V5_STAMP(n) ((void)0)
-#endif
-// Diagnostic build only (-DSMX_V5_WHATIF=<bits>): leaves parts of the work out (WRONG results) to see what the
-// kernel time is sensitive to.  1: no row scans; 2: no cost evaluation; 4: no stage-1 comb rows; 8: no stage-2 comb
-// rows; 16: no q stores; 32: no guidance loads; 64: no hand-off (every strip like strip 0); 128: no input loads;
-// 256: row scans without their LDS writes; 512: row scans without the adds; 1024: row scans at normal priority;
-// 2048: no record / flag stores (every strip like the last); 4096: no hand-in (every strip like the first); 8192: the stage-1
-// waves do not wait for the stage-2 copy-out
-#ifndef SMX_V5_WHATIF
-#define SMX_V5_WHATIF 0
-#endif
-constexpr int WHATIF = SMX_V5_WHATIF;
-// Diagnostic build only (-DSMX_V5_MARK): comments in the ISA around the interior-path regions tools/isa_budget.py counts
-#ifdef SMX_V5_MARK
-#define V5_MARK(name) asm volatile("; MARK " name)
-#else
-#define V5_MARK(name) ((void)0)
-#endif
-#ifndef SMX_V5_WMAP
-#define SMX_V5_WMAP 0
-#endif
-constexpr int WMAP = SMX_V5_WMAP;
 // Wave priorities of the roles while they work (the row-scan wave runs at 3, the stage-2 waves' copy-out too): a slot ends
 // with its slowest wave, and the stage-2 comb waves have a quarter of a slot to spare -- measured: cost 2 / stage 1 1 /
 // stage 2 0 is 4 % faster than all 0 on KITTI shape and 1-2 % on shapes up to 4 Mpix x 128 disparities, but 3-4 % SLOWER on
 // Motorcycle and 4K, where no priority at all is best (Args::prio: the host switches the whole set by the size of the launch)
-#ifndef SMX_V5_PRIO_COST
-#define SMX_V5_PRIO_COST 2
-#endif
-#ifndef SMX_V5_PRIO_S1
-#define SMX_V5_PRIO_S1 1
-#endif
-#ifndef SMX_V5_PRIO_S2HEAD
-#define SMX_V5_PRIO_S2HEAD 3
-#endif
-#ifndef SMX_V5_PRIO_SCAN
-#define SMX_V5_PRIO_SCAN 3
-#endif
-#ifndef SMX_V5_S2_KEEP
-#define SMX_V5_S2_KEEP 12
-#endif
-#ifndef SMX_V5_TOUCH
-#define SMX_V5_TOUCH 0      // (A/B: load-to-LDS touches of the next band's cost lines: slower, 0.84 against 0.78 ms per KITTI pair)
-#endif
-constexpr int S2_KEEP = SMX_V5_S2_KEEP;     // vector-memory operations a stage-2 wave issues behind its record store in an interior slot (ten q rows + two loads; five less with row-pair stores)
-constexpr int PRIO_COST = SMX_V5_PRIO_COST, PRIO_S1 = SMX_V5_PRIO_S1, PRIO_S2HEAD = SMX_V5_PRIO_S2HEAD, PRIO_SCAN = SMX_V5_PRIO_SCAN;
-
-#if (SMX_V5_WHATIF & 16384)
-__device__ uint64_t g_masksink[1 << 16];
-#endif
-#ifdef SMX_V5_DUMP
-// Diagnostic build only: tile 1 (current buffer), tile 2 and the comb registers of one item behind the barrier that
-// ends phase SMX_V5_DUMP_PH (0 W, 1 R, 2 X) of iteration SMX_V5_DUMP_IT
-__device__ float g_dump[2 * TILE_F + NT * 48];
-#endif
+constexpr int PRIO_COST = 2, PRIO_S1 = 1, PRIO_S2HEAD = 3, PRIO_SCAN = 3;
+constexpr int S2_KEEP = 12;     // vector-memory operations a stage-2 wave issues behind its record store in an interior slot (ten q rows + two loads; five less with row-pair stores)
 
 // ---- DPP left taps fused into the arithmetic: lane i reads lane i-1 (`wave_shr:1`: the combs of nine lanes are not whole DPP
 // rows, so there is no zero fill in front of a comb).  (The compiler keeps a separate v_mov_b32_dpp per tap; the fused forms
@@ -244,14 +179,11 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
     __shared__ unsigned s_peekn;                                    // the NEXT item's predecessor flag as peeked at in the last slot of the front item
     __shared__ unsigned s_seen;                                     // last value read from the left neighbour's flag
     __shared__ unsigned s_peek[2];                                  // the flag as peeked at during slot sl -> [(sl + 1) & 1], read by every wave at the top of slot sl + 1
-    __shared__ unsigned touch_sink[64];                             // where the cost wave's prefetch touches of a cost volume land (never read)
     __shared__ unsigned s_x1;                                       // stage-2 waves that have taken their rows out of tile 2 (counts up through an item)
 
     const int lane = threadIdx.x & 63;
-    const int hwave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // role of a hardware wave (waves w and w + 4 of a workgroup share a SIMD)
-    const int wave = WMAP == 1 ? (int)((0x75436210u >> (4 * hwave)) & 7u) : WMAP == 2 ? (int)((0x54317620u >> (4 * hwave)) & 7u)
-                     : WMAP == 3 ? (int)((0x53764210u >> (4 * hwave)) & 7u) : WMAP == 4 ? (int)((0x57436210u >> (4 * hwave)) & 7u) : hwave;
+    // the hardware wave, which fixes its role (waves w and w + 4 of a workgroup share a SIMD)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tid = 64 * wave + lane;
     const int w = A.w, h = A.h, K = A.K, NI = A.NI, nsv = A.nsv;
     const CostConst cc = A.cc;
@@ -277,10 +209,7 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
     constexpr int NQROW = SW / 4;                                   // quads per tile row (76 / 57)
     constexpr int NCT = 64;                                         // cost threads: the cost wave
     constexpr int NRB = 4;                                          // rounds whose loads are in flight together
-#ifndef SMX_V5_NRBC
-#define SMX_V5_NRBC 4
-#endif
-    constexpr int NRBC = SMX_V5_NRBC;                               // ... with materialised cost volumes (their quads come from HBM)
+    constexpr int NRBC = 4;                                         // ... with materialised cost volumes (their quads come from HBM)
     static_assert(2 * NRBC >= (BH * (SW / 4) + 63) / 64, "two batches");
     constexpr int NCT2 = 0;
     constexpr int NQT = BH * NQROW;                                 // quads per band
@@ -320,13 +249,6 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         unsigned* myflag = A.flags;
         int o_fg1 = 0, o_fg2 = 0, o_g1p = 0, o_i2p = 0, o_i2b = 0, o_in = 0, o_out = 0;
         rsrc_t r_q = r_fix;
-#if (SMX_V5_WHATIF & 16384)
-        // (what-if 16384: the cost of a pairwise pre-reduction of q in stage 2 -- odd slices load the q rows of the slice before,
-        // select, store the minimum and a ballot; results wrong by construction)
-        [[maybe_unused]] float qo[(ST2 && (WHATIF & 16384)) ? BH : 1];
-        [[maybe_unused]] rsrc_t r_qp = r_fix;
-        [[maybe_unused]] bool pairB = false;
-#endif
         // q rows: comb-ordered scratch (row y of this strip at (k h + y) * OWS) or the caller's [h][w]
         int q_pitch = 0, q_row0 = 0;
         auto decode = [&](int it) {
@@ -337,7 +259,7 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             slice = sv - view * A.nslices;
             base1 = OWS * k - 1;
             base2 = OWS * k - R - 1;
-            pred = k > 0 && !(WHATIF & (64 | 4096)); succ = k + 1 < K && !(WHATIF & (64 | 2048));
+            pred = k > 0; succ = k + 1 < K;
             d = A.d0[view] + slice;
             myflag = A.flags + (size_t)sv * K + k;
             o_fg1 = (int)A.o_fg[view]; o_fg2 = (int)A.o_fg[view ^ 1];
@@ -349,10 +271,6 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             o_in = (int)((((unsigned)(k - 1) & 1u) * (unsigned)nsv + (unsigned)sv) * recb);
             o_out = (int)((((unsigned)k & 1u) * (unsigned)nsv + (unsigned)sv) * recb);
             r_q = mk_rsrc(A.q[view] + (size_t)slice * A.q_plane, A.q_plane * 4);
-#if (SMX_V5_WHATIF & 16384)
-            pairB = (slice & 1) != 0;
-            r_qp = mk_rsrc(A.q[view] + (size_t)(slice > 0 ? slice - 1 : 0) * A.q_plane, A.q_plane * 4);
-#endif
             // (qperm: q_pitch is the pitch of a row PAIR, the rows of a pair lie side by side -- smx_agg_v5.h)
             q_pitch = QPERM ? OWS * 8 : (int)w4; q_row0 = QPERM ? k * ((h + 1) / 2) * (OWS * 8) : 0;
             xedge = base1 < 0 || base1 + SW > w;
@@ -535,22 +453,8 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         // materialised cost volumes: the cost quads of a band come from HBM (the image planes from L2), and they are consumed in the
         // slot they are issued in -- their latency sat on the cost wave's path twice per slot (0.78 ms per KITTI pair against 0.63
         // from the images).  Holding a band of them in registers across the slot spills (28 more live registers: 0.96 ms).
-        // Instead the cost wave TOUCHES the next band's lines a slot ahead -- one dword per 128 bytes of its ten row segments,
-        // 70 lanes of two load-to-LDS instructions, no register, nothing waits for them -- so that the real loads hit in L2.
-        auto cw_touch_p = [&](int ib) {
-            if constexpr (ROLE == ROLE_COST) {
-                constexpr int SEGS = (SW * 4 + 124 + 127) / 128;            // 128-byte lines a row segment of SW costs can touch (7)
-                static_assert(BH * SEGS <= 128, "two touch instructions per band");
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int l = min(opaque(lane) + 64 * half, BH * SEGS - 1);
-                    const int row = l / SEGS, seg = l - row * SEGS;
-                    const int y = min(BH * ib + row, h - 1);
-                    const int off = min(max((y * w + base1) * 4 + seg * 128, 0), (int)plane4 - 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_c, (__attribute__((address_space(3))) void*)touch_sink, 4, off, 0, 0, 0);
-                }
-            }
-        };
+        // Touching the next band's lines a slot ahead with load-to-LDS instructions, so that the real loads hit in L2, was
+        // slower as well: 0.84 against 0.78 ms per KITTI pair.
         auto cw_finish = [&](int ib, float* dst, auto R0c, auto EDGEc, auto SRCc) {
             constexpr bool EDGE = decltype(EDGEc)::value, SRCC = decltype(SRCc)::value;
             constexpr int NB = SRCC ? NRBC : NRB;
@@ -620,7 +524,6 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             // cost evaluation)
             const bool edge = xedge || BH * ib + BH > h;
             if (A.src_cost) {
-                if (SMX_V5_TOUCH) cw_touch_p(ib + 1);
                 if (edge) run(std::true_type{}, std::true_type{}); else run(std::false_type{}, std::true_type{});
             } else if (edge) run(std::true_type{}, std::false_type{});
             else { V5_MARK("cost begin"); run(std::false_type{}, std::false_type{}); V5_MARK("cost end"); }
@@ -635,24 +538,18 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         // of living in a register through the rows.  (bit_cast of the whole vector: taking .y/.z/.w of the builtin's result
         // through a u4 copy let the compiler narrow the load to ONE dword -- wrong results, found by bisection)
         auto g1_load = [&](int P, auto Sc) {
-            if constexpr (ROLE == ROLE_S1 && !(WHATIF & 32)) {
+            if constexpr (ROLE == ROLE_S1) {
                 const int Pc = __builtin_amdgcn_readfirstlane(min(max(P, 0), 5 * NI - 1));
                 const unsigned vgl = (unsigned)(64 * wave + opaque(lane)) * 16u;
                 gr[decltype(Sc)::value] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r_fix, (int)vgl, o_g1p + Pc * (CLP * 16), 0));
             }
         };
         auto issue_guid = [&](int ib, int yq0) {
-            if (WHATIF & 32) return;
             const int ibc = __builtin_amdgcn_readfirstlane(min(max(ib, 0), NI - 1));
             if constexpr (ST2) {
                 // (yq0 = 10 (ib - 1) - 18 at every call site: the band grid of the planes)
-#ifdef SMX_V5_GI_B32     // (A/B: five 4-byte loads straight into their registers instead of a 16-byte load that needs an aligned quad)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) gI[c] = ldu(r_fix, vg * 4u, o_i2p + ibc * (CLP * 16) + 4 * c);
-#else
                 const u4 a = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(r_fix, (int)(vg * 4u), o_i2p + ibc * (CLP * 16), 0));
                 gI[0] = a.x; gI[1] = a.y; gI[2] = a.z; gI[3] = a.w;
-#endif
                 gI[4] = ldu(r_fix, vg, o_i2b + ibc * (CLP * 4));
             }
         };
@@ -696,10 +593,9 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             float acc = (sc_st == 0 && pred1) ? cinp[sc_row][sc_comp] : -0.0f;
             f4* const r4 = (f4*)row;
             constexpr int NG = SW / 4;
-#ifndef SMX_V5_SCAN_PF
-#define SMX_V5_SCAN_PF 4        // (round 5 A/B on KITTI shape: 4 -> 0.816 ms per pair, 8 -> 0.823, 12 -> 0.819)
-#endif
-            constexpr int PF = SMX_V5_SCAN_PF;          // groups of reads in flight ahead of the dependent adds
+            // groups of reads in flight ahead of the dependent adds (round 5 A/B on KITTI shape: 4 -> 0.816 ms per pair,
+            // 8 -> 0.823, 12 -> 0.819)
+            constexpr int PF = 4;
             f4 v[PF];
 #pragma unroll
             for (int g = 0; g < PF; ++g) v[g] = r4[g];
@@ -712,19 +608,13 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                 const f4 in = v[g % PF];
                 if (g + PF < NG) v[g % PF] = r4[g + PF];
                 f4& x = xo[g & 1];
-                if ((WHATIF & 512) && g >= 5) { x = in; } else {
                 acc = in.x + acc; x.x = acc;
                 acc = in.y + acc; x.y = acc;
                 acc = in.z + acc; x.z = acc;
                 if (g == 4 && keep) acc = in.z;            // column 18 = the halo's last: the carry
                 acc = in.w + acc; x.w = acc;
-                }
                 if (g < 5 && keep) { x.x = in.x; x.y = in.y; x.z = in.z; if (g < 4) x.w = in.w; }
-#ifdef SMX_V5_SCAN_W64
-                if (!((WHATIF & 256) && g >= 5)) { ((f2*)row)[2 * g] = (f2){x.x, x.y}; ((f2*)row)[2 * g + 1] = (f2){x.z, x.w}; }
-#else
-                if (!((WHATIF & 256) && g >= 5)) r4[g] = x; else asm volatile("" :: "v"(x));
-#endif
+                r4[g] = x;
                 asm volatile("" :: "v"(xo[(g & 1) ^ 1]));
             }
         };
@@ -751,7 +641,6 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         // of it (they do that first thing in the slot and count up s_x1); waited for right in front of the first a/b store
         unsigned x1_need = 0;
         auto wait_x1 = [&]() {
-            if (WHATIF & 8192) return;
             for (unsigned spins = 0; __hip_atomic_load(&s_x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < x1_need; ++spins) {
                 __builtin_amdgcn_s_sleep(1);
                 if (spins > (1u << 24)) { flag_store(A.status, 1u + (unsigned)item); break; }   // (cannot happen: every wave reaches its increment)
@@ -888,30 +777,13 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             const float tqb = mb.x * (float)ip.y;
             float qva = tqa + ma.y;
             float qvb = tqb + mb.y;
-#if (SMX_V5_WHATIF & 16384)
-            if constexpr (ST2) {
-                if (pairB) {
-                    const float oa = qo[T0], ob = qo[T0 + 1];
-                    const bool sa = qva == qva && !(oa < qva), sb = qvb == qvb && !(ob < qvb);
-                    const uint64_t ba = __builtin_amdgcn_ballot_w64(sa), bb = __builtin_amdgcn_ballot_w64(sb);
-                    qva = sa ? qva : oa;
-                    qvb = sb ? qvb : ob;
-                    if (lane == 0) {
-                        g_masksink[((blockIdx.x * 8 + wave) * 64 + (yq & 31)) & 0xffff] = ba;
-                        g_masksink[((blockIdx.x * 8 + wave) * 64 + 32 + (yq & 31)) & 0xffff] = bb;
-                    }
-                }
-            }
-#endif
-            if (!(WHATIF & 16)) {
-                if constexpr (QPERM) {
-                    // own scratch: the two rows of the pair as ONE 8-byte store (yq is even; a row behind an image of odd height
-                    // lands in the padding row of the last pair)
-                    if (va) __builtin_amdgcn_raw_buffer_store_b64((u2){__builtin_bit_cast(unsigned, qva), __builtin_bit_cast(unsigned, qvb)}, r_q, (int)vo, q_row0 + (yq >> 1) * q_pitch, AUX_NT);
-                } else {
-                    if (va) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, qva), r_q, (int)vo, q_row0 + yq * q_pitch, AUX_NT);
-                    if (vb) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, qvb), r_q, (int)vo, q_row0 + (yq + 1) * q_pitch, AUX_NT);
-                }
+            if constexpr (QPERM) {
+                // own scratch: the two rows of the pair as ONE 8-byte store (yq is even; a row behind an image of odd height
+                // lands in the padding row of the last pair)
+                if (va) __builtin_amdgcn_raw_buffer_store_b64((u2){__builtin_bit_cast(unsigned, qva), __builtin_bit_cast(unsigned, qvb)}, r_q, (int)vo, q_row0 + (yq >> 1) * q_pitch, AUX_NT);
+            } else {
+                if (va) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, qva), r_q, (int)vo, q_row0 + yq * q_pitch, AUX_NT);
+                if (vb) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, qvb), r_q, (int)vo, q_row0 + (yq + 1) * q_pitch, AUX_NT);
             }
             if constexpr (BORDER) rcb = rcn;
             __builtin_amdgcn_sched_barrier(0);
@@ -990,17 +862,14 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                     if (A.prio) __builtin_amdgcn_s_setprio(PRIO_S1);
                     x1_need = (unsigned)NS1 * (unsigned)(g + 1);
                     const bool border = BH * sl - R < R + 1 || BH * sl - R + BH - 1 > h - 1 - R;
-                    if (WHATIF & 4) wait_x1();                  // (the rows wait in front of their first store)
                     V5_STAMP(4);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(WHATIF & 4)) {
 #define V5_P1(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::false_type{}, std::false_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
 #define V5_P1E(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, std::false_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
 #define V5_P1B(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, std::true_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
                     if (border) { rcb = rcp_pair(BH * sl - R); V5_P1B(0) V5_STAMP(6); V5_P1B(2) V5_STAMP(7); V5_P1B(4) V5_STAMP(8); V5_P1B(6) V5_STAMP(9); V5_P1B(8) V5_STAMP(10); }
                     else if (xedge || k == 0) { V5_P1E(0) V5_P1E(2) V5_P1E(4) V5_P1E(6) V5_P1E(8) }
                     else { V5_MARK("s1rows begin"); V5_P1(0) V5_STAMP(6); V5_P1(2) V5_STAMP(7); V5_P1(4) V5_STAMP(8); V5_P1(6) V5_STAMP(9); V5_P1(8) V5_STAMP(10); V5_MARK("s1rows end"); }
-                    }
 #undef V5_P1
 #undef V5_P1E
 #undef V5_P1B
@@ -1052,44 +921,26 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                 __builtin_amdgcn_s_setprio(0);
                 V5_STAMP(3);
                 V5_STAMP(4);
-                [[maybe_unused]] bool s2_interior = false;
+                bool s2_interior = false;
                 if (sl >= 2) {
                     const int yq0 = BH * (sl - 2) - 2 * R;
                     const bool border = yq0 < R + 1 || yq0 + BH - 1 > h - 1 - R;
-                    s2_interior = !border && !(WHATIF & (8 | 16 | 32)) && sl != q_last;
-#if (SMX_V5_WHATIF & 16384)
-                    if constexpr (ST2) {
-                        if (pairB) {
-#pragma unroll
-                            for (int t = 0; t < BH; ++t)
-                            {
-                                const int yc = min(max(yq0 + t, 0), h - 1);
-                                qo[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_qp, (int)vo, q_row0 + (QPERM ? (yc >> 1) * q_pitch + (yc & 1) * 4 : yc * q_pitch), AUX_NT));
-                            }
-                        }
-                    }
-#endif
+                    s2_interior = !border && sl != q_last;
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(WHATIF & 8)) {
 #define V5_P2(TT) rows2_pair(std::integral_constant<int, BH * PAR + TT>{}, std::false_type{}, sl);
 #define V5_P2B(TT) rows2_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, sl);
                     if (border) { rcb = rcp_pair(yq0); V5_P2B(0) V5_STAMP(6); V5_P2B(2) V5_STAMP(7); V5_P2B(4) V5_STAMP(8); V5_P2B(6) V5_STAMP(9); V5_P2B(8) V5_STAMP(10); }
                     else { V5_MARK("s2rows begin"); V5_P2(0) V5_STAMP(6); V5_P2(2) V5_STAMP(7); V5_P2(4) V5_STAMP(8); V5_P2(6) V5_STAMP(9); V5_P2(8) V5_STAMP(10); V5_MARK("s2rows end"); }
-                    }
 #undef V5_P2
 #undef V5_P2B
                 }
                 issue_guid(sl, BH * (sl - 1) - 2 * R);
                 // the record stored above is complete in memory before the barrier behind which it is published
                 // (vector-memory operations of a wave complete in issue order: what was issued behind the record store -- the
-                // q stores of an interior band, ten rows or five row pairs, and the two guidance loads -- may stay in flight;
-                // -DSMX_V5_S2_KEEP=0: the full drain of round 4; the item's last slot drains everything: FLAG_DONE follows)
-#ifdef SMX_V5_GI_B32
-                constexpr int KEEP = S2_KEEP > 0 ? (QPERM ? S2_KEEP - BH / 2 : S2_KEEP) + 3 : 0;
-#else
-                constexpr int KEEP = S2_KEEP > 0 ? (QPERM ? S2_KEEP - BH / 2 : S2_KEEP) : 0;
-#endif
-                if (KEEP > 0 && s2_interior) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(KEEP) : "memory"); else
+                // q stores of an interior band, ten rows or five row pairs, and the two guidance loads -- may stay in flight,
+                // where round 4 drained everything; the item's last slot drains everything: FLAG_DONE follows)
+                constexpr int KEEP = QPERM ? S2_KEEP - BH / 2 : S2_KEEP;
+                if (s2_interior) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(KEEP) : "memory"); else
                 drain_vmem();
             }
         };
@@ -1108,7 +959,7 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                 const int it = s_queue[nf & 3];
                 ending = it >= A.nitems;
                 if (ending && nf == 0) return true;     // (a workgroup without any ticket)
-                f_pred = !ending && it / nsv > 0 && !(WHATIF & (64 | 4096));
+                f_pred = !ending && it / nsv > 0;
                 // every wave must come to the same `seen` (the wait below has a barrier in it): what the cost wave peeked at in
                 // the slot before, for THIS item
                 seen = nf > 0 ? s_peekn : 0u;
@@ -1150,15 +1001,13 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             }
             // ---- the slot's work ----------------------------------------------------------------------------------------
             if constexpr (ROLE == ROLE_SCAN) {
-                if (!(WHATIF & 1024) && A.prio) __builtin_amdgcn_s_setprio(PRIO_SCAN);
+                if (A.prio) __builtin_amdgcn_s_setprio(PRIO_SCAN);
                 V5_MARK("scan begin");
-                if (!(WHATIF & 1)) {
-                    const int i1 = own && slf + 1 < NI ? slf + 1 : -1;
-                    // (front slot -2: the back item's last a/b band with rows inside the image can still be waiting, P == s1_last + 3;
-                    // it is the band in front of this global slot's like any other)
-                    const int i2 = slf == -2 ? (b_own ? P - 3 : -1) : (own ? slf - 1 : -1);
-                    rowscans(i1, i2, G1[1], G2[1], GC[0], pred, slf == -2 ? b_pred : pred);
-                }
+                const int i1 = own && slf + 1 < NI ? slf + 1 : -1;
+                // (front slot -2: the back item's last a/b band with rows inside the image can still be waiting, P == s1_last + 3;
+                // it is the band in front of this global slot's like any other)
+                const int i2 = slf == -2 ? (b_own ? P - 3 : -1) : (own ? slf - 1 : -1);
+                rowscans(i1, i2, G1[1], G2[1], GC[0], pred, slf == -2 ? b_pred : pred);
                 V5_MARK("scan end");
                 __builtin_amdgcn_s_setprio(0);
             } else if constexpr (ROLE == ROLE_COST) {
@@ -1180,13 +1029,13 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                         unsigned pn = 0u;
                         if (nxt < A.nitems) {
                             const int kn = nxt / nsv, svn = nxt - kn * nsv;
-                            if (kn > 0 && !(WHATIF & (64 | 4096))) pn = flag_load(A.flags + (size_t)svn * K + kn - 1);
+                            if (kn > 0) pn = flag_load(A.flags + (size_t)svn * K + kn - 1);
                         }
                         s_peekn = pn;
                     }
                 }
                 if (A.prio) __builtin_amdgcn_s_setprio(PRIO_COST);
-                if (own && !(WHATIF & 2) && slf + 2 < NI) eval_band_p(slf + 2, G1[2]);
+                if (own && slf + 2 < NI) eval_band_p(slf + 2, G1[2]);
                 __builtin_amdgcn_s_setprio(0);
             } else if constexpr (ROLE == ROLE_S1) {
                 if (own) slot_s1(PARc, slf);
@@ -1459,10 +1308,7 @@ int v5_launch(const v5::Args& a, hipStream_t st) {
     int dev = 0, ncu = 256;
     SMX_HIP(hipGetDevice(&dev));
     SMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    int per_cu = v5::WG_PER_CU;                          // persistent: WG_PER_CU workgroups per CU
-    static const int env_per_cu = env_int_once("SMX_V5_WG_PER_CU", 0);   // experiments: fewer workgroups per CU
-    if (env_per_cu >= 1 && env_per_cu <= v5::WG_PER_CU) per_cu = env_per_cu;
-    const int slots = per_cu * ncu;
+    const int slots = v5::WG_PER_CU * ncu;               // persistent: WG_PER_CU workgroups per CU
     const int grid = a.nitems < slots ? a.nitems : slots;
     if (a.fast && a.qperm) hipLaunchKernelGGL((v5::k_v5_walk<1, 1>), dim3((unsigned)grid), dim3(v5::NT), 0, st, a);
     else if (a.fast) hipLaunchKernelGGL((v5::k_v5_walk<1, 0>), dim3((unsigned)grid), dim3(v5::NT), 0, st, a);
@@ -1483,20 +1329,5 @@ extern "C" __attribute__((visibility("default"))) int smx_debug_v5_occupancy(int
     if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
     return SMX_OK;
 }
-
-#ifdef SMX_V5_STAMPS
-extern "C" __attribute__((visibility("default"))) int smx_debug_read_stamps5(unsigned long long* out, int n) {
-    const int m = 10 * v5::STAMP_SLOTS;
-    SMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(v5::g_stamps), sizeof(unsigned long long) * (n < m ? n : m)));
-    return m;
-}
-#endif
-#ifdef SMX_V5_DUMP
-extern "C" __attribute__((visibility("default"))) int smx_debug_read_dump5(float* out, int n) {
-    const int m = 2 * v5::TILE_F + v5::NT * 48;
-    SMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(v5::g_dump), sizeof(float) * (n < m ? n : m)));
-    return m;
-}
-#endif
 
 }  // namespace smx

@@ -39,14 +39,11 @@ struct StageTimer {
     }
 };
 static thread_local StageTimer g_timer;
-#ifndef SMX_DEFAULT_AGG_PATH
-#define SMX_DEFAULT_AGG_PATH 0
-#endif
 // Aggregation path of the calling thread's smx_dev_* / host-pointer calls (smx_set_agg_path); a persistent
 // context carries its own (smx_ctx_set_agg_path).  0 auto, 1 multi-kernel, 2 fused (walker chosen by the call),
 // 3 fused with the ring walker (smx_agg_v4.hip), 4 fused FAST (not bit-exact), 5 fused with the comb walker
 // (smx_agg_v5.hip; an error where it does not apply)
-static thread_local int g_agg_path = SMX_DEFAULT_AGG_PATH;
+static thread_local int g_agg_path = 0;
 static thread_local int g_last_path = 0;
 static thread_local int g_max_chunk = 0;     // smx_set_max_slices_per_launch
 static thread_local int g_keys_fresh = 0;    // smx_set_keys_fresh

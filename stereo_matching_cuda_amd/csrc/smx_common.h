@@ -65,12 +65,6 @@ struct LdsLimitOnce {
         return err[i];
     }
 };
-// developer overrides from the environment, read once per process (never per call)
-inline int env_int_once(const char* name, int absent) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : absent;
-}
-
 // Stage boundary of the calling thread's timed call (smx_set_timing(1) / smx_stage_times): records a HIP event of the
 // CURRENT device on `st`; a no-op when timing is off.  Stage ids: smx_capi.hip.
 enum StageId { ST_BEGIN = 0, ST_UPLOAD, ST_GUIDANCE, ST_WALK, ST_WTA, ST_FINISH, ST_DOWNLOAD, ST_COUNT };
