@@ -150,6 +150,13 @@ int smx_ctx_stereo_pair_async(smx_ctx* ctx, const uint8_t* gray_l, const uint8_t
 int smx_ctx_wait(smx_ctx* ctx, smx_pair_out* staged, const smx_pair_out* copy_to);
 /* Aggregation path of this context (ids as for smx_set_agg_path below). */
 int smx_ctx_set_agg_path(smx_ctx* ctx, int path);
+/* Sub-pixel disparity of this context (smx_dev_subpixel_pair below): mode 0 off (the default), SMX_SUBPIX_PARABOLA or
+ * SMX_SUBPIX_EQUIANGULAR.  The state and map buffers are allocated on first use.  While it is on, smx_ctx_stereo_pair
+ * aggregates through the _nbr passes and computes the maps, and smx_ctx_stereo_pair_async returns SMX_E_ARG.
+ * smx_ctx_subpixel_maps copies the maps of the last synchronous smx_ctx_stereo_pair of the context (n floats each; any
+ * pointer may be NULL); SMX_E_ARG if that pair ran without sub-pixel.  No other output changes. */
+int smx_ctx_set_subpixel(smx_ctx* ctx, int mode);
+int smx_ctx_subpixel_maps(smx_ctx* ctx, float* sub_l, float* sub_r, float* sub_filled);
 
 /* ------------------------------------------------------------------------------------
  * Device-pointer API (async on `stream`, no allocation inside)
@@ -213,6 +220,42 @@ int smx_dev_aggregate_wta_pair_cost(const smx_params* p, const uint8_t* d_left, 
                                     const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr,
                                     int s_begin, int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg,
                                     void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Sub-pixel refinement (not a stage of the reference; opt-in).  The _nbr forms of the aggregation calls also keep, per
+ * pixel, the aggregated costs of the running winner's neighbouring slices, in a state d_nbr of three f32 planes per view
+ * [3][h][w]: 0 lo = the cost of the slice just before the winner, 1 hi = the cost of the slice just after it, 2 last = the
+ * cost of the last slice the view has aggregated.  Keys and winners are those of the plain calls, bit for bit.
+ *   - d_nbr is IN/OUT like d_keys: 3*n floats (smx_dev_aggregate_wta_nbr) or 6*n, left view first
+ *     (smx_dev_aggregate_wta_pair_nbr); it needs no initialisation -- a pixel whose key is the identity (fresh keys,
+ *     smx_dev_init_keys) starts without state.
+ *   - Calls on one set of keys must cover ascending, contiguous slice ranges.  A neighbour outside the slices aggregated
+ *     so far is unknown (NaN): hi of a winner at the last slice so far, lo of a winner at the first slice of the first call.
+ *     A pixel whose key stays the identity has lo = hi = NaN.
+ *   - smx_dev_aggregate_wta_pair_nbr takes d_cost_l / d_cost_r both NULL (the _pair convention) or both set (_pair_cost).
+ *   - Both honour smx_set_max_slices_per_launch and smx_set_keys_fresh like the plain calls; the workspace is the same.
+ * The state is per volume: it does not combine across D-shards. */
+int smx_dev_aggregate_wta_nbr(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
+                              const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
+                              int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
+                              size_t workspace_bytes, float* d_nbr, void* stream);
+int smx_dev_aggregate_wta_pair_nbr(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
+                                   const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr,
+                                   int s_begin, int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg,
+                                   void* d_workspace, size_t workspace_bytes, float* d_nbr, void* stream);
+
+#define SMX_SUBPIX_PARABOLA 1    /* delta = (a - b) / (2 (a + b)) */
+#define SMX_SUBPIX_EQUIANGULAR 2 /* delta = (a - b) / (2 max(a, b)) */
+/* The sub-pixel maps of a pair behind smx_dev_finish_pair, both views in one launch (no allocation: graph-capturable).
+ * Per pixel of view v: c0 = the cost of its key, a = lo - c0, b = hi - c0 (f32), delta as above, and delta = 0 where the
+ * key is the identity, lo or hi is NaN, or the result is not finite; d_sub[v*n + i] = d_dmap[v*n + i] + delta.  By the
+ * tie rule (the last slice of equal costs wins) a >= 0 and b > 0, so |delta| <= 0.5.
+ *   d_keys 2n, d_nbr 6n (the _pair_nbr state), d_dmap 2n (the finish's label maps), d_sub 2n floats out (not d_dmap).
+ *   d_sub_filled: NULL, or n floats out for the left view: d_sub where the LR check kept the pixel, d_filled where it did
+ *   not -- fill_occlusion's test, (int)d_occlusion[i] < dminl.  d_occlusion / d_filled may be NULL without it. */
+int smx_dev_subpixel_pair(int mode, const int64_t* d_keys, const float* d_nbr, const float* d_dmap, const float* d_occlusion,
+                          const float* d_filled, int w, int h, int dminl, float* d_sub, float* d_sub_filled, void* stream);
+/* delta for one pixel, on the host (no GPU): the formula of smx_dev_subpixel_pair, bit for bit; 0 for a bad mode */
+float smx_subpixel_delta(int mode, float c0, float lo, float hi);
 
 /* Synchronous health check of the last smx_dev_aggregate_wta[_pair] call that used d_workspace:
  * copies the call's status word back (call it after synchronising the launch stream).  SMX_E_HIP if

@@ -114,7 +114,17 @@ SIGNATURES = {
     "smx_wmf_weights": (_i, [_WP, _vp, _vp]),
     "smx_weighted_median": (_i, [_WP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_dev_weighted_median": (_i, [_WP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "smx_dev_aggregate_wta_nbr": (_i, [_PP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "smx_dev_aggregate_wta_pair_nbr": (_i, [_PP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
+                                           _vp]),
+    "smx_dev_subpixel_pair": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "smx_subpixel_delta": (_f, [_i, _f, _f, _f]),
+    "smx_ctx_set_subpixel": (_i, [_vp, _i]),
+    "smx_ctx_subpixel_maps": (_i, [_vp, _vp, _vp, _vp]),
 }
+
+# smx.h SMX_SUBPIX_*: the sub-pixel fits by name
+SUBPIX_MODES = {"parabola": 1, "equiangular": 2}
 
 _lib = None
 
@@ -174,3 +184,11 @@ def default_wmf_params():
     p = WmfParams()
     lib().smx_default_wmf_params(C.byref(p))
     return p
+
+
+def subpixel_delta(mode, c0, lo, hi):
+    """The sub-pixel offset of a winner of cost c0 with neighbours lo, hi (smx_subpixel_delta: the formula of the GPU
+    kernel, on the host).  mode: "parabola" or "equiangular"."""
+    if mode not in SUBPIX_MODES:
+        raise ValueError(f"subpixel mode must be 'parabola' or 'equiangular', not {mode!r}")
+    return lib().smx_subpixel_delta(SUBPIX_MODES[mode], c0, lo, hi)

@@ -1153,6 +1153,35 @@ __global__ __launch_bounds__(256) void k_v4_wta2(WtaArgs wa, size_t n, int count
     keys[id + 1] = c < k1 ? c : k1;
 }
 
+// k_v4_wta that also keeps the winner's neighbouring q in the views' state planes nbr [3][n] (smx_common.h WtaRunNbr,
+// nbr_merge).  Same gate and fresh rule.  grid (ceil(n/256), nviews)
+__global__ __launch_bounds__(256) void k_v4_wta_nbr(WtaArgs wa, float* nbr0, float* nbr1, size_t n, int count, int slice0) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= n || wta_gate_closed(wa.gate, wa.gate_nonzero)) return;
+    const float* __restrict__ q = wa.q[blockIdx.y] + id;
+    int64_t* keys = wa.keys[blockIdx.y];
+    float* const nbr = (blockIdx.y ? nbr1 : nbr0) + id;
+    const int64_t key = wa.fresh ? KEY_IDENTITY : keys[id];
+    const bool ld = key != KEY_IDENTITY;                // (no winner yet: the state is not read)
+    float lo = ld ? nbr[0] : 0.0f, hi = ld ? nbr[n] : 0.0f, last = ld ? nbr[2 * n] : 0.0f;
+    WtaRunNbr r(nbr_prev0(key, last));
+    const float q0 = __builtin_nontemporal_load(&q[0]);
+    r.step(q0, (uint32_t)slice0);
+    int z = 1;
+    for (; z + 8 <= count; z += 8) {
+        float v[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[t] = __builtin_nontemporal_load(&q[(size_t)(z + t) * n]);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) r.step(v[t], (uint32_t)(slice0 + z + t));
+    }
+    for (; z < count; ++z) r.step(__builtin_nontemporal_load(&q[(size_t)z * n]), (uint32_t)(slice0 + z));
+    keys[id] = nbr_merge(r, key, (uint32_t)slice0, q0, &lo, &hi, &last);
+    nbr[0] = lo;
+    nbr[n] = hi;
+    nbr[2 * n] = last;
+}
+
 }  // namespace v4
 
 // =============================================================================================
@@ -1286,7 +1315,7 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
                  const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
                  const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
                  uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                 hipStream_t st, const AggOpts& opt, AggInfo* info) {
+                 hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr) {
     const int R = p->radius;
     const bool fast = opt.fast;
     V4Layout L = v4_layout(w, h, R);
@@ -1522,17 +1551,25 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
         // queued fall-back exactly one of the two runs, so both may take the flag)
         const bool fresh = opt.keys_fresh && s0 == s_begin;
         wa.fresh = fresh ? 1 : 0;
+        // (d_nbr: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge)
+        float* const nbr1 = d_nbr ? d_nbr[nviews - 1] : nullptr;
         if (use_v5 && own_q) {
-            if ((rc = v5_wta_launch(nviews, wa.q, wa.keys, w, h, cnt, s0, fallback4 ? status + 1 : nullptr, fresh, st))) return rc;
+            if (d_nbr) rc = v5_wta_nbr_launch(nviews, wa.q, wa.keys, d_nbr, w, h, cnt, s0, fallback4 ? status + 1 : nullptr, fresh, st);
+            else rc = v5_wta_launch(nviews, wa.q, wa.keys, w, h, cnt, s0, fallback4 ? status + 1 : nullptr, fresh, st);
+            if (rc) return rc;
             if (fallback4) {
                 // ... and the WTA over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
                 wa.gate = status + 1; wa.gate_nonzero = 1;
-                if (al8) hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)L.plane, 512), nviews), dim3(256), 0, st, wa, L.plane, cnt, s0);
+                if (d_nbr) hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, d_nbr[0], nbr1, L.plane, cnt, s0);
+                else if (al8) hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)L.plane, 512), nviews), dim3(256), 0, st, wa, L.plane, cnt, s0);
                 else hipLaunchKernelGGL(v4::k_v4_wta, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, L.plane, cnt, s0);
                 SMX_HIP(hipGetLastError());
                 ++nl;
             }
-        } else if (al8)
+        } else if (d_nbr)
+            hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, d_nbr[0], nbr1,
+                               L.plane, cnt, s0);
+        else if (al8)
             hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)L.plane, 512), nviews), dim3(256), 0, st, wa,
                                L.plane, cnt, s0);
         else

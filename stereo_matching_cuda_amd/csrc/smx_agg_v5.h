@@ -98,5 +98,8 @@ int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, a
 // (skip_if != NULL: a device word; the pass does nothing when it is nonzero)
 int v5_wta_launch(int nviews, const float* const* q, int64_t* const* keys, int w, int h, int count, int slice0,
                   const unsigned* skip_if, bool fresh, hipStream_t st);
+// the same that also keeps the winners' neighbours in the views' state planes nbr [3][h][w] (smx_common.h nbr_merge)
+int v5_wta_nbr_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, int w, int h, int count,
+                      int slice0, const unsigned* skip_if, bool fresh, hipStream_t st);
 
 }  // namespace smx

@@ -56,7 +56,7 @@ int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
                  const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
                  const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
                  uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                 hipStream_t st, const AggOpts& opt, AggInfo* info);
+                 hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr);
 size_t v5_fix_bytes(int w, int h, int nviews);
 int v4_read_status(const void* d_ws, unsigned* out, int nwords);
 void v4_geometry(int* ow, int* bh);
@@ -70,7 +70,7 @@ static int aggregate_fused(int path, const smx_params* p, int nviews, const uint
                            const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
                            const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
                            uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                           hipStream_t st, int* launches) {
+                           hipStream_t st, int* launches, float* const* d_nbr = nullptr) {
     if (g_keys_fresh && s_end <= s_begin) {
         // nothing to aggregate: the promise "the call presets the keys" still holds
         for (int v = 0; v < nviews; ++v) { int rk = launch_init_keys(d_keys[v], (int64_t)w * h, st); if (rk) return rk; }
@@ -82,7 +82,7 @@ static int aggregate_fused(int path, const smx_params* p, int nviews, const uint
     opt.max_chunk = g_max_chunk;
     AggInfo info;
     int rc = aggregate_v4(p, nviews, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys, d_mean_u8,
-                          d_agg, d_ws, ws_bytes, st, opt, &info);
+                          d_agg, d_ws, ws_bytes, st, opt, &info, d_nbr);
     if (rc) return rc;
     g_last_info = info;
     if (launches) *launches = info.launches;
@@ -137,7 +137,7 @@ void smx_default_params(smx_params* p) {
 
 const char* smx_last_error(void) { return g_err.c_str(); }
 
-const char* smx_version(void) { return "smx-hip gfx950 0.10 (weighted-median refinement of the filled map: smx_weighted_median; comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker; WTA winner in the float domain; guidance in three launches; two 512-thread workgroups per CU)"; }
+const char* smx_version(void) { return "smx-hip gfx950 0.11 (sub-pixel disparity from the winner's neighbouring costs: smx_dev_subpixel_pair; weighted-median refinement of the filled map: smx_weighted_median; comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker; WTA winner in the float domain; guidance in three launches; two 512-thread workgroups per CU)"; }
 
 int smx_device_count(void) {
     int n = 0;
@@ -394,24 +394,25 @@ int smx_dev_finish_pair(const smx_params* p, const int64_t* d_keys, int w, int h
     return rc;
 }
 
-int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
-                          const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
-                          int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
-                          size_t workspace_bytes, void* stream) {
+// smx_dev_aggregate_wta and, with d_nbr != NULL (the view's state planes, smx_common.h nbr_merge), its _nbr form
+static int aggregate_wta_one(const char* who, const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
+                             const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
+                             int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
+                             size_t workspace_bytes, float* d_nbr, void* stream) {
     SMX_ARG(p && d_guide && d_keys && d_workspace);
     SMX_ARG(d_cost || d_other);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
-    { int rcd = check_same_device(d_workspace, "smx_dev_aggregate_wta"); if (rcd) return rcd; }
+    { int rcd = check_same_device(d_workspace, who); if (rcd) return rcd; }
     hipStream_t st = (hipStream_t)stream;
     stage_mark(ST_BEGIN, st);
     // fused path (agg_path_for); cost built on the fly or read from d_cost
     const char* why = nullptr;
     const int path = agg_path_for(p, w, h, 1, d_cost != nullptr, g_agg_path, &why);
-    if (!path) return fail(SMX_E_ARG, "smx_dev_aggregate_wta: fused path %d forced but %s", g_agg_path, why);
+    if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", who, g_agg_path, why);
     if (path != 1) {
         g_launches = 0;
         int rc2 = aggregate_fused(path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
-                               &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches);
+                               &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches, d_nbr ? &d_nbr : nullptr);
         if (rc2) return rc2;
         return SMX_OK;
     }
@@ -428,7 +429,7 @@ int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uin
         base += WS_ALIGN;
     }
     if (workspace_bytes < WS_ALIGN || avail < pb * 10)
-        return fail(SMX_E_WS, "smx_dev_aggregate_wta: workspace %zu B < %zu B needed for one slice",
+        return fail(SMX_E_WS, "%s: workspace %zu B < %zu B needed for one slice", who,
                     workspace_bytes, smx_agg_workspace_bytes(w, h, 1));
     const int per_slice = d_cost ? 4 : 5;
     const int total = s_end - s_begin;
@@ -472,17 +473,36 @@ int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uin
         if ((rc = launch_ab(p, T0, T1, mean_im, cinv, A, B, w, h, cnt, st))) return rc;
         if ((rc = launch_integral(2, A, B, A, B, w, h, cnt, st))) return rc;
         float* agg = d_agg ? d_agg + (int64_t)(s0 - s_begin) * n : nullptr;
-        if ((rc = launch_q_wta(p, A, B, im, d_keys, agg, w, h, cnt, s0, st))) return rc;
+        if (d_nbr) rc = launch_q_wta_nbr(p, A, B, im, d_keys, d_nbr, agg, w, h, cnt, s0, st);
+        else rc = launch_q_wta(p, A, B, im, d_keys, agg, w, h, cnt, s0, st);
+        if (rc) return rc;
         g_launches += 6;
         stage_mark(ST_WALK, st);      // (this path folds the WTA into its last pass)
     }
     return SMX_OK;
 }
 
+int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
+                          const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
+                          int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
+                          size_t workspace_bytes, void* stream) {
+    return aggregate_wta_one("smx_dev_aggregate_wta", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
+                             d_mean_u8, d_agg, d_workspace, workspace_bytes, nullptr, stream);
+}
+
+int smx_dev_aggregate_wta_nbr(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
+                              const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
+                              int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
+                              size_t workspace_bytes, float* d_nbr, void* stream) {
+    SMX_ARG(d_nbr);
+    return aggregate_wta_one("smx_dev_aggregate_wta_nbr", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
+                             d_mean_u8, d_agg, d_workspace, workspace_bytes, d_nbr, stream);
+}
+
 static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
                           const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin,
                           int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
-                          size_t workspace_bytes, void* stream) {
+                          size_t workspace_bytes, void* stream, float* d_nbr = nullptr) {
     SMX_ARG(p && d_left && d_right && d_keys && d_workspace);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
     SMX_ARG((d_cost_l != nullptr) == (d_cost_r != nullptr));
@@ -502,19 +522,21 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
         int64_t* keys[2] = {d_keys, d_keys + n};
         uint8_t* mean[2] = {d_mean_u8, d_mean_u8 ? d_mean_u8 + n : nullptr};
         float* agg[2] = {d_agg, d_agg ? d_agg + vol : nullptr};
+        float* nbr[2] = {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr};
         g_launches = 0;
         int rc2 = aggregate_fused(path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
                                d_mean_u8 ? mean : nullptr, d_agg ? agg : nullptr, d_workspace,
-                               workspace_bytes, st, &g_launches);
+                               workspace_bytes, st, &g_launches, d_nbr ? nbr : nullptr);
         if (rc2) return rc2;
         return SMX_OK;
     }
-    int rc = smx_dev_aggregate_wta(p, d_left, d_right, d_cost_l, w, h, dminl, s_begin, s_end, d_keys,
-                                   d_mean_u8, d_agg, d_workspace, workspace_bytes, stream);
+    const char* one = d_nbr ? who : "smx_dev_aggregate_wta";
+    int rc = aggregate_wta_one(one, p, d_left, d_right, d_cost_l, w, h, dminl, s_begin, s_end, d_keys,
+                               d_mean_u8, d_agg, d_workspace, workspace_bytes, d_nbr, stream);
     if (rc) return rc;
-    return smx_dev_aggregate_wta(p, d_right, d_left, d_cost_r, w, h, dminr, s_begin, s_end, d_keys + n,
-                                 d_mean_u8 ? d_mean_u8 + n : nullptr, d_agg ? d_agg + vol : nullptr,
-                                 d_workspace, workspace_bytes, stream);
+    return aggregate_wta_one(one, p, d_right, d_left, d_cost_r, w, h, dminr, s_begin, s_end, d_keys + n,
+                             d_mean_u8 ? d_mean_u8 + n : nullptr, d_agg ? d_agg + vol : nullptr,
+                             d_workspace, workspace_bytes, d_nbr ? d_nbr + 3 * n : nullptr, stream);
 }
 
 int smx_dev_aggregate_wta_pair(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
@@ -532,6 +554,31 @@ int smx_dev_aggregate_wta_pair_cost(const smx_params* p, const uint8_t* d_left, 
     SMX_ARG(d_cost_l && d_cost_r);
     return aggregate_pair("smx_dev_aggregate_wta_pair_cost", p, d_left, d_right, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin,
                           s_end, d_keys, d_mean_u8, d_agg, d_workspace, workspace_bytes, stream);
+}
+
+int smx_dev_aggregate_wta_pair_nbr(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
+                                   const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr,
+                                   int s_begin, int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg,
+                                   void* d_workspace, size_t workspace_bytes, float* d_nbr, void* stream) {
+    SMX_ARG(d_nbr);
+    return aggregate_pair("smx_dev_aggregate_wta_pair_nbr", p, d_left, d_right, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin,
+                          s_end, d_keys, d_mean_u8, d_agg, d_workspace, workspace_bytes, stream, d_nbr);
+}
+
+static bool subpix_mode_ok(int mode) { return mode == SMX_SUBPIX_PARABOLA || mode == SMX_SUBPIX_EQUIANGULAR; }
+
+int smx_dev_subpixel_pair(int mode, const int64_t* d_keys, const float* d_nbr, const float* d_dmap, const float* d_occlusion,
+                          const float* d_filled, int w, int h, int dminl, float* d_sub, float* d_sub_filled, void* stream) {
+    SMX_ARG(subpix_mode_ok(mode));
+    SMX_ARG(d_keys && d_nbr && d_dmap && d_sub && w >= 1 && h >= 1);
+    SMX_ARG(d_sub != d_dmap);
+    SMX_ARG(!d_sub_filled || (d_occlusion && d_filled));
+    return launch_subpixel_pair(mode, d_keys, d_nbr, d_dmap, d_occlusion, d_filled, w, h, dminl, d_sub, d_sub_filled,
+                                (hipStream_t)stream);
+}
+
+float smx_subpixel_delta(int mode, float c0, float lo, float hi) {
+    return subpix_mode_ok(mode) ? subpixel_delta(mode, c0, lo, hi) : 0.0f;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -745,6 +792,10 @@ struct smx_ctx {
     hipStream_t st = nullptr;
     // keys / best / dmap / mean: left view first, right view behind it (one buffer each)
     DevBuf dL, dR, keys, best, map, mean, occ, fil, ws, costL, costR, aggLR;
+    // sub-pixel maps (smx_ctx_set_subpixel): neighbour state [2][3][h][w], maps [2][h][w] and [h][w], allocated on first use
+    int subpix = 0;
+    bool sub_valid = false;     // the maps belong to the last synchronous pair
+    DevBuf nbr, sub, subf;
     // pipelined entry (smx_ctx_stereo_pair_async): two slots of device inputs / results and pinned host staging, created
     // on first use.  Staging of a slot: [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l
     // mean_r | status word] coming down.
@@ -816,7 +867,7 @@ int smx_destroy(smx_ctx* c) {
 // The path of one pair on the context's stream: device images in, the eight result planes out (+ the optional volumes
 // of the context).  Shared by the synchronous and the pipelined host-pointer entry.
 static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dminl, int dminr, bool want_cost, bool want_agg,
-                       float* bestL, float* mapL, uint8_t* mean, float* occ, float* fil) {
+                       float* bestL, float* mapL, uint8_t* mean, float* occ, float* fil, bool subpix = false) {
     const smx_params* p = &c->p;
     const int w = c->w, h = c->h, size_d = c->size_d;
     const size_t n = c->n;
@@ -844,26 +895,30 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
         int64_t* kv[2] = {keysL, keysR};
         uint8_t* mv[2] = {mean, mean + n};
         float* av[2] = {c->aggLR.as<float>(), want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr};
+        float* nv[2] = {c->nbr.as<float>(), c->nbr.as<float>() + 3 * n};
         g_launches = 0;
         if ((rc = aggregate_fused(path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
-                                  want_agg ? av : nullptr, c->ws.p, c->ws_bytes, st, &g_launches)))
+                                  want_agg ? av : nullptr, c->ws.p, c->ws_bytes, st, &g_launches, subpix ? nv : nullptr)))
             return rc;
     } else {
         const int saved = g_agg_path;
         g_agg_path = 1;
-        if ((rc = smx_dev_aggregate_wta(p, dL, dR, want_cost ? c->costL.as<float>() : nullptr, w, h, dminl, 0, size_d,
-                                        keysL, mean, want_agg ? c->aggLR.as<float>() : nullptr, c->ws.p,
-                                        c->ws_bytes, st)))
+        if ((rc = aggregate_wta_one("smx_dev_aggregate_wta", p, dL, dR, want_cost ? c->costL.as<float>() : nullptr, w, h, dminl, 0,
+                                    size_d, keysL, mean, want_agg ? c->aggLR.as<float>() : nullptr, c->ws.p,
+                                    c->ws_bytes, subpix ? c->nbr.as<float>() : nullptr, st)))
             { g_agg_path = saved; return rc; }
-        if ((rc = smx_dev_aggregate_wta(p, dR, dL, want_cost ? c->costR.as<float>() : nullptr, w, h, dminr, 0, size_d,
-                                        keysR, mean + n,
-                                        want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr, c->ws.p,
-                                        c->ws_bytes, st)))
+        if ((rc = aggregate_wta_one("smx_dev_aggregate_wta", p, dR, dL, want_cost ? c->costR.as<float>() : nullptr, w, h, dminr, 0,
+                                    size_d, keysR, mean + n,
+                                    want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr, c->ws.p,
+                                    c->ws_bytes, subpix ? c->nbr.as<float>() + 3 * n : nullptr, st)))
             { g_agg_path = saved; return rc; }
         g_agg_path = saved;
     }
     // main.cu:112-118 presets, winning slices, main.cu:140-155
-    return smx_dev_finish_pair(p, keysL, w, h, dminl, dminr, dminl - 100, (float)dminl, bestL, mapL, occ, fil, st);
+    if ((rc = smx_dev_finish_pair(p, keysL, w, h, dminl, dminr, dminl - 100, (float)dminl, bestL, mapL, occ, fil, st))) return rc;
+    if (!subpix) return SMX_OK;
+    return smx_dev_subpixel_pair(c->subpix, keysL, c->nbr.as<float>(), mapL, occ, fil, w, h, dminl, c->sub.as<float>(),
+                                 c->subf.as<float>(), st);
 }
 
 static int ctx_check_device(smx_ctx* c, const char* who) {
@@ -886,6 +941,9 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     const bool want_agg = out->agg_l || out->agg_r;
     if (want_cost && !c->costL.p) { SMX_HIP(c->costL.alloc(vb)); SMX_HIP(c->costR.alloc(vb)); }
     if (want_agg && !c->aggLR.p) SMX_HIP(c->aggLR.alloc(2 * vb));
+    const bool subpix = c->subpix != 0;
+    if (subpix && !c->nbr.p) { SMX_HIP(c->nbr.alloc(6 * fb)); SMX_HIP(c->sub.alloc(2 * fb)); SMX_HIP(c->subf.alloc(fb)); }
+    c->sub_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     stage_mark(ST_BEGIN, st);
     SMX_HIP(hipMemcpyAsync(dL, gray_l, n, hipMemcpyHostToDevice, st));
@@ -894,7 +952,7 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     float* bestL = c->best.as<float>(); float* bestR = bestL + n;
     float* mapL = c->map.as<float>();   float* mapR = mapL + n;
     if ((rc = ctx_enqueue(c, dL, dR, dminl, dminr, want_cost, want_agg, bestL, mapL, c->mean.as<uint8_t>(), c->occ.as<float>(),
-                          c->fil.as<float>())))
+                          c->fil.as<float>(), subpix)))
         return rc;
     struct { void* dst; const void* src; size_t b; } copies[] = {
         {out->best_l, bestL, fb}, {out->best_r, bestR, fb}, {out->dmap_l, mapL, fb},
@@ -907,7 +965,29 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
         if (cp.dst && cp.src) SMX_HIP(hipMemcpyAsync(cp.dst, cp.src, cp.b, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    return smx_dev_agg_status(c->ws.p);
+    if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
+    c->sub_valid = subpix;
+    return SMX_OK;
+}
+
+int smx_ctx_set_subpixel(smx_ctx* c, int mode) {
+    SMX_ARG(c);
+    if (mode != 0 && !subpix_mode_ok(mode))
+        return fail(SMX_E_ARG, "smx_ctx_set_subpixel: mode must be 0, SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR");
+    c->subpix = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_subpixel_maps(smx_ctx* c, float* sub_l, float* sub_r, float* sub_filled) {
+    SMX_ARG(c);
+    int rc;
+    if ((rc = ctx_check_device(c, "smx_ctx_subpixel_maps"))) return rc;
+    if (!c->sub_valid) return fail(SMX_E_ARG, "smx_ctx_subpixel_maps: the last smx_ctx_stereo_pair ran without sub-pixel");
+    const size_t n = c->n, fb = n * sizeof(float);
+    if (sub_l) SMX_HIP(hipMemcpy(sub_l, c->sub.p, fb, hipMemcpyDeviceToHost));
+    if (sub_r) SMX_HIP(hipMemcpy(sub_r, c->sub.as<float>() + n, fb, hipMemcpyDeviceToHost));
+    if (sub_filled) SMX_HIP(hipMemcpy(sub_filled, c->subf.p, fb, hipMemcpyDeviceToHost));
+    return SMX_OK;
 }
 
 // ---- pipelined host-pointer entry ---------------------------------------------------------------------------------
@@ -937,6 +1017,7 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     SMX_ARG(c && gray_l && gray_r);
     int rc;
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
+    if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: two pairs are in flight already (smx_ctx_wait takes the older one)");
     if ((rc = ctx_async_setup(c))) return rc;

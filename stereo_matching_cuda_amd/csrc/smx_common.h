@@ -123,4 +123,56 @@ __host__ __device__ inline void unpack_key(int64_t key, float* cost, uint32_t* s
     *slice = 0xFFFFFFFFu - (uint32_t)((uint64_t)key & 0xFFFFFFFFu);
 }
 
+// ---- neighbours of the winner (sub-pixel refinement, smx_subpix.hip) -------------------------------------------------
+// WtaRun plus the q of the winner's neighbouring slices: lo = the slice just before the winner, hi = the slice just after it
+// (NaN while that slice has not been seen), prev = the previous slice (the run starts it at the pixel's `last`, or at NaN
+// for a pixel without a winner yet).  Same winner as WtaRun.
+struct WtaRunNbr {
+    float m = __builtin_inff();
+    uint32_t z = 0xFFFFFFFFu;
+    float lo = __builtin_nanf(""), hi = __builtin_nanf(""), prev;
+    __host__ __device__ explicit WtaRunNbr(float prev0) : prev(prev0) {}
+    __host__ __device__ inline void step(float q, uint32_t slice) {
+        const bool take = q <= m;
+        const float h1 = z + 1u == slice ? q : hi;      // (no winner yet: z + 1 wraps to 0, and hi means nothing)
+        lo = take ? prev : lo;
+        hi = take ? __builtin_nanf("") : h1;
+        m = take ? q : m;
+        z = take ? slice : z;
+        prev = q;
+    }
+    __host__ __device__ inline int64_t key() const { return z == 0xFFFFFFFFu ? KEY_IDENTITY : pack_key(m, z); }
+};
+
+// Per-pixel neighbour state d_nbr of a view: three f32 planes [3][h][w] -- 0 lo, 1 hi, 2 last (the q of the last slice
+// the view has aggregated).  The merge of a pass's run (slices slice0 .., first q `q0`) with the pixel's incoming key:
+// the run wins -> lo, hi of the run; the old winner stays -> lo unchanged, hi = q0 if the winner is slice0 - 1; a key
+// that stays the identity has no winner (lo = hi = NaN); always last = the run's prev.  Returns the merged key.
+__host__ __device__ inline float nbr_prev0(int64_t key_in, float last_in) { return key_in != KEY_IDENTITY ? last_in : __builtin_nanf(""); }
+__host__ __device__ inline int64_t nbr_merge(const WtaRunNbr& r, int64_t key_in, uint32_t slice0, float q0, float* lo, float* hi,
+                                             float* last) {
+    const int64_t kk = r.key();
+    const uint32_t zin = 0xFFFFFFFFu - (uint32_t)((uint64_t)key_in & 0xFFFFFFFFu);
+    if (kk < key_in) {
+        *lo = r.lo;
+        *hi = r.hi;
+    } else if (key_in == KEY_IDENTITY) {
+        *lo = *hi = __builtin_nanf("");
+    } else if (zin + 1u == slice0) {
+        *hi = q0;
+    }
+    *last = r.prev;
+    return kk < key_in ? kk : key_in;
+}
+
+// The sub-pixel offset of a winner of cost c0 from its neighbours lo, hi (SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR;
+// smx_subpixel_delta is the host copy of the C-ABI): 0 for an unknown neighbour (NaN) and for a result that is not finite
+__host__ __device__ inline float subpixel_delta(int mode, float c0, float lo, float hi) {
+    if (lo != lo || hi != hi) return 0.0f;
+    const float a = lo - c0, b = hi - c0;
+    const float den = mode == SMX_SUBPIX_PARABOLA ? a + b : fmaxf(a, b);
+    const float d = (a - b) / (2.0f * den);
+    return d - d == 0.0f ? d : 0.0f;
+}
+
 }  // namespace smx

@@ -290,6 +290,39 @@ __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ 
     keys[id] = key;
 }
 
+// k_q_wta that also keeps the winner's neighbouring q in the view's state planes nbr [3][h][w] (smx_common.h WtaRunNbr,
+// nbr_merge: the same winner as the packed-key min above)
+__global__ void k_q_wta_nbr(const float* __restrict__ Sa, const float* __restrict__ Sb,
+                            const float* __restrict__ im, int64_t* __restrict__ keys, float* __restrict__ nbr,
+                            float* __restrict__ agg, int w, int h, int count, int slice0, int R) {
+    int x = blockIdx.x * blockDim.x + threadIdx.x;
+    int y = blockIdx.y;
+    if (x >= w) return;
+    const int64_t n = (int64_t)w * h;
+    BoxTaps t = box_taps(x, y, w, h, R);
+    int64_t id = (int64_t)y * w + x;
+    float I = im[id];
+    const int64_t key = keys[id];
+    const bool ld = key != KEY_IDENTITY;                 // (no winner yet: the state is not read)
+    float lo = ld ? nbr[id] : 0.0f, hi = ld ? nbr[n + id] : 0.0f, last = ld ? nbr[2 * n + id] : 0.0f;
+    WtaRunNbr r(nbr_prev0(key, last));
+    float q0 = 0.0f;
+    for (int z = 0; z < count; ++z) {
+        const int64_t po = (int64_t)z * n;
+        float abar = box_eval(Sa + po, t);
+        float bbar = box_eval(Sb + po, t);
+        float m = abar * I;
+        float q = m + bbar;
+        q0 = z == 0 ? q : q0;
+        r.step(q, (uint32_t)(slice0 + z));
+        if (agg) agg[po + id] = q;
+    }
+    keys[id] = nbr_merge(r, key, (uint32_t)slice0, q0, &lo, &hi, &last);
+    nbr[id] = lo;
+    nbr[n + id] = hi;
+    nbr[2 * n + id] = last;
+}
+
 __global__ void k_init_keys(int64_t* keys, int64_t n) {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) keys[k] = KEY_IDENTITY;
@@ -633,6 +666,16 @@ int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const fl
     if (count <= 0) return SMX_OK;
     dim3 grid(cdiv(w, 256), h);
     hipLaunchKernelGGL(k_q_wta, grid, dim3(256), 0, st, Sa, Sb, im, keys, agg, w, h, count, slice0,
+                       p->radius);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
+int launch_q_wta_nbr(const smx_params* p, const float* Sa, const float* Sb, const float* im,
+                     int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
+    if (count <= 0) return SMX_OK;
+    dim3 grid(cdiv(w, 256), h);
+    hipLaunchKernelGGL(k_q_wta_nbr, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0,
                        p->radius);
     SMX_HIP(hipGetLastError());
     return SMX_OK;

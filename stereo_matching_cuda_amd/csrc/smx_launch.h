@@ -15,6 +15,8 @@ int launch_ab(const smx_params* p, const float* Sp, const float* SIp, const floa
               const float* cinv, float* A, float* B, int w, int h, int nplanes, hipStream_t st);
 int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const float* im,
                  int64_t* keys, float* agg, int w, int h, int count, int slice0, hipStream_t st);
+int launch_q_wta_nbr(const smx_params* p, const float* Sa, const float* Sb, const float* im,
+                     int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st);
 int launch_init_keys(int64_t* keys, int64_t n, hipStream_t st);
 int launch_init_wta(float* best, float* dmap, int64_t n, hipStream_t st);
 int launch_apply_keys(const int64_t* keys, int64_t n, int dmin, float* best, float* dmap, hipStream_t st);
@@ -32,4 +34,7 @@ int launch_finish_pair_row(const smx_params* p, const int64_t* keys, int w, int 
 int wmf_bucket_shift(int size_d);
 int launch_weighted_median(int radius, const uint16_t* ws, const uint16_t* wc, const uint8_t* guide, const float* disp,
                            const float* select, float* out, int w, int h, int dmin, int size_d, hipStream_t st);
+// smx_subpix.hip: sub-pixel maps of both views (smx_dev_subpixel_pair)
+int launch_subpixel_pair(int mode, const int64_t* keys, const float* nbr, const float* dmap, const float* occlusion,
+                         const float* filled, int w, int h, int dminl, float* sub, float* sub_filled, hipStream_t st);
 }  // namespace smx

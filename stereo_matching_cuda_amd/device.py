@@ -25,12 +25,18 @@ class PairPipeline:
 
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
-                 wmf=None, wmf_params=None):
+                 wmf=None, wmf_params=None, subpixel=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
-        filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched."""
+        filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
+        subpixel: None, "parabola" or "equiangular" -- sub-pixel maps from the winners' neighbouring aggregated costs (not
+        a stage of the reference): the aggregation keeps them in self.nbr (2, 3, h, w) through the _nbr entries, and
+        finish() runs smx_dev_subpixel_pair into self.sub (2, h, w) and self.sub_filled (h, w).  With None nothing is
+        allocated or launched."""
         if wmf not in (None, "occluded", "all"):
             raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
+        if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
+            raise ValueError(f"subpixel must be None, 'parabola' or 'equiangular', not {subpixel!r}")
         self.lib = _lib.lib()
         self.w, self.h, self.size_d = int(w), int(h), int(size_d)
         self.n = self.w * self.h
@@ -67,6 +73,10 @@ class PairPipeline:
         self.wmf_params = (wmf_params if wmf_params is not None else _lib.default_wmf_params()) if wmf else None
         self.refined = torch.empty((self.h, self.w), **f) if wmf else None
         self._guide = None            # left image of the last aggregation: the guide of the refinement
+        self.subpixel = subpixel
+        self.nbr = torch.empty((2, 3, self.h, self.w), **f) if subpixel else None
+        self.sub = torch.empty((2, self.h, self.w), **f) if subpixel else None
+        self.sub_filled = torch.empty((self.h, self.w), **f) if subpixel else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -99,9 +109,15 @@ class PairPipeline:
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
             try:
-                _lib.check(L.smx_dev_aggregate_wta_pair_cost(
-                    P, _dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr,
-                    self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
+                if self.subpixel:
+                    _lib.check(L.smx_dev_aggregate_wta_pair_nbr(
+                        P, _dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr,
+                        self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes,
+                        _dp(self.nbr), st))
+                else:
+                    _lib.check(L.smx_dev_aggregate_wta_pair_cost(
+                        P, _dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr,
+                        self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
             finally:
                 L.smx_set_max_slices_per_launch(0)
 
@@ -125,9 +141,15 @@ class PairPipeline:
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
             try:
-                _lib.check(L.smx_dev_aggregate_wta_pair(
-                    P, _dp(gray_l), _dp(gray_r), self.w, self.h, self.dminl, self.dminr, self.s_begin,
-                    self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
+                if self.subpixel:
+                    _lib.check(L.smx_dev_aggregate_wta_pair_nbr(
+                        P, _dp(gray_l), _dp(gray_r), None, None, self.w, self.h, self.dminl, self.dminr, self.s_begin,
+                        self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes,
+                        _dp(self.nbr), st))
+                else:
+                    _lib.check(L.smx_dev_aggregate_wta_pair(
+                        P, _dp(gray_l), _dp(gray_r), self.w, self.h, self.dminl, self.dminr, self.s_begin,
+                        self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
             finally:
                 L.smx_set_max_slices_per_launch(0)
 
@@ -144,9 +166,15 @@ class PairPipeline:
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
             try:
-                _lib.check(L.smx_dev_aggregate_wta(
-                    P, _dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end,
-                    _dp(self.keys[view]), _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes, st))
+                if self.subpixel:
+                    _lib.check(L.smx_dev_aggregate_wta_nbr(
+                        P, _dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end,
+                        _dp(self.keys[view]), _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes,
+                        _dp(self.nbr[view]), st))
+                else:
+                    _lib.check(L.smx_dev_aggregate_wta(
+                        P, _dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end,
+                        _dp(self.keys[view]), _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes, st))
             finally:
                 L.smx_set_max_slices_per_launch(0)
 
@@ -165,8 +193,20 @@ class PairPipeline:
             _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                              self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                              _dp(self.occlusion), _dp(self.filled), st))
+        if self.subpixel:
+            self.subpixel_maps()
         if self.wmf:
             self.refine()
+
+    def subpixel_maps(self):
+        """Sub-pixel maps of both views from the keys, the neighbour state and the finish's maps (smx_dev_subpixel_pair,
+        one launch): self.sub = dmap + delta, self.sub_filled = the left one where the LR check kept the pixel, filled
+        where it did not."""
+        with self._on_device():
+            _lib.check(self.lib.smx_dev_subpixel_pair(_lib.SUBPIX_MODES[self.subpixel], _dp(self.keys), _dp(self.nbr),
+                                                      _dp(self.dmap), _dp(self.occlusion), _dp(self.filled), self.w,
+                                                      self.h, self.dminl, _dp(self.sub), _dp(self.sub_filled),
+                                                      self._stream()))
 
     def refine(self):
         """The weighted median of the filled left map, guided by the left image the last aggregate() saw, into
@@ -215,4 +255,6 @@ class PairPipeline:
             r["aggl"], r["aggr"] = c(self.agg[0]), c(self.agg[1])
         if self.wmf:
             r["refined"] = c(self.refined)
+        if self.subpixel:
+            r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.sub[0]), c(self.sub[1]), c(self.sub_filled)
         return r

@@ -22,6 +22,9 @@
 //                     parameters; Hosni et al.'s last step, not in the reference), on every path: MODE `occluded`
 //                     filters the pixels the LR check invalidated, `all` every pixel.  Writes occlu_mapl_wmf.png
 //                     beside the 12 images, and --pfm / --png16 then hold the refined map
+//   --subpixel FIT    sub-pixel disparity (`parabola` or `equiangular`) from the winners' neighbouring aggregated costs
+//                     (smx_ctx_set_subpixel; implies --fused): --pfm / --png16 then hold the sub-pixel filled map.
+//                     Not with --wmf, --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -89,6 +92,7 @@ struct Options {
     bool fused = false, host_compare = false, fast = false;
     std::string pfm, png16;
     std::string wmf;         // "" = no refinement, else "occluded" or "all"
+    int subpixel = 0;        // 0 = off, else SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
     bool pipeline = false;
@@ -113,6 +117,15 @@ Options parse(int argc, char** argv) {
             value(o.wmf);
             if (o.ok && o.wmf != "occluded" && o.wmf != "all") {
                 std::fprintf(stderr, "--wmf needs `occluded` or `all`, not `%s`\n", o.wmf.c_str());
+                o.ok = false;
+            }
+        }
+        else if (a == "--subpixel") {
+            std::string v;
+            value(v);
+            o.subpixel = v == "parabola" ? SMX_SUBPIX_PARABOLA : v == "equiangular" ? SMX_SUBPIX_EQUIANGULAR : 0;
+            if (o.ok && !o.subpixel) {
+                std::fprintf(stderr, "--subpixel needs `parabola` or `equiangular`, not `%s`\n", v.c_str());
                 o.ok = false;
             }
         }
@@ -153,6 +166,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "bad disparity range [%d, %d]: need dmin <= dmax and at most 4096 labels\n", d_lo, d_hi);
         return 2;
     }
+    if (opt.subpixel && (!opt.wmf.empty() || opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--subpixel cannot be combined with --wmf (the median works on integer labels), --ngpu or "
+                             "--pipeline\n");
+        return 2;
+    }
     if (opt.ngpu < 0 || opt.ngpu > smx_device_count()) {
         std::fprintf(stderr, "--ngpu %d: this node shows %d HIP device(s)\n", opt.ngpu, smx_device_count());
         return 2;
@@ -174,7 +192,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const bool fused = opt.fused || sh_create;
+    const bool fused = opt.fused || sh_create || opt.subpixel;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -210,6 +228,7 @@ int main(int argc, char** argv) {
         unused_u8[v].assign(n, 0);
     }
     std::vector<float> occlusion, filled;
+    std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
     if (!fused) {
         // the reference's data flow: every stage is a host -> device -> host round trip
         for (int v = 0; v < 2; ++v) cost[v].resize((size_t)n * size_d);
@@ -248,6 +267,7 @@ int main(int argc, char** argv) {
         smx_ctx* ctx = nullptr;
         if (sh_create) CHECK(sh_create(&smx_config().params, w, h, size_d, opt.ngpu, opt.overlap ? 1 : 0, &sctx));
         else CHECK(smx_create(&smx_config().params, w, h, size_d, &ctx));
+        if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
@@ -279,6 +299,10 @@ int main(int argc, char** argv) {
                 stage_ms = t;
             }
             CHECK(smx_set_timing(0));
+        }
+        if (opt.subpixel) {
+            sub_filled.resize(n);
+            CHECK(smx_ctx_subpixel_maps(ctx, nullptr, nullptr, sub_filled.data()));
         }
         if (sh_create) CHECK(sh_destroy(sctx));
         else CHECK(smx_destroy(ctx));
@@ -324,8 +348,9 @@ int main(int argc, char** argv) {
         const std::vector<unsigned char> img = normalise_like_reference(refined.data(), (size_t)n);
         if (!smx_png_write((outdir + "/occlu_mapl_wmf.png").c_str(), w, h, 1, img.data())) ++write_failures;
     }
-    // disparity outputs in dataset conventions: positive pixel offsets of the filled left map (the refined one with --wmf)
-    const float* final_map = refined.empty() ? filled.data() : refined.data();
+    // disparity outputs in dataset conventions: positive pixel offsets of the filled left map (the refined one with --wmf,
+    // the sub-pixel one with --subpixel)
+    const float* final_map = !sub_filled.empty() ? sub_filled.data() : refined.empty() ? filled.data() : refined.data();
     if (!opt.pfm.empty()) {
         std::vector<float> d(n);
         for (int i = 0; i < n; ++i) d[i] = -final_map[i];

@@ -46,6 +46,9 @@ class ShardedPair:
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
+        if world > 1 and kw.get("subpixel") is not None:
+            # the neighbours of a winner at a shard boundary were aggregated on another rank
+            raise ValueError("subpixel needs the whole slice range on one rank (world == 1)")
         self.rank, self.world, self.group = rank, world, group
         s0, s1 = shard_range(size_d, rank, world)
         self.pipe = PairPipeline(w, h, size_d, s_begin=s0, s_end=s1, **kw)
