@@ -1,0 +1,82 @@
+// smx_agg.h -- the fused aggregation as the C-ABI sees it (smx_agg.hip): which aggregation a call runs, the one
+// description of its workspace, the orchestration of the two walkers (comb: smx_agg_v5.hip, ring: smx_agg_v4.hip).
+#pragma once
+#include "smx_common.h"
+
+namespace smx {
+
+// Options / report of one fused aggregation call (aggregate_fused; set and read through the C-ABI:
+// smx_set_agg_path, smx_set_max_slices_per_launch, smx_last_agg_path, smx_last_agg_chunk)
+struct AggOpts {
+    bool fast = false;       // FAST mode (not bit-exact)
+    int walker = 0;          // 0 choose, 4 ring walker forced, 5 comb walker forced (an error where it does not apply)
+    int max_chunk = 0;       // upper bound on the slices of one walker launch; 0 = as many as the workspace holds
+    bool keys_fresh = false; // the keys hold nothing yet: the first WTA pass starts from the identity (no smx_dev_init_keys needed)
+};
+struct AggInfo {
+    int walker_used = 0;     // 4 ring walker, 5 comb walker
+    int chunk = 0;           // slices per walker launch (of the first = largest launch)
+    int walker_launches = 0;
+    int launches = 0;        // all kernel launches + memsets of the call
+};
+
+// The one decision of which aggregation a call runs (smx_dev_aggregate_wta, the pair entries, the context, the workspace size):
+// 1 the multi-kernel path, 2 the ring walker, 4 FAST, 5 the comb walker; 0, with *why set, where the forced path does not apply.
+// forced is the caller's smx_set_agg_path value: 0 auto, 1 multi-kernel, 2 fused (walker chosen here), 3 ring walker, 4 FAST,
+// 5 comb walker.  Pure host arithmetic (no GPU needed: smx_debug_agg_path).
+int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, int forced, const char** why);
+
+// The workspace of one fused aggregation call.  Byte offsets from the 256-byte aligned start of the caller's workspace, in
+// carving order; every region is a multiple of 256 bytes.  All sizes derive from this: the carving of aggregate_fused, the
+// comb walker's descriptor bound (v5_fix_bytes), the chunk a workspace holds (agg_plan) and agg_workspace_bytes.
+struct AggLayout {
+    bool comb;            // the comb walker runs (else the ring walker)
+    bool fallback;        // ... with the ring walker queued behind it (materialised cost volumes)
+    bool own_q;           // the q planes live here (else the walkers write the caller's volume)
+    int nviews, chunk;    // views, slices per walker launch
+    int K, NI;            // strips and bands of the walker that runs
+    int K4, NI4;          // the ring walker's (what a queued fall-back runs with)
+    int K_flags;          // flag words per slice-view (fall-back: the larger of the two walkers')
+    size_t plane;         // floats per [h][w] plane
+    size_t qplane;        // floats per slice of q (own planes of the comb walker are comb-ordered: K * OWS >= w columns per row)
+    size_t q_slice;       // bytes per slice of a view's own q planes; 0: the caller's volume
+    size_t hand_sv;       // floats of hand-off records per slice-view (fall-back: the larger of the two walkers')
+    // ---- the fixed part
+    size_t status;        // 256 B: the call's status words (smx_dev_agg_status, smx_dev_agg_fallback)
+    size_t fg[2];         // both image planes [h][w + 2 PADX] (a single view's partner too)
+    size_t guid[2];       // per view: (mean_I, 1/(var_I + eps)) [h][w]
+    size_t g1p[2], i2p[2];   // per view, comb walker only: the comb-ordered copies (smx_agg_v5.h), view by view
+    size_t fix_end;       // [fg[0], fix_end): what the comb walker addresses through its one 32-bit-offset descriptor
+    size_t scratch[2][2]; // per view: integrals of I and of I*I
+    size_t chunk_begin;   // ---- per chunk of `chunk` slices
+    size_t q[2];          // per view: own q planes, q_slice apart
+    size_t hand;          // hand-off records of chunk * nviews slice-views
+    size_t ctrl;          // control block: ticket (AGG_CTRL_BYTES) + flags [sv][K_flags]
+    size_t ctrl_bytes;
+    size_t end;
+};
+constexpr size_t AGG_CTRL_BYTES = 256;   // ticket (zeroed with the flags before every launch)
+AggLayout agg_layout(int w, int h, int radius, int nviews, bool comb, bool fallback, bool own_q, int chunk);
+// The layout a call runs with -- walker, queued fall-back, the chunk its workspace holds (at most `total` slices and
+// opt.max_chunk) -- or the call's error.  `lost`: the bytes in front of the workspace's 256-byte boundary.  Pure host
+// arithmetic (smx_debug_agg_chunk).
+int agg_plan(const smx_params* p, int w, int h, int nviews, bool use_cost, bool own_q, const AggOpts& opt, size_t ws_bytes,
+             size_t lost, int total, AggLayout* L);
+// bytes for ONE view with `nslices` slices in flight, whichever walker and radius the call runs (q planes included)
+size_t agg_workspace_bytes(int w, int h, int nslices);
+// Bytes of the region the comb walker addresses through its one 32-bit-offset descriptor
+size_t v5_fix_bytes(int w, int h, int nviews);
+// status words of the last fused aggregation that used this workspace: [0] != 0: a hand-off wait timed out;
+// [1] != 0: the comb walker met cost values outside its exactness argument and the queued ring walker redid the chunk
+int agg_read_status(const void* d_ws, unsigned* out, int nwords);
+
+// Aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses d_guide[v]
+// as guidance; its cost slices are d_cost[v] (materialised, slice s at (s - s_begin)*w*h) or, when
+// d_cost[v] == NULL, are built on the fly against d_guide[v ^ 1] (nviews == 2) / d_other[0].
+int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_guide,
+                    const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
+                    const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
+                    uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
+                    hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr);
+
+}  // namespace smx

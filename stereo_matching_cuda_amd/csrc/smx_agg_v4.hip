@@ -42,17 +42,13 @@
 
 #include <type_traits>
 
-#include "smx_agg_dev.h"
-#include "smx_agg_v5.h"
-#include "smx_launch.h"
+#include "smx_agg_v4.h"
 
 namespace smx {
 namespace v4 {
 using namespace aggdev;
 
-constexpr int OW = 64;                  // output columns per strip = one wave
-constexpr int RMAX = 9;                 // largest supported box radius
-constexpr int HWMAX = 2 * RMAX + 1;     // halo / overlap columns
+// (OW, RMAX, HWMAX, BH, WG_PER_CU, the hand-off record and the argument block: smx_agg_v4.h)
 constexpr int TWMAX = OW + HWMAX;       // ring columns in use (83 at R = 9)
 // A ring row is component-planar: ROWF floats = the first components (p / a) of its columns at [0, OFF1), the
 // second ones (I p / b) at [OFF1, OFF1 + NCOLP).  The row scan then moves four columns of one component per LDS
@@ -64,37 +60,12 @@ constexpr int ROWF = OFF1 + NCOLP;      // 172
 static_assert(NCOLP >= TWMAX && NCOLP % 4 == 0 && OFF1 % 4 == 0 && OFF1 >= NCOLP, "planar ring row");
 constexpr int NT = 512;
 constexpr int NWAVE = NT / 64;
-// Band height 16: rings of 36 rows, 50 KB of LDS, three workgroups per CU, fewer idle rows at the bottom of a strip
-// than with 32 (rings of 52 rows, 72 KB, two workgroups per CU)
-constexpr int BH = 16;                  // band height
 constexpr int RPW = BH / NWAVE;         // rows of a band per wave in the LANE = COLUMN phases
 constexpr int RR = BH + 2 * RMAX + 2;   // ring rows: a band of box means needs BH + 2R + 1 rows
-constexpr int WG_PER_CU = 3;
 static_assert(RR % 4 == 0 && RR % RPW == 0 && BH % RPW == 0 && RPW % 2 == 0,
               "groups of four (column scan) and of RPW (box, cost) consecutive ring rows never wrap");
 
 enum Src { SRC_IMG = 0, SRC_COST = 1 };
-
-
-struct View {
-    const fg_t* FG1;      // this view's image plane [h][w + 2 PADX], sentinel columns on either side
-    const fg_t* FG2;      // the other view's (SRC_IMG)
-    const float* cost;    // SRC_COST: [slice][h][w]
-    const f2* guid;       // (mean_I, 1/(var_I + eps)) [h][w]
-    float* q;             // out: [slice][h][w]
-    int d0;               // disparity of local slice 0
-};
-
-struct Args {
-    View v[2];
-    int w, h, R, K, NI, nslices, nsv, nitems;
-    f2* hand;             // hand-off records [parity][sv][iteration] (see REC_F2)
-    unsigned* flags;      // [sv][K]  published-record counters (zeroed before every launch)
-    unsigned* ticket;     // work-item counter              (zeroed before every launch)
-    unsigned* status;     // != 0: a flag wait timed out (results invalid)
-    const unsigned* only_if;   // != NULL: the launch does nothing unless this word is nonzero (the queued fall-back behind the comb walker)
-    CostConst cc;
-};
 
 // ---------------------------------------------------------------------------------------------
 // prep: u8 image [h][w] -> (value, x-derivative) half2 plane [h][w + 2 PADX] with PADX sentinel columns on
@@ -282,12 +253,7 @@ __global__ void k_v4_guid_finish(GuidArgs ga, int w, int h, int R, double eps) {
     if (ga.mean_u8[view]) ga.mean_u8[view][id] = mean_to_u8(g.x);
 }
 
-// Hand-off record of one iteration (per parity and slice-view), written and read in 16-byte units:
-//   [0, BH)              stage-1 row carries of band i        (float2 per row)
-//   [BH, 2 BH)           stage-2 row carries of band i-1
-//   [2 BH, 2 BH + BH*HP) last 2R+1 columns of the stage-2 integral of band i-1, HP = 20 float2 per row
-constexpr int HP = HWMAX + 1;
-constexpr int REC_F2 = 2 * BH + BH * HP;          // float2 per record
+// (the hand-off record REC_F2: smx_agg_v4.h)
 constexpr int REC_U = REC_F2 / 2;                 // 16-byte units per record: one per thread
 static_assert(REC_U <= NT && HP % 2 == 0 && BH % 2 == 0, "one 16-byte hand-off unit per thread");
 
@@ -1185,61 +1151,43 @@ __global__ __launch_bounds__(256) void k_v4_wta_nbr(WtaArgs wa, float* nbr0, flo
 }  // namespace v4
 
 // =============================================================================================
-// host orchestration
+// launchers (smx_agg_v4.h)
 // =============================================================================================
 static inline unsigned cdivu4(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
-struct V4Layout {
-    int K, NI;
-    size_t fg;        // floats per image plane (half2 = 4 B per pixel)
-    size_t plane;     // floats per w*h plane
-    size_t sv_hand;   // floats of hand-off records per slice-view (2 parities x NI records)
-};
-
-static V4Layout v4_layout(int w, int h, int R) {
-    V4Layout L;
-    L.K = (w + R + v4::OW - 1) / v4::OW;
-    L.NI = (h - 1 + 2 * R) / v4::BH + 2;     // the q rows of iteration i end at BH i - 2R
-    L.fg = (size_t)(w + 2 * v4::PADX) * h;
-    L.plane = (size_t)w * h;
-    L.sv_hand = (size_t)2 * L.NI * v4::REC_F2 * 2;   // parity x records x float2
-    return L;
-}
-
-void v4_geometry(int* ow, int* bh) { *ow = v4::OW; *bh = v4::BH; }
-
 bool v4_supported(const smx_params* p) { return p->radius >= 0 && p->radius <= v4::RMAX; }
 
-// Both walkers build the cost of a partner outside the image from the sentinel cell (60000, 60000) of k_v4_guid_rows and rely
-// on min(|d|, threshold) saturating to the threshold there, so that the cost is the border constant of costVolume.cu:184.  In
-// the ring walker's f32 differences the nearest a pixel value (0 .. 255) and a derivative (multiples of 0.5 in [-127.5, 127.5])
-// come to the sentinel is |255 - 60000| = 59745 and |127.5 - 60000| = 59872.5: larger thresholds would not saturate (the comb
-// walker's bounds, in packed halves, are tighter: v5_supported).  The multi-kernel path uses the border constant itself.
-constexpr int RING_TH_COLOR_MAX = 59745, RING_TH_GRAD_MAX = 59872;
-
-static bool ring_applies(const smx_params* p, bool use_cost) {
-    return v4_supported(p) && (use_cost || (p->th_color <= RING_TH_COLOR_MAX && p->th_grad <= RING_TH_GRAD_MAX));
-}
-
-constexpr size_t V4_CTRL_BYTES = 256;   // ticket (zeroed with the flags before every launch)
-
-static size_t v4_flag_bytes_k(int K, int nsv) { return align_up(V4_CTRL_BYTES + (size_t)nsv * K * sizeof(unsigned), 256); }
-static size_t v4_flag_bytes(const V4Layout& L, int nsv) { return v4_flag_bytes_k(L.K, nsv); }
-
-// bytes for ONE view with `nslices` slices in flight (q planes included)
-size_t v4_workspace_bytes(int w, int h, int nslices) {
-    V4Layout L = v4_layout(w, h, v4::RMAX);
-    size_t b = 256;
-    b += 2 * align_up(L.fg * 4, 256);                               // both image planes (single-view calls too)
-    b += align_up(L.plane * 8, 256);                                // (mean_I, 1/(var+eps))
-    b += 2 * align_up(L.plane * 4, 256);                            // guidance scratch: integrals of I, I*I
-    const size_t qp5 = v5::q_plane_floats(w, h);                     // comb-ordered q plane of the comb walker
-    b += (size_t)nslices * align_up((L.plane > qp5 ? L.plane : qp5) * 4, 256);   // q
-    b += align_up((size_t)v5::strips(w) * v5::bands(h) * v5::CLP * 100, 256) + 512;   // comb-ordered guidance planes (80 + 20 B per lane and band)
-    const size_t hand5 = v5::sv_hand_floats(h);                    // the comb walker's records (smx_agg_v5.hip)
-    b += align_up((size_t)nslices * (L.sv_hand > hand5 ? L.sv_hand : hand5) * 4, 256);
-    b += v4_flag_bytes(L, 2 * nslices);                             // control block (shared by both views; K of either walker <= L.K)
-    return b + 16 * 256;
+int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, hipStream_t st) {
+    v4::GuidArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int v = 0; v < nviews; ++v) {
+        ga.FG[v] = g.FG[v];
+        ga.S[v][0] = g.S0[v]; ga.S[v][1] = g.S1[v];
+        ga.G[v] = g.G[v];
+        ga.mean_u8[v] = g.mean_u8[v];
+    }
+    for (int i = 0; i < 2; ++i) {
+        ga.prep.I[i] = g.I[i]; ga.prep.FG[i] = g.FG[i];
+        ga.prep.zero[i] = g.zero[i]; ga.prep.nzero[i] = g.nzero[i];
+    }
+    const int nimg = g.I[1] ? 2 : 1;
+    ga.nimg = nimg; ga.nviews = nviews;
+    // rows per workgroup: few enough that the launch fills the chip, and whole rows fit the LDS
+    const int wpad = v4::gr_wpad(w);
+    int rows = (int)((size_t)(152 * 1024) / ((size_t)8 * wpad));
+    const int fillrows = h * nviews / 256;
+    rows = rows > fillrows ? fillrows : rows;
+    rows = rows > v4::GR_MAXROWS ? v4::GR_MAXROWS : rows;
+    rows = rows < 1 && (size_t)8 * wpad <= (size_t)(152 * 1024) ? 1 : rows;
+    if (rows < 1) return fail(SMX_E_ARG, "aggregate_fused: image too wide for the guidance row scan");
+    static LdsLimitOnce lim;     // (once per device: the sharded driver runs several devices from one process)
+    SMX_HIP(lim.ensure((const void*)v4::k_v4_guid_rows, 160 * 1024));
+    hipLaunchKernelGGL(v4::k_v4_guid_rows, dim3(cdivu4(h, rows), nimg > nviews ? nimg : nviews), dim3(v4::GR_NT), (size_t)8 * rows * wpad, st,
+                       ga, w, h, rows);
+    hipLaunchKernelGGL(v4::k_v4_guid_cols, dim3(cdivu4(w, 64), 2, nviews), dim3(64 * v4::GC_NW), 0, st, ga, w, h);
+    if (finish) hipLaunchKernelGGL(v4::k_v4_guid_finish, dim3(cdivu4(w, 256), h, nviews), dim3(256), 0, st, ga, w, h, R, eps);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
 }
 
 template <int SRC, bool FAST>
@@ -1257,329 +1205,28 @@ static int launch_walk4(const v4::Args& a, hipStream_t st) {
     return SMX_OK;
 }
 
-// status words of the last fused aggregation that used this workspace: [0] != 0: a hand-off wait timed out;
-// [1] != 0: the comb walker met cost values outside its exactness argument and the queued ring walker redid the chunk
-int v4_read_status(const void* d_ws, unsigned* out, int nwords) {
-    const char* base = (const char*)align_up((size_t)d_ws, 256);
-    SMX_HIP(hipMemcpy(out, base, sizeof(unsigned) * (size_t)nwords, hipMemcpyDeviceToHost));
-    return SMX_OK;
+int v4_walk_launch(const v4::Args& a, bool use_cost, bool fast, hipStream_t st) {
+    if (fast) return use_cost ? launch_walk4<v4::SRC_COST, true>(a, st) : launch_walk4<v4::SRC_IMG, true>(a, st);
+    return use_cost ? launch_walk4<v4::SRC_COST, false>(a, st) : launch_walk4<v4::SRC_IMG, false>(a, st);
 }
 
-// Bytes of the region the comb walker addresses through its one 32-bit-offset descriptor: both image planes, the
-// guidance planes of the views and their comb-ordered copies (the carving order of aggregate_v4)
-size_t v5_fix_bytes(int w, int h, int nviews) {
-    const V4Layout L = v4_layout(w, h, v4::RMAX);
-    const size_t permb = (size_t)v5::strips(w) * v5::bands(h) * v5::CLP;
-    return 2 * align_up(L.fg * 4, 256) + (size_t)nviews * (align_up(L.plane * 8, 256) + align_up(permb * 5 * 16, 256) + align_up(permb * 20, 256));
-}
-
-// The comb walker (smx_agg_v5.hip) serves radius 9 with eps >= 1; with costs built from the images, default-like cost
-// parameters (v5_supported); with materialised cost volumes, planes of at least one 16-byte quad (the kernel checks the values).
-// It addresses both image planes, the guidance planes and their comb-ordered copies through ONE buffer descriptor with 32-bit
-// offsets, 0x80000000 marking "outside": the whole region must stay below 2 GiB (v5_fix_bytes: the terms of the carving).
-static bool v5_applies(const smx_params* p, int w, int h, int nviews, bool use_cost) {
-    return v5_fix_bytes(w, h, nviews) < 0x80000000ull &&
-           (use_cost ? v5_supported_cost(p) && (size_t)w * h >= 4 : v5_supported(p));
-}
-
-// The one decision of which aggregation a call runs (smx_dev_aggregate_wta, the pair entries, the context, the workspace size):
-// 1 the multi-kernel path, 2 the ring walker, 4 FAST, 5 the comb walker; 0, with *why set, where the forced path does not apply.
-// forced is the caller's smx_set_agg_path value: 0 auto, 1 multi-kernel, 2 fused (walker chosen here), 3 ring walker, 4 FAST,
-// 5 comb walker.  Pure host arithmetic (no GPU needed: smx_debug_agg_path).
-int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, int forced, const char** why) {
-    *why = nullptr;
-    if (forced == 1) return 1;
-    if (!ring_applies(p, use_cost)) {
-        if (forced == 0) return 1;
-        *why = !v4_supported(p) ? "radius > 9"
-                                : "th_color > 59745 or th_grad > 59872 (the sentinel cell of an out-of-range partner would not "
-                                  "saturate the truncation: only the multi-kernel path gives the border cost there)";
-        return 0;
-    }
-    const bool comb = v5_applies(p, w, h, nviews, use_cost);
-    if (forced == 5 && !comb) {
-        *why = "the comb walker does not apply (radius 9, eps in [1, 1e30), default-like cost parameters where the costs are "
-               "built from the images -- thresholds exact in fp16, th_color <= 59744, th_grad <= 59872 --, planes within "
-               "its 2 GiB descriptor)";
-        return 0;
-    }
-    if (forced == 3) return 2;
-    if (forced == 4) return 4;
-    return comb ? 5 : 2;
-}
-
-// Aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses d_guide[v]
-// as guidance; its cost slices are d_cost[v] (materialised, slice s at (s - s_begin)*w*h) or, when
-// d_cost[v] == NULL, are built on the fly against d_guide[v ^ 1] (nviews == 2) / d_other[0].
-int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                 const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                 const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                 uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                 hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr) {
-    const int R = p->radius;
-    const bool fast = opt.fast;
-    V4Layout L = v4_layout(w, h, R);
-    const bool use_cost = d_cost && d_cost[0];
-    // The comb walker (smx_agg_v5.hip) serves the hot case: radius 9, costs built from the images, exact mode.
-    // opt.walker: 0 = choose, 4 = the ring walker of this file.  Both share this orchestration: image planes, guidance
-    // statistics, chunking, WTA pass; only the strip / band geometry and the records differ.
-    // (Where each walker applies: v5_applies, agg_path_for.)
-    // Materialised cost volumes (the reference's calling convention, guidedFilter.cu:198-200) run on the comb walker too
-    // (round 5): its cost wave loads the costs and CHECKS them -- +0 or a normal number in [2^-60, 2^60] is what its exactness
-    // argument covers.  A violation cannot come back to the host of an asynchronous call, so the ring walker, which takes
-    // any input, is queued behind it with a device-side gate (`only_if`): it does nothing unless the comb walker raised the
-    // second status word, and the two WTA passes are gated the other way round.  Cost: two empty launches and a memset.
-    const bool use_v5 = opt.walker != 4 && v5_applies(p, w, h, nviews, use_cost);
-    const bool fallback4 = use_v5 && use_cost;
-    // (the entry points' decision once more: neither walker runs where agg_path_for would not send the call to it)
-    const char* why = nullptr;
-    if (!agg_path_for(p, w, h, nviews, use_cost, opt.walker == 5 ? 5 : 3, &why)) return fail(SMX_E_ARG, "aggregate_v4: %s", why);
-    if (info) { *info = AggInfo(); info->walker_used = use_v5 ? 5 : 4; }
-    const V4Layout L4 = L;      // the ring walker's geometry (the queued fall-back uses it)
-    if (use_v5) {
-        L.K = v5::strips(w);
-        L.NI = v5::bands(h);
-        L.sv_hand = v5::sv_hand_floats(h);
-    }
-    // records and flags are shared by the two walkers of a call with a queued fall-back: the larger of each
-    const size_t sv_hand_c = fallback4 && L4.sv_hand > L.sv_hand ? L4.sv_hand : L.sv_hand;
-    const int K_c = fallback4 && L4.K > L.K ? L4.K : L.K;
-    // every plane is addressed through 32-bit buffer offsets, with 0x80000000 as "outside the image"
-    if ((size_t)h * ((size_t)w + 2 * v4::PADX) * 8 >= 0x80000000ull)
-        return fail(SMX_E_ARG, "aggregate_v4: an image plane of %d x %d exceeds 2 GiB", w, h);
-    if (use_cost && nviews == 2 && !d_cost[1])
-        return fail(SMX_E_ARG, "aggregate_v4: both views need a cost volume or none");
-    char* base = (char*)align_up((size_t)d_ws, 256);
-    size_t avail = ws_bytes > (size_t)(base - (char*)d_ws) ? ws_bytes - (size_t)(base - (char*)d_ws) : 0;
-    bool oom = false;
-    auto carve = [&](size_t bytes) {
-        char* r = base;
-        size_t b = align_up(bytes, 256);
-        if (b > avail) { oom = true; b = avail; }
-        base += b;
-        avail -= b;
-        return (void*)r;
-    };
-    // first 256 B: status word of the call (smx_dev_agg_status)
-    unsigned* status = (unsigned*)carve(256);
-    if (oom) return fail(SMX_E_WS, "aggregate_v4: workspace too small");
-    // fixed part: image planes, guidance statistics, guidance scratch
-    v4::fg_t* FG[2];
-    float* gs[4];
-    v4::f2* gpair[2];
-    for (int i = 0; i < 2; ++i) FG[i] = (v4::fg_t*)carve(L.fg * 4);
-    for (int v = 0; v < nviews; ++v) gpair[v] = (v4::f2*)carve(L.plane * 8);
-    // comb-ordered guidance planes of the comb walker (smx_agg_v5.h): [K][h][CLP] per view
-    v4::f2* g1p[2] = {nullptr, nullptr};
-    unsigned* i2p[2] = {nullptr, nullptr};
-    // (band-major, smx_agg_v5.h: 5 NI row pairs of 16 B per lane; per band 16 B + 4 B per lane)
-    const size_t permb = (size_t)v5::strips(w) * v5::bands(h) * v5::CLP;
-    if (use_v5)
-        for (int v = 0; v < nviews; ++v) {
-            g1p[v] = (v4::f2*)carve(permb * 5 * 16);
-            i2p[v] = (unsigned*)carve(permb * 20);
-        }
-    const char* const fix_end = base;       // image planes + guidance planes: the comb walker addresses them through one descriptor
-    if (use_v5 && (size_t)(fix_end - (const char*)FG[0]) >= 0x80000000ull)
-        return fail(SMX_E_ARG, "aggregate_v4: comb walker planes exceed the 2 GiB descriptor (v5_fix_bytes out of step with the carving)");
-    for (int i = 0; i < 2 * nviews; ++i) gs[i] = (float*)carve(L.plane * 4);
-    const int total = s_end - s_begin;
-    // per slice-view: q plane (unless the caller's volume is written directly) + records + flags
-    const bool own_q = !(d_agg && d_agg[0]);
-    // (the comb walker's own q planes are comb-ordered: K * OWS >= w columns per row)
-    const size_t qplane = use_v5 && own_q ? v5::q_plane_floats(w, h) : L.plane;
-    const size_t per_sv = (own_q ? align_up(qplane * 4, 256) : 0) + sv_hand_c * 4 +
-                          (size_t)K_c * sizeof(unsigned);
-    size_t fit = avail > 8 * 256 + V4_CTRL_BYTES ? (avail - 8 * 256 - V4_CTRL_BYTES) / (per_sv * nviews) : 0;
-    if (oom || (fit < 1 && total > 0))
-        return fail(SMX_E_WS, "aggregate_v4: workspace %zu B too small (need >= %zu B per view)",
-                    ws_bytes, v4_workspace_bytes(w, h, 1));
-    int chunk = fit > (size_t)total ? total : (int)fit;
-    if (opt.max_chunk > 0 && chunk > opt.max_chunk) chunk = opt.max_chunk;
-    if (chunk < 1) chunk = 1;
-    if (info) info->chunk = chunk;
-    const int nsv_max = chunk * nviews;
-    float* qbuf[2] = {nullptr, nullptr};
-    if (own_q)
-        for (int v = 0; v < nviews; ++v) qbuf[v] = (float*)carve((size_t)chunk * align_up(qplane * 4, 256));
-    v4::f2* hand = (v4::f2*)carve((size_t)nsv_max * sv_hand_c * 4);
-    char* ctrl = (char*)carve(v4_flag_bytes_k(K_c, nsv_max));
-    if (oom) return fail(SMX_E_WS, "aggregate_v4: workspace carve overflow");
-    int nl = 0, rc;
-
-    v4::PrepArgs pa;
-    pa.I[0] = d_guide[0];
-    pa.I[1] = nviews == 2 ? d_guide[1] : (d_other ? d_other[0] : nullptr);
-    pa.FG[0] = FG[0]; pa.FG[1] = FG[1];
-    const int nimg = pa.I[1] ? 2 : 1;
-    pa.zero[0] = status; pa.nzero[0] = 64;
-    pa.zero[1] = (unsigned*)ctrl; pa.nzero[1] = (unsigned)(v4_flag_bytes_k(K_c, nsv_max) / 4);
-    // (no launch of its own: k_v4_guid_rows below does this kernel's work for its image rows)
-
-    // ---- guidance statistics (guidedFilter.cu:58-123): (mean_I, 1/(var_I + eps)), optional u8 mean image
-    {
-        v4::GuidArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        for (int v = 0; v < nviews; ++v) {
-            ga.FG[v] = FG[v];
-            ga.S[v][0] = gs[2 * v]; ga.S[v][1] = gs[2 * v + 1];
-            ga.G[v] = gpair[v];
-            ga.mean_u8[v] = d_mean_u8 ? d_mean_u8[v] : nullptr;
-        }
-        ga.prep = pa; ga.nimg = nimg; ga.nviews = nviews;
-        {
-            // rows per workgroup: few enough that the launch fills the chip, and whole rows fit the LDS
-            const int wpad = v4::gr_wpad(w);
-            int rows = (int)((size_t)(152 * 1024) / ((size_t)8 * wpad));
-            const int fillrows = h * nviews / 256;
-            rows = rows > fillrows ? fillrows : rows;
-            rows = rows > v4::GR_MAXROWS ? v4::GR_MAXROWS : rows;
-            rows = rows < 1 && (size_t)8 * wpad <= (size_t)(152 * 1024) ? 1 : rows;
-            if (rows < 1) return fail(SMX_E_ARG, "aggregate_v4: image too wide for the guidance row scan");
-            static LdsLimitOnce lim;     // (once per device: the sharded driver runs several devices from one process)
-            SMX_HIP(lim.ensure((const void*)v4::k_v4_guid_rows, 160 * 1024));
-            hipLaunchKernelGGL(v4::k_v4_guid_rows, dim3(cdivu4(h, rows), nimg > nviews ? nimg : nviews), dim3(v4::GR_NT), (size_t)8 * rows * wpad, st,
-                               ga, w, h, rows);
-        }
-        hipLaunchKernelGGL(v4::k_v4_guid_cols, dim3(cdivu4(w, 64), 2, nviews), dim3(64 * v4::GC_NW), 0, st, ga, w, h);
-        if (use_v5) {
-            // (the comb walker's planes: the statistics are evaluated where the comb-ordered copy is written, and G / the u8
-            // mean leave from there too -- one launch and one round trip of G less than finish + permute)
-            const float* S0[2] = {ga.S[0][0], ga.S[1][0]};
-            const float* S1[2] = {ga.S[0][1], ga.S[1][1]};
-            if ((rc = v5_perm_launch(nviews, S0, S1, gpair, ga.mean_u8, FG, g1p, i2p, w, h, p->eps, st))) return rc;
-        } else {
-            hipLaunchKernelGGL(v4::k_v4_guid_finish, dim3(cdivu4(w, 256), h, nviews), dim3(256), 0, st, ga, w, h, R, p->eps);
-        }
-        SMX_HIP(hipGetLastError());
-        nl += 3;
-    }
-    stage_mark(ST_GUIDANCE, st);
-
-    v4::Args a0;
-    memset(&a0, 0, sizeof(a0));
-    a0.w = w; a0.h = h; a0.R = R; a0.K = L.K; a0.NI = L.NI;
-    a0.cc = make_cost_const(p);
-    for (int v = 0; v < nviews; ++v) {
-        a0.v[v].FG1 = FG[v]; a0.v[v].FG2 = FG[v ^ 1];
-        a0.v[v].guid = gpair[v];
-    }
-    for (int s0 = s_begin; s0 < s_end; s0 += chunk) {
-        const int cnt = (s_end - s0) < chunk ? (s_end - s0) : chunk;
-        v4::Args a = a0;
-        v4::WtaArgs wa;
-        for (int v = 0; v < 2; ++v) {
-            const int vv = v < nviews ? v : 0;
-            float* qv = own_q ? qbuf[vv] : d_agg[vv] + (size_t)(s0 - s_begin) * L.plane;   // (own planes: `qplane` floats apart)
-            if (v < nviews) {
-                a.v[v].q = qv;
-                a.v[v].d0 = dmin[v] + s0;
-                a.v[v].cost = use_cost ? d_cost[v] + (size_t)(s0 - s_begin) * L.plane : nullptr;
-            }
-            wa.q[v] = qv;
-            wa.keys[v] = d_keys[vv];
-        }
-        a.nslices = cnt; a.nsv = cnt * nviews;
-        a.nitems = a.nsv * L.K;
-        a.hand = hand;
-        a.ticket = (unsigned*)ctrl; a.status = status;
-        a.flags = (unsigned*)(ctrl + V4_CTRL_BYTES);
-        if (s0 != s_begin) SMX_HIP(hipMemsetAsync(ctrl, 0, v4_flag_bytes_k(K_c, a.nsv), st));   // (first chunk: cleared by k_v4_guid_rows)
-        if (use_v5) {
-            v5::Args b;
-            memset(&b, 0, sizeof(b));
-            b.fix = (const char*)FG[0];
-            b.fix_bytes = (size_t)(fix_end - (const char*)FG[0]);
-            for (int v = 0; v < 2; ++v) {
-                const int vv = v < nviews ? v : 0;
-                b.o_fg[v] = (unsigned)((const char*)FG[v] - b.fix);
-                b.o_g1p[v] = (unsigned)((const char*)g1p[vv] - b.fix);
-                b.o_i2p[v] = (unsigned)((const char*)i2p[vv] - b.fix);
-                b.q[v] = a.v[vv].q;
-                b.d0[v] = a.v[vv].d0;
-            }
-            b.w = w; b.h = h; b.K = L.K; b.NI = L.NI;
-            b.P = v5::period(h, L.K);
-            b.nslices = a.nslices; b.nsv = a.nsv; b.nitems = a.nitems;
-            b.hand = (float*)hand; b.flags = a.flags; b.ticket = a.ticket; b.status = a.status;
-            b.src_cost = use_cost ? 1 : 0;
-            b.cost_plane = L.plane;
-            b.bad = status + 1;
-            for (int v = 0; v < 2; ++v) b.cost[v] = a.v[v < nviews ? v : 0].cost;
-            b.cc = a.cc;
-            {
-                const _Float16 hc = (_Float16)a.cc.th_color, hg = (_Float16)a.cc.th_grad;
-                unsigned short uc, ug;
-                memcpy(&uc, &hc, 2); memcpy(&ug, &hg, 2);
-                b.th2 = (unsigned)uc | ((unsigned)ug << 16);
-            }
-            b.fast = fast ? 1 : 0;
-            {
-                // Role priorities (smx_agg_v5.hip PRIO_*) only while the launch's q planes stay below 6 GB.  Measured in rounds 4
-                // and 5 (profiles/r05_prio_*): worth 2-7 % on KITTI geometry up to 1 500 slices (5.7 GB of q), on Motorcycle / 4K
-                // geometry with few slices and on every aspect ratio at KITTI's volume; 0.4-4.8 % slower on 4K (34 GB of q per
-                // launch), and -3.8 %, +3.0 % and -1.7 % on Motorcycle (15 GB) on three boxes.  The losing case has identical
-                // instruction counts but vector-memory operations 32 % longer in flight (profiles/r05_prio_pmc_motorcycle.txt);
-                // its cause is not established, so the rule follows the variable the effect follows: the q bytes of the launch.
-                constexpr double PRIO_MAX_Q_BYTES = 6e9;
-                const double q_bytes = (double)a.nsv * (double)qplane * 4.0;
-                b.prio = q_bytes < PRIO_MAX_Q_BYTES ? 1 : 0;
-            }
-            b.qperm = own_q ? 1 : 0;
-            b.q_plane = qplane;
-            rc = v5_launch(b, st);
-            if (!rc && fallback4) {
-                // the queued ring walker (does nothing unless status[1] was raised): its own geometry, fresh tickets and flags
-                SMX_HIP(hipMemsetAsync(ctrl, 0, v4_flag_bytes_k(K_c, a.nsv), st));
-                v4::Args a4 = a;
-                a4.K = L4.K; a4.NI = L4.NI;
-                a4.nitems = a4.nsv * L4.K;
-                a4.only_if = status + 1;
-                rc = fast ? launch_walk4<v4::SRC_COST, true>(a4, st) : launch_walk4<v4::SRC_COST, false>(a4, st);
-                nl += 2;
-            }
-        } else if (fast) rc = use_cost ? launch_walk4<v4::SRC_COST, true>(a, st) : launch_walk4<v4::SRC_IMG, true>(a, st);
-        else rc = use_cost ? launch_walk4<v4::SRC_COST, false>(a, st) : launch_walk4<v4::SRC_IMG, false>(a, st);
-        if (rc) return rc;
-        if (info) ++info->walker_launches;
-        stage_mark(ST_WALK, st);
-        bool al8 = L.plane % 2 == 0;
-        for (int v = 0; v < nviews; ++v) al8 = al8 && ((uintptr_t)wa.q[v] & 7) == 0;
-        wa.gate = nullptr; wa.gate_nonzero = 0;
-        // (opt.keys_fresh: the caller's keys hold nothing yet -- the first WTA pass of the call starts from the identity instead
-        // of loading them, which saves the smx_dev_init_keys launch in front of the call; with the gated pair of passes of a
-        // queued fall-back exactly one of the two runs, so both may take the flag)
-        const bool fresh = opt.keys_fresh && s0 == s_begin;
-        wa.fresh = fresh ? 1 : 0;
-        // (d_nbr: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge)
-        float* const nbr1 = d_nbr ? d_nbr[nviews - 1] : nullptr;
-        if (use_v5 && own_q) {
-            if (d_nbr) rc = v5_wta_nbr_launch(nviews, wa.q, wa.keys, d_nbr, w, h, cnt, s0, fallback4 ? status + 1 : nullptr, fresh, st);
-            else rc = v5_wta_launch(nviews, wa.q, wa.keys, w, h, cnt, s0, fallback4 ? status + 1 : nullptr, fresh, st);
-            if (rc) return rc;
-            if (fallback4) {
-                // ... and the WTA over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
-                wa.gate = status + 1; wa.gate_nonzero = 1;
-                if (d_nbr) hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, d_nbr[0], nbr1, L.plane, cnt, s0);
-                else if (al8) hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)L.plane, 512), nviews), dim3(256), 0, st, wa, L.plane, cnt, s0);
-                else hipLaunchKernelGGL(v4::k_v4_wta, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, L.plane, cnt, s0);
-                SMX_HIP(hipGetLastError());
-                ++nl;
-            }
-        } else if (d_nbr)
-            hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa, d_nbr[0], nbr1,
-                               L.plane, cnt, s0);
-        else if (al8)
-            hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)L.plane, 512), nviews), dim3(256), 0, st, wa,
-                               L.plane, cnt, s0);
-        else
-            hipLaunchKernelGGL(v4::k_v4_wta, dim3(cdivu4((int64_t)L.plane, 256), nviews), dim3(256), 0, st, wa,
-                               L.plane, cnt, s0);
-        SMX_HIP(hipGetLastError());
-        stage_mark(ST_WTA, st);
-        nl += s0 != s_begin ? 3 : 2;
-    }
-    if (info) info->launches = nl;
+int v4_wta_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, size_t n, int count, int slice0,
+                  const unsigned* only_if, bool fresh, hipStream_t st) {
+    v4::WtaArgs wa;
+    for (int v = 0; v < 2; ++v) { wa.q[v] = q[v < nviews ? v : 0]; wa.keys[v] = keys[v < nviews ? v : 0]; }
+    wa.gate = only_if; wa.gate_nonzero = only_if ? 1 : 0;
+    wa.fresh = fresh ? 1 : 0;
+    // two pixels per lane where every plane can be read in 8-byte units
+    bool al8 = n % 2 == 0;
+    for (int v = 0; v < nviews; ++v) al8 = al8 && ((uintptr_t)wa.q[v] & 7) == 0;
+    if (nbr)
+        hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)n, 256), nviews), dim3(256), 0, st, wa, nbr[0], nbr[nviews - 1], n,
+                           count, slice0);
+    else if (al8)
+        hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)n, 512), nviews), dim3(256), 0, st, wa, n, count, slice0);
+    else
+        hipLaunchKernelGGL(v4::k_v4_wta, dim3(cdivu4((int64_t)n, 256), nviews), dim3(256), 0, st, wa, n, count, slice0);
+    SMX_HIP(hipGetLastError());
     return SMX_OK;
 }
 

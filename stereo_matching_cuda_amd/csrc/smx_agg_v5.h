@@ -1,5 +1,5 @@
-// smx_agg_v5.h -- interface of the comb-form aggregation kernel (smx_agg_v5.hip) towards the host orchestration
-// of smx_agg_v4.hip: argument block, strip / band / record geometry, eligibility.
+// smx_agg_v5.h -- interface of the comb walker (smx_agg_v5.hip) towards the host orchestration of smx_agg.hip:
+// argument block, strip / band / record geometry, eligibility, launchers.
 #pragma once
 #include "smx_agg_dev.h"
 
@@ -8,7 +8,7 @@ namespace v5 {
 
 // Comb length 9: seven combs per wave, three comb waves per stage + a row-scan wave + a cost wave (512 threads, two
 // workgroups per CU at 128 VGPRs); the row scans run beside the comb rows.  (Round 4 also built comb lengths 12 and 16 as
-// three-barrier forms -- slower; tools/variants/ keeps that file.)
+// three-barrier forms -- slower; the history keeps that file.)
 constexpr int L = 9;                    // lanes of a comb
 constexpr int CPW = 64 / L;             // combs per wave
 constexpr int NS1 = (19 + CPW - 1) / CPW;   // comb waves per stage
@@ -89,6 +89,8 @@ inline size_t sv_hand_floats(int h) { return (size_t)2 * records(h) * REC_U * 4;
 // term >= 2^-60, eps >= 1
 bool v5_supported(const smx_params* p);
 bool v5_supported_cost(const smx_params* p);     // the same for materialised cost volumes (values checked in the kernel)
+// slot geometry of an item of h rows in K strips: bands, the last stage-2 slot, v5::period (smx_debug_v5_period)
+void v5_slots(int h, int K, int* bands, int* q_last, int* period);
 int v5_launch(const v5::Args& a, hipStream_t st);
 // comb-ordered guidance planes of one call: G (mean_I, 1/(var+eps)) [h][w] and the image planes FG -> g1p, i2p
 int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G, uint8_t* const* mean_u8,

@@ -26,8 +26,8 @@
 //   stage-2 combs  the a/b band sl-2 out of tile 2[sl%2] into registers (first thing: the stage-1 waves wait for that
 //                  through an LDS counter before their first store), hand-off record of pass sl-1 -> global (sc1);
 //                  S2 += R2, box, division, q rows [10 sl - 38, 10 sl - 28) -> HBM
-// (The earlier three-barrier forms with comb lengths 12 / 16 -- W / R / X phases, the row scans on wave 0 -- are history:
-// tools/variants/smx_agg_v5_r04_L9_L12_L16.hip, not built into the library.)
+// (The earlier three-barrier forms with comb lengths 12 / 16 -- W / R / X phases, the row scans on wave 0 -- are in the
+// history of this file: round 4.)
 // Hand-off, tickets and the bounded flag waits are those of smx_agg_v4.hip (strip-major tickets: the left neighbour of
 // an item always holds an earlier ticket); every wave takes the flag value it acts on from an LDS word written in the
 // slot before (s_peek), so that all eight waves agree on whether the slot has the extra barrier of a wait.
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         auto cost_verdict = [&]() {
             if constexpr (ROLE == ROLE_COST) {
                 // a cost of the volume outside {+0} U [2^-60, 2^60] (negative, -0, denormal, tiny, huge, infinite, NaN): this
-                // kernel's results for the chunk do not count (smx_agg_v4.hip has queued the ring walker behind it)
+                // kernel's results for the chunk do not count (smx_agg.hip has queued the ring walker behind it)
                 if (A.src_cost && __builtin_amdgcn_ballot_w64(c_max > 0x5d800000u || c_min1 < 0x21800000u - 1u) != 0 && lane == 0)
                     flag_store(A.bad, 1u);
                 c_max = 0u; c_min1 = 0xffffffffu;
@@ -1371,7 +1371,6 @@ int v5_wta_nbr_launch(int nviews, const float* const* q, int64_t* const* keys, f
     return SMX_OK;
 }
 
-void v5_geometry(int* ow, int* bh) { *ow = v5::OWS; *bh = v5::BH; }
 void v5_slots(int h, int K, int* bands, int* q_last, int* period) { *bands = v5::bands(h); *q_last = (h + 37) / 10; *period = v5::period(h, K); }
 
 bool v5_supported(const smx_params* p) {

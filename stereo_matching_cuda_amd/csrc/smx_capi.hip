@@ -8,6 +8,9 @@
 #include <string>
 #include <vector>
 
+#include "smx_agg.h"
+#include "smx_agg_v4.h"
+#include "smx_agg_v5.h"
 #include "smx_launch.h"
 
 namespace smx {
@@ -49,28 +52,12 @@ static thread_local int g_max_chunk = 0;     // smx_set_max_slices_per_launch
 static thread_local int g_keys_fresh = 0;    // smx_set_keys_fresh
 static thread_local AggInfo g_last_info;     // smx_last_agg_chunk
 
-// smx_agg_v4.hip (host orchestration of both fused walkers)
-int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, int forced, const char** why);
-size_t v4_workspace_bytes(int w, int h, int nslices);
-int aggregate_v4(const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                 const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                 const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                 uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                 hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr);
-size_t v5_fix_bytes(int w, int h, int nviews);
-int v4_read_status(const void* d_ws, unsigned* out, int nwords);
-void v4_geometry(int* ow, int* bh);
-// smx_agg_v5.hip
-bool v5_supported(const smx_params* p);
-void v5_geometry(int* ow, int* bh);
-void v5_slots(int h, int K, int* bands, int* q_last, int* period);
-
 // the fused aggregation of the path agg_path_for chose (2 = ring walker, 4 = FAST, 5 = comb walker); reports it
-static int aggregate_fused(int path, const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                           const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                           const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                           uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                           hipStream_t st, int* launches, float* const* d_nbr = nullptr) {
+static int fused_entry(int path, const smx_params* p, int nviews, const uint8_t* const* d_guide,
+                       const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
+                       const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
+                       uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
+                       hipStream_t st, int* launches, float* const* d_nbr = nullptr) {
     if (g_keys_fresh && s_end <= s_begin) {
         // nothing to aggregate: the promise "the call presets the keys" still holds
         for (int v = 0; v < nviews; ++v) { int rk = launch_init_keys(d_keys[v], (int64_t)w * h, st); if (rk) return rk; }
@@ -81,8 +68,8 @@ static int aggregate_fused(int path, const smx_params* p, int nviews, const uint
     opt.walker = path == 2 ? 4 : path == 5 ? 5 : 0;
     opt.max_chunk = g_max_chunk;
     AggInfo info;
-    int rc = aggregate_v4(p, nviews, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys, d_mean_u8,
-                          d_agg, d_ws, ws_bytes, st, opt, &info, d_nbr);
+    int rc = aggregate_fused(p, nviews, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys, d_mean_u8,
+                             d_agg, d_ws, ws_bytes, st, opt, &info, d_nbr);
     if (rc) return rc;
     g_last_info = info;
     if (launches) *launches = info.launches;
@@ -218,7 +205,7 @@ size_t smx_agg_workspace_bytes(int w, int h, int nslices) {
     if (w < 1 || h < 1 || nslices < 1) return 0;
     // v1 path: guidance im, mean_im, cinv, S_im, S_sq ; per slice in flight: cost, T0, T1, A, B
     const size_t v1 = plane_bytes(w, h) * (5 + 5 * (size_t)nslices) + 2 * WS_ALIGN;
-    const size_t f = v4_workspace_bytes(w, h, nslices);
+    const size_t f = agg_workspace_bytes(w, h, nslices);
     return v1 > f ? v1 : f;
 }
 
@@ -227,7 +214,7 @@ size_t smx_agg_workspace_bytes_for(const smx_params* p, int w, int h, int nslice
     // where a fused walker runs for costs built from the images (agg_path_for; forced paths aside: smx_set_agg_path(1) callers
     // size with smx_agg_workspace_bytes): image / guidance planes, per slice ONE q plane + the hand-off records
     const char* why = nullptr;
-    if (agg_path_for(p, w, h, 2, false, 0, &why) != 1) return v4_workspace_bytes(w, h, nslices);
+    if (agg_path_for(p, w, h, 2, false, 0, &why) != 1) return agg_workspace_bytes(w, h, nslices);
     return smx_agg_workspace_bytes(w, h, nslices);
 }
 
@@ -275,6 +262,25 @@ __attribute__((visibility("default"))) int smx_debug_agg_path(const smx_params* 
     return SMX_OK;
 }
 
+// (dev / test hook, not in smx.h: the slices per walker launch of a fused call with these arguments -- agg_plan, the layout
+// aggregate_fused runs with -- on a workspace of ws_bytes that loses the worst case of 255 bytes to its 256-byte alignment;
+// forced as for smx_debug_agg_path; SMX_E_WS where the workspace holds no slice; the thread's knobs are not applied)
+__attribute__((visibility("default"))) int smx_debug_agg_chunk(const smx_params* p, int w, int h, int nviews, int use_cost,
+                                                               int own_q, int forced, uint64_t ws_bytes, int slices, int* chunk) {
+    SMX_ARG(p && chunk && w >= 2 && h >= 1 && (nviews == 1 || nviews == 2) && forced >= 0 && forced <= 5 && p->radius >= 0 && slices >= 0);
+    const char* why = nullptr;
+    const int path = agg_path_for(p, w, h, nviews, use_cost != 0, forced, &why);
+    if (!path) return fail(SMX_E_ARG, "smx_debug_agg_chunk: fused path %d forced but %s", forced, why);
+    if (path == 1) return fail(SMX_E_ARG, "smx_debug_agg_chunk: the call runs the multi-kernel path");
+    AggOpts opt;
+    opt.walker = path == 2 ? 4 : path == 5 ? 5 : 0;
+    AggLayout L;
+    const int rc = agg_plan(p, w, h, nviews, use_cost != 0, own_q != 0, opt, (size_t)ws_bytes, 255, slices, &L);
+    if (rc) return rc;
+    *chunk = L.chunk;
+    return SMX_OK;
+}
+
 // (dev / test hook, not in smx.h: WtaRun, the float-domain winner of a run of ascending slices as the WTA kernels form it)
 __attribute__((visibility("default"))) int smx_debug_wta_run(const float* q, int n, uint32_t slice0, int64_t* key) {
     SMX_ARG(q && key && n >= 0);
@@ -297,12 +303,11 @@ __attribute__((visibility("default"))) int smx_debug_v5_period(int h, int K, int
 }
 
 int smx_agg_geometry(int radius, int* strip_cols, int* band_rows, int* tile_cols) {
-    int ow = 0, bh = 0;
-    v4_geometry(&ow, &bh);
+    int ow = v4::OW, bh = v4::BH;
     smx_params p;
     smx_default_params(&p);
     p.radius = radius;
-    if (g_agg_path != 3 && g_agg_path != 4 && v5_supported(&p)) v5_geometry(&ow, &bh);   // the comb walker
+    if (g_agg_path != 3 && g_agg_path != 4 && v5_supported(&p)) { ow = v5::OWS; bh = v5::BH; }   // the comb walker
     if (strip_cols) *strip_cols = ow;
     if (band_rows) *band_rows = bh;
     if (tile_cols) *tile_cols = ow + 2 * radius + 1;
@@ -312,7 +317,7 @@ int smx_agg_geometry(int radius, int* strip_cols, int* band_rows, int* tile_cols
 int smx_dev_agg_status(const void* d_workspace) {
     SMX_ARG(d_workspace);
     unsigned st = 0;
-    int rc = v4_read_status(d_workspace, &st, 1);
+    int rc = agg_read_status(d_workspace, &st, 1);
     if (rc) return rc;
     if (st != 0)
         return fail(SMX_E_HIP, "fused aggregation: hand-off wait of work item %u timed out (results invalid)",
@@ -323,7 +328,7 @@ int smx_dev_agg_status(const void* d_workspace) {
 int smx_dev_agg_fallback(const void* d_workspace, int* ring_walker_reran) {
     SMX_ARG(d_workspace && ring_walker_reran);
     unsigned st[2] = {0, 0};
-    int rc = v4_read_status(d_workspace, st, 2);
+    int rc = agg_read_status(d_workspace, st, 2);
     if (rc) return rc;
     *ring_walker_reran = st[1] != 0;
     return SMX_OK;
@@ -411,8 +416,8 @@ static int aggregate_wta_one(const char* who, const smx_params* p, const uint8_t
     if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", who, g_agg_path, why);
     if (path != 1) {
         g_launches = 0;
-        int rc2 = aggregate_fused(path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
-                               &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches, d_nbr ? &d_nbr : nullptr);
+        int rc2 = fused_entry(path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
+                              &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches, d_nbr ? &d_nbr : nullptr);
         if (rc2) return rc2;
         return SMX_OK;
     }
@@ -524,9 +529,9 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
         float* agg[2] = {d_agg, d_agg ? d_agg + vol : nullptr};
         float* nbr[2] = {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr};
         g_launches = 0;
-        int rc2 = aggregate_fused(path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
-                               d_mean_u8 ? mean : nullptr, d_agg ? agg : nullptr, d_workspace,
-                               workspace_bytes, st, &g_launches, d_nbr ? nbr : nullptr);
+        int rc2 = fused_entry(path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
+                              d_mean_u8 ? mean : nullptr, d_agg ? agg : nullptr, d_workspace,
+                              workspace_bytes, st, &g_launches, d_nbr ? nbr : nullptr);
         if (rc2) return rc2;
         return SMX_OK;
     }
@@ -897,7 +902,7 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
         float* av[2] = {c->aggLR.as<float>(), want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr};
         float* nv[2] = {c->nbr.as<float>(), c->nbr.as<float>() + 3 * n};
         g_launches = 0;
-        if ((rc = aggregate_fused(path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
+        if ((rc = fused_entry(path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
                                   want_agg ? av : nullptr, c->ws.p, c->ws_bytes, st, &g_launches, subpix ? nv : nullptr)))
             return rc;
     } else {

@@ -70,21 +70,6 @@ struct LdsLimitOnce {
 enum StageId { ST_BEGIN = 0, ST_UPLOAD, ST_GUIDANCE, ST_WALK, ST_WTA, ST_FINISH, ST_DOWNLOAD, ST_COUNT };
 void stage_mark(int stage, hipStream_t st);
 
-// Options / report of one fused aggregation call (smx_agg_v4.hip aggregate_v4; set and read through the C-ABI:
-// smx_set_agg_path, smx_set_max_slices_per_launch, smx_last_agg_path, smx_last_agg_chunk)
-struct AggOpts {
-    bool fast = false;       // FAST mode (not bit-exact)
-    int walker = 0;          // 0 choose, 4 ring walker forced, 5 comb walker forced (an error where it does not apply)
-    int max_chunk = 0;       // upper bound on the slices of one walker launch; 0 = as many as the workspace holds
-    bool keys_fresh = false; // the keys hold nothing yet: the first WTA pass starts from the identity (no smx_dev_init_keys needed)
-};
-struct AggInfo {
-    int walker_used = 0;     // 4 ring walker, 5 comb walker
-    int chunk = 0;           // slices per walker launch (of the first = largest launch)
-    int walker_launches = 0;
-    int launches = 0;        // all kernel launches + memsets of the call
-};
-
 // ---- packed WTA key ---------------------------------------------------------------------
 // key = sord(cost) << 32 | (0xFFFFFFFF - slice), compared as SIGNED 64-bit integers: sord = monotone
 // f32 -> i32 (-0 folded to +0), so that the per-pixel reduction of the shards is a plain int64 MIN

@@ -158,7 +158,7 @@ def test_integration_md_c_snippets_compile_against_the_headers(tmp_path):
 
 def test_comb_walker_descriptor_bound(lib):
     """The comb walker addresses both image planes, the guidance planes and their comb-ordered copies through ONE buffer
-    descriptor with 32-bit offsets (0x80000000 = "outside the image"): aggregate_v4 picks it only while that region stays
+    descriptor with 32-bit offsets (0x80000000 = "outside the image"): aggregate_fused picks it only while that region stays
     below 2 GiB.  The bound is the exact sum of the carved parts, not a per-pixel estimate (round-4 advisor finding: a
     24 B/pixel guard let 8192x5460 through at ~49 B/pixel).  Pure arithmetic: no GPU."""
     fn = C.CDLL(_lib.SO_PATH).smx_debug_v5_fix_bytes
