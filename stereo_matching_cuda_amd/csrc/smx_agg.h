@@ -1,21 +1,46 @@
-// smx_agg.h -- the fused aggregation as the C-ABI sees it (smx_agg.hip): which aggregation a call runs, the one
-// description of its workspace, the orchestration of the two walkers (comb: smx_agg_v5.hip, ring: smx_agg_v4.hip).
+// smx_agg.h -- the aggregation as the C-ABI sees it (smx_agg.hip): the description of a call, which aggregation it runs, the
+// one description of each workspace, the orchestration of the two walkers (comb: smx_agg_v5.hip, ring: smx_agg_v4.hip) and of
+// the multi-kernel path (smx_kernels.hip).
 #pragma once
 #include "smx_common.h"
 
 namespace smx {
 
-// Options / report of one fused aggregation call (aggregate_fused; set and read through the C-ABI:
-// smx_set_agg_path, smx_set_max_slices_per_launch, smx_last_agg_path, smx_last_agg_chunk)
+// One aggregation call: aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses guide[v] as
+// guidance; its cost slices are cost[v] (materialised, slice s at (s - s_begin)*w*h; all views or none) or, where cost[v] is
+// NULL, are built on the fly against other[v].  Pointers are NULL where absent: mean_u8 (the u8 mean image), agg (the
+// aggregated volume), nbr (the winners' neighbours, smx_common.h nbr_merge).  Everything a call depends on is here or in AggOpts.
+struct AggCall {
+    const char* who;         // the C-ABI entry, for error texts
+    const smx_params* p;
+    int nviews;
+    const uint8_t* guide[2];
+    const uint8_t* other[2];
+    const float* cost[2];
+    int dmin[2];             // disparity of slice 0
+    int64_t* keys[2];        // IN/OUT: the packed WTA keys [h][w]
+    uint8_t* mean_u8[2];
+    float* agg[2];
+    float* nbr[2];
+    int w, h, s_begin, s_end;
+    void* ws;                // the caller's workspace, any alignment
+    size_t ws_bytes;
+    hipStream_t st;
+};
+// Options / report of one call (set and read through the C-ABI: smx_set_max_slices_per_launch, smx_set_keys_fresh,
+// smx_last_agg_path, smx_last_agg_chunk, smx_last_agg_ms)
 struct AggOpts {
     bool fast = false;       // FAST mode (not bit-exact)
     int walker = 0;          // 0 choose, 4 ring walker forced, 5 comb walker forced (an error where it does not apply)
     int max_chunk = 0;       // upper bound on the slices of one walker launch; 0 = as many as the workspace holds
     bool keys_fresh = false; // the keys hold nothing yet: the first WTA pass starts from the identity (no smx_dev_init_keys needed)
+    // fast / walker of a fused path agg_path_for chose (2, 4, 5); `aggregate` sets them itself
+    void take_path(int path) { fast = path == 4; walker = path == 2 ? 4 : path == 5 ? 5 : 0; }
 };
 struct AggInfo {
-    int walker_used = 0;     // 4 ring walker, 5 comb walker
-    int chunk = 0;           // slices per walker launch (of the first = largest launch)
+    int path = 0;            // the aggregation that ran: 1 multi-kernel, 2 ring walker, 4 FAST, 5 comb walker
+    int walker_used = 0;     // 4 ring walker, 5 comb walker; 0 on the multi-kernel path
+    int chunk = 0;           // slices per walker launch (of the first = largest launch) / per pass of the multi-kernel path
     int walker_launches = 0;
     int launches = 0;        // all kernel launches + memsets of the call
 };
@@ -70,13 +95,28 @@ size_t v5_fix_bytes(int w, int h, int nviews);
 // [1] != 0: the comb walker met cost values outside its exactness argument and the queued ring walker redid the chunk
 int agg_read_status(const void* d_ws, unsigned* out, int nwords);
 
-// Aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses d_guide[v]
-// as guidance; its cost slices are d_cost[v] (materialised, slice s at (s - s_begin)*w*h) or, when
-// d_cost[v] == NULL, are built on the fly against d_guide[v ^ 1] (nviews == 2) / d_other[0].
-int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                    const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                    const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                    uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                    hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr);
+// The workspace of one call on the multi-kernel path, in the same terms.  The views of a call run one after the other in the
+// same planes.  The volumes of a chunk are packed with a plane stride of w*h floats (the kernels index planes as z*w*h).
+struct MultiLayout {
+    int chunk;            // slices per pass
+    int volumes;          // volumes of a chunk: T0, T1, A, B and, where the costs are built from the images, C
+    size_t status;        // 256 B: the status words (smx_dev_agg_status; this path cannot time out: cleared, never raised)
+    size_t im, mean_im, cinv, g0, g1;   // [h][w] f32 each: the image, mean_I, 1/(var_I + eps), two integrals
+    size_t chunk_begin;   // ---- per chunk of `chunk` slices, [chunk][h][w] f32 each
+    size_t T0, T1, A, B;
+    size_t C;             // the costs, where they are built from the images (else 0: none)
+    size_t end;
+};
+MultiLayout multi_layout(int w, int h, bool use_cost, int chunk);
+// The layout a call runs with -- the chunk its workspace holds, at most `total` slices; opt.max_chunk is "of the fused
+// aggregation" (smx.h) and not honoured -- or SMX_E_WS in the name of `who`.  Pure host arithmetic (smx_debug_agg_chunk).
+int multi_plan(const char* who, int w, int h, bool use_cost, size_t ws_bytes, size_t lost, int total, MultiLayout* L);
+// bytes for ONE view with `nslices` slices in flight on the multi-kernel path
+size_t multi_workspace_bytes(int w, int h, int nslices);
+
+// The one way into an aggregation: decides the path (agg_path_for with the caller's `forced`; an error in the name of c.who
+// where it does not apply) and runs the fused aggregation or the multi-kernel path for all views of the call.  opt: max_chunk
+// and keys_fresh; fast / walker follow from the path.
+int aggregate(const AggCall& c, int forced, const AggOpts& opt, AggInfo* info);
 
 }  // namespace smx

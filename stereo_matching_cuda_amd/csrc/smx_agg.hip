@@ -1,11 +1,13 @@
-// smx_agg.hip -- host side of the fused aggregation (smx_agg.h): the gates of the two walkers, the workspace layout, and the
-// orchestration of one call: guidance, then per chunk of slices a walker launch and a WTA pass.  No kernel lives here: the
-// comb walker's are in smx_agg_v5.hip, the ring walker's and the guidance kernels in smx_agg_v4.hip.
+// smx_agg.hip -- host side of the aggregation (smx_agg.h): the gates of the two walkers, the workspace layouts, and the
+// orchestration of one call.  Fused: guidance, then per chunk of slices a walker launch and a WTA pass.  Multi-kernel: per view
+// guidance, then per chunk the passes of the reference's slice loop.  No kernel lives here: the comb walker's are in
+// smx_agg_v5.hip, the ring walker's and the guidance kernels in smx_agg_v4.hip, the multi-kernel path's in smx_kernels.hip.
 #include <string.h>
 
 #include "smx_agg.h"
 #include "smx_agg_v4.h"
 #include "smx_agg_v5.h"
+#include "smx_launch.h"
 
 namespace smx {
 
@@ -55,7 +57,7 @@ int agg_path_for(const smx_params* p, int w, int h, int nviews, bool use_cost, i
 }
 
 // =============================================================================================
-// the workspace
+// the workspace of the fused aggregation
 // =============================================================================================
 static size_t agg_ctrl_bytes(int K, size_t nsv) { return align_up(AGG_CTRL_BYTES + nsv * K * sizeof(unsigned), 256); }
 
@@ -162,7 +164,7 @@ int agg_read_status(const void* d_ws, unsigned* out, int nwords) {
 }
 
 // =============================================================================================
-// one call
+// one fused call
 // =============================================================================================
 // the comb walker's arguments for the chunk the ring walker's `a` describes
 static v5::Args comb_args(const v4::Args& a, const AggLayout& L, char* base, bool use_cost, bool fast) {
@@ -208,18 +210,19 @@ static v5::Args comb_args(const v4::Args& a, const AggLayout& L, char* base, boo
 
 // Image planes and guidance statistics of the call (guidedFilter.cu:58-123) in three launches: (mean_I, 1/(var_I + eps)), the
 // optional u8 mean image, the comb walker's comb-ordered copies.  *out: the planes the walkers read.
-static int guidance(const AggLayout& L, char* base, const smx_params* p, const uint8_t* const* d_guide,
-                    const uint8_t* const* d_other, uint8_t* const* d_mean_u8, int w, int h, hipStream_t st, v4::Guidance* out) {
-    const int nviews = L.nviews;
+static int guidance(const AggLayout& L, char* base, const AggCall& c, v4::Guidance* out) {
+    const int nviews = L.nviews, w = c.w, h = c.h;
+    const smx_params* const p = c.p;
+    hipStream_t st = c.st;
     v4::Guidance& g = *out;
     memset(&g, 0, sizeof(g));
-    g.I[0] = d_guide[0];
-    g.I[1] = nviews == 2 ? d_guide[1] : (d_other ? d_other[0] : nullptr);
+    g.I[0] = c.guide[0];
+    g.I[1] = nviews == 2 ? c.guide[1] : c.other[0];
     for (int i = 0; i < 2; ++i) g.FG[i] = (aggdev::fg_t*)(base + L.fg[i]);
     for (int v = 0; v < nviews; ++v) {
         g.S0[v] = (float*)(base + L.scratch[v][0]); g.S1[v] = (float*)(base + L.scratch[v][1]);
         g.G[v] = (aggdev::f2*)(base + L.guid[v]);
-        g.mean_u8[v] = d_mean_u8 ? d_mean_u8[v] : nullptr;
+        g.mean_u8[v] = c.mean_u8[v];
     }
     // (the status words and the first chunk's control block are cleared here: no memset in front of the first walker)
     g.zero[0] = (unsigned*)(base + L.status); g.nzero[0] = 64;
@@ -234,24 +237,28 @@ static int guidance(const AggLayout& L, char* base, const smx_params* p, const u
     return v5_perm_launch(nviews, g.S0, g.S1, g.G, g.mean_u8, g.FG, g1p, i2p, w, h, p->eps, st);
 }
 
-int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                    const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                    const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                    uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                    hipStream_t st, const AggOpts& opt, AggInfo* info, float* const* d_nbr) {
-    const bool use_cost = d_cost && d_cost[0];
-    const bool own_q = !(d_agg && d_agg[0]);
-    if (use_cost && nviews == 2 && !d_cost[1])
-        return fail(SMX_E_ARG, "aggregate_fused: both views need a cost volume or none");
-    char* const base = (char*)align_up((size_t)d_ws, 256);
+static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) {
+    const smx_params* const p = c.p;
+    const int nviews = c.nviews, w = c.w, h = c.h, s_begin = c.s_begin, s_end = c.s_end;
+    hipStream_t st = c.st;
+    const bool use_cost = c.cost[0] != nullptr;
+    const bool own_q = !c.agg[0];
+    float* const* const d_nbr = c.nbr[0] ? c.nbr : nullptr;
+    char* const base = (char*)align_up((size_t)c.ws, 256);
     AggLayout L;
-    int rc = agg_plan(p, w, h, nviews, use_cost, own_q, opt, ws_bytes, (size_t)(base - (char*)d_ws), s_end - s_begin, &L);
+    int rc = agg_plan(p, w, h, nviews, use_cost, own_q, opt, c.ws_bytes, (size_t)(base - (char*)c.ws), s_end - s_begin, &L);
     if (rc) return rc;
-    if (info) { *info = AggInfo(); info->walker_used = L.comb ? 5 : 4; info->chunk = L.chunk; }
+    info->walker_used = L.comb ? 5 : 4;
+    info->chunk = L.chunk;
+    if (opt.keys_fresh && s_end <= s_begin) {
+        // nothing to aggregate: the promise "the call presets the keys" still holds
+        for (int v = 0; v < nviews; ++v)
+            if ((rc = launch_init_keys(c.keys[v], (int64_t)w * h, st))) return rc;
+    }
     unsigned* const status = (unsigned*)(base + L.status);
     char* const ctrl = base + L.ctrl;
     v4::Guidance g;
-    if ((rc = guidance(L, base, p, d_guide, d_other, d_mean_u8, w, h, st, &g))) return rc;
+    if ((rc = guidance(L, base, c, &g))) return rc;
     int nl = 3;
     stage_mark(ST_GUIDANCE, st);
 
@@ -272,9 +279,9 @@ int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_gui
         v4::Args a = a0;
         const float* q[2] = {nullptr, nullptr};
         for (int v = 0; v < nviews; ++v) {
-            a.v[v].q = own_q ? (float*)(base + L.q[v]) : d_agg[v] + (size_t)(s0 - s_begin) * L.plane;   // (own planes: `qplane` floats apart)
-            a.v[v].d0 = dmin[v] + s0;
-            a.v[v].cost = use_cost ? d_cost[v] + (size_t)(s0 - s_begin) * L.plane : nullptr;
+            a.v[v].q = own_q ? (float*)(base + L.q[v]) : c.agg[v] + (size_t)(s0 - s_begin) * L.plane;   // (own planes: `qplane` floats apart)
+            a.v[v].d0 = c.dmin[v] + s0;
+            a.v[v].cost = use_cost ? c.cost[v] + (size_t)(s0 - s_begin) * L.plane : nullptr;
             q[v] = a.v[v].q;
         }
         a.nslices = cnt; a.nsv = cnt * nviews;
@@ -295,7 +302,7 @@ int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_gui
             }
         } else rc = v4_walk_launch(a, use_cost, opt.fast, st);
         if (rc) return rc;
-        if (info) ++info->walker_launches;
+        ++info->walker_launches;
         stage_mark(ST_WALK, st);
         // (opt.keys_fresh: the caller's keys hold nothing yet -- the first WTA pass of the call starts from the identity instead
         // of loading them, which saves the smx_dev_init_keys launch in front of the call; with the gated pair of passes of a
@@ -303,20 +310,135 @@ int aggregate_fused(const smx_params* p, int nviews, const uint8_t* const* d_gui
         const bool fresh = opt.keys_fresh && s0 == s_begin;
         // (d_nbr: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge)
         if (L.comb && own_q) {
-            if (d_nbr) rc = v5_wta_nbr_launch(nviews, q, d_keys, d_nbr, w, h, cnt, s0, fell_back, fresh, st);
-            else rc = v5_wta_launch(nviews, q, d_keys, w, h, cnt, s0, fell_back, fresh, st);
+            if (d_nbr) rc = v5_wta_nbr_launch(nviews, q, c.keys, d_nbr, w, h, cnt, s0, fell_back, fresh, st);
+            else rc = v5_wta_launch(nviews, q, c.keys, w, h, cnt, s0, fell_back, fresh, st);
             if (!rc && L.fallback) {
                 // ... and the WTA over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
-                rc = v4_wta_launch(nviews, q, d_keys, d_nbr, L.plane, cnt, s0, fell_back, fresh, st);
+                rc = v4_wta_launch(nviews, q, c.keys, d_nbr, L.plane, cnt, s0, fell_back, fresh, st);
                 ++nl;
             }
-        } else rc = v4_wta_launch(nviews, q, d_keys, d_nbr, L.plane, cnt, s0, nullptr, fresh, st);
+        } else rc = v4_wta_launch(nviews, q, c.keys, d_nbr, L.plane, cnt, s0, nullptr, fresh, st);
         if (rc) return rc;
         stage_mark(ST_WTA, st);
         nl += s0 != s_begin ? 3 : 2;
     }
-    if (info) info->launches = nl;
+    info->launches = nl;
     return SMX_OK;
+}
+
+// =============================================================================================
+// the multi-kernel path: its workspace, one call
+// =============================================================================================
+MultiLayout multi_layout(int w, int h, bool use_cost, int chunk) {
+    MultiLayout L;
+    memset(&L, 0, sizeof(L));
+    L.chunk = chunk;
+    L.volumes = use_cost ? 4 : 5;
+    size_t at = 0;
+    auto region = [&at](size_t bytes) { const size_t o = at; at += align_up(bytes, 256); return o; };
+    const size_t plane = (size_t)w * h * sizeof(float);
+    L.status = region(256);
+    for (size_t* o : {&L.im, &L.mean_im, &L.cinv, &L.g0, &L.g1}) *o = region(plane);
+    L.chunk_begin = at;
+    for (size_t* o : {&L.T0, &L.T1, &L.A, &L.B}) *o = region(chunk * plane);
+    if (!use_cost) L.C = region(chunk * plane);
+    L.end = at;
+    return L;
+}
+
+// What smx_agg_workspace_bytes promises for this path: costs built from the images, every slice's planes rounded up on their
+// own (never less than the layout of nslices slices), and the up to 255 B in front of the workspace's 256-byte boundary.
+size_t multi_workspace_bytes(int w, int h, int nslices) {
+    const MultiLayout L = multi_layout(w, h, false, 1);
+    return L.end + (size_t)(nslices - 1) * (L.end - L.chunk_begin) + 256;
+}
+
+int multi_plan(const char* who, int w, int h, bool use_cost, size_t ws_bytes, size_t lost, int total, MultiLayout* L) {
+    const size_t avail = ws_bytes > lost ? ws_bytes - lost : 0;
+    // (every call needs the room of one slice whose costs are built from the images, also where they are materialised)
+    if (multi_layout(w, h, false, 1).end > avail)
+        return fail(SMX_E_WS, "%s: workspace %zu B < %zu B needed for one slice", who, ws_bytes, multi_workspace_bytes(w, h, 1));
+    // the largest chunk, of at most `total` slices, whose layout ends inside the workspace: from what would fit unrounded
+    *L = multi_layout(w, h, use_cost, 1);
+    const size_t fit = (avail - L->chunk_begin) / L->volumes / ((size_t)w * h * sizeof(float));
+    int chunk = fit > (size_t)total ? total : (int)fit;
+    if (chunk < 1) chunk = 1;
+    while (chunk > 1 && multi_layout(w, h, use_cost, chunk).end > avail) --chunk;
+    *L = multi_layout(w, h, use_cost, chunk);
+    return SMX_OK;
+}
+
+// guidedFilter.cu:58-238 for every view of the call, one after the other in the same planes: the guidance statistics in three
+// launches, then `chunk` slices per pass of the slice loop.  The WTA is folded into the last launch of a pass.
+static int aggregate_multi(const AggCall& c, const AggOpts& opt, AggInfo* info) {
+    const smx_params* const p = c.p;
+    const int w = c.w, h = c.h;
+    hipStream_t st = c.st;
+    const int64_t n = (int64_t)w * h;
+    char* const base = (char*)align_up((size_t)c.ws, 256);
+    MultiLayout L;
+    int rc = multi_plan(c.who, w, h, c.cost[0] != nullptr, c.ws_bytes, (size_t)(base - (char*)c.ws), c.s_end - c.s_begin, &L);
+    if (rc) return rc;
+    info->chunk = L.chunk;
+    float* const im = (float*)(base + L.im);
+    float* const mean_im = (float*)(base + L.mean_im);
+    float* const cinv = (float*)(base + L.cinv);
+    float* const g0 = (float*)(base + L.g0);
+    float* const g1 = (float*)(base + L.g1);
+    float* const T0 = (float*)(base + L.T0);
+    float* const T1 = (float*)(base + L.T1);
+    float* const A = (float*)(base + L.A);
+    float* const B = (float*)(base + L.B);
+    float* const C = L.C ? (float*)(base + L.C) : nullptr;
+    for (int v = 0; v < c.nviews; ++v) {
+        if (opt.keys_fresh && (rc = launch_init_keys(c.keys[v], n, st))) return rc;
+        SMX_HIP(hipMemsetAsync(base + L.status, 0, 256, st));
+        // guidance statistics (guidedFilter.cu:58-123)
+        if ((rc = launch_guid_prep(c.guide[v], im, g1, n, st))) return rc;
+        if ((rc = launch_integral(2, im, g1, g0, g1, w, h, 1, st))) return rc;
+        if ((rc = launch_guid_finish(p, g0, g1, mean_im, cinv, c.mean_u8[v], w, h, st))) return rc;
+        info->launches += 4;
+        stage_mark(ST_GUIDANCE, st);
+        // slice loop (guidedFilter.cu:171-238)
+        for (int s0 = c.s_begin; s0 < c.s_end; s0 += L.chunk) {
+            const int cnt = (c.s_end - s0) < L.chunk ? (c.s_end - s0) : L.chunk;
+            const float* cost = c.cost[v] ? c.cost[v] + (int64_t)(s0 - c.s_begin) * n : C;
+            if (!c.cost[v]) {
+                if ((rc = launch_cost(p, c.guide[v], c.other[v], C, w, h, c.dmin[v] + s0, cnt, st))) return rc;
+                ++info->launches;
+            }
+            if ((rc = launch_integral(1, cost, im, T0, T1, w, h, cnt, st))) return rc;
+            if ((rc = launch_ab(p, T0, T1, mean_im, cinv, A, B, w, h, cnt, st))) return rc;
+            if ((rc = launch_integral(2, A, B, A, B, w, h, cnt, st))) return rc;
+            float* agg = c.agg[v] ? c.agg[v] + (int64_t)(s0 - c.s_begin) * n : nullptr;
+            if (c.nbr[v]) rc = launch_q_wta_nbr(p, A, B, im, c.keys[v], c.nbr[v], agg, w, h, cnt, s0, st);
+            else rc = launch_q_wta(p, A, B, im, c.keys[v], agg, w, h, cnt, s0, st);
+            if (rc) return rc;
+            info->launches += 6;
+            stage_mark(ST_WALK, st);
+        }
+    }
+    return SMX_OK;
+}
+
+// =============================================================================================
+// the one dispatch
+// =============================================================================================
+int aggregate(const AggCall& c, int forced, const AggOpts& opt, AggInfo* info) {
+    const bool use_cost = c.cost[0] != nullptr;
+    if (c.nviews == 2 && use_cost != (c.cost[1] != nullptr))
+        return fail(SMX_E_ARG, "%s: both views need a cost volume or none", c.who);
+    const char* why = nullptr;
+    const int path = agg_path_for(c.p, c.w, c.h, c.nviews, use_cost, forced, &why);
+    if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", c.who, forced, why);
+    AggInfo mine;
+    if (!info) info = &mine;
+    *info = AggInfo();
+    info->path = path;
+    if (path == 1) return aggregate_multi(c, opt, info);
+    AggOpts o = opt;
+    o.take_path(path);
+    return aggregate_fused(c, o, info);
 }
 
 }  // namespace smx

@@ -1,5 +1,6 @@
-// smx_capi.hip -- the C-ABI of include/smx.h: argument checks, workspace carving, stage
-// orchestration, and the host-pointer wrappers that mirror the reference's per-stage functions.
+// smx_capi.hip -- the C-ABI of include/smx.h: argument checks, the calling thread's knobs, stage timing, the host-pointer
+// wrappers that mirror the reference's per-stage functions, and the persistent context.  Every aggregation goes through
+// run_aggregation into smx_agg.hip.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -18,7 +19,6 @@ namespace smx {
 static thread_local std::string g_err;
 static thread_local int g_timing = 0;        // 0 off, 1 the last call, 2 cumulative over calls
 static thread_local int g_launches = 0;
-static thread_local int g_in_ctx = 0;        // inside a persistent-context entry: the entry marks ST_BEGIN itself, nested calls do not
 static thread_local int g_marks_dropped = 0;
 // Stage timing of the calling thread (smx_set_timing / smx_stage_times): a list of (stage, event) marks of the
 // last timed call; the time between two consecutive marks belongs to the stage of the later one.  Events are taken
@@ -50,36 +50,27 @@ static thread_local int g_agg_path = 0;
 static thread_local int g_last_path = 0;
 static thread_local int g_max_chunk = 0;     // smx_set_max_slices_per_launch
 static thread_local int g_keys_fresh = 0;    // smx_set_keys_fresh
-static thread_local AggInfo g_last_info;     // smx_last_agg_chunk
+static thread_local AggInfo g_last_info;     // smx_last_agg_chunk: the last FUSED aggregation
 
-// the fused aggregation of the path agg_path_for chose (2 = ring walker, 4 = FAST, 5 = comb walker); reports it
-static int fused_entry(int path, const smx_params* p, int nviews, const uint8_t* const* d_guide,
-                       const uint8_t* const* d_other, const float* const* d_cost, int w, int h,
-                       const int* dmin, int s_begin, int s_end, int64_t* const* d_keys,
-                       uint8_t* const* d_mean_u8, float* const* d_agg, void* d_ws, size_t ws_bytes,
-                       hipStream_t st, int* launches, float* const* d_nbr = nullptr) {
-    if (g_keys_fresh && s_end <= s_begin) {
-        // nothing to aggregate: the promise "the call presets the keys" still holds
-        for (int v = 0; v < nviews; ++v) { int rk = launch_init_keys(d_keys[v], (int64_t)w * h, st); if (rk) return rk; }
-    }
+// Every aggregation of this file -- the device entries with forced = the thread's path, the context with its own -- meets the
+// thread's knobs here and nowhere else.  A context call, too, takes keys_fresh and max_chunk from the CALLING thread, and
+// smx_last_agg_chunk keeps describing the thread's last fused aggregation (smx.h), so a multi-kernel call leaves it alone.
+static int run_aggregation(const AggCall& c, int forced) {
     AggOpts opt;
     opt.keys_fresh = g_keys_fresh != 0;
-    opt.fast = path == 4;
-    opt.walker = path == 2 ? 4 : path == 5 ? 5 : 0;
     opt.max_chunk = g_max_chunk;
     AggInfo info;
-    int rc = aggregate_fused(p, nviews, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys, d_mean_u8,
-                             d_agg, d_ws, ws_bytes, st, opt, &info, d_nbr);
+    g_launches = 0;
+    const int rc = aggregate(c, forced, opt, &info);
     if (rc) return rc;
-    g_last_info = info;
-    if (launches) *launches = info.launches;
-    g_last_path = path;
+    g_last_path = info.path;
+    g_launches = info.launches;
+    if (info.path != 1) g_last_info = info;
     return SMX_OK;
 }
 
 void stage_mark(int stage, hipStream_t st) {
     if (!g_timing) return;
-    if (stage == ST_BEGIN && g_in_ctx > 1) return;       // (a device-pointer call nested in a context entry: one call, one ST_BEGIN)
     if (stage == ST_BEGIN && g_timing == 1) { g_timer.begin(); g_marks_dropped = 0; }
     if (g_timer.marks.size() >= 32768) { ++g_marks_dropped; return; }
     hipEvent_t e = g_timer.get();
@@ -104,10 +95,6 @@ struct DevBuf {
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
     template <class T> T* as() { return (T*)p; }
 };
-
-constexpr size_t WS_ALIGN = 256;
-
-static size_t plane_bytes(int w, int h) { return align_up((size_t)w * h * sizeof(float), WS_ALIGN); }
 
 }  // namespace smx
 
@@ -203,10 +190,9 @@ int smx_dev_integral(const float* d_in, float* d_out, int w, int h, int nplanes,
 
 size_t smx_agg_workspace_bytes(int w, int h, int nslices) {
     if (w < 1 || h < 1 || nslices < 1) return 0;
-    // v1 path: guidance im, mean_im, cinv, S_im, S_sq ; per slice in flight: cost, T0, T1, A, B
-    const size_t v1 = plane_bytes(w, h) * (5 + 5 * (size_t)nslices) + 2 * WS_ALIGN;
-    const size_t f = agg_workspace_bytes(w, h, nslices);
-    return v1 > f ? v1 : f;
+    // whichever path the call runs: the multi-kernel one (five planes per slice in flight) or a fused walker
+    const size_t m = multi_workspace_bytes(w, h, nslices), f = agg_workspace_bytes(w, h, nslices);
+    return m > f ? m : f;
 }
 
 size_t smx_agg_workspace_bytes_for(const smx_params* p, int w, int h, int nslices) {
@@ -262,22 +248,24 @@ __attribute__((visibility("default"))) int smx_debug_agg_path(const smx_params* 
     return SMX_OK;
 }
 
-// (dev / test hook, not in smx.h: the slices per walker launch of a fused call with these arguments -- agg_plan, the layout
-// aggregate_fused runs with -- on a workspace of ws_bytes that loses the worst case of 255 bytes to its 256-byte alignment;
-// forced as for smx_debug_agg_path; SMX_E_WS where the workspace holds no slice; the thread's knobs are not applied)
+// (dev / test hook, not in smx.h: the slices per walker launch, or per pass of the multi-kernel path, of a call with these
+// arguments -- agg_plan / multi_plan, the layout the call runs with -- on a workspace of ws_bytes that loses the worst case of
+// 255 bytes to its 256-byte alignment; forced as for smx_debug_agg_path; SMX_E_WS where the workspace holds no slice; the
+// thread's knobs are not applied)
 __attribute__((visibility("default"))) int smx_debug_agg_chunk(const smx_params* p, int w, int h, int nviews, int use_cost,
                                                                int own_q, int forced, uint64_t ws_bytes, int slices, int* chunk) {
     SMX_ARG(p && chunk && w >= 2 && h >= 1 && (nviews == 1 || nviews == 2) && forced >= 0 && forced <= 5 && p->radius >= 0 && slices >= 0);
     const char* why = nullptr;
     const int path = agg_path_for(p, w, h, nviews, use_cost != 0, forced, &why);
     if (!path) return fail(SMX_E_ARG, "smx_debug_agg_chunk: fused path %d forced but %s", forced, why);
-    if (path == 1) return fail(SMX_E_ARG, "smx_debug_agg_chunk: the call runs the multi-kernel path");
     AggOpts opt;
-    opt.walker = path == 2 ? 4 : path == 5 ? 5 : 0;
+    opt.take_path(path);
     AggLayout L;
-    const int rc = agg_plan(p, w, h, nviews, use_cost != 0, own_q != 0, opt, (size_t)ws_bytes, 255, slices, &L);
+    MultiLayout M;
+    const int rc = path == 1 ? multi_plan("smx_debug_agg_chunk", w, h, use_cost != 0, (size_t)ws_bytes, 255, slices, &M)
+                             : agg_plan(p, w, h, nviews, use_cost != 0, own_q != 0, opt, (size_t)ws_bytes, 255, slices, &L);
     if (rc) return rc;
-    *chunk = L.chunk;
+    *chunk = path == 1 ? M.chunk : L.chunk;
     return SMX_OK;
 }
 
@@ -399,100 +387,33 @@ int smx_dev_finish_pair(const smx_params* p, const int64_t* d_keys, int w, int h
     return rc;
 }
 
+// The tail of the five device entries: the kernels need the workspace on the current device; one timed call; the thread's path
+static int dev_aggregate(const AggCall& c) {
+    const int rc = check_same_device(c.ws, c.who);
+    if (rc) return rc;
+    stage_mark(ST_BEGIN, c.st);
+    return run_aggregation(c, g_agg_path);
+}
+
 // smx_dev_aggregate_wta and, with d_nbr != NULL (the view's state planes, smx_common.h nbr_merge), its _nbr form
-static int aggregate_wta_one(const char* who, const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
-                             const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
-                             int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
-                             size_t workspace_bytes, float* d_nbr, void* stream) {
+static int aggregate_view(const char* who, const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
+                          const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
+                          int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
+                          size_t workspace_bytes, float* d_nbr, void* stream) {
     SMX_ARG(p && d_guide && d_keys && d_workspace);
     SMX_ARG(d_cost || d_other);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
-    { int rcd = check_same_device(d_workspace, who); if (rcd) return rcd; }
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(ST_BEGIN, st);
-    // fused path (agg_path_for); cost built on the fly or read from d_cost
-    const char* why = nullptr;
-    const int path = agg_path_for(p, w, h, 1, d_cost != nullptr, g_agg_path, &why);
-    if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", who, g_agg_path, why);
-    if (path != 1) {
-        g_launches = 0;
-        int rc2 = fused_entry(path, p, 1, &d_guide, &d_other, &d_cost, w, h, &dmin, s_begin, s_end, &d_keys,
-                              &d_mean_u8, &d_agg, d_workspace, workspace_bytes, st, &g_launches, d_nbr ? &d_nbr : nullptr);
-        if (rc2) return rc2;
-        return SMX_OK;
-    }
-    g_last_path = 1;
-    if (g_keys_fresh) { int rk = launch_init_keys(d_keys, (int64_t)w * h, st); if (rk) return rk; }
-    const size_t pb = plane_bytes(w, h);
-    const int64_t n = (int64_t)w * h;
-    char* base = (char*)align_up((size_t)d_workspace, WS_ALIGN);
-    size_t avail = workspace_bytes > (size_t)(base - (char*)d_workspace) + WS_ALIGN
-                       ? workspace_bytes - (size_t)(base - (char*)d_workspace) - WS_ALIGN : 0;
-    if (avail >= pb * 10) {
-        // first 256 B: status word of the call (smx_dev_agg_status); this path cannot time out
-        SMX_HIP(hipMemsetAsync(base, 0, WS_ALIGN, st));
-        base += WS_ALIGN;
-    }
-    if (workspace_bytes < WS_ALIGN || avail < pb * 10)
-        return fail(SMX_E_WS, "%s: workspace %zu B < %zu B needed for one slice", who,
-                    workspace_bytes, smx_agg_workspace_bytes(w, h, 1));
-    const int per_slice = d_cost ? 4 : 5;
-    const int total = s_end - s_begin;
-    const size_t slice_b = (size_t)n * sizeof(float);
-    // largest chunk c with 5 guidance planes + per_slice volumes of c slices inside `avail`
-    size_t c_fit = (avail - 5 * pb) / per_slice / slice_b;
-    while (c_fit > 1 && 5 * pb + per_slice * align_up(c_fit * slice_b, WS_ALIGN) > avail) --c_fit;
-    int chunk = c_fit > (size_t)total ? total : (int)c_fit;
-    if (chunk < 1) chunk = 1;
-    float* im = (float*)(base + 0 * pb);
-    float* mean_im = (float*)(base + 1 * pb);
-    float* cinv = (float*)(base + 2 * pb);
-    float* g0 = (float*)(base + 3 * pb);
-    float* g1 = (float*)(base + 4 * pb);
-    char* cb = base + 5 * pb;
-    // chunk volumes are packed with plane stride n floats (kernels index planes as z*n)
-    const size_t vol = align_up((size_t)chunk * slice_b, WS_ALIGN);
-    float* T0 = (float*)(cb + 0 * vol);
-    float* T1 = (float*)(cb + 1 * vol);
-    float* A = (float*)(cb + 2 * vol);
-    float* B = (float*)(cb + 3 * vol);
-    float* C = d_cost ? nullptr : (float*)(cb + 4 * vol);
-
-    int rc;
-    g_launches = 0;
-    // guidance statistics (guidedFilter.cu:58-123)
-    if ((rc = launch_guid_prep(d_guide, im, g1, n, st))) return rc;
-    if ((rc = launch_integral(2, im, g1, g0, g1, w, h, 1, st))) return rc;
-    if ((rc = launch_guid_finish(p, g0, g1, mean_im, cinv, d_mean_u8, w, h, st))) return rc;
-    g_launches += 4;
-    stage_mark(ST_GUIDANCE, st);
-    // slice loop (guidedFilter.cu:171-238), `chunk` slices per pass
-    for (int s0 = s_begin; s0 < s_end; s0 += chunk) {
-        const int cnt = (s_end - s0) < chunk ? (s_end - s0) : chunk;
-        const float* cost = d_cost ? d_cost + (int64_t)(s0 - s_begin) * n : C;
-        if (!d_cost) {
-            if ((rc = launch_cost(p, d_guide, d_other, C, w, h, dmin + s0, cnt, st))) return rc;
-            ++g_launches;
-        }
-        if ((rc = launch_integral(1, cost, im, T0, T1, w, h, cnt, st))) return rc;
-        if ((rc = launch_ab(p, T0, T1, mean_im, cinv, A, B, w, h, cnt, st))) return rc;
-        if ((rc = launch_integral(2, A, B, A, B, w, h, cnt, st))) return rc;
-        float* agg = d_agg ? d_agg + (int64_t)(s0 - s_begin) * n : nullptr;
-        if (d_nbr) rc = launch_q_wta_nbr(p, A, B, im, d_keys, d_nbr, agg, w, h, cnt, s0, st);
-        else rc = launch_q_wta(p, A, B, im, d_keys, agg, w, h, cnt, s0, st);
-        if (rc) return rc;
-        g_launches += 6;
-        stage_mark(ST_WALK, st);      // (this path folds the WTA into its last pass)
-    }
-    return SMX_OK;
+    const AggCall c = {who, p, 1, {d_guide}, {d_other}, {d_cost}, {dmin}, {d_keys}, {d_mean_u8}, {d_agg}, {d_nbr},
+                       w, h, s_begin, s_end, d_workspace, workspace_bytes, (hipStream_t)stream};
+    return dev_aggregate(c);
 }
 
 int smx_dev_aggregate_wta(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
                           const float* d_cost, int w, int h, int dmin, int s_begin, int s_end,
                           int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
                           size_t workspace_bytes, void* stream) {
-    return aggregate_wta_one("smx_dev_aggregate_wta", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
-                             d_mean_u8, d_agg, d_workspace, workspace_bytes, nullptr, stream);
+    return aggregate_view("smx_dev_aggregate_wta", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
+                          d_mean_u8, d_agg, d_workspace, workspace_bytes, nullptr, stream);
 }
 
 int smx_dev_aggregate_wta_nbr(const smx_params* p, const uint8_t* d_guide, const uint8_t* d_other,
@@ -500,8 +421,8 @@ int smx_dev_aggregate_wta_nbr(const smx_params* p, const uint8_t* d_guide, const
                               int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
                               size_t workspace_bytes, float* d_nbr, void* stream) {
     SMX_ARG(d_nbr);
-    return aggregate_wta_one("smx_dev_aggregate_wta_nbr", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
-                             d_mean_u8, d_agg, d_workspace, workspace_bytes, d_nbr, stream);
+    return aggregate_view("smx_dev_aggregate_wta_nbr", p, d_guide, d_other, d_cost, w, h, dmin, s_begin, s_end, d_keys,
+                          d_mean_u8, d_agg, d_workspace, workspace_bytes, d_nbr, stream);
 }
 
 static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
@@ -511,37 +432,13 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
     SMX_ARG(p && d_left && d_right && d_keys && d_workspace);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
     SMX_ARG((d_cost_l != nullptr) == (d_cost_r != nullptr));
-    { int rcd = check_same_device(d_workspace, who); if (rcd) return rcd; }
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(ST_BEGIN, st);
     const int64_t n = (int64_t)w * h;
     const int64_t vol = n * (s_end - s_begin);
-    const char* why = nullptr;
-    const int path = agg_path_for(p, w, h, 2, d_cost_l != nullptr, g_agg_path, &why);
-    if (!path) return fail(SMX_E_ARG, "%s: fused path %d forced but %s", who, g_agg_path, why);
-    if (path != 1) {
-        const uint8_t* guide[2] = {d_left, d_right};
-        const uint8_t* other[2] = {d_right, d_left};
-        const float* cost[2] = {d_cost_l, d_cost_r};
-        const int dmin[2] = {dminl, dminr};
-        int64_t* keys[2] = {d_keys, d_keys + n};
-        uint8_t* mean[2] = {d_mean_u8, d_mean_u8 ? d_mean_u8 + n : nullptr};
-        float* agg[2] = {d_agg, d_agg ? d_agg + vol : nullptr};
-        float* nbr[2] = {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr};
-        g_launches = 0;
-        int rc2 = fused_entry(path, p, 2, guide, other, d_cost_l ? cost : nullptr, w, h, dmin, s_begin, s_end, keys,
-                              d_mean_u8 ? mean : nullptr, d_agg ? agg : nullptr, d_workspace,
-                              workspace_bytes, st, &g_launches, d_nbr ? nbr : nullptr);
-        if (rc2) return rc2;
-        return SMX_OK;
-    }
-    const char* one = d_nbr ? who : "smx_dev_aggregate_wta";
-    int rc = aggregate_wta_one(one, p, d_left, d_right, d_cost_l, w, h, dminl, s_begin, s_end, d_keys,
-                               d_mean_u8, d_agg, d_workspace, workspace_bytes, d_nbr, stream);
-    if (rc) return rc;
-    return aggregate_wta_one(one, p, d_right, d_left, d_cost_r, w, h, dminr, s_begin, s_end, d_keys + n,
-                             d_mean_u8 ? d_mean_u8 + n : nullptr, d_agg ? d_agg + vol : nullptr,
-                             d_workspace, workspace_bytes, d_nbr ? d_nbr + 3 * n : nullptr, stream);
+    const AggCall c = {who, p, 2, {d_left, d_right}, {d_right, d_left}, {d_cost_l, d_cost_r}, {dminl, dminr}, {d_keys, d_keys + n},
+                       {d_mean_u8, d_mean_u8 ? d_mean_u8 + n : nullptr}, {d_agg, d_agg ? d_agg + vol : nullptr},
+                       {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr},
+                       w, h, s_begin, s_end, d_workspace, workspace_bytes, (hipStream_t)stream};
+    return dev_aggregate(c);
 }
 
 int smx_dev_aggregate_wta_pair(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
@@ -880,10 +777,6 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     int rc;
     const int64_t nn = (int64_t)n;
     int64_t* keysL = c->keys.as<int64_t>(); int64_t* keysR = keysL + n;
-    const char* why = nullptr;
-    const int path = agg_path_for(p, w, h, 2, want_cost, c->agg_path, &why);
-    if (!path) return fail(SMX_E_ARG, "smx_ctx_stereo_pair: fused path %d forced but %s", c->agg_path, why);
-    struct Nest { Nest() { g_in_ctx += 2; } ~Nest() { g_in_ctx -= 2; } } nest;     // (nested smx_dev_* calls do not restart the stage marks)
     // cost volumes are materialised only when the caller asks for them (main.cu:80-82) and then feed
     // the aggregation like in the reference; otherwise the slices are built on the fly inside it.
     if (want_cost) {
@@ -891,34 +784,15 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
         if ((rc = smx_dev_cost_volume(p, dR, dL, c->costR.as<float>(), w, w, h, dminr, 0, size_d, st))) return rc;
     }
     if ((rc = smx_dev_init_keys(keysL, 2 * nn, st))) return rc;
-    // main.cu:133-134, both views per kernel launch
-    if (path != 1) {
-        const uint8_t* guide[2] = {dL, dR};
-        const uint8_t* other[2] = {dR, dL};
-        const float* cost[2] = {c->costL.as<float>(), c->costR.as<float>()};
-        const int dmin[2] = {dminl, dminr};
-        int64_t* kv[2] = {keysL, keysR};
-        uint8_t* mv[2] = {mean, mean + n};
-        float* av[2] = {c->aggLR.as<float>(), want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr};
-        float* nv[2] = {c->nbr.as<float>(), c->nbr.as<float>() + 3 * n};
-        g_launches = 0;
-        if ((rc = fused_entry(path, p, 2, guide, other, want_cost ? cost : nullptr, w, h, dmin, 0, size_d, kv, mv,
-                                  want_agg ? av : nullptr, c->ws.p, c->ws_bytes, st, &g_launches, subpix ? nv : nullptr)))
-            return rc;
-    } else {
-        const int saved = g_agg_path;
-        g_agg_path = 1;
-        if ((rc = aggregate_wta_one("smx_dev_aggregate_wta", p, dL, dR, want_cost ? c->costL.as<float>() : nullptr, w, h, dminl, 0,
-                                    size_d, keysL, mean, want_agg ? c->aggLR.as<float>() : nullptr, c->ws.p,
-                                    c->ws_bytes, subpix ? c->nbr.as<float>() : nullptr, st)))
-            { g_agg_path = saved; return rc; }
-        if ((rc = aggregate_wta_one("smx_dev_aggregate_wta", p, dR, dL, want_cost ? c->costR.as<float>() : nullptr, w, h, dminr, 0,
-                                    size_d, keysR, mean + n,
-                                    want_agg ? c->aggLR.as<float>() + (size_t)size_d * n : nullptr, c->ws.p,
-                                    c->ws_bytes, subpix ? c->nbr.as<float>() + 3 * n : nullptr, st)))
-            { g_agg_path = saved; return rc; }
-        g_agg_path = saved;
-    }
+    // main.cu:133-134, both views per call, on the context's own path
+    float* const costL = want_cost ? c->costL.as<float>() : nullptr;
+    float* const costR = want_cost ? c->costR.as<float>() : nullptr;
+    float* const aggL = want_agg ? c->aggLR.as<float>() : nullptr;
+    float* const nbrL = subpix ? c->nbr.as<float>() : nullptr;
+    const AggCall call = {"smx_ctx_stereo_pair", p, 2, {dL, dR}, {dR, dL}, {costL, costR}, {dminl, dminr}, {keysL, keysR},
+                          {mean, mean + n}, {aggL, want_agg ? aggL + (size_t)size_d * n : nullptr},
+                          {nbrL, subpix ? nbrL + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
+    if ((rc = run_aggregation(call, c->agg_path))) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
     if ((rc = smx_dev_finish_pair(p, keysL, w, h, dminl, dminr, dminl - 100, (float)dminl, bestL, mapL, occ, fil, st))) return rc;
     if (!subpix) return SMX_OK;

@@ -101,25 +101,26 @@ class PairPipeline:
         finally:
             self.lib.smx_set_keys_fresh(0)
 
+    def _aggregate_call(self, entry, *args):
+        """entry(params, *args, stream): an aggregation entry on this pipeline's device and its current stream, with
+        `slices_in_flight` as the calling thread's bound on the slices per launch for the time of the call."""
+        with self._on_device():
+            _lib.check(self.lib.smx_set_max_slices_per_launch(self.slices_in_flight))
+            try:
+                _lib.check(entry(C.byref(self.params), *args, self._stream()))
+            finally:
+                self.lib.smx_set_max_slices_per_launch(0)
+
     def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r):
         """Both views per launch from materialised cost volumes of this rank's slices (smx_dev_aggregate_wta_pair_cost):
         the reference's data flow, read p + write q."""
         self._guide = gray_l
-        with self._on_device():
-            L, P, st = self.lib, C.byref(self.params), self._stream()
-            _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
-            try:
-                if self.subpixel:
-                    _lib.check(L.smx_dev_aggregate_wta_pair_nbr(
-                        P, _dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr,
-                        self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes,
-                        _dp(self.nbr), st))
-                else:
-                    _lib.check(L.smx_dev_aggregate_wta_pair_cost(
-                        P, _dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr,
-                        self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
-            finally:
-                L.smx_set_max_slices_per_launch(0)
+        args = (_dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr, self.s_begin,
+                self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes)
+        if self.subpixel:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_nbr, *args, _dp(self.nbr))
+        else:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_cost, *args)
 
     def cost_volumes(self, gray_l, gray_r):
         """The two raw cost volumes of this rank's slices, resident in HBM (smx_dev_cost_volume; main.cu:80-82)."""
@@ -137,21 +138,13 @@ class PairPipeline:
     def aggregate_pair(self, gray_l, gray_r):
         """Both views per kernel launch (smx_dev_aggregate_wta_pair)."""
         self._guide = gray_l
-        with self._on_device():
-            L, P, st = self.lib, C.byref(self.params), self._stream()
-            _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
-            try:
-                if self.subpixel:
-                    _lib.check(L.smx_dev_aggregate_wta_pair_nbr(
-                        P, _dp(gray_l), _dp(gray_r), None, None, self.w, self.h, self.dminl, self.dminr, self.s_begin,
-                        self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes,
-                        _dp(self.nbr), st))
-                else:
-                    _lib.check(L.smx_dev_aggregate_wta_pair(
-                        P, _dp(gray_l), _dp(gray_r), self.w, self.h, self.dminl, self.dminr, self.s_begin,
-                        self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes, st))
-            finally:
-                L.smx_set_max_slices_per_launch(0)
+        args = (self.w, self.h, self.dminl, self.dminr, self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean),
+                _dp(self.agg), _dp(self.ws), self.ws_bytes)
+        if self.subpixel:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_nbr, _dp(gray_l), _dp(gray_r), None, None, *args,
+                                 _dp(self.nbr))
+        else:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair, _dp(gray_l), _dp(gray_r), *args)
 
     def init_keys(self):
         with self._on_device():
@@ -162,21 +155,12 @@ class PairPipeline:
         if view == 0:
             self._guide = guide
         agg = self.agg[view] if self.agg is not None else None
-        with self._on_device():
-            L, P, st = self.lib, C.byref(self.params), self._stream()
-            _lib.check(L.smx_set_max_slices_per_launch(self.slices_in_flight))
-            try:
-                if self.subpixel:
-                    _lib.check(L.smx_dev_aggregate_wta_nbr(
-                        P, _dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end,
-                        _dp(self.keys[view]), _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes,
-                        _dp(self.nbr[view]), st))
-                else:
-                    _lib.check(L.smx_dev_aggregate_wta(
-                        P, _dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end,
-                        _dp(self.keys[view]), _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes, st))
-            finally:
-                L.smx_set_max_slices_per_launch(0)
+        args = (_dp(guide), _dp(other), _dp(cost), self.w, self.h, dmin, self.s_begin, self.s_end, _dp(self.keys[view]),
+                _dp(self.mean[view]), _dp(agg), _dp(self.ws), self.ws_bytes)
+        if self.subpixel:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_nbr, *args, _dp(self.nbr[view]))
+        else:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta, *args)
 
     def last_chunk(self):
         """(slices per walker launch, walker launches) of this thread's last fused aggregation: what

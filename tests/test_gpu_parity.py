@@ -320,6 +320,40 @@ def test_radius_above_nine_uses_the_multi_kernel_path(orc):
     assert smx.lib().smx_last_agg_path() == 1
 
 
+def test_a_two_view_multi_kernel_call_is_one_timed_call():
+    """A pair call on the multi-kernel path is ONE call to the stage timing: cumulative timing counts a step once and its
+    stage times cover both views; the launches smx_last_agg_ms reports are those of both views, twice a one-view call's."""
+    import torch
+    from stereo_matching_cuda_amd._lib import StageMs
+    from stereo_matching_cuda_amd.device import PairPipeline
+    L = smx.lib()
+    w, h, D = 90, 70, 5
+    Il, Ir = (torch.from_numpy(a).cuda() for a in synth.gen_pair(w, h, D, 5))
+    pipe = PairPipeline(w, h, D, multi_kernel=True)
+    ms, launches = C.c_float(), C.c_int()
+    L.smx_set_agg_path(1)
+    try:
+        smx.check(L.smx_set_timing(2))
+        for _ in range(3):
+            pipe.run(Il, Ir)
+        t = StageMs()
+        smx.check(L.smx_stage_times(C.byref(t)))
+        assert L.smx_last_agg_path() == 1
+        assert (t.calls, t.dropped) == (3, 0) and t.guidance > 0 and t.aggregation > 0
+        smx.check(L.smx_set_timing(1))
+        pipe.init_keys()
+        pipe.aggregate_pair(Il, Ir)
+        smx.check(L.smx_last_agg_ms(C.byref(ms), C.byref(launches)))
+        pair = launches.value
+        pipe.aggregate_view(0, Il, Ir)
+        smx.check(L.smx_last_agg_ms(C.byref(ms), C.byref(launches)))
+        # (per view: 4 for the guidance, and 6 + 1 for the cost for the one chunk the workspace holds all slices of)
+        assert launches.value == 4 + 7 and pair == 2 * launches.value
+    finally:
+        L.smx_set_timing(0)
+        L.smx_set_agg_path(0)
+
+
 def test_default_path_is_the_fused_one(tsukuba_gray):
     import torch
     from stereo_matching_cuda_amd.device import PairPipeline
@@ -979,6 +1013,68 @@ def test_persistent_context_reuses_its_buffers(orc):
                     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (seed, key)
                 else:
                     assert np.array_equal(got, ref), (seed, key)
+    finally:
+        smx.check(L.smx_destroy(ctx))
+
+
+def _ctx_outbufs(n):
+    from stereo_matching_cuda_amd._lib import PairOut
+    bufs = {k: np.empty(n, np.float32) for k in ("best_l", "best_r", "dmap_l", "dmap_r", "occlusion", "filled")}
+    bufs.update({k: np.empty(n, np.uint8) for k in ("mean_l", "mean_r")})
+    out = PairOut()
+    for k, a in bufs.items():
+        setattr(out, k, a.ctypes.data)
+    return bufs, out
+
+
+def test_a_context_runs_its_own_path_whatever_the_threads(orc):
+    """smx_ctx_set_agg_path(c, 1) while the calling thread forces the comb walker: the context's pair runs the multi-kernel
+    path and equals the oracle; the thread's path is untouched -- its next smx_dev_aggregate_wta_pair runs the comb walker."""
+    import torch
+    from stereo_matching_cuda_amd.device import PairPipeline
+    L = smx.lib()
+    w, h, D = 150, 100, 7
+    Il, Ir = synth.gen_pair(w, h, D, 14)
+    want = orc.stereo_pair(Il, Ir, D)
+    params = smx.default_params()
+    ctx = C.c_void_p()
+    smx.check(L.smx_create(C.byref(params), w, h, D, C.byref(ctx)))
+    L.smx_set_agg_path(5)
+    try:
+        smx.check(L.smx_ctx_set_agg_path(ctx, 1))
+        bufs, out = _ctx_outbufs(w * h)
+        smx.check(L.smx_ctx_stereo_pair(ctx, Il.ctypes.data, Ir.ctypes.data, -(D - 1), 0, C.byref(out)))
+        assert L.smx_last_agg_path() == 1
+        for k, a in bufs.items():
+            _eq(a, np.asarray(want[k.replace("_", "")]).reshape(-1), k)
+        pipe = PairPipeline(w, h, D)
+        pipe.init_keys()
+        pipe.aggregate_pair(torch.from_numpy(Il).cuda(), torch.from_numpy(Ir).cuda())
+        assert L.smx_last_agg_path() == 5
+        pipe.finish()
+        r = pipe.results()
+        for k in KEYS:
+            _eq(r[k], want[k], k)
+    finally:
+        L.smx_set_agg_path(0)
+        smx.check(L.smx_destroy(ctx))
+
+
+def test_a_context_error_names_the_context_entry():
+    """A context forced to the comb walker at radius 12: SMX_E_ARG, reported under the entry that was called."""
+    L = smx.lib()
+    w, h, D = 64, 40, 3
+    Il, Ir = synth.gen_pair(w, h, D, 15)
+    params = smx.default_params()
+    params.radius = 12
+    ctx = C.c_void_p()
+    smx.check(L.smx_create(C.byref(params), w, h, D, C.byref(ctx)))
+    try:
+        smx.check(L.smx_ctx_set_agg_path(ctx, 5))
+        _, out = _ctx_outbufs(w * h)
+        assert L.smx_ctx_stereo_pair(ctx, Il.ctypes.data, Ir.ctypes.data, -(D - 1), 0, C.byref(out)) == -1
+        text = L.smx_last_error().decode()
+        assert text.startswith("smx_ctx_stereo_pair:") and "fused path 5 forced but radius > 9" in text, text
     finally:
         smx.check(L.smx_destroy(ctx))
 
