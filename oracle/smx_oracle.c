@@ -9,9 +9,15 @@
  * Pinning: the restatement is checked (tests/test_oracle_golden.py) against the
  * 12 output images the reference's authors committed next to their two Tsukuba
  * inputs (reference stereo_matching_cuda/data/ *.png, copied as data fixtures to
- * tests/golden/), and against the sha256 manifest of raw f32/u8 dumps recorded in
- * SURVEY.md Appendix C.  The reference itself is CUDA-only (needs cuda_runtime.h
- * and nvcc, neither in this image), so no oracle/_ref build exists.
+ * tests/golden/), and (tests/test_oracle_ref.py) against the reference's own code:
+ * oracle/ref_build.py compiles the reference as host programs, one per set of its
+ * macros, behind a stand-in for the CUDA runtime (oracle/ref_shim, oracle/ref_driver.cpp;
+ * into oracle/_ref/, git-ignored) and records what they compute for every case of
+ * oracle/ref_cases.py -- radii 0..12, other eps / alpha / thresholds / d_lr, other
+ * disparity ranges, images smaller than the window, presets and ties, the fill's
+ * non-integer maps -- in tests/golden/ref_cases/.  The Tsukuba case of that table
+ * reproduces the sha256 manifest of SURVEY.md Appendix C.  oracle/REF_CASES.md says
+ * which kernels that pins and which cases the reference has no defined answer for.
  *
  * Arithmetic contract: IEEE f32, every operation rounded
  * individually in source order, no FMA contraction -> build with
