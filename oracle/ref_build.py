@@ -7,7 +7,9 @@ directory is absent this script prints one line and succeeds, leaving an existin
 Per macro set of the case table (ref_cases.VARIANTS):
   1. copy the six translation units behind the five pinned host functions (costVolume, guidedFilter, helpers, integral,
      occlusion, rgb_to_grayscale: .cu), every .cuh and SystemIncludes.h to oracle/_ref/src_<variant>/.  main.cu, filter.cu
-     (dead code with shared-memory tile kernels), the stb headers and the images are not copied;
+     (dead code with shared-memory tile kernels), the stb headers and the images are not copied.  Of main.cu only the text
+     of write_mat (main.cu:13-35, the float -> 8-bit normaliser in front of the PNG writer) is cut out into a unit of its own,
+     write_mat.cu, behind the stbi_write_png stand-in of oracle/ref_shim/stb_image_write.h;
   2. rewrite every `kernel<<<grid, block>>>(args);` to `LAUNCH(kernel, grid, block, args);` (oracle/ref_shim/cuda_runtime.h:
      serial thread loop, refused for every kernel not known to be exact under it -- the list is in that header);
   3. rewrite the #define lines of SystemIncludes.h to the macro set;
@@ -44,11 +46,12 @@ REF = os.path.join(HERE, "_ref")
 FIXTURES = os.path.join(ROOT, "tests", "golden", "ref_cases")
 UNITS = ("costVolume", "guidedFilter", "helpers", "integral", "occlusion", "rgb_to_grayscale")
 RECIPE = ("ref_build.py", "ref_cases.py", "ref_driver.cpp", "ref_shim/cuda_runtime.h", "ref_shim/device_launch_parameters.h",
-          "ref_shim/shim.cpp")
+          "ref_shim/shim.cpp", "ref_shim/stb_image_write.h")
+WRITE_MAT_RE = re.compile(r"^void write_mat\([^)]*\) \{\n.*?^\}\n", re.M | re.S)
 JOBS = min(16, os.cpu_count() or 1)
 FLAGS = ["-ffp-contract=off", "-fno-fast-math", "-w", "-std=c++14"]
 FLAVOURS = {"": ["-O2"], "_san": ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                                  "-fno-sanitize-recover=all"]}
+                                  "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all"]}
 # Two reports of AddressSanitizer that are neither an access out of bounds nor an overflow are switched off, on every case alike:
 # integralOnCPU frees a new[] block with free() (integral.cu:94, :118: alloc-dealloc-mismatch), and detect_occlusion never
 # frees two host buffers (occlusion.cu:21-22: leak).
@@ -66,6 +69,14 @@ def _reference_files(ref):
     return sorted(f for f in os.listdir(ref) if f.endswith(".cuh") or f == "SystemIncludes.h" or f[:-3] in UNITS and f.endswith(".cu"))
 
 
+def _write_mat_unit(ref):
+    """write_mat of main.cu as a translation unit: the function's own text between two lines of ours."""
+    text = open(os.path.join(ref, "main.cu"), encoding="utf-8", errors="surrogateescape").read()
+    found = WRITE_MAT_RE.findall(text)
+    assert len(found) == 1 and "main(" not in found[0] and found[0].count("stbi_write_png(") == 1, found
+    return '#include <cstdlib>\n#include <cstring>\n#include "stb_image_write.h"\n\n' + found[0]
+
+
 def stamp_of(ref):
     h = hashlib.sha256()
     for f in RECIPE:
@@ -73,6 +84,7 @@ def stamp_of(ref):
     for f in _reference_files(ref):
         h.update(f.encode())
         h.update(open(os.path.join(ref, f), "rb").read())
+    h.update(_write_mat_unit(ref).encode("utf-8", errors="surrogateescape"))
     h.update(open(os.path.join(ROOT, "tests", "golden", "tsukuba_golden.npz"), "rb").read())
     return h.hexdigest()
 
@@ -107,6 +119,8 @@ def _prepare_sources(ref, name, m):
                 assert k == 1, (key, k)
         with open(os.path.join(src, f), "w", encoding="utf-8", errors="surrogateescape") as out:
             out.write(text)
+    with open(os.path.join(src, "write_mat.cu"), "w", encoding="utf-8", errors="surrogateescape") as out:
+        out.write(_write_mat_unit(ref))
     return src
 
 
@@ -129,7 +143,7 @@ def build_programs(ref, pool):
         src = _prepare_sources(ref, name, m)
         for flavour, flags in FLAVOURS.items():
             objs = []
-            units = [os.path.join(src, u + ".cu") for u in UNITS] + [os.path.join(HERE, "ref_driver.cpp"),
+            units = [os.path.join(src, u + ".cu") for u in UNITS + ("write_mat",)] + [os.path.join(HERE, "ref_driver.cpp"),
                                                                      os.path.join(HERE, "ref_shim", "shim.cpp")]
             for u in units:
                 o = os.path.join(src, os.path.basename(u) + flavour + ".o")

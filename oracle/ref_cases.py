@@ -4,7 +4,7 @@ oracle/ref_build.py builds the reference once per distinct macro set of this tab
 `inputs(case)`, runs the reference and records the results (tests/golden/ref_cases/<name>.npz).  The tests import this module
 to regenerate the identical inputs: nothing here reads the reference or oracle/_ref.
 
-A case: name, macros (the #define lines of SystemIncludes.h it is built with), mode (pair / gf / occ / gray, the modes of
+A case: name, macros (the #define lines of SystemIncludes.h it is built with), mode (pair / gf / occ / gray / wm, the modes of
 oracle/ref_driver.cpp), w, h, seed, recipe and what the recipe needs.  `axes` names the axis values of the issue a case stands
 for; oracle/REF_CASES.md is checked against it.
 """
@@ -58,6 +58,11 @@ M_EPS100 = macros(EPS=100.0)
 M_A05 = macros(ALPHA=0.5)
 M_TH20 = macros(TH_color=20, TH_grad=5)
 M_LR2 = macros(D_LR=2)
+# ranges the command line of smx_main can ask for and no other set has: one that does not end at zero, one that crosses
+# zero (its right view starts at -6, its positive-disparity outputs hold negative values), one with a single label
+M_NZ = macros(D_MIN=-40, D_MAX=-6)
+M_X0 = macros(D_MIN=-5, D_MAX=6)
+M_ONE = macros(D_MIN=-4, D_MAX=-4)
 
 CASES = []
 
@@ -101,6 +106,23 @@ for _tag, _m in (("r9", M_DEF), ("r0", M_R0), ("r3", M_R3), ("r12", M_R12)):
 for _tag, _m in (("r1", M_R1), ("r4", M_R4), ("r5", M_R5)):
     _case(f"{_tag}_20x20", _m, "pair", 20, 20, 400 + _m["RADIUS"], "shift", (f"radius={_m['RADIUS']}", "shape=20x20"))
 
+# RGB(A) pairs for the drop-in main (tests/test_gpu_main_cases.py): smx_main converts RGB itself and takes only the range
+# from its command line, so every other macro is at its default.  `shift`: columns the right view is moved by, one value per
+# horizontal band of the image (the true left disparity of a band is -shift).  The seeds of the two smallest cases were searched
+# for what tests/test_gpu_main_cases.py asserts of the recordings: cli_2x1 has one occluded pixel and two labels per view, and
+# slice 0 of cli_19x40's right cost volume has its smallest value in its first pixel alone (a wrapped 8-bit level)
+for _name, _m, _w, _h, _ch, _seed, _shift, _extra in (
+        ("cli_d70_129x70", M_D70, 129, 70, 3, 500, (9, 31), {}),
+        ("cli_r9_210x150", M_R9, 210, 150, 4, 501, (9, 17), {}),
+        ("cli_19x40", M_DEF, 19, 40, 3, 2690, (6, 2), {}),
+        ("cli_2x1", M_DEF, 2, 1, 3, 24, (1,), {}),
+        ("cli_kitti_1242x375", M_KITTI, 1242, 375, 3, 504, (9, 25), {"hash_only": ("bestl", "bestr")}),
+        ("cli_nz_210x150", M_NZ, 210, 150, 3, 505, (9, 30), {}),
+        ("cli_x0_210x150", M_X0, 210, 150, 3, 506, (3, -4), {}),
+        ("cli_one_64x9", M_ONE, 64, 9, 3, 507, (4,), {})):
+    _case(_name, _m, "pair", _w, _h, _seed, "rgb", (f"range=({_m['D_MIN']},{_m['D_MAX']})", f"shape={_w}x{_h}",
+                                                    f"cli=RGB input, {_ch} channels"), channels=_ch, shift=_shift, **_extra)
+
 # ---- gf mode: compute_guided_filter on a supplied volume with supplied presets ------------------------------------------
 _case("gf_fresh", M_DEF, "gf", 45, 37, 11, "gf_random", ("gf=fresh presets",), size_d=6, dmin=-5)
 _case("gf_inout", M_DEF, "gf", 45, 37, 11, "gf_inout", ("gf=presets below some q", "gf=ties with the preset on alternate rows"),
@@ -124,6 +146,15 @@ for _tag, _m in (("dlr0", M_DEF), ("dlr1", M_R1), ("dlr2", M_R4)):
 _case("gray_lattice", M_DEF, "gray", 52 ** 3, 1, 0, "gray_lattice", ("gray=5-step lattice",), channels=3)
 _case("gray_rgba", M_DEF, "gray", 65, 33, 5, "gray_random", ("gray=4 channels",), channels=4)
 
+# ---- wm mode: write_mat, the float -> 8-bit normaliser in front of the PNG writer (main.cu:13-35) --------------------------
+# Its minimum skips every element that raises the running maximum (`else if`, main.cu:22), so what it does depends on the
+# order of the values, not only on their range.
+for _recipe, _what in (("wm_random", "random map"), ("wm_first_min", "first element is the global minimum (a negative level wraps)"),
+                       ("wm_increasing", "strictly increasing (min stays 150000000)"), ("wm_decreasing", "strictly decreasing"),
+                       ("wm_two_valued", "two values"), ("wm_occlusion", "integer labels with the d_lo - 100 sentinel scattered"),
+                       ("wm_constant", "constant map")):
+    _case(_recipe, M_DEF, "wm", 331, 1, 600, _recipe, (f"wm={_what}",))
+
 BY_NAME = {c["name"]: c for c in CASES}
 VARIANTS = {}
 for _c in CASES:
@@ -137,6 +168,19 @@ def _pair_images(c):
     if c["recipe"] == "tsukuba":
         g = np.load(os.path.join(_ROOT, "tests", "golden", "tsukuba_golden.npz"))
         return g["tsukuba0"], g["tsukuba1"]
+    if c["recipe"] == "rgb":
+        # every channel is noise of its own; the right view is the left one moved by shift[b] columns in band b; with four
+        # channels the alpha of each view is noise too (the conversion must ignore it)
+        shifts = c["shift"]
+        pad = max(abs(s) for s in shifts)
+        base = rng.integers(0, 256, size=(h, w + 2 * pad, 3), dtype=np.uint8)
+        left = base[:, pad:pad + w]
+        right = np.empty_like(left)
+        for rows, s in zip(np.array_split(np.arange(h), len(shifts)), shifts):
+            right[rows] = base[rows, pad + s:pad + s + w]
+        if c["channels"] == 4:
+            left, right = (np.concatenate([v, rng.integers(0, 256, size=(h, w, 1), dtype=np.uint8)], -1) for v in (left, right))
+        return np.ascontiguousarray(left), np.ascontiguousarray(right)
     if c["recipe"] == "noise":
         return (rng.integers(0, 256, size=(h, w), dtype=np.uint8), rng.integers(0, 256, size=(h, w), dtype=np.uint8))
     # "shift": the right view is the left one moved by `shift` columns, so the true disparity lies inside every range that
@@ -201,6 +245,26 @@ def inputs(c, needs=None):
         half = rng.random((h, w)) < 0.25                    # abs(d + dR) compares in float: halves sit between the d_lr steps
         dr[half] += np.float32(0.5)
         return {"dl": dl, "dr": dr}
+    if mode == "wm":
+        n = w * h
+        if recipe == "wm_constant":
+            return {"mat": np.full(n, -7.0, np.float32)}
+        if recipe == "wm_two_valued":
+            return {"mat": np.where(rng.random(n) < 0.5, np.float32(-3.5), np.float32(12.25)).astype(np.float32)}
+        if recipe == "wm_occlusion":                        # an occlusion map of the default range: labels -15..0, sentinel -115
+            mat = rng.integers(-15, 1, size=n).astype(np.float32)
+            mat[rng.random(n) < 0.2] = -115.0
+            return {"mat": mat}
+        mat = (rng.standard_normal(n) * 100.0).astype(np.float32)
+        if recipe == "wm_first_min":
+            mat[0] = mat.min() - np.float32(40.0)
+        elif recipe in ("wm_increasing", "wm_decreasing"):
+            mat = np.unique(mat)                            # sorted, no two equal
+            mat = np.ascontiguousarray(mat if recipe == "wm_increasing" else mat[::-1])
+            assert mat.size == n
+        else:
+            assert recipe == "wm_random", recipe
+        return {"mat": mat}
     assert mode == "gray"
     if recipe == "gray_lattice":                            # every (r, g, b) on a 5-step lattice, incl. sums that land on integers
         v = np.arange(0, 256, 5, dtype=np.uint8)
@@ -217,6 +281,8 @@ def driver_args(c):
         return [w, h, c["size_d"], c["dmin"]]
     if c["mode"] == "occ":
         return [w, h, c["d_occlusion"], c["vmin"]]
+    if c["mode"] == "wm":
+        return [w * h]
     return [w * h, c["channels"]]
 
 
@@ -233,6 +299,7 @@ OUTPUTS = {
            "mean": ("mean.u8", np.uint8, False), "agg": ("agg.f32", np.float32, True)},
     "occ": {"occlusion": ("occlusion.f32", np.float32, False), "filled": ("filled.f32", np.float32, False)},
     "gray": {"gray": ("gray.u8", np.uint8, False)},
+    "wm": {"u8": ("mat.u8", np.uint8, False)},
 }
 
 

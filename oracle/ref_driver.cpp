@@ -3,7 +3,8 @@
  *
  * oracle/ref_build.py compiles it against a temporary copy of the reference (one build per set of the macros of
  * SystemIncludes.h) and the host stand-in of oracle/ref_shim.  It reads raw little-endian arrays from a directory, calls
- * rgb_to_grayscale / compute_cost / compute_guided_filter / detect_occlusion / fill_occlusion, and writes raw arrays back.
+ * rgb_to_grayscale / compute_cost / compute_guided_filter / detect_occlusion / fill_occlusion / write_mat, and writes raw arrays
+ * back.
  *
  *   ref_<variant> pair <dir> <w> <h> [channels]
  *       in : left.u8 right.u8          gray [h][w], or interleaved RGB(A) when channels is 3 or 4
@@ -17,6 +18,8 @@
  *       out: occlusion.f32 (only with dr.f32), filled.f32
  *   ref_<variant> gray <dir> <n> <channels>
  *       in : rgb.u8      out: gray.u8
+ *   ref_<variant> wm <dir> <n>
+ *       in : mat.f32     out: mat.u8   (the bytes write_mat hands to the PNG writer, main.cu:32)
  */
 #include "rgb_to_grayscale.cuh"
 #include "costVolume.cuh"
@@ -25,6 +28,9 @@
 
 #include <string>
 #include <vector>
+
+/* main.cu:13 -- no header of the reference declares it; ref_build.py cuts its text into a unit of its own */
+void write_mat(float* mat, const char* filename, int w, int h, int start);
 
 static std::string g_dir;
 
@@ -157,8 +163,17 @@ static int run_gray(int n, int channels) {
     return 0;
 }
 
+static int run_wm(int n) {
+    float* mat = slurp<float>("mat.f32", n);
+    capture_to("mat.u8");
+    write_mat(mat, "mat.u8", n, 1, 0);
+    capture_to(nullptr);
+    free(mat);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 5) { fprintf(stderr, "usage: %s pair|gf|occ|gray <dir> ...\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s pair|gf|occ|gray|wm <dir> ...\n", argv[0]); return 2; }
     const std::string mode = argv[1];
     g_dir = argv[2];
     std::vector<double> a;
@@ -167,6 +182,7 @@ int main(int argc, char** argv) {
     if (mode == "gf" && a.size() == 4) return run_gf((int)a[0], (int)a[1], (int)a[2], (int)a[3]);
     if (mode == "occ" && a.size() == 4) return run_occ((int)a[0], (int)a[1], (int)a[2], (float)a[3]);
     if (mode == "gray" && a.size() == 2) return run_gray((int)a[0], (int)a[1]);
+    if (mode == "wm" && a.size() == 1) return run_wm((int)a[0]);
     fprintf(stderr, "ref_driver: bad arguments for mode %s\n", mode.c_str());
     return 2;
 }

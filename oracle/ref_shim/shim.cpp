@@ -1,5 +1,6 @@
 /* Definitions for oracle/ref_shim/cuda_runtime.h (host stand-in for the CUDA runtime; test infrastructure). */
 #include "cuda_runtime.h"
+#include "stb_image_write.h"
 
 thread_local ref_uint3 threadIdx, blockIdx;
 thread_local dim3 blockDim, gridDim;
@@ -28,4 +29,9 @@ void ref_capture_q(const float* q, int n) {
         fprintf(stderr, "ref_shim: short write of an aggregated plane\n");
         abort();
     }
+}
+
+int stbi_write_png(const char*, int w, int h, int comp, const void* data, int) {
+    const size_t bytes = (size_t)w * h * comp;
+    return ref_capture_file && fwrite(data, 1, bytes, ref_capture_file) == bytes;
 }

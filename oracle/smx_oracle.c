@@ -290,12 +290,18 @@ ORC_API void orc_fill_occlusion(float* disp, int w, int h, float vMin) {
 }
 
 /* ---- main.cu:13-35 (write_mat) : min/max normalisation to u8 --------------
- * Note the `else if`: min is only updated by elements that did not raise max. */
+ * Note the `else if`: min is only updated by elements that did not raise max.
+ * A map with max == min (a constant one) has no defined image in the reference; all zeros here, like
+ * normalise_like_reference (host/helpers.cuh) and smx.write_mat. */
 ORC_API void orc_write_mat_u8(const float* mat, uint8_t* out, int64_t n) {
     float max = -150000000.0f, min = 150000000.0f;
     for (int64_t i = 0; i < n; ++i) {
         if (mat[i] > max) max = mat[i];
         else if (mat[i] <= min) min = mat[i];
+    }
+    if (max == min) {                   /* 0/0 or x/0 converted to int in the reference: undefined.  Defined here as zeros */
+        memset(out, 0, (size_t)n);
+        return;
     }
     for (int64_t i = 0; i < n; ++i) {
         int c = (mat[i] - min) * 255.0f / (max - min);

@@ -2,7 +2,7 @@
 // Same stage order, same progress lines on stdout, same 12 output images, and every stage goes
 // through the reference-named host functions of this directory (which forward to the HIP kernels
 // behind include/smx.h).  The code itself is organised differently: buffers are std::vectors, the
-// outputs are table driven, and the image normaliser is a two-pass restatement of write_mat.
+// outputs are table driven, and the image normaliser (helpers.cuh) is a two-pass restatement of write_mat.
 //
 //   smx_main                         reference behaviour: ./data/tsukuba0.png, ./data/tsukuba1.png,
 //                                    D_MIN..D_MAX from the macros, outputs into ./data/
@@ -53,26 +53,6 @@
 #include "wmf.cuh"
 
 namespace {
-
-// Float map -> 8-bit image exactly like the reference's write_mat (main.cu:13-35): the maximum is
-// the true maximum, but the minimum only considers elements that did NOT raise the running maximum
-// at their position (the reference's `else if`); values map through (v - min) * 255 / (max - min)
-// in f32 and are truncated.
-std::vector<unsigned char> normalise_like_reference(const float* v, size_t n) {
-    float hi = -150000000.0f, lo = 150000000.0f;
-    for (size_t i = 0; i < n; ++i) {
-        const bool raises_max = v[i] > hi;
-        if (raises_max) hi = v[i];
-        if (!raises_max && v[i] <= lo) lo = v[i];
-    }
-    std::vector<unsigned char> out(n);
-    const float span = hi - lo;
-    for (size_t i = 0; i < n; ++i) {
-        const int level = (v[i] - lo) * 255.0f / span;
-        out[i] = (unsigned char)level;
-    }
-    return out;
-}
 
 struct Pair {
     int w = 0, h = 0;

@@ -187,7 +187,9 @@ def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, wa
 
 def write_mat(mat):
     """Host-side float -> u8 normaliser of main.cu:13-35 (PNG writer input).  The reference's
-    loop only lowers `min` on elements that did not raise `max` (`else if`, main.cu:22)."""
+    loop only lowers `min` on elements that did not raise `max` (`else if`, main.cu:22).
+    A map with max == min (a constant one) divides by zero there and converts the result to int, which defines nothing:
+    it is all zeros here, like normalise_like_reference (host/helpers.cuh) and orc_write_mat_u8."""
     m = np.ascontiguousarray(mat, dtype=np.float32).ravel()
     prev = np.concatenate(([np.float32(-150000000.0)], np.maximum.accumulate(m)[:-1]))
     prev = np.maximum(prev, np.float32(-150000000.0))
@@ -197,5 +199,7 @@ def write_mat(mat):
     mn = np.float32(150000000.0)
     if rest.size:
         mn = min(mn, rest.min())
+    if mx == mn:
+        return np.zeros(np.shape(mat), np.uint8)
     c = ((m - np.float32(mn)) * np.float32(255.0) / np.float32(mx - mn)).astype(np.float32)
     return c.astype(np.int32).astype(np.uint8).reshape(np.shape(mat))

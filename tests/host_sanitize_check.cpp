@@ -2,12 +2,16 @@
 // tests/test_host_mirror.py::test_host_layer_and_oracle_under_sanitizers on the CPU only:
 //   * the CPU twins of stereo_matching_cuda_amd/host/cpu_twins.cpp against the oracle (oracle/smx_oracle.c,
 //     compiled into this program with the same sanitizers) on a small seeded pair, bit for bit;
-//   * the PNG reader / writers of host/png_io.cpp on well-formed and malformed files given on the command line.
+//   * the PNG reader / writers of host/png_io.cpp on well-formed and malformed files given on the command line;
+//   * normalise_like_reference (host/helpers.cuh) on the maps listed in <dir>/wm/list.txt: <name>.f32 in, <name>.u8 the
+//     bytes the reference's write_mat handed to its PNG writer (tests/golden/ref_cases/wm_*.npz), byte for byte.
 // No GPU and no libsmx_hip.so: the one symbol the twins need from the host layer (smx_config) is defined here.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <vector>
 
 #include "costVolume.cuh"
@@ -45,6 +49,7 @@ void orc_guided_filter(const orc_params* P, const uint8_t* I, const float* cost,
                        float* agg, int w, int h, int dmin, int s_begin, int s_end);
 void orc_detect_occlusion(const orc_params* P, float* dL, const float* dR, int dOcc, int w, int h);
 void orc_fill_occlusion(float* disp, int w, int h, float vMin);
+void orc_write_mat_u8(const float* mat, uint8_t* out, int64_t n);
 }
 
 static int fails = 0;
@@ -120,6 +125,22 @@ int main(int argc, char** argv) {
         if (!smx_png_write_gray16(f16.c_str(), w, h, d16.data()) || !smx_pfm_write(fp.c_str(), w, h, S.data())) {
             std::printf("MISMATCH png16 / pfm write\n");
             ++fails;
+        }
+        std::ifstream list(dir + "/wm/list.txt");
+        for (std::string name; list >> name;) {
+            std::ifstream fin(dir + "/wm/" + name + ".f32", std::ios::binary), fwant(dir + "/wm/" + name + ".u8", std::ios::binary);
+            const std::vector<char> raw((std::istreambuf_iterator<char>(fin)), std::istreambuf_iterator<char>());
+            const std::vector<char> want((std::istreambuf_iterator<char>(fwant)), std::istreambuf_iterator<char>());
+            std::vector<float> mat(raw.size() / 4);
+            std::memcpy(mat.data(), raw.data(), mat.size() * 4);
+            const std::vector<unsigned char> got = normalise_like_reference(mat.data(), mat.size());
+            if (mat.empty() || got.size() != want.size()) { std::printf("MISMATCH write_mat %s (sizes)\n", name.c_str()); ++fails; }
+            else {
+                same(("write_mat " + name).c_str(), got.data(), want.data(), got.size());
+                std::vector<unsigned char> ogot(mat.size(), 0xAA);
+                orc_write_mat_u8(mat.data(), ogot.data(), (int64_t)mat.size());
+                same(("oracle write_mat " + name).c_str(), ogot.data(), want.data(), ogot.size());
+            }
         }
         for (int a = 2; a < argc; ++a) {      // malformed files: must be rejected (or loaded) without any report
             int mw, mh, mc;

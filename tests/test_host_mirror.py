@@ -287,10 +287,40 @@ def test_png_reader_rejects_malformed_files(tmp_path):
         assert out.returncode == 0 and out.stdout.strip() == want, (name, out.stdout, out.stderr)
 
 
+def _write_mat_cases():
+    """{name: (map f32, the 8-bit image expected of it)}: every kept wm case of oracle/ref_cases.py with what the reference's
+    own write_mat made of it, and the constant map, which the reference defines nothing for (oracle/REF_CASES.md) and the
+    project defines as all zeros."""
+    import ref_fixtures as rf
+    from oracle import ref_cases as rc
+    out = {}
+    for name in rf.names("wm"):
+        c, fx = rf.load(name)
+        out[name] = (rf.inputs(c)["mat"], fx["u8"].ravel())
+    mat = rc.inputs(rc.BY_NAME["wm_constant"])["mat"]
+    assert "wm_constant" not in out and mat.size > 1 and mat.min() == mat.max()
+    out["wm_constant"] = (mat, np.zeros(mat.size, np.uint8))
+    return out
+
+
+def test_the_three_normalisers_give_the_reference_bytes(orc):
+    """smx.write_mat and oracle.write_mat_u8 on every map of _write_mat_cases, byte for byte (normalise_like_reference of
+    host/helpers.cuh and the oracle's C function run on the same maps in the sanitizer test below)."""
+    import stereo_matching_cuda_amd as smx
+    for name, (mat, want) in _write_mat_cases().items():
+        for what, fn in (("smx.write_mat", smx.write_mat), ("oracle.write_mat_u8", orc.write_mat_u8)):
+            got = fn(mat)
+            assert got.dtype == np.uint8 and got.tobytes() == want.tobytes(), (name, what)
+            assert fn(mat.reshape(1, -1)).shape == (1, mat.size)
+
+
 def test_host_layer_and_oracle_under_sanitizers(tmp_path):
     """SURVEY 5 (sanitizers): the CPU twins of host/cpu_twins.cpp, the PNG / PFM code of host/png_io.cpp and the
     oracle, all compiled with -fsanitize=address,undefined (-fno-sanitize-recover): the twins equal the oracle
     bit for bit on a seeded pair, the PNG reader survives malformed files, and no sanitizer report appears.
+    The float -> 8-bit normaliser of host/helpers.cuh runs there on every recorded map of the reference's write_mat
+    (tests/golden/ref_cases/wm_*.npz) and on the constant map the reference defines nothing for (all zeros here), and
+    smx.write_mat and the oracle's write_mat_u8 are held to the same bytes.
     CPU only (no GPU sanitizer runs on this pool)."""
     import shutil
     import struct
@@ -300,6 +330,7 @@ def test_host_layer_and_oracle_under_sanitizers(tmp_path):
     exe = str(tmp_path / "sanitize_check")
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
     obj = str(tmp_path / "oracle.o")
+    san.append("-fsanitize=float-cast-overflow")          # (not part of `undefined`: NaN or an infinity converted to int)
     subprocess.check_call(["gcc", "-O1", "-ffp-contract=off", "-c", os.path.join(ROOT, "oracle", "smx_oracle.c"), "-o", obj] + san)
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + HOST,
                            os.path.join(ROOT, "tests", "host_sanitize_check.cpp"), os.path.join(HOST, "cpu_twins.cpp"),
@@ -326,6 +357,13 @@ def test_host_layer_and_oracle_under_sanitizers(tmp_path):
     for name, (blob, _) in cases.items():
         (tmp_path / name).write_bytes(blob)
         files.append(str(tmp_path / name))
+    wm = _write_mat_cases()
+    assert len(wm) >= 7 and "wm_constant" in wm
+    (tmp_path / "wm").mkdir()
+    (tmp_path / "wm" / "list.txt").write_text("\n".join(wm) + "\n")
+    for name, (mat, want) in wm.items():
+        mat.tofile(tmp_path / "wm" / (name + ".f32"))
+        want.tofile(tmp_path / "wm" / (name + ".u8"))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe, str(tmp_path)] + files, capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -336,6 +374,8 @@ def test_host_layer_and_oracle_under_sanitizers(tmp_path):
     for name, (_, want) in cases.items():
         if want:
             assert f"{want} {tmp_path / name}" in r.stdout, (name, r.stdout)
+    for name in wm:
+        assert f"ok write_mat {name}\n" in r.stdout and f"ok oracle write_mat {name}\n" in r.stdout, (name, r.stdout)
 
 
 @pytest.mark.gpu

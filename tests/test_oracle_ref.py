@@ -56,6 +56,8 @@ def run_oracle(orc, c, inp):
             d = r["occlusion"] = orc.detect_occlusion(d, inp["dr"], c["d_occlusion"], params=p)
         r["filled"] = orc.fill_occlusion(d, c["vmin"])
         return r
+    if c["mode"] == "wm":
+        return {"u8": orc.write_mat_u8(inp["mat"].reshape(c["h"], c["w"]))}
     return {"gray": orc.gray(inp["rgb"].reshape(c["h"], c["w"], c["channels"]), params=p)}
 
 
