@@ -368,6 +368,51 @@ int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const flo
 int smx_dev_weighted_median(const smx_wmf_params* p, const uint8_t* d_guide, const float* d_disp,
                             const float* d_select, float* d_out, int w, int h, int dmin, int size_d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Census / Hamming matching cost (not a stage of the reference; opt-in alternative to compute_cost)
+ * ---------------------------------------------------------------------------------- */
+
+/* The census transform (Zabih & Woodfill) with a Hamming-distance cost.  It depends only on the ORDER of the gray values
+ * in a window, so a strictly increasing change of one image's intensities (exposure, gain) leaves the volume untouched.
+ * Defaults: rx 4, ry 3 (a 9 x 7 window, 62 bits), th 62.  Valid: 1 <= rx <= 4, 1 <= ry <= 3, th >= 1.
+ *   code  of pixel (y, x) of image I: a uint64_t.  The window's neighbours are numbered k = 0, 1, ... with dy = -ry .. ry in
+ *         the outer loop and dx = -rx .. rx in the inner one, the centre skipped; bit k (bit 0 = LSB) is set iff
+ *         I[clamp(y + dy, 0, h - 1)][clamp(x + dx, 0, w - 1)] < I[y][x].  (Replicate clamp: an image smaller than the
+ *         window is legal.)  nbits = (2 rx + 1)(2 ry + 1) - 1 <= 62.
+ *   cost  of view v, slice z: own = the view's codes, other = the other view's, d = dmin_v + z, t = min(th, nbits):
+ *         cost[z][y][x] = (float)min(popcount(own[y][x] ^ other[y][x + d]), t) if 0 <= x + d < w, else (float)t.
+ *         Layout [z][y][x], slice z at (z - s_begin) * w*h, xx = x + d: as smx_dev_cost_volume.
+ * The costs are small non-negative integers: every aggregation path takes them as materialised volumes
+ * (smx_dev_aggregate_wta_pair_cost, the _nbr forms), the comb walker without its fall-back. */
+typedef struct smx_census_params {
+    int rx, ry;   /* window (2 rx + 1) x (2 ry + 1) */
+    int th;       /* truncation of the Hamming distance; the cost of a partner outside the image */
+} smx_census_params;
+void smx_default_census_params(smx_census_params* p);
+/* (2 rx + 1)(2 ry + 1) - 1, or SMX_E_ARG for invalid parameters.  Host only, no GPU. */
+int smx_census_bits(const smx_census_params* p);
+
+/* d_img: nimages contiguous w*h u8 planes -> d_code: nimages contiguous w*h planes of codes, one launch (a pair passes 2). */
+int smx_dev_census(const smx_census_params* p, const uint8_t* d_img, uint64_t* d_code, int w, int h, int nimages,
+                   void* stream);
+/* d_code: the codes of the left image, then those of the right one (2 * w*h).  Slices [s_begin, s_end) of the left volume
+ * (labels dminl + z) into d_cost_l and of the right volume (labels dminr + z) into d_cost_r, both in one launch; either
+ * cost pointer may be NULL (not both), which gives the single-view form.  w, h >= 1. */
+int smx_dev_census_cost_pair(const smx_census_params* p, const uint64_t* d_code, float* d_cost_l, float* d_cost_r, int w,
+                             int h, int dminl, int dminr, int s_begin, int s_end, void* stream);
+/* Host pointers, synchronous; mirrors smx_compute_cost: the volume of i1 against i2, size_d*w*h floats, labels dmin + z. */
+int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h,
+                    int size_d, int dmin);
+
+#define SMX_COST_REFERENCE 0   /* compute_cost (costVolume.cu): the default */
+#define SMX_COST_CENSUS 1
+/* Matching cost of this context.  With SMX_COST_CENSUS (census: NULL = the defaults) smx_ctx_stereo_pair builds the codes
+ * once per pair, then runs census cost chunk -> aggregation from that chunk (the _pair_cost form, or _pair_nbr with
+ * sub-pixel on) over ascending contiguous chunks of slices, then the usual finish; cost_l / cost_r of smx_pair_out receive
+ * the census volumes; th_color / th_grad / alpha of smx_params are unused, radius, eps and d_lr apply as always.  The code
+ * and chunk buffers are allocated on first use.  smx_ctx_stereo_pair_async returns SMX_E_ARG while census is on. */
+int smx_ctx_set_cost(smx_ctx* ctx, int mode, const smx_census_params* census);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

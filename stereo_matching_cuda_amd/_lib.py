@@ -38,6 +38,11 @@ class WmfParams(C.Structure):
     _fields_ = [("radius", C.c_int), ("sigma_s", C.c_double), ("sigma_c", C.c_double)]
 
 
+class CensusParams(C.Structure):
+    """smx_census_params: the census / Hamming matching cost (not a stage of the reference)."""
+    _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("th", C.c_int)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -61,6 +66,7 @@ _vp, _i, _i64, _f, _sz, _u64, _u32 = (C.c_void_p, C.c_int, C.c_int64, C.c_float,
                                       C.c_uint64, C.c_uint32)
 _PP = C.POINTER(Params)
 _WP = C.POINTER(WmfParams)
+_CP = C.POINTER(CensusParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -121,7 +127,16 @@ SIGNATURES = {
     "smx_subpixel_delta": (_f, [_i, _f, _f, _f]),
     "smx_ctx_set_subpixel": (_i, [_vp, _i]),
     "smx_ctx_subpixel_maps": (_i, [_vp, _vp, _vp, _vp]),
+    "smx_default_census_params": (None, [_CP]),
+    "smx_census_bits": (_i, [_CP]),
+    "smx_dev_census": (_i, [_CP, _vp, _vp, _i, _i, _i, _vp]),
+    "smx_dev_census_cost_pair": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "smx_census_cost": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_cost": (_i, [_vp, _i, _CP]),
 }
+
+# smx.h SMX_COST_*: the matching costs by name
+COST_MODES = {"reference": 0, "census": 1}
 
 # smx.h SMX_SUBPIX_*: the sub-pixel fits by name
 SUBPIX_MODES = {"parabola": 1, "equiangular": 2}
@@ -183,6 +198,12 @@ def default_params():
 def default_wmf_params():
     p = WmfParams()
     lib().smx_default_wmf_params(C.byref(p))
+    return p
+
+
+def default_census_params():
+    p = CensusParams()
+    lib().smx_default_census_params(C.byref(p))
     return p
 
 

@@ -663,6 +663,56 @@ int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const flo
     return SMX_OK;
 }
 
+// ---- census / Hamming matching cost (not in the reference; smx_census.hip) ----------------------------
+void smx_default_census_params(smx_census_params* p) {
+    if (!p) return;
+    p->rx = 4; p->ry = 3; p->th = 62;
+}
+
+static bool census_params_ok(const smx_census_params* p) {
+    return p && p->rx >= 1 && p->rx <= 4 && p->ry >= 1 && p->ry <= 3 && p->th >= 1;
+}
+static int census_nbits(const smx_census_params* p) { return (2 * p->rx + 1) * (2 * p->ry + 1) - 1; }
+static int census_t(const smx_census_params* p) { return p->th < census_nbits(p) ? p->th : census_nbits(p); }
+
+int smx_census_bits(const smx_census_params* p) {
+    SMX_ARG(census_params_ok(p));
+    return census_nbits(p);
+}
+
+int smx_dev_census(const smx_census_params* p, const uint8_t* d_img, uint64_t* d_code, int w, int h, int nimages,
+                   void* stream) {
+    SMX_ARG(census_params_ok(p) && d_img && d_code && w >= 1 && h >= 1 && nimages >= 1);
+    return launch_census(p->rx, p->ry, d_img, d_code, w, h, nimages, (hipStream_t)stream);
+}
+
+int smx_dev_census_cost_pair(const smx_census_params* p, const uint64_t* d_code, float* d_cost_l, float* d_cost_r, int w,
+                             int h, int dminl, int dminr, int s_begin, int s_end, void* stream) {
+    SMX_ARG(census_params_ok(p) && d_code && (d_cost_l || d_cost_r));
+    SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
+    return launch_census_cost_pair(census_t(p), d_code, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end,
+                                   (hipStream_t)stream);
+}
+
+int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h,
+                    int size_d, int dmin) {
+    SMX_ARG(census_params_ok(p) && i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);
+    const size_t n = (size_t)w * h;
+    DevBuf img, code, dc;
+    SMX_HIP(img.alloc(2 * n));
+    SMX_HIP(code.alloc(2 * n * sizeof(uint64_t)));
+    SMX_HIP(dc.alloc(n * size_d * sizeof(float)));
+    SMX_HIP(hipMemcpy(img.p, i1, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + n, i2, n, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = smx_dev_census(p, img.as<uint8_t>(), code.as<uint64_t>(), w, h, 2, nullptr))) return rc;
+    if ((rc = smx_dev_census_cost_pair(p, code.as<uint64_t>(), dc.as<float>(), nullptr, w, h, dmin, 0, 0, size_d, nullptr)))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(hipMemcpy(cost, dc.p, n * size_d * sizeof(float), hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);
@@ -698,6 +748,12 @@ struct smx_ctx {
     int subpix = 0;
     bool sub_valid = false;     // the maps belong to the last synchronous pair
     DevBuf nbr, sub, subf;
+    // census matching cost (smx_ctx_set_cost): the codes of both images [2][h][w] and, unless the whole volumes exist
+    // (costL / costR), the cost slices of one chunk of both views [2][census_chunk][h][w]; allocated on first use
+    int cost_mode = SMX_COST_REFERENCE;
+    smx_census_params census;
+    int census_chunk = 0;
+    DevBuf codes, ccost;
     // pipelined entry (smx_ctx_stereo_pair_async): two slots of device inputs / results and pinned host staging, created
     // on first use.  Staging of a slot: [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l
     // mean_r | status word] coming down.
@@ -766,6 +822,39 @@ int smx_destroy(smx_ctx* c) {
     return SMX_OK;
 }
 
+// Census mode of ctx_enqueue: the codes once per pair, then census cost chunk -> aggregation from that chunk over ascending
+// contiguous chunks of `call`'s slices.  The chunk's slices go into the whole volumes where the context holds them, else
+// into the chunk buffer.  Only the first chunk may take the thread's keys as fresh (the later ones accumulate into them).
+static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
+    const int w = c->w, h = c->h;
+    const size_t n = c->n;
+    hipStream_t st = call.st;
+    uint64_t* codes = c->codes.as<uint64_t>();
+    int rc;
+    if (call.guide[1] == call.guide[0] + n) {
+        if ((rc = smx_dev_census(&c->census, call.guide[0], codes, w, h, 2, st))) return rc;
+    } else {
+        for (int v = 0; v < 2; ++v)
+            if ((rc = smx_dev_census(&c->census, call.guide[v], codes + v * n, w, h, 1, st))) return rc;
+    }
+    const int chunk = whole ? c->size_d : c->census_chunk;
+    struct Fresh { int saved; Fresh() : saved(g_keys_fresh) {} ~Fresh() { g_keys_fresh = saved; } } fresh;
+    for (int s0 = call.s_begin; s0 < call.s_end; s0 += chunk) {
+        const int s1 = s0 + chunk < call.s_end ? s0 + chunk : call.s_end;
+        float* cl = whole ? c->costL.as<float>() + (size_t)s0 * n : c->ccost.as<float>();
+        float* cr = whole ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
+        if ((rc = smx_dev_census_cost_pair(&c->census, codes, cl, cr, w, h, call.dmin[0], call.dmin[1], s0, s1, st))) return rc;
+        AggCall part = call;
+        part.s_begin = s0; part.s_end = s1;
+        part.cost[0] = cl; part.cost[1] = cr;
+        for (int v = 0; v < 2; ++v)
+            if (call.agg[v]) part.agg[v] = call.agg[v] + (size_t)(s0 - call.s_begin) * n;
+        if ((rc = run_aggregation(part, c->agg_path))) return rc;
+        g_keys_fresh = 0;
+    }
+    return SMX_OK;
+}
+
 // The path of one pair on the context's stream: device images in, the eight result planes out (+ the optional volumes
 // of the context).  Shared by the synchronous and the pipelined host-pointer entry.
 static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dminl, int dminr, bool want_cost, bool want_agg,
@@ -779,7 +868,8 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     int64_t* keysL = c->keys.as<int64_t>(); int64_t* keysR = keysL + n;
     // cost volumes are materialised only when the caller asks for them (main.cu:80-82) and then feed
     // the aggregation like in the reference; otherwise the slices are built on the fly inside it.
-    if (want_cost) {
+    const bool census = c->cost_mode == SMX_COST_CENSUS;
+    if (want_cost && !census) {
         if ((rc = smx_dev_cost_volume(p, dL, dR, c->costL.as<float>(), w, w, h, dminl, 0, size_d, st))) return rc;
         if ((rc = smx_dev_cost_volume(p, dR, dL, c->costR.as<float>(), w, w, h, dminr, 0, size_d, st))) return rc;
     }
@@ -792,7 +882,9 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     const AggCall call = {"smx_ctx_stereo_pair", p, 2, {dL, dR}, {dR, dL}, {costL, costR}, {dminl, dminr}, {keysL, keysR},
                           {mean, mean + n}, {aggL, want_agg ? aggL + (size_t)size_d * n : nullptr},
                           {nbrL, subpix ? nbrL + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
-    if ((rc = run_aggregation(call, c->agg_path))) return rc;
+    if (census) rc = ctx_census_aggregate(c, call, want_cost);
+    else rc = run_aggregation(call, c->agg_path);
+    if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
     if ((rc = smx_dev_finish_pair(p, keysL, w, h, dminl, dminr, dminl - 100, (float)dminl, bestL, mapL, occ, fil, st))) return rc;
     if (!subpix) return SMX_OK;
@@ -822,6 +914,15 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     if (want_agg && !c->aggLR.p) SMX_HIP(c->aggLR.alloc(2 * vb));
     const bool subpix = c->subpix != 0;
     if (subpix && !c->nbr.p) { SMX_HIP(c->nbr.alloc(6 * fb)); SMX_HIP(c->sub.alloc(2 * fb)); SMX_HIP(c->subf.alloc(fb)); }
+    if (c->cost_mode == SMX_COST_CENSUS) {
+        if (!c->codes.p) SMX_HIP(c->codes.alloc(2 * n * sizeof(uint64_t)));
+        if (!want_cost && !c->ccost.p) {
+            // at most 1 GiB for the chunk's two cost buffers
+            const size_t fit = ((size_t)1 << 30) / (2 * fb);
+            c->census_chunk = (int)(fit < 1 ? 1 : fit > (size_t)size_d ? (size_t)size_d : fit);
+            SMX_HIP(c->ccost.alloc(2 * (size_t)c->census_chunk * fb));
+        }
+    }
     c->sub_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     stage_mark(ST_BEGIN, st);
@@ -854,6 +955,22 @@ int smx_ctx_set_subpixel(smx_ctx* c, int mode) {
     if (mode != 0 && !subpix_mode_ok(mode))
         return fail(SMX_E_ARG, "smx_ctx_set_subpixel: mode must be 0, SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR");
     c->subpix = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
+    SMX_ARG(c);
+    if (mode != SMX_COST_REFERENCE && mode != SMX_COST_CENSUS)
+        return fail(SMX_E_ARG, "smx_ctx_set_cost: mode must be SMX_COST_REFERENCE or SMX_COST_CENSUS");
+    if (mode == SMX_COST_CENSUS) {
+        smx_census_params p;
+        smx_default_census_params(&p);
+        if (census) p = *census;
+        if (!census_params_ok(&p))
+            return fail(SMX_E_ARG, "smx_ctx_set_cost: census needs 1 <= rx <= 4, 1 <= ry <= 3, th >= 1");
+        c->census = p;
+    }
+    c->cost_mode = mode;
     return SMX_OK;
 }
 
@@ -897,6 +1014,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     int rc;
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
+    if (c->cost_mode != SMX_COST_REFERENCE)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: two pairs are in flight already (smx_ctx_wait takes the older one)");
     if ((rc = ctx_async_setup(c))) return rc;

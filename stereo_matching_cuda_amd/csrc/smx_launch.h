@@ -37,4 +37,8 @@ int launch_weighted_median(int radius, const uint16_t* ws, const uint16_t* wc, c
 // smx_subpix.hip: sub-pixel maps of both views (smx_dev_subpixel_pair)
 int launch_subpixel_pair(int mode, const int64_t* keys, const float* nbr, const float* dmap, const float* occlusion,
                          const float* filled, int w, int h, int dminl, float* sub, float* sub_filled, hipStream_t st);
+// smx_census.hip: census codes of nimages planes; Hamming cost slices [s_begin, s_end) of one or both views (t = min(th, nbits))
+int launch_census(int rx, int ry, const uint8_t* img, uint64_t* code, int w, int h, int nimages, hipStream_t st);
+int launch_census_cost_pair(int t, const uint64_t* code, float* cost_l, float* cost_r, int w, int h, int dminl, int dminr,
+                            int s_begin, int s_end, hipStream_t st);
 }  // namespace smx

@@ -25,14 +25,22 @@ class PairPipeline:
 
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
-                 wmf=None, wmf_params=None, subpixel=None):
+                 wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
         subpixel: None, "parabola" or "equiangular" -- sub-pixel maps from the winners' neighbouring aggregated costs (not
         a stage of the reference): the aggregation keeps them in self.nbr (2, 3, h, w) through the _nbr entries, and
         finish() runs smx_dev_subpixel_pair into self.sub (2, h, w) and self.sub_filled (h, w).  With None nothing is
-        allocated or launched."""
+        allocated or launched.
+        cost: None or "census" -- the matching cost.  None is the reference's (built on the fly inside the aggregation,
+        or passed to aggregate()); nothing is allocated or launched for it.  "census" is the census / Hamming cost
+        (include/smx.h smx_dev_census, smx_dev_census_cost_pair; census_params: CensusParams, None = the defaults): the
+        pipeline owns the codes self.codes (2, h, w) and a cost buffer self.census_cost of `slices_in_flight` slices per
+        view, which the max_ws_bytes bound counts, and aggregate(gray_l, gray_r) runs cost chunk -> aggregation from
+        that chunk over its slice range.  th_color / th_grad / alpha of `params` are unused then."""
+        if cost not in (None, "census"):
+            raise ValueError(f"cost must be None or 'census', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
             raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
         if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
@@ -53,7 +61,10 @@ class PairPipeline:
         # (smx_set_agg_path(1)) needs the parameter-agnostic bound
         need = (lambda n: self.lib.smx_agg_workspace_bytes(self.w, self.h, n)) if multi_kernel else \
                (lambda n: self.lib.smx_agg_workspace_bytes_for(C.byref(self.params), self.w, self.h, n))
-        while sif > 1 and 2 * need(sif) > max_ws_bytes:
+        self.cost = cost
+        self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
+        chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
+        while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
         self.slices_in_flight = sif
         # pair calls (both views per launch) need twice the single-view workspace
@@ -77,6 +88,10 @@ class PairPipeline:
         self.nbr = torch.empty((2, 3, self.h, self.w), **f) if subpixel else None
         self.sub = torch.empty((2, self.h, self.w), **f) if subpixel else None
         self.sub_filled = torch.empty((self.h, self.w), **f) if subpixel else None
+        self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
+        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost else None
+        # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
+        self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) if cost and want_agg and sif < local else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -89,9 +104,13 @@ class PairPipeline:
         """Cost build (fused unless cost_* given) + guided-filter aggregation + running WTA of this
         rank's slices, both views.  Leaves packed keys in self.keys."""
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
+        if self.cost and (cost_l is not None or cost_r is not None):
+            raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
         self.lib.smx_set_keys_fresh(1)
         try:
-            if cost_l is None and cost_r is None:
+            if self.cost:
+                self._aggregate_census(gray_l, gray_r)
+            elif cost_l is None and cost_r is None:
                 self.aggregate_pair(gray_l, gray_r)
             elif cost_l is not None and cost_r is not None:
                 self.aggregate_pair_cost(gray_l, gray_r, cost_l, cost_r)
@@ -111,12 +130,43 @@ class PairPipeline:
             finally:
                 self.lib.smx_set_max_slices_per_launch(0)
 
-    def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r):
+    def _aggregate_census(self, gray_l, gray_r):
+        """The census flow: the codes of both images once (one launch where the two images lie back to back in memory,
+        else one per image), then per chunk of `slices_in_flight` slices smx_dev_census_cost_pair into self.census_cost
+        and the aggregation from it.  Only the first chunk takes the keys as fresh; the later ones accumulate."""
+        L, P = self.lib, C.byref(self.census_params)
+        with self._on_device():
+            st = self._stream()
+            if gray_r.data_ptr() == gray_l.data_ptr() + self.n:
+                _lib.check(L.smx_dev_census(P, _dp(gray_l), _dp(self.codes), self.w, self.h, 2, st))
+            else:
+                for v, g in enumerate((gray_l, gray_r)):
+                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), self.w, self.h, 1, st))
+        sif = self.slices_in_flight
+        for c0 in range(self.s_begin, self.s_end, sif):
+            c1 = min(self.s_end, c0 + sif)
+            cl, cr = self.census_cost[0], self.census_cost[1]
+            with self._on_device():
+                _lib.check(L.smx_dev_census_cost_pair(P, _dp(self.codes), _dp(cl), _dp(cr), self.w, self.h, self.dminl,
+                                                      self.dminr, c0, c1, self._stream()))
+            whole = self.agg is None or self._agg_chunk is None
+            self.aggregate_pair_cost(gray_l, gray_r, cl, cr, c0, c1, self.agg if whole else self._agg_chunk)
+            if not whole:
+                # (the call wrote its two views c1 - c0 slices apart, whatever the buffer holds)
+                flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, self.h, self.w)
+                self.agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
+            L.smx_set_keys_fresh(0)
+
+    def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r, s_begin=None, s_end=None, agg=None):
         """Both views per launch from materialised cost volumes of this rank's slices (smx_dev_aggregate_wta_pair_cost):
-        the reference's data flow, read p + write q."""
+        the reference's data flow, read p + write q.  s_begin / s_end: a sub-range of the pipeline's slices whose cost
+        slices cost_* hold (default: all of them); agg: where its aggregated slices go (default: self.agg)."""
         self._guide = gray_l
-        args = (_dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr, self.s_begin,
-                self.s_end, _dp(self.keys), _dp(self.mean), _dp(self.agg), _dp(self.ws), self.ws_bytes)
+        s_begin = self.s_begin if s_begin is None else s_begin
+        s_end = self.s_end if s_end is None else s_end
+        agg = self.agg if agg is None else agg
+        args = (_dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr, s_begin,
+                s_end, _dp(self.keys), _dp(self.mean), _dp(agg), _dp(self.ws), self.ws_bytes)
         if self.subpixel:
             self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_nbr, *args, _dp(self.nbr))
         else:

@@ -25,6 +25,10 @@
 //   --subpixel FIT    sub-pixel disparity (`parabola` or `equiangular`) from the winners' neighbouring aggregated costs
 //                     (smx_ctx_set_subpixel; implies --fused): --pfm / --png16 then hold the sub-pixel filled map.
 //                     Not with --wmf, --ngpu or --pipeline
+//   --cost census     the census / Hamming matching cost instead of the reference's (smx_ctx_set_cost; implies --fused): the
+//                     same twelve images, the two cost images from the census volumes.  --census-window WxH gives the
+//                     window in pixels (odd, 3x3 .. 9x7; default 9x7), --census-th N the truncation (>= 1; default 62).
+//                     Composes with --wmf, --subpixel, --pfm and --png16; not with --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -42,6 +46,7 @@
 #include <chrono>
 #include <vector>
 
+#include "census.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
@@ -73,6 +78,8 @@ struct Options {
     std::string pfm, png16;
     std::string wmf;         // "" = no refinement, else "occluded" or "all"
     int subpixel = 0;        // 0 = off, else SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR
+    bool census = false;     // --cost census
+    smx_census_params census_params;
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
     bool pipeline = false;
@@ -82,6 +89,8 @@ struct Options {
 
 Options parse(int argc, char** argv) {
     Options o;
+    smx_default_census_params(&o.census_params);
+    bool census_option = false;     // --census-window / --census-th seen
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto value = [&](std::string& dst) {
@@ -109,12 +118,50 @@ Options parse(int argc, char** argv) {
                 o.ok = false;
             }
         }
+        else if (a == "--cost") {
+            std::string v;
+            value(v);
+            o.census = v == "census";
+            if (o.ok && !o.census && v != "reference") {
+                std::fprintf(stderr, "--cost needs `reference` or `census`, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+        }
+        else if (a == "--census-window") {
+            std::string v;
+            value(v);
+            int ww = 0, wh = 0;
+            char x = 0, rest = 0;
+            census_option = true;
+            if (o.ok && (std::sscanf(v.c_str(), "%d%c%d%c", &ww, &x, &wh, &rest) != 3 || x != 'x' || ww < 3 || ww > 9 ||
+                         wh < 3 || wh > 7 || ww % 2 == 0 || wh % 2 == 0)) {
+                std::fprintf(stderr, "--census-window needs WxH with odd W in 3 .. 9 and odd H in 3 .. 7, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.census_params.rx = ww / 2; o.census_params.ry = wh / 2;
+        }
+        else if (a == "--census-th") {
+            std::string v;
+            value(v);
+            char* end = nullptr;
+            const long th = std::strtol(v.c_str(), &end, 10);
+            census_option = true;
+            if (o.ok && (v.empty() || *end || th < 1 || th > 1000000)) {
+                std::fprintf(stderr, "--census-th needs an integer >= 1, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.census_params.th = (int)th;
+        }
         else if (a == "--ngpu") { std::string v; value(v); o.ngpu = std::atoi(v.c_str()); }
         else if (a == "--pipeline") o.pipeline = true;
         else if (a == "--pairs") { std::string v; value(v); o.pairs = std::atoi(v.c_str()); }
         else if (a == "--overlap") o.overlap = true;
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); o.ok = false; }
         else o.positional.push_back(a);
+    }
+    if (o.ok && census_option && !o.census) {
+        std::fprintf(stderr, "--census-window and --census-th need --cost census\n");
+        o.ok = false;
     }
     return o;
 }
@@ -151,6 +198,10 @@ int main(int argc, char** argv) {
                              "--pipeline\n");
         return 2;
     }
+    if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
     if (opt.ngpu < 0 || opt.ngpu > smx_device_count()) {
         std::fprintf(stderr, "--ngpu %d: this node shows %d HIP device(s)\n", opt.ngpu, smx_device_count());
         return 2;
@@ -172,7 +223,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const bool fused = opt.fused || sh_create || opt.subpixel;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -231,8 +282,13 @@ int main(int argc, char** argv) {
         // is materialised, for the two cost images the reference writes)
         std::cout << "Cost Volume ..." << std::endl;
         for (int v = 0; v < 2; ++v) cost[v].resize((size_t)n);
-        CHECK(smx_compute_cost(&smx_config().params, gray[0], gray[1], cost[0].data(), w, w, h, h, 1, dmin[0]));
-        CHECK(smx_compute_cost(&smx_config().params, gray[1], gray[0], cost[1].data(), w, w, h, h, 1, dmin[1]));
+        if (opt.census) {
+            compute_census_cost(gray[0], gray[1], cost[0].data(), w, h, 1, dmin[0], opt.census_params);
+            compute_census_cost(gray[1], gray[0], cost[1].data(), w, h, 1, dmin[1], opt.census_params);
+        } else {
+            CHECK(smx_compute_cost(&smx_config().params, gray[0], gray[1], cost[0].data(), w, w, h, h, 1, dmin[0]));
+            CHECK(smx_compute_cost(&smx_config().params, gray[1], gray[0], cost[1].data(), w, w, h, h, 1, dmin[1]));
+        }
         std::cout << "guided filter ..." << std::endl;
         occlusion.resize(n);
         filled.resize(n);
@@ -248,6 +304,7 @@ int main(int argc, char** argv) {
         if (sh_create) CHECK(sh_create(&smx_config().params, w, h, size_d, opt.ngpu, opt.overlap ? 1 : 0, &sctx));
         else CHECK(smx_create(&smx_config().params, w, h, size_d, &ctx));
         if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
+        if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)

@@ -1,6 +1,7 @@
 // stages.cpp -- the reference's per-stage host functions (same names, arguments and in/out
 // behaviour) as thin forwards to the C-ABI of include/smx.h.  Host pointers in, host pointers out,
 // synchronous, errors abort like the reference's CHECK macro.
+#include "census.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
@@ -72,6 +73,12 @@ void compute_cost(unsigned char* i1, unsigned char* i2, float* cost, int w1, int
             ok = check_errors(twin.data() + (size_t)z * w1 * h1, cost + (size_t)z * w1 * h1, w1 * h1) && ok;
         if (ok) cout << "Cost volume ok!" << endl;
     }
+}
+
+// not in the reference: the census / Hamming cost volume (smx_main --cost census)
+void compute_census_cost(unsigned char* i1, unsigned char* i2, float* cost, int w, int h, int size_d, int dmin,
+                         const smx_census_params& p) {
+    CHECK(smx_census_cost(&p, i1, i2, cost, w, h, size_d, dmin));
 }
 
 // integral.cu:3-51

@@ -154,6 +154,39 @@ def wmf_weights(params=None):
     return spatial, rng
 
 
+def census_transform(img, params=None):
+    """Census codes of an (h, w) u8 image -> (h, w) uint64 (include/smx.h smx_dev_census; not a stage of the reference).
+    Device buffers come from torch; the transform is the HIP kernel."""
+    import torch
+    img = _c(img, np.uint8)
+    if img.ndim != 2:
+        raise ValueError("census_transform expects an (h, w) uint8 image")
+    h, w = img.shape
+    p = params if params is not None else _lib.default_census_params()
+    L = _lib.lib()
+    bits = L.smx_census_bits(C.byref(p))
+    if bits < 0:                                   # bad parameters: an SmxError before anything touches the device
+        _lib.check(bits)
+    d_img = torch.from_numpy(img).cuda()
+    d_code = torch.empty((h, w), dtype=torch.int64, device=d_img.device)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(L.smx_dev_census(C.byref(p), C.c_void_p(d_img.data_ptr()), C.c_void_p(d_code.data_ptr()), w, h, 1, st))
+    return d_code.cpu().numpy().view(np.uint64)
+
+
+def census_cost(i1, i2, size_d, dmin, params=None):
+    """Census / Hamming cost volume of i1 against i2, [z][y][x], slice z has label dmin + z (smx_census_cost; the census
+    counterpart of compute_cost)."""
+    i1, i2 = _c(i1, np.uint8), _c(i2, np.uint8)
+    if i1.ndim != 2 or i2.shape != i1.shape:
+        raise ValueError("census_cost expects two (h, w) uint8 images of one shape")
+    h, w = i1.shape
+    p = params if params is not None else _lib.default_census_params()
+    cost = np.empty((max(size_d, 0), h, w), np.float32)
+    _lib.check(_lib.lib().smx_census_cost(C.byref(p), _ptr(i1), _ptr(i2), _ptr(cost), w, h, size_d, dmin))
+    return cost
+
+
 def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, want_agg=False,
                 params=None):
     """main.cu:65-155 on two gray images, device-resident between the stages."""
