@@ -177,7 +177,18 @@ int smx_dev_integral(const float* d_in, float* d_out, int w, int h, int nplanes,
 /* Bytes of workspace smx_dev_aggregate_wta needs for `nslices` slices of ONE view in flight (the pair
  * call needs twice that): image / guidance planes, per slice one aggregated plane plus the strip
  * hand-off records, control words.  The first 256 bytes hold the call's status word
- * (smx_dev_agg_status).  Fewer slices in flight than s_end - s_begin only means more launches. */
+ * (smx_dev_agg_status).  Fewer slices in flight than s_end - s_begin only means more launches.
+ *
+ * The memory contract of the five aggregation entries (smx_dev_aggregate_wta, _pair, _pair_cost, _nbr, _pair_nbr;
+ * tests/test_gpu_memory_contract.py):
+ *   - A call writes nothing outside [d_workspace, d_workspace + workspace_bytes) and the stated extents of its outputs:
+ *     d_keys n keys per view, d_mean_u8 n bytes per view, d_agg (s_end - s_begin) * n floats per view, d_nbr 3n floats per
+ *     view (n = w*h).  A workspace too small for one slice is SMX_E_WS before anything is launched or written.
+ *   - The workspace may hold anything on entry: the call clears the status words, tickets and flags it relies on, and reads
+ *     no other region before it has written it.
+ *   - d_workspace needs no alignment: the call uses it from the next 256-byte boundary on, and the sizes below include the
+ *     up to 255 bytes that loses.
+ *   - Inputs (the images, d_cost*) are not modified. */
 size_t smx_agg_workspace_bytes(int w, int h, int nslices);
 /* The same for the path that `p` will run in auto mode: where a fused walker runs (radius <= 9, thresholds within the
  * sentinel bound below) it needs ONE plane per slice in flight (plus its hand-off records), about a quarter of the

@@ -15,8 +15,8 @@ import pytest
 
 import stereo_matching_cuda_amd as smx
 from stereo_matching_cuda_amd import _lib
+from guarded import SMX_E_WS, min_workspace
 
-SMX_E_WS = -3
 SHAPES = [(1242, 375), (384, 288), (2964, 2000), (3840, 2160), (8192, 5460), (2, 1), (152, 10), (153, 11), (330, 25)]
 SLICES = (1, 2, 7, 16, 192, 512)
 
@@ -88,11 +88,8 @@ def test_documented_workspace_holds_the_slices_it_is_sized_for(so):
                 # the smallest workspace (in 256-byte steps) that holds one slice: at most the documented size, not below the
                 # planes every call writes (status words, two image planes [h][w + 8] of 4 B, per view (mean_I, 1/(var + eps))
                 # of 8 B and two integrals of 4 B, own q planes of 4 B); one step below it the call reports SMX_E_WS
-                lo, hi = 0, nviews * ws_one // 256            # lo fails, hi holds
                 assert chunk(*args, 0, n) == (None, SMX_E_WS), where
-                while hi - lo > 1:
-                    mid = (lo + hi) // 2
-                    lo, hi = (lo, mid) if chunk(*args, mid * 256, n)[1] == 0 else (mid, hi)
+                hi = min_workspace(so, *args, n) // 256       # (the bisection: tests/guarded.py)
                 written = 256 + 2 * (w + 8) * h * 4 + nviews * w * h * (16 + (4 if own_q else 0))
                 assert hi * 256 >= written, where
                 got, rc = chunk(*args, hi * 256, n)
@@ -111,11 +108,8 @@ def test_documented_workspace_holds_the_slices_it_is_sized_for(so):
                     for ws in (nviews * ws_any, ws_any, ws_one, nviews * ws_one):
                         got, rc = chunk(*args, ws, n)
                         assert rc == 0 and got >= 1 and got == _multi_kernel_chunk(w, h, cost, ws, n), where
-                    lo, hi = 0, ws_one // 256             # lo fails, hi holds
                     assert chunk(*args, 0, n) == (None, SMX_E_WS), where
-                    while hi - lo > 1:
-                        mid = (lo + hi) // 2
-                        lo, hi = (lo, mid) if chunk(*args, mid * 256, n)[1] == 0 else (mid, hi)
+                    hi = min_workspace(so, *args, n) // 256
                     assert hi * 256 == 512 + 10 * _align256(4 * w * h), where
                     got, rc = chunk(*args, hi * 256, n)
                     assert rc == 0 and got >= 1 and got == _multi_kernel_chunk(w, h, cost, hi * 256, n), where
