@@ -8,6 +8,7 @@
 #include "smx_agg_v4.h"
 #include "smx_agg_v5.h"
 #include "smx_launch.h"
+#include "smx_wta.h"
 
 namespace smx {
 
@@ -129,7 +130,7 @@ int agg_plan(const smx_params* p, int w, int h, int nviews, bool use_cost, bool 
     // Materialised cost volumes (the reference's calling convention, guidedFilter.cu:198-200) run on the comb walker too
     // (round 5): its cost wave loads the costs and CHECKS them -- +0 or a normal number in [2^-60, 2^60] is what its exactness
     // argument covers.  A violation cannot come back to the host of an asynchronous call, so the ring walker, which takes
-    // any input, is queued behind it with a device-side gate (`only_if`): it does nothing unless the comb walker raised the
+    // any input, is queued behind it with a device-side gate (v4::Args::gate): it does nothing unless the comb walker raised the
     // second status word, and the two WTA passes are gated the other way round.  Cost: two empty launches and a memset.
     const bool comb = opt.walker != 4 && v5_applies(p, w, h, nviews, use_cost);
     const bool fallback = comb && use_cost;
@@ -296,7 +297,7 @@ static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) 
                 v4::Args a4 = a;
                 a4.K = L.K4; a4.NI = L.NI4;
                 a4.nitems = a4.nsv * L.K4;
-                a4.only_if = fell_back;
+                a4.gate = fell_back;
                 rc = v4_walk_launch(a4, true, opt.fast, st);
                 nl += 2;
             }
@@ -309,15 +310,15 @@ static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) 
         // queued fall-back exactly one of the two runs, so both may take the flag)
         const bool fresh = opt.keys_fresh && s0 == s_begin;
         // (d_nbr: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge)
-        if (L.comb && own_q) {
-            if (d_nbr) rc = v5_wta_nbr_launch(nviews, q, c.keys, d_nbr, w, h, cnt, s0, fell_back, fresh, st);
-            else rc = v5_wta_launch(nviews, q, c.keys, w, h, cnt, s0, fell_back, fresh, st);
-            if (!rc && L.fallback) {
-                // ... and the WTA over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
-                rc = v4_wta_launch(nviews, q, c.keys, d_nbr, L.plane, cnt, s0, fell_back, fresh, st);
-                ++nl;
-            }
-        } else rc = v4_wta_launch(nviews, q, c.keys, d_nbr, L.plane, cnt, s0, nullptr, fresh, st);
+        // over the planes of the walker that ran (smx_wta.h: runs iff gate == NULL || (*gate != 0) == gate_nonzero) ...
+        const bool comb_q = L.comb && own_q;
+        rc = wta_launch(comb_q ? WTA_COMB : WTA_NATURAL, nviews, q, c.keys, d_nbr, w, h, L.qplane, cnt, s0, comb_q ? fell_back : nullptr,
+                        0, fresh, st);
+        if (!rc && comb_q && L.fallback) {
+            // ... and over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
+            rc = wta_launch(WTA_NATURAL, nviews, q, c.keys, d_nbr, w, h, L.plane, cnt, s0, fell_back, 1, fresh, st);
+            ++nl;
+        }
         if (rc) return rc;
         stage_mark(ST_WTA, st);
         nl += s0 != s_begin ? 3 : 2;
@@ -411,9 +412,7 @@ static int aggregate_multi(const AggCall& c, const AggOpts& opt, AggInfo* info) 
             if ((rc = launch_ab(p, T0, T1, mean_im, cinv, A, B, w, h, cnt, st))) return rc;
             if ((rc = launch_integral(2, A, B, A, B, w, h, cnt, st))) return rc;
             float* agg = c.agg[v] ? c.agg[v] + (int64_t)(s0 - c.s_begin) * n : nullptr;
-            if (c.nbr[v]) rc = launch_q_wta_nbr(p, A, B, im, c.keys[v], c.nbr[v], agg, w, h, cnt, s0, st);
-            else rc = launch_q_wta(p, A, B, im, c.keys[v], agg, w, h, cnt, s0, st);
-            if (rc) return rc;
+            if ((rc = launch_q_wta(p, A, B, im, c.keys[v], c.nbr[v], agg, w, h, cnt, s0, st))) return rc;
             info->launches += 6;
             stage_mark(ST_WALK, st);
         }

@@ -42,7 +42,7 @@ struct Args {
     unsigned* flags;      // [sv][K]  published-record counters (zeroed before every launch)
     unsigned* ticket;     // work-item counter              (zeroed before every launch)
     unsigned* status;     // != 0: a flag wait timed out (results invalid)
-    const unsigned* only_if;   // != NULL: the launch does nothing unless this word is nonzero (the queued fall-back behind the comb walker)
+    const unsigned* gate;      // != NULL: the launch does nothing unless this word is nonzero (the queued fall-back behind the comb walker)
     CostConst cc;
 };
 
@@ -66,10 +66,5 @@ bool v4_supported(const smx_params* p);          // radius 0 .. RMAX
 int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, hipStream_t st);
 // the walker over a.nitems items: costs from a.v[].cost or built from the image planes; fast: the FAST mode (not bit-exact)
 int v4_walk_launch(const v4::Args& a, bool use_cost, bool fast, hipStream_t st);
-// packed-key WTA over `count` q planes [slice][n] (slice slice0 ..) of `nviews` views -> keys [n]; nbr != NULL: the pass
-// that also keeps the winners' neighbours in the views' state planes [3][n] (smx_common.h nbr_merge)
-// (only_if != NULL: a device word; the pass does nothing unless it is nonzero)
-int v4_wta_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, size_t n, int count, int slice0,
-                  const unsigned* only_if, bool fresh, hipStream_t st);
 
 }  // namespace smx

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
         c = (4 * (wave - QW0) + (l >> 4)) * 4;
     };
 
-    if (A.only_if && flag_load(const_cast<unsigned*>(A.only_if)) == 0u) return;     // (uniform: every thread reads the same word)
+    if (A.gate && flag_load(const_cast<unsigned*>(A.gate)) == 0u) return;     // (uniform: every thread reads the same word)
     if (tid == 0) s_item = (int)__hip_atomic_fetch_add((gu32*)A.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (;;) {
         wg_barrier();
@@ -1053,101 +1053,6 @@ __global__ __launch_bounds__(NT, 2 * WG_PER_CU) void k_v4_walk(Args A) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// WTA over the chunk's q planes [slice][h][w] (dispSelectOnGPU guidedFilter.cu:403-411 in packed-key
-// form).  One lane per pixel; grid (ceil(n/256), nviews)
-// ---------------------------------------------------------------------------------------------
-struct WtaArgs {
-    const float* q[2];
-    int64_t* keys[2];
-    const unsigned* gate;     // != NULL: the pass runs only if (*gate != 0) == gate_nonzero (which walker's q planes are valid)
-    int gate_nonzero;
-    int fresh;                // != 0: the keys hold nothing yet: start from the identity instead of loading them
-};
-__device__ __forceinline__ bool wta_gate_closed(const unsigned* gate, int gate_nonzero) {
-    return gate && (int)(flag_load(const_cast<unsigned*>(gate)) != 0u) != gate_nonzero;
-}
-
-__global__ __launch_bounds__(256) void k_v4_wta(WtaArgs wa, size_t n, int count, int slice0) {
-    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (id >= n || wta_gate_closed(wa.gate, wa.gate_nonzero)) return;
-    const float* __restrict__ q = wa.q[blockIdx.y] + id;
-    int64_t* keys = wa.keys[blockIdx.y];
-    const int64_t key = wa.fresh ? KEY_IDENTITY : keys[id];
-    WtaRun r;                           // (smx_common.h: the winner of this call's slices, packed once)
-    int z = 0;
-    for (; z + 8 <= count; z += 8) {
-        float v[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = __builtin_nontemporal_load(&q[(size_t)(z + t) * n]);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) r.step(v[t], (uint32_t)(slice0 + z + t));
-    }
-    for (; z < count; ++z) r.step(__builtin_nontemporal_load(&q[(size_t)z * n]), (uint32_t)(slice0 + z));
-    const int64_t kk = r.key();
-    keys[id] = kk < key ? kk : key;
-}
-
-// The same with two pixels per lane (8-byte loads).  Needs an even plane size n and 8-byte aligned planes.
-// grid (ceil(n/512), nviews)
-__global__ __launch_bounds__(256) void k_v4_wta2(WtaArgs wa, size_t n, int count, int slice0) {
-    const size_t id = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    if (id >= n || wta_gate_closed(wa.gate, wa.gate_nonzero)) return;
-    const float* __restrict__ q = wa.q[blockIdx.y] + id;
-    int64_t* keys = wa.keys[blockIdx.y];
-    const int64_t k0 = wa.fresh ? KEY_IDENTITY : keys[id], k1 = wa.fresh ? KEY_IDENTITY : keys[id + 1];
-    WtaRun r0, r1;
-    int z = 0;
-    constexpr int U = 8;               // loads in flight per lane (4 / 16 / 24 measure the same)
-    for (; z + U <= count; z += U) {
-        f2 v[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = __builtin_nontemporal_load((const f2*)&q[(size_t)(z + t) * n]);
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-            r0.step(v[t].x, (uint32_t)(slice0 + z + t));
-            r1.step(v[t].y, (uint32_t)(slice0 + z + t));
-        }
-    }
-    for (; z < count; ++z) {
-        const f2 v = __builtin_nontemporal_load((const f2*)&q[(size_t)z * n]);
-        r0.step(v.x, (uint32_t)(slice0 + z));
-        r1.step(v.y, (uint32_t)(slice0 + z));
-    }
-    const int64_t a = r0.key(), c = r1.key();
-    keys[id] = a < k0 ? a : k0;
-    keys[id + 1] = c < k1 ? c : k1;
-}
-
-// k_v4_wta that also keeps the winner's neighbouring q in the views' state planes nbr [3][n] (smx_common.h WtaRunNbr,
-// nbr_merge).  Same gate and fresh rule.  grid (ceil(n/256), nviews)
-__global__ __launch_bounds__(256) void k_v4_wta_nbr(WtaArgs wa, float* nbr0, float* nbr1, size_t n, int count, int slice0) {
-    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (id >= n || wta_gate_closed(wa.gate, wa.gate_nonzero)) return;
-    const float* __restrict__ q = wa.q[blockIdx.y] + id;
-    int64_t* keys = wa.keys[blockIdx.y];
-    float* const nbr = (blockIdx.y ? nbr1 : nbr0) + id;
-    const int64_t key = wa.fresh ? KEY_IDENTITY : keys[id];
-    const bool ld = key != KEY_IDENTITY;                // (no winner yet: the state is not read)
-    float lo = ld ? nbr[0] : 0.0f, hi = ld ? nbr[n] : 0.0f, last = ld ? nbr[2 * n] : 0.0f;
-    WtaRunNbr r(nbr_prev0(key, last));
-    const float q0 = __builtin_nontemporal_load(&q[0]);
-    r.step(q0, (uint32_t)slice0);
-    int z = 1;
-    for (; z + 8 <= count; z += 8) {
-        float v[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = __builtin_nontemporal_load(&q[(size_t)(z + t) * n]);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) r.step(v[t], (uint32_t)(slice0 + z + t));
-    }
-    for (; z < count; ++z) r.step(__builtin_nontemporal_load(&q[(size_t)z * n]), (uint32_t)(slice0 + z));
-    keys[id] = nbr_merge(r, key, (uint32_t)slice0, q0, &lo, &hi, &last);
-    nbr[0] = lo;
-    nbr[n] = hi;
-    nbr[2 * n] = last;
-}
-
 }  // namespace v4
 
 // =============================================================================================
@@ -1208,26 +1113,6 @@ static int launch_walk4(const v4::Args& a, hipStream_t st) {
 int v4_walk_launch(const v4::Args& a, bool use_cost, bool fast, hipStream_t st) {
     if (fast) return use_cost ? launch_walk4<v4::SRC_COST, true>(a, st) : launch_walk4<v4::SRC_IMG, true>(a, st);
     return use_cost ? launch_walk4<v4::SRC_COST, false>(a, st) : launch_walk4<v4::SRC_IMG, false>(a, st);
-}
-
-int v4_wta_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, size_t n, int count, int slice0,
-                  const unsigned* only_if, bool fresh, hipStream_t st) {
-    v4::WtaArgs wa;
-    for (int v = 0; v < 2; ++v) { wa.q[v] = q[v < nviews ? v : 0]; wa.keys[v] = keys[v < nviews ? v : 0]; }
-    wa.gate = only_if; wa.gate_nonzero = only_if ? 1 : 0;
-    wa.fresh = fresh ? 1 : 0;
-    // two pixels per lane where every plane can be read in 8-byte units
-    bool al8 = n % 2 == 0;
-    for (int v = 0; v < nviews; ++v) al8 = al8 && ((uintptr_t)wa.q[v] & 7) == 0;
-    if (nbr)
-        hipLaunchKernelGGL(v4::k_v4_wta_nbr, dim3(cdivu4((int64_t)n, 256), nviews), dim3(256), 0, st, wa, nbr[0], nbr[nviews - 1], n,
-                           count, slice0);
-    else if (al8)
-        hipLaunchKernelGGL(v4::k_v4_wta2, dim3(cdivu4((int64_t)n, 512), nviews), dim3(256), 0, st, wa, n, count, slice0);
-    else
-        hipLaunchKernelGGL(v4::k_v4_wta, dim3(cdivu4((int64_t)n, 256), nviews), dim3(256), 0, st, wa, n, count, slice0);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
 }
 
 }  // namespace smx

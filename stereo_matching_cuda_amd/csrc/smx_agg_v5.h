@@ -9,6 +9,7 @@ namespace v5 {
 // Comb length 9: seven combs per wave, three comb waves per stage + a row-scan wave + a cost wave (512 threads, two
 // workgroups per CU at 128 VGPRs); the row scans run beside the comb rows.  (Round 4 also built comb lengths 12 and 16 as
 // three-barrier forms -- slower; the history keeps that file.)
+constexpr int R = 9, HW = 2 * R + 1;    // box radius, window width
 constexpr int L = 9;                    // lanes of a comb
 constexpr int CPW = 64 / L;             // combs per wave
 constexpr int NS1 = (19 + CPW - 1) / CPW;   // comb waves per stage
@@ -30,7 +31,7 @@ struct Args {
     unsigned o_i2p[2];    // u32x4 [K][NI][CLP] + u32 [K][NI][CLP] behind it: image values (fp16 pairs) of the ten q rows of band ib at the q column OWS k - 19 + 19 il + rho
     // out, per view: qperm != 0: comb-ordered scratch [slice][K][ceil(h/2)][OWS][2]: the rows 2 yp, 2 yp + 1 of column
     // OWS k + 19 (il-1) + rho side by side at [(L-1) rho + il - 1] (a wave stores ONE contiguous run of 8-byte units per row
-    // pair -- round 5: half the store instructions of a row at a time; read back by k_v5_wta); else the caller's [slice][h][w]
+    // pair -- round 5: half the store instructions of a row at a time; read back through q_pixel below); else the caller's [slice][h][w]
     // materialised cost volumes (src_cost != 0): slice s of view v at cost[v] + s * cost_plane, [h][w] each (the reference's
     // calling convention, guidedFilter.cu:198); else the costs are built from the image planes
     const float* cost[2];
@@ -55,6 +56,21 @@ struct Args {
 
 inline int strips(int w) { return (w + OWS - 1) / OWS; }
 inline size_t q_plane_floats(int w, int h) { return (size_t)strips(w) * ((h + 1) / 2) * 2 * OWS; }   // comb-ordered q scratch per slice: row pairs
+// The inverse of that layout and of k_v5_walk's q stores (vo, q_row0, q_pitch): the pixel (x, y) of element e of a comb-ordered
+// plane of K strips -- element = ((k hp + yp) OWS + p) 2 + (y & 1) with hp = ceil(h/2) row pairs, p = (L-1) rho + il - 1 for
+// column OWS k + 19 (il-1) + rho (the last strip: p = the local column).  false: the element lies outside the image (the second
+// row of a ragged last pair, the tail of the last strip's rows).  A plane is a whole number of quads of consecutive elements
+// (two columns x the two rows of a pair) and starts 64-byte aligned where the scratch is carved 256-byte aligned.
+static_assert((2 * OWS) % 4 == 0, "quads (two columns x the two rows of a pair) do not straddle pair rows");
+__device__ inline bool q_pixel(size_t e, int w, int h, int K, int* x, int* y) {
+    const int hp = (h + 1) / 2;
+    const int prow = (int)(e / (2 * OWS)), rem = (int)(e - (size_t)prow * (2 * OWS));   // prow = k hp + yp
+    const int p = rem >> 1, k = prow / hp;
+    const int rho = p / (L - 1), i1 = p - (L - 1) * rho;
+    *y = 2 * (prow - k * hp) + (rem & 1);
+    *x = OWS * k + (k + 1 < K ? HW * i1 + rho : p);        // (the last strip is in column order)
+    return *x < w && *y < h;
+}
 inline int bands(int h) { return (h + 2 * 9 + BH - 1) / BH + 2; }     // the q rows of iteration i end at 10 i - 28
 inline int records(int h) { return bands(h) + 2; }                   // hand-off records per (strip boundary, slice-view)
 // An item occupies its roles for fewer slots than it has: the cost wave for local slots -2 .. s1_last - 2, stage 1 for
@@ -96,12 +112,5 @@ int v5_launch(const v5::Args& a, hipStream_t st);
 int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G, uint8_t* const* mean_u8,
                    const aggdev::fg_t* const* FG, aggdev::f2* const* g1p, unsigned* const* i2p, int w, int h, double eps,
                    hipStream_t st);
-// packed-key WTA over `count` comb-ordered q planes (slice slice0 ..) of `nviews` views -> keys [h][w]
-// (skip_if != NULL: a device word; the pass does nothing when it is nonzero)
-int v5_wta_launch(int nviews, const float* const* q, int64_t* const* keys, int w, int h, int count, int slice0,
-                  const unsigned* skip_if, bool fresh, hipStream_t st);
-// the same that also keeps the winners' neighbours in the views' state planes nbr [3][h][w] (smx_common.h nbr_merge)
-int v5_wta_nbr_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, int w, int h, int count,
-                      int slice0, const unsigned* skip_if, bool fresh, hipStream_t st);
 
 }  // namespace smx

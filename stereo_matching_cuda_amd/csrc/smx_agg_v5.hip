@@ -57,7 +57,7 @@ namespace smx {
 namespace v5 {
 using namespace aggdev;
 
-constexpr int R = 9, HW = 2 * R + 1;
+// (R, HW, L, OWS, BH, the q scratch's layout and the argument block: smx_agg_v5.h)
 constexpr int SWU = HW * L;             // integral-image columns per strip (171)
 constexpr int SW = (SWU + 3) / 4 * 4;   // tile columns: whole quads (the columns behind SWU are never used)
 static_assert(OWS == HW * (L - 1) && SWU == OWS + HW && CPW * L <= 64 && CPW * NS1 >= HW, "strip geometry");
@@ -1170,153 +1170,6 @@ __global__ __launch_bounds__(CLP) void k_v5_perm(PermArgs pa, int w, int h, int 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// WTA over the chunk's comb-ordered q planes [slice][K][ceil(h/2)][OWS][2] (dispSelectOnGPU guidedFilter.cu:403-411):
-// four elements per lane (two columns x the two rows of a pair), coalesced nt loads, 8 in flight; the keys stay [h][w] --
-// the lane finds its pixels once per call.  grid (ceil(plane / 1024), nviews)
-// ---------------------------------------------------------------------------------------------------------------
-struct Wta5Args {
-    const float* q[2];
-    int64_t* keys[2];
-    const unsigned* skip_if;      // != NULL: the pass does nothing if this word is nonzero (the comb walker's planes do not count)
-    int fresh;                    // != 0: the keys hold nothing yet (no smx_dev_init_keys ran): start from the identity, do not load them
-};
-// Four elements per lane, 16-byte loads: a row pair of a strip is 2 OWS = 304 floats, so a plane is a whole number of quads
-// and every plane starts 64-byte aligned (q_plane_floats is a multiple of 304; the scratch is carved 256-byte aligned)
-static_assert((2 * OWS) % 4 == 0, "quads (two columns x the two rows of a pair) do not straddle pair rows");
-__global__ __launch_bounds__(256) void k_v5_wta(Wta5Args wa, int w, int h, int K, int count, int slice0) {
-    constexpr int EPL = 4;
-    const int hp = (h + 1) / 2;                                 // row pairs: [K][hp][OWS][2] (smx_agg_v5.h)
-    const size_t np = (size_t)K * hp * (2 * OWS);
-#ifdef SMX_WTA_REV       // (A/B: the planes back to front -- the strips the walker wrote last first)
-    const size_t e0 = ((size_t)(gridDim.x - 1 - blockIdx.x) * 256 + threadIdx.x) * EPL;
-#else
-    const size_t e0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * EPL;
-#endif
-    if (e0 >= np || (wa.skip_if && flag_load(const_cast<unsigned*>(wa.skip_if)) != 0u)) return;
-    const float* __restrict__ q = wa.q[blockIdx.y] + e0;
-    int64_t* const keys = wa.keys[blockIdx.y];
-    // the pixels of this lane's elements (once per call)
-    int64_t* kp[EPL];
-    int64_t key[EPL];
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-        const size_t e = e0 + j;
-        const int prow = (int)(e / (2 * OWS)), rem = (int)(e - (size_t)prow * (2 * OWS));   // prow = k hp + yp
-        const int p = rem >> 1, k = prow / hp, y = 2 * (prow - k * hp) + (rem & 1);
-        const int rho = p / (L - 1), i1 = p - (L - 1) * rho;
-        const int x = OWS * k + (k + 1 < K ? HW * i1 + rho : p);        // (the last strip is in column order)
-        kp[j] = e < np && x < w && y < h ? keys + (size_t)y * w + x : nullptr;
-        key[j] = kp[j] && !wa.fresh ? *kp[j] : KEY_IDENTITY;
-    }
-    // nothing of this lane lies in the image (the tail of a row of the last strip): no load at all
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) any = any || kp[j];
-    if (!any) return;
-    typedef float fv __attribute__((ext_vector_type(EPL)));
-    WtaRun run[EPL];                    // (smx_common.h: the winner of this call's slices in the float domain, packed once)
-    auto step = [&](const fv v, unsigned slice) {
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) run[j].step(v[j], slice);
-    };
-    int z = 0;
-    constexpr int U = 8;
-    for (; z + U <= count; z += U) {
-        fv v[U];
-#pragma unroll
-#ifdef SMX_WTA_LD_PLAIN
-        for (int t = 0; t < U; ++t) v[t] = *(const fv*)&q[(size_t)(z + t) * np];
-#else
-        for (int t = 0; t < U; ++t) v[t] = __builtin_nontemporal_load((const fv*)&q[(size_t)(z + t) * np]);
-#endif
-#pragma unroll
-        for (int t = 0; t < U; ++t) step(v[t], (unsigned)(slice0 + z + t));
-    }
-    for (; z < count; ++z) step(__builtin_nontemporal_load((const fv*)&q[(size_t)z * np]), (unsigned)(slice0 + z));
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-        const int64_t kk = run[j].key();
-        key[j] = kk < key[j] ? kk : key[j];
-    }
-#pragma unroll
-    for (int j = 0; j < EPL; ++j)
-        if (kp[j]) *kp[j] = key[j];
-}
-
-// k_v5_wta that also keeps the winner's neighbouring q in the views' state planes nbr [3][h][w] (smx_common.h WtaRunNbr,
-// nbr_merge).  Same pixel decode, grid and skip_if.
-struct Wta5NbrArgs {
-    const float* q[2];
-    int64_t* keys[2];
-    float* nbr[2];
-    const unsigned* skip_if;
-    int fresh;
-};
-__global__ __launch_bounds__(256) void k_v5_wta_nbr(Wta5NbrArgs wa, int w, int h, int K, int count, int slice0) {
-    constexpr int EPL = 4;
-    const int hp = (h + 1) / 2;
-    const size_t np = (size_t)K * hp * (2 * OWS);
-    const size_t e0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * EPL;
-    if (e0 >= np || (wa.skip_if && flag_load(const_cast<unsigned*>(wa.skip_if)) != 0u)) return;
-    const float* __restrict__ q = wa.q[blockIdx.y] + e0;
-    int64_t* const keys = wa.keys[blockIdx.y];
-    float* const nbr = wa.nbr[blockIdx.y];
-    const size_t n = (size_t)w * h;
-    size_t pix[EPL];
-    bool in[EPL];
-    int64_t key[EPL];
-    float lo[EPL], hi[EPL], last[EPL];
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-        const size_t e = e0 + j;
-        const int prow = (int)(e / (2 * OWS)), rem = (int)(e - (size_t)prow * (2 * OWS));
-        const int p = rem >> 1, k = prow / hp, y = 2 * (prow - k * hp) + (rem & 1);
-        const int rho = p / (L - 1), i1 = p - (L - 1) * rho;
-        const int x = OWS * k + (k + 1 < K ? HW * i1 + rho : p);
-        in[j] = e < np && x < w && y < h;
-        pix[j] = in[j] ? (size_t)y * w + x : 0;
-        key[j] = in[j] && !wa.fresh ? keys[pix[j]] : KEY_IDENTITY;
-        const bool ld = key[j] != KEY_IDENTITY;        // (no winner yet: the state is not read)
-        lo[j] = ld ? nbr[pix[j]] : 0.0f;
-        hi[j] = ld ? nbr[n + pix[j]] : 0.0f;
-        last[j] = ld ? nbr[2 * n + pix[j]] : 0.0f;
-    }
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) any = any || in[j];
-    if (!any) return;
-    typedef float fv __attribute__((ext_vector_type(EPL)));
-    WtaRunNbr run[EPL] = {WtaRunNbr(nbr_prev0(key[0], last[0])), WtaRunNbr(nbr_prev0(key[1], last[1])),
-                          WtaRunNbr(nbr_prev0(key[2], last[2])), WtaRunNbr(nbr_prev0(key[3], last[3]))};
-    auto step = [&](const fv v, unsigned slice) {
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) run[j].step(v[j], slice);
-    };
-    const fv q0 = __builtin_nontemporal_load((const fv*)&q[0]);
-    step(q0, (unsigned)slice0);
-    int z = 1;
-    constexpr int U = 8;
-    for (; z + U <= count; z += U) {
-        fv v[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = __builtin_nontemporal_load((const fv*)&q[(size_t)(z + t) * np]);
-#pragma unroll
-        for (int t = 0; t < U; ++t) step(v[t], (unsigned)(slice0 + z + t));
-    }
-    for (; z < count; ++z) step(__builtin_nontemporal_load((const fv*)&q[(size_t)z * np]), (unsigned)(slice0 + z));
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-        key[j] = nbr_merge(run[j], key[j], (uint32_t)slice0, q0[j], &lo[j], &hi[j], &last[j]);
-        if (in[j]) {
-            keys[pix[j]] = key[j];
-            nbr[pix[j]] = lo[j];
-            nbr[n + pix[j]] = hi[j];
-            nbr[2 * n + pix[j]] = last[j];
-        }
-    }
-}
-
 }  // namespace v5
 
 int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G, uint8_t* const* mean_u8,
@@ -1331,42 +1184,6 @@ int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, a
     pa.eps = eps;
     const int K = v5::strips(w), NI = v5::bands(h);
     hipLaunchKernelGGL(v5::k_v5_perm, dim3((unsigned)(K * NI * (v5::BH / 2)), (unsigned)nviews), dim3(v5::CLP), 0, st, pa, w, h, K, NI);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int v5_wta_launch(int nviews, const float* const* q, int64_t* const* keys, int w, int h, int count, int slice0,
-                  const unsigned* skip_if, bool fresh, hipStream_t st) {
-    v5::Wta5Args wa;
-    wa.skip_if = skip_if;
-    wa.fresh = fresh ? 1 : 0;
-    for (int v = 0; v < 2; ++v) { wa.q[v] = q[v < nviews ? v : 0]; wa.keys[v] = keys[v < nviews ? v : 0]; }
-    const int K = v5::strips(w);
-    const size_t np = v5::q_plane_floats(w, h);
-    for (int v = 0; v < nviews; ++v)
-        if (((uintptr_t)wa.q[v] & 15) != 0) return fail(SMX_E_ARG, "v5_wta_launch: q scratch of view %d is not 16-byte aligned", v);
-    hipLaunchKernelGGL(v5::k_v5_wta, dim3((unsigned)((np / 4 + 255) / 256), (unsigned)nviews), dim3(256), 0, st, wa, w, h, K,
-                       count, slice0);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int v5_wta_nbr_launch(int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, int w, int h, int count,
-                      int slice0, const unsigned* skip_if, bool fresh, hipStream_t st) {
-    v5::Wta5NbrArgs wa;
-    wa.skip_if = skip_if;
-    wa.fresh = fresh ? 1 : 0;
-    for (int v = 0; v < 2; ++v) {
-        const int vv = v < nviews ? v : 0;
-        wa.q[v] = q[vv]; wa.keys[v] = keys[vv]; wa.nbr[v] = nbr[vv];
-    }
-    const int K = v5::strips(w);
-    const size_t np = v5::q_plane_floats(w, h);
-    for (int v = 0; v < nviews; ++v)
-        if (((uintptr_t)wa.q[v] & 15) != 0) return fail(SMX_E_ARG, "v5_wta_nbr_launch: q scratch of view %d is not 16-byte aligned", v);
-    if (count < 1) return SMX_OK;
-    hipLaunchKernelGGL(v5::k_v5_wta_nbr, dim3((unsigned)((np / 4 + 255) / 256), (unsigned)nviews), dim3(256), 0, st, wa, w, h, K,
-                       count, slice0);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }

@@ -8,6 +8,7 @@
 //
 // Reference citations are relative to the reference's stereo_matching_cuda/ directory.
 #include "smx_common.h"
+#include "smx_wta.h"
 
 namespace smx {
 
@@ -263,11 +264,13 @@ __global__ void k_ab(const float* __restrict__ Sp, const float* __restrict__ SIp
 
 // =====================================================================================
 // q = box(S_a)*I + box(S_b) and running WTA over the chunk's slices
-// (guidedFilter.cu:363-369 compute_q, :403-411 dispSelectOnGPU).  One lane per pixel; the key
-// min reproduces `if (best >= q) {...}` with slices ascending: ties go to the larger slice.
+// (guidedFilter.cu:363-369 compute_q, :403-411 dispSelectOnGPU).  One lane per pixel; the pixel's state, its merge with
+// the incoming key and the stores are WtaPixel (smx_wta.h): ties go to the larger slice like `if (best >= q) {...}` with
+// slices ascending.  NBR: also keeps the winner's neighbouring q in the view's state planes nbr [3][h][w].
 // =====================================================================================
+template <bool NBR>
 __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ Sb,
-                        const float* __restrict__ im, int64_t* __restrict__ keys,
+                        const float* __restrict__ im, int64_t* keys, float* nbr,
                         float* __restrict__ agg, int w, int h, int count, int slice0, int R) {
     int x = blockIdx.x * blockDim.x + threadIdx.x;
     int y = blockIdx.y;
@@ -276,51 +279,20 @@ __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ 
     BoxTaps t = box_taps(x, y, w, h, R);
     int64_t id = (int64_t)y * w + x;
     float I = im[id];
-    int64_t key = keys[id];
+    WtaPixel<NBR> px;
+    px.load(keys, nbr, (size_t)n, (size_t)id, true, false);
     for (int z = 0; z < count; ++z) {
         const int64_t po = (int64_t)z * n;
         float abar = box_eval(Sa + po, t);
         float bbar = box_eval(Sb + po, t);
         float m = abar * I;
         float q = m + bbar;
-        int64_t k = pack_key(q, (uint32_t)(slice0 + z));
-        key = k < key ? k : key;
+        if (z == 0) px.begin(q, (uint32_t)slice0);
+        else px.step(q, (uint32_t)(slice0 + z));
         if (agg) agg[po + id] = q;
     }
-    keys[id] = key;
-}
-
-// k_q_wta that also keeps the winner's neighbouring q in the view's state planes nbr [3][h][w] (smx_common.h WtaRunNbr,
-// nbr_merge: the same winner as the packed-key min above)
-__global__ void k_q_wta_nbr(const float* __restrict__ Sa, const float* __restrict__ Sb,
-                            const float* __restrict__ im, int64_t* __restrict__ keys, float* __restrict__ nbr,
-                            float* __restrict__ agg, int w, int h, int count, int slice0, int R) {
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y;
-    if (x >= w) return;
-    const int64_t n = (int64_t)w * h;
-    BoxTaps t = box_taps(x, y, w, h, R);
-    int64_t id = (int64_t)y * w + x;
-    float I = im[id];
-    const int64_t key = keys[id];
-    const bool ld = key != KEY_IDENTITY;                 // (no winner yet: the state is not read)
-    float lo = ld ? nbr[id] : 0.0f, hi = ld ? nbr[n + id] : 0.0f, last = ld ? nbr[2 * n + id] : 0.0f;
-    WtaRunNbr r(nbr_prev0(key, last));
-    float q0 = 0.0f;
-    for (int z = 0; z < count; ++z) {
-        const int64_t po = (int64_t)z * n;
-        float abar = box_eval(Sa + po, t);
-        float bbar = box_eval(Sb + po, t);
-        float m = abar * I;
-        float q = m + bbar;
-        q0 = z == 0 ? q : q0;
-        r.step(q, (uint32_t)(slice0 + z));
-        if (agg) agg[po + id] = q;
-    }
-    keys[id] = nbr_merge(r, key, (uint32_t)slice0, q0, &lo, &hi, &last);
-    nbr[id] = lo;
-    nbr[n + id] = hi;
-    nbr[2 * n + id] = last;
+    px.merge((uint32_t)slice0);
+    px.store(keys, nbr, (size_t)n, (size_t)id);
 }
 
 __global__ void k_init_keys(int64_t* keys, int64_t n) {
@@ -662,21 +634,13 @@ int launch_ab(const smx_params* p, const float* Sp, const float* SIp, const floa
 }
 
 int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                 int64_t* keys, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
+                 int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
     if (count <= 0) return SMX_OK;
     dim3 grid(cdiv(w, 256), h);
-    hipLaunchKernelGGL(k_q_wta, grid, dim3(256), 0, st, Sa, Sb, im, keys, agg, w, h, count, slice0,
-                       p->radius);
-    SMX_HIP(hipGetLastError());
-    return SMX_OK;
-}
-
-int launch_q_wta_nbr(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                     int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
-    if (count <= 0) return SMX_OK;
-    dim3 grid(cdiv(w, 256), h);
-    hipLaunchKernelGGL(k_q_wta_nbr, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0,
-                       p->radius);
+    if (nbr)
+        hipLaunchKernelGGL(k_q_wta<true>, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0, p->radius);
+    else
+        hipLaunchKernelGGL(k_q_wta<false>, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0, p->radius);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }

@@ -13,10 +13,9 @@ int launch_guid_finish(const smx_params* p, const float* S_im, const float* S_sq
                        float* cinv, uint8_t* mean_u8, int w, int h, hipStream_t st);
 int launch_ab(const smx_params* p, const float* Sp, const float* SIp, const float* mean_im,
               const float* cinv, float* A, float* B, int w, int h, int nplanes, hipStream_t st);
+// (nbr != NULL: the pass also keeps the winners' neighbours in the view's state planes [3][h][w])
 int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                 int64_t* keys, float* agg, int w, int h, int count, int slice0, hipStream_t st);
-int launch_q_wta_nbr(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                     int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st);
+                 int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st);
 int launch_init_keys(int64_t* keys, int64_t n, hipStream_t st);
 int launch_init_wta(float* best, float* dmap, int64_t n, hipStream_t st);
 int launch_apply_keys(const int64_t* keys, int64_t n, int dmin, float* best, float* dmap, hipStream_t st);

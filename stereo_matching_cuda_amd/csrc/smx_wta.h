@@ -1,0 +1,84 @@
+// smx_wta.h -- the winner-take-all pass (dispSelectOnGPU guidedFilter.cu:403-411 in packed-key form): what one pixel
+// holds while a pass runs over its q values (WtaPixel: the fused aggregation's pass in smx_wta.hip and the multi-kernel
+// path's k_q_wta use the same one), and the pass over materialised q planes with its one launcher.
+#pragma once
+#include "smx_common.h"
+
+namespace smx {
+
+// One pixel of a pass: the key it comes in with (or the identity), the run over this pass's ascending slices, the merge of
+// the two, the stores.  NBR: the pass also keeps the winner's neighbouring q in the view's state planes nbr [3][n] (lo, hi,
+// last).  The numerics are WtaRun / WtaRunNbr / nbr_prev0 / nbr_merge (smx_common.h).
+//   load(keys, nbr, n, pix, on, fresh)   on: the pixel exists; fresh: the keys hold nothing yet -- start from the identity
+//   begin(q, slice0), step(q, slice) ..  the pass's slices in ascending order, the first one through begin
+//   merge(slice0)                        the run against what the pixel came in with
+//   store(keys, nbr, n, pix)
+template <bool NBR>
+struct WtaPixel;
+
+template <>
+struct WtaPixel<false> {
+    int64_t key;
+    WtaRun run;             // (the winner of this pass's slices in the float domain, packed once)
+    __device__ inline void load(const int64_t* keys, const float*, size_t, size_t pix, bool on, bool fresh) {
+        key = on && !fresh ? keys[pix] : KEY_IDENTITY;
+    }
+    __device__ inline void begin(float q, uint32_t slice0) { run.step(q, slice0); }
+    __device__ inline void step(float q, uint32_t slice) { run.step(q, slice); }
+    __device__ inline void merge(uint32_t) {
+        const int64_t kk = run.key();
+        key = kk < key ? kk : key;
+    }
+    __device__ inline void store(int64_t* keys, float*, size_t, size_t pix) const { keys[pix] = key; }
+};
+
+template <>
+struct WtaPixel<true> {
+    int64_t key;
+    float lo, hi, last, q0 = 0.0f;
+    WtaRunNbr run{0.0f};
+    __device__ inline void load(const int64_t* keys, const float* nbr, size_t n, size_t pix, bool on, bool fresh) {
+        key = on && !fresh ? keys[pix] : KEY_IDENTITY;
+        const bool ld = key != KEY_IDENTITY;            // (no winner yet: the state is not read)
+        lo = ld ? nbr[pix] : 0.0f;
+        hi = ld ? nbr[n + pix] : 0.0f;
+        last = ld ? nbr[2 * n + pix] : 0.0f;
+        run = WtaRunNbr(nbr_prev0(key, last));
+    }
+    __device__ inline void begin(float q, uint32_t slice0) { q0 = q; run.step(q, slice0); }     // (nbr_merge wants the first q)
+    __device__ inline void step(float q, uint32_t slice) { run.step(q, slice); }
+    __device__ inline void merge(uint32_t slice0) { key = nbr_merge(run, key, slice0, q0, &lo, &hi, &last); }
+    __device__ inline void store(int64_t* keys, float* nbr, size_t n, size_t pix) const {
+        keys[pix] = key;
+        nbr[pix] = lo;
+        nbr[n + pix] = hi;
+        nbr[2 * n + pix] = last;
+    }
+};
+
+// Which pixel an element of a q plane belongs to
+enum WtaOrder {
+    WTA_NATURAL = 0,    // [h][w]: the ring walker's planes, the caller's volume
+    WTA_COMB = 1,       // the comb walker's row-pair scratch (smx_agg_v5.h q_plane_floats, q_pixel)
+};
+
+// A pass over `count` planes (slices slice0 ..) of up to two views; keys [n] and nbr [3][n] stay in pixel order
+struct WtaPass {
+    const float* q[2];
+    int64_t* keys[2];
+    float* nbr[2];            // NULL: the plain pass
+    size_t plane;             // floats from one slice's plane to the next
+    size_t n;                 // pixels (w * h)
+    int w, h, K;              // (K: strips of the comb scratch)
+    const unsigned* gate;     // the pass runs iff gate == NULL || (*gate != 0) == gate_nonzero: which walker's planes count
+    int gate_nonzero;
+    int fresh;                // != 0: the keys hold nothing yet: start from the identity instead of loading them
+};
+
+// The one launcher: `nviews` views, q planes `plane` floats apart, nbr == NULL for the plain pass.  Natural order takes two
+// pixels per lane where every plane can be read in 8-byte units; comb order takes four and wants 16-byte aligned planes
+// (SMX_E_ARG otherwise).  count < 1: no launch.
+int wta_launch(WtaOrder order, int nviews, const float* const* q, int64_t* const* keys, float* const* nbr, int w, int h,
+               size_t plane, int count, int slice0, const unsigned* gate, int gate_nonzero, bool fresh, hipStream_t st);
+
+}  // namespace smx

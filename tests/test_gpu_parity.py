@@ -447,7 +447,7 @@ def test_comb_walker_fuzz(orc, seed):
     r = _device_pair(Il, Ir, D, path=5, dminl=dminl, dminr=dminr, want_agg=True, params=p)
     for k in KEYS + ("aggl", "aggr"):
         _eq(r[k], want[k], f"seed {seed} w={w} h={h} D={D} {k}")
-    r = _device_pair(Il, Ir, D, path=5, dminl=dminl, dminr=dminr, want_agg=False, params=p)     # the comb-ordered scratch + k_v5_wta
+    r = _device_pair(Il, Ir, D, path=5, dminl=dminl, dminr=dminr, want_agg=False, params=p)     # the comb-ordered scratch + k_wta<Comb, 4, false>
     for k in KEYS:
         _eq(r[k], want[k], f"seed {seed} w={w} h={h} D={D} scratch layout {k}")
     # the reference's calling convention: materialised cost volumes through the same kernel (guidedFilter.cu:198)

@@ -1,6 +1,6 @@
 """Sub-pixel refinement on the GPU (smx_dev_aggregate_wta*_nbr, smx_dev_subpixel_pair, PairPipeline(subpixel=...), the
 context and smx_main --subpixel), bit-exact against tests/subpix_ref.py.  Every neighbour run passes no d_agg, so the WTA
-pass over the walker's own scratch (k_v5_wta_nbr for the comb walker) is what is tested; the reference volume comes from a
+pass over the walker's own scratch (k_wta<Comb, 4, true> for the comb walker) is what is tested; the reference volume comes from a
 separate run with want_agg, or from the oracle.
 
 Run on the GPU box:  python -m pytest tests -m gpu -q -k subpix

@@ -3,7 +3,7 @@ python tools/subpix_time.py [workload] [repeats]
 Two PairPipelines on the synthetic pair, one plain and one with subpixel="parabola", in one process; each repeat times N
 steps of one, then N of the other (alternating, so that clocks and caches drift alike for both).  Prints ms per pair step
 (aggregate + finish, + smx_dev_subpixel_pair for the sub-pixel one; host clock around N steps ended by a synchronise).
-Kernel times: run it under `rocprofv3 --kernel-trace --stats` (k_v5_wta against k_v5_wta_nbr, k_subpixel_pair)."""
+Kernel times: run it under `rocprofv3 --kernel-trace --stats` (k_wta<Comb, 4, false> against k_wta<Comb, 4, true>, k_subpixel_pair)."""
 import os
 import sys
 import time

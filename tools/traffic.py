@@ -6,7 +6,7 @@ pmc_WRITE_SIZE) into the HBM-traffic figure bench.py reports as roofline.traffic
 
 Per MI355X_MICROARCH.md (HBM / rocprofv3): FETCH_SIZE and WRITE_SIZE come from separate --pmc passes
 and are in KiB; on gfx950 FETCH_SIZE reports half of the bytes of a coalesced stream.  The x2 is
-checked here on k_v5_wta / k_v4_wta2, which read the aggregated volumes exactly once (known byte count: the
+checked here on k_wta<Comb, 4, false> / k_wta<Natural, 2, false>, which read the aggregated volumes exactly once (known byte count: the
 bench's 2 x 1242 x 375 x 192 floats + the key planes)."""
 import collections
 import csv
@@ -14,7 +14,7 @@ import glob
 import json
 import os, sys
 
-AGG_KERNELS = ("k_v4_", "k_v5_")      # every kernel of the fused aggregation call (either walker)
+AGG_KERNELS = ("k_v4_", "k_v5_", "k_wta<")      # every kernel of the fused aggregation call (either walker, the WTA pass)
 WALKERS = ("k_v5_walk", "k_v4_walk")
 
 

@@ -1,4 +1,4 @@
-// HBM read ceiling on gfx950 for the access shape of the WTA pass (k_v5_wta): every lane walks `planes` planes of a
+// HBM read ceiling on gfx950 for the access shape of the WTA pass (k_wta<Comb, 4, false>, csrc/smx_wta.hip): every lane walks `planes` planes of a
 // 715 MB volume with 16-byte nt loads, 8 in flight, one lane per 16 bytes of a plane -- and the same bytes as one flat stream.
 // Question (round 5): the WTA pass reads q at 5.6 TB/s; is that the machine's read ceiling for a volume that was written just
 // before, or the kernel's?
