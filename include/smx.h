@@ -4,7 +4,8 @@
  *
  * This is the drop-in boundary for the one hot path of hamza1030/stereo_matching_cuda:
  *   gray -> cost volume -> guided-filter aggregation + winner-take-all -> LR check -> fill,
- * and, beyond the reference, an optional weighted-median refinement of the filled map (smx_weighted_median).
+ * and, beyond the reference, an optional weighted-median refinement of the filled map (smx_weighted_median) and an
+ * optional speckle filter in front of the fill (smx_speckle_filter).
  * Every entry point cites the reference host function it replaces (paths relative to the
  * reference's stereo_matching_cuda/ directory).  Plain pointers and sizes only.
  *
@@ -423,6 +424,50 @@ int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t
  * the census volumes; th_color / th_grad / alpha of smx_params are unused, radius, eps and d_lr apply as always.  The code
  * and chunk buffers are allocated on first use.  smx_ctx_stereo_pair_async returns SMX_E_ARG while census is on. */
 int smx_ctx_set_cost(smx_ctx* ctx, int mode, const smx_census_params* census);
+
+/* ------------------------------------------------------------------------------------
+ * Speckle removal (not a stage of the reference; opt-in, between the LR check and fill_occlusion)
+ * ---------------------------------------------------------------------------------- */
+
+/* OpenCV's filterSpeckles rule: small islands of mutually consistent disparity are invalidated, so that the scan-line
+ * fill (and wmf "occluded") replaces them.  Defaults: max_size 200, max_diff 1.0f.
+ *   counts:   a pixel p counts iff disp[p] is finite and passes fill_occlusion's validity test against vmin, i.e.
+ *             (float)(int)disp[p] >= vmin with the truncation toward zero (saturating at +-2^31) and the comparison of
+ *             k_fill_occlusion.  NaN and +-inf never count; -0.0 is 0; the LR-check marker dmin - 100 does not count
+ *             (with vmin = dmin).
+ *   joined:   4-neighbours p, q are joined iff both count and fabsf(disp[p] - disp[q]) <= max_diff, evaluated in f32
+ *             without contraction (numpy float32 gives the same bits), fractional (sub-pixel) maps included.
+ *   components: the connected components of that graph (the relation is not transitive; the components are well
+ *             defined: a chain a, a + 1, a + 2 is one component at max_diff 1).
+ *   result:   out[p] = new_val iff p counts and its component has <= max_size pixels; every other pixel is copied bit
+ *             for bit.  max_size == 0 copies the map.
+ * d_out == d_disp is allowed.  Valid: max_size >= 0, max_diff finite and >= 0, w, h >= 1, w*h < 2^31 (SMX_E_ARG
+ * otherwise); a workspace smaller than smx_speckle_workspace_bytes(w, h) is SMX_E_WS (about 8 bytes per pixel: a u32
+ * label plane and a u32 size plane; 0 for invalid w, h).  The workspace needs no alignment and may hold anything.
+ * smx_dev_speckle_filter: device pointers, four kernel launches on `stream`, no allocation, no synchronisation
+ * (graph-capturable); it touches only [0, smx_speckle_workspace_bytes) of d_ws and the w*h floats of d_out.  The result
+ * does not depend on scheduling: it is the same bits in every run.
+ * smx_speckle_filter: host pointers, synchronous. */
+typedef struct smx_speckle_params {
+    int max_size;     /* components of at most this many pixels are invalidated */
+    float max_diff;   /* largest difference between joined 4-neighbours */
+} smx_speckle_params;
+void smx_default_speckle_params(smx_speckle_params* p);
+size_t smx_speckle_workspace_bytes(int w, int h);
+int smx_dev_speckle_filter(const smx_speckle_params* p, const float* d_disp, float* d_out, int w, int h, float vmin,
+                           float new_val, void* d_ws, size_t ws_bytes, void* stream);
+int smx_speckle_filter(const smx_speckle_params* p, const float* disp, float* out, int w, int h, float vmin,
+                       float new_val);
+/* Test hook, NOT part of the stable contract (it may change or go with the kernels): the tile of the labelling kernel
+ * (columns, rows), so that the tests put their shapes and components on the seams between tiles. */
+int smx_speckle_geometry(int* tile_cols, int* tile_rows);
+/* Speckle removal of this context: NULL switches it off (the default).  While it is on, smx_ctx_stereo_pair filters the
+ * left map after the LR check with vmin = dminl, new_val = dminl - 100; out->filled is the fill of the despeckled map and
+ * the sub-pixel fit's sub_filled takes the despeckled map for its test; out->occlusion stays the LR-check map.
+ * smx_ctx_stereo_pair_async returns SMX_E_ARG.  smx_ctx_speckle_map copies the despeckled map of the last synchronous
+ * smx_ctx_stereo_pair of the context (n floats); SMX_E_ARG if that pair ran without it.  Buffers are allocated on first use. */
+int smx_ctx_set_speckle(smx_ctx* ctx, const smx_speckle_params* p);
+int smx_ctx_speckle_map(smx_ctx* ctx, float* despeckled);
 
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);

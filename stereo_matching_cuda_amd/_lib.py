@@ -43,6 +43,11 @@ class CensusParams(C.Structure):
     _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("th", C.c_int)]
 
 
+class SpeckleParams(C.Structure):
+    """smx_speckle_params: the connected-component speckle filter (not a stage of the reference)."""
+    _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -67,6 +72,7 @@ _vp, _i, _i64, _f, _sz, _u64, _u32 = (C.c_void_p, C.c_int, C.c_int64, C.c_float,
 _PP = C.POINTER(Params)
 _WP = C.POINTER(WmfParams)
 _CP = C.POINTER(CensusParams)
+_SP = C.POINTER(SpeckleParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -133,6 +139,13 @@ SIGNATURES = {
     "smx_dev_census_cost_pair": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "smx_census_cost": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_cost": (_i, [_vp, _i, _CP]),
+    "smx_default_speckle_params": (None, [_SP]),
+    "smx_speckle_workspace_bytes": (_sz, [_i, _i]),
+    "smx_dev_speckle_filter": (_i, [_SP, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
+    "smx_speckle_filter": (_i, [_SP, _vp, _vp, _i, _i, _f, _f]),
+    "smx_speckle_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "smx_ctx_set_speckle": (_i, [_vp, _SP]),
+    "smx_ctx_speckle_map": (_i, [_vp, _vp]),
 }
 
 # smx.h SMX_COST_*: the matching costs by name
@@ -204,6 +217,12 @@ def default_wmf_params():
 def default_census_params():
     p = CensusParams()
     lib().smx_default_census_params(C.byref(p))
+    return p
+
+
+def default_speckle_params():
+    p = SpeckleParams()
+    lib().smx_default_speckle_params(C.byref(p))
     return p
 
 

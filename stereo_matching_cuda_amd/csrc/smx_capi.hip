@@ -663,6 +663,49 @@ int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const flo
     return SMX_OK;
 }
 
+// ---- speckle removal (not in the reference; smx_speckle.hip) -------------------------------------------
+void smx_default_speckle_params(smx_speckle_params* p) {
+    if (!p) return;
+    p->max_size = 200; p->max_diff = 1.0f;
+}
+
+static bool speckle_params_ok(const smx_speckle_params* p) {
+    return p && p->max_size >= 0 && isfinite(p->max_diff) && p->max_diff >= 0.0f;
+}
+static bool speckle_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
+
+size_t smx_speckle_workspace_bytes(int w, int h) { return speckle_shape_ok(w, h) ? speckle_workspace_bytes(w, h) : 0; }
+
+int smx_speckle_geometry(int* tile_cols, int* tile_rows) {
+    SMX_ARG(tile_cols && tile_rows);
+    speckle_tile(tile_cols, tile_rows);
+    return SMX_OK;
+}
+
+int smx_dev_speckle_filter(const smx_speckle_params* p, const float* d_disp, float* d_out, int w, int h, float vmin,
+                           float new_val, void* d_ws, size_t ws_bytes, void* stream) {
+    SMX_ARG(speckle_params_ok(p) && d_disp && d_out && speckle_shape_ok(w, h));
+    if (!d_ws || ws_bytes < speckle_workspace_bytes(w, h))
+        return fail(SMX_E_WS, "smx_dev_speckle_filter: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
+                    speckle_workspace_bytes(w, h));
+    return launch_speckle_filter(p->max_size, p->max_diff, d_disp, d_out, w, h, vmin, new_val, d_ws, (hipStream_t)stream);
+}
+
+int smx_speckle_filter(const smx_speckle_params* p, const float* disp, float* out, int w, int h, float vmin,
+                       float new_val) {
+    SMX_ARG(speckle_params_ok(p) && disp && out && speckle_shape_ok(w, h));
+    const size_t bytes = (size_t)w * h * sizeof(float), wsb = speckle_workspace_bytes(w, h);
+    DevBuf dD, dW;
+    SMX_HIP(dD.alloc(bytes));
+    SMX_HIP(dW.alloc(wsb));
+    SMX_HIP(hipMemcpy(dD.p, disp, bytes, hipMemcpyHostToDevice));
+    int rc = smx_dev_speckle_filter(p, dD.as<float>(), dD.as<float>(), w, h, vmin, new_val, dW.p, wsb, nullptr);
+    if (rc) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(hipMemcpy(out, dD.p, bytes, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
 // ---- census / Hamming matching cost (not in the reference; smx_census.hip) ----------------------------
 void smx_default_census_params(smx_census_params* p) {
     if (!p) return;
@@ -754,6 +797,11 @@ struct smx_ctx {
     smx_census_params census;
     int census_chunk = 0;
     DevBuf codes, ccost;
+    // speckle removal (smx_ctx_set_speckle): the despeckled left map [h][w] and the filter's workspace, allocated on first use
+    bool speckle = false;
+    bool spk_valid = false;     // the map belongs to the last synchronous pair
+    smx_speckle_params spk_params;
+    DevBuf spk, spk_ws;
     // pipelined entry (smx_ctx_stereo_pair_async): two slots of device inputs / results and pinned host staging, created
     // on first use.  Staging of a slot: [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l
     // mean_r | status word] coming down.
@@ -887,8 +935,18 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
     if ((rc = smx_dev_finish_pair(p, keysL, w, h, dminl, dminr, dminl - 100, (float)dminl, bestL, mapL, occ, fil, st))) return rc;
+    const float* kept = occ;        // the map whose validity test says which pixels the fill replaced
+    if (c->speckle) {
+        // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
+        float* spk = c->spk.as<float>();
+        if ((rc = smx_dev_speckle_filter(&c->spk_params, occ, spk, w, h, (float)dminl, (float)(dminl - 100), c->spk_ws.p,
+                                         speckle_workspace_bytes(w, h), st)))
+            return rc;
+        if ((rc = launch_fill_occlusion(spk, fil, w, h, (float)dminl, st))) return rc;
+        kept = spk;
+    }
     if (!subpix) return SMX_OK;
-    return smx_dev_subpixel_pair(c->subpix, keysL, c->nbr.as<float>(), mapL, occ, fil, w, h, dminl, c->sub.as<float>(),
+    return smx_dev_subpixel_pair(c->subpix, keysL, c->nbr.as<float>(), mapL, kept, fil, w, h, dminl, c->sub.as<float>(),
                                  c->subf.as<float>(), st);
 }
 
@@ -923,7 +981,9 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
             SMX_HIP(c->ccost.alloc(2 * (size_t)c->census_chunk * fb));
         }
     }
+    if (c->speckle && !c->spk.p) { SMX_HIP(c->spk.alloc(fb)); SMX_HIP(c->spk_ws.alloc(speckle_workspace_bytes(c->w, c->h))); }
     c->sub_valid = false;
+    c->spk_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     stage_mark(ST_BEGIN, st);
     SMX_HIP(hipMemcpyAsync(dL, gray_l, n, hipMemcpyHostToDevice, st));
@@ -947,6 +1007,7 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     SMX_HIP(hipStreamSynchronize(st));
     if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
     c->sub_valid = subpix;
+    c->spk_valid = c->speckle;
     return SMX_OK;
 }
 
@@ -971,6 +1032,27 @@ int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
         c->census = p;
     }
     c->cost_mode = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_speckle(smx_ctx* c, const smx_speckle_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!speckle_params_ok(p))
+            return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs max_size >= 0 and a finite max_diff >= 0");
+        if (!speckle_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs w*h < 2^31");
+        c->spk_params = *p;
+    }
+    c->speckle = p != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_speckle_map(smx_ctx* c, float* despeckled) {
+    SMX_ARG(c);
+    int rc;
+    if ((rc = ctx_check_device(c, "smx_ctx_speckle_map"))) return rc;
+    if (!c->spk_valid) return fail(SMX_E_ARG, "smx_ctx_speckle_map: the last smx_ctx_stereo_pair ran without speckle removal");
+    if (despeckled) SMX_HIP(hipMemcpy(despeckled, c->spk.p, c->n * sizeof(float), hipMemcpyDeviceToHost));
     return SMX_OK;
 }
 
@@ -1014,6 +1096,7 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     int rc;
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
+    if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)

@@ -40,4 +40,9 @@ int launch_subpixel_pair(int mode, const int64_t* keys, const float* nbr, const 
 int launch_census(int rx, int ry, const uint8_t* img, uint64_t* code, int w, int h, int nimages, hipStream_t st);
 int launch_census_cost_pair(int t, const uint64_t* code, float* cost_l, float* cost_r, int w, int h, int dminl, int dminr,
                             int s_begin, int s_end, hipStream_t st);
+// smx_speckle.hip: the connected-component filter (smx_dev_speckle_filter); ws: speckle_workspace_bytes(w, h) bytes
+size_t speckle_workspace_bytes(int w, int h);
+int launch_speckle_filter(int max_size, float max_diff, const float* disp, float* out, int w, int h, float vmin,
+                          float new_val, void* ws, hipStream_t st);
+void speckle_tile(int* tw, int* th);
 }  // namespace smx

@@ -25,7 +25,7 @@ class PairPipeline:
 
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
-                 wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None):
+                 wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -38,13 +38,20 @@ class PairPipeline:
         (include/smx.h smx_dev_census, smx_dev_census_cost_pair; census_params: CensusParams, None = the defaults): the
         pipeline owns the codes self.codes (2, h, w) and a cost buffer self.census_cost of `slices_in_flight` slices per
         view, which the max_ws_bytes bound counts, and aggregate(gray_l, gray_r) runs cost chunk -> aggregation from
-        that chunk over its slice range.  th_color / th_grad / alpha of `params` are unused then."""
+        that chunk over its slice range.  th_color / th_grad / alpha of `params` are unused then.
+        speckle: None, True (the defaults) or SpeckleParams -- speckle removal (not a stage of the reference;
+        smx_dev_speckle_filter behind the finish): self.despeckled = self.occlusion without its small connected components
+        (vmin = dminl, new_val = dminl - 100), self.filled = the fill of self.despeckled, and the sub-pixel fit and
+        wmf="occluded" take self.despeckled where they took self.occlusion, which stays the LR-check map.  The pipeline
+        owns the filter's workspace.  With None nothing is allocated or launched."""
         if cost not in (None, "census"):
             raise ValueError(f"cost must be None or 'census', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
             raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
         if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
             raise ValueError(f"subpixel must be None, 'parabola' or 'equiangular', not {subpixel!r}")
+        if speckle is not None and speckle is not True and not isinstance(speckle, _lib.SpeckleParams):
+            raise ValueError(f"speckle must be None, True or SpeckleParams, not {speckle!r}")
         self.lib = _lib.lib()
         self.w, self.h, self.size_d = int(w), int(h), int(size_d)
         self.n = self.w * self.h
@@ -88,6 +95,10 @@ class PairPipeline:
         self.nbr = torch.empty((2, 3, self.h, self.w), **f) if subpixel else None
         self.sub = torch.empty((2, self.h, self.w), **f) if subpixel else None
         self.sub_filled = torch.empty((self.h, self.w), **f) if subpixel else None
+        self.speckle = _lib.default_speckle_params() if speckle is True else speckle
+        self.despeckled = torch.empty((self.h, self.w), **f) if self.speckle else None
+        self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
+        self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
         self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost else None
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
@@ -227,10 +238,27 @@ class PairPipeline:
             _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                              self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                              _dp(self.occlusion), _dp(self.filled), st))
+        if self.speckle:
+            self.despeckle()
         if self.subpixel:
             self.subpixel_maps()
         if self.wmf:
             self.refine()
+
+    def despeckle(self):
+        """self.despeckled = the LR-checked left map without its small connected components (smx_dev_speckle_filter), and
+        self.filled rewritten as the fill of that map."""
+        with self._on_device():
+            L, st = self.lib, self._stream()
+            _lib.check(L.smx_dev_speckle_filter(C.byref(self.speckle), _dp(self.occlusion), _dp(self.despeckled), self.w,
+                                                self.h, float(self.dminl), float(self.dminl - 100), _dp(self.speckle_ws),
+                                                self.speckle_ws_bytes, st))
+            self.filled.copy_(self.despeckled)
+            _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+
+    def _kept(self):
+        """The map whose validity test tells which pixels the fill replaced."""
+        return self.despeckled if self.speckle else self.occlusion
 
     def subpixel_maps(self):
         """Sub-pixel maps of both views from the keys, the neighbour state and the finish's maps (smx_dev_subpixel_pair,
@@ -238,7 +266,7 @@ class PairPipeline:
         where it did not."""
         with self._on_device():
             _lib.check(self.lib.smx_dev_subpixel_pair(_lib.SUBPIX_MODES[self.subpixel], _dp(self.keys), _dp(self.nbr),
-                                                      _dp(self.dmap), _dp(self.occlusion), _dp(self.filled), self.w,
+                                                      _dp(self.dmap), _dp(self._kept()), _dp(self.filled), self.w,
                                                       self.h, self.dminl, _dp(self.sub), _dp(self.sub_filled),
                                                       self._stream()))
 
@@ -248,13 +276,14 @@ class PairPipeline:
         if self._guide is None:
             raise RuntimeError("refine() needs the left image: run an aggregation first")
         with self._on_device():
-            sel = self.occlusion if self.wmf == "occluded" else None
+            sel = self._kept() if self.wmf == "occluded" else None
             _lib.check(self.lib.smx_dev_weighted_median(C.byref(self.wmf_params), _dp(self._guide), _dp(self.filled),
                                                         _dp(sel), _dp(self.refined), self.w, self.h, self.dminl,
                                                         self.size_d, self._stream()))
 
     def finish_per_call(self):
-        """The same through the per-stage entry points (the reference's call sequence, seven launches)."""
+        """The same through the per-stage entry points (the reference's call sequence, seven launches); with speckle
+        removal on, despeckle() behind them, as in finish().  The sub-pixel fit and the weighted median are not run."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_dev_init_wta(_dp(self.best), _dp(self.dmap), 2 * self.n, st))
@@ -267,6 +296,8 @@ class PairPipeline:
                                                   self.dminl - 100, self.w, self.h, st))  # main.cu:149
             self.filled.copy_(self.occlusion)                                    # main.cu:153
             _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+        if self.speckle:
+            self.despeckle()
 
     def run(self, gray_l, gray_r):
         self.aggregate(gray_l, gray_r)
@@ -289,6 +320,8 @@ class PairPipeline:
             r["aggl"], r["aggr"] = c(self.agg[0]), c(self.agg[1])
         if self.wmf:
             r["refined"] = c(self.refined)
+        if self.speckle:
+            r["despeckled"] = c(self.despeckled)
         if self.subpixel:
             r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.sub[0]), c(self.sub[1]), c(self.sub_filled)
         return r

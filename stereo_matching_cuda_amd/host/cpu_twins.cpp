@@ -14,6 +14,7 @@
 #include "integral.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "speckle.cuh"
 #include "wmf.cuh"
 
 using std::vector;
@@ -265,4 +266,39 @@ void weighted_medianOnCPU(const unsigned char* guide, const float* disparity, co
                 if (!found && total && 2 * cum >= total) { out[i] = (float)(dmin + k); found = true; }
             }
         }
+}
+
+// ---- speckle.cuh (not in the reference) ------------------------------------------------------
+// The speckle filter of include/smx.h as a flood fill: one breadth-first search per component.
+void speckle_filterOnCPU(const float* disparity, float* out, const int w, const int h, float vmin, float new_val,
+                         const smx_speckle_params& p) {
+    const size_t n = (size_t)w * h;
+    auto counts = [&](float v) {
+        if (!(std::fabs(v) <= 3.402823466e38f)) return false;
+        const float t = v >= 2147483648.0f ? 2147483648.0f : v < -2147483648.0f ? -2147483648.0f : (float)(int)v;
+        return t >= vmin;
+    };
+    vector<char> seen(n, 0);
+    vector<size_t> comp;
+    for (size_t i = 0; i < n; ++i) out[i] = disparity[i];
+    for (size_t s = 0; s < n; ++s) {
+        if (seen[s] || !counts(disparity[s])) continue;
+        comp.assign(1, s);
+        seen[s] = 1;
+        for (size_t k = 0; k < comp.size(); ++k) {
+            const size_t i = comp[k];
+            const int x = (int)(i % w), y = (int)(i / w);
+            const size_t nb[4] = {i - 1, i + 1, i - w, i + w};
+            const bool in[4] = {x > 0, x + 1 < w, y > 0, y + 1 < h};
+            for (int d = 0; d < 4; ++d) {
+                if (!in[d] || seen[nb[d]] || !counts(disparity[nb[d]])) continue;
+                volatile float diff = disparity[i] - disparity[nb[d]];     // one rounded f32 difference
+                if (!(std::fabs(diff) <= p.max_diff)) continue;
+                seen[nb[d]] = 1;
+                comp.push_back(nb[d]);
+            }
+        }
+        if (comp.size() <= (size_t)p.max_size)
+            for (size_t i : comp) out[i] = new_val;
+    }
 }

@@ -29,6 +29,12 @@
 //                     same twelve images, the two cost images from the census volumes.  --census-window WxH gives the
 //                     window in pixels (odd, 3x3 .. 9x7; default 9x7), --census-th N the truncation (>= 1; default 62).
 //                     Composes with --wmf, --subpixel, --pfm and --png16; not with --ngpu or --pipeline
+//   --speckle SIZE[,DIFF]  speckle removal between the LR check and the fill (smx_speckle_filter; not in the reference), on
+//                     every single-GPU path: connected components of at most SIZE pixels whose 4-neighbours differ by at
+//                     most DIFF (default 1) are invalidated like LR failures.  Writes occlu_mapl_despeckled.png beside
+//                     the 12 images; occlu_mapl_filled.png (and --wmf occluded, --subpixel, --pfm, --png16 behind it) then
+//                     come from the despeckled map.  Composes with --wmf, --subpixel, --cost census; not with --ngpu or
+//                     --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -54,6 +60,7 @@
 #include "occlusion.cuh"
 #include "png_io.h"
 #include "rgb_to_grayscale.cuh"
+#include "speckle.cuh"
 #include "winner_take_all.cuh"
 #include "wmf.cuh"
 
@@ -80,6 +87,8 @@ struct Options {
     int subpixel = 0;        // 0 = off, else SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR
     bool census = false;     // --cost census
     smx_census_params census_params;
+    bool speckle = false;    // --speckle
+    smx_speckle_params speckle_params;
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
     bool pipeline = false;
@@ -90,6 +99,7 @@ struct Options {
 Options parse(int argc, char** argv) {
     Options o;
     smx_default_census_params(&o.census_params);
+    smx_default_speckle_params(&o.speckle_params);
     bool census_option = false;     // --census-window / --census-th seen
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -152,6 +162,20 @@ Options parse(int argc, char** argv) {
             }
             o.census_params.th = (int)th;
         }
+        else if (a == "--speckle") {
+            std::string v;
+            value(v);
+            int size = -1;
+            float diff = 1.0f;
+            char comma = 0, rest = 0;
+            const int got = std::sscanf(v.c_str(), "%d%c%f%c", &size, &comma, &diff, &rest);
+            o.speckle = true;
+            if (o.ok && (!(got == 1 || (got == 3 && comma == ',')) || size < 0 || !(diff >= 0.0f) || !(diff <= 3.4e38f))) {
+                std::fprintf(stderr, "--speckle needs SIZE[,DIFF] with SIZE >= 0 and a finite DIFF >= 0, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.speckle_params.max_size = size; o.speckle_params.max_diff = diff;
+        }
         else if (a == "--ngpu") { std::string v; value(v); o.ngpu = std::atoi(v.c_str()); }
         else if (a == "--pipeline") o.pipeline = true;
         else if (a == "--pairs") { std::string v; value(v); o.pairs = std::atoi(v.c_str()); }
@@ -200,6 +224,10 @@ int main(int argc, char** argv) {
     }
     if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
         std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
+    if (opt.speckle && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--speckle cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
     if (opt.ngpu < 0 || opt.ngpu > smx_device_count()) {
@@ -260,6 +288,7 @@ int main(int argc, char** argv) {
     }
     std::vector<float> occlusion, filled;
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
+    std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     if (!fused) {
         // the reference's data flow: every stage is a host -> device -> host round trip
         for (int v = 0; v < 2; ++v) cost[v].resize((size_t)n * size_d);
@@ -275,7 +304,12 @@ int main(int argc, char** argv) {
         occlusion = dmap[0];
         detect_occlusion(occlusion.data(), dmap[1].data(), dmin[0] - 100, unused_u8[0].data(),
                          unused_u8[1].data(), w, h);                                   // main.cu:149-150
-        filled = occlusion;
+        if (opt.speckle) {
+            despeckled.resize(n);
+            speckle_filter(occlusion.data(), despeckled.data(), w, h, (float)d_lo, (float)(d_lo - 100), opt.speckle_params,
+                           host_compare);
+        }
+        filled = opt.speckle ? despeckled : occlusion;
         fill_occlusion(filled.data(), w, h, (float)d_lo);                              // main.cu:154-155
     } else {
         // device-resident: one call, the cost slices never leave the CU (only slice 0 of each volume
@@ -305,6 +339,7 @@ int main(int argc, char** argv) {
         else CHECK(smx_create(&smx_config().params, w, h, size_d, &ctx));
         if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
         if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
+        if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
@@ -341,6 +376,10 @@ int main(int argc, char** argv) {
             sub_filled.resize(n);
             CHECK(smx_ctx_subpixel_maps(ctx, nullptr, nullptr, sub_filled.data()));
         }
+        if (opt.speckle) {
+            despeckled.resize(n);
+            CHECK(smx_ctx_speckle_map(ctx, despeckled.data()));
+        }
         if (sh_create) CHECK(sh_destroy(sctx));
         else CHECK(smx_destroy(ctx));
         std::cout << "guided filter ok" << std::endl;
@@ -348,6 +387,12 @@ int main(int argc, char** argv) {
             std::vector<float> lr(dmap[0]);
             detect_occlusionOnCPU(lr.data(), dmap[1].data(), dmin[0] - 100, w, h);
             bool ok = check_errors(lr.data(), occlusion.data(), n);
+            if (opt.speckle) {
+                std::vector<float> twin(n);
+                speckle_filterOnCPU(lr.data(), twin.data(), w, h, (float)d_lo, (float)(d_lo - 100), opt.speckle_params);
+                ok = check_errors(twin.data(), despeckled.data(), n) && ok;
+                lr = twin;
+            }
             fill_occlusionOnCPU(lr.data(), w, h, (float)d_lo);
             ok = check_errors(lr.data(), filled.data(), n) && ok;
             if (ok) std::cout << "Occlusion ok!" << std::endl;
@@ -358,7 +403,8 @@ int main(int argc, char** argv) {
     if (!opt.wmf.empty()) {
         std::cout << "weighted median ..." << std::endl;
         refined.resize(n);
-        weighted_median(gray[0], filled.data(), opt.wmf == "occluded" ? occlusion.data() : nullptr, refined.data(), w, h,
+        float* kept = opt.speckle ? despeckled.data() : occlusion.data();     // whose test says what the fill replaced
+        weighted_median(gray[0], filled.data(), opt.wmf == "occluded" ? kept : nullptr, refined.data(), w, h,
                         d_lo, size_d, host_compare);
     }
     const double duration = (std::clock() - t_begin) / (double)CLOCKS_PER_SEC;
@@ -380,6 +426,10 @@ int main(int argc, char** argv) {
     for (const F32Out& o : f32_outputs) {
         const std::vector<unsigned char> img = normalise_like_reference(o.data, (size_t)n);
         if (!smx_png_write((outdir + "/" + o.name).c_str(), w, h, 1, img.data())) ++write_failures;
+    }
+    if (!despeckled.empty()) {
+        const std::vector<unsigned char> img = normalise_like_reference(despeckled.data(), (size_t)n);
+        if (!smx_png_write((outdir + "/occlu_mapl_despeckled.png").c_str(), w, h, 1, img.data())) ++write_failures;
     }
     if (!refined.empty()) {
         const std::vector<unsigned char> img = normalise_like_reference(refined.data(), (size_t)n);

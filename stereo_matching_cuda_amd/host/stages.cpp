@@ -7,6 +7,7 @@
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "speckle.cuh"
 #include "wmf.cuh"
 
 #include <vector>
@@ -136,5 +137,16 @@ void weighted_median(unsigned char* guide, float* disparity, float* select, floa
         std::vector<float> twin((size_t)w * h);
         weighted_medianOnCPU(guide, disparity, select, twin.data(), w, h, dmin, size_d, p);
         if (check_errors(twin.data(), out, w * h)) cout << "Weighted median ok!" << endl;
+    }
+}
+
+// not in the reference: speckle removal between the LR check and fill_occlusion (smx_main --speckle)
+void speckle_filter(float* disparity, float* out, const int w, const int h, float vmin, float new_val,
+                    const smx_speckle_params& p, bool host_gpu_compare) {
+    CHECK(smx_speckle_filter(&p, disparity, out, w, h, vmin, new_val));
+    if (host_gpu_compare) {
+        std::vector<float> twin((size_t)w * h);
+        speckle_filterOnCPU(disparity, twin.data(), w, h, vmin, new_val, p);
+        if (check_errors(twin.data(), out, w * h)) cout << "Speckle filter ok!" << endl;
     }
 }

@@ -44,7 +44,7 @@ class ShardedPair:
     """D-sharded stereo pair: local aggregation of this rank's slices, ONE all-reduce of both
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
     The census matching cost (PairPipeline(cost="census")) is not part of the sharded driver: cost="census" raises
-    ValueError."""
+    ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -53,6 +53,8 @@ class ShardedPair:
             raise ValueError("subpixel needs the whole slice range on one rank (world == 1)")
         if kw.get("cost") is not None:
             raise ValueError("the census cost is not part of the sharded driver: use PairPipeline(cost='census')")
+        if kw.get("speckle") is not None:
+            raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
         self.rank, self.world, self.group = rank, world, group
         s0, s1 = shard_range(size_d, rank, world)
         self.pipe = PairPipeline(w, h, size_d, s_begin=s0, s_end=s1, **kw)

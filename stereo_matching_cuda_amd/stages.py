@@ -145,6 +145,21 @@ def weighted_median(guide, disparity, dmin, size_d, select=None, params=None):
     return out
 
 
+def speckle_filter(disparity, vmin, new_val, params=None):
+    """Speckle removal of a disparity map (include/smx.h smx_speckle_filter; not a stage of the reference): connected
+    components of 4-neighbours that count (finite, fill_occlusion's test against vmin) and differ by at most
+    params.max_diff; the pixels of components of at most params.max_size pixels become new_val, every other pixel is
+    copied bit for bit.  Returns a new (h, w) float32 array."""
+    d = _c(disparity, np.float32)
+    if d.ndim != 2:
+        raise ValueError("speckle_filter expects an (h, w) float32 map")
+    h, w = d.shape
+    out = np.empty((h, w), np.float32)
+    p = params if params is not None else _lib.default_speckle_params()
+    _lib.check(_lib.lib().smx_speckle_filter(C.byref(p), _ptr(d), _ptr(out), w, h, float(vmin), float(new_val)))
+    return out
+
+
 def wmf_weights(params=None):
     """(spatial[0 .. 2 r^2], range[0 .. 255]) uint16 weight tables of the weighted median (smx_wmf_weights)."""
     p = params if params is not None else _lib.default_wmf_params()
