@@ -469,6 +469,57 @@ int smx_speckle_geometry(int* tile_cols, int* tile_rows);
 int smx_ctx_set_speckle(smx_ctx* ctx, const smx_speckle_params* p);
 int smx_ctx_speckle_map(smx_ctx* ctx, float* despeckled);
 
+/* ------------------------------------------------------------------------------------
+ * Semi-global matching (not a stage of the reference; opt-in alternative to the guided-filter aggregation)
+ * ---------------------------------------------------------------------------------- */
+
+/* SGM (Hirschmueller 2008) with constant penalties over whole cost volumes.  Defaults: p1 10, p2 120, paths 8 (libSGM's for
+ * a census cost of this size).  Valid: 0 <= p1 <= p2 <= 4095, paths 4 or 8; w, h >= 1, w*h < 2^31,
+ * 1 <= size_d <= SMX_SGM_MAX_D (SMX_E_ARG otherwise).
+ *   input:      one cost volume per view, f32, [z][y][x] (smx_dev_census_cost_pair, smx_dev_cost_volume).  Each value is
+ *               read as the integer C = c >= 0 ? (c <= 255 ? (int)c : 255) : 0, so NaN gives 0: the call is total, memory-
+ *               safe and deterministic on any bits.
+ *   directions: (dx, dy) = (1,0) (-1,0) (0,1) (0,-1) for paths 4; also (1,1) (-1,1) (1,-1) (-1,-1) for paths 8.
+ *   recurrence: for a direction r and a pixel p: L_r(p, d) = C(p, d) if p - r lies outside the image; otherwise, with
+ *               m = min_k L_r(p - r, k),
+ *                 L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + p1, L_r(p-r, d+1) + p1, m + p2) - m
+ *               where terms with d-1 < 0 or d+1 >= size_d are left out.  Integers throughout: L_r <= 255 + p2 <= 4350 and
+ *               S(p, d) = sum_r L_r(p, d) <= 34800, exact in u16 and in f32 in any order, so the result is the same bits
+ *               in every run whatever the schedule.
+ *   d_keys:     OUT only: d_keys[p] = smx_pack_key((float)S(p, z*), z*), z* the LARGEST z of minimal S (the project's tie
+ *               rule: the last slice of equal costs wins) -- the keys of a fresh winner-take-all over the f32 volume S.
+ *   d_agg:      optional, size_d * n floats: (float)S in [z][y][x].
+ *   d_nbr:      optional, 3n floats in the layout and meaning of the _nbr state after one whole-volume call:
+ *               lo = S(z* - 1) (NaN at z* = 0), hi = S(z* + 1) (NaN at z* = size_d - 1), last = S(size_d - 1);
+ *               smx_dev_subpixel_pair works on it unchanged.
+ * SGM needs the whole disparity range of a pixel at once: there is no s_begin / s_end, no accumulation into existing keys
+ * and no combination across D-shards.
+ * smx_dev_sgm_wta_pair: either cost pointer may be NULL (not both), the one-view form, whose outputs hold that one view;
+ * with both, d_keys holds 2n keys, d_agg two volumes and d_nbr 6n floats, left view first.  A fixed sequence of kernel
+ * launches on `stream` (5 for paths 4, 9 for paths 8), no allocation, no synchronisation (graph-capturable).  d_ws needs no
+ * alignment and may hold anything; fewer than smx_sgm_workspace_bytes(w, h, size_d, nviews) bytes is SMX_E_WS before
+ * anything is launched (about 3 bytes per pixel and disparity, size_d rounded up to 64; 0 for invalid sizes or nviews
+ * other than 1, 2).  Nothing is written outside the workspace and the stated extents; the inputs are not modified.
+ * smx_sgm_aggregate: host pointers, synchronous, one view.  agg (optional) receives S; best (optional, n floats) the
+ * winner's S and disp_map (optional, n floats) dmin + z*, both OUT only. */
+#define SMX_SGM_MAX_D 256
+typedef struct smx_sgm_params { int p1, p2; int paths; } smx_sgm_params;
+void smx_default_sgm_params(smx_sgm_params* p);
+size_t smx_sgm_workspace_bytes(int w, int h, int size_d, int nviews);
+int smx_dev_sgm_wta_pair(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                         int64_t* d_keys, float* d_agg, float* d_nbr, void* d_ws, size_t ws_bytes, void* stream);
+int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
+                      int size_d, int dmin);
+
+#define SMX_AGG_GUIDED 0   /* the reference's guided filter: the default */
+#define SMX_AGG_SGM 1
+/* Aggregation of this context.  With SMX_AGG_SGM (sgm: NULL = the defaults) smx_ctx_stereo_pair builds both whole cost
+ * volumes (census, or the reference cost read through the clamp above), runs smx_dev_sgm_wta_pair (with the neighbour state
+ * when sub-pixel is on), then the usual finish, speckle removal and sub-pixel fit.  agg_l / agg_r of smx_pair_out receive S;
+ * mean_l / mean_r are not produced (SMX_E_ARG if requested); radius and eps of smx_params are unused.  The volumes and the
+ * workspace are allocated on first use.  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on. */
+int smx_ctx_set_aggregation(smx_ctx* ctx, int mode, const smx_sgm_params* sgm);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -48,6 +48,11 @@ class SpeckleParams(C.Structure):
     _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
 
 
+class SgmParams(C.Structure):
+    """smx_sgm_params: semi-global matching (not a stage of the reference)."""
+    _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("paths", C.c_int)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -73,6 +78,7 @@ _PP = C.POINTER(Params)
 _WP = C.POINTER(WmfParams)
 _CP = C.POINTER(CensusParams)
 _SP = C.POINTER(SpeckleParams)
+_GP = C.POINTER(SgmParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -146,7 +152,15 @@ SIGNATURES = {
     "smx_speckle_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "smx_ctx_set_speckle": (_i, [_vp, _SP]),
     "smx_ctx_speckle_map": (_i, [_vp, _vp]),
+    "smx_default_sgm_params": (None, [_GP]),
+    "smx_sgm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_sgm_wta_pair": (_i, [_GP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_sgm_aggregate": (_i, [_GP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_aggregation": (_i, [_vp, _i, _GP]),
 }
+
+# smx.h SMX_AGG_*: the aggregations by name
+AGG_MODES = {"guided": 0, "sgm": 1}
 
 # smx.h SMX_COST_*: the matching costs by name
 COST_MODES = {"reference": 0, "census": 1}
@@ -223,6 +237,12 @@ def default_census_params():
 def default_speckle_params():
     p = SpeckleParams()
     lib().smx_default_speckle_params(C.byref(p))
+    return p
+
+
+def default_sgm_params():
+    p = SgmParams()
+    lib().smx_default_sgm_params(C.byref(p))
     return p
 
 

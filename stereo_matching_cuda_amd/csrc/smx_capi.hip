@@ -756,6 +756,68 @@ int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t
     return SMX_OK;
 }
 
+// ---- semi-global matching (not in the reference; smx_sgm.hip) -----------------------------------------
+void smx_default_sgm_params(smx_sgm_params* p) {
+    if (!p) return;
+    p->p1 = 10; p->p2 = 120; p->paths = 8;
+}
+
+static bool sgm_params_ok(const smx_sgm_params* p) {
+    return p && p->p1 >= 0 && p->p1 <= p->p2 && p->p2 <= 4095 && (p->paths == 4 || p->paths == 8);
+}
+static bool sgm_shape_ok(int w, int h, int size_d) {
+    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= SMX_SGM_MAX_D;
+}
+
+size_t smx_sgm_workspace_bytes(int w, int h, int size_d, int nviews) {
+    return sgm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? sgm_workspace_bytes(w, h, size_d, nviews) : 0;
+}
+
+int smx_dev_sgm_wta_pair(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                         int64_t* d_keys, float* d_agg, float* d_nbr, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!sgm_params_ok(p))
+        return fail(SMX_E_ARG, "smx_dev_sgm_wta_pair: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_dev_sgm_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    SMX_ARG((d_cost_l || d_cost_r) && d_keys);
+    const size_t need = sgm_workspace_bytes(w, h, size_d, d_cost_l && d_cost_r ? 2 : 1);
+    if (!d_ws || ws_bytes < need)
+        return fail(SMX_E_WS, "smx_dev_sgm_wta_pair: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0, need);
+    return launch_sgm_wta_pair(p->p1, p->p2, p->paths, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_ws,
+                               (hipStream_t)stream);
+}
+
+int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
+                      int size_d, int dmin) {
+    if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_sgm_aggregate: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    SMX_ARG(cost != nullptr);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = sgm_workspace_bytes(w, h, size_d, 1);
+    DevBuf dC, dA, dK, dW;
+    SMX_HIP(dC.alloc(vb));
+    if (agg) SMX_HIP(dA.alloc(vb));
+    SMX_HIP(dK.alloc(n * sizeof(int64_t)));
+    SMX_HIP(dW.alloc(wsb));
+    SMX_HIP(hipMemcpy(dC.p, cost, vb, hipMemcpyHostToDevice));
+    int rc = smx_dev_sgm_wta_pair(p, dC.as<float>(), nullptr, w, h, size_d, dK.as<int64_t>(), agg ? dA.as<float>() : nullptr,
+                                  nullptr, dW.p, wsb, nullptr);
+    if (rc) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (agg) SMX_HIP(hipMemcpy(agg, dA.p, vb, hipMemcpyDeviceToHost));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(hipMemcpy(keys.data(), dK.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);
@@ -802,6 +864,11 @@ struct smx_ctx {
     bool spk_valid = false;     // the map belongs to the last synchronous pair
     smx_speckle_params spk_params;
     DevBuf spk, spk_ws;
+    // semi-global matching (smx_ctx_set_aggregation): its workspace for both views, allocated on first use; the whole cost
+    // volumes it reads are costL / costR
+    int agg_mode = SMX_AGG_GUIDED;
+    smx_sgm_params sgm;
+    DevBuf sgm_ws;
     // pipelined entry (smx_ctx_stereo_pair_async): two slots of device inputs / results and pinned host staging, created
     // on first use.  Staging of a slot: [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l
     // mean_r | status word] coming down.
@@ -903,6 +970,17 @@ static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
     return SMX_OK;
 }
 
+// SGM mode of ctx_enqueue with the census cost: the codes, then both whole volumes, in one launch each.
+static int ctx_census_volumes(smx_ctx* c, const AggCall& call) {
+    const size_t n = c->n;
+    uint64_t* codes = c->codes.as<uint64_t>();
+    int rc;
+    for (int v = 0; v < 2; ++v)
+        if ((rc = smx_dev_census(&c->census, call.guide[v], codes + v * n, c->w, c->h, 1, call.st))) return rc;
+    return smx_dev_census_cost_pair(&c->census, codes, c->costL.as<float>(), c->costR.as<float>(), c->w, c->h, call.dmin[0],
+                                    call.dmin[1], 0, c->size_d, call.st);
+}
+
 // The path of one pair on the context's stream: device images in, the eight result planes out (+ the optional volumes
 // of the context).  Shared by the synchronous and the pipelined host-pointer entry.
 static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dminl, int dminr, bool want_cost, bool want_agg,
@@ -917,6 +995,8 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     // cost volumes are materialised only when the caller asks for them (main.cu:80-82) and then feed
     // the aggregation like in the reference; otherwise the slices are built on the fly inside it.
     const bool census = c->cost_mode == SMX_COST_CENSUS;
+    const bool sgm = c->agg_mode == SMX_AGG_SGM;
+    if (sgm) want_cost = true;      // SGM reads whole volumes
     if (want_cost && !census) {
         if ((rc = smx_dev_cost_volume(p, dL, dR, c->costL.as<float>(), w, w, h, dminl, 0, size_d, st))) return rc;
         if ((rc = smx_dev_cost_volume(p, dR, dL, c->costR.as<float>(), w, w, h, dminr, 0, size_d, st))) return rc;
@@ -930,7 +1010,12 @@ static int ctx_enqueue(smx_ctx* c, const uint8_t* dL, const uint8_t* dR, int dmi
     const AggCall call = {"smx_ctx_stereo_pair", p, 2, {dL, dR}, {dR, dL}, {costL, costR}, {dminl, dminr}, {keysL, keysR},
                           {mean, mean + n}, {aggL, want_agg ? aggL + (size_t)size_d * n : nullptr},
                           {nbrL, subpix ? nbrL + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
-    if (census) rc = ctx_census_aggregate(c, call, want_cost);
+    if (sgm) {
+        if (census) rc = ctx_census_volumes(c, call);
+        if (!rc)
+            rc = smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p,
+                                      sgm_workspace_bytes(w, h, size_d, 2), st);
+    } else if (census) rc = ctx_census_aggregate(c, call, want_cost);
     else rc = run_aggregation(call, c->agg_path);
     if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
@@ -966,15 +1051,19 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair"))) return rc;
     if (c->submitted != c->waited) return fail(SMX_E_ARG, "smx_ctx_stereo_pair: pipelined pairs are still in flight (smx_ctx_wait)");
     hipStream_t st = c->st;
-    const bool want_cost = out->cost_l || out->cost_r;
+    const bool sgm = c->agg_mode == SMX_AGG_SGM;
+    if (sgm && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair: semi-global matching (smx_ctx_set_aggregation) produces no mean images");
+    const bool want_cost = out->cost_l || out->cost_r || sgm;
     const bool want_agg = out->agg_l || out->agg_r;
+    if (sgm && !c->sgm_ws.p) SMX_HIP(c->sgm_ws.alloc(sgm_workspace_bytes(c->w, c->h, size_d, 2)));
     if (want_cost && !c->costL.p) { SMX_HIP(c->costL.alloc(vb)); SMX_HIP(c->costR.alloc(vb)); }
     if (want_agg && !c->aggLR.p) SMX_HIP(c->aggLR.alloc(2 * vb));
     const bool subpix = c->subpix != 0;
     if (subpix && !c->nbr.p) { SMX_HIP(c->nbr.alloc(6 * fb)); SMX_HIP(c->sub.alloc(2 * fb)); SMX_HIP(c->subf.alloc(fb)); }
     if (c->cost_mode == SMX_COST_CENSUS) {
         if (!c->codes.p) SMX_HIP(c->codes.alloc(2 * n * sizeof(uint64_t)));
-        if (!want_cost && !c->ccost.p) {
+        if (!want_cost && !c->ccost.p) {     // (SGM takes whole volumes: no chunk buffer)
             // at most 1 GiB for the chunk's two cost buffers
             const size_t fit = ((size_t)1 << 30) / (2 * fb);
             c->census_chunk = (int)(fit < 1 ? 1 : fit > (size_t)size_d ? (size_t)size_d : fit);
@@ -1005,7 +1094,7 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
         if (cp.dst && cp.src) SMX_HIP(hipMemcpyAsync(cp.dst, cp.src, cp.b, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
+    if (!sgm && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM kernels wait for nothing)
     c->sub_valid = subpix;
     c->spk_valid = c->speckle;
     return SMX_OK;
@@ -1032,6 +1121,24 @@ int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
         c->census = p;
     }
     c->cost_mode = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_aggregation(smx_ctx* c, int mode, const smx_sgm_params* sgm) {
+    SMX_ARG(c);
+    if (mode != SMX_AGG_GUIDED && mode != SMX_AGG_SGM)
+        return fail(SMX_E_ARG, "smx_ctx_set_aggregation: mode must be SMX_AGG_GUIDED or SMX_AGG_SGM");
+    if (mode == SMX_AGG_SGM) {
+        smx_sgm_params p;
+        smx_default_sgm_params(&p);
+        if (sgm) p = *sgm;
+        if (!sgm_params_ok(&p))
+            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+        if (!sgm_shape_ok(c->w, c->h, c->size_d))
+            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs w*h < 2^31 and size_d <= %d", SMX_SGM_MAX_D);
+        c->sgm = p;
+    }
+    c->agg_mode = mode;
     return SMX_OK;
 }
 
@@ -1097,6 +1204,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
     if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
+    if (c->agg_mode != SMX_AGG_GUIDED)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)

@@ -45,4 +45,9 @@ size_t speckle_workspace_bytes(int w, int h);
 int launch_speckle_filter(int max_size, float max_diff, const float* disp, float* out, int w, int h, float vmin,
                           float new_val, void* ws, hipStream_t st);
 void speckle_tile(int* tw, int* th);
+// smx_sgm.hip: semi-global matching of one or both whole cost volumes (smx_dev_sgm_wta_pair); ws: sgm_workspace_bytes bytes
+int sgm_padded_d(int size_d);
+size_t sgm_workspace_bytes(int w, int h, int size_d, int nviews);
+int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const float* cost_r, int w, int h, int size_d,
+                        int64_t* keys, float* agg, float* nbr, void* ws, hipStream_t st);
 }  // namespace smx

@@ -25,7 +25,8 @@ class PairPipeline:
 
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
-                 wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None):
+                 wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
+                 aggregation=None, sgm_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -43,7 +44,16 @@ class PairPipeline:
         smx_dev_speckle_filter behind the finish): self.despeckled = self.occlusion without its small connected components
         (vmin = dminl, new_val = dminl - 100), self.filled = the fill of self.despeckled, and the sub-pixel fit and
         wmf="occluded" take self.despeckled where they took self.occlusion, which stays the LR-check map.  The pipeline
-        owns the filter's workspace.  With None nothing is allocated or launched."""
+        owns the filter's workspace.  With None nothing is allocated or launched.
+        aggregation: None or "sgm" -- None is the reference's guided filter.  "sgm" is semi-global matching (not a stage of
+        the reference; include/smx.h smx_dev_sgm_wta_pair; sgm_params: SgmParams, None = the defaults): aggregate() builds
+        both WHOLE cost volumes into self.sgm_cost (2, size_d, h, w) -- census with cost="census", else the reference's cost,
+        which SGM reads through its clamp to 0 .. 255 -- and runs the one SGM call into self.keys (and self.agg = S,
+        self.nbr).  The pipeline owns the volumes and the SGM workspace self.sgm_ws; max_ws_bytes counts both, and a
+        slice sub-range or a size that does not fit raises ValueError.  No guided-filter workspace is allocated, self.mean
+        stays zero, and radius / eps of `params` are unused.  With None nothing is allocated or launched."""
+        if aggregation not in (None, "sgm"):
+            raise ValueError(f"aggregation must be None or 'sgm', not {aggregation!r}")
         if cost not in (None, "census"):
             raise ValueError(f"cost must be None or 'census', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
@@ -61,6 +71,20 @@ class PairPipeline:
         self.s_end = self.size_d if s_end is None else int(s_end)
         self.device = torch.device(device)
         self.params = params if params is not None else _lib.default_params()
+        self.aggregation = aggregation
+        self.sgm_params = self.sgm_cost = self.sgm_ws = None
+        self.sgm_ws_bytes = 0
+        if aggregation:
+            if self.s_begin != 0 or self.s_end != self.size_d:
+                raise ValueError("semi-global matching needs a pixel's whole disparity range: no slice sub-range")
+            self.sgm_params = sgm_params if sgm_params is not None else _lib.default_sgm_params()
+            self.sgm_ws_bytes = int(self.lib.smx_sgm_workspace_bytes(self.w, self.h, self.size_d, 2))
+            if self.sgm_ws_bytes == 0:
+                raise ValueError(f"semi-global matching does not take {self.w} x {self.h} x {self.size_d} "
+                                 "(w*h < 2^31, size_d <= 256)")
+            if self.sgm_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
+                raise ValueError(f"semi-global matching needs {self.sgm_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
+                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
         local = max(1, self.s_end - self.s_begin)
         sif = local if slices_in_flight is None else max(1, min(local, int(slices_in_flight)))
         # workspace of the path these parameters run (smx_agg_workspace_bytes_for follows the library's choice: a fused
@@ -74,8 +98,8 @@ class PairPipeline:
         while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
         self.slices_in_flight = sif
-        # pair calls (both views per launch) need twice the single-view workspace
-        self.ws_bytes = 2 * int(need(sif))
+        # pair calls (both views per launch) need twice the single-view workspace (SGM does not use it)
+        self.ws_bytes = 0 if aggregation else 2 * int(need(sif))
         dev = self.device
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         # keys[0] = left view, keys[1] = right view: one buffer so the shard merge is ONE all-reduce
@@ -83,7 +107,7 @@ class PairPipeline:
         f = dict(dtype=torch.float32, device=dev)
         self.best = torch.empty((2, self.h, self.w), **f)
         self.dmap = torch.empty((2, self.h, self.w), **f)
-        self.mean = torch.empty((2, self.h, self.w), dtype=torch.uint8, device=dev)
+        self.mean = (torch.zeros if aggregation else torch.empty)((2, self.h, self.w), dtype=torch.uint8, device=dev)
         self.occlusion = torch.empty((self.h, self.w), **f)
         self.filled = torch.empty((self.h, self.w), **f)
         self.agg = (torch.empty((2, local, self.h, self.w), **f) if want_agg else None)
@@ -100,9 +124,13 @@ class PairPipeline:
         self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
         self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
-        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost else None
+        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not aggregation else None
+        if aggregation:
+            self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
+            self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
-        self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) if cost and want_agg and sif < local else None
+        self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
+            if cost and want_agg and sif < local and not aggregation else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -117,6 +145,8 @@ class PairPipeline:
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
         if self.cost and (cost_l is not None or cost_r is not None):
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
+        if self.aggregation:
+            return self._aggregate_sgm(gray_l, gray_r, cost_l, cost_r)
         self.lib.smx_set_keys_fresh(1)
         try:
             if self.cost:
@@ -167,6 +197,29 @@ class PairPipeline:
                 flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, self.h, self.w)
                 self.agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
             L.smx_set_keys_fresh(0)
+
+    def _aggregate_sgm(self, gray_l, gray_r, cost_l=None, cost_r=None):
+        """The SGM flow: both whole cost volumes (the caller's, census, or the reference's cost) and the one
+        smx_dev_sgm_wta_pair call, which writes the keys (and S, the neighbour state) of both views."""
+        if (cost_l is None) != (cost_r is None):
+            raise ValueError("pass both cost volumes or neither")
+        self._guide = gray_l
+        L, w, h = self.lib, self.w, self.h
+        cl, cr = (cost_l, cost_r) if cost_l is not None else (self.sgm_cost[0], self.sgm_cost[1])
+        with self._on_device():
+            st = self._stream()
+            if self.cost:
+                P = C.byref(self.census_params)
+                for v, g in enumerate((gray_l, gray_r)):
+                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, st))
+                _lib.check(L.smx_dev_census_cost_pair(P, _dp(self.codes), _dp(cl), _dp(cr), w, h, self.dminl, self.dminr, 0,
+                                                      self.size_d, st))
+            elif cost_l is None:
+                P = C.byref(self.params)
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
+            _lib.check(L.smx_dev_sgm_wta_pair(C.byref(self.sgm_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys),
+                                              _dp(self.agg), _dp(self.nbr), _dp(self.sgm_ws), self.sgm_ws_bytes, st))
 
     def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r, s_begin=None, s_end=None, agg=None):
         """Both views per launch from materialised cost volumes of this rank's slices (smx_dev_aggregate_wta_pair_cost):
@@ -306,6 +359,8 @@ class PairPipeline:
     def check_status(self):
         """Raise if a workgroup of the fused aggregation gave up waiting for a neighbour."""
         torch.cuda.synchronize(self.device)
+        if self.aggregation:            # (the SGM kernels wait for nothing: no status word)
+            return
         with self._on_device():
             _lib.check(self.lib.smx_dev_agg_status(_dp(self.ws)))
 

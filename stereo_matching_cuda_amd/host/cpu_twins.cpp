@@ -14,6 +14,7 @@
 #include "integral.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "sgm.cuh"
 #include "speckle.cuh"
 #include "wmf.cuh"
 
@@ -300,5 +301,57 @@ void speckle_filterOnCPU(const float* disparity, float* out, const int w, const 
         }
         if (comp.size() <= (size_t)p.max_size)
             for (size_t i : comp) out[i] = new_val;
+    }
+}
+
+// ---- sgm.cuh (not in the reference) ----------------------------------------------------------
+// Semi-global matching by the definition in include/smx.h: per direction one pass over the image in path order, every
+// pixel from its predecessor p - r, integers throughout.
+void sgm_aggregateOnCPU(const float* cost, float* agg, float* best, float* disp_map, const int w, const int h,
+                        const int size_d, const int dmin, const smx_sgm_params& p) {
+    static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
+    const size_t n = (size_t)w * h;
+    vector<int> C(n * size_d), L(n * size_d), S(n * size_d, 0);     // [pixel][d]
+    for (int d = 0; d < size_d; ++d)
+        for (size_t i = 0; i < n; ++i) {
+            const float c = cost[(size_t)d * n + i];
+            C[i * size_d + d] = c >= 0.0f ? (c <= 255.0f ? (int)c : 255) : 0;
+        }
+    for (int r = 0; r < p.paths; ++r) {
+        const int dx = dirs[r][0], dy = dirs[r][1];
+        for (int iy = 0; iy < h; ++iy) {
+            const int y = dy >= 0 ? iy : h - 1 - iy;
+            for (int ix = 0; ix < w; ++ix) {
+                const int x = dx >= 0 ? ix : w - 1 - ix;
+                const int px = x - dx, py = y - dy;
+                int* cur = &L[((size_t)y * w + x) * size_d];
+                const int* c = &C[((size_t)y * w + x) * size_d];
+                if (px < 0 || px >= w || py < 0 || py >= h) {
+                    for (int d = 0; d < size_d; ++d) cur[d] = c[d];
+                } else {
+                    const int* prev = &L[((size_t)py * w + px) * size_d];
+                    int m = prev[0];
+                    for (int d = 1; d < size_d; ++d) m = prev[d] < m ? prev[d] : m;
+                    for (int d = 0; d < size_d; ++d) {
+                        int t = prev[d] < m + p.p2 ? prev[d] : m + p.p2;
+                        if (d - 1 >= 0 && prev[d - 1] + p.p1 < t) t = prev[d - 1] + p.p1;
+                        if (d + 1 < size_d && prev[d + 1] + p.p1 < t) t = prev[d + 1] + p.p1;
+                        cur[d] = c[d] + t - m;
+                    }
+                }
+                int* s = &S[((size_t)y * w + x) * size_d];
+                for (int d = 0; d < size_d; ++d) s[d] += cur[d];
+            }
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const int* s = &S[i * size_d];
+        int z = 0;
+        for (int d = 1; d < size_d; ++d)
+            if (s[d] <= s[z]) z = d;                 // the last slice of equal sums wins
+        if (best) best[i] = (float)s[z];
+        if (disp_map) disp_map[i] = (float)(dmin + z);
+        if (agg)
+            for (int d = 0; d < size_d; ++d) agg[(size_t)d * n + i] = (float)s[d];
     }
 }

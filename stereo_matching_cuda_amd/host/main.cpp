@@ -35,6 +35,12 @@
 //                     the 12 images; occlu_mapl_filled.png (and --wmf occluded, --subpixel, --pfm, --png16 behind it) then
 //                     come from the despeckled map.  Composes with --wmf, --subpixel, --cost census; not with --ngpu or
 //                     --pipeline
+//   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
+//                     census cost unless --cost reference is given): the same twelve images, the two mean images empty.
+//                     --sgm-p P1,P2 gives the penalties (0 <= P1 <= P2 <= 4095; default 10,120), --sgm-paths 4|8 the number
+//                     of directions (default 8).  With --host-compare the CPU twin (sgm_aggregateOnCPU) redoes both
+//                     views from the cost volumes and check_errors compares.  At most 256 labels.  Composes with --wmf,
+//                     --subpixel, --speckle, --pfm and --png16; not with --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -60,6 +66,7 @@
 #include "occlusion.cuh"
 #include "png_io.h"
 #include "rgb_to_grayscale.cuh"
+#include "sgm.cuh"
 #include "speckle.cuh"
 #include "winner_take_all.cuh"
 #include "wmf.cuh"
@@ -87,6 +94,9 @@ struct Options {
     int subpixel = 0;        // 0 = off, else SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR
     bool census = false;     // --cost census
     smx_census_params census_params;
+    bool cost_given = false; // --cost seen
+    bool sgm = false;        // --aggregation sgm
+    smx_sgm_params sgm_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
     int ngpu = 0;            // 0 = not given: the single-GPU paths
@@ -100,6 +110,8 @@ Options parse(int argc, char** argv) {
     Options o;
     smx_default_census_params(&o.census_params);
     smx_default_speckle_params(&o.speckle_params);
+    smx_default_sgm_params(&o.sgm_params);
+    bool sgm_option = false;        // --sgm-p / --sgm-paths seen
     bool census_option = false;     // --census-window / --census-th seen
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -131,6 +143,7 @@ Options parse(int argc, char** argv) {
         else if (a == "--cost") {
             std::string v;
             value(v);
+            o.cost_given = true;
             o.census = v == "census";
             if (o.ok && !o.census && v != "reference") {
                 std::fprintf(stderr, "--cost needs `reference` or `census`, not `%s`\n", v.c_str());
@@ -162,6 +175,38 @@ Options parse(int argc, char** argv) {
             }
             o.census_params.th = (int)th;
         }
+        else if (a == "--aggregation") {
+            std::string v;
+            value(v);
+            o.sgm = v == "sgm";
+            if (o.ok && !o.sgm && v != "guided") {
+                std::fprintf(stderr, "--aggregation needs `guided` or `sgm`, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+        }
+        else if (a == "--sgm-p") {
+            std::string v;
+            value(v);
+            int p1 = -1, p2 = -1;
+            char comma = 0, rest = 0;
+            sgm_option = true;
+            if (o.ok && (std::sscanf(v.c_str(), "%d%c%d%c", &p1, &comma, &p2, &rest) != 3 || comma != ',' || p1 < 0 || p1 > p2 ||
+                         p2 > 4095)) {
+                std::fprintf(stderr, "--sgm-p needs P1,P2 with 0 <= P1 <= P2 <= 4095, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.sgm_params.p1 = p1; o.sgm_params.p2 = p2;
+        }
+        else if (a == "--sgm-paths") {
+            std::string v;
+            value(v);
+            sgm_option = true;
+            if (o.ok && v != "4" && v != "8") {
+                std::fprintf(stderr, "--sgm-paths needs 4 or 8, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.sgm_params.paths = v == "4" ? 4 : 8;
+        }
         else if (a == "--speckle") {
             std::string v;
             value(v);
@@ -187,6 +232,11 @@ Options parse(int argc, char** argv) {
         std::fprintf(stderr, "--census-window and --census-th need --cost census\n");
         o.ok = false;
     }
+    if (o.ok && sgm_option && !o.sgm) {
+        std::fprintf(stderr, "--sgm-p and --sgm-paths need --aggregation sgm\n");
+        o.ok = false;
+    }
+    if (o.sgm && !o.cost_given) o.census = true;     // census + SGM is the standard pairing
     return o;
 }
 
@@ -226,6 +276,14 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
+    if (opt.sgm && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--aggregation sgm cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
+    if (opt.sgm && (long long)d_hi - d_lo + 1 > SMX_SGM_MAX_D) {
+        std::fprintf(stderr, "--aggregation sgm takes at most %d labels\n", SMX_SGM_MAX_D);
+        return 2;
+    }
     if (opt.speckle && (opt.ngpu != 0 || opt.pipeline)) {
         std::fprintf(stderr, "--speckle cannot be combined with --ngpu or --pipeline\n");
         return 2;
@@ -251,7 +309,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -330,7 +388,7 @@ int main(int argc, char** argv) {
         std::memset(&out, 0, sizeof(out));
         out.best_l = best[0].data(); out.best_r = best[1].data();
         out.dmap_l = dmap[0].data(); out.dmap_r = dmap[1].data();
-        out.mean_l = mean[0].data(); out.mean_r = mean[1].data();
+        if (!opt.sgm) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }     // (SGM has no mean images)
         out.occlusion = occlusion.data(); out.filled = filled.data();
         // one persistent context for all pairs: nothing is allocated, created or destroyed per pair
         void* sctx = nullptr;
@@ -340,6 +398,7 @@ int main(int argc, char** argv) {
         if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
         if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
         if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
+        if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
@@ -383,6 +442,19 @@ int main(int argc, char** argv) {
         if (sh_create) CHECK(sh_destroy(sctx));
         else CHECK(smx_destroy(ctx));
         std::cout << "guided filter ok" << std::endl;
+        if (host_compare && opt.sgm) {
+            // the twin redoes both views from whole cost volumes built by the stage wrappers
+            bool ok = true;
+            for (int v = 0; v < 2; ++v) {
+                std::vector<float> vol((size_t)n * size_d), tb(n), td(n);
+                if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
+                else CHECK(smx_compute_cost(&smx_config().params, gray[v], gray[1 - v], vol.data(), w, w, h, h, size_d, dmin[v]));
+                sgm_aggregateOnCPU(vol.data(), nullptr, tb.data(), td.data(), w, h, size_d, dmin[v], opt.sgm_params);
+                ok = check_errors(tb.data(), best[v].data(), n) && ok;
+                ok = check_errors(td.data(), dmap[v].data(), n) && ok;
+            }
+            if (ok) std::cout << "Semi-global matching ok!" << std::endl;
+        }
         if (host_compare) {
             std::vector<float> lr(dmap[0]);
             detect_occlusionOnCPU(lr.data(), dmap[1].data(), dmin[0] - 100, w, h);

@@ -7,6 +7,7 @@
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "sgm.cuh"
 #include "speckle.cuh"
 #include "wmf.cuh"
 
@@ -148,5 +149,19 @@ void speckle_filter(float* disparity, float* out, const int w, const int h, floa
         std::vector<float> twin((size_t)w * h);
         speckle_filterOnCPU(disparity, twin.data(), w, h, vmin, new_val, p);
         if (check_errors(twin.data(), out, w * h)) cout << "Speckle filter ok!" << endl;
+    }
+}
+
+// not in the reference: semi-global matching instead of the guided filter (smx_main --aggregation sgm)
+void sgm_aggregate(float* cost, float* agg, float* best, float* disp_map, const int w, const int h, const int size_d,
+                   const int dmin, const smx_sgm_params& p, bool host_gpu_compare) {
+    CHECK(smx_sgm_aggregate(&p, cost, agg, best, disp_map, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
+        sgm_aggregateOnCPU(cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d, dmin, p);
+        bool ok = check_errors(tb.data(), best, w * h);
+        ok = check_errors(td.data(), disp_map, w * h) && ok;
+        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
+        if (ok) cout << "Semi-global matching ok!" << endl;
     }
 }

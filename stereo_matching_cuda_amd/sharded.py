@@ -44,7 +44,8 @@ class ShardedPair:
     """D-sharded stereo pair: local aggregation of this rank's slices, ONE all-reduce of both
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
     The census matching cost (PairPipeline(cost="census")) is not part of the sharded driver: cost="census" raises
-    ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError."""
+    ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError.  Nor is semi-global
+    matching, which needs a pixel's whole disparity range on one rank: aggregation="sgm" raises ValueError."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -55,6 +56,8 @@ class ShardedPair:
             raise ValueError("the census cost is not part of the sharded driver: use PairPipeline(cost='census')")
         if kw.get("speckle") is not None:
             raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
+        if kw.get("aggregation") is not None:
+            raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
         self.rank, self.world, self.group = rank, world, group
         s0, s1 = shard_range(size_d, rank, world)
         self.pipe = PairPipeline(w, h, size_d, s_begin=s0, s_end=s1, **kw)

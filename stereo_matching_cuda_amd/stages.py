@@ -202,6 +202,22 @@ def census_cost(i1, i2, size_d, dmin, params=None):
     return cost
 
 
+def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
+    """Semi-global matching of one (size_d, h, w) float32 cost volume (smx_sgm_aggregate; include/smx.h has the
+    definition).  Returns (agg, best, disp_map): S as float32 [z][y][x] (None without want_agg), the winner's S and
+    dmin + z*, z* the last slice of minimal S."""
+    c = _c(cost, np.float32)
+    if c.ndim != 3:
+        raise ValueError("sgm_aggregate expects a (size_d, h, w) float32 volume")
+    size_d, h, w = c.shape
+    p = params if params is not None else _lib.default_sgm_params()
+    agg = np.empty((size_d, h, w), np.float32) if want_agg else None
+    best, disp = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_sgm_aggregate(C.byref(p), _ptr(c), None if agg is None else _ptr(agg), _ptr(best), _ptr(disp),
+                                            w, h, size_d, int(dmin)))
+    return agg, best, disp
+
+
 def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, want_agg=False,
                 params=None):
     """main.cu:65-155 on two gray images, device-resident between the stages."""
