@@ -36,7 +36,8 @@
 //                     come from the despeckled map.  Composes with --wmf, --subpixel, --cost census; not with --ngpu or
 //                     --pipeline
 //   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
-//                     census cost unless --cost reference is given): the same twelve images, the two mean images empty.
+//                     census cost, --census-window / --census-th included, unless --cost reference is given): the same
+//                     twelve images, the two mean images empty.
 //                     --sgm-p P1,P2 gives the penalties (0 <= P1 <= P2 <= 4095; default 10,120), --sgm-paths 4|8 the number
 //                     of directions (default 8).  With --host-compare the CPU twin (sgm_aggregateOnCPU) redoes both
 //                     views from the cost volumes and check_errors compares.  At most 256 labels.  Composes with --wmf,
@@ -228,15 +229,16 @@ Options parse(int argc, char** argv) {
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); o.ok = false; }
         else o.positional.push_back(a);
     }
-    if (o.ok && census_option && !o.census) {
-        std::fprintf(stderr, "--census-window and --census-th need --cost census\n");
+    if (o.sgm && !o.cost_given) o.census = true;     // census + SGM is the standard pairing
+    if (o.ok && census_option && !o.census) {        // (after the line above: the census options go with the implied cost too)
+        std::fprintf(stderr, "--census-window and --census-th need the census cost (--cost census, or --aggregation sgm "
+                             "without --cost reference)\n");
         o.ok = false;
     }
     if (o.ok && sgm_option && !o.sgm) {
         std::fprintf(stderr, "--sgm-p and --sgm-paths need --aggregation sgm\n");
         o.ok = false;
     }
-    if (o.sgm && !o.cost_given) o.census = true;     // census + SGM is the standard pairing
     return o;
 }
 
@@ -272,12 +274,13 @@ int main(int argc, char** argv) {
                              "--pipeline\n");
         return 2;
     }
-    if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
-        std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
-        return 2;
-    }
+    // (before the census refusal: SGM implies the census cost, and the message names the option that was given)
     if (opt.sgm && (opt.ngpu != 0 || opt.pipeline)) {
         std::fprintf(stderr, "--aggregation sgm cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
+    if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
     if (opt.sgm && (long long)d_hi - d_lo + 1 > SMX_SGM_MAX_D) {

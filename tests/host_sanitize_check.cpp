@@ -5,6 +5,8 @@
 //   * the PNG reader / writers of host/png_io.cpp on well-formed and malformed files given on the command line;
 //   * normalise_like_reference (host/helpers.cuh) on the maps listed in <dir>/wm/list.txt: <name>.f32 in, <name>.u8 the
 //     bytes the reference's write_mat handed to its PNG writer (tests/golden/ref_cases/wm_*.npz), byte for byte.
+// The twins of the opt-in stages (sgm_aggregateOnCPU, speckle_filterOnCPU, weighted_medianOnCPU) have the other half of
+// this leg: tests/host_twins_check.cpp, run by tests/test_host_twins_cpu.py against the numpy references.
 // No GPU and no libsmx_hip.so: the one symbol the twins need from the host layer (smx_config) is defined here.
 #include <cmath>
 #include <cstdio>

@@ -105,3 +105,23 @@ def comb(h, w, vertical=True):
         s[:, 0] = 1
         s[::2, :] = 1
     return s
+
+
+def structured(h, w):
+    """name -> (map, [(max_diff, the size of the largest component at that max_diff, or None where it is not stated)]):
+    the maps that stress connectivity, shared by tests/test_gpu_speckle.py and tests/test_host_twins_cpu.py.  With
+    vmin 0 every pixel counts.  The ramps a, a + 1, a + 2, ... are one component at max_diff 1 and one per column (row)
+    at max_diff 0; the chain 4 5 6 9 joins three columns of every four."""
+    y, x = np.mgrid[0:h, 0:w]
+    board = ((x + y) % 2).astype(np.float32)
+    ramp_x, ramp_y = x.astype(np.float32), y.astype(np.float32)
+    return {
+        "constant": (np.full((h, w), 3, np.float32), [(0, h * w)]),
+        "checkerboard": (board, [(0, 1), (1, h * w)]),
+        "spiral": (spiral(h, w), [(0, None)]),
+        "comb down": (comb(h, w, True), [(0, None)]),
+        "comb right": (comb(h, w, False), [(0, None)]),
+        "ramp x": (ramp_x, [(1, h * w), (0, h)]),
+        "ramp y": (ramp_y, [(1, h * w), (0, w)]),
+        "chain": (np.tile(np.array([4, 5, 6, 9], np.float32), (h, w // 4)), [(1, 3 * h), (0, h)]),
+    }

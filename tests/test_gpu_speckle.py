@@ -69,19 +69,7 @@ H5, W5 = 5 * U, 5 * T
 
 
 def _structured():
-    y, x = np.mgrid[0:H5, 0:W5]
-    board = ((x + y) % 2).astype(np.float32)
-    ramp_x, ramp_y = x.astype(np.float32), y.astype(np.float32)
-    return {
-        "constant": (np.full((H5, W5), 3, np.float32), [(0, H5 * W5)]),
-        "checkerboard": (board, [(0, 1), (1, H5 * W5)]),
-        "spiral": (ref.spiral(H5, W5), [(0, None)]),
-        "comb down": (ref.comb(H5, W5, True), [(0, None)]),
-        "comb right": (ref.comb(H5, W5, False), [(0, None)]),
-        "ramp x": (ramp_x, [(1, H5 * W5), (0, H5)]),
-        "ramp y": (ramp_y, [(1, H5 * W5), (0, W5)]),
-        "chain": (np.tile(np.array([4, 5, 6, 9], np.float32), (H5, W5 // 4)), [(1, 3 * H5), (0, H5)]),
-    }
+    return ref.structured(H5, W5)          # (shared with tests/test_host_twins_cpu.py)
 
 
 @pytest.mark.parametrize("name", ["constant", "checkerboard", "spiral", "comb down", "comb right", "ramp x", "ramp y",

@@ -1,7 +1,9 @@
 """The C++ drop-in host layer (stereo_matching_cuda_amd/host/: main.cpp + the reference's per-stage
 headers) built against libsmx_hip.so.  CPU: it builds, keeps the reference's function names, and
 fails loudly without a GPU.  GPU: running the drop-in main on the reference's Tsukuba pair writes
-12 PNGs whose pixels equal the 12 PNGs the reference's authors committed."""
+12 PNGs whose pixels equal the 12 PNGs the reference's authors committed.
+The CPU twins of the opt-in stages (SGM, speckle removal, weighted median) are held to their numpy references, plain and
+under the sanitizers, in tests/test_host_twins_cpu.py; the main's --aggregation sgm path in tests/test_gpu_main_sgm.py."""
 import os
 import re
 import subprocess
