@@ -1,0 +1,47 @@
+// smx_api.h -- what smx_capi.hip (the thread's state, the device entries, the checks), smx_host.hip (the host-pointer wrappers)
+// and smx_ctx.hip (the persistent context) share.  The thread's state itself stays inside smx_capi.hip.
+#pragma once
+#include "smx_agg.h"
+
+namespace smx {
+
+// RAII device allocation of the host-pointer wrappers and of the context.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    // Holds at least `want` bytes afterwards; does nothing where it does already.  A failure leaves it empty: a later call retries.
+    hipError_t ensure(size_t want) {
+        if (p && bytes >= want) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        const hipError_t e = hipMalloc(&p, want ? want : 1);
+        bytes = e == hipSuccess ? want : 0;
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    // allocate and copy up; copy down
+    hipError_t upload(const void* host, size_t n) {
+        const hipError_t e = ensure(n);
+        return e != hipSuccess ? e : hipMemcpy(p, host, n, hipMemcpyHostToDevice);
+    }
+    hipError_t download(void* host, size_t n) const { return hipMemcpy(host, p, n, hipMemcpyDeviceToHost); }
+    template <class T> T* as() { return (T*)p; }
+};
+
+// Every aggregation of the C-ABI meets the calling thread's knobs here.  accumulates: the call adds to keys that an earlier
+// chunk of the same pair wrote, so the thread's keys_fresh does not apply to it.
+int run_aggregation(const AggCall& c, int forced, bool accumulates);
+int thread_agg_path();                  // smx_set_agg_path of the calling thread (what smx_create copies)
+int agg_status_error(unsigned status);  // a workspace's status word [0] -> SMX_OK or the "hand-off wait ... timed out" error
+struct TimingPause { int saved; TimingPause(); ~TimingPause(); };   // while one lives, stage_mark records nothing
+bool subpix_mode_ok(int mode);
+bool wmf_params_ok(const smx_wmf_params* p);
+bool census_params_ok(const smx_census_params* p);
+bool speckle_params_ok(const smx_speckle_params* p);
+bool speckle_shape_ok(int w, int h);
+bool sgm_params_ok(const smx_sgm_params* p);
+bool sgm_shape_ok(int w, int h, int size_d);
+size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
+
+}  // namespace smx

@@ -1,0 +1,433 @@
+// smx_ctx.hip -- the persistent context of the host-pointer pair entry (smx_create .. smx_ctx_wait, smx_stereo_pair).  A pair's
+// needs are decided once (PairNeeds), reserved in one place (ctx_reserve) and run by ctx_enqueue, which both entries share.
+#include <string.h>
+
+#include <array>
+#include <new>
+
+#include "smx_api.h"
+#include "smx_launch.h"
+
+using namespace smx;
+
+struct smx_ctx {
+    smx_params p;
+    int w = 0, h = 0, size_d = 0, dev = -1;
+    int agg_path = 0;      // this context's aggregation path (smx_ctx_set_agg_path); starts as the creating thread's
+    size_t n = 0, ws_bytes = 0;
+    hipStream_t st = nullptr;
+    // keys / best / dmap / mean: left view first, right view behind it (one buffer each)
+    DevBuf dL, dR, keys, best, map, mean, occ, fil, ws, costL, costR, aggLR;
+    // The buffers of the opt-in stages are allocated on first use (ctx_reserve).
+    // sub-pixel maps (smx_ctx_set_subpixel): neighbour state [2][3][h][w], maps [2][h][w] and [h][w]
+    int subpix = 0;
+    bool sub_valid = false;     // the maps belong to the last synchronous pair
+    DevBuf nbr, sub, subf;
+    // census cost (smx_ctx_set_cost): the codes [2][h][w]; without whole volumes, one chunk of both views [2][census_chunk][h][w]
+    int cost_mode = SMX_COST_REFERENCE;
+    smx_census_params census;
+    int census_chunk = 0;
+    DevBuf codes, ccost;
+    // speckle removal (smx_ctx_set_speckle): the despeckled left map [h][w] and the filter's workspace
+    bool speckle = false;
+    bool spk_valid = false;     // the map belongs to the last synchronous pair
+    smx_speckle_params spk_params;
+    DevBuf spk, spk_ws;
+    // semi-global matching (smx_ctx_set_aggregation): its workspace for both views; it reads the whole volumes costL / costR
+    int agg_mode = SMX_AGG_GUIDED;
+    smx_sgm_params sgm;
+    DevBuf sgm_ws;
+    // pipelined entry: two slots of device inputs / results and pinned staging, created on first use.  Staging of a slot:
+    // [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l mean_r | status word] coming down.
+    struct Slot {
+        DevBuf in, res, mean;
+        uint8_t* h_in = nullptr;
+        char* h_out = nullptr;
+        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+    } slot[2];
+    hipStream_t st_up = nullptr, st_dn = nullptr;
+    uint64_t submitted = 0, waited = 0;
+    ~smx_ctx() {
+        for (Slot& sl : slot) {
+            if (sl.h_in) (void)hipHostFree(sl.h_in);
+            if (sl.h_out) (void)hipHostFree(sl.h_out);
+            for (hipEvent_t e : {sl.up, sl.done, sl.down})
+                if (e) (void)hipEventDestroy(e);
+        }
+        for (hipStream_t x : {st, st_up, st_dn})
+            if (x) (void)hipStreamDestroy(x);
+    }
+};
+
+// What one pair asks of the context beyond the eight result planes, decided once per pair by the entry that was called
+// (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them); its device images with the disparity of
+// slice 0 of either view; where its results go on the device (best / map / mean: left view first, right view behind it).
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle; };
+struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; };
+struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
+
+// Every buffer `need` asks for, each under its own guard: after a failed allocation the next call simply retries.
+static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
+    const size_t fb = c->n * sizeof(float), vb = fb * c->size_d;
+    if (need.sgm) SMX_HIP(c->sgm_ws.ensure(sgm_workspace_bytes(c->w, c->h, c->size_d, 2)));
+    if (need.cost) { SMX_HIP(c->costL.ensure(vb)); SMX_HIP(c->costR.ensure(vb)); }
+    if (need.agg) SMX_HIP(c->aggLR.ensure(2 * vb));
+    if (need.subpix) { SMX_HIP(c->nbr.ensure(6 * fb)); SMX_HIP(c->sub.ensure(2 * fb)); SMX_HIP(c->subf.ensure(fb)); }
+    if (need.census) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
+    if (need.census && !need.cost) {
+        const size_t fit = ((size_t)1 << 30) / (2 * fb);     // the chunk's two cost buffers: at most 1 GiB, at least one slice
+        c->census_chunk = (int)(fit < 1 ? 1 : fit > (size_t)c->size_d ? (size_t)c->size_d : fit);
+        SMX_HIP(c->ccost.ensure(2 * (size_t)c->census_chunk * fb));
+    }
+    if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
+    return SMX_OK;
+}
+
+// The census codes of both images of `call`: one launch where they lie back to back, else one per image
+static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
+    uint64_t* codes = c->codes.as<uint64_t>();
+    if (call.guide[1] == call.guide[0] + c->n) return smx_dev_census(&c->census, call.guide[0], codes, c->w, c->h, 2, call.st);
+    int rc = SMX_OK;
+    for (int v = 0; v < 2 && !rc; ++v) rc = smx_dev_census(&c->census, call.guide[v], codes + v * c->n, c->w, c->h, 1, call.st);
+    return rc;
+}
+
+// Census mode of ctx_enqueue: census cost chunk -> aggregation from that chunk, over ascending contiguous chunks of `call`'s
+// slices, into the whole volumes where the context holds them, else into the chunk buffer.  Chunks after the first accumulate.
+static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
+    const size_t n = c->n;
+    const int chunk = whole ? c->size_d : c->census_chunk;
+    int rc;
+    for (int s0 = call.s_begin; s0 < call.s_end; s0 += chunk) {
+        const int s1 = s0 + chunk < call.s_end ? s0 + chunk : call.s_end;
+        float* cl = whole ? c->costL.as<float>() + (size_t)s0 * n : c->ccost.as<float>();
+        float* cr = whole ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
+        if ((rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), cl, cr, c->w, c->h, call.dmin[0], call.dmin[1],
+                                           s0, s1, call.st)))
+            return rc;
+        AggCall part = call;
+        part.s_begin = s0; part.s_end = s1;
+        part.cost[0] = cl; part.cost[1] = cr;
+        for (int v = 0; v < 2; ++v)
+            if (call.agg[v]) part.agg[v] = call.agg[v] + (size_t)(s0 - call.s_begin) * n;
+        if ((rc = run_aggregation(part, c->agg_path, s0 != call.s_begin))) return rc;
+    }
+    return SMX_OK;
+}
+
+// The path of one pair on the context's stream: device images in, the eight result planes (+ the context's volumes) out.
+static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
+    const smx_params* p = &c->p;
+    const int w = c->w, h = c->h, size_d = c->size_d;
+    const size_t n = c->n;
+    hipStream_t st = c->st;
+    int rc;
+    int64_t* keysL = c->keys.as<int64_t>();
+    // cost volumes are materialised only when the caller asks for them (main.cu:80-82) or SGM reads them, and then feed
+    // the aggregation like in the reference; otherwise the slices are built on the fly inside it.
+    float* const costL = need.cost ? c->costL.as<float>() : nullptr;
+    float* const costR = need.cost ? c->costR.as<float>() : nullptr;
+    float* const aggL = need.agg ? c->aggLR.as<float>() : nullptr;
+    float* const nbrL = need.subpix ? c->nbr.as<float>() : nullptr;
+    if (need.cost && !need.census) {
+        if ((rc = smx_dev_cost_volume(p, in.left, in.right, costL, w, w, h, in.dminl, 0, size_d, st))) return rc;
+        if ((rc = smx_dev_cost_volume(p, in.right, in.left, costR, w, w, h, in.dminr, 0, size_d, st))) return rc;
+    }
+    if ((rc = smx_dev_init_keys(keysL, 2 * (int64_t)n, st))) return rc;
+    // main.cu:133-134, both views per call, on the context's own path
+    const AggCall call = {"smx_ctx_stereo_pair", p, 2, {in.left, in.right}, {in.right, in.left}, {costL, costR},
+                          {in.dminl, in.dminr}, {keysL, keysL + n}, {out.mean, out.mean + n},
+                          {aggL, need.agg ? aggL + (size_t)size_d * n : nullptr}, {nbrL, need.subpix ? nbrL + 3 * n : nullptr},
+                          w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
+    if (need.census && (rc = ctx_census_codes(c, call))) return rc;
+    if (need.sgm) {
+        // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
+        if (need.census) rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), costL, costR, w, h, in.dminl,
+                                                       in.dminr, 0, size_d, st);
+        if (!rc) rc = smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p,
+                                           sgm_workspace_bytes(w, h, size_d, 2), st);
+    } else if (need.census) rc = ctx_census_aggregate(c, call, need.cost);
+    else rc = run_aggregation(call, c->agg_path, false);
+    if (rc) return rc;
+    // main.cu:112-118 presets, winning slices, main.cu:140-155
+    if ((rc = smx_dev_finish_pair(p, keysL, w, h, in.dminl, in.dminr, in.dminl - 100, (float)in.dminl, out.best, out.map,
+                                  out.occ, out.fil, st)))
+        return rc;
+    const float* kept = out.occ;    // the map whose validity test says which pixels the fill replaced
+    if (need.speckle) {
+        // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
+        float* spk = c->spk.as<float>();
+        if ((rc = smx_dev_speckle_filter(&c->spk_params, out.occ, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
+                                         c->spk_ws.p, speckle_workspace_bytes(w, h), st)))
+            return rc;
+        if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
+        kept = spk;
+    }
+    if (!need.subpix) return SMX_OK;
+    return smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl, c->sub.as<float>(),
+                                 c->subf.as<float>(), st);
+}
+
+static int ctx_check_device(smx_ctx* c, const char* who) {
+    int dev = -1;
+    SMX_HIP(hipGetDevice(&dev));
+    if (dev != c->dev) return fail(SMX_E_ARG, "%s: the context lives on device %d, current device is %d", who, c->dev, dev);
+    return SMX_OK;
+}
+
+// The planes of a smx_pair_out in the order of the struct -- the eight result planes, then the four volumes -- with their bytes
+// per pixel.  Both entries copy `from` one such struct `to` another through this table; a NULL plane is skipped.
+struct PlaneRef { void* p; size_t elem; };
+static std::array<PlaneRef, 12> pair_planes(const smx_pair_out& o, size_t size_d) {
+    const size_t f = sizeof(float), v = f * size_d;
+    return {{{o.best_l, f}, {o.best_r, f}, {o.dmap_l, f}, {o.dmap_r, f}, {o.mean_l, 1}, {o.mean_r, 1}, {o.occlusion, f},
+             {o.filled, f}, {o.cost_l, v}, {o.cost_r, v}, {o.agg_l, v}, {o.agg_r, v}}};
+}
+
+extern "C" {
+
+int smx_create(const smx_params* p, int w, int h, int size_d, smx_ctx** out) {
+    SMX_ARG(p && out && w >= 2 && h >= 1 && size_d >= 1 && p->radius >= 0);
+    *out = nullptr;
+    smx_ctx* c = new (std::nothrow) smx_ctx;
+    if (!c) return fail(SMX_E_HIP, "smx_create: out of host memory");
+    struct Guard { smx_ctx* c; ~Guard() { delete c; } } guard{c};
+    c->p = *p; c->w = w; c->h = h; c->size_d = size_d;
+    c->agg_path = thread_agg_path();
+    c->n = (size_t)w * h;
+    const size_t n = c->n, fb = n * sizeof(float);
+    SMX_HIP(hipGetDevice(&c->dev));
+    SMX_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+    c->ws_bytes = 2 * pick_ws_bytes(w, h, size_d);     // both views per launch
+    SMX_HIP(c->dL.ensure(n)); SMX_HIP(c->dR.ensure(n));
+    SMX_HIP(c->keys.ensure(2 * n * 8));
+    SMX_HIP(c->best.ensure(2 * fb)); SMX_HIP(c->map.ensure(2 * fb));
+    SMX_HIP(c->mean.ensure(2 * n));
+    SMX_HIP(c->occ.ensure(fb)); SMX_HIP(c->fil.ensure(fb));
+    SMX_HIP(c->ws.ensure(c->ws_bytes));
+    guard.c = nullptr;
+    *out = c;
+    return SMX_OK;
+}
+
+int smx_ctx_set_agg_path(smx_ctx* c, int path) {
+    SMX_ARG(c);
+    if (path < 0 || path > 5) return fail(SMX_E_ARG, "smx_ctx_set_agg_path: path must be 0 .. 5");
+    c->agg_path = path;
+    return SMX_OK;
+}
+
+int smx_destroy(smx_ctx* c) {
+    if (!c) return SMX_OK;
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    if (c->dev >= 0 && dev != c->dev) (void)hipSetDevice(c->dev);
+    for (hipStream_t x : {c->st_up, c->st, c->st_dn})
+        if (x) (void)hipStreamSynchronize(x);
+    delete c;
+    if (dev >= 0) (void)hipSetDevice(dev);
+    return SMX_OK;
+}
+
+int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r, int dminl, int dminr,
+                        const smx_pair_out* out) {
+    SMX_ARG(c && gray_l && gray_r && out);
+    const size_t n = c->n;
+    int rc;
+    if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair"))) return rc;
+    if (c->submitted != c->waited) return fail(SMX_E_ARG, "smx_ctx_stereo_pair: pipelined pairs are still in flight (smx_ctx_wait)");
+    hipStream_t st = c->st;
+    const bool sgm = c->agg_mode == SMX_AGG_SGM;
+    if (sgm && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair: semi-global matching (smx_ctx_set_aggregation) produces no mean images");
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
+                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle};
+    if ((rc = ctx_reserve(c, need))) return rc;
+    c->sub_valid = c->spk_valid = false;
+    uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
+    stage_mark(ST_BEGIN, st);
+    SMX_HIP(hipMemcpyAsync(dL, gray_l, n, hipMemcpyHostToDevice, st));
+    SMX_HIP(hipMemcpyAsync(dR, gray_r, n, hipMemcpyHostToDevice, st));
+    stage_mark(ST_UPLOAD, st);
+    float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
+    uint8_t* mean = c->mean.as<uint8_t>();
+    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr}, need, {best, map, mean, c->occ.as<float>(), c->fil.as<float>()}))) return rc;
+    const smx_pair_out dev = {best, best + n, map, map + n, mean, mean + n, c->occ.as<float>(), c->fil.as<float>(),
+                              c->costL.as<float>(), c->costR.as<float>(), agg, need.agg ? agg + c->size_d * n : nullptr};
+    const auto to = pair_planes(*out, c->size_d), from = pair_planes(dev, c->size_d);
+    for (size_t i = 0; i < to.size(); ++i)
+        if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
+    stage_mark(ST_DOWNLOAD, st);
+    SMX_HIP(hipStreamSynchronize(st));
+    if (!need.sgm && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM kernels wait for nothing)
+    c->sub_valid = need.subpix;
+    c->spk_valid = need.speckle;
+    return SMX_OK;
+}
+
+int smx_ctx_set_subpixel(smx_ctx* c, int mode) {
+    SMX_ARG(c);
+    if (mode != 0 && !subpix_mode_ok(mode))
+        return fail(SMX_E_ARG, "smx_ctx_set_subpixel: mode must be 0, SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR");
+    c->subpix = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
+    SMX_ARG(c);
+    if (mode != SMX_COST_REFERENCE && mode != SMX_COST_CENSUS)
+        return fail(SMX_E_ARG, "smx_ctx_set_cost: mode must be SMX_COST_REFERENCE or SMX_COST_CENSUS");
+    if (mode == SMX_COST_CENSUS) {
+        smx_census_params p;
+        smx_default_census_params(&p);
+        if (census) p = *census;
+        if (!census_params_ok(&p))
+            return fail(SMX_E_ARG, "smx_ctx_set_cost: census needs 1 <= rx <= 4, 1 <= ry <= 3, th >= 1");
+        c->census = p;
+    }
+    c->cost_mode = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_aggregation(smx_ctx* c, int mode, const smx_sgm_params* sgm) {
+    SMX_ARG(c);
+    if (mode != SMX_AGG_GUIDED && mode != SMX_AGG_SGM)
+        return fail(SMX_E_ARG, "smx_ctx_set_aggregation: mode must be SMX_AGG_GUIDED or SMX_AGG_SGM");
+    if (mode == SMX_AGG_SGM) {
+        smx_sgm_params p;
+        smx_default_sgm_params(&p);
+        if (sgm) p = *sgm;
+        if (!sgm_params_ok(&p))
+            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+        if (!sgm_shape_ok(c->w, c->h, c->size_d))
+            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs w*h < 2^31 and size_d <= %d", SMX_SGM_MAX_D);
+        c->sgm = p;
+    }
+    c->agg_mode = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_speckle(smx_ctx* c, const smx_speckle_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!speckle_params_ok(p))
+            return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs max_size >= 0 and a finite max_diff >= 0");
+        if (!speckle_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs w*h < 2^31");
+        c->spk_params = *p;
+    }
+    c->speckle = p != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_speckle_map(smx_ctx* c, float* despeckled) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_speckle_map")) return rc;
+    if (!c->spk_valid) return fail(SMX_E_ARG, "smx_ctx_speckle_map: the last smx_ctx_stereo_pair ran without speckle removal");
+    if (despeckled) SMX_HIP(c->spk.download(despeckled, c->n * sizeof(float)));
+    return SMX_OK;
+}
+
+int smx_ctx_subpixel_maps(smx_ctx* c, float* sub_l, float* sub_r, float* sub_filled) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_subpixel_maps")) return rc;
+    if (!c->sub_valid) return fail(SMX_E_ARG, "smx_ctx_subpixel_maps: the last smx_ctx_stereo_pair ran without sub-pixel");
+    const size_t n = c->n, fb = n * sizeof(float);
+    if (sub_l) SMX_HIP(c->sub.download(sub_l, fb));
+    if (sub_r) SMX_HIP(hipMemcpy(sub_r, c->sub.as<float>() + n, fb, hipMemcpyDeviceToHost));
+    if (sub_filled) SMX_HIP(c->subf.download(sub_filled, fb));
+    return SMX_OK;
+}
+
+// ---- pipelined host-pointer entry ---------------------------------------------------------------------------------
+// Pair k uses slot k % 2.  Three streams: uploads, the path, downloads; events chain a pair through them, so that the
+// upload of pair k+1 and the download of pair k-1 run under the aggregation of pair k.
+static int ctx_async_setup(smx_ctx* c) {
+    if (c->st_up) return SMX_OK;
+    const size_t n = c->n;
+    for (hipStream_t* x : {&c->st_up, &c->st_dn}) SMX_HIP(hipStreamCreateWithFlags(x, hipStreamNonBlocking));
+    for (smx_ctx::Slot& sl : c->slot) {
+        SMX_HIP(sl.in.ensure(2 * n));
+        SMX_HIP(sl.res.ensure(6 * n * sizeof(float)));
+        SMX_HIP(sl.mean.ensure(2 * n));
+        SMX_HIP(hipHostMalloc((void**)&sl.h_in, 2 * n, hipHostMallocDefault));
+        SMX_HIP(hipHostMalloc((void**)&sl.h_out, 6 * n * sizeof(float) + 2 * n + 256, hipHostMallocDefault));
+        for (hipEvent_t* e : {&sl.up, &sl.done, &sl.down}) SMX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    return SMX_OK;
+}
+
+int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r, int dminl, int dminr) {
+    SMX_ARG(c && gray_l && gray_r);
+    int rc;
+    if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
+    if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
+    if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
+    if (c->agg_mode != SMX_AGG_GUIDED)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
+    if (c->cost_mode != SMX_COST_REFERENCE)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
+    if (c->submitted - c->waited >= 2)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: two pairs are in flight already (smx_ctx_wait takes the older one)");
+    if ((rc = ctx_async_setup(c))) return rc;
+    // no stage marks in the pipelined entry: pairs overlap on three streams, so "the stages of the last call" has no meaning
+    // here, and an event record per stage is a bubble on the queue the pipeline exists to keep full
+    TimingPause pause;
+    const size_t n = c->n, fb = n * sizeof(float);
+    smx_ctx::Slot& sl = c->slot[c->submitted & 1];
+    // the caller's images into the slot's pinned staging: the caller's buffers are free again when this call returns
+    memcpy(sl.h_in, gray_l, n);
+    memcpy(sl.h_in + n, gray_r, n);
+    uint8_t* dL = sl.in.as<uint8_t>(); uint8_t* dR = dL + n;
+    SMX_HIP(hipMemcpyAsync(dL, sl.h_in, 2 * n, hipMemcpyHostToDevice, c->st_up));
+    SMX_HIP(hipEventRecord(sl.up, c->st_up));
+    SMX_HIP(hipStreamWaitEvent(c->st, sl.up, 0));
+    float* r = sl.res.as<float>();                       // best_l best_r dmap_l dmap_r occlusion filled
+    // (every opt-in stage was refused above: the pair needs nothing beyond the eight planes)
+    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr}, PairNeeds{}, {r, r + 2 * n, sl.mean.as<uint8_t>(), r + 4 * n, r + 5 * n})))
+        return rc;
+    // status word of this pair's aggregation (the next pair's launch clears it): behind the planes in the staging
+    char* status_h = sl.h_out + 6 * fb + 2 * n;
+    SMX_HIP(hipMemcpyAsync(status_h, (const char*)align_up((size_t)c->ws.p, 256), sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
+    SMX_HIP(hipEventRecord(sl.done, c->st));
+    SMX_HIP(hipStreamWaitEvent(c->st_dn, sl.done, 0));
+    SMX_HIP(hipMemcpyAsync(sl.h_out, r, 6 * fb, hipMemcpyDeviceToHost, c->st_dn));
+    SMX_HIP(hipMemcpyAsync(sl.h_out + 6 * fb, sl.mean.p, 2 * n, hipMemcpyDeviceToHost, c->st_dn));
+    SMX_HIP(hipEventRecord(sl.down, c->st_dn));
+    ++c->submitted;
+    return SMX_OK;
+}
+
+int smx_ctx_wait(smx_ctx* c, smx_pair_out* staged, const smx_pair_out* copy_to) {
+    SMX_ARG(c);
+    if (c->submitted == c->waited) return fail(SMX_E_ARG, "smx_ctx_wait: no pair in flight");
+    int rc;
+    if ((rc = ctx_check_device(c, "smx_ctx_wait"))) return rc;
+    smx_ctx::Slot& sl = c->slot[c->waited & 1];
+    SMX_HIP(hipEventSynchronize(sl.down));
+    ++c->waited;
+    const size_t n = c->n, fb = n * sizeof(float);
+    float* f = (float*)sl.h_out;
+    uint8_t* m = (uint8_t*)(sl.h_out + 6 * fb);
+    const smx_pair_out v = {f, f + n, f + 2 * n, f + 3 * n, m, m + n, f + 4 * n, f + 5 * n};     // (no volumes)
+    if (staged) *staged = v;
+    if (copy_to) {
+        const auto to = pair_planes(*copy_to, c->size_d), from = pair_planes(v, c->size_d);
+        for (size_t i = 0; i < to.size(); ++i)
+            if (to[i].p && from[i].p) memcpy(to[i].p, from[i].p, n * from[i].elem);
+    }
+    unsigned status = 0;
+    memcpy(&status, sl.h_out + 6 * fb + 2 * n, sizeof(status));
+    return agg_status_error(status);
+}
+
+int smx_stereo_pair(const smx_params* p, const uint8_t* gray_l, const uint8_t* gray_r, int w, int h,
+                    int size_d, int dminl, int dminr, const smx_pair_out* out) {
+    SMX_ARG(p && gray_l && gray_r && out && w >= 2 && h >= 1 && size_d >= 1);
+    smx_ctx* c = nullptr;
+    if (int rc = smx_create(p, w, h, size_d, &c)) return rc;
+    const int rc = smx_ctx_stereo_pair(c, gray_l, gray_r, dminl, dminr, out);
+    (void)smx_destroy(c);
+    return rc;
+}
+
+}  // extern "C"

@@ -1,0 +1,204 @@
+// smx_host.hip -- the host-pointer stage entries of include/smx.h (the reference's L2 wrappers).  Each reads as: its argument
+// checks, its inputs, the device entry of smx_capi.hip, the synchronise, its outputs.
+#include <limits.h>
+
+#include <vector>
+
+#include "smx_api.h"
+#include "smx_launch.h"
+
+using namespace smx;
+
+size_t smx::pick_ws_bytes(int w, int h, int size_d) {
+    // every slice in flight, but at most ~2 GiB of them
+    const size_t one = smx_agg_workspace_bytes(w, h, 1), all = smx_agg_workspace_bytes(w, h, size_d), cap = (size_t)2 << 30;
+    return all <= cap ? all : one > cap ? one : cap;
+}
+
+extern "C" {
+
+int smx_rgb_to_grayscale(const smx_params* p, const uint8_t* h_rgb, int64_t n, int channels, uint8_t* h_gray) {
+    SMX_ARG(p && h_rgb && h_gray && n > 0 && channels >= 3);
+    DevBuf rgb, gray;
+    SMX_HIP(rgb.upload(h_rgb, (size_t)n * channels));
+    SMX_HIP(gray.ensure((size_t)n));
+    if (int rc = smx_dev_rgb_to_grayscale(p, rgb.as<uint8_t>(), n, channels, gray.as<uint8_t>(), nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(gray.download(h_gray, (size_t)n));
+    return SMX_OK;
+}
+
+int smx_compute_cost(const smx_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w1, int w2, int h1, int h2,
+                     int size_d, int dmin) {
+    SMX_ARG(p && i1 && i2 && cost && size_d >= 1);
+    SMX_ARG(w1 >= 2 && w1 == w2 && h1 >= 1 && h1 == h2);
+    const size_t n = (size_t)w1 * h1;
+    DevBuf d1, d2, dc;
+    SMX_HIP(d1.upload(i1, n));
+    SMX_HIP(d2.upload(i2, n));
+    SMX_HIP(dc.ensure(n * size_d * sizeof(float)));
+    if (int rc = smx_dev_cost_volume(p, d1.as<uint8_t>(), d2.as<uint8_t>(), dc.as<float>(), w1, w2, h1, dmin, 0, size_d, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dc.download(cost, n * size_d * sizeof(float)));
+    return SMX_OK;
+}
+
+int smx_integral(const float* image, float* integral, int width, int height) {
+    SMX_ARG(image && integral && width >= 1 && height >= 1);
+    const size_t bytes = (size_t)width * height * sizeof(float);
+    DevBuf d;
+    SMX_HIP(d.upload(image, bytes));
+    if (int rc = smx_dev_integral(d.as<float>(), d.as<float>(), width, height, 1, nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(d.download(integral, bytes));
+    return SMX_OK;
+}
+
+int smx_compute_guided_filter(const smx_params* p, const uint8_t* i, const float* cost, float* filter_cost, float* disp_map,
+                              uint8_t* mean, float* agg, int w, int h, int size_d, int dmin) {
+    SMX_ARG(p && i && cost && filter_cost && disp_map && size_d >= 1 && w >= 2 && h >= 1);
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), vb = fb * size_d;
+    const size_t ws_bytes = pick_ws_bytes(w, h, size_d);
+    DevBuf dI, dC, dBest, dMap, dMean, dKeys, dAgg, ws;
+    SMX_HIP(dI.upload(i, n));
+    SMX_HIP(dC.upload(cost, vb));
+    SMX_HIP(dBest.upload(filter_cost, fb));
+    SMX_HIP(dMap.upload(disp_map, fb));
+    SMX_HIP(dMean.ensure(n));
+    SMX_HIP(dKeys.ensure(n * sizeof(int64_t)));
+    if (agg) SMX_HIP(dAgg.ensure(vb));
+    SMX_HIP(ws.ensure(ws_bytes));
+    int rc;
+    if ((rc = smx_dev_init_keys(dKeys.as<int64_t>(), (int64_t)n, nullptr))) return rc;
+    if ((rc = smx_dev_aggregate_wta(p, dI.as<uint8_t>(), nullptr, dC.as<float>(), w, h, dmin, 0, size_d, dKeys.as<int64_t>(),
+                                    dMean.as<uint8_t>(), agg ? dAgg.as<float>() : nullptr, ws.p, ws_bytes, nullptr)))
+        return rc;
+    if ((rc = smx_dev_apply_keys(dKeys.as<int64_t>(), (int64_t)n, dmin, dBest.as<float>(), dMap.as<float>(), nullptr))) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if ((rc = smx_dev_agg_status(ws.p))) return rc;
+    SMX_HIP(dBest.download(filter_cost, fb));
+    SMX_HIP(dMap.download(disp_map, fb));
+    if (mean) SMX_HIP(dMean.download(mean, n));
+    if (agg) SMX_HIP(dAgg.download(agg, vb));
+    return SMX_OK;
+}
+
+int smx_detect_occlusion(const smx_params* p, float* disparityLeft, const float* disparityRight, int dOcclusion, int w, int h) {
+    SMX_ARG(p && disparityLeft && disparityRight && w >= 1 && h >= 1);
+    const size_t bytes = (size_t)w * h * sizeof(float);
+    DevBuf dL, dR;
+    SMX_HIP(dL.upload(disparityLeft, bytes));
+    SMX_HIP(dR.upload(disparityRight, bytes));
+    if (int rc = smx_dev_detect_occlusion(p, dL.as<float>(), dR.as<float>(), dOcclusion, w, h, nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dL.download(disparityLeft, bytes));
+    return SMX_OK;
+}
+
+int smx_fill_occlusion(float* disparity, int w, int h, float vMin) {
+    SMX_ARG(disparity && w >= 1 && h >= 1);
+    const size_t bytes = (size_t)w * h * sizeof(float);
+    DevBuf d;
+    SMX_HIP(d.upload(disparity, bytes));
+    if (int rc = smx_dev_fill_occlusion(d.as<float>(), w, h, vMin, nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(d.download(disparity, bytes));
+    return SMX_OK;
+}
+
+int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const float* disp, const float* select, float* out, int w,
+                        int h, int dmin, int size_d) {
+    SMX_ARG(wmf_params_ok(p) && guide && disp && out && w >= 1 && h >= 1);
+    SMX_ARG(size_d >= 1 && size_d <= 4096 && (long long)dmin + size_d <= INT_MAX);
+    SMX_ARG((const void*)out != (const void*)disp);
+    const size_t n = (size_t)w * h, bytes = n * sizeof(float);
+    DevBuf dG, dD, dS, dO;
+    SMX_HIP(dG.upload(guide, n));
+    SMX_HIP(dD.upload(disp, bytes));
+    SMX_HIP(dO.ensure(bytes));
+    if (select) SMX_HIP(dS.upload(select, bytes));
+    if (int rc = smx_dev_weighted_median(p, dG.as<uint8_t>(), dD.as<float>(), select ? dS.as<float>() : nullptr, dO.as<float>(),
+                                         w, h, dmin, size_d, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dO.download(out, bytes));
+    return SMX_OK;
+}
+
+int smx_speckle_filter(const smx_speckle_params* p, const float* disp, float* out, int w, int h, float vmin, float new_val) {
+    SMX_ARG(speckle_params_ok(p) && disp && out && speckle_shape_ok(w, h));
+    const size_t bytes = (size_t)w * h * sizeof(float), wsb = speckle_workspace_bytes(w, h);
+    DevBuf dD, dW;
+    SMX_HIP(dD.upload(disp, bytes));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_speckle_filter(p, dD.as<float>(), dD.as<float>(), w, h, vmin, new_val, dW.p, wsb, nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dD.download(out, bytes));
+    return SMX_OK;
+}
+
+int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h,
+                    int size_d, int dmin) {
+    SMX_ARG(census_params_ok(p) && i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);
+    const size_t n = (size_t)w * h;
+    DevBuf img, code, dc;
+    SMX_HIP(img.ensure(2 * n));
+    SMX_HIP(code.ensure(2 * n * sizeof(uint64_t)));
+    SMX_HIP(dc.ensure(n * size_d * sizeof(float)));
+    SMX_HIP(hipMemcpy(img.p, i1, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + n, i2, n, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = smx_dev_census(p, img.as<uint8_t>(), code.as<uint64_t>(), w, h, 2, nullptr))) return rc;
+    if ((rc = smx_dev_census_cost_pair(p, code.as<uint64_t>(), dc.as<float>(), nullptr, w, h, dmin, 0, 0, size_d, nullptr)))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dc.download(cost, n * size_d * sizeof(float)));
+    return SMX_OK;
+}
+
+int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
+                      int size_d, int dmin) {
+    if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_sgm_aggregate: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    SMX_ARG(cost != nullptr);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = sgm_workspace_bytes(w, h, size_d, 1);
+    DevBuf dC, dA, dK, dW;
+    SMX_HIP(dC.upload(cost, vb));
+    if (agg) SMX_HIP(dA.ensure(vb));
+    SMX_HIP(dK.ensure(n * sizeof(int64_t)));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_sgm_wta_pair(p, dC.as<float>(), nullptr, w, h, size_d, dK.as<int64_t>(), agg ? dA.as<float>() : nullptr,
+                                      nullptr, dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (agg) SMX_HIP(dA.download(agg, vb));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(dK.download(keys.data(), n * sizeof(int64_t)));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
+int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
+    SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
+    const size_t n = (size_t)w * h;
+    DevBuf dI, dM, dV;
+    SMX_HIP(dI.upload(image, n));
+    SMX_HIP(dM.ensure(n));
+    SMX_HIP(dV.ensure(n * sizeof(float)));
+    if (int rc = smx_dev_filter(p, dI.as<uint8_t>(), w, h, dM.as<uint8_t>(), dV.as<float>(), nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dM.download(mean, n));
+    SMX_HIP(dV.download(var, n * sizeof(float)));
+    return SMX_OK;
+}
+
+}  // extern "C"

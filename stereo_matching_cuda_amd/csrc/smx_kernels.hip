@@ -565,7 +565,7 @@ __global__ void k_filter(const uint8_t* __restrict__ I, uint8_t* __restrict__ me
 }  // namespace smx
 
 // =====================================================================================
-// launchers (used by smx_capi.hip)
+// launchers (used by the C-ABI: smx_capi.hip, smx_ctx.hip)
 // =====================================================================================
 namespace smx {
 

@@ -1155,6 +1155,95 @@ def test_pipelined_context_equals_the_synchronous_entry(orc):
 
 
 @pytest.mark.gpu
+def test_one_context_through_changing_settings():
+    """ONE context taken through (a) the defaults, (b) the census cost through the chunk buffer, (c) the census cost with the
+    whole cost volumes asked, (d) SGM + census + sub-pixel + speckle removal with the aggregated volumes asked and no mean
+    images, (e) everything off again: at every step each plane handed out -- in (d) the sub-pixel maps and the despeckled map
+    too -- equals, bit for bit, what a FRESH context that is given only that step's settings hands out; (e) equals (a), and so
+    does one smx_ctx_stereo_pair_async / smx_ctx_wait round behind it.  This guards the one place that reserves the buffers of
+    the opt-in stages: a buffer a later step needs and an earlier one did not, or one kept from an earlier step, must not
+    change a result.  The fresh contexts are themselves pinned to the oracle and the numpy references by the test_context tests
+    of the stages.  At this shape the census chunk equals size_d, so the multi-chunk loop of the context is NOT exercised here;
+    test_chunks_and_split_calls covers that logic through the device API.  The caller's buffers are pre-filled differently for
+    the two contexts, so a plane that is not written at all cannot pass."""
+    from stereo_matching_cuda_amd import _lib
+    L = smx.lib()
+    w, h, D = 129, 70, 8
+    n = w * h
+    Il, Ir = synth.gen_pair(w, h, D, 31)
+    params, spk = smx.default_params(), _lib.default_speckle_params()
+    maps = ("best_l", "best_r", "dmap_l", "dmap_r", "occlusion", "filled")
+    eight = maps + ("mean_l", "mean_r")
+    steps = [("a", (), eight),
+             ("b", ("census",), eight),
+             ("c", ("census",), eight + ("cost_l", "cost_r")),
+             ("d", ("census", "sgm", "subpix", "speckle"), maps + ("agg_l", "agg_r")),
+             ("e", (), eight)]
+
+    def create():
+        ctx = C.c_void_p()
+        smx.check(L.smx_create(C.byref(params), w, h, D, C.byref(ctx)))
+        return ctx
+
+    def configure(ctx, on, every):
+        """every: call each setter, so that what an earlier step switched on goes off; else only the setters of what is on"""
+        if every or "census" in on:
+            smx.check(L.smx_ctx_set_cost(ctx, _lib.COST_MODES["census" if "census" in on else "reference"], None))
+        if every or "sgm" in on:
+            smx.check(L.smx_ctx_set_aggregation(ctx, _lib.AGG_MODES["sgm" if "sgm" in on else "guided"], None))
+        if every or "subpix" in on:
+            smx.check(L.smx_ctx_set_subpixel(ctx, _lib.SUBPIX_MODES["parabola"] if "subpix" in on else 0))
+        if every or "speckle" in on:
+            smx.check(L.smx_ctx_set_speckle(ctx, C.byref(spk) if "speckle" in on else None))
+
+    def outbufs(planes, fill):
+        bufs = {k: np.full(n * (D if k[:-2] in ("cost", "agg") else 1) * (1 if k.startswith("mean") else 4), fill, np.uint8)
+                .view(np.uint8 if k.startswith("mean") else np.float32) for k in planes}
+        return bufs, _lib.PairOut(**{k: v.ctypes.data for k, v in bufs.items() if hasattr(_lib.PairOut, k)})
+
+    def run(ctx, on, planes, fill):
+        bufs, out = outbufs(planes, fill)
+        smx.check(L.smx_ctx_stereo_pair(ctx, Il.ctypes.data, Ir.ctypes.data, -(D - 1), 0, C.byref(out)))
+        if "subpix" in on:
+            sub, _ = outbufs(("sub_l", "sub_r", "sub_filled"), fill)
+            smx.check(L.smx_ctx_subpixel_maps(ctx, *(sub[k].ctypes.data for k in ("sub_l", "sub_r", "sub_filled"))))
+            bufs.update(sub)
+        if "speckle" in on:
+            bufs["despeckled"] = outbufs(("despeckled",), fill)[0]["despeckled"]
+            smx.check(L.smx_ctx_speckle_map(ctx, bufs["despeckled"].ctypes.data))
+        return bufs
+
+    def same(got, want, name):
+        assert got.keys() == want.keys(), (name, sorted(got), sorted(want))
+        for k in got:
+            a, b = got[k], want[k]
+            if a.dtype == np.float32:
+                a, b = a.view(np.uint32), b.view(np.uint32)
+            assert np.array_equal(a, b), (name, k, int((a != b).sum()))
+
+    one = create()
+    try:
+        seen = {}
+        for name, on, planes in steps:
+            configure(one, on, every=True)
+            seen[name] = run(one, on, planes, 0xAA)
+            fresh = create()
+            try:
+                configure(fresh, on, every=False)
+                same(seen[name], run(fresh, on, planes, 0x55), "step " + name)
+            finally:
+                smx.check(L.smx_destroy(fresh))
+        assert "sub_filled" in seen["d"] and "despeckled" in seen["d"] and "agg_r" in seen["d"] and "cost_r" in seen["c"]
+        same(seen["e"], seen["a"], "e against a")
+        bufs, out = outbufs(eight, 0x33)
+        smx.check(L.smx_ctx_stereo_pair_async(one, Il.ctypes.data, Ir.ctypes.data, -(D - 1), 0))
+        smx.check(L.smx_ctx_wait(one, None, C.byref(out)))
+        same(bufs, seen["a"], "pipelined round against a")
+    finally:
+        smx.check(L.smx_destroy(one))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["tsukuba", "synthetic"])
 def test_fast_mode_is_close_but_not_bit_exact(tsukuba_gray, tsukuba_oracle, orc, shape):
     """the FAST aggregation (smx_set_agg_path(4)) is reported separately and never the default.
