@@ -181,10 +181,10 @@ int smx_dev_integral(const float* d_in, float* d_out, int w, int h, int nplanes,
  * (smx_dev_agg_status).  Fewer slices in flight than s_end - s_begin only means more launches.
  *
  * The memory contract of the five aggregation entries (smx_dev_aggregate_wta, _pair, _pair_cost, _nbr, _pair_nbr;
- * tests/test_gpu_memory_contract.py):
+ * tests/test_gpu_memory_contract.py) and of smx_dev_aggregate_wta_pair_uq (tests/test_gpu_uniq.py):
  *   - A call writes nothing outside [d_workspace, d_workspace + workspace_bytes) and the stated extents of its outputs:
  *     d_keys n keys per view, d_mean_u8 n bytes per view, d_agg (s_end - s_begin) * n floats per view, d_nbr 3n floats per
- *     view (n = w*h).  A workspace too small for one slice is SMX_E_WS before anything is launched or written.
+ *     view, d_uq 3n floats per view (n = w*h).  A workspace too small for one slice is SMX_E_WS before anything is launched or written.
  *   - The workspace may hold anything on entry: the call clears the status words, tickets and flags it relies on, and reads
  *     no other region before it has written it.
  *   - d_workspace needs no alignment: the call uses it from the next 256-byte boundary on, and the sizes below include the
@@ -519,6 +519,73 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
  * mean_l / mean_r are not produced (SMX_E_ARG if requested); radius and eps of smx_params are unused.  The volumes and the
  * workspace are allocated on first use.  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on. */
 int smx_ctx_set_aggregation(smx_ctx* ctx, int mode, const smx_sgm_params* sgm);
+
+/* ------------------------------------------------------------------------------------
+ * Uniqueness (peak-ratio) filtering (not a stage of the reference; opt-in, between the LR check and speckle removal)
+ * ---------------------------------------------------------------------------------- */
+
+/* The test of OpenCV's uniquenessRatio / libSGM's uniqueness: a winner is ambiguous when a disparity that is not its
+ * neighbour costs almost as little.  The aggregated volume q is normally never materialised, so the second-best cost is
+ * kept by the one pass that reads every q: the winner-take-all pass.
+ *
+ * The second-best cost.  For a pixel of one view the slices z come in ascending order with aggregated costs q(z).
+ *   winner:  (c0, z*) exactly as in the plain calls: the smallest cost, the last slice among equal costs, a NaN never wins.
+ *   sec   =  min { q(k) : k seen, |k - z*| >= 2, q(k) not NaN }, +inf if there is no such slice.  The winner's two
+ *            neighbours are left out because a good peak is wide; a tie two or more slices away gives sec == c0.  Among
+ *            equal values (-0 == +0) the bits are those of the first such slice.
+ * The streaming form.  State per pixel: the key (m, z*), sec, rest = the min of the costs of all seen slices except the last
+ * seen (+inf if none), last = the cost of the last seen slice (NaN if none).  At slice z with cost v, in f32 with plain
+ * comparisons (a NaN compares false):
+ *     take = v <= m
+ *     sec  = take ? rest : ((z >= z* + 2 && v < sec) ? v : sec)
+ *     m, z* = take ? (v, z) : (m, z*)
+ *     rest = last < rest ? last : rest ;  last = v
+ * When the winner moves to z, everything up to z - 2 is non-adjacent to it: that is `rest`.  A run resumed from the stored
+ * state (m, z* unpacked from the key; an identity key starts blank and reads no state) equals one run over all slices,
+ * whatever the chunking; there is no merge step.
+ *
+ * State.  d_uq holds three f32 planes [3][h][w] per view: 0 sec, 1 rest, 2 last (6n floats for a pair, left view first).
+ *   - IN/OUT like d_keys; it needs no initialisation: a pixel whose key is the identity, or a call made with fresh keys
+ *     (smx_set_keys_fresh), starts without state.
+ *   - Calls on one set of keys must cover ascending, contiguous slice ranges (the _nbr rule).
+ *   - It does not combine across D-shards, and it is independent of d_nbr: both may be requested in one call.
+ *
+ * smx_dev_aggregate_wta_pair_uq: smx_dev_aggregate_wta_pair_nbr that also keeps d_uq (required); d_nbr NULL or 6n floats;
+ * d_cost_l / d_cost_r both NULL or both set.  Keys (and d_nbr, d_agg, d_mean_u8) are those of the other entries, bit for
+ * bit.  It honours smx_set_max_slices_per_launch, smx_set_keys_fresh, every aggregation path and the queued ring-walker
+ * fall-back; same workspace, same number of launches.
+ * smx_dev_sgm_wta_pair_uq: smx_dev_sgm_wta_pair that also writes d_uq (required; 3n floats per view of the call) after its one
+ * run over the whole range; same launches, same workspace.  Exact: S are integers. */
+int smx_dev_aggregate_wta_pair_uq(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
+                                  const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr,
+                                  int s_begin, int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg,
+                                  void* d_workspace, size_t workspace_bytes, float* d_nbr, float* d_uq, void* stream);
+int smx_dev_sgm_wta_pair_uq(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                            int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes,
+                            void* stream);
+/* The test, one view: c0 = the cost of d_keys[p], s = d_uq[p] (the sec plane; n = w*h keys and floats are read).
+ *   rejected: pixel p is rejected iff its key is not the identity, ratio > 0 and s - c0 < ratio * fabsf(c0), in f32 without
+ *             contraction.  ratio: finite and >= 0 (SMX_E_ARG otherwise); 0 rejects nothing; OpenCV's u percent is
+ *             ratio = u / (100 - u).  An unknown s (+inf, NaN) is never rejected.
+ *   result:   d_out[p] = new_val iff d_disp[p] counts -- the speckle filter's validity rule against vmin -- and p is
+ *             rejected; every other pixel is copied bit for bit.  d_out == d_disp is allowed.
+ *   d_margin: NULL, or n floats out: s - c0, +inf where s is unknown, NaN where the key is the identity.
+ * smx_dev_uniqueness: device pointers, one kernel launch on `stream`, no allocation, no synchronisation, no workspace
+ * (graph-capturable); it writes the n floats of d_out and of d_margin only.  smx_uniqueness_filter: host pointers,
+ * synchronous; uq needs its first n floats (the sec plane) only. */
+int smx_dev_uniqueness(float ratio, const int64_t* d_keys, const float* d_uq, const float* d_disp, float* d_out,
+                       float* d_margin, int w, int h, float vmin, float new_val, void* stream);
+int smx_uniqueness_filter(float ratio, const int64_t* keys, const float* uq, const float* disp, float* out, float* margin, int w,
+                          int h, float vmin, float new_val);
+/* The uniqueness test of this context: ratio 0 switches it off (the default); NaN, negative or infinite is SMX_E_ARG.  While
+ * it is on, smx_ctx_stereo_pair keeps the state of both views (with either cost, either aggregation and both census chunk
+ * loops) and filters the left map after the LR check with vmin = dminl, new_val = dminl - 100.  Order: LR check -> uniqueness
+ * -> speckle -> fill -> sub-pixel sub_filled; out->filled is the fill of the last of these maps, out->occlusion stays the
+ * LR-check map.  smx_ctx_stereo_pair_async returns SMX_E_ARG.  smx_ctx_uniqueness_map copies the filtered map and the
+ * margins of the last synchronous smx_ctx_stereo_pair of the context (n floats each; either may be NULL); SMX_E_ARG if that
+ * pair ran without the test.  Buffers are allocated on first use. */
+int smx_ctx_set_uniqueness(smx_ctx* ctx, float ratio);
+int smx_ctx_uniqueness_map(smx_ctx* ctx, float* map, float* margin);
 
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);

@@ -18,11 +18,11 @@ from ._lib import (CensusParams, Params, SgmParams, SmxError, SpeckleParams, Wmf
                    subpixel_delta)
 from .stages import (census_cost, census_transform, compute_cost, compute_guided_filter, detect_occlusion,  # noqa: F401
                      fill_occlusion, filter, init_wta, integral, rgb_to_grayscale, sgm_aggregate, speckle_filter, stereo_pair,
-                     weighted_median, wmf_weights, write_mat)
+                     uniqueness_filter, weighted_median, wmf_weights, write_mat)
 
 __all__ = ["Params", "SmxError", "build", "default_params", "lib", "rgb_to_grayscale",
            "compute_cost", "compute_guided_filter", "integral", "detect_occlusion", "fill_occlusion",
            "init_wta", "stereo_pair", "write_mat", "filter", "check", "WmfParams", "default_wmf_params",
            "weighted_median", "wmf_weights", "subpixel_delta", "CensusParams", "default_census_params",
            "census_transform", "census_cost", "SpeckleParams", "default_speckle_params", "speckle_filter",
-           "SgmParams", "default_sgm_params", "sgm_aggregate"]
+           "SgmParams", "default_sgm_params", "sgm_aggregate", "uniqueness_filter"]

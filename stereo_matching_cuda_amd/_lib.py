@@ -157,6 +157,13 @@ SIGNATURES = {
     "smx_dev_sgm_wta_pair": (_i, [_GP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "smx_sgm_aggregate": (_i, [_GP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_aggregation": (_i, [_vp, _i, _GP]),
+    "smx_dev_aggregate_wta_pair_uq": (_i, [_PP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
+                                          _vp, _vp]),
+    "smx_dev_sgm_wta_pair_uq": (_i, [_GP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_dev_uniqueness": (_i, [_f, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),
+    "smx_uniqueness_filter": (_i, [_f, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f]),
+    "smx_ctx_set_uniqueness": (_i, [_vp, _f]),
+    "smx_ctx_uniqueness_map": (_i, [_vp, _vp, _vp]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name

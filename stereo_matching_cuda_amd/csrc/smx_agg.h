@@ -9,7 +9,8 @@ namespace smx {
 // One aggregation call: aggregation + WTA of slices [s_begin, s_end) of `nviews` (1 or 2) views.  View v uses guide[v] as
 // guidance; its cost slices are cost[v] (materialised, slice s at (s - s_begin)*w*h; all views or none) or, where cost[v] is
 // NULL, are built on the fly against other[v].  Pointers are NULL where absent: mean_u8 (the u8 mean image), agg (the
-// aggregated volume), nbr (the winners' neighbours, smx_common.h nbr_merge).  Everything a call depends on is here or in AggOpts.
+// aggregated volume), nbr (the winners' neighbours, smx_common.h nbr_merge), uq (the winners' second-best cost, smx_common.h
+// WtaRunUq).  Everything a call depends on is here or in AggOpts.
 struct AggCall {
     const char* who;         // the C-ABI entry, for error texts
     const smx_params* p;
@@ -22,6 +23,7 @@ struct AggCall {
     uint8_t* mean_u8[2];
     float* agg[2];
     float* nbr[2];
+    float* uq[2];
     int w, h, s_begin, s_end;
     void* ws;                // the caller's workspace, any alignment
     size_t ws_bytes;

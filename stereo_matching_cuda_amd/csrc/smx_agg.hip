@@ -245,6 +245,7 @@ static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) 
     const bool use_cost = c.cost[0] != nullptr;
     const bool own_q = !c.agg[0];
     float* const* const d_nbr = c.nbr[0] ? c.nbr : nullptr;
+    float* const* const d_uq = c.uq[0] ? c.uq : nullptr;
     char* const base = (char*)align_up((size_t)c.ws, 256);
     AggLayout L;
     int rc = agg_plan(p, w, h, nviews, use_cost, own_q, opt, c.ws_bytes, (size_t)(base - (char*)c.ws), s_end - s_begin, &L);
@@ -309,14 +310,15 @@ static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) 
         // of loading them, which saves the smx_dev_init_keys launch in front of the call; with the gated pair of passes of a
         // queued fall-back exactly one of the two runs, so both may take the flag)
         const bool fresh = opt.keys_fresh && s0 == s_begin;
-        // (d_nbr: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge)
+        // (d_nbr / d_uq: the same passes that also keep the winners' neighbours, smx_common.h nbr_merge, and their second-best
+        // cost, WtaRunUq; of the gated pair exactly one runs, so the state is advanced once)
         // over the planes of the walker that ran (smx_wta.h: runs iff gate == NULL || (*gate != 0) == gate_nonzero) ...
         const bool comb_q = L.comb && own_q;
-        rc = wta_launch(comb_q ? WTA_COMB : WTA_NATURAL, nviews, q, c.keys, d_nbr, w, h, L.qplane, cnt, s0, comb_q ? fell_back : nullptr,
-                        0, fresh, st);
+        rc = wta_launch(comb_q ? WTA_COMB : WTA_NATURAL, nviews, q, c.keys, d_nbr, d_uq, w, h, L.qplane, cnt, s0,
+                        comb_q ? fell_back : nullptr, 0, fresh, st);
         if (!rc && comb_q && L.fallback) {
             // ... and over the ring walker's planes ([slice][h][w] at the start of the same buffers), if it ran
-            rc = wta_launch(WTA_NATURAL, nviews, q, c.keys, d_nbr, w, h, L.plane, cnt, s0, fell_back, 1, fresh, st);
+            rc = wta_launch(WTA_NATURAL, nviews, q, c.keys, d_nbr, d_uq, w, h, L.plane, cnt, s0, fell_back, 1, fresh, st);
             ++nl;
         }
         if (rc) return rc;
@@ -412,7 +414,7 @@ static int aggregate_multi(const AggCall& c, const AggOpts& opt, AggInfo* info) 
             if ((rc = launch_ab(p, T0, T1, mean_im, cinv, A, B, w, h, cnt, st))) return rc;
             if ((rc = launch_integral(2, A, B, A, B, w, h, cnt, st))) return rc;
             float* agg = c.agg[v] ? c.agg[v] + (int64_t)(s0 - c.s_begin) * n : nullptr;
-            if ((rc = launch_q_wta(p, A, B, im, c.keys[v], c.nbr[v], agg, w, h, cnt, s0, st))) return rc;
+            if ((rc = launch_q_wta(p, A, B, im, c.keys[v], c.nbr[v], c.uq[v], agg, w, h, cnt, s0, st))) return rc;
             info->launches += 6;
             stage_mark(ST_WALK, st);
         }

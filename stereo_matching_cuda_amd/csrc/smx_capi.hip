@@ -100,6 +100,7 @@ bool wmf_params_ok(const smx_wmf_params* p) {
            p->sigma_c > 0;
 }
 bool census_params_ok(const smx_census_params* p) { return p && p->rx >= 1 && p->rx <= 4 && p->ry >= 1 && p->ry <= 3 && p->th >= 1; }
+bool uniq_ratio_ok(float ratio) { return isfinite(ratio) && ratio >= 0.0f; }
 bool speckle_params_ok(const smx_speckle_params* p) { return p && p->max_size >= 0 && isfinite(p->max_diff) && p->max_diff >= 0.0f; }
 bool speckle_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
 bool sgm_params_ok(const smx_sgm_params* p) {
@@ -291,6 +292,24 @@ __attribute__((visibility("default"))) int smx_debug_wta_run(const float* q, int
     return SMX_OK;
 }
 
+// (dev / test hook, not in smx.h: WtaRunUq over one chunk of ascending slices, resumed from key / state [sec, rest, last] and
+// left there -- the pixel of the UQ passes on the host)
+__attribute__((visibility("default"))) int smx_debug_uq_run(const float* q, int n, uint32_t slice0, int64_t* key, float* state) {
+    SMX_ARG(q && key && state && n >= 0);
+    WtaRunUq r;
+    r.resume(*key, state[0], state[1], state[2]);
+    for (int i = 0; i < n; ++i) r.step(q[i], slice0 + (uint32_t)i);
+    *key = r.key();
+    state[0] = r.sec; state[1] = r.rest; state[2] = r.last;
+    return SMX_OK;
+}
+
+// (dev / test hook, not in smx.h: the uniqueness test of one pixel as the filter kernel forms it; returns 1 where rejected)
+__attribute__((visibility("default"))) int smx_debug_uniq_test(int64_t key, float s, float ratio, float* margin) {
+    SMX_ARG(margin);
+    return uniq_rejects(key, s, ratio, margin) ? 1 : 0;
+}
+
 // (dev / test hook, not in smx.h: the comb walker's slot geometry for an image of h rows in K strips -- bands per item, the
 // last stage-2 slot, the period between the starts of two items of a workgroup -- for tools/v5_protocol_sim.py)
 __attribute__((visibility("default"))) int smx_debug_v5_period(int h, int K, int* bands, int* q_last, int* period) {
@@ -412,7 +431,7 @@ static int aggregate_view(const char* who, const smx_params* p, const uint8_t* d
     SMX_ARG(p && d_guide && d_keys && d_workspace);
     SMX_ARG(d_cost || d_other);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
-    const AggCall c = {who, p, 1, {d_guide}, {d_other}, {d_cost}, {dmin}, {d_keys}, {d_mean_u8}, {d_agg}, {d_nbr},
+    const AggCall c = {who, p, 1, {d_guide}, {d_other}, {d_cost}, {dmin}, {d_keys}, {d_mean_u8}, {d_agg}, {d_nbr}, {nullptr},
                        w, h, s_begin, s_end, d_workspace, workspace_bytes, (hipStream_t)stream};
     return dev_aggregate(c);
 }
@@ -437,7 +456,7 @@ int smx_dev_aggregate_wta_nbr(const smx_params* p, const uint8_t* d_guide, const
 static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
                           const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin,
                           int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg, void* d_workspace,
-                          size_t workspace_bytes, void* stream, float* d_nbr = nullptr) {
+                          size_t workspace_bytes, void* stream, float* d_nbr = nullptr, float* d_uq = nullptr) {
     SMX_ARG(p && d_left && d_right && d_keys && d_workspace);
     SMX_ARG(w >= 2 && h >= 1 && s_begin >= 0 && s_end >= s_begin && p->radius >= 0);
     SMX_ARG((d_cost_l != nullptr) == (d_cost_r != nullptr));
@@ -445,7 +464,7 @@ static int aggregate_pair(const char* who, const smx_params* p, const uint8_t* d
     const int64_t vol = n * (s_end - s_begin);
     const AggCall c = {who, p, 2, {d_left, d_right}, {d_right, d_left}, {d_cost_l, d_cost_r}, {dminl, dminr}, {d_keys, d_keys + n},
                        {d_mean_u8, d_mean_u8 ? d_mean_u8 + n : nullptr}, {d_agg, d_agg ? d_agg + vol : nullptr},
-                       {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr},
+                       {d_nbr, d_nbr ? d_nbr + 3 * n : nullptr}, {d_uq, d_uq ? d_uq + 3 * n : nullptr},
                        w, h, s_begin, s_end, d_workspace, workspace_bytes, (hipStream_t)stream};
     return dev_aggregate(c);
 }
@@ -474,6 +493,22 @@ int smx_dev_aggregate_wta_pair_nbr(const smx_params* p, const uint8_t* d_left, c
     SMX_ARG(d_nbr);
     return aggregate_pair("smx_dev_aggregate_wta_pair_nbr", p, d_left, d_right, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin,
                           s_end, d_keys, d_mean_u8, d_agg, d_workspace, workspace_bytes, stream, d_nbr);
+}
+
+int smx_dev_aggregate_wta_pair_uq(const smx_params* p, const uint8_t* d_left, const uint8_t* d_right,
+                                  const float* d_cost_l, const float* d_cost_r, int w, int h, int dminl, int dminr,
+                                  int s_begin, int s_end, int64_t* d_keys, uint8_t* d_mean_u8, float* d_agg,
+                                  void* d_workspace, size_t workspace_bytes, float* d_nbr, float* d_uq, void* stream) {
+    SMX_ARG(d_uq);
+    return aggregate_pair("smx_dev_aggregate_wta_pair_uq", p, d_left, d_right, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin,
+                          s_end, d_keys, d_mean_u8, d_agg, d_workspace, workspace_bytes, stream, d_nbr, d_uq);
+}
+
+int smx_dev_uniqueness(float ratio, const int64_t* d_keys, const float* d_uq, const float* d_disp, float* d_out,
+                       float* d_margin, int w, int h, float vmin, float new_val, void* stream) {
+    SMX_ARG(uniq_ratio_ok(ratio));
+    SMX_ARG(d_keys && d_uq && d_disp && d_out && w >= 1 && h >= 1);
+    return launch_uniqueness(ratio, d_keys, d_uq, d_disp, d_out, d_margin, (int64_t)w * h, vmin, new_val, (hipStream_t)stream);
 }
 
 int smx_dev_subpixel_pair(int mode, const int64_t* d_keys, const float* d_nbr, const float* d_dmap, const float* d_occlusion,
@@ -579,18 +614,33 @@ size_t smx_sgm_workspace_bytes(int w, int h, int size_d, int nviews) {
     return sgm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? sgm_workspace_bytes(w, h, size_d, nviews) : 0;
 }
 
-int smx_dev_sgm_wta_pair(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
-                         int64_t* d_keys, float* d_agg, float* d_nbr, void* d_ws, size_t ws_bytes, void* stream) {
+static int sgm_wta_pair(const char* who, const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h,
+                        int size_d, int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes,
+                        void* stream) {
     if (!sgm_params_ok(p))
-        return fail(SMX_E_ARG, "smx_dev_sgm_wta_pair: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
+        return fail(SMX_E_ARG, "%s: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8", who);
     if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_dev_sgm_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+        return fail(SMX_E_ARG, "%s: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", who, SMX_SGM_MAX_D);
     SMX_ARG((d_cost_l || d_cost_r) && d_keys);
     const size_t need = sgm_workspace_bytes(w, h, size_d, d_cost_l && d_cost_r ? 2 : 1);
     if (!d_ws || ws_bytes < need)
-        return fail(SMX_E_WS, "smx_dev_sgm_wta_pair: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0, need);
-    return launch_sgm_wta_pair(p->p1, p->p2, p->paths, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_ws,
+        return fail(SMX_E_WS, "%s: workspace of %zu bytes, %zu needed", who, d_ws ? ws_bytes : (size_t)0, need);
+    return launch_sgm_wta_pair(p->p1, p->p2, p->paths, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_uq, d_ws,
                                (hipStream_t)stream);
+}
+
+int smx_dev_sgm_wta_pair(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                         int64_t* d_keys, float* d_agg, float* d_nbr, void* d_ws, size_t ws_bytes, void* stream) {
+    return sgm_wta_pair("smx_dev_sgm_wta_pair", p, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, nullptr, d_ws, ws_bytes,
+                        stream);
+}
+
+int smx_dev_sgm_wta_pair_uq(const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                            int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes,
+                            void* stream) {
+    SMX_ARG(d_uq);
+    return sgm_wta_pair("smx_dev_sgm_wta_pair_uq", p, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_uq, d_ws, ws_bytes,
+                        stream);
 }
 
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,

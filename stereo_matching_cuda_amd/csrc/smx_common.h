@@ -150,6 +150,59 @@ __host__ __device__ inline int64_t nbr_merge(const WtaRunNbr& r, int64_t key_in,
     return kk < key_in ? kk : key_in;
 }
 
+// ---- second-best cost of the winner (uniqueness test, smx_uniq.hip) ----------------------------------------------------
+// WtaRun plus sec = the smallest cost among the seen slices at least two away from the winner (+inf if there is none; a
+// NaN never counts), kept in one pass by two more values: rest = the smallest cost of all seen slices but the last seen
+// (+inf if none), last = the cost of the last seen slice (NaN if none).  When the winner moves to slice z, every slice up
+// to z - 2 is non-adjacent to it, and their minimum is `rest`; while it stays, a slice from z* + 2 on competes for sec
+// directly.  Same winner as WtaRun.  Every minimum takes a value only where it is strictly smaller, so among equal costs
+// (-0 == +0) the first seen stays: one ascending scan from +inf over the eligible slices gives the same bits.
+// The state (m, z, sec, rest, last) is all a run needs: a run resumed from it equals one run over all slices, whatever the
+// chunking -- no merge step.  Per-pixel state d_uq of a view: three f32 planes [3][h][w] -- 0 sec, 1 rest, 2 last; m and z
+// come back from the pixel's key (resume), an identity key starts blank.
+struct WtaRunUq {
+    float m = __builtin_inff();
+    uint32_t z = 0xFFFFFFFFu;
+    float sec = __builtin_inff(), rest = __builtin_inff(), last = __builtin_nanf("");
+    __host__ __device__ inline void resume(int64_t key, float sec_in, float rest_in, float last_in) {
+        const bool on = key != KEY_IDENTITY;
+        float c;
+        uint32_t s;
+        unpack_key(key, &c, &s);
+        m = on ? c : __builtin_inff();
+        z = on ? s : 0xFFFFFFFFu;
+        sec = on ? sec_in : __builtin_inff();
+        rest = on ? rest_in : __builtin_inff();
+        last = on ? last_in : __builtin_nanf("");
+    }
+    __host__ __device__ inline void step(float q, uint32_t slice) {
+        const bool take = q <= m;
+        // (no winner yet: z + 2 wraps to 1, but every q so far was a NaN, this one too -- else it is taken -- and q < sec is false)
+        const bool far = slice >= z + 2u && q < sec;
+        sec = take ? rest : (far ? q : sec);
+        m = take ? q : m;
+        z = take ? slice : z;
+        rest = last < rest ? last : rest;
+        last = q;
+    }
+    __host__ __device__ inline int64_t key() const { return z == 0xFFFFFFFFu ? KEY_IDENTITY : pack_key(m, z); }
+};
+
+// The uniqueness (peak-ratio) test of one pixel: c0 = the cost of its key, s = its sec.  Rejected iff the key is not the
+// identity and s - c0 < ratio * |c0| (f32, each operation rounded on its own); an infinite or NaN s rejects nothing, nor
+// does ratio == 0.  *margin = s - c0: +inf where s is unknown (+inf or NaN), NaN where the key is the identity.
+__host__ __device__ inline bool uniq_rejects(int64_t key, float s, float ratio, float* margin) {
+    if (key == KEY_IDENTITY) { *margin = __builtin_nanf(""); return false; }
+    float c0;
+    uint32_t z;
+    unpack_key(key, &c0, &z);
+    if (!(s < __builtin_inff())) { *margin = __builtin_inff(); return false; }     // +inf, NaN: unknown
+    const float d = s - c0;
+    *margin = d;
+    const float bound = ratio * fabsf(c0);
+    return ratio > 0.0f && d < bound;
+}
+
 // The sub-pixel offset of a winner of cost c0 from its neighbours lo, hi (SMX_SUBPIX_PARABOLA / SMX_SUBPIX_EQUIANGULAR;
 // smx_subpixel_delta is the host copy of the C-ABI): 0 for an unknown neighbour (NaN) and for a result that is not finite
 __host__ __device__ inline float subpixel_delta(int mode, float c0, float lo, float hi) {

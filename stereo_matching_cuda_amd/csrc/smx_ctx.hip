@@ -37,6 +37,10 @@ struct smx_ctx {
     int agg_mode = SMX_AGG_GUIDED;
     smx_sgm_params sgm;
     DevBuf sgm_ws;
+    // uniqueness filtering (smx_ctx_set_uniqueness): the state [2][3][h][w], the filtered left map and the margins [h][w]
+    float uniq = 0.0f;          // the ratio; 0 = off
+    bool uq_valid = false;      // the maps belong to the last synchronous pair
+    DevBuf uq, uq_map, uq_margin;
     // pipelined entry: two slots of device inputs / results and pinned staging, created on first use.  Staging of a slot:
     // [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l mean_r | status word] coming down.
     struct Slot {
@@ -62,7 +66,7 @@ struct smx_ctx {
 // What one pair asks of the context beyond the eight result planes, decided once per pair by the entry that was called
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them); its device images with the disparity of
 // slice 0 of either view; where its results go on the device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -80,6 +84,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
         SMX_HIP(c->ccost.ensure(2 * (size_t)c->census_chunk * fb));
     }
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
+    if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
     return SMX_OK;
 }
 
@@ -129,6 +134,7 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     float* const costR = need.cost ? c->costR.as<float>() : nullptr;
     float* const aggL = need.agg ? c->aggLR.as<float>() : nullptr;
     float* const nbrL = need.subpix ? c->nbr.as<float>() : nullptr;
+    float* const uqL = need.uniq ? c->uq.as<float>() : nullptr;     // (no initialisation: the keys start as the identity)
     if (need.cost && !need.census) {
         if ((rc = smx_dev_cost_volume(p, in.left, in.right, costL, w, w, h, in.dminl, 0, size_d, st))) return rc;
         if ((rc = smx_dev_cost_volume(p, in.right, in.left, costR, w, w, h, in.dminr, 0, size_d, st))) return rc;
@@ -138,14 +144,16 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     const AggCall call = {"smx_ctx_stereo_pair", p, 2, {in.left, in.right}, {in.right, in.left}, {costL, costR},
                           {in.dminl, in.dminr}, {keysL, keysL + n}, {out.mean, out.mean + n},
                           {aggL, need.agg ? aggL + (size_t)size_d * n : nullptr}, {nbrL, need.subpix ? nbrL + 3 * n : nullptr},
-                          w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
+                          {uqL, need.uniq ? uqL + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
     if (need.census && (rc = ctx_census_codes(c, call))) return rc;
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
         if (need.census) rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), costL, costR, w, h, in.dminl,
                                                        in.dminr, 0, size_d, st);
-        if (!rc) rc = smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p,
-                                           sgm_workspace_bytes(w, h, size_d, 2), st);
+        const size_t sgm_bytes = sgm_workspace_bytes(w, h, size_d, 2);
+        if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->sgm_ws.p,
+                                                          sgm_bytes, st)
+                                : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p, sgm_bytes, st);
     } else if (need.census) rc = ctx_census_aggregate(c, call, need.cost);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
@@ -154,10 +162,20 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
                                   out.occ, out.fil, st)))
         return rc;
     const float* kept = out.occ;    // the map whose validity test says which pixels the fill replaced
+    if (need.uniq) {
+        // the ambiguous winners of the LR-checked left map join the invalidated pixels; the fill starts over from that map
+        // (unless speckle removal follows, which does it)
+        float* um = c->uq_map.as<float>();
+        if ((rc = smx_dev_uniqueness(c->uniq, keysL, uqL, out.occ, um, c->uq_margin.as<float>(), w, h, (float)in.dminl,
+                                     (float)(in.dminl - 100), st)))
+            return rc;
+        if (!need.speckle && (rc = launch_fill_occlusion(um, out.fil, w, h, (float)in.dminl, st))) return rc;
+        kept = um;
+    }
     if (need.speckle) {
         // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
         float* spk = c->spk.as<float>();
-        if ((rc = smx_dev_speckle_filter(&c->spk_params, out.occ, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
+        if ((rc = smx_dev_speckle_filter(&c->spk_params, kept, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
                                          c->spk_ws.p, speckle_workspace_bytes(w, h), st)))
             return rc;
         if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
@@ -241,9 +259,9 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     if (sgm && (out->mean_l || out->mean_r))
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair: semi-global matching (smx_ctx_set_aggregation) produces no mean images");
     const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle};
+                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle, c->uniq > 0.0f};
     if ((rc = ctx_reserve(c, need))) return rc;
-    c->sub_valid = c->spk_valid = false;
+    c->sub_valid = c->spk_valid = c->uq_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     stage_mark(ST_BEGIN, st);
     SMX_HIP(hipMemcpyAsync(dL, gray_l, n, hipMemcpyHostToDevice, st));
@@ -262,6 +280,7 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
     if (!need.sgm && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM kernels wait for nothing)
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
+    c->uq_valid = need.uniq;
     return SMX_OK;
 }
 
@@ -327,6 +346,22 @@ int smx_ctx_speckle_map(smx_ctx* c, float* despeckled) {
     return SMX_OK;
 }
 
+int smx_ctx_set_uniqueness(smx_ctx* c, float ratio) {
+    SMX_ARG(c);
+    if (!uniq_ratio_ok(ratio)) return fail(SMX_E_ARG, "smx_ctx_set_uniqueness: the ratio must be finite and >= 0 (0 = off)");
+    c->uniq = ratio;
+    return SMX_OK;
+}
+
+int smx_ctx_uniqueness_map(smx_ctx* c, float* map, float* margin) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_uniqueness_map")) return rc;
+    if (!c->uq_valid) return fail(SMX_E_ARG, "smx_ctx_uniqueness_map: the last smx_ctx_stereo_pair ran without the uniqueness test");
+    if (map) SMX_HIP(c->uq_map.download(map, c->n * sizeof(float)));
+    if (margin) SMX_HIP(c->uq_margin.download(margin, c->n * sizeof(float)));
+    return SMX_OK;
+}
+
 int smx_ctx_subpixel_maps(smx_ctx* c, float* sub_l, float* sub_r, float* sub_filled) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_subpixel_maps")) return rc;
@@ -362,6 +397,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
     if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
+    if (c->uniq > 0.0f)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
     if (c->cost_mode != SMX_COST_REFERENCE)

@@ -138,6 +138,25 @@ int smx_speckle_filter(const smx_speckle_params* p, const float* disp, float* ou
     return SMX_OK;
 }
 
+int smx_uniqueness_filter(float ratio, const int64_t* keys, const float* uq, const float* disp, float* out, float* margin, int w,
+                          int h, float vmin, float new_val) {
+    SMX_ARG(uniq_ratio_ok(ratio));
+    SMX_ARG(keys && uq && disp && out && w >= 1 && h >= 1);
+    const size_t n = (size_t)w * h, bytes = n * sizeof(float);
+    DevBuf dK, dU, dD, dM;
+    SMX_HIP(dK.upload(keys, n * sizeof(int64_t)));
+    SMX_HIP(dU.upload(uq, bytes));                    // (the test reads the sec plane only)
+    SMX_HIP(dD.upload(disp, bytes));
+    if (margin) SMX_HIP(dM.ensure(bytes));
+    if (int rc = smx_dev_uniqueness(ratio, dK.as<int64_t>(), dU.as<float>(), dD.as<float>(), dD.as<float>(),
+                                    margin ? dM.as<float>() : nullptr, w, h, vmin, new_val, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dD.download(out, bytes));
+    if (margin) SMX_HIP(dM.download(margin, bytes));
+    return SMX_OK;
+}
+
 int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h,
                     int size_d, int dmin) {
     SMX_ARG(census_params_ok(p) && i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);

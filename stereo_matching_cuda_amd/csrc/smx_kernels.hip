@@ -266,11 +266,12 @@ __global__ void k_ab(const float* __restrict__ Sp, const float* __restrict__ SIp
 // q = box(S_a)*I + box(S_b) and running WTA over the chunk's slices
 // (guidedFilter.cu:363-369 compute_q, :403-411 dispSelectOnGPU).  One lane per pixel; the pixel's state, its merge with
 // the incoming key and the stores are WtaPixel (smx_wta.h): ties go to the larger slice like `if (best >= q) {...}` with
-// slices ascending.  NBR: also keeps the winner's neighbouring q in the view's state planes nbr [3][h][w].
+// slices ascending.  NBR: also keeps the winner's neighbouring q in the view's state planes nbr [3][h][w]; UQ: its
+// second-best cost in uq [3][h][w].
 // =====================================================================================
-template <bool NBR>
+template <bool NBR, bool UQ>
 __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ Sb,
-                        const float* __restrict__ im, int64_t* keys, float* nbr,
+                        const float* __restrict__ im, int64_t* keys, float* nbr, float* uq,
                         float* __restrict__ agg, int w, int h, int count, int slice0, int R) {
     int x = blockIdx.x * blockDim.x + threadIdx.x;
     int y = blockIdx.y;
@@ -279,8 +280,8 @@ __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ 
     BoxTaps t = box_taps(x, y, w, h, R);
     int64_t id = (int64_t)y * w + x;
     float I = im[id];
-    WtaPixel<NBR> px;
-    px.load(keys, nbr, (size_t)n, (size_t)id, true, false);
+    WtaPixel<NBR, UQ> px;
+    px.load(keys, nbr, uq, (size_t)n, (size_t)id, true, false);
     for (int z = 0; z < count; ++z) {
         const int64_t po = (int64_t)z * n;
         float abar = box_eval(Sa + po, t);
@@ -292,7 +293,7 @@ __global__ void k_q_wta(const float* __restrict__ Sa, const float* __restrict__ 
         if (agg) agg[po + id] = q;
     }
     px.merge((uint32_t)slice0);
-    px.store(keys, nbr, (size_t)n, (size_t)id);
+    px.store(keys, nbr, uq, (size_t)n, (size_t)id);
 }
 
 __global__ void k_init_keys(int64_t* keys, int64_t n) {
@@ -634,13 +635,16 @@ int launch_ab(const smx_params* p, const float* Sp, const float* SIp, const floa
 }
 
 int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                 int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
+                 int64_t* keys, float* nbr, float* uq, float* agg, int w, int h, int count, int slice0, hipStream_t st) {
     if (count <= 0) return SMX_OK;
     dim3 grid(cdiv(w, 256), h);
-    if (nbr)
-        hipLaunchKernelGGL(k_q_wta<true>, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0, p->radius);
-    else
-        hipLaunchKernelGGL(k_q_wta<false>, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, agg, w, h, count, slice0, p->radius);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, Sa, Sb, im, keys, nbr, uq, agg, w, h, count, slice0, p->radius);
+    };
+    if (nbr && uq) go(k_q_wta<true, true>);
+    else if (uq) go(k_q_wta<false, true>);
+    else if (nbr) go(k_q_wta<true, false>);
+    else go(k_q_wta<false, false>);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }

@@ -13,9 +13,10 @@ int launch_guid_finish(const smx_params* p, const float* S_im, const float* S_sq
                        float* cinv, uint8_t* mean_u8, int w, int h, hipStream_t st);
 int launch_ab(const smx_params* p, const float* Sp, const float* SIp, const float* mean_im,
               const float* cinv, float* A, float* B, int w, int h, int nplanes, hipStream_t st);
-// (nbr != NULL: the pass also keeps the winners' neighbours in the view's state planes [3][h][w])
+// (nbr != NULL: the pass also keeps the winners' neighbours in the view's state planes [3][h][w]; uq != NULL: their
+// second-best cost, in planes of the same shape)
 int launch_q_wta(const smx_params* p, const float* Sa, const float* Sb, const float* im,
-                 int64_t* keys, float* nbr, float* agg, int w, int h, int count, int slice0, hipStream_t st);
+                 int64_t* keys, float* nbr, float* uq, float* agg, int w, int h, int count, int slice0, hipStream_t st);
 int launch_init_keys(int64_t* keys, int64_t n, hipStream_t st);
 int launch_init_wta(float* best, float* dmap, int64_t n, hipStream_t st);
 int launch_apply_keys(const int64_t* keys, int64_t n, int dmin, float* best, float* dmap, hipStream_t st);
@@ -49,5 +50,8 @@ void speckle_tile(int* tw, int* th);
 int sgm_padded_d(int size_d);
 size_t sgm_workspace_bytes(int w, int h, int size_d, int nviews);
 int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const float* cost_r, int w, int h, int size_d,
-                        int64_t* keys, float* agg, float* nbr, void* ws, hipStream_t st);
+                        int64_t* keys, float* agg, float* nbr, float* uq, void* ws, hipStream_t st);
+// smx_uniq.hip: the uniqueness test on a disparity map (smx_dev_uniqueness)
+int launch_uniqueness(float ratio, const int64_t* keys, const float* uq, const float* disp, float* out, float* margin, int64_t n,
+                      float vmin, float new_val, hipStream_t st);
 }  // namespace smx

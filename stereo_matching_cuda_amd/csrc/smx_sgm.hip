@@ -38,6 +38,7 @@ struct SgmArgs {
     int64_t* keys[2];
     float* agg[2];
     float* nbr[2];
+    float* uq[2];
     uint8_t* c8[2];
     uint16_t* s16[2];
     int w, h, size_d, dp, p1, p2, xtiles;
@@ -249,6 +250,15 @@ __global__ __launch_bounds__(256) void k_sgm_select(const SgmArgs a) {
         nb[n] = z + 1 < a.size_d ? (float)mine[z + 1] : __builtin_nanf("");
         nb[2 * n] = (float)mine[a.size_d - 1];
     }
+    if (a.uq[v]) {
+        // the uniqueness state of one run over the whole range (smx_common.h WtaRunUq; exact: S are integers)
+        WtaRunUq r;
+        for (int d = 0; d < a.size_d; ++d) r.step((float)mine[d], (uint32_t)d);
+        float* u = a.uq[v] + row + x0 + x;
+        u[0] = r.sec;
+        u[n] = r.rest;
+        u[2 * n] = r.last;
+    }
 }
 
 template <int VPL> int launch_paths(const SgmArgs& a, int nviews, int paths, hipStream_t st) {
@@ -275,7 +285,7 @@ size_t sgm_workspace_bytes(int w, int h, int size_d, int nviews) {
 }
 
 int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const float* cost_r, int w, int h, int size_d,
-                        int64_t* keys, float* agg, float* nbr, void* ws, hipStream_t st) {
+                        int64_t* keys, float* agg, float* nbr, float* uq, void* ws, hipStream_t st) {
     const int64_t n = (int64_t)w * h;
     SgmArgs a = {};
     int nviews = 0;
@@ -290,6 +300,7 @@ int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const fl
         a.keys[nviews] = keys + slot * n;
         a.agg[nviews] = agg ? agg + (int64_t)slot * size_d * n : nullptr;
         a.nbr[nviews] = nbr ? nbr + (int64_t)slot * 3 * n : nullptr;
+        a.uq[nviews] = uq ? uq + (int64_t)slot * 3 * n : nullptr;
         a.c8[nviews] = base + (size_t)nviews * 3 * plane;
         a.s16[nviews] = reinterpret_cast<uint16_t*>(base + (size_t)nviews * 3 * plane + plane);
         ++nviews;

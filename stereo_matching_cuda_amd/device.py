@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None):
+                 aggregation=None, sgm_params=None, uniqueness=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -51,7 +51,22 @@ class PairPipeline:
         which SGM reads through its clamp to 0 .. 255 -- and runs the one SGM call into self.keys (and self.agg = S,
         self.nbr).  The pipeline owns the volumes and the SGM workspace self.sgm_ws; max_ws_bytes counts both, and a
         slice sub-range or a size that does not fit raises ValueError.  No guided-filter workspace is allocated, self.mean
-        stays zero, and radius / eps of `params` are unused.  With None nothing is allocated or launched."""
+        stays zero, and radius / eps of `params` are unused.  With None nothing is allocated or launched.
+        uniqueness: None or a ratio > 0 -- the uniqueness (peak-ratio) test (not a stage of the reference; include/smx.h
+        smx_dev_uniqueness; OpenCV's uniquenessRatio u is ratio = u / (100 - u)): the aggregation keeps the winners'
+        second-best cost in self.uq (2, 3, h, w) through the _uq entries, and finish() runs the test on the LR-checked left map
+        into self.unique (vmin = dminl, new_val = dminl - 100) with s - c0 in self.margin.  Order: LR check -> uniqueness ->
+        speckle -> fill -> sub-pixel sub_filled -> weighted median: speckle removal takes self.unique where it took
+        self.occlusion, which stays the LR-check map, and self.filled is the fill of the last of these maps.  With None nothing
+        is allocated or launched.  A slice sub-range (a D-shard) raises ValueError."""
+        if uniqueness is not None:
+            uniqueness = float(uniqueness)
+            if not (0.0 < uniqueness < float("inf")):
+                raise ValueError(f"uniqueness must be None or a finite ratio > 0, not {uniqueness!r}")
+            # (the state belongs to the keys of ONE volume: after a key reduction across D-shards it would be tested against
+            # winners it does not belong to)
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
         if aggregation not in (None, "sgm"):
             raise ValueError(f"aggregation must be None or 'sgm', not {aggregation!r}")
         if cost not in (None, "census"):
@@ -119,6 +134,10 @@ class PairPipeline:
         self.nbr = torch.empty((2, 3, self.h, self.w), **f) if subpixel else None
         self.sub = torch.empty((2, self.h, self.w), **f) if subpixel else None
         self.sub_filled = torch.empty((self.h, self.w), **f) if subpixel else None
+        self.uniqueness = uniqueness
+        self.uq = torch.empty((2, 3, self.h, self.w), **f) if uniqueness else None
+        self.unique = torch.empty((self.h, self.w), **f) if uniqueness else None
+        self.margin = torch.empty((self.h, self.w), **f) if uniqueness else None
         self.speckle = _lib.default_speckle_params() if speckle is True else speckle
         self.despeckled = torch.empty((self.h, self.w), **f) if self.speckle else None
         self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
@@ -218,8 +237,11 @@ class PairPipeline:
                 P = C.byref(self.params)
                 _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
                 _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
-            _lib.check(L.smx_dev_sgm_wta_pair(C.byref(self.sgm_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys),
-                                              _dp(self.agg), _dp(self.nbr), _dp(self.sgm_ws), self.sgm_ws_bytes, st))
+            head = (C.byref(self.sgm_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys), _dp(self.agg), _dp(self.nbr))
+            if self.uniqueness:
+                _lib.check(L.smx_dev_sgm_wta_pair_uq(*head, _dp(self.uq), _dp(self.sgm_ws), self.sgm_ws_bytes, st))
+            else:
+                _lib.check(L.smx_dev_sgm_wta_pair(*head, _dp(self.sgm_ws), self.sgm_ws_bytes, st))
 
     def aggregate_pair_cost(self, gray_l, gray_r, cost_l, cost_r, s_begin=None, s_end=None, agg=None):
         """Both views per launch from materialised cost volumes of this rank's slices (smx_dev_aggregate_wta_pair_cost):
@@ -231,7 +253,9 @@ class PairPipeline:
         agg = self.agg if agg is None else agg
         args = (_dp(gray_l), _dp(gray_r), _dp(cost_l), _dp(cost_r), self.w, self.h, self.dminl, self.dminr, s_begin,
                 s_end, _dp(self.keys), _dp(self.mean), _dp(agg), _dp(self.ws), self.ws_bytes)
-        if self.subpixel:
+        if self.uniqueness:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_uq, *args, _dp(self.nbr), _dp(self.uq))
+        elif self.subpixel:
             self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_nbr, *args, _dp(self.nbr))
         else:
             self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_cost, *args)
@@ -254,7 +278,10 @@ class PairPipeline:
         self._guide = gray_l
         args = (self.w, self.h, self.dminl, self.dminr, self.s_begin, self.s_end, _dp(self.keys), _dp(self.mean),
                 _dp(self.agg), _dp(self.ws), self.ws_bytes)
-        if self.subpixel:
+        if self.uniqueness:
+            self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_uq, _dp(gray_l), _dp(gray_r), None, None, *args,
+                                 _dp(self.nbr), _dp(self.uq))
+        elif self.subpixel:
             self._aggregate_call(self.lib.smx_dev_aggregate_wta_pair_nbr, _dp(gray_l), _dp(gray_r), None, None, *args,
                                  _dp(self.nbr))
         else:
@@ -265,6 +292,8 @@ class PairPipeline:
             _lib.check(self.lib.smx_dev_init_keys(_dp(self.keys), 2 * self.n, self._stream()))
 
     def aggregate_view(self, view, guide, other, cost=None):
+        if self.uniqueness:
+            raise ValueError("the uniqueness state is kept by the pair entries: pass both cost volumes or neither")
         dmin = self.dminl if view == 0 else self.dminr
         if view == 0:
             self._guide = guide
@@ -291,6 +320,8 @@ class PairPipeline:
             _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                              self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                              _dp(self.occlusion), _dp(self.filled), st))
+        if self.uniqueness:
+            self.uniqueness_filter()
         if self.speckle:
             self.despeckle()
         if self.subpixel:
@@ -298,12 +329,26 @@ class PairPipeline:
         if self.wmf:
             self.refine()
 
-    def despeckle(self):
-        """self.despeckled = the LR-checked left map without its small connected components (smx_dev_speckle_filter), and
-        self.filled rewritten as the fill of that map."""
+    def uniqueness_filter(self):
+        """self.unique = the LR-checked left map without the pixels whose winner fails the uniqueness test
+        (smx_dev_uniqueness on the left view's keys and state, one launch), self.margin = s - c0, and -- unless speckle removal
+        follows, which does it -- self.filled rewritten as the fill of that map."""
         with self._on_device():
             L, st = self.lib, self._stream()
-            _lib.check(L.smx_dev_speckle_filter(C.byref(self.speckle), _dp(self.occlusion), _dp(self.despeckled), self.w,
+            _lib.check(L.smx_dev_uniqueness(self.uniqueness, _dp(self.keys[0]), _dp(self.uq[0]), _dp(self.occlusion),
+                                            _dp(self.unique), _dp(self.margin), self.w, self.h, float(self.dminl),
+                                            float(self.dminl - 100), st))
+            if not self.speckle:
+                self.filled.copy_(self.unique)
+                _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+
+    def despeckle(self):
+        """self.despeckled = the LR-checked (and, with uniqueness on, uniqueness-filtered) left map without its small connected
+        components (smx_dev_speckle_filter), and self.filled rewritten as the fill of that map."""
+        with self._on_device():
+            L, st = self.lib, self._stream()
+            src = self.unique if self.uniqueness else self.occlusion
+            _lib.check(L.smx_dev_speckle_filter(C.byref(self.speckle), _dp(src), _dp(self.despeckled), self.w,
                                                 self.h, float(self.dminl), float(self.dminl - 100), _dp(self.speckle_ws),
                                                 self.speckle_ws_bytes, st))
             self.filled.copy_(self.despeckled)
@@ -311,7 +356,7 @@ class PairPipeline:
 
     def _kept(self):
         """The map whose validity test tells which pixels the fill replaced."""
-        return self.despeckled if self.speckle else self.occlusion
+        return self.despeckled if self.speckle else self.unique if self.uniqueness else self.occlusion
 
     def subpixel_maps(self):
         """Sub-pixel maps of both views from the keys, the neighbour state and the finish's maps (smx_dev_subpixel_pair,
@@ -335,8 +380,9 @@ class PairPipeline:
                                                         self.size_d, self._stream()))
 
     def finish_per_call(self):
-        """The same through the per-stage entry points (the reference's call sequence, seven launches); with speckle
-        removal on, despeckle() behind them, as in finish().  The sub-pixel fit and the weighted median are not run."""
+        """The same through the per-stage entry points (the reference's call sequence, seven launches); with the uniqueness
+        test or speckle removal on, uniqueness_filter() / despeckle() behind them, as in finish().  The sub-pixel fit and the
+        weighted median are not run."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_dev_init_wta(_dp(self.best), _dp(self.dmap), 2 * self.n, st))
@@ -349,6 +395,8 @@ class PairPipeline:
                                                   self.dminl - 100, self.w, self.h, st))  # main.cu:149
             self.filled.copy_(self.occlusion)                                    # main.cu:153
             _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+        if self.uniqueness:
+            self.uniqueness_filter()
         if self.speckle:
             self.despeckle()
 
@@ -375,6 +423,8 @@ class PairPipeline:
             r["aggl"], r["aggr"] = c(self.agg[0]), c(self.agg[1])
         if self.wmf:
             r["refined"] = c(self.refined)
+        if self.uniqueness:
+            r["unique"], r["margin"] = c(self.unique), c(self.margin)
         if self.speckle:
             r["despeckled"] = c(self.despeckled)
         if self.subpixel:

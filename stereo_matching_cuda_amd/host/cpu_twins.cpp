@@ -6,6 +6,7 @@
 // correct twin (the reference's version writes pixel indices as labels and divides in double,
 // SURVEY.md section 4), so that check_errors() can hold it against the GPU result bit for bit.
 // Everything is plain f32 arithmetic in source order; build with -ffp-contract=off.
+#include <limits>
 #include <vector>
 
 #include "costVolume.cuh"
@@ -16,6 +17,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
+#include "uniqueness.cuh"
 #include "wmf.cuh"
 
 using std::vector;
@@ -301,6 +303,48 @@ void speckle_filterOnCPU(const float* disparity, float* out, const int w, const 
         }
         if (comp.size() <= (size_t)p.max_size)
             for (size_t i : comp) out[i] = new_val;
+    }
+}
+
+// ---- uniqueness.cuh (not in the reference) ---------------------------------------------------
+// The uniqueness test of include/smx.h by the definition: the winner first, then a second loop over the slices at least two
+// away from it.  (The kernels keep sec in one pass; this is the check of that streaming form.)
+void uniqueness_onCPU(const float* agg, const float* disparity, float* out, float* margin, const int w, const int h,
+                      const int size_d, float ratio, float vmin, float new_val) {
+    const size_t n = (size_t)w * h;
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    auto counts = [&](float v) {
+        if (!(std::fabs(v) <= 3.402823466e38f)) return false;
+        const float t = v >= 2147483648.0f ? 2147483648.0f : v < -2147483648.0f ? -2147483648.0f : (float)(int)v;
+        return t >= vmin;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        // smallest cost, the last slice among equal costs, a NaN never
+        int zs = -1;
+        float c0 = inf;
+        for (int z = 0; z < size_d; ++z) {
+            const float v = agg[(size_t)z * n + i];
+            if (v <= c0) { c0 = v; zs = z; }
+        }
+        out[i] = disparity[i];
+        if (zs < 0) {
+            if (margin) margin[i] = nan;
+            continue;
+        }
+        if (c0 == 0.0f) c0 = 0.0f;          // (the key folds -0 to +0)
+        float sec = inf;
+        for (int z = 0; z < size_d; ++z) {
+            const float v = agg[(size_t)z * n + i];
+            if ((z <= zs - 2 || z >= zs + 2) && v < sec) sec = v;
+        }
+        if (!(sec < inf)) {
+            if (margin) margin[i] = inf;
+            continue;
+        }
+        volatile float d = sec - c0;         // one rounded f32 difference, one rounded product
+        volatile float bound = ratio * std::fabs(c0);
+        if (margin) margin[i] = d;
+        if (ratio > 0.0f && d < bound && counts(disparity[i])) out[i] = new_val;
     }
 }
 

@@ -42,6 +42,14 @@
 //                     of directions (default 8).  With --host-compare the CPU twin (sgm_aggregateOnCPU) redoes both
 //                     views from the cost volumes and check_errors compares.  At most 256 labels.  Composes with --wmf,
 //                     --subpixel, --speckle, --pfm and --png16; not with --ngpu or --pipeline
+//   --uniqueness PCT  the uniqueness (peak-ratio) test between the LR check and speckle removal (smx_ctx_set_uniqueness; not
+//                     in the reference; implies --fused): 0 <= PCT < 100 is OpenCV's uniquenessRatio, i.e. the ratio
+//                     PCT / (100 - PCT); 0 is off.  A left pixel whose winner has a non-neighbouring disparity that costs less
+//                     than (1 + ratio) times as much is invalidated like an LR failure.  Writes occlu_mapl_unique.png beside
+//                     the 12 images; the later stages start from that map.  With --host-compare the CPU twin
+//                     (uniqueness_onCPU: brute force over the left aggregated volume) redoes it.  Composes with --cost
+//                     census, --aggregation sgm, --speckle, --subpixel, --wmf, --pfm and --png16; not with --ngpu or
+//                     --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -69,6 +77,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
+#include "uniqueness.cuh"
 #include "winner_take_all.cuh"
 #include "wmf.cuh"
 
@@ -100,6 +109,7 @@ struct Options {
     smx_sgm_params sgm_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
+    float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
     bool pipeline = false;
@@ -222,6 +232,17 @@ Options parse(int argc, char** argv) {
             }
             o.speckle_params.max_size = size; o.speckle_params.max_diff = diff;
         }
+        else if (a == "--uniqueness") {
+            std::string v;
+            value(v);
+            char* end = nullptr;
+            const float pct = std::strtof(v.c_str(), &end);
+            if (o.ok && (v.empty() || *end || !(pct >= 0.0f) || !(pct < 100.0f))) {
+                std::fprintf(stderr, "--uniqueness needs a percentage PCT with 0 <= PCT < 100, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            if (o.ok) o.uniqueness = pct / (100.0f - pct);
+        }
         else if (a == "--ngpu") { std::string v; value(v); o.ngpu = std::atoi(v.c_str()); }
         else if (a == "--pipeline") o.pipeline = true;
         else if (a == "--pairs") { std::string v; value(v); o.pairs = std::atoi(v.c_str()); }
@@ -291,6 +312,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--speckle cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
+    if (opt.uniqueness > 0.0f && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--uniqueness cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
     if (opt.ngpu < 0 || opt.ngpu > smx_device_count()) {
         std::fprintf(stderr, "--ngpu %d: this node shows %d HIP device(s)\n", opt.ngpu, smx_device_count());
         return 2;
@@ -312,7 +337,8 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm;
+    const bool uniq = opt.uniqueness > 0.0f;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm || uniq;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -350,6 +376,7 @@ int main(int argc, char** argv) {
     std::vector<float> occlusion, filled;
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
+    std::vector<float> unique;         // --uniqueness: the LR-checked left map without its ambiguous winners
     if (!fused) {
         // the reference's data flow: every stage is a host -> device -> host round trip
         for (int v = 0; v < 2; ++v) cost[v].resize((size_t)n * size_d);
@@ -393,6 +420,11 @@ int main(int argc, char** argv) {
         out.dmap_l = dmap[0].data(); out.dmap_r = dmap[1].data();
         if (!opt.sgm) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }     // (SGM has no mean images)
         out.occlusion = occlusion.data(); out.filled = filled.data();
+        std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness twin reads
+        if (uniq && host_compare) {
+            agg_l.resize((size_t)n * size_d);
+            out.agg_l = agg_l.data();
+        }
         // one persistent context for all pairs: nothing is allocated, created or destroyed per pair
         void* sctx = nullptr;
         smx_ctx* ctx = nullptr;
@@ -401,6 +433,7 @@ int main(int argc, char** argv) {
         if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
         if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
         if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
+        if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
         if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
@@ -442,6 +475,10 @@ int main(int argc, char** argv) {
             despeckled.resize(n);
             CHECK(smx_ctx_speckle_map(ctx, despeckled.data()));
         }
+        if (uniq) {
+            unique.resize(n);
+            CHECK(smx_ctx_uniqueness_map(ctx, unique.data(), nullptr));
+        }
         if (sh_create) CHECK(sh_destroy(sctx));
         else CHECK(smx_destroy(ctx));
         std::cout << "guided filter ok" << std::endl;
@@ -462,6 +499,15 @@ int main(int argc, char** argv) {
             std::vector<float> lr(dmap[0]);
             detect_occlusionOnCPU(lr.data(), dmap[1].data(), dmin[0] - 100, w, h);
             bool ok = check_errors(lr.data(), occlusion.data(), n);
+            if (uniq) {
+                std::vector<float> twin(n);
+                uniqueness_onCPU(agg_l.data(), lr.data(), twin.data(), nullptr, w, h, size_d, opt.uniqueness, (float)d_lo,
+                                 (float)(d_lo - 100));
+                const bool same = check_errors(twin.data(), unique.data(), n);
+                if (same) std::cout << "Uniqueness ok!" << std::endl;
+                ok = same && ok;
+                lr = twin;
+            }
             if (opt.speckle) {
                 std::vector<float> twin(n);
                 speckle_filterOnCPU(lr.data(), twin.data(), w, h, (float)d_lo, (float)(d_lo - 100), opt.speckle_params);
@@ -478,7 +524,8 @@ int main(int argc, char** argv) {
     if (!opt.wmf.empty()) {
         std::cout << "weighted median ..." << std::endl;
         refined.resize(n);
-        float* kept = opt.speckle ? despeckled.data() : occlusion.data();     // whose test says what the fill replaced
+        // whose test says what the fill replaced
+        float* kept = opt.speckle ? despeckled.data() : uniq ? unique.data() : occlusion.data();
         weighted_median(gray[0], filled.data(), opt.wmf == "occluded" ? kept : nullptr, refined.data(), w, h,
                         d_lo, size_d, host_compare);
     }
@@ -505,6 +552,10 @@ int main(int argc, char** argv) {
     if (!despeckled.empty()) {
         const std::vector<unsigned char> img = normalise_like_reference(despeckled.data(), (size_t)n);
         if (!smx_png_write((outdir + "/occlu_mapl_despeckled.png").c_str(), w, h, 1, img.data())) ++write_failures;
+    }
+    if (!unique.empty()) {
+        const std::vector<unsigned char> img = normalise_like_reference(unique.data(), (size_t)n);
+        if (!smx_png_write((outdir + "/occlu_mapl_unique.png").c_str(), w, h, 1, img.data())) ++write_failures;
     }
     if (!refined.empty()) {
         const std::vector<unsigned char> img = normalise_like_reference(refined.data(), (size_t)n);

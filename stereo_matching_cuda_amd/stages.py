@@ -160,6 +160,26 @@ def speckle_filter(disparity, vmin, new_val, params=None):
     return out
 
 
+def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
+    """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
+    reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
+    of the view's uniqueness state); a pixel whose map value counts against vmin and whose winner has
+    sec - c0 < ratio * |c0| becomes new_val, every other pixel is copied bit for bit.  Returns a new (h, w) float32 array,
+    or (map, margin) with want_margin."""
+    d = _c(disparity, np.float32)
+    if d.ndim != 2:
+        raise ValueError("uniqueness_filter expects an (h, w) float32 map")
+    k, s = _c(keys, np.int64), _c(sec, np.float32)
+    if k.shape != d.shape or s.shape != d.shape:
+        raise ValueError("keys and sec must have the map's shape")
+    h, w = d.shape
+    out = np.empty((h, w), np.float32)
+    margin = np.empty((h, w), np.float32) if want_margin else None
+    _lib.check(_lib.lib().smx_uniqueness_filter(float(ratio), _ptr(k), _ptr(s), _ptr(d), _ptr(out), _ptr(margin), w, h,
+                                                float(vmin), float(new_val)))
+    return (out, margin) if want_margin else out
+
+
 def wmf_weights(params=None):
     """(spatial[0 .. 2 r^2], range[0 .. 255]) uint16 weight tables of the weighted median (smx_wmf_weights)."""
     p = params if params is not None else _lib.default_wmf_params()
