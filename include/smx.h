@@ -587,6 +587,72 @@ int smx_uniqueness_filter(float ratio, const int64_t* keys, const float* uq, con
 int smx_ctx_set_uniqueness(smx_ctx* ctx, float ratio);
 int smx_ctx_uniqueness_map(smx_ctx* ctx, float* map, float* margin);
 
+/* ------------------------------------------------------------------------------------
+ * Colour (RGB) guidance for the guided-filter aggregation (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The guided filter of He et al. with a colour guide, as in Hosni / Rhemann et al.'s cost-volume filtering: the 3 x 3
+ * covariance of the guide per window instead of the gray variance, so that an edge between two colours of equal luminance
+ * stays an edge.  tests/cgf_ref.py is this definition in numpy; the result equals it bit for bit.
+ *   inputs:    per view the guide, u8 [h][w][channels], channels 3 or 4 with R, G, B the first three bytes, and the cost
+ *              volume, materialised: f32 [z][y][x], slice s of [s_begin, s_end) at d_cost[(s - s_begin) * w*h].
+ *   integral:  f32, row prefix left to right, then column prefix top to bottom, each a sequential chain acc = v + acc from
+ *              -0.0f (integral.cu:78-131, as everywhere in this library).
+ *   box mean:  the clamped window of radius `radius`: ((S11 - S10) - S01) + S00 with the taps outside the image left out,
+ *              divided by (float)area (computeMeanOnGPU guidedFilter.cu:305-318).
+ *   guidance, once per view: I_c = (float)u8 for c in r, g, b; the six products I_c I_c' (exact in f32); the nine box means
+ *              mu_c, m_cc'; v_cc' = m_cc' - mu_c * mu_c' (the product rounded before the difference).  Then in double, every
+ *              product and every sum rounded on its own:
+ *                a = (double)v_rr + eps, b = v_rg, c = v_rb, d = v_gg + eps, e = v_gb, f = v_bb + eps
+ *                A = d*f - e*e, B = c*e - b*f, C = b*e - c*d, D = a*f - c*c, E = b*c - a*e, F = a*d - b*b
+ *                det = (a*A + b*B) + c*C
+ *              and six f32 planes (float)(X / det), X = A .. F: the rows (A B C; B D E; C E F) of (Sigma + eps I)^-1.  A zero
+ *              or negative det gets no special treatment: what IEEE gives propagates, and a NaN never wins.
+ *   per slice p: box means mu_p and m_cp of p and of I_c * p (f32 product); cov_c = m_cp - mu_c * mu_p;
+ *                a_r = (A cov_r + B cov_g) + C cov_b, a_g = (B cov_r + D cov_g) + E cov_b, a_b = (C cov_r + E cov_g) + F cov_b;
+ *                b = mu_p - ((a_r mu_r + a_g mu_g) + a_b mu_b); box means of a_r, a_g, a_b, b give abar_c, bbar;
+ *                q = ((abar_r I_r + abar_g I_g) + abar_b I_b) + bbar.  All f32, left to right.
+ *   winner:    the packed keys and the tie rule of smx_dev_aggregate_wta (the last slice of equal costs wins).
+ *   parameters: radius (any >= 0) and eps of smx_params; nothing else of it is read.
+ *
+ * smx_dev_cgf_wta_pair: both views in every launch.  Either rgb / cost pair may be NULL (not both; a view's guide and cost
+ * come together) for the one-view form, whose outputs hold that one view.
+ *   d_keys:  IN/OUT like smx_dev_aggregate_wta_pair_cost: n keys per view (left first), accumulated across calls and across
+ *            D-shards by the int64 min; smx_set_keys_fresh does not apply: the keys are always loaded.
+ *   d_agg:   optional, (s_end - s_begin) * n floats per view: q.
+ *   d_nbr, d_uq: optional, 3n floats per view each: the neighbour state and the second-best state of the _nbr / _uq entries
+ *            above, with their meaning and their rule (ascending, contiguous ranges on one set of keys).
+ * The slices go in chunks that fit the workspace (smx_set_max_slices_per_launch bounds the chunk as well); the chunking does
+ * not change a bit.  Per chunk six kernel launches, four more per call for the guidance; no allocation, no synchronisation
+ * (graph-capturable).  smx_cgf_workspace_bytes(w, h, nslices, nviews) holds `nslices` slices in flight: per view 9 guidance
+ * planes and max(9, 8 * nslices) working planes of w*h floats, plus 255 bytes (0 for invalid sizes: w, h >= 1, h <= 65535,
+ * w*h < 2^31, nslices >= 1, nviews 1 or 2).  Fewer bytes than for one slice is SMX_E_WS before anything is launched.  The
+ * memory contract is that of the aggregation entries above smx_agg_workspace_bytes: nothing is written outside the workspace
+ * and the stated extents, the workspace may hold anything and needs no alignment, the inputs are not modified.
+ * smx_colour_guided_filter: host pointers, one view, synchronous; filter_cost / disp_map IN/OUT and agg as for
+ * smx_compute_guided_filter (there is no mean image). */
+size_t smx_cgf_workspace_bytes(int w, int h, int nslices, int nviews);
+int smx_dev_cgf_wta_pair(const smx_params* p, const uint8_t* d_rgb_l, const uint8_t* d_rgb_r, int channels,
+                         const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
+                         float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_colour_guided_filter(const smx_params* p, const uint8_t* rgb, int channels, const float* cost, float* filter_cost,
+                             float* disp_map, float* agg, int w, int h, int size_d, int dmin);
+
+#define SMX_GUIDE_GRAY 0   /* the reference's gray guide: the default */
+#define SMX_GUIDE_RGB 1
+/* Guidance of this context's guided filter.  smx_ctx_stereo_pair_rgb takes the pair as colour images (u8 [h][w][channels],
+ * channels 3 or 4), makes the gray images on the device (smx_dev_rgb_to_grayscale) for the matching cost -- the reference's,
+ * or census per smx_ctx_set_cost -- and then runs the pair as smx_ctx_stereo_pair does: with SMX_GUIDE_GRAY it equals
+ * smx_ctx_stereo_pair on the converted images; with SMX_GUIDE_RGB both cost volumes go chunk by chunk through
+ * smx_dev_cgf_wta_pair (with the neighbour and second-best states where sub-pixel or uniqueness are on), then the usual finish,
+ * uniqueness, speckle removal and sub-pixel fit.  cost_* / agg_* of smx_pair_out receive the volumes.  The colour images, the
+ * workspace and the chunk buffers are allocated on first use.  While SMX_GUIDE_RGB is on: mean_l / mean_r are not produced
+ * (SMX_E_ARG if requested); SMX_AGG_SGM is SMX_E_ARG at the pair call; smx_ctx_stereo_pair, which has no colour images, and
+ * smx_ctx_stereo_pair_async return SMX_E_ARG. */
+int smx_ctx_set_guidance(smx_ctx* ctx, int mode);
+int smx_ctx_stereo_pair_rgb(smx_ctx* ctx, const uint8_t* rgb_l, const uint8_t* rgb_r, int channels, int dminl, int dminr,
+                            const smx_pair_out* out);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -164,10 +164,18 @@ SIGNATURES = {
     "smx_uniqueness_filter": (_i, [_f, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f]),
     "smx_ctx_set_uniqueness": (_i, [_vp, _f]),
     "smx_ctx_uniqueness_map": (_i, [_vp, _vp, _vp]),
+    "smx_cgf_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_cgf_wta_pair": (_i, [_PP, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_colour_guided_filter": (_i, [_PP, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_guidance": (_i, [_vp, _i]),
+    "smx_ctx_stereo_pair_rgb": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(PairOut)]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
 AGG_MODES = {"guided": 0, "sgm": 1}
+
+# smx.h SMX_GUIDE_*: the guides of the guided filter by name
+GUIDE_MODES = {"gray": 0, "rgb": 1}
 
 # smx.h SMX_COST_*: the matching costs by name
 COST_MODES = {"reference": 0, "census": 1}

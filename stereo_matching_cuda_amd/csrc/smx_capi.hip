@@ -643,6 +643,29 @@ int smx_dev_sgm_wta_pair_uq(const smx_sgm_params* p, const float* d_cost_l, cons
                         stream);
 }
 
+// ---- colour-guided filter aggregation (not in the reference; smx_cgf.hip) -----------------------------------------
+static bool cgf_shape_ok(int w, int h) { return w >= 1 && h >= 1 && h <= 65535 && (long long)w * h < (1ll << 31); }
+
+size_t smx_cgf_workspace_bytes(int w, int h, int nslices, int nviews) {
+    return cgf_shape_ok(w, h) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cgf_workspace_bytes(w, h, nslices, nviews) : 0;
+}
+
+int smx_dev_cgf_wta_pair(const smx_params* p, const uint8_t* d_rgb_l, const uint8_t* d_rgb_r, int channels,
+                         const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
+                         float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    SMX_ARG(p && p->radius >= 0 && (channels == 3 || channels == 4));
+    if (!cgf_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cgf_wta_pair: needs w >= 1, 1 <= h <= 65535 and w*h < 2^31");
+    SMX_ARG(s_begin >= 0 && s_end > s_begin && d_keys);
+    SMX_ARG((d_cost_l || d_cost_r) && !d_rgb_l == !d_cost_l && !d_rgb_r == !d_cost_r);
+    const int nviews = d_cost_l && d_cost_r ? 2 : 1;
+    const int chunk = d_ws ? cgf_chunk(w, h, nviews, ws_bytes, s_end - s_begin, g_max_chunk) : 0;
+    if (chunk < 1)
+        return fail(SMX_E_WS, "smx_dev_cgf_wta_pair: workspace of %zu bytes, %zu needed for one slice in flight",
+                    d_ws ? ws_bytes : (size_t)0, cgf_workspace_bytes(w, h, 1, nviews));
+    return launch_cgf_wta_pair(p, d_rgb_l, d_rgb_r, channels, d_cost_l, d_cost_r, w, h, s_begin, s_end, d_keys, d_agg, d_nbr,
+                               d_uq, d_ws, chunk, (hipStream_t)stream);
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);

@@ -41,6 +41,12 @@ struct smx_ctx {
     float uniq = 0.0f;          // the ratio; 0 = off
     bool uq_valid = false;      // the maps belong to the last synchronous pair
     DevBuf uq, uq_map, uq_margin;
+    // colour guidance (smx_ctx_set_guidance): the two colour images [2][h][w][4], the colour-guided filter's workspace for both
+    // views and, without whole volumes, one chunk of both views' cost slices [2][cgf_chunk][h][w]
+    int guide_mode = SMX_GUIDE_GRAY;
+    int cgf_chunk = 0;
+    size_t cgf_ws_bytes = 0;
+    DevBuf rgb, cgf_ws, cgf_cost;
     // pipelined entry: two slots of device inputs / results and pinned staging, created on first use.  Staging of a slot:
     // [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l mean_r | status word] coming down.
     struct Slot {
@@ -66,8 +72,8 @@ struct smx_ctx {
 // What one pair asks of the context beyond the eight result planes, decided once per pair by the entry that was called
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them); its device images with the disparity of
 // slice 0 of either view; where its results go on the device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq; };
-struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf; };
+struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
 // Every buffer `need` asks for, each under its own guard: after a failed allocation the next call simply retries.
@@ -85,6 +91,16 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     }
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
     if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
+    if (need.cgf) {
+        // the most slices in flight whose workspace (and chunk of cost slices, without whole volumes) stay within ~2 GiB
+        const size_t cap = (size_t)2 << 30;
+        int k = c->size_d;
+        while (k > 1 && cgf_workspace_bytes(c->w, c->h, k, 2) + (need.cost ? 0 : 2 * (size_t)k * fb) > cap) k = (k + 1) / 2;
+        c->cgf_chunk = k;
+        c->cgf_ws_bytes = cgf_workspace_bytes(c->w, c->h, k, 2);
+        SMX_HIP(c->cgf_ws.ensure(c->cgf_ws_bytes));
+        if (!need.cost) SMX_HIP(c->cgf_cost.ensure(2 * (size_t)k * fb));
+    }
     return SMX_OK;
 }
 
@@ -116,6 +132,39 @@ static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
         for (int v = 0; v < 2; ++v)
             if (call.agg[v]) part.agg[v] = call.agg[v] + (size_t)(s0 - call.s_begin) * n;
         if ((rc = run_aggregation(part, c->agg_path, s0 != call.s_begin))) return rc;
+    }
+    return SMX_OK;
+}
+
+// Colour-guided mode of ctx_enqueue: cost chunk (census or the reference's; the whole volumes where the context holds them) ->
+// smx_dev_cgf_wta_pair from that chunk, over ascending contiguous chunks, accumulating into the keys and the states.  With the
+// aggregated volumes wanted, a chunk goes view by view: the pair form lays its two views a chunk apart, the context a volume.
+static int ctx_cgf_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
+    const size_t n = c->n;
+    const int w = c->w, h = c->h, chunk = c->cgf_chunk;
+    int rc;
+    for (int s0 = 0; s0 < c->size_d; s0 += chunk) {
+        const int s1 = s0 + chunk < c->size_d ? s0 + chunk : c->size_d;
+        float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->cgf_cost.as<float>();
+        float* cr = need.cost ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
+        if (need.census) {
+            if ((rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), cl, cr, w, h, in.dminl, in.dminr, s0, s1, call.st)))
+                return rc;
+        } else if (!need.cost) {        // (whole reference volumes were built up front)
+            if ((rc = smx_dev_cost_volume(&c->p, in.left, in.right, cl, w, w, h, in.dminl, s0, s1, call.st))) return rc;
+            if ((rc = smx_dev_cost_volume(&c->p, in.right, in.left, cr, w, w, h, in.dminr, s0, s1, call.st))) return rc;
+        }
+        if (!need.agg) {
+            rc = smx_dev_cgf_wta_pair(&c->p, in.rgb_l, in.rgb_r, in.channels, cl, cr, w, h, s0, s1, call.keys[0], nullptr, call.nbr[0],
+                                      call.uq[0], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
+        } else {
+            rc = smx_dev_cgf_wta_pair(&c->p, in.rgb_l, nullptr, in.channels, cl, nullptr, w, h, s0, s1, call.keys[0],
+                                      call.agg[0] + (size_t)s0 * n, call.nbr[0], call.uq[0], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
+            if (!rc)
+                rc = smx_dev_cgf_wta_pair(&c->p, nullptr, in.rgb_r, in.channels, nullptr, cr, w, h, s0, s1, call.keys[1],
+                                          call.agg[1] + (size_t)s0 * n, call.nbr[1], call.uq[1], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
+        }
+        if (rc) return rc;
     }
     return SMX_OK;
 }
@@ -154,7 +203,8 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->sgm_ws.p,
                                                           sgm_bytes, st)
                                 : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p, sgm_bytes, st);
-    } else if (need.census) rc = ctx_census_aggregate(c, call, need.cost);
+    } else if (need.cgf) rc = ctx_cgf_aggregate(c, in, call, need);
+    else if (need.census) rc = ctx_census_aggregate(c, call, need.cost);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
@@ -247,29 +297,52 @@ int smx_destroy(smx_ctx* c) {
     return SMX_OK;
 }
 
-int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r, int dminl, int dminr,
-                        const smx_pair_out* out) {
-    SMX_ARG(c && gray_l && gray_r && out);
+}  // extern "C"
+
+// The synchronous pair entry on gray images (channels == 0: img_l / img_r are the gray images) or on colour images, whose
+// gray images for the cost are made on the device.
+static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uint8_t* img_r, int channels, int dminl, int dminr,
+                    const smx_pair_out* out) {
     const size_t n = c->n;
     int rc;
-    if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair"))) return rc;
-    if (c->submitted != c->waited) return fail(SMX_E_ARG, "smx_ctx_stereo_pair: pipelined pairs are still in flight (smx_ctx_wait)");
+    if ((rc = ctx_check_device(c, who))) return rc;
+    if (c->submitted != c->waited) return fail(SMX_E_ARG, "%s: pipelined pairs are still in flight (smx_ctx_wait)", who);
     hipStream_t st = c->st;
     const bool sgm = c->agg_mode == SMX_AGG_SGM;
+    const bool cgf = c->guide_mode == SMX_GUIDE_RGB;
     if (sgm && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair: semi-global matching (smx_ctx_set_aggregation) produces no mean images");
+        return fail(SMX_E_ARG, "%s: semi-global matching (smx_ctx_set_aggregation) produces no mean images", who);
+    if (cgf && !channels)
+        return fail(SMX_E_ARG, "%s: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb", who);
+    if (cgf && sgm) return fail(SMX_E_ARG, "%s: colour guidance belongs to the guided filter, not to semi-global matching", who);
+    if (cgf && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "%s: the colour-guided filter (smx_ctx_set_guidance) produces no mean images", who);
+    if (cgf && smx_cgf_workspace_bytes(c->w, c->h, 1, 2) == 0)
+        return fail(SMX_E_ARG, "%s: the colour-guided filter needs h <= 65535 and w*h < 2^31", who);
     const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle, c->uniq > 0.0f};
+                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle, c->uniq > 0.0f, cgf};
     if ((rc = ctx_reserve(c, need))) return rc;
+    if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
     c->sub_valid = c->spk_valid = c->uq_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
+    uint8_t* rgbL = channels ? c->rgb.as<uint8_t>() : nullptr;
+    uint8_t* rgbR = channels ? rgbL + n * (size_t)channels : nullptr;
     stage_mark(ST_BEGIN, st);
-    SMX_HIP(hipMemcpyAsync(dL, gray_l, n, hipMemcpyHostToDevice, st));
-    SMX_HIP(hipMemcpyAsync(dR, gray_r, n, hipMemcpyHostToDevice, st));
+    if (channels) {
+        SMX_HIP(hipMemcpyAsync(rgbL, img_l, n * (size_t)channels, hipMemcpyHostToDevice, st));
+        SMX_HIP(hipMemcpyAsync(rgbR, img_r, n * (size_t)channels, hipMemcpyHostToDevice, st));
+        if ((rc = smx_dev_rgb_to_grayscale(&c->p, rgbL, (int64_t)n, channels, dL, st))) return rc;
+        if ((rc = smx_dev_rgb_to_grayscale(&c->p, rgbR, (int64_t)n, channels, dR, st))) return rc;
+    } else {
+        SMX_HIP(hipMemcpyAsync(dL, img_l, n, hipMemcpyHostToDevice, st));
+        SMX_HIP(hipMemcpyAsync(dR, img_r, n, hipMemcpyHostToDevice, st));
+    }
     stage_mark(ST_UPLOAD, st);
     float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
     uint8_t* mean = c->mean.as<uint8_t>();
-    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr}, need, {best, map, mean, c->occ.as<float>(), c->fil.as<float>()}))) return rc;
+    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need,
+                          {best, map, mean, c->occ.as<float>(), c->fil.as<float>()})))
+        return rc;
     const smx_pair_out dev = {best, best + n, map, map + n, mean, mean + n, c->occ.as<float>(), c->fil.as<float>(),
                               c->costL.as<float>(), c->costR.as<float>(), agg, need.agg ? agg + c->size_d * n : nullptr};
     const auto to = pair_planes(*out, c->size_d), from = pair_planes(dev, c->size_d);
@@ -277,10 +350,32 @@ int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r
         if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    if (!need.sgm && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM kernels wait for nothing)
+    if (!need.sgm && !need.cgf && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM and colour-guided kernels wait for nothing)
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
+    return SMX_OK;
+}
+
+extern "C" {
+
+int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r, int dminl, int dminr,
+                        const smx_pair_out* out) {
+    SMX_ARG(c && gray_l && gray_r && out);
+    return ctx_pair(c, "smx_ctx_stereo_pair", gray_l, gray_r, 0, dminl, dminr, out);
+}
+
+int smx_ctx_stereo_pair_rgb(smx_ctx* c, const uint8_t* rgb_l, const uint8_t* rgb_r, int channels, int dminl, int dminr,
+                            const smx_pair_out* out) {
+    SMX_ARG(c && rgb_l && rgb_r && out && (channels == 3 || channels == 4));
+    return ctx_pair(c, "smx_ctx_stereo_pair_rgb", rgb_l, rgb_r, channels, dminl, dminr, out);
+}
+
+int smx_ctx_set_guidance(smx_ctx* c, int mode) {
+    SMX_ARG(c);
+    if (mode != SMX_GUIDE_GRAY && mode != SMX_GUIDE_RGB)
+        return fail(SMX_E_ARG, "smx_ctx_set_guidance: mode must be SMX_GUIDE_GRAY or SMX_GUIDE_RGB");
+    c->guide_mode = mode;
     return SMX_OK;
 }
 
@@ -401,6 +496,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
+    if (c->guide_mode != SMX_GUIDE_GRAY)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)

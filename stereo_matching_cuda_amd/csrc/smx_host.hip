@@ -206,6 +206,37 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
     return SMX_OK;
 }
 
+int smx_colour_guided_filter(const smx_params* p, const uint8_t* rgb, int channels, const float* cost, float* filter_cost,
+                             float* disp_map, float* agg, int w, int h, int size_d, int dmin) {
+    SMX_ARG(p && rgb && cost && filter_cost && disp_map && size_d >= 1 && w >= 1 && h >= 1);
+    SMX_ARG(p->radius >= 0 && (channels == 3 || channels == 4));
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), vb = fb * size_d;
+    // every slice in flight, but at most ~2 GiB of them
+    const size_t one = smx_cgf_workspace_bytes(w, h, 1, 1), all = smx_cgf_workspace_bytes(w, h, size_d, 1), cap = (size_t)2 << 30;
+    SMX_ARG(one != 0);
+    const size_t ws_bytes = all <= cap ? all : one > cap ? one : cap;
+    DevBuf dI, dC, dBest, dMap, dKeys, dAgg, ws;
+    SMX_HIP(dI.upload(rgb, n * channels));
+    SMX_HIP(dC.upload(cost, vb));
+    SMX_HIP(dBest.upload(filter_cost, fb));
+    SMX_HIP(dMap.upload(disp_map, fb));
+    SMX_HIP(dKeys.ensure(n * sizeof(int64_t)));
+    if (agg) SMX_HIP(dAgg.ensure(vb));
+    SMX_HIP(ws.ensure(ws_bytes));
+    int rc;
+    if ((rc = smx_dev_init_keys(dKeys.as<int64_t>(), (int64_t)n, nullptr))) return rc;
+    if ((rc = smx_dev_cgf_wta_pair(p, dI.as<uint8_t>(), nullptr, channels, dC.as<float>(), nullptr, w, h, 0, size_d,
+                                   dKeys.as<int64_t>(), agg ? dAgg.as<float>() : nullptr, nullptr, nullptr, ws.p, ws_bytes,
+                                   nullptr)))
+        return rc;
+    if ((rc = smx_dev_apply_keys(dKeys.as<int64_t>(), (int64_t)n, dmin, dBest.as<float>(), dMap.as<float>(), nullptr))) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dBest.download(filter_cost, fb));
+    SMX_HIP(dMap.download(disp_map, fb));
+    if (agg) SMX_HIP(dAgg.download(agg, vb));
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -54,4 +54,11 @@ int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const fl
 // smx_uniq.hip: the uniqueness test on a disparity map (smx_dev_uniqueness)
 int launch_uniqueness(float ratio, const int64_t* keys, const float* uq, const float* disp, float* out, float* margin, int64_t n,
                       float vmin, float new_val, hipStream_t st);
+// smx_cgf.hip: the colour-guided filter aggregation (smx_dev_cgf_wta_pair); ws: cgf_workspace_bytes bytes for the slices in
+// flight, chunk: cgf_chunk of that workspace (>= 1)
+size_t cgf_workspace_bytes(int w, int h, int nslices, int nviews);
+int cgf_chunk(int w, int h, int nviews, size_t ws_bytes, int count, int max_chunk);
+int launch_cgf_wta_pair(const smx_params* p, const uint8_t* rgb_l, const uint8_t* rgb_r, int ch, const float* cost_l,
+                        const float* cost_r, int w, int h, int s_begin, int s_end, int64_t* keys, float* agg, float* nbr,
+                        float* uq, void* ws, int chunk, hipStream_t st);
 }  // namespace smx

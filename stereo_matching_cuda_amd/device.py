@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, uniqueness=None):
+                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -58,7 +58,18 @@ class PairPipeline:
         into self.unique (vmin = dminl, new_val = dminl - 100) with s - c0 in self.margin.  Order: LR check -> uniqueness ->
         speckle -> fill -> sub-pixel sub_filled -> weighted median: speckle removal takes self.unique where it took
         self.occlusion, which stays the LR-check map, and self.filled is the fill of the last of these maps.  With None nothing
-        is allocated or launched.  A slice sub-range (a D-shard) raises ValueError."""
+        is allocated or launched.  A slice sub-range (a D-shard) raises ValueError.
+        guidance: None or "rgb" -- None is the reference's gray guide.  "rgb" is the colour-guided filter (not a stage of the
+        reference; include/smx.h smx_dev_cgf_wta_pair): aggregate() / run() take the colour images rgb_l=, rgb_r= ((h, w, 3 or
+        4) uint8 on the device) beside the gray ones, which still give the matching cost, and run cost chunk (the
+        reference's cost into self.cgf_cost, or census) -> smx_dev_cgf_wta_pair over chunks of `slices_in_flight` slices.
+        The pipeline owns the chunk's cost slices and the workspace self.cgf_ws (max_ws_bytes counts both); no workspace of
+        the gray path is allocated and self.mean stays zero.  Not with aggregation="sgm".  With None nothing is allocated or
+        launched."""
+        if guidance not in (None, "rgb"):
+            raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
+        if guidance and aggregation:
+            raise ValueError("colour guidance belongs to the guided filter: not with aggregation='sgm'")
         if uniqueness is not None:
             uniqueness = float(uniqueness)
             if not (0.0 < uniqueness < float("inf")):
@@ -107,6 +118,14 @@ class PairPipeline:
         # (smx_set_agg_path(1)) needs the parameter-agnostic bound
         need = (lambda n: self.lib.smx_agg_workspace_bytes(self.w, self.h, n)) if multi_kernel else \
                (lambda n: self.lib.smx_agg_workspace_bytes_for(C.byref(self.params), self.w, self.h, n))
+        self.guidance = guidance
+        self.cgf_ws = self.cgf_cost = None
+        self.cgf_ws_bytes = 0
+        if guidance:
+            if self.lib.smx_cgf_workspace_bytes(self.w, self.h, 1, 2) == 0:
+                raise ValueError(f"the colour-guided filter does not take {self.w} x {self.h} (h <= 65535, w*h < 2^31)")
+            # both views in one workspace, and the reference cost goes through a chunk buffer like the census cost
+            need = lambda n: (self.lib.smx_cgf_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
         self.cost = cost
         self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
         chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
@@ -114,7 +133,7 @@ class PairPipeline:
             sif = (sif + 1) // 2
         self.slices_in_flight = sif
         # pair calls (both views per launch) need twice the single-view workspace (SGM does not use it)
-        self.ws_bytes = 0 if aggregation else 2 * int(need(sif))
+        self.ws_bytes = 0 if aggregation or guidance else 2 * int(need(sif))
         dev = self.device
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         # keys[0] = left view, keys[1] = right view: one buffer so the shard merge is ONE all-reduce
@@ -122,7 +141,7 @@ class PairPipeline:
         f = dict(dtype=torch.float32, device=dev)
         self.best = torch.empty((2, self.h, self.w), **f)
         self.dmap = torch.empty((2, self.h, self.w), **f)
-        self.mean = (torch.zeros if aggregation else torch.empty)((2, self.h, self.w), dtype=torch.uint8, device=dev)
+        self.mean = (torch.zeros if aggregation or guidance else torch.empty)((2, self.h, self.w), dtype=torch.uint8, device=dev)
         self.occlusion = torch.empty((self.h, self.w), **f)
         self.filled = torch.empty((self.h, self.w), **f)
         self.agg = (torch.empty((2, local, self.h, self.w), **f) if want_agg else None)
@@ -147,9 +166,13 @@ class PairPipeline:
         if aggregation:
             self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
+        if guidance:
+            self.cgf_ws_bytes = int(self.lib.smx_cgf_workspace_bytes(self.w, self.h, sif, 2))
+            self.cgf_ws = torch.empty(self.cgf_ws_bytes, dtype=torch.uint8, device=dev)
+            self.cgf_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
         self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
-            if cost and want_agg and sif < local and not aggregation else None
+            if (cost or guidance) and want_agg and sif < local and not aggregation else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -158,9 +181,16 @@ class PairPipeline:
         return torch.cuda.device(self.device)
 
     # -- stages ------------------------------------------------------------------------------
-    def aggregate(self, gray_l, gray_r, cost_l=None, cost_r=None):
+    def aggregate(self, gray_l, gray_r, cost_l=None, cost_r=None, rgb_l=None, rgb_r=None):
         """Cost build (fused unless cost_* given) + guided-filter aggregation + running WTA of this
-        rank's slices, both views.  Leaves packed keys in self.keys."""
+        rank's slices, both views.  Leaves packed keys in self.keys.  rgb_l / rgb_r: the colour guides of
+        guidance="rgb" (required then, refused otherwise)."""
+        if self.guidance:
+            if rgb_l is None or rgb_r is None:
+                raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
+            return self._aggregate_cgf(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
+        if rgb_l is not None or rgb_r is not None:
+            raise ValueError("rgb_l / rgb_r are the guides of guidance='rgb': this pipeline has the gray guide")
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
         if self.cost and (cost_l is not None or cost_r is not None):
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
@@ -216,6 +246,53 @@ class PairPipeline:
                 flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, self.h, self.w)
                 self.agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
             L.smx_set_keys_fresh(0)
+
+    def _aggregate_cgf(self, gray_l, gray_r, rgb_l, rgb_r, cost_l=None, cost_r=None):
+        """The colour-guided flow: fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views
+        (the caller's volumes, census, or the reference's cost) and smx_dev_cgf_wta_pair from them, which accumulates into
+        the keys (and the neighbour / second-best states)."""
+        if (cost_l is None) != (cost_r is None):
+            raise ValueError("pass both cost volumes or neither")
+        if self.cost and cost_l is not None:
+            raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
+        for t in (rgb_l, rgb_r):
+            if t.dtype != torch.uint8 or t.dim() != 3 or tuple(t.shape[:2]) != (self.h, self.w) or t.shape[2] not in (3, 4) \
+                    or not t.is_contiguous():
+                raise ValueError(f"a colour guide is a contiguous ({self.h}, {self.w}, 3 or 4) uint8 tensor")
+        if rgb_l.shape[2] != rgb_r.shape[2]:
+            raise ValueError("both colour guides need the same number of channels")
+        self._guide = gray_l
+        L, w, h, ch = self.lib, self.w, self.h, int(rgb_l.shape[2])
+        self.init_keys()
+        if self.cost:
+            P = C.byref(self.census_params)
+            with self._on_device():
+                for v, g in enumerate((gray_l, gray_r)):
+                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, self._stream()))
+        sif = self.slices_in_flight
+        for c0 in range(self.s_begin, self.s_end, sif):
+            c1 = min(self.s_end, c0 + sif)
+            with self._on_device():
+                st = self._stream()
+                if cost_l is not None:
+                    cl, cr = cost_l[c0 - self.s_begin:], cost_r[c0 - self.s_begin:]
+                elif self.cost:
+                    cl, cr = self.census_cost[0], self.census_cost[1]
+                    _lib.check(L.smx_dev_census_cost_pair(C.byref(self.census_params), _dp(self.codes), _dp(cl), _dp(cr), w, h,
+                                                          self.dminl, self.dminr, c0, c1, st))
+                else:
+                    cl, cr = self.cgf_cost[0], self.cgf_cost[1]
+                    P = C.byref(self.params)
+                    _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, c0, c1, st))
+                    _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, c0, c1, st))
+            whole = self.agg is None or self._agg_chunk is None
+            self._aggregate_call(L.smx_dev_cgf_wta_pair, _dp(rgb_l), _dp(rgb_r), ch, _dp(cl), _dp(cr), w, h, c0, c1,
+                                 _dp(self.keys), _dp(self.agg if whole else self._agg_chunk), _dp(self.nbr), _dp(self.uq),
+                                 _dp(self.cgf_ws), self.cgf_ws_bytes)
+            if not whole:
+                # (the call wrote its two views c1 - c0 slices apart, whatever the buffer holds)
+                flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, h, w)
+                self.agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
 
     def _aggregate_sgm(self, gray_l, gray_r, cost_l=None, cost_r=None):
         """The SGM flow: both whole cost volumes (the caller's, census, or the reference's cost) and the one
@@ -400,14 +477,14 @@ class PairPipeline:
         if self.speckle:
             self.despeckle()
 
-    def run(self, gray_l, gray_r):
-        self.aggregate(gray_l, gray_r)
+    def run(self, gray_l, gray_r, rgb_l=None, rgb_r=None):
+        self.aggregate(gray_l, gray_r, rgb_l=rgb_l, rgb_r=rgb_r)
         self.finish()
 
     def check_status(self):
         """Raise if a workgroup of the fused aggregation gave up waiting for a neighbour."""
         torch.cuda.synchronize(self.device)
-        if self.aggregation:            # (the SGM kernels wait for nothing: no status word)
+        if self.aggregation or self.guidance:            # (the SGM and colour-guided kernels wait for nothing: no status word)
             return
         with self._on_device():
             _lib.check(self.lib.smx_dev_agg_status(_dp(self.ws)))

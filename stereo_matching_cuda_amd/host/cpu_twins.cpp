@@ -9,6 +9,7 @@
 #include <limits>
 #include <vector>
 
+#include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
@@ -193,6 +194,90 @@ void guided_filter_onCpu(unsigned char* im1, float* cost, float* filtered_cost, 
             q[k] = m + mp[k];
         }
         dispSelectOnCPU(q.data(), filtered_cost, dmap, n, dmin + s);
+    }
+}
+
+// ---- colourGuidedFilter.cuh (not in the reference) ------------------------------------------
+// The definition of include/smx.h (above smx_cgf_workspace_bytes), sequentially: integral images as integralOnCPU, box means as
+// computeMeanOnCPU with the radius given, the 3 x 3 inverse in double with every product and sum rounded on its own.
+namespace {
+void cgf_box_mean(const float* img, float* S, float* mean, const int w, const int h, const int R) {
+    integralOnCPU(const_cast<float*>(img), S, w, h);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const int y0 = std::max(-1, y - R - 1), y1 = std::min(h - 1, y + R);
+            const int x0 = std::max(-1, x - R - 1), x1 = std::min(w - 1, x + R);
+            float val = S[(size_t)y1 * w + x1];
+            if (x0 >= 0) val -= S[(size_t)y1 * w + x0];
+            if (y0 >= 0) val -= S[(size_t)y0 * w + x1];
+            if (x0 >= 0 && y0 >= 0) val += S[(size_t)y0 * w + x0];
+            mean[(size_t)y * w + x] = val / (float)((x1 - x0) * (y1 - y0));
+        }
+}
+}  // namespace
+
+void colour_guided_filterOnCPU(const unsigned char* rgb, int channels, const float* cost, float* filter_cost, float* disp_map,
+                               float* agg, const int w, const int h, const int size_d, const int dmin, const int radius,
+                               const double eps) {
+    const size_t n = (size_t)w * h;
+    const int R = std::min(radius, std::max(w, h));      // (a window beyond the image is the image)
+    vector<float> I[3], mu[3], inv[6], cov[3], a[4], abar[4];
+    vector<float> S(n), t(n), m(n), mp(n), q(n);
+    for (int c = 0; c < 3; ++c) {
+        I[c].resize(n); mu[c].resize(n); cov[c].resize(n);
+        for (size_t k = 0; k < n; ++k) I[c][k] = (float)(int)rgb[k * channels + c];
+        cgf_box_mean(I[c].data(), S.data(), mu[c].data(), w, h, R);
+    }
+    for (int c = 0; c < 4; ++c) { a[c].resize(n); abar[c].resize(n); }
+    // v_cc' in the order rr, rg, rb, gg, gb, bb, kept in inv[] until the inverse overwrites them
+    static const int pair[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    for (int j = 0; j < 6; ++j) {
+        inv[j].resize(n);
+        for (size_t k = 0; k < n; ++k) t[k] = I[pair[j][0]][k] * I[pair[j][1]][k];
+        cgf_box_mean(t.data(), S.data(), m.data(), w, h, R);
+        for (size_t k = 0; k < n; ++k) {
+            const float prod = mu[pair[j][0]][k] * mu[pair[j][1]][k];
+            inv[j][k] = m[k] - prod;
+        }
+    }
+    for (size_t k = 0; k < n; ++k) {
+        const double va = (double)inv[0][k] + eps, vb = (double)inv[1][k], vc = (double)inv[2][k];
+        const double vd = (double)inv[3][k] + eps, ve = (double)inv[4][k], vf = (double)inv[5][k] + eps;
+        const double A = vd * vf - ve * ve, B = vc * ve - vb * vf, C = vb * ve - vc * vd;
+        const double D = va * vf - vc * vc, E = vb * vc - va * ve, F = va * vd - vb * vb;
+        const double det = (va * A + vb * B) + vc * C;
+        inv[0][k] = (float)(A / det); inv[1][k] = (float)(B / det); inv[2][k] = (float)(C / det);
+        inv[3][k] = (float)(D / det); inv[4][k] = (float)(E / det); inv[5][k] = (float)(F / det);
+    }
+    for (int s = 0; s < size_d; ++s) {
+        const float* p = cost + (size_t)s * n;
+        cgf_box_mean(p, S.data(), mp.data(), w, h, R);
+        for (int c = 0; c < 3; ++c) {
+            for (size_t k = 0; k < n; ++k) t[k] = I[c][k] * p[k];
+            cgf_box_mean(t.data(), S.data(), m.data(), w, h, R);
+            for (size_t k = 0; k < n; ++k) {
+                const float prod = mu[c][k] * mp[k];
+                cov[c][k] = m[k] - prod;
+            }
+        }
+        for (size_t k = 0; k < n; ++k) {
+            const float cr = cov[0][k], cg = cov[1][k], cb = cov[2][k];
+            const float r0 = inv[0][k] * cr, r1 = inv[1][k] * cg, r2 = inv[2][k] * cb;
+            const float g0 = inv[1][k] * cr, g1 = inv[3][k] * cg, g2 = inv[4][k] * cb;
+            const float b0 = inv[2][k] * cr, b1 = inv[4][k] * cg, b2 = inv[5][k] * cb;
+            a[0][k] = (r0 + r1) + r2;
+            a[1][k] = (g0 + g1) + g2;
+            a[2][k] = (b0 + b1) + b2;
+            const float s0 = a[0][k] * mu[0][k], s1 = a[1][k] * mu[1][k], s2 = a[2][k] * mu[2][k];
+            a[3][k] = mp[k] - ((s0 + s1) + s2);
+        }
+        for (int c = 0; c < 4; ++c) cgf_box_mean(a[c].data(), S.data(), abar[c].data(), w, h, R);
+        for (size_t k = 0; k < n; ++k) {
+            const float q0 = abar[0][k] * I[0][k], q1 = abar[1][k] * I[1][k], q2 = abar[2][k] * I[2][k];
+            q[k] = ((q0 + q1) + q2) + abar[3][k];
+        }
+        if (agg) std::memcpy(agg + (size_t)s * n, q.data(), n * sizeof(float));
+        dispSelectOnCPU(q.data(), filter_cost, disp_map, (int)n, dmin + s);
     }
 }
 

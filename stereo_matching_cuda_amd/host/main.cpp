@@ -50,6 +50,12 @@
 //                     (uniqueness_onCPU: brute force over the left aggregated volume) redoes it.  Composes with --cost
 //                     census, --aggregation sgm, --speckle, --subpixel, --wmf, --pfm and --png16; not with --ngpu or
 //                     --pipeline
+//   --guidance rgb    the guided filter with the colour images as its guide instead of the gray ones (smx_ctx_set_guidance,
+//                     smx_ctx_stereo_pair_rgb; not in the reference; implies --fused): an edge between two colours of equal
+//                     luminance stays an edge.  The same twelve images, the two mean images empty.  With --host-compare the
+//                     CPU twin (colour_guided_filterOnCPU) redoes both views from the cost volumes and check_errors
+//                     compares.  Composes with --cost census, --subpixel, --uniqueness, --speckle, --wmf, --pfm and --png16;
+//                     not with --aggregation sgm, --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -68,6 +74,7 @@
 #include <vector>
 
 #include "census.cuh"
+#include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
@@ -109,6 +116,7 @@ struct Options {
     smx_sgm_params sgm_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
+    bool rgb = false;        // --guidance rgb
     float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
     int pairs = 1;
@@ -243,6 +251,15 @@ Options parse(int argc, char** argv) {
             }
             if (o.ok) o.uniqueness = pct / (100.0f - pct);
         }
+        else if (a == "--guidance") {
+            std::string v;
+            value(v);
+            o.rgb = v == "rgb";
+            if (o.ok && !o.rgb && v != "gray") {
+                std::fprintf(stderr, "--guidance needs `gray` or `rgb`, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+        }
         else if (a == "--ngpu") { std::string v; value(v); o.ngpu = std::atoi(v.c_str()); }
         else if (a == "--pipeline") o.pipeline = true;
         else if (a == "--pairs") { std::string v; value(v); o.pairs = std::atoi(v.c_str()); }
@@ -300,6 +317,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--aggregation sgm cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
+    if (opt.rgb && (opt.sgm || opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--guidance rgb cannot be combined with --aggregation sgm, --ngpu or --pipeline\n");
+        return 2;
+    }
     if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
         std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
         return 2;
@@ -338,7 +359,7 @@ int main(int argc, char** argv) {
         }
     }
     const bool uniq = opt.uniqueness > 0.0f;
-    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm || uniq;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm || uniq || opt.rgb;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -354,6 +375,10 @@ int main(int argc, char** argv) {
         return 1;
     }
     const int w = in.w, h = in.h, n = w * h;
+    if (opt.rgb && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
+        std::fprintf(stderr, "--guidance rgb needs two images of 3 or of 4 channels, not %d and %d\n", in.channels[0], in.channels[1]);
+        return 1;
+    }
     std::cout << "Resolution : " << w << "x" << h << std::endl;
 
     std::cout << "RGB to grayscale ..." << std::endl;
@@ -418,7 +443,7 @@ int main(int argc, char** argv) {
         std::memset(&out, 0, sizeof(out));
         out.best_l = best[0].data(); out.best_r = best[1].data();
         out.dmap_l = dmap[0].data(); out.dmap_r = dmap[1].data();
-        if (!opt.sgm) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }     // (SGM has no mean images)
+        if (!opt.sgm && !opt.rgb) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }     // (SGM and the colour guide have no mean images)
         out.occlusion = occlusion.data(); out.filled = filled.data();
         std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness twin reads
         if (uniq && host_compare) {
@@ -435,9 +460,11 @@ int main(int argc, char** argv) {
         if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
         if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
         if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
+        if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
+                   : opt.rgb ? smx_ctx_stereo_pair_rgb(ctx, in.rgb[0], in.rgb[1], in.channels[0], dmin[0], dmin[1], &out)
                              : smx_ctx_stereo_pair(ctx, gray[0], gray[1], dmin[0], dmin[1], &out);
         };
         CHECK(run_pair());
@@ -494,6 +521,21 @@ int main(int argc, char** argv) {
                 ok = check_errors(td.data(), dmap[v].data(), n) && ok;
             }
             if (ok) std::cout << "Semi-global matching ok!" << std::endl;
+        }
+        if (host_compare && opt.rgb) {
+            // the twin redoes both views from whole cost volumes built by the stage wrappers, from the reference's presets
+            bool ok = true;
+            for (int v = 0; v < 2; ++v) {
+                std::vector<float> vol((size_t)n * size_d), tb(n), td(n, 0.0f);
+                std::memset(tb.data(), 0x7F, sizeof(float) * n);
+                if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
+                else CHECK(smx_compute_cost(&smx_config().params, gray[v], gray[1 - v], vol.data(), w, w, h, h, size_d, dmin[v]));
+                colour_guided_filterOnCPU(in.rgb[v], in.channels[v], vol.data(), tb.data(), td.data(), nullptr, w, h, size_d, dmin[v],
+                                          smx_config().params.radius, smx_config().params.eps);
+                ok = check_errors(tb.data(), best[v].data(), n) && ok;
+                ok = check_errors(td.data(), dmap[v].data(), n) && ok;
+            }
+            if (ok) std::cout << "Colour guided filter ok!" << std::endl;
         }
         if (host_compare) {
             std::vector<float> lr(dmap[0]);

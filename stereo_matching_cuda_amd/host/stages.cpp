@@ -7,6 +7,7 @@
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "colourGuidedFilter.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
 #include "wmf.cuh"
@@ -149,6 +150,26 @@ void speckle_filter(float* disparity, float* out, const int w, const int h, floa
         std::vector<float> twin((size_t)w * h);
         speckle_filterOnCPU(disparity, twin.data(), w, h, vmin, new_val, p);
         if (check_errors(twin.data(), out, w * h)) cout << "Speckle filter ok!" << endl;
+    }
+}
+
+// not in the reference: the guided filter with a colour guide (smx_main --guidance rgb)
+void compute_colour_guided_filter(unsigned char* rgb, int channels, float* cost, float* filter_cost, float* disp_map, float* agg,
+                                  const int w, const int h, const int size_d, const int dmin, bool host_gpu_compare) {
+    std::vector<float> tb, td;
+    if (host_gpu_compare) {            // (filter_cost / disp_map are IN/OUT: the twin starts from what the GPU starts from)
+        tb.assign(filter_cost, filter_cost + (size_t)w * h);
+        td.assign(disp_map, disp_map + (size_t)w * h);
+    }
+    CHECK(smx_colour_guided_filter(&smx_config().params, rgb, channels, cost, filter_cost, disp_map, agg, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        std::vector<float> ta(agg ? (size_t)w * h * size_d : 0);
+        colour_guided_filterOnCPU(rgb, channels, cost, tb.data(), td.data(), agg ? ta.data() : nullptr, w, h, size_d, dmin,
+                                  smx_config().params.radius, smx_config().params.eps);
+        bool ok = check_errors(tb.data(), filter_cost, w * h);
+        ok = check_errors(td.data(), disp_map, w * h) && ok;
+        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
+        if (ok) cout << "Colour guided filter ok!" << endl;
     }
 }
 

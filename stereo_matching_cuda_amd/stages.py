@@ -108,6 +108,25 @@ def compute_guided_filter(i, cost, filter_cost, disp_map, dmin, want_agg=False, 
     return mean, agg
 
 
+def colour_guided_filter(rgb, cost, filter_cost, disp_map, dmin, want_agg=False, params=None):
+    """Colour-guided filter aggregation + WTA (smx_colour_guided_filter; not a stage of the reference): rgb is the
+    (h, w, 3 or 4) uint8 guide.  filter_cost/disp_map are updated IN PLACE like compute_guided_filter's; returns agg or None."""
+    rgb, cost = _c(rgb, np.uint8), _c(cost, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] not in (3, 4):
+        raise ValueError("colour_guided_filter expects an (h, w, 3 or 4) uint8 guide")
+    h, w, ch = rgb.shape
+    size_d = cost.shape[0]
+    if cost.shape != (size_d, h, w):
+        raise ValueError("cost must be (size_d, h, w)")
+    for a in (filter_cost, disp_map):
+        if a.dtype != np.float32 or a.shape != (h, w) or not a.flags.c_contiguous:
+            raise ValueError("filter_cost/disp_map must be C-contiguous float32 (h, w) arrays")
+    agg = np.empty((size_d, h, w), np.float32) if want_agg else None
+    _lib.check(_lib.lib().smx_colour_guided_filter(
+        C.byref(_params(params)), _ptr(rgb), ch, _ptr(cost), _ptr(filter_cost), _ptr(disp_map), _ptr(agg), w, h, size_d, dmin))
+    return agg
+
+
 def detect_occlusion(disparity_left, disparity_right, d_occlusion, params=None):
     """LR consistency check; returns the updated copy of disparity_left.  occlusion.cu:17-85."""
     dl = _c(disparity_left, np.float32).copy()
