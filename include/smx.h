@@ -653,6 +653,68 @@ int smx_ctx_set_guidance(smx_ctx* ctx, int mode);
 int smx_ctx_stereo_pair_rgb(smx_ctx* ctx, const uint8_t* rgb_l, const uint8_t* rgb_r, int channels, int dminl, int dminr,
                             const smx_pair_out* out);
 
+/* ------------------------------------------------------------------------------------
+ * AD-Census matching cost: census plus absolute differences (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The census cost throws away everything but the ORDER of the gray values in its window: two patches of equal local order and
+ * different magnitudes cost 0 against each other (a periodic pattern whose periods differ in brightness ties between the true
+ * label and the labels one period away).  AD-Census (Mei et al. 2011) adds the absolute difference of the pixels, each term
+ * through rho(c, lambda) = 1 - exp(-c / lambda): the term that discriminates dominates and neither runs away.
+ * tests/adcensus_ref.py is this definition in numpy; the volume equals it bit for bit.
+ * Defaults: the census defaults, lambda_census 30, lambda_ad 10, scale 127.5, colour 0.  Valid: the census part as for
+ * smx_census_bits; both lambda finite with 0 < lambda <= 1e6; scale finite with 2^-20 <= scale <= 2^20; colour 0 or 1.
+ *   tables, computed on the host in double (nch = 3 if colour else 1), SMX_ADCENSUS_TABLE_FLOATS floats:
+ *         T[k]      = (float)(scale * (1.0 - exp(-(double)k / lambda_census)))          k = 0 .. 63
+ *         T[64 + s] = (float)(scale * (1.0 - exp(-(double)s / ((double)nch * lambda_ad))))   s = 0 .. 765
+ *         T[0] and T[64] are +0.0 and every other entry is a normal number in [2^-60, 2^60]: the value set of the comb
+ *         walker's exactness argument (smx_dev_agg_fallback), so no aggregation path takes its fall-back.  With the default
+ *         scale the cost lies in [0, 255], which the clamp of smx_dev_sgm_wta_pair keeps.
+ *   cost  of view v, slice z: own = the view, other = the other one, d = dmin_v + z, xx = x + d, t = min(th, nbits), the
+ *         codes those of smx_dev_census on the gray images.  If 0 <= xx < w:
+ *           hc = min(popcount(code_own[y][x] ^ code_other[y][xx]), t)
+ *           s  = sum over the channels c of |own_c[y][x] - other_c[y][xx]|    (one gray channel, or R, G, B: the first three
+ *                bytes of a pixel; a 4th byte is ignored)
+ *           cost[z][y][x] = T[hc] + T[64 + s]                                  (one f32 addition)
+ *         else cost[z][y][x] = T[t] + T[64 + 255 * nch].
+ *         Layout, slice placement and [s_begin, s_end) as for smx_dev_census_cost_pair. */
+typedef struct smx_adcensus_params {
+    smx_census_params census;   /* window and Hamming truncation, as for the census cost */
+    double lambda_census;       /* default 30 */
+    double lambda_ad;           /* default 10 */
+    double scale;               /* default 127.5: the cost lies in [0, 255], which SGM's clamp keeps */
+    int colour;                 /* 0: AD on the gray images; 1: AD on R, G, B of the colour images */
+} smx_adcensus_params;
+#define SMX_ADCENSUS_TABLE_FLOATS (64 + 766)
+void smx_default_adcensus_params(smx_adcensus_params* p);
+/* The tables above into `tables` (SMX_ADCENSUS_TABLE_FLOATS floats).  Host only: works without a GPU. */
+int smx_adcensus_tables(const smx_adcensus_params* p, float* tables);
+/* The same into device memory: a set-up call that copies from host memory and waits for the copy on `stream`.  NOT
+ * graph-capturable: upload the table once, outside any capture. */
+int smx_dev_adcensus_tables(const smx_adcensus_params* p, float* d_tables, void* stream);
+/* d_tables: smx_dev_adcensus_tables of the same parameters; d_code: the codes of the left gray image, then those of the right
+ * one (smx_dev_census with p->census); d_img_l / d_img_r: u8 [h][w][channels], channels 1 with colour 0 (the gray images), 3 or
+ * 4 with colour 1 (anything else is SMX_E_ARG).  Slices [s_begin, s_end) of the left volume (labels dminl + z) into d_cost_l
+ * and of the right volume (labels dminr + z) into d_cost_r, both in one launch; either cost pointer may be NULL (not both),
+ * which gives the single-view form.  One launch, no allocation, no synchronisation (graph-capturable).  w, h >= 1. */
+int smx_dev_adcensus_cost_pair(const smx_adcensus_params* p, const float* d_tables, const uint64_t* d_code,
+                               const uint8_t* d_img_l, const uint8_t* d_img_r, int channels, float* d_cost_l, float* d_cost_r,
+                               int w, int h, int dminl, int dminr, int s_begin, int s_end, void* stream);
+/* Host pointers, synchronous; mirrors smx_census_cost: the volume of i1 against i2 (u8 [h][w][channels]), size_d*w*h floats,
+ * labels dmin + z.  With colour input the gray images for the codes come from smx_dev_rgb_to_grayscale with the default
+ * smx_params. */
+int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uint8_t* i2, int channels, float* cost, int w,
+                      int h, int size_d, int dmin);
+/* The AD-Census cost of this context.  Non-NULL switches it on and replaces whatever smx_ctx_set_cost chose; NULL switches it
+ * off again (the reference's cost), and so does a later smx_ctx_set_cost.  (A setter of its own: smx_ctx_set_cost takes
+ * SMX_COST_REFERENCE and SMX_COST_CENSUS only.)  The flows are those of the census cost: codes once per pair, then cost chunk ->
+ * aggregation (the gray walkers, the colour-guided filter, SGM with the whole volumes); cost_l / cost_r of smx_pair_out
+ * receive the AD-Census volumes.  With colour 0 it runs through smx_ctx_stereo_pair, and through smx_ctx_stereo_pair_rgb with
+ * the AD term from the converted gray images.  With colour 1 it runs through smx_ctx_stereo_pair_rgb only, with either guide;
+ * smx_ctx_stereo_pair returns SMX_E_ARG.  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on.  The table and the
+ * buffers are allocated on first use. */
+int smx_ctx_set_adcensus(smx_ctx* ctx, const smx_adcensus_params* p);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -43,6 +43,15 @@ class CensusParams(C.Structure):
     _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("th", C.c_int)]
 
 
+class AdCensusParams(C.Structure):
+    """smx_adcensus_params: the AD-Census matching cost, census plus absolute differences (not a stage of the reference)."""
+    _fields_ = [("census", CensusParams), ("lambda_census", C.c_double), ("lambda_ad", C.c_double), ("scale", C.c_double),
+                ("colour", C.c_int)]
+
+
+ADCENSUS_TABLE_FLOATS = 64 + 766      # smx.h SMX_ADCENSUS_TABLE_FLOATS
+
+
 class SpeckleParams(C.Structure):
     """smx_speckle_params: the connected-component speckle filter (not a stage of the reference)."""
     _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
@@ -77,6 +86,7 @@ _vp, _i, _i64, _f, _sz, _u64, _u32 = (C.c_void_p, C.c_int, C.c_int64, C.c_float,
 _PP = C.POINTER(Params)
 _WP = C.POINTER(WmfParams)
 _CP = C.POINTER(CensusParams)
+_AP = C.POINTER(AdCensusParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
 
@@ -145,6 +155,12 @@ SIGNATURES = {
     "smx_dev_census_cost_pair": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "smx_census_cost": (_i, [_CP, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_cost": (_i, [_vp, _i, _CP]),
+    "smx_default_adcensus_params": (None, [_AP]),
+    "smx_adcensus_tables": (_i, [_AP, _vp]),
+    "smx_dev_adcensus_tables": (_i, [_AP, _vp, _vp]),
+    "smx_dev_adcensus_cost_pair": (_i, [_AP, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "smx_adcensus_cost": (_i, [_AP, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_adcensus": (_i, [_vp, _AP]),
     "smx_default_speckle_params": (None, [_SP]),
     "smx_speckle_workspace_bytes": (_sz, [_i, _i]),
     "smx_dev_speckle_filter": (_i, [_SP, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
@@ -246,6 +262,12 @@ def default_wmf_params():
 def default_census_params():
     p = CensusParams()
     lib().smx_default_census_params(C.byref(p))
+    return p
+
+
+def default_adcensus_params():
+    p = AdCensusParams()
+    lib().smx_default_adcensus_params(C.byref(p))
     return p
 
 

@@ -38,6 +38,7 @@ struct TimingPause { int saved; TimingPause(); ~TimingPause(); };   // while one
 bool subpix_mode_ok(int mode);
 bool wmf_params_ok(const smx_wmf_params* p);
 bool census_params_ok(const smx_census_params* p);
+bool adcensus_params_ok(const smx_adcensus_params* p);
 bool speckle_params_ok(const smx_speckle_params* p);
 bool uniq_ratio_ok(float ratio);
 bool speckle_shape_ok(int w, int h);

@@ -100,6 +100,11 @@ bool wmf_params_ok(const smx_wmf_params* p) {
            p->sigma_c > 0;
 }
 bool census_params_ok(const smx_census_params* p) { return p && p->rx >= 1 && p->rx <= 4 && p->ry >= 1 && p->ry <= 3 && p->th >= 1; }
+bool adcensus_params_ok(const smx_adcensus_params* p) {
+    return p && census_params_ok(&p->census) && isfinite(p->lambda_census) && p->lambda_census > 0 && p->lambda_census <= 1e6 &&
+           isfinite(p->lambda_ad) && p->lambda_ad > 0 && p->lambda_ad <= 1e6 && isfinite(p->scale) && p->scale >= 0x1p-20 &&
+           p->scale <= 0x1p20 && (p->colour == 0 || p->colour == 1);
+}
 bool uniq_ratio_ok(float ratio) { return isfinite(ratio) && ratio >= 0.0f; }
 bool speckle_params_ok(const smx_speckle_params* p) { return p && p->max_size >= 0 && isfinite(p->max_diff) && p->max_diff >= 0.0f; }
 bool speckle_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
@@ -602,6 +607,41 @@ int smx_dev_census_cost_pair(const smx_census_params* p, const uint64_t* d_code,
     SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
     return launch_census_cost_pair(census_t(p), d_code, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end,
                                    (hipStream_t)stream);
+}
+
+// ---- AD-Census matching cost (not in the reference; smx_adcensus.hip) ----------------------------------
+void smx_default_adcensus_params(smx_adcensus_params* p) {
+    if (!p) return;
+    smx_default_census_params(&p->census);
+    p->lambda_census = 30.0; p->lambda_ad = 10.0; p->scale = 127.5; p->colour = 0;
+}
+
+int smx_adcensus_tables(const smx_adcensus_params* p, float* tables) {
+    SMX_ARG(adcensus_params_ok(p) && tables);
+    // (1.0 - exp(-x), not -expm1(-x): the latter is -0.0 at x = 0, which the comb walker's cost check does not admit)
+    const double la = (double)(p->colour ? 3 : 1) * p->lambda_ad;
+    for (int k = 0; k < 64; ++k) tables[k] = (float)(p->scale * (1.0 - exp(-(double)k / p->lambda_census)));
+    for (int s = 0; s <= 765; ++s) tables[64 + s] = (float)(p->scale * (1.0 - exp(-(double)s / la)));
+    return SMX_OK;
+}
+
+int smx_dev_adcensus_tables(const smx_adcensus_params* p, float* d_tables, void* stream) {
+    SMX_ARG(adcensus_params_ok(p) && d_tables);
+    float t[SMX_ADCENSUS_TABLE_FLOATS];
+    smx_adcensus_tables(p, t);
+    SMX_HIP(hipMemcpyAsync(d_tables, t, sizeof(t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    SMX_HIP(hipStreamSynchronize((hipStream_t)stream));     // (t lives on this stack)
+    return SMX_OK;
+}
+
+int smx_dev_adcensus_cost_pair(const smx_adcensus_params* p, const float* d_tables, const uint64_t* d_code,
+                               const uint8_t* d_img_l, const uint8_t* d_img_r, int channels, float* d_cost_l, float* d_cost_r,
+                               int w, int h, int dminl, int dminr, int s_begin, int s_end, void* stream) {
+    SMX_ARG(adcensus_params_ok(p) && d_tables && d_code && d_img_l && d_img_r && (d_cost_l || d_cost_r));
+    SMX_ARG(p->colour ? channels == 3 || channels == 4 : channels == 1);
+    SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
+    return launch_adcensus_cost_pair(census_t(&p->census), p->colour ? 3 : 1, d_tables, d_code, d_img_l, d_img_r, channels,
+                                     d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end, (hipStream_t)stream);
 }
 
 // ---- semi-global matching (not in the reference; smx_sgm.hip) -----------------------------------------

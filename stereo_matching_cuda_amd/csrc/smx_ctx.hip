@@ -28,6 +28,12 @@ struct smx_ctx {
     smx_census_params census;
     int census_chunk = 0;
     DevBuf codes, ccost;
+    // AD-Census cost (smx_ctx_set_adcensus): it takes the place of the census cost in every flow, with the same codes and chunk
+    // buffers, and its table on the device
+    bool adcensus = false;
+    bool adc_tab_valid = false; // the device table holds the tables of `adc`
+    smx_adcensus_params adc;
+    DevBuf adc_tab;
     // speckle removal (smx_ctx_set_speckle): the despeckled left map [h][w] and the filter's workspace
     bool speckle = false;
     bool spk_valid = false;     // the map belongs to the last synchronous pair
@@ -70,8 +76,9 @@ struct smx_ctx {
 };
 
 // What one pair asks of the context beyond the eight result planes, decided once per pair by the entry that was called
-// (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them); its device images with the disparity of
-// slice 0 of either view; where its results go on the device (best / map / mean: left view first, right view behind it).
+// (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
+// census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
+// device (best / map / mean: left view first, right view behind it).
 struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
@@ -107,15 +114,27 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
 // The census codes of both images of `call`: one launch where they lie back to back, else one per image
 static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
     uint64_t* codes = c->codes.as<uint64_t>();
-    if (call.guide[1] == call.guide[0] + c->n) return smx_dev_census(&c->census, call.guide[0], codes, c->w, c->h, 2, call.st);
+    const smx_census_params* cp = c->adcensus ? &c->adc.census : &c->census;
+    if (call.guide[1] == call.guide[0] + c->n) return smx_dev_census(cp, call.guide[0], codes, c->w, c->h, 2, call.st);
     int rc = SMX_OK;
-    for (int v = 0; v < 2 && !rc; ++v) rc = smx_dev_census(&c->census, call.guide[v], codes + v * c->n, c->w, c->h, 1, call.st);
+    for (int v = 0; v < 2 && !rc; ++v) rc = smx_dev_census(cp, call.guide[v], codes + v * c->n, c->w, c->h, 1, call.st);
     return rc;
+}
+
+// Slices [s0, s1) of both views' cost from the codes: the census cost, or AD-Census with its AD term from the gray images or
+// from the colour images of the pair
+static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int s0, int s1, hipStream_t st) {
+    const uint64_t* codes = c->codes.as<uint64_t>();
+    if (!c->adcensus) return smx_dev_census_cost_pair(&c->census, codes, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
+    const bool colour = c->adc.colour != 0;
+    return smx_dev_adcensus_cost_pair(&c->adc, c->adc_tab.as<float>(), codes, colour ? in.rgb_l : in.left,
+                                      colour ? in.rgb_r : in.right, colour ? in.channels : 1, cl, cr, c->w, c->h, in.dminl,
+                                      in.dminr, s0, s1, st);
 }
 
 // Census mode of ctx_enqueue: census cost chunk -> aggregation from that chunk, over ascending contiguous chunks of `call`'s
 // slices, into the whole volumes where the context holds them, else into the chunk buffer.  Chunks after the first accumulate.
-static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
+static int ctx_census_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, bool whole) {
     const size_t n = c->n;
     const int chunk = whole ? c->size_d : c->census_chunk;
     int rc;
@@ -123,9 +142,7 @@ static int ctx_census_aggregate(smx_ctx* c, const AggCall& call, bool whole) {
         const int s1 = s0 + chunk < call.s_end ? s0 + chunk : call.s_end;
         float* cl = whole ? c->costL.as<float>() + (size_t)s0 * n : c->ccost.as<float>();
         float* cr = whole ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
-        if ((rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), cl, cr, c->w, c->h, call.dmin[0], call.dmin[1],
-                                           s0, s1, call.st)))
-            return rc;
+        if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
         AggCall part = call;
         part.s_begin = s0; part.s_end = s1;
         part.cost[0] = cl; part.cost[1] = cr;
@@ -148,8 +165,7 @@ static int ctx_cgf_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, 
         float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->cgf_cost.as<float>();
         float* cr = need.cost ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
         if (need.census) {
-            if ((rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), cl, cr, w, h, in.dminl, in.dminr, s0, s1, call.st)))
-                return rc;
+            if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
         } else if (!need.cost) {        // (whole reference volumes were built up front)
             if ((rc = smx_dev_cost_volume(&c->p, in.left, in.right, cl, w, w, h, in.dminl, s0, s1, call.st))) return rc;
             if ((rc = smx_dev_cost_volume(&c->p, in.right, in.left, cr, w, w, h, in.dminr, s0, s1, call.st))) return rc;
@@ -197,14 +213,13 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     if (need.census && (rc = ctx_census_codes(c, call))) return rc;
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
-        if (need.census) rc = smx_dev_census_cost_pair(&c->census, c->codes.as<uint64_t>(), costL, costR, w, h, in.dminl,
-                                                       in.dminr, 0, size_d, st);
+        if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
         const size_t sgm_bytes = sgm_workspace_bytes(w, h, size_d, 2);
         if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->sgm_ws.p,
                                                           sgm_bytes, st)
                                 : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p, sgm_bytes, st);
     } else if (need.cgf) rc = ctx_cgf_aggregate(c, in, call, need);
-    else if (need.census) rc = ctx_census_aggregate(c, call, need.cost);
+    else if (need.census) rc = ctx_census_aggregate(c, in, call, need.cost);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155
@@ -319,9 +334,17 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         return fail(SMX_E_ARG, "%s: the colour-guided filter (smx_ctx_set_guidance) produces no mean images", who);
     if (cgf && smx_cgf_workspace_bytes(c->w, c->h, 1, 2) == 0)
         return fail(SMX_E_ARG, "%s: the colour-guided filter needs h <= 65535 and w*h < 2^31", who);
+    if (c->adcensus && c->adc.colour && !channels)
+        return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
+                               "smx_ctx_stereo_pair_rgb", who);
     const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS, sgm, c->speckle, c->uniq > 0.0f, cgf};
+                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf};
     if ((rc = ctx_reserve(c, need))) return rc;
+    if (c->adcensus && !c->adc_tab_valid) {
+        SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
+        if ((rc = smx_dev_adcensus_tables(&c->adc, c->adc_tab.as<float>(), st))) return rc;
+        c->adc_tab_valid = true;
+    }
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
     c->sub_valid = c->spk_valid = c->uq_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
@@ -400,6 +423,21 @@ int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
         c->census = p;
     }
     c->cost_mode = mode;
+    c->adcensus = false;
+    return SMX_OK;
+}
+
+int smx_ctx_set_adcensus(smx_ctx* c, const smx_adcensus_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!adcensus_params_ok(p))
+            return fail(SMX_E_ARG, "smx_ctx_set_adcensus: needs a valid census window, 0 < lambda <= 1e6, 2^-20 <= scale <= 2^20 "
+                                   "and colour 0 or 1");
+        c->adc = *p;
+        c->adc_tab_valid = false;
+        c->cost_mode = SMX_COST_REFERENCE;      // (it replaces whatever smx_ctx_set_cost chose)
+    }
+    c->adcensus = p != nullptr;
     return SMX_OK;
 }
 
@@ -500,6 +538,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
+    if (c->adcensus)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the AD-Census cost is on (smx_ctx_set_adcensus): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: two pairs are in flight already (smx_ctx_wait takes the older one)");
     if ((rc = ctx_async_setup(c))) return rc;

@@ -176,6 +176,37 @@ int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t
     return SMX_OK;
 }
 
+int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uint8_t* i2, int channels, float* cost, int w,
+                      int h, int size_d, int dmin) {
+    SMX_ARG(adcensus_params_ok(p) && i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);
+    SMX_ARG(p->colour ? channels == 3 || channels == 4 : channels == 1);
+    const size_t n = (size_t)w * h, ib = n * (size_t)channels;
+    DevBuf img, gray, code, tab, dc;
+    SMX_HIP(img.ensure(2 * ib));
+    SMX_HIP(code.ensure(2 * n * sizeof(uint64_t)));
+    SMX_HIP(tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
+    SMX_HIP(dc.ensure(n * size_d * sizeof(float)));
+    SMX_HIP(hipMemcpy(img.p, i1, ib, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + ib, i2, ib, hipMemcpyHostToDevice));
+    int rc;
+    const uint8_t* g = img.as<uint8_t>();
+    if (p->colour) {          // the codes come from the gray images
+        smx_params dp;
+        smx_default_params(&dp);
+        SMX_HIP(gray.ensure(2 * n));
+        if ((rc = smx_dev_rgb_to_grayscale(&dp, img.as<uint8_t>(), (int64_t)(2 * n), channels, gray.as<uint8_t>(), nullptr))) return rc;
+        g = gray.as<uint8_t>();
+    }
+    if ((rc = smx_dev_adcensus_tables(p, tab.as<float>(), nullptr))) return rc;
+    if ((rc = smx_dev_census(&p->census, g, code.as<uint64_t>(), w, h, 2, nullptr))) return rc;
+    if ((rc = smx_dev_adcensus_cost_pair(p, tab.as<float>(), code.as<uint64_t>(), img.as<uint8_t>(), img.as<uint8_t>() + ib, channels,
+                                         dc.as<float>(), nullptr, w, h, dmin, 0, 0, size_d, nullptr)))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dc.download(cost, n * size_d * sizeof(float)));
+    return SMX_OK;
+}
+
 int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
                       int size_d, int dmin) {
     if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");

@@ -41,6 +41,11 @@ int launch_subpixel_pair(int mode, const int64_t* keys, const float* nbr, const 
 int launch_census(int rx, int ry, const uint8_t* img, uint64_t* code, int w, int h, int nimages, hipStream_t st);
 int launch_census_cost_pair(int t, const uint64_t* code, float* cost_l, float* cost_r, int w, int h, int dminl, int dminr,
                             int s_begin, int s_end, hipStream_t st);
+// smx_adcensus.hip: AD-Census cost slices [s_begin, s_end) of one or both views (t = min(th, nbits); nch = 1 or 3 channels in
+// the AD term; ch = bytes per pixel of img_l / img_r: 1, 3 or 4; table: SMX_ADCENSUS_TABLE_FLOATS floats on the device)
+int launch_adcensus_cost_pair(int t, int nch, const float* table, const uint64_t* code, const uint8_t* img_l, const uint8_t* img_r,
+                              int ch, float* cost_l, float* cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end,
+                              hipStream_t st);
 // smx_speckle.hip: the connected-component filter (smx_dev_speckle_filter); ws: speckle_workspace_bytes(w, h) bytes
 size_t speckle_workspace_bytes(int w, int h);
 int launch_speckle_filter(int max_size, float max_diff, const float* disp, float* out, int w, int h, float vmin,

@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None):
+                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -40,6 +40,10 @@ class PairPipeline:
         pipeline owns the codes self.codes (2, h, w) and a cost buffer self.census_cost of `slices_in_flight` slices per
         view, which the max_ws_bytes bound counts, and aggregate(gray_l, gray_r) runs cost chunk -> aggregation from
         that chunk over its slice range.  th_color / th_grad / alpha of `params` are unused then.
+        cost="adcensus" is AD-Census, census plus absolute differences (include/smx.h smx_dev_adcensus_cost_pair;
+        adcensus_params: AdCensusParams, None = the defaults): the flows and buffers of the census cost, with the device table
+        self.adcensus_table, uploaded here, beside them.  With adcensus_params.colour 1 the AD term comes from the colour
+        images: aggregate() / run() need rgb_l=, rgb_r= then, with either guide.
         speckle: None, True (the defaults) or SpeckleParams -- speckle removal (not a stage of the reference;
         smx_dev_speckle_filter behind the finish): self.despeckled = self.occlusion without its small connected components
         (vmin = dminl, new_val = dminl - 100), self.filled = the fill of self.despeckled, and the sub-pixel fit and
@@ -80,8 +84,8 @@ class PairPipeline:
                 raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
         if aggregation not in (None, "sgm"):
             raise ValueError(f"aggregation must be None or 'sgm', not {aggregation!r}")
-        if cost not in (None, "census"):
-            raise ValueError(f"cost must be None or 'census', not {cost!r}")
+        if cost not in (None, "census", "adcensus"):
+            raise ValueError(f"cost must be None, 'census' or 'adcensus', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
             raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
         if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
@@ -127,7 +131,12 @@ class PairPipeline:
             # both views in one workspace, and the reference cost goes through a chunk buffer like the census cost
             need = lambda n: (self.lib.smx_cgf_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
         self.cost = cost
-        self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
+        self.adcensus_params = self.adcensus_table = self._rgb = None
+        if cost == "adcensus":
+            self.adcensus_params = adcensus_params if adcensus_params is not None else _lib.default_adcensus_params()
+            self.census_params = self.adcensus_params.census          # (the codes are those of its census part)
+        else:
+            self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
         chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
         while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
@@ -163,6 +172,11 @@ class PairPipeline:
         self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
         self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not aggregation else None
+        if cost == "adcensus":
+            self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
+            with self._on_device():     # a set-up call: it waits for its copy, and stays outside any graph capture
+                _lib.check(self.lib.smx_dev_adcensus_tables(C.byref(self.adcensus_params), _dp(self.adcensus_table),
+                                                            self._stream()))
         if aggregation:
             self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
@@ -184,12 +198,19 @@ class PairPipeline:
     def aggregate(self, gray_l, gray_r, cost_l=None, cost_r=None, rgb_l=None, rgb_r=None):
         """Cost build (fused unless cost_* given) + guided-filter aggregation + running WTA of this
         rank's slices, both views.  Leaves packed keys in self.keys.  rgb_l / rgb_r: the colour guides of
-        guidance="rgb" (required then, refused otherwise)."""
+        guidance="rgb" and the images of the AD term of cost="adcensus" with colour 1 (required then, refused otherwise)."""
+        colour_cost = self.cost == "adcensus" and bool(self.adcensus_params.colour)
         if self.guidance:
             if rgb_l is None or rgb_r is None:
                 raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
+            self._rgb = (rgb_l, rgb_r)
             return self._aggregate_cgf(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
-        if rgb_l is not None or rgb_r is not None:
+        if colour_cost:
+            if rgb_l is None or rgb_r is None:
+                raise ValueError("cost='adcensus' with colour 1 needs the colour images: pass rgb_l= and rgb_r=")
+            self._check_rgb(rgb_l, rgb_r)
+            self._rgb = (rgb_l, rgb_r)
+        elif rgb_l is not None or rgb_r is not None:
             raise ValueError("rgb_l / rgb_r are the guides of guidance='rgb': this pipeline has the gray guide")
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
         if self.cost and (cost_l is not None or cost_r is not None):
@@ -220,9 +241,30 @@ class PairPipeline:
             finally:
                 self.lib.smx_set_max_slices_per_launch(0)
 
+    def _check_rgb(self, rgb_l, rgb_r):
+        for t in (rgb_l, rgb_r):
+            if t.dtype != torch.uint8 or t.dim() != 3 or tuple(t.shape[:2]) != (self.h, self.w) or t.shape[2] not in (3, 4) \
+                    or not t.is_contiguous():
+                raise ValueError(f"a colour guide is a contiguous ({self.h}, {self.w}, 3 or 4) uint8 tensor")
+        if rgb_l.shape[2] != rgb_r.shape[2]:
+            raise ValueError("both colour guides need the same number of channels")
+
+    def _code_cost(self, gray_l, gray_r, cl, cr, c0, c1, st):
+        """Slices [c0, c1) of both views' cost from self.codes into cl, cr: the census cost, or AD-Census with its AD term from
+        the gray images or, with colour 1, from the colour images of this aggregate()."""
+        L, w, h = self.lib, self.w, self.h
+        if self.cost == "census":
+            _lib.check(L.smx_dev_census_cost_pair(C.byref(self.census_params), _dp(self.codes), _dp(cl), _dp(cr), w, h,
+                                                  self.dminl, self.dminr, c0, c1, st))
+            return
+        il, ir = self._rgb if self.adcensus_params.colour else (gray_l, gray_r)
+        ch = int(il.shape[2]) if self.adcensus_params.colour else 1
+        _lib.check(L.smx_dev_adcensus_cost_pair(C.byref(self.adcensus_params), _dp(self.adcensus_table), _dp(self.codes), _dp(il),
+                                                _dp(ir), ch, _dp(cl), _dp(cr), w, h, self.dminl, self.dminr, c0, c1, st))
+
     def _aggregate_census(self, gray_l, gray_r):
-        """The census flow: the codes of both images once (one launch where the two images lie back to back in memory,
-        else one per image), then per chunk of `slices_in_flight` slices smx_dev_census_cost_pair into self.census_cost
+        """The census flow, and AD-Census's: the codes of both images once (one launch where the two images lie back to back in
+        memory, else one per image), then per chunk of `slices_in_flight` slices the cost (_code_cost) into self.census_cost
         and the aggregation from it.  Only the first chunk takes the keys as fresh; the later ones accumulate."""
         L, P = self.lib, C.byref(self.census_params)
         with self._on_device():
@@ -237,8 +279,7 @@ class PairPipeline:
             c1 = min(self.s_end, c0 + sif)
             cl, cr = self.census_cost[0], self.census_cost[1]
             with self._on_device():
-                _lib.check(L.smx_dev_census_cost_pair(P, _dp(self.codes), _dp(cl), _dp(cr), self.w, self.h, self.dminl,
-                                                      self.dminr, c0, c1, self._stream()))
+                self._code_cost(gray_l, gray_r, cl, cr, c0, c1, self._stream())
             whole = self.agg is None or self._agg_chunk is None
             self.aggregate_pair_cost(gray_l, gray_r, cl, cr, c0, c1, self.agg if whole else self._agg_chunk)
             if not whole:
@@ -255,12 +296,7 @@ class PairPipeline:
             raise ValueError("pass both cost volumes or neither")
         if self.cost and cost_l is not None:
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
-        for t in (rgb_l, rgb_r):
-            if t.dtype != torch.uint8 or t.dim() != 3 or tuple(t.shape[:2]) != (self.h, self.w) or t.shape[2] not in (3, 4) \
-                    or not t.is_contiguous():
-                raise ValueError(f"a colour guide is a contiguous ({self.h}, {self.w}, 3 or 4) uint8 tensor")
-        if rgb_l.shape[2] != rgb_r.shape[2]:
-            raise ValueError("both colour guides need the same number of channels")
+        self._check_rgb(rgb_l, rgb_r)
         self._guide = gray_l
         L, w, h, ch = self.lib, self.w, self.h, int(rgb_l.shape[2])
         self.init_keys()
@@ -278,8 +314,7 @@ class PairPipeline:
                     cl, cr = cost_l[c0 - self.s_begin:], cost_r[c0 - self.s_begin:]
                 elif self.cost:
                     cl, cr = self.census_cost[0], self.census_cost[1]
-                    _lib.check(L.smx_dev_census_cost_pair(C.byref(self.census_params), _dp(self.codes), _dp(cl), _dp(cr), w, h,
-                                                          self.dminl, self.dminr, c0, c1, st))
+                    self._code_cost(gray_l, gray_r, cl, cr, c0, c1, st)
                 else:
                     cl, cr = self.cgf_cost[0], self.cgf_cost[1]
                     P = C.byref(self.params)
@@ -308,8 +343,7 @@ class PairPipeline:
                 P = C.byref(self.census_params)
                 for v, g in enumerate((gray_l, gray_r)):
                     _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, st))
-                _lib.check(L.smx_dev_census_cost_pair(P, _dp(self.codes), _dp(cl), _dp(cr), w, h, self.dminl, self.dminr, 0,
-                                                      self.size_d, st))
+                self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
             elif cost_l is None:
                 P = C.byref(self.params)
                 _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))

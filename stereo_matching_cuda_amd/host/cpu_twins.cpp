@@ -9,6 +9,7 @@
 #include <limits>
 #include <vector>
 
+#include "adcensus.cuh"
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
@@ -431,6 +432,53 @@ void uniqueness_onCPU(const float* agg, const float* disparity, float* out, floa
         if (margin) margin[i] = d;
         if (ratio > 0.0f && d < bound && counts(disparity[i])) out[i] = new_val;
     }
+}
+
+// ---- adcensus.cuh (not in the reference) -----------------------------------------------------
+// The AD-Census cost by the definition in include/smx.h, one cell at a time: the census codes of the two gray images
+// (replicate clamp, bit k in window order with the centre skipped), then per cell the truncated Hamming distance, the sum of
+// the absolute differences over the channels, two table reads and one f32 addition.
+void adcensus_costOnCPU(const unsigned char* i1, const unsigned char* i2, const unsigned char* g1, const unsigned char* g2,
+                        int channels, float* cost, const int w, const int h, const int size_d, const int dmin,
+                        const smx_adcensus_params& p, const float* table) {
+    const size_t n = (size_t)w * h;
+    const int rx = p.census.rx, ry = p.census.ry, nbits = (2 * rx + 1) * (2 * ry + 1) - 1;
+    const int t = p.census.th < nbits ? p.census.th : nbits, nch = p.colour ? 3 : 1;
+    vector<uint64_t> code[2] = {vector<uint64_t>(n), vector<uint64_t>(n)};
+    const unsigned char* gray[2] = {g1, g2};
+    for (int v = 0; v < 2; ++v)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const unsigned char c = gray[v][(size_t)y * w + x];
+                uint64_t bits = 0;
+                int k = 0;
+                for (int dy = -ry; dy <= ry; ++dy)
+                    for (int dx = -rx; dx <= rx; ++dx) {
+                        if (dy == 0 && dx == 0) continue;
+                        const int yy = y + dy < 0 ? 0 : y + dy > h - 1 ? h - 1 : y + dy;
+                        const int xx = x + dx < 0 ? 0 : x + dx > w - 1 ? w - 1 : x + dx;
+                        if (gray[v][(size_t)yy * w + xx] < c) bits |= (uint64_t)1 << k;
+                        ++k;
+                    }
+                code[v][(size_t)y * w + x] = bits;
+            }
+    const float border = table[t] + table[64 + 255 * nch];
+    for (int z = 0; z < size_d; ++z)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const long long xx = (long long)x + dmin + z;
+                float* out = cost + (size_t)z * n + (size_t)y * w + x;
+                if (xx < 0 || xx >= w) { *out = border; continue; }
+                const size_t a = (size_t)y * w + x, b = (size_t)y * w + (size_t)xx;
+                const int pc = __builtin_popcountll(code[0][a] ^ code[1][b]);
+                const int hc = pc < t ? pc : t;
+                int s = 0;
+                for (int c = 0; c < nch; ++c) {
+                    const int d = (int)i1[a * channels + c] - (int)i2[b * channels + c];
+                    s += d < 0 ? -d : d;
+                }
+                *out = table[hc] + table[64 + s];
+            }
 }
 
 // ---- sgm.cuh (not in the reference) ----------------------------------------------------------

@@ -29,6 +29,15 @@
 //                     same twelve images, the two cost images from the census volumes.  --census-window WxH gives the
 //                     window in pixels (odd, 3x3 .. 9x7; default 9x7), --census-th N the truncation (>= 1; default 62).
 //                     Composes with --wmf, --subpixel, --pfm and --png16; not with --ngpu or --pipeline
+//   --cost adcensus   AD-Census, census plus absolute differences, each through 1 - exp(-c / lambda) (smx_ctx_set_adcensus;
+//                     implies --fused): the cost for pairs whose repeating patterns the census cost alone ties on.  The same
+//                     twelve images, the two cost images from the AD-Census volumes.  --census-window / --census-th apply to its
+//                     census part; --adcensus-lambda C,A gives the two lambda (0 < lambda <= 1e6; default 30,10),
+//                     --adcensus-scale S the scale (2^-20 .. 2^20; default 127.5), --ad gray|rgb the images of the absolute
+//                     difference: the gray ones (default) or R, G, B of the PNGs (smx_ctx_stereo_pair_rgb).  With
+//                     --host-compare the CPU twin (adcensus_costOnCPU) redoes the cost images.  Composes with --aggregation
+//                     sgm, --guidance rgb, --subpixel, --uniqueness, --speckle, --wmf, --pfm and --png16; not with --ngpu or
+//                     --pipeline
 //   --speckle SIZE[,DIFF]  speckle removal between the LR check and the fill (smx_speckle_filter; not in the reference), on
 //                     every single-GPU path: connected components of at most SIZE pixels whose 4-neighbours differ by at
 //                     most DIFF (default 1) are invalidated like LR failures.  Writes occlu_mapl_despeckled.png beside
@@ -73,6 +82,7 @@
 #include <chrono>
 #include <vector>
 
+#include "adcensus.cuh"
 #include "census.cuh"
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
@@ -112,6 +122,9 @@ struct Options {
     bool census = false;     // --cost census
     smx_census_params census_params;
     bool cost_given = false; // --cost seen
+    bool adcensus = false;   // --cost adcensus
+    bool ad_rgb = false;     // --ad rgb: the absolute differences on R, G, B of the colour images
+    smx_adcensus_params adc_params;     // (its census part is filled from census_params after the parse)
     bool sgm = false;        // --aggregation sgm
     smx_sgm_params sgm_params;
     bool speckle = false;    // --speckle
@@ -132,6 +145,8 @@ Options parse(int argc, char** argv) {
     smx_default_sgm_params(&o.sgm_params);
     bool sgm_option = false;        // --sgm-p / --sgm-paths seen
     bool census_option = false;     // --census-window / --census-th seen
+    bool adcensus_option = false;   // --adcensus-lambda / --adcensus-scale / --ad seen
+    smx_default_adcensus_params(&o.adc_params);
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto value = [&](std::string& dst) {
@@ -164,8 +179,44 @@ Options parse(int argc, char** argv) {
             value(v);
             o.cost_given = true;
             o.census = v == "census";
-            if (o.ok && !o.census && v != "reference") {
-                std::fprintf(stderr, "--cost needs `reference` or `census`, not `%s`\n", v.c_str());
+            o.adcensus = v == "adcensus";
+            if (o.ok && !o.census && !o.adcensus && v != "reference") {
+                std::fprintf(stderr, "--cost needs `reference`, `census` or `adcensus`, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+        }
+        else if (a == "--adcensus-lambda") {
+            std::string v;
+            value(v);
+            double lc = 0, la = 0;
+            char comma = 0, rest = 0;
+            adcensus_option = true;
+            if (o.ok && (std::sscanf(v.c_str(), "%lf%c%lf%c", &lc, &comma, &la, &rest) != 3 || comma != ',' || !(lc > 0) ||
+                         !(lc <= 1e6) || !(la > 0) || !(la <= 1e6))) {
+                std::fprintf(stderr, "--adcensus-lambda needs C,A with 0 < C, A <= 1e6, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.adc_params.lambda_census = lc; o.adc_params.lambda_ad = la;
+        }
+        else if (a == "--adcensus-scale") {
+            std::string v;
+            value(v);
+            char* end = nullptr;
+            const double sc = std::strtod(v.c_str(), &end);
+            adcensus_option = true;
+            if (o.ok && (v.empty() || *end || !(sc >= 1.0 / 1048576.0) || !(sc <= 1048576.0))) {
+                std::fprintf(stderr, "--adcensus-scale needs a scale S with 2^-20 <= S <= 2^20, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.adc_params.scale = sc;
+        }
+        else if (a == "--ad") {
+            std::string v;
+            value(v);
+            adcensus_option = true;
+            o.ad_rgb = v == "rgb";
+            if (o.ok && !o.ad_rgb && v != "gray") {
+                std::fprintf(stderr, "--ad needs `gray` or `rgb`, not `%s`\n", v.c_str());
                 o.ok = false;
             }
         }
@@ -268,11 +319,17 @@ Options parse(int argc, char** argv) {
         else o.positional.push_back(a);
     }
     if (o.sgm && !o.cost_given) o.census = true;     // census + SGM is the standard pairing
-    if (o.ok && census_option && !o.census) {        // (after the line above: the census options go with the implied cost too)
+    if (o.ok && census_option && !o.census && !o.adcensus) {     // (after the line above: the census options go with the implied cost too)
         std::fprintf(stderr, "--census-window and --census-th need the census cost (--cost census, or --aggregation sgm "
-                             "without --cost reference)\n");
+                             "without --cost reference) or --cost adcensus\n");
         o.ok = false;
     }
+    if (o.ok && adcensus_option && !o.adcensus) {
+        std::fprintf(stderr, "--adcensus-lambda, --adcensus-scale and --ad need --cost adcensus\n");
+        o.ok = false;
+    }
+    o.adc_params.census = o.census_params;
+    o.adc_params.colour = o.ad_rgb ? 1 : 0;
     if (o.ok && sgm_option && !o.sgm) {
         std::fprintf(stderr, "--sgm-p and --sgm-paths need --aggregation sgm\n");
         o.ok = false;
@@ -325,6 +382,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
         return 2;
     }
+    if (opt.adcensus && (opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--cost adcensus cannot be combined with --ngpu or --pipeline\n");
+        return 2;
+    }
     if (opt.sgm && (long long)d_hi - d_lo + 1 > SMX_SGM_MAX_D) {
         std::fprintf(stderr, "--aggregation sgm takes at most %d labels\n", SMX_SGM_MAX_D);
         return 2;
@@ -359,7 +420,7 @@ int main(int argc, char** argv) {
         }
     }
     const bool uniq = opt.uniqueness > 0.0f;
-    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.sgm || uniq || opt.rgb;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -375,8 +436,9 @@ int main(int argc, char** argv) {
         return 1;
     }
     const int w = in.w, h = in.h, n = w * h;
-    if (opt.rgb && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
-        std::fprintf(stderr, "--guidance rgb needs two images of 3 or of 4 channels, not %d and %d\n", in.channels[0], in.channels[1]);
+    if ((opt.rgb || opt.ad_rgb) && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
+        std::fprintf(stderr, "%s needs two images of 3 or of 4 channels, not %d and %d\n", opt.rgb ? "--guidance rgb" : "--ad rgb",
+                     in.channels[0], in.channels[1]);
         return 1;
     }
     std::cout << "Resolution : " << w << "x" << h << std::endl;
@@ -388,6 +450,9 @@ int main(int argc, char** argv) {
     // left volume: labels d_lo .. d_hi; right volume: labels -d_hi .. -d_lo   (main.cu:79-82)
     const int size_d = d_hi - d_lo + 1;
     const int dmin[2] = {d_lo, -d_hi};
+    // --cost adcensus: the images of its absolute differences, and their bytes per pixel
+    unsigned char* const ad_img[2] = {opt.ad_rgb ? in.rgb[0] : gray[0], opt.ad_rgb ? in.rgb[1] : gray[1]};
+    const int ad_ch = opt.ad_rgb ? in.channels[0] : 1;
     // WTA presets of main.cu:112-118: memset(best, 9999999.0f) stores byte 0x7F everywhere
     std::vector<float> best[2], dmap[2], cost[2];
     std::vector<unsigned char> mean[2], unused_u8[2];
@@ -429,7 +494,10 @@ int main(int argc, char** argv) {
         // is materialised, for the two cost images the reference writes)
         std::cout << "Cost Volume ..." << std::endl;
         for (int v = 0; v < 2; ++v) cost[v].resize((size_t)n);
-        if (opt.census) {
+        if (opt.adcensus) {
+            for (int v = 0; v < 2; ++v)
+                compute_adcensus_cost(ad_img[v], ad_img[1 - v], ad_ch, cost[v].data(), w, h, 1, dmin[v], opt.adc_params, host_compare);
+        } else if (opt.census) {
             compute_census_cost(gray[0], gray[1], cost[0].data(), w, h, 1, dmin[0], opt.census_params);
             compute_census_cost(gray[1], gray[0], cost[1].data(), w, h, 1, dmin[1], opt.census_params);
         } else {
@@ -457,6 +525,7 @@ int main(int argc, char** argv) {
         else CHECK(smx_create(&smx_config().params, w, h, size_d, &ctx));
         if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
         if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
+        if (opt.adcensus) CHECK(smx_ctx_set_adcensus(ctx, &opt.adc_params));
         if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
         if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
         if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
@@ -464,7 +533,7 @@ int main(int argc, char** argv) {
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
-                   : opt.rgb ? smx_ctx_stereo_pair_rgb(ctx, in.rgb[0], in.rgb[1], in.channels[0], dmin[0], dmin[1], &out)
+                   : opt.rgb || opt.ad_rgb ? smx_ctx_stereo_pair_rgb(ctx, in.rgb[0], in.rgb[1], in.channels[0], dmin[0], dmin[1], &out)
                              : smx_ctx_stereo_pair(ctx, gray[0], gray[1], dmin[0], dmin[1], &out);
         };
         CHECK(run_pair());
@@ -514,7 +583,9 @@ int main(int argc, char** argv) {
             bool ok = true;
             for (int v = 0; v < 2; ++v) {
                 std::vector<float> vol((size_t)n * size_d), tb(n), td(n);
-                if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
+                if (opt.adcensus)
+                    compute_adcensus_cost(ad_img[v], ad_img[1 - v], ad_ch, vol.data(), w, h, size_d, dmin[v], opt.adc_params, false);
+                else if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
                 else CHECK(smx_compute_cost(&smx_config().params, gray[v], gray[1 - v], vol.data(), w, w, h, h, size_d, dmin[v]));
                 sgm_aggregateOnCPU(vol.data(), nullptr, tb.data(), td.data(), w, h, size_d, dmin[v], opt.sgm_params);
                 ok = check_errors(tb.data(), best[v].data(), n) && ok;
@@ -528,7 +599,9 @@ int main(int argc, char** argv) {
             for (int v = 0; v < 2; ++v) {
                 std::vector<float> vol((size_t)n * size_d), tb(n), td(n, 0.0f);
                 std::memset(tb.data(), 0x7F, sizeof(float) * n);
-                if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
+                if (opt.adcensus)
+                    compute_adcensus_cost(ad_img[v], ad_img[1 - v], ad_ch, vol.data(), w, h, size_d, dmin[v], opt.adc_params, false);
+                else if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
                 else CHECK(smx_compute_cost(&smx_config().params, gray[v], gray[1 - v], vol.data(), w, w, h, h, size_d, dmin[v]));
                 colour_guided_filterOnCPU(in.rgb[v], in.channels[v], vol.data(), tb.data(), td.data(), nullptr, w, h, size_d, dmin[v],
                                           smx_config().params.radius, smx_config().params.eps);

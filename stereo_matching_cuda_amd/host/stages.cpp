@@ -1,6 +1,7 @@
 // stages.cpp -- the reference's per-stage host functions (same names, arguments and in/out
 // behaviour) as thin forwards to the C-ABI of include/smx.h.  Host pointers in, host pointers out,
 // synchronous, errors abort like the reference's CHECK macro.
+#include "adcensus.cuh"
 #include "census.cuh"
 #include "costVolume.cuh"
 #include "filter.cuh"
@@ -82,6 +83,28 @@ void compute_cost(unsigned char* i1, unsigned char* i2, float* cost, int w1, int
 void compute_census_cost(unsigned char* i1, unsigned char* i2, float* cost, int w, int h, int size_d, int dmin,
                          const smx_census_params& p) {
     CHECK(smx_census_cost(&p, i1, i2, cost, w, h, size_d, dmin));
+}
+
+// not in the reference: the AD-Census cost volume (smx_main --cost adcensus)
+void compute_adcensus_cost(unsigned char* i1, unsigned char* i2, int channels, float* cost, int w, int h, int size_d, int dmin,
+                           const smx_adcensus_params& p, bool host_gpu_compare) {
+    CHECK(smx_adcensus_cost(&p, i1, i2, channels, cost, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        const size_t n = (size_t)w * h;
+        std::vector<float> table(SMX_ADCENSUS_TABLE_FLOATS), twin(n * size_d);
+        CHECK(smx_adcensus_tables(&p, table.data()));
+        std::vector<unsigned char> g1, g2;          // the gray images of the codes, made like the device makes them
+        if (channels > 1) {
+            g1.resize(n); g2.resize(n);
+            sumArraysOnHost(i1, g1.data(), (int)n, channels);
+            sumArraysOnHost(i2, g2.data(), (int)n, channels);
+        }
+        adcensus_costOnCPU(i1, i2, channels > 1 ? g1.data() : i1, channels > 1 ? g2.data() : i2, channels, twin.data(), w, h,
+                           size_d, dmin, p, table.data());
+        bool ok = true;
+        for (int z = 0; z < size_d; ++z) ok = check_errors(twin.data() + (size_t)z * n, cost + (size_t)z * n, (int)n) && ok;
+        if (ok) cout << "AD-Census cost ok!" << endl;
+    }
 }
 
 // integral.cu:3-51

@@ -43,9 +43,9 @@ def merge_keys_host(key_arrays):
 class ShardedPair:
     """D-sharded stereo pair: local aggregation of this rank's slices, ONE all-reduce of both
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
-    The census matching cost (PairPipeline(cost="census")) is not part of the sharded driver: cost="census" raises
-    ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError.  Nor is semi-global
-    matching, which needs a pixel's whole disparity range on one rank: aggregation="sgm" raises ValueError."""
+    The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
+    cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError.  Nor
+    is semi-global matching, which needs a pixel's whole disparity range on one rank: aggregation="sgm" raises ValueError."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -53,7 +53,8 @@ class ShardedPair:
             # the neighbours of a winner at a shard boundary were aggregated on another rank
             raise ValueError("subpixel needs the whole slice range on one rank (world == 1)")
         if kw.get("cost") is not None:
-            raise ValueError("the census cost is not part of the sharded driver: use PairPipeline(cost='census')")
+            raise ValueError("the census and AD-Census costs are not part of the sharded driver: use "
+                             f"PairPipeline(cost={kw['cost']!r})")
         if kw.get("speckle") is not None:
             raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
         if kw.get("aggregation") is not None:

@@ -241,6 +241,29 @@ def census_cost(i1, i2, size_d, dmin, params=None):
     return cost
 
 
+def adcensus_tables(params=None):
+    """The AD-Census tables (smx_adcensus_tables; host only): a float32 array of 64 + 766 entries, T[k] the census half,
+    T[64 + s] the absolute-difference half."""
+    p = params if params is not None else _lib.default_adcensus_params()
+    t = np.zeros(_lib.ADCENSUS_TABLE_FLOATS, np.float32)
+    _lib.check(_lib.lib().smx_adcensus_tables(C.byref(p), _ptr(t)))
+    return t
+
+
+def adcensus_cost(i1, i2, size_d, dmin, params=None):
+    """AD-Census cost volume of i1 against i2, [z][y][x], slice z has label dmin + z (smx_adcensus_cost).  The images are
+    (h, w) uint8 with params.colour 0, or (h, w, 3 or 4) uint8 with params.colour 1."""
+    i1, i2 = _c(i1, np.uint8), _c(i2, np.uint8)
+    if i1.ndim not in (2, 3) or i2.shape != i1.shape:
+        raise ValueError("adcensus_cost expects two (h, w) or two (h, w, channels) uint8 images of one shape")
+    h, w = i1.shape[:2]
+    ch = 1 if i1.ndim == 2 else i1.shape[2]
+    p = params if params is not None else _lib.default_adcensus_params()
+    cost = np.empty((max(size_d, 0), h, w), np.float32)
+    _lib.check(_lib.lib().smx_adcensus_cost(C.byref(p), _ptr(i1), _ptr(i2), ch, _ptr(cost), w, h, size_d, dmin))
+    return cost
+
+
 def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
     """Semi-global matching of one (size_d, h, w) float32 cost volume (smx_sgm_aggregate; include/smx.h has the
     definition).  Returns (agg, best, disp_map): S as float32 [z][y][x] (None without want_agg), the winner's S and
