@@ -715,6 +715,69 @@ int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uin
  * buffers are allocated on first use. */
 int smx_ctx_set_adcensus(smx_ctx* ctx, const smx_adcensus_params* p);
 
+/* ------------------------------------------------------------------------------------
+ * Cross-based aggregation: colour-adaptive support regions (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* Cross-based aggregation (Zhang, Lu, Lafruit 2009), the step of Mei et al. 2011 between the AD-Census cost and the scan-line
+ * optimiser: every pixel gets a support region that grows up to l1 pixels in each direction through similar colour and stops
+ * dead at a colour edge; it is built once per view from the guide alone and applied to every slice with two passes of sums.
+ * Everything is an exact integer, so the result is the same bits in every run and under every schedule.
+ * tests/cross_ref.py is this definition in numpy; the result equals it bit for bit.
+ * Defaults (Mei's values): l1 34, l2 17, tau1 20, tau2 6, iterations 4.  Valid: 1 <= l1 <= 63, 0 <= l2 <= l1,
+ * 1 <= tau2 <= tau1 <= 256, 1 <= iterations <= 4; anything else is SMX_E_ARG before any device call.
+ *   guide:   u8 [h][w][channels], channels 1 (gray), 3 or 4 (a fourth byte is ignored); D(p, q) = max over the channels c of
+ *            |I_c(p) - I_c(q)|.
+ *   arms:    for a pixel p and a direction e (left, right, up, down) the largest k in 0 .. l1 such that every j = 1 .. k has,
+ *            with q_j = p + j e: q_j inside the image, D(q_j, p) < tau1, D(q_j, q_{j-1}) < tau1, and D(q_j, p) < tau2 where
+ *            j > l2.  The comparisons are strict (tau = 256 accepts everything); an arm may be 0.  One u32 per pixel holds the
+ *            four arms: l | r << 8 | u << 16 | d << 24.
+ *   values:  a cost c is read through the clamp of smx_dev_sgm_wta_pair, C = c >= 0 ? (c <= 255 ? (int)c : 255) : 0 (a NaN
+ *            gives 0: the call is total on any bits); V_0 = 16 * C, four fractional bits.
+ *   iteration i = 0 .. iterations - 1: even i sums horizontally first,
+ *              H(y, x) = sum of V(y, x') over x - l(y, x) <= x' <= x + r(y, x),
+ *              S(y, x) = sum of H(y', x) over y - u(y, x) <= y' <= y + d(y, x);
+ *            odd i vertically first: T(y, x) = the sum of V over the vertical arm of (y, x), S(y, x) = the sum of T(y, x') over
+ *            the horizontal arm of (y, x).  area_HV / area_VH are the same sums of V = 1 (1 .. 127^2).  With `area` the area of
+ *            the iteration's order, in floor division: V_{i+1} = (2 S + area) / (2 area).  V <= 4080 and S < 2^26 always.
+ *   output:  q = (float)V_iterations * 0.0625f (exact).
+ *   winner:  the packed keys and the tie rule of smx_dev_aggregate_wta (the last slice of equal costs wins).
+ *
+ * smx_dev_cross_arms: the arms planes of the guides, n u32 each, the left view's first; either guide may be NULL (not both),
+ * which leaves the one plane.  One launch.
+ * smx_dev_cross_wta_pair has the shape and the rules of smx_dev_cgf_wta_pair: both views in every launch; either guide / cost
+ * pair may be NULL (not both; a view's guide and cost come together) for the one-view form, whose outputs hold that one view;
+ * the cost slices [s_begin, s_end) materialised at d_cost[(s - s_begin) * w*h]; d_keys IN/OUT, accumulated across calls and
+ * D-shards by the int64 min; d_agg optional, (s_end - s_begin) * n floats per view: q; d_nbr, d_uq optional, 3n floats per
+ * view each, with their rule (ascending, contiguous ranges on one set of keys).  The slices go in chunks that fit the workspace
+ * (smx_set_max_slices_per_launch bounds the chunk as well); the chunking does not change a bit.  Five launches per call for
+ * the support regions, then per chunk two per iteration and the winner-take-all pass; no allocation, no synchronisation
+ * (graph-capturable).  smx_cross_workspace_bytes(w, h, nslices, nviews) holds `nslices` slices in flight: per view and pixel
+ * 8 bytes of arms and areas and, per slice in flight, 12 bytes (two u16 planes, the u32 sums between an iteration's two
+ * passes, one f32 plane), plus 255 bytes (0 for invalid sizes: w, h >= 1, w*h < 2^31, nslices >= 1, nviews 1 or 2).  Fewer
+ * bytes than for one slice is SMX_E_WS before anything is launched.  The memory contract is that of the aggregation entries
+ * above smx_agg_workspace_bytes: nothing is written outside the workspace and the stated extents, the workspace may hold
+ * anything and needs no alignment, the inputs are not modified.
+ * smx_cross_aggregate: host pointers, one view, synchronous; filter_cost / disp_map IN/OUT and agg as for
+ * smx_colour_guided_filter. */
+typedef struct smx_cross_params { int l1, l2, tau1, tau2, iterations; } smx_cross_params;
+void smx_default_cross_params(smx_cross_params* p);
+size_t smx_cross_workspace_bytes(int w, int h, int nslices, int nviews);
+int smx_dev_cross_arms(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels, int w, int h,
+                       uint32_t* d_arms, void* stream);
+int smx_dev_cross_wta_pair(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
+                           const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
+                           float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int channels, const float* cost, float* filter_cost,
+                        float* disp_map, float* agg, int w, int h, int size_d, int dmin);
+/* Cross-based aggregation of this context.  Non-NULL switches it on, NULL switches it off again (the guided filter).  (A
+ * setter of its own: smx_ctx_set_aggregation takes SMX_AGG_GUIDED and SMX_AGG_SGM only.)  The flow is that of the colour
+ * guide: cost chunk -> smx_dev_cross_wta_pair, the cost being the reference's, census or AD-Census.  The guide is the gray
+ * pair through smx_ctx_stereo_pair and the colour images through smx_ctx_stereo_pair_rgb.  mean_l / mean_r are not produced
+ * (SMX_E_ARG if requested).  Together with SMX_AGG_SGM or SMX_GUIDE_RGB the pair call returns SMX_E_ARG, and so does
+ * smx_ctx_stereo_pair_async while it is on.  The workspace and the chunk buffers are allocated on first use. */
+int smx_ctx_set_cross(smx_ctx* ctx, const smx_cross_params* p);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -62,6 +62,11 @@ class SgmParams(C.Structure):
     _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("paths", C.c_int)]
 
 
+class CrossParams(C.Structure):
+    """smx_cross_params: cross-based aggregation (not a stage of the reference)."""
+    _fields_ = [("l1", C.c_int), ("l2", C.c_int), ("tau1", C.c_int), ("tau2", C.c_int), ("iterations", C.c_int)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -89,6 +94,7 @@ _CP = C.POINTER(CensusParams)
 _AP = C.POINTER(AdCensusParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
+_XP = C.POINTER(CrossParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -185,6 +191,12 @@ SIGNATURES = {
     "smx_colour_guided_filter": (_i, [_PP, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_guidance": (_i, [_vp, _i]),
     "smx_ctx_stereo_pair_rgb": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(PairOut)]),
+    "smx_default_cross_params": (None, [_XP]),
+    "smx_cross_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_cross_arms": (_i, [_XP, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "smx_dev_cross_wta_pair": (_i, [_XP, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_cross_aggregate": (_i, [_XP, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_cross": (_i, [_vp, _XP]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -280,6 +292,12 @@ def default_speckle_params():
 def default_sgm_params():
     p = SgmParams()
     lib().smx_default_sgm_params(C.byref(p))
+    return p
+
+
+def default_cross_params():
+    p = CrossParams()
+    lib().smx_default_cross_params(C.byref(p))
     return p
 
 

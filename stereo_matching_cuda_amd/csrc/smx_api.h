@@ -32,6 +32,7 @@ struct DevBuf {
 // Every aggregation of the C-ABI meets the calling thread's knobs here.  accumulates: the call adds to keys that an earlier
 // chunk of the same pair wrote, so the thread's keys_fresh does not apply to it.
 int run_aggregation(const AggCall& c, int forced, bool accumulates);
+int thread_max_chunk();                // smx_set_max_slices_per_launch of the calling thread
 int thread_agg_path();                  // smx_set_agg_path of the calling thread (what smx_create copies)
 int agg_status_error(unsigned status);  // a workspace's status word [0] -> SMX_OK or the "hand-off wait ... timed out" error
 struct TimingPause { int saved; TimingPause(); ~TimingPause(); };   // while one lives, stage_mark records nothing
@@ -44,6 +45,8 @@ bool uniq_ratio_ok(float ratio);
 bool speckle_shape_ok(int w, int h);
 bool sgm_params_ok(const smx_sgm_params* p);
 bool sgm_shape_ok(int w, int h, int size_d);
+bool cross_params_ok(const smx_cross_params* p);
+bool cross_shape_ok(int w, int h);
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

@@ -87,6 +87,7 @@ int fail(int code, const char* fmt, ...) {
 }
 
 int thread_agg_path() { return g_agg_path; }
+int thread_max_chunk() { return g_max_chunk; }
 TimingPause::TimingPause() : saved(g_timing) { g_timing = 0; }
 TimingPause::~TimingPause() { g_timing = saved; }
 int agg_status_error(unsigned status) {

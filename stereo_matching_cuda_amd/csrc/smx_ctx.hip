@@ -53,6 +53,13 @@ struct smx_ctx {
     int cgf_chunk = 0;
     size_t cgf_ws_bytes = 0;
     DevBuf rgb, cgf_ws, cgf_cost;
+    // cross-based aggregation (smx_ctx_set_cross): its workspace for both views and, without whole volumes, one chunk of both
+    // views' cost slices [2][cross_chunk][h][w]
+    bool cross = false;
+    smx_cross_params cross_params;
+    int cross_chunk = 0;
+    size_t cross_ws_bytes = 0;
+    DevBuf cross_ws, cross_cost;
     // pipelined entry: two slots of device inputs / results and pinned staging, created on first use.  Staging of a slot:
     // [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l mean_r | status word] coming down.
     struct Slot {
@@ -79,7 +86,7 @@ struct smx_ctx {
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -107,6 +114,15 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
         c->cgf_ws_bytes = cgf_workspace_bytes(c->w, c->h, k, 2);
         SMX_HIP(c->cgf_ws.ensure(c->cgf_ws_bytes));
         if (!need.cost) SMX_HIP(c->cgf_cost.ensure(2 * (size_t)k * fb));
+    }
+    if (need.cross) {
+        const size_t cap = (size_t)2 << 30;
+        int k = c->size_d;
+        while (k > 1 && cross_workspace_bytes(c->w, c->h, k, 2) + (need.cost ? 0 : 2 * (size_t)k * fb) > cap) k = (k + 1) / 2;
+        c->cross_chunk = k;
+        c->cross_ws_bytes = cross_workspace_bytes(c->w, c->h, k, 2);
+        SMX_HIP(c->cross_ws.ensure(c->cross_ws_bytes));
+        if (!need.cost) SMX_HIP(c->cross_cost.ensure(2 * (size_t)k * fb));
     }
     return SMX_OK;
 }
@@ -185,6 +201,42 @@ static int ctx_cgf_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, 
     return SMX_OK;
 }
 
+// Cross-based mode of ctx_enqueue: the flow of ctx_cgf_aggregate with smx_dev_cross_wta_pair; the guide is the colour pair where
+// the pair came as colour images, else the gray pair.
+static int ctx_cross_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
+    const size_t n = c->n;
+    const int w = c->w, h = c->h, chunk = c->cross_chunk;
+    const uint8_t* gl = in.channels ? in.rgb_l : in.left;
+    const uint8_t* gr = in.channels ? in.rgb_r : in.right;
+    const int ch = in.channels ? in.channels : 1;
+    const smx_cross_params* cp = &c->cross_params;
+    int rc;
+    for (int s0 = 0; s0 < c->size_d; s0 += chunk) {
+        const int s1 = s0 + chunk < c->size_d ? s0 + chunk : c->size_d;
+        float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->cross_cost.as<float>();
+        float* cr = need.cost ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
+        if (need.census) {
+            if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
+        } else if (!need.cost) {        // (whole reference volumes were built up front)
+            if ((rc = smx_dev_cost_volume(&c->p, in.left, in.right, cl, w, w, h, in.dminl, s0, s1, call.st))) return rc;
+            if ((rc = smx_dev_cost_volume(&c->p, in.right, in.left, cr, w, w, h, in.dminr, s0, s1, call.st))) return rc;
+        }
+        if (!need.agg) {
+            rc = smx_dev_cross_wta_pair(cp, gl, gr, ch, cl, cr, w, h, s0, s1, call.keys[0], nullptr, call.nbr[0], call.uq[0],
+                                        c->cross_ws.p, c->cross_ws_bytes, call.st);
+        } else {
+            rc = smx_dev_cross_wta_pair(cp, gl, nullptr, ch, cl, nullptr, w, h, s0, s1, call.keys[0], call.agg[0] + (size_t)s0 * n,
+                                        call.nbr[0], call.uq[0], c->cross_ws.p, c->cross_ws_bytes, call.st);
+            if (!rc)
+                rc = smx_dev_cross_wta_pair(cp, nullptr, gr, ch, nullptr, cr, w, h, s0, s1, call.keys[1],
+                                            call.agg[1] + (size_t)s0 * n, call.nbr[1], call.uq[1], c->cross_ws.p,
+                                            c->cross_ws_bytes, call.st);
+        }
+        if (rc) return rc;
+    }
+    return SMX_OK;
+}
+
 // The path of one pair on the context's stream: device images in, the eight result planes (+ the context's volumes) out.
 static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
     const smx_params* p = &c->p;
@@ -219,6 +271,7 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
                                                           sgm_bytes, st)
                                 : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p, sgm_bytes, st);
     } else if (need.cgf) rc = ctx_cgf_aggregate(c, in, call, need);
+    else if (need.cross) rc = ctx_cross_aggregate(c, in, call, need);
     else if (need.census) rc = ctx_census_aggregate(c, in, call, need.cost);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
@@ -334,11 +387,17 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         return fail(SMX_E_ARG, "%s: the colour-guided filter (smx_ctx_set_guidance) produces no mean images", who);
     if (cgf && smx_cgf_workspace_bytes(c->w, c->h, 1, 2) == 0)
         return fail(SMX_E_ARG, "%s: the colour-guided filter needs h <= 65535 and w*h < 2^31", who);
+    const bool cross = c->cross;
+    if (cross && sgm) return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) and semi-global matching are both on", who);
+    if (cross && cgf) return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) and colour guidance are both on", who);
+    if (cross && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) produces no mean images", who);
+    if (cross && !cross_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "%s: cross-based aggregation needs w*h < 2^31", who);
     if (c->adcensus && c->adc.colour && !channels)
         return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
                                "smx_ctx_stereo_pair_rgb", who);
     const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf};
+                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross};
     if ((rc = ctx_reserve(c, need))) return rc;
     if (c->adcensus && !c->adc_tab_valid) {
         SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
@@ -373,7 +432,8 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    if (!need.sgm && !need.cgf && (rc = smx_dev_agg_status(c->ws.p))) return rc;      // (the SGM and colour-guided kernels wait for nothing)
+    // (the SGM, colour-guided and cross-based kernels wait for nothing)
+    if (!need.sgm && !need.cgf && !need.cross && (rc = smx_dev_agg_status(c->ws.p))) return rc;
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
@@ -399,6 +459,18 @@ int smx_ctx_set_guidance(smx_ctx* c, int mode) {
     if (mode != SMX_GUIDE_GRAY && mode != SMX_GUIDE_RGB)
         return fail(SMX_E_ARG, "smx_ctx_set_guidance: mode must be SMX_GUIDE_GRAY or SMX_GUIDE_RGB");
     c->guide_mode = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_cross(smx_ctx* c, const smx_cross_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!cross_params_ok(p))
+            return fail(SMX_E_ARG, "smx_ctx_set_cross: needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and "
+                                   "1 <= iterations <= 4");
+        c->cross_params = *p;
+    }
+    c->cross = p != nullptr;
     return SMX_OK;
 }
 
@@ -536,6 +608,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
     if (c->guide_mode != SMX_GUIDE_GRAY)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb");
+    if (c->cross)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-based aggregation is on (smx_ctx_set_cross): use smx_ctx_stereo_pair");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->adcensus)

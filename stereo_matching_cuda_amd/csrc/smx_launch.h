@@ -66,4 +66,13 @@ int cgf_chunk(int w, int h, int nviews, size_t ws_bytes, int count, int max_chun
 int launch_cgf_wta_pair(const smx_params* p, const uint8_t* rgb_l, const uint8_t* rgb_r, int ch, const float* cost_l,
                         const float* cost_r, int w, int h, int s_begin, int s_end, int64_t* keys, float* agg, float* nbr,
                         float* uq, void* ws, int chunk, hipStream_t st);
+// smx_cross.hip: cross-based aggregation (smx_dev_cross_wta_pair); ws: cross_workspace_bytes bytes for the slices in flight,
+// chunk: cross_chunk of that workspace (>= 1)
+size_t cross_workspace_bytes(int w, int h, int nslices, int nviews);
+int cross_chunk(int w, int h, int nviews, size_t ws_bytes, int count, int max_chunk);
+int launch_cross_arms(const smx_cross_params* p, const uint8_t* guide_l, const uint8_t* guide_r, int ch, int w, int h,
+                      uint32_t* arms, hipStream_t st);
+int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, const uint8_t* guide_r, int ch, const float* cost_l,
+                          const float* cost_r, int w, int h, int s_begin, int s_end, int64_t* keys, float* agg, float* nbr,
+                          float* uq, void* ws, int chunk, hipStream_t st);
 }  // namespace smx

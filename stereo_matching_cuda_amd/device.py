@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None):
+                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -69,11 +69,16 @@ class PairPipeline:
         reference's cost into self.cgf_cost, or census) -> smx_dev_cgf_wta_pair over chunks of `slices_in_flight` slices.
         The pipeline owns the chunk's cost slices and the workspace self.cgf_ws (max_ws_bytes counts both); no workspace of
         the gray path is allocated and self.mean stays zero.  Not with aggregation="sgm".  With None nothing is allocated or
-        launched."""
+        launched.
+        aggregation="cross" is cross-based aggregation (not a stage of the reference; include/smx.h smx_dev_cross_wta_pair;
+        cross_params: CrossParams, None = the defaults): the flow and the buffers of guidance="rgb" -- cost chunk (the
+        reference's cost into self.cross_cost, census or AD-Census) -> smx_dev_cross_wta_pair over chunks of
+        `slices_in_flight` slices, with the workspace self.cross_ws -- and slice sub-ranges are allowed.  The guide is the
+        colour pair rgb_l=, rgb_r= of aggregate() / run() where it is given, else the gray pair.  Not with guidance="rgb"."""
         if guidance not in (None, "rgb"):
             raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
         if guidance and aggregation:
-            raise ValueError("colour guidance belongs to the guided filter: not with aggregation='sgm'")
+            raise ValueError(f"colour guidance belongs to the guided filter: not with aggregation={aggregation!r}")
         if uniqueness is not None:
             uniqueness = float(uniqueness)
             if not (0.0 < uniqueness < float("inf")):
@@ -82,8 +87,9 @@ class PairPipeline:
             # winners it does not belong to)
             if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
                 raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
-        if aggregation not in (None, "sgm"):
-            raise ValueError(f"aggregation must be None or 'sgm', not {aggregation!r}")
+        if aggregation not in (None, "sgm", "cross"):
+            raise ValueError(f"aggregation must be None, 'sgm' or 'cross', not {aggregation!r}")
+        sgm, cross = aggregation == "sgm", aggregation == "cross"
         if cost not in (None, "census", "adcensus"):
             raise ValueError(f"cost must be None, 'census' or 'adcensus', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
@@ -104,7 +110,7 @@ class PairPipeline:
         self.aggregation = aggregation
         self.sgm_params = self.sgm_cost = self.sgm_ws = None
         self.sgm_ws_bytes = 0
-        if aggregation:
+        if sgm:
             if self.s_begin != 0 or self.s_end != self.size_d:
                 raise ValueError("semi-global matching needs a pixel's whole disparity range: no slice sub-range")
             self.sgm_params = sgm_params if sgm_params is not None else _lib.default_sgm_params()
@@ -130,6 +136,13 @@ class PairPipeline:
                 raise ValueError(f"the colour-guided filter does not take {self.w} x {self.h} (h <= 65535, w*h < 2^31)")
             # both views in one workspace, and the reference cost goes through a chunk buffer like the census cost
             need = lambda n: (self.lib.smx_cgf_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
+        self.cross_params = self.cross_ws = self.cross_cost = None
+        self.cross_ws_bytes = 0
+        if cross:
+            self.cross_params = cross_params if cross_params is not None else _lib.default_cross_params()
+            if self.lib.smx_cross_workspace_bytes(self.w, self.h, 1, 2) == 0:
+                raise ValueError(f"cross-based aggregation does not take {self.w} x {self.h} (w*h < 2^31)")
+            need = lambda n: (self.lib.smx_cross_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
         self.cost = cost
         self.adcensus_params = self.adcensus_table = self._rgb = None
         if cost == "adcensus":
@@ -171,22 +184,26 @@ class PairPipeline:
         self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
         self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
-        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not aggregation else None
+        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm else None
         if cost == "adcensus":
             self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
             with self._on_device():     # a set-up call: it waits for its copy, and stays outside any graph capture
                 _lib.check(self.lib.smx_dev_adcensus_tables(C.byref(self.adcensus_params), _dp(self.adcensus_table),
                                                             self._stream()))
-        if aggregation:
+        if sgm:
             self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
         if guidance:
             self.cgf_ws_bytes = int(self.lib.smx_cgf_workspace_bytes(self.w, self.h, sif, 2))
             self.cgf_ws = torch.empty(self.cgf_ws_bytes, dtype=torch.uint8, device=dev)
             self.cgf_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
+        if cross:
+            self.cross_ws_bytes = int(self.lib.smx_cross_workspace_bytes(self.w, self.h, sif, 2))
+            self.cross_ws = torch.empty(self.cross_ws_bytes, dtype=torch.uint8, device=dev)
+            self.cross_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
         self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
-            if (cost or guidance) and want_agg and sif < local and not aggregation else None
+            if (cost or guidance or cross) and want_agg and sif < local and not sgm else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -205,6 +222,15 @@ class PairPipeline:
                 raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
             self._rgb = (rgb_l, rgb_r)
             return self._aggregate_cgf(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
+        if self.aggregation == "cross":
+            if (rgb_l is None) != (rgb_r is None):
+                raise ValueError("pass both colour guides or neither")
+            if colour_cost and rgb_l is None:
+                raise ValueError("cost='adcensus' with colour 1 needs the colour images: pass rgb_l= and rgb_r=")
+            if rgb_l is not None:
+                self._check_rgb(rgb_l, rgb_r)
+                self._rgb = (rgb_l, rgb_r)
+            return self._aggregate_cross(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
         if colour_cost:
             if rgb_l is None or rgb_r is None:
                 raise ValueError("cost='adcensus' with colour 1 needs the colour images: pass rgb_l= and rgb_r=")
@@ -215,7 +241,7 @@ class PairPipeline:
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
         if self.cost and (cost_l is not None or cost_r is not None):
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
-        if self.aggregation:
+        if self.aggregation == "sgm":
             return self._aggregate_sgm(gray_l, gray_r, cost_l, cost_r)
         self.lib.smx_set_keys_fresh(1)
         try:
@@ -292,13 +318,27 @@ class PairPipeline:
         """The colour-guided flow: fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views
         (the caller's volumes, census, or the reference's cost) and smx_dev_cgf_wta_pair from them, which accumulates into
         the keys (and the neighbour / second-best states)."""
+        self._check_rgb(rgb_l, rgb_r)
+        self._aggregate_chunks(gray_l, gray_r, cost_l, cost_r, self.cgf_cost, self.lib.smx_dev_cgf_wta_pair, C.byref(self.params),
+                               rgb_l, rgb_r, int(rgb_l.shape[2]), self.cgf_ws, self.cgf_ws_bytes)
+
+    def _aggregate_cross(self, gray_l, gray_r, rgb_l, rgb_r, cost_l=None, cost_r=None):
+        """The cross-based flow: that of the colour guide with smx_dev_cross_wta_pair; the guide is the colour pair where it is
+        given, else the gray pair."""
+        gl, gr, ch = (rgb_l, rgb_r, int(rgb_l.shape[2])) if rgb_l is not None else (gray_l, gray_r, 1)
+        self._aggregate_chunks(gray_l, gray_r, cost_l, cost_r, self.cross_cost, self.lib.smx_dev_cross_wta_pair,
+                               C.byref(self.cross_params), gl, gr, ch, self.cross_ws, self.cross_ws_bytes)
+
+    def _aggregate_chunks(self, gray_l, gray_r, cost_l, cost_r, own_cost, entry, params, guide_l, guide_r, ch, ws, ws_bytes):
+        """Fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views (the caller's volumes, census /
+        AD-Census into self.census_cost, or the reference's cost into own_cost) and `entry` -- smx_dev_cgf_wta_pair or
+        smx_dev_cross_wta_pair -- from them, which accumulates into the keys (and the neighbour / second-best states)."""
         if (cost_l is None) != (cost_r is None):
             raise ValueError("pass both cost volumes or neither")
         if self.cost and cost_l is not None:
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
-        self._check_rgb(rgb_l, rgb_r)
         self._guide = gray_l
-        L, w, h, ch = self.lib, self.w, self.h, int(rgb_l.shape[2])
+        L, w, h = self.lib, self.w, self.h
         self.init_keys()
         if self.cost:
             P = C.byref(self.census_params)
@@ -316,14 +356,19 @@ class PairPipeline:
                     cl, cr = self.census_cost[0], self.census_cost[1]
                     self._code_cost(gray_l, gray_r, cl, cr, c0, c1, st)
                 else:
-                    cl, cr = self.cgf_cost[0], self.cgf_cost[1]
+                    cl, cr = own_cost[0], own_cost[1]
                     P = C.byref(self.params)
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, c0, c1, st))
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, c0, c1, st))
             whole = self.agg is None or self._agg_chunk is None
-            self._aggregate_call(L.smx_dev_cgf_wta_pair, _dp(rgb_l), _dp(rgb_r), ch, _dp(cl), _dp(cr), w, h, c0, c1,
-                                 _dp(self.keys), _dp(self.agg if whole else self._agg_chunk), _dp(self.nbr), _dp(self.uq),
-                                 _dp(self.cgf_ws), self.cgf_ws_bytes)
+            with self._on_device():
+                _lib.check(L.smx_set_max_slices_per_launch(sif))
+                try:
+                    _lib.check(entry(params, _dp(guide_l), _dp(guide_r), ch, _dp(cl), _dp(cr), w, h, c0, c1, _dp(self.keys),
+                                     _dp(self.agg if whole else self._agg_chunk), _dp(self.nbr), _dp(self.uq), _dp(ws), ws_bytes,
+                                     self._stream()))
+                finally:
+                    L.smx_set_max_slices_per_launch(0)
             if not whole:
                 # (the call wrote its two views c1 - c0 slices apart, whatever the buffer holds)
                 flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, h, w)
@@ -518,7 +563,7 @@ class PairPipeline:
     def check_status(self):
         """Raise if a workgroup of the fused aggregation gave up waiting for a neighbour."""
         torch.cuda.synchronize(self.device)
-        if self.aggregation or self.guidance:            # (the SGM and colour-guided kernels wait for nothing: no status word)
+        if self.aggregation or self.guidance:            # (the SGM, colour-guided and cross-based kernels wait for nothing)
             return
         with self._on_device():
             _lib.check(self.lib.smx_dev_agg_status(_dp(self.ws)))

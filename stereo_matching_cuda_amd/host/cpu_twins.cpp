@@ -12,6 +12,7 @@
 #include "adcensus.cuh"
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
+#include "crossAggregation.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "integral.cuh"
@@ -279,6 +280,80 @@ void colour_guided_filterOnCPU(const unsigned char* rgb, int channels, const flo
         }
         if (agg) std::memcpy(agg + (size_t)s * n, q.data(), n * sizeof(float));
         dispSelectOnCPU(q.data(), filter_cost, disp_map, (int)n, dmin + s);
+    }
+}
+
+// ---- crossAggregation.cuh (not in the reference) ------------------------------------------------
+// The definition of include/smx.h (above smx_cross_workspace_bytes) in scalar integer arithmetic: every arm walked step by
+// step, every sum taken pixel by pixel over the arm.
+namespace {
+int cross_dist(const unsigned char* a, const unsigned char* b, const int nc) {
+    int d = 0;
+    for (int c = 0; c < nc; ++c) d = std::max(d, std::abs((int)a[c] - (int)b[c]));
+    return d;
+}
+// the arm of pixel (x, y) in direction (dx, dy)
+int cross_arm(const unsigned char* g, const int ch, const int nc, const int w, const int h, const int x, const int y,
+              const int dx, const int dy, const smx_cross_params& p) {
+    const unsigned char* pp = g + ((size_t)y * w + x) * ch;
+    const unsigned char* prev = pp;
+    int k = 0;
+    for (int j = 1; j <= p.l1; ++j) {
+        const int qx = x + j * dx, qy = y + j * dy;
+        if (qx < 0 || qx >= w || qy < 0 || qy >= h) break;
+        const unsigned char* q = g + ((size_t)qy * w + qx) * ch;
+        const int dp = cross_dist(q, pp, nc);
+        if (!(dp < p.tau1 && cross_dist(q, prev, nc) < p.tau1 && (j <= p.l2 || dp < p.tau2))) break;
+        k = j;
+        prev = q;
+    }
+    return k;
+}
+// out = the sums of in over the horizontal (vertical == false) or vertical arm of every pixel
+void cross_pass(const vector<uint32_t>& in, vector<uint32_t>& out, const vector<int>* arm, const int w, const int h,
+                const bool vertical) {
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t id = (size_t)y * w + x;
+            uint32_t s = 0;
+            if (vertical) for (int yy = y - arm[2][id]; yy <= y + arm[3][id]; ++yy) s += in[(size_t)yy * w + x];
+            else for (int xx = x - arm[0][id]; xx <= x + arm[1][id]; ++xx) s += in[(size_t)y * w + xx];
+            out[id] = s;
+        }
+}
+}  // namespace
+
+void cross_aggregateOnCPU(const unsigned char* guide, int channels, const float* cost, float* filter_cost, float* disp_map,
+                          float* agg, const int w, const int h, const int size_d, const int dmin, const smx_cross_params& p) {
+    const size_t n = (size_t)w * h;
+    const int nc = channels == 1 ? 1 : 3;
+    static const int dir[4][2] = {{-1, 0}, {1, 0}, {0, -1}, {0, 1}};       // left, right, up, down
+    vector<int> arm[4];
+    for (int e = 0; e < 4; ++e) {
+        arm[e].resize(n);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) arm[e][(size_t)y * w + x] = cross_arm(guide, channels, nc, w, h, x, y, dir[e][0], dir[e][1], p);
+    }
+    // the areas of the two orders: the same sums of 1
+    vector<uint32_t> one(n, 1u), t(n), area[2], v(n), s(n);
+    for (int order = 0; order < 2; ++order) {
+        area[order].resize(n);
+        cross_pass(one, t, arm, w, h, order == 1);
+        cross_pass(t, area[order], arm, w, h, order == 0);
+    }
+    vector<float> q(n);
+    for (int z = 0; z < size_d; ++z) {
+        const float* c = cost + (size_t)z * n;
+        for (size_t k = 0; k < n; ++k) v[k] = 16u * (c[k] >= 0.0f ? (c[k] <= 255.0f ? (uint32_t)(int)c[k] : 255u) : 0u);
+        for (int i = 0; i < p.iterations; ++i) {
+            const int order = i & 1;
+            cross_pass(v, t, arm, w, h, order == 1);
+            cross_pass(t, s, arm, w, h, order == 0);
+            for (size_t k = 0; k < n; ++k) v[k] = (2u * s[k] + area[order][k]) / (2u * area[order][k]);
+        }
+        for (size_t k = 0; k < n; ++k) q[k] = (float)v[k] * 0.0625f;
+        if (agg) std::memcpy(agg + (size_t)z * n, q.data(), n * sizeof(float));
+        dispSelectOnCPU(q.data(), filter_cost, disp_map, (int)n, dmin + z);
     }
 }
 

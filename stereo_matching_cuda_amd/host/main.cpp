@@ -65,6 +65,14 @@
 //                     CPU twin (colour_guided_filterOnCPU) redoes both views from the cost volumes and check_errors
 //                     compares.  Composes with --cost census, --subpixel, --uniqueness, --speckle, --wmf, --pfm and --png16;
 //                     not with --aggregation sgm, --ngpu or --pipeline
+//   --aggregation cross  cross-based aggregation instead of the guided filter (smx_ctx_set_cross, smx_ctx_stereo_pair_rgb; not in
+//                     the reference; implies --fused): colour-adaptive support regions whose guide is the colour pair.  The same
+//                     twelve images, the two mean images empty.  --cross-arms L1,L2 gives the arm lengths (1 <= L1 <= 63,
+//                     0 <= L2 <= L1; default 34,17), --cross-tau T1,T2 the colour thresholds (1 <= T2 <= T1 <= 256; default
+//                     20,6), --cross-iterations N the iterations (1 .. 4; default 4).  With --host-compare the CPU twin
+//                     (cross_aggregateOnCPU) redoes both views from the cost volumes and check_errors compares.  Composes with
+//                     --cost census / adcensus, --subpixel, --uniqueness, --speckle, --wmf, --pfm and --png16; not with
+//                     --guidance rgb, --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -92,6 +100,7 @@
 #include "occlusion.cuh"
 #include "png_io.h"
 #include "rgb_to_grayscale.cuh"
+#include "crossAggregation.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
 #include "uniqueness.cuh"
@@ -127,6 +136,8 @@ struct Options {
     smx_adcensus_params adc_params;     // (its census part is filled from census_params after the parse)
     bool sgm = false;        // --aggregation sgm
     smx_sgm_params sgm_params;
+    bool cross = false;      // --aggregation cross
+    smx_cross_params cross_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
     bool rgb = false;        // --guidance rgb
@@ -143,7 +154,9 @@ Options parse(int argc, char** argv) {
     smx_default_census_params(&o.census_params);
     smx_default_speckle_params(&o.speckle_params);
     smx_default_sgm_params(&o.sgm_params);
+    smx_default_cross_params(&o.cross_params);
     bool sgm_option = false;        // --sgm-p / --sgm-paths seen
+    bool cross_option = false;      // --cross-arms / --cross-tau / --cross-iterations seen
     bool census_option = false;     // --census-window / --census-th seen
     bool adcensus_option = false;   // --adcensus-lambda / --adcensus-scale / --ad seen
     smx_default_adcensus_params(&o.adc_params);
@@ -249,10 +262,47 @@ Options parse(int argc, char** argv) {
             std::string v;
             value(v);
             o.sgm = v == "sgm";
-            if (o.ok && !o.sgm && v != "guided") {
-                std::fprintf(stderr, "--aggregation needs `guided` or `sgm`, not `%s`\n", v.c_str());
+            o.cross = v == "cross";
+            if (o.ok && !o.sgm && !o.cross && v != "guided") {
+                std::fprintf(stderr, "--aggregation needs `guided`, `sgm` or `cross`, not `%s`\n", v.c_str());
                 o.ok = false;
             }
+        }
+        else if (a == "--cross-arms") {
+            std::string v;
+            value(v);
+            int l1 = -1, l2 = -1;
+            char comma = 0, rest = 0;
+            cross_option = true;
+            if (o.ok && (std::sscanf(v.c_str(), "%d%c%d%c", &l1, &comma, &l2, &rest) != 3 || comma != ',' || l1 < 1 || l1 > 63 ||
+                         l2 < 0 || l2 > l1)) {
+                std::fprintf(stderr, "--cross-arms needs L1,L2 with 1 <= L1 <= 63 and 0 <= L2 <= L1, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.cross_params.l1 = l1; o.cross_params.l2 = l2;
+        }
+        else if (a == "--cross-tau") {
+            std::string v;
+            value(v);
+            int t1 = -1, t2 = -1;
+            char comma = 0, rest = 0;
+            cross_option = true;
+            if (o.ok && (std::sscanf(v.c_str(), "%d%c%d%c", &t1, &comma, &t2, &rest) != 3 || comma != ',' || t2 < 1 || t2 > t1 ||
+                         t1 > 256)) {
+                std::fprintf(stderr, "--cross-tau needs T1,T2 with 1 <= T2 <= T1 <= 256, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.cross_params.tau1 = t1; o.cross_params.tau2 = t2;
+        }
+        else if (a == "--cross-iterations") {
+            std::string v;
+            value(v);
+            cross_option = true;
+            if (o.ok && v != "1" && v != "2" && v != "3" && v != "4") {
+                std::fprintf(stderr, "--cross-iterations needs 1, 2, 3 or 4, not `%s`\n", v.c_str());
+                o.ok = false;
+            }
+            o.cross_params.iterations = o.ok ? v[0] - '0' : 0;
         }
         else if (a == "--sgm-p") {
             std::string v;
@@ -334,6 +384,10 @@ Options parse(int argc, char** argv) {
         std::fprintf(stderr, "--sgm-p and --sgm-paths need --aggregation sgm\n");
         o.ok = false;
     }
+    if (o.ok && cross_option && !o.cross) {
+        std::fprintf(stderr, "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross\n");
+        o.ok = false;
+    }
     return o;
 }
 
@@ -378,6 +432,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--guidance rgb cannot be combined with --aggregation sgm, --ngpu or --pipeline\n");
         return 2;
     }
+    if (opt.cross && (opt.rgb || opt.ngpu != 0 || opt.pipeline)) {
+        std::fprintf(stderr, "--aggregation cross cannot be combined with --guidance rgb, --ngpu or --pipeline\n");
+        return 2;
+    }
     if (opt.census && (opt.ngpu != 0 || opt.pipeline)) {
         std::fprintf(stderr, "--cost census cannot be combined with --ngpu or --pipeline\n");
         return 2;
@@ -420,7 +478,7 @@ int main(int argc, char** argv) {
         }
     }
     const bool uniq = opt.uniqueness > 0.0f;
-    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb;
+    const bool fused = opt.fused || sh_create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb || opt.cross;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -436,8 +494,9 @@ int main(int argc, char** argv) {
         return 1;
     }
     const int w = in.w, h = in.h, n = w * h;
-    if ((opt.rgb || opt.ad_rgb) && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
-        std::fprintf(stderr, "%s needs two images of 3 or of 4 channels, not %d and %d\n", opt.rgb ? "--guidance rgb" : "--ad rgb",
+    if ((opt.rgb || opt.ad_rgb || opt.cross) && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
+        std::fprintf(stderr, "%s needs two images of 3 or of 4 channels, not %d and %d\n",
+                     opt.rgb ? "--guidance rgb" : opt.cross ? "--aggregation cross" : "--ad rgb",
                      in.channels[0], in.channels[1]);
         return 1;
     }
@@ -511,7 +570,8 @@ int main(int argc, char** argv) {
         std::memset(&out, 0, sizeof(out));
         out.best_l = best[0].data(); out.best_r = best[1].data();
         out.dmap_l = dmap[0].data(); out.dmap_r = dmap[1].data();
-        if (!opt.sgm && !opt.rgb) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }     // (SGM and the colour guide have no mean images)
+        // (SGM, the colour guide and cross-based aggregation have no mean images)
+        if (!opt.sgm && !opt.rgb && !opt.cross) { out.mean_l = mean[0].data(); out.mean_r = mean[1].data(); }
         out.occlusion = occlusion.data(); out.filled = filled.data();
         std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness twin reads
         if (uniq && host_compare) {
@@ -530,10 +590,11 @@ int main(int argc, char** argv) {
         if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
         if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
         if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
+        if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
         if (!sh_create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
         auto run_pair = [&]() {
             return sh_create ? sh_run(sctx, gray[0], gray[1], dmin[0], dmin[1], &out)
-                   : opt.rgb || opt.ad_rgb ? smx_ctx_stereo_pair_rgb(ctx, in.rgb[0], in.rgb[1], in.channels[0], dmin[0], dmin[1], &out)
+                   : opt.rgb || opt.ad_rgb || opt.cross ? smx_ctx_stereo_pair_rgb(ctx, in.rgb[0], in.rgb[1], in.channels[0], dmin[0], dmin[1], &out)
                              : smx_ctx_stereo_pair(ctx, gray[0], gray[1], dmin[0], dmin[1], &out);
         };
         CHECK(run_pair());
@@ -609,6 +670,23 @@ int main(int argc, char** argv) {
                 ok = check_errors(td.data(), dmap[v].data(), n) && ok;
             }
             if (ok) std::cout << "Colour guided filter ok!" << std::endl;
+        }
+        if (host_compare && opt.cross) {
+            // the twin redoes both views from whole cost volumes built by the stage wrappers, from the reference's presets
+            bool ok = true;
+            for (int v = 0; v < 2; ++v) {
+                std::vector<float> vol((size_t)n * size_d), tb(n), td(n, 0.0f);
+                std::memset(tb.data(), 0x7F, sizeof(float) * n);
+                if (opt.adcensus)
+                    compute_adcensus_cost(ad_img[v], ad_img[1 - v], ad_ch, vol.data(), w, h, size_d, dmin[v], opt.adc_params, false);
+                else if (opt.census) compute_census_cost(gray[v], gray[1 - v], vol.data(), w, h, size_d, dmin[v], opt.census_params);
+                else CHECK(smx_compute_cost(&smx_config().params, gray[v], gray[1 - v], vol.data(), w, w, h, h, size_d, dmin[v]));
+                cross_aggregateOnCPU(in.rgb[v], in.channels[v], vol.data(), tb.data(), td.data(), nullptr, w, h, size_d, dmin[v],
+                                     opt.cross_params);
+                ok = check_errors(tb.data(), best[v].data(), n) && ok;
+                ok = check_errors(td.data(), dmap[v].data(), n) && ok;
+            }
+            if (ok) std::cout << "Cross-based aggregation ok!" << std::endl;
         }
         if (host_compare) {
             std::vector<float> lr(dmap[0]);

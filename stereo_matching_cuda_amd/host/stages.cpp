@@ -4,6 +4,7 @@
 #include "adcensus.cuh"
 #include "census.cuh"
 #include "costVolume.cuh"
+#include "crossAggregation.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
@@ -193,6 +194,25 @@ void compute_colour_guided_filter(unsigned char* rgb, int channels, float* cost,
         ok = check_errors(td.data(), disp_map, w * h) && ok;
         if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
         if (ok) cout << "Colour guided filter ok!" << endl;
+    }
+}
+
+// not in the reference: cross-based aggregation instead of the guided filter (smx_main --aggregation cross)
+void cross_aggregate(unsigned char* guide, int channels, float* cost, float* filter_cost, float* disp_map, float* agg,
+                     const int w, const int h, const int size_d, const int dmin, const smx_cross_params& p, bool host_gpu_compare) {
+    std::vector<float> tb, td;
+    if (host_gpu_compare) {            // (filter_cost / disp_map are IN/OUT: the twin starts from what the GPU starts from)
+        tb.assign(filter_cost, filter_cost + (size_t)w * h);
+        td.assign(disp_map, disp_map + (size_t)w * h);
+    }
+    CHECK(smx_cross_aggregate(&p, guide, channels, cost, filter_cost, disp_map, agg, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        std::vector<float> ta(agg ? (size_t)w * h * size_d : 0);
+        cross_aggregateOnCPU(guide, channels, cost, tb.data(), td.data(), agg ? ta.data() : nullptr, w, h, size_d, dmin, p);
+        bool ok = check_errors(tb.data(), filter_cost, w * h);
+        ok = check_errors(td.data(), disp_map, w * h) && ok;
+        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
+        if (ok) cout << "Cross-based aggregation ok!" << endl;
     }
 }
 

@@ -127,6 +127,29 @@ def colour_guided_filter(rgb, cost, filter_cost, disp_map, dmin, want_agg=False,
     return agg
 
 
+def cross_aggregate(guide, cost, filter_cost, disp_map, dmin, want_agg=False, params=None):
+    """Cross-based aggregation + WTA (smx_cross_aggregate; not a stage of the reference): guide is the (h, w) gray or
+    (h, w, 3 or 4) colour uint8 guide, params a CrossParams (None = the defaults).  filter_cost/disp_map are updated IN PLACE
+    like compute_guided_filter's; returns agg or None."""
+    guide, cost = _c(guide, np.uint8), _c(cost, np.float32)
+    if guide.ndim == 2:
+        guide = guide[:, :, None]
+    if guide.ndim != 3 or guide.shape[2] not in (1, 3, 4):
+        raise ValueError("cross_aggregate expects an (h, w) or (h, w, 1, 3 or 4) uint8 guide")
+    h, w, ch = guide.shape
+    size_d = cost.shape[0]
+    if cost.shape != (size_d, h, w):
+        raise ValueError("cost must be (size_d, h, w)")
+    for a in (filter_cost, disp_map):
+        if a.dtype != np.float32 or a.shape != (h, w) or not a.flags.c_contiguous:
+            raise ValueError("filter_cost/disp_map must be C-contiguous float32 (h, w) arrays")
+    p = params if params is not None else _lib.default_cross_params()
+    agg = np.empty((size_d, h, w), np.float32) if want_agg else None
+    _lib.check(_lib.lib().smx_cross_aggregate(
+        C.byref(p), _ptr(guide), ch, _ptr(cost), _ptr(filter_cost), _ptr(disp_map), _ptr(agg), w, h, size_d, dmin))
+    return agg
+
+
 def detect_occlusion(disparity_left, disparity_right, d_occlusion, params=None):
     """LR consistency check; returns the updated copy of disparity_left.  occlusion.cu:17-85."""
     dl = _c(disparity_left, np.float32).copy()
