@@ -304,6 +304,8 @@ int smx_last_agg_path(void);
  * iteration; the fused walker handles as many per launch as the caller's workspace holds, and accumulates the running WTA
  * across launches.  smx_set_max_slices_per_launch(n > 0) bounds that number for the calling thread's calls whatever the
  * workspace holds (0 = no bound, the default) -- the knob behind `slices_in_flight` of the Python pipeline and bench.py.
+ * It also bounds the chunks in which a context's pair call (smx_ctx_stereo_pair[_rgb]) walks the slices with the census or
+ * AD-Census cost, colour guidance or cross-based aggregation on; no chunking changes a bit.
  * smx_last_agg_chunk reports what the calling thread's last fused aggregation did: slices per walker launch (of the first,
  * i.e. largest, launch) and the number of walker launches. */
 int smx_set_max_slices_per_launch(int n);

@@ -45,8 +45,9 @@ bool uniq_ratio_ok(float ratio);
 bool speckle_shape_ok(int w, int h);
 bool sgm_params_ok(const smx_sgm_params* p);
 bool sgm_shape_ok(int w, int h, int size_d);
-bool cross_params_ok(const smx_cross_params* p);
+bool cross_params_ok(const smx_cross_params* p);       // (smx_cross.hip, beside the limits of its kernels)
 bool cross_shape_ok(int w, int h);
+constexpr const char* CROSS_RANGES = "needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and 1 <= iterations <= 4";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

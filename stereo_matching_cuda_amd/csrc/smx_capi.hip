@@ -707,6 +707,42 @@ int smx_dev_cgf_wta_pair(const smx_params* p, const uint8_t* d_rgb_l, const uint
                                d_uq, d_ws, chunk, (hipStream_t)stream);
 }
 
+// ---- cross-based aggregation (not in the reference; smx_cross.hip) ---------------------------------------------------
+void smx_default_cross_params(smx_cross_params* p) {
+    if (!p) return;
+    p->l1 = 34; p->l2 = 17; p->tau1 = 20; p->tau2 = 6; p->iterations = 4;
+}
+
+size_t smx_cross_workspace_bytes(int w, int h, int nslices, int nviews) {
+    return cross_shape_ok(w, h) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cross_workspace_bytes(w, h, nslices, nviews) : 0;
+}
+
+int smx_dev_cross_arms(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels, int w, int h,
+                       uint32_t* d_arms, void* stream) {
+    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_arms: %s", CROSS_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_arms: needs w, h >= 1 and w*h < 2^31");
+    SMX_ARG((d_guide_l || d_guide_r) && d_arms);
+    return launch_cross_arms(p, d_guide_l, d_guide_r, channels, w, h, d_arms, (hipStream_t)stream);
+}
+
+int smx_dev_cross_wta_pair(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
+                           const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
+                           float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: %s", CROSS_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: needs w, h >= 1 and w*h < 2^31");
+    SMX_ARG(s_begin >= 0 && s_end > s_begin && d_keys);
+    SMX_ARG((d_cost_l || d_cost_r) && !d_guide_l == !d_cost_l && !d_guide_r == !d_cost_r);
+    const int nviews = d_cost_l && d_cost_r ? 2 : 1;
+    const int chunk = d_ws ? cross_chunk(w, h, nviews, ws_bytes, s_end - s_begin, g_max_chunk) : 0;
+    if (chunk < 1)
+        return fail(SMX_E_WS, "smx_dev_cross_wta_pair: workspace of %zu bytes, %zu needed for one slice in flight",
+                    d_ws ? ws_bytes : (size_t)0, cross_workspace_bytes(w, h, 1, nviews));
+    return launch_cross_wta_pair(p, d_guide_l, d_guide_r, channels, d_cost_l, d_cost_r, w, h, s_begin, s_end, d_keys, d_agg,
+                                 d_nbr, d_uq, d_ws, chunk, (hipStream_t)stream);
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);

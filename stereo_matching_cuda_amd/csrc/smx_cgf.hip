@@ -307,23 +307,13 @@ int launch_cgf_wta_pair(const smx_params* p, const uint8_t* rgb_l, const uint8_t
                         float* uq, void* ws, int chunk, hipStream_t st) {
     const int64_t n = (int64_t)w * h;
     const int count = s_end - s_begin, R = p->radius;
-    const bool both = cost_l && cost_r;
     CgfViews v = {};
-    int V = 0;
+    const ViewSlots s = view_slots(cost_l, cost_r, keys, agg, nbr, uq, count, n);
+    const int V = s.V;
     const uint8_t* rgbs[2] = {rgb_l, rgb_r};
     const float* costs[2] = {cost_l, cost_r};
-    for (int view = 0; view < 2; ++view) {
-        if (!costs[view]) continue;
-        // with both views the outputs hold the left view first; the one-view form has the one view at the front
-        const int slot = both ? view : 0;
-        v.rgb[V] = rgbs[view];
-        v.cost[V] = costs[view];
-        v.keys[V] = keys + slot * n;
-        v.agg[V] = agg ? agg + (int64_t)slot * count * n : nullptr;
-        v.nbr[V] = nbr ? nbr + (int64_t)slot * 3 * n : nullptr;
-        v.uq[V] = uq ? uq + (int64_t)slot * 3 * n : nullptr;
-        ++V;
-    }
+    s.put(v);
+    for (int k = 0; k < V; ++k) { v.rgb[k] = rgbs[s.view[k]]; v.cost[k] = costs[s.view[k]]; }
     float* G = reinterpret_cast<float*>(align_up((size_t)ws, 256));
     float* W = G + (int64_t)V * 9 * n;
     const dim3 b256(256), bscan(64 * CGF_NP);

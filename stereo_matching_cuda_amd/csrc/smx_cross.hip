@@ -299,26 +299,13 @@ int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, con
                           float* uq, void* ws, int chunk, hipStream_t st) {
     const int64_t n = (int64_t)w * h;
     const int count = s_end - s_begin, l1 = p->l1;
-    const bool both = cost_l && cost_r;
+    const ViewSlots s = view_slots(cost_l, cost_r, keys, agg, nbr, uq, count, n);
+    const int V = s.V;
     const uint8_t* guide[2] = {};
     const float* cost[2] = {};
-    int64_t* vkeys[2] = {};
-    float *vagg[2] = {}, *vnbr[2] = {}, *vuq[2] = {};
-    int V = 0;
     const uint8_t* guides[2] = {guide_l, guide_r};
     const float* costs[2] = {cost_l, cost_r};
-    for (int view = 0; view < 2; ++view) {
-        if (!costs[view]) continue;
-        // with both views the outputs hold the left view first; the one-view form has the one view at the front
-        const int slot = both ? view : 0;
-        guide[V] = guides[view];
-        cost[V] = costs[view];
-        vkeys[V] = keys + slot * n;
-        vagg[V] = agg ? agg + (int64_t)slot * count * n : nullptr;
-        vnbr[V] = nbr ? nbr + (int64_t)slot * 3 * n : nullptr;
-        vuq[V] = uq ? uq + (int64_t)slot * 3 * n : nullptr;
-        ++V;
-    }
+    for (int k = 0; k < V; ++k) { guide[k] = guides[s.view[k]]; cost[k] = costs[s.view[k]]; }
     uint8_t* base = reinterpret_cast<uint8_t*>(align_up((size_t)ws, 256));
     uint32_t* ARMS = reinterpret_cast<uint32_t*>(base);
     uint16_t* AREA = reinterpret_cast<uint16_t*>(base + (size_t)V * 4 * n);
@@ -346,7 +333,7 @@ int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, con
     for (int z0 = 0; z0 < count; z0 += chunk) {
         const int c = count - z0 < chunk ? count - z0 : chunk;
         const float* q[2] = {};
-        for (int k = 0; k < V; ++k) q[k] = vagg[k] ? vagg[k] + (int64_t)z0 * n : Q + (int64_t)k * c * n;
+        for (int k = 0; k < V; ++k) q[k] = s.agg[k] ? s.agg[k] + (int64_t)z0 * n : Q + (int64_t)k * c * n;
         for (int i = 0; i < p->iterations; ++i) {
             const int order = i & 1;
             const bool last = i + 1 == p->iterations;
@@ -366,7 +353,7 @@ int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, con
             }
             if (int rc = launch_two_pass(order, first, second, ARMS, V, c, w, h, l1, st)) return rc;
         }
-        if (int rc = wta_launch(WTA_NATURAL, V, q, vkeys, nbr ? vnbr : nullptr, uq ? vuq : nullptr, w, h, (size_t)n, c,
+        if (int rc = wta_launch(WTA_NATURAL, V, q, s.keys, nbr ? s.nbr : nullptr, uq ? s.uq : nullptr, w, h, (size_t)n, c,
                                 s_begin + z0, nullptr, 0, false, st))
             return rc;
     }
@@ -374,78 +361,3 @@ int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, con
 }
 
 }  // namespace smx
-
-using namespace smx;
-
-extern "C" {
-
-void smx_default_cross_params(smx_cross_params* p) {
-    if (!p) return;
-    p->l1 = 34; p->l2 = 17; p->tau1 = 20; p->tau2 = 6; p->iterations = 4;
-}
-
-size_t smx_cross_workspace_bytes(int w, int h, int nslices, int nviews) {
-    return cross_shape_ok(w, h) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cross_workspace_bytes(w, h, nslices, nviews) : 0;
-}
-
-static const char* const CROSS_RANGES = "needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and 1 <= iterations <= 4";
-
-int smx_dev_cross_arms(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels, int w, int h,
-                       uint32_t* d_arms, void* stream) {
-    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_arms: %s", CROSS_RANGES);
-    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_arms: needs w, h >= 1 and w*h < 2^31");
-    SMX_ARG((d_guide_l || d_guide_r) && d_arms);
-    return launch_cross_arms(p, d_guide_l, d_guide_r, channels, w, h, d_arms, (hipStream_t)stream);
-}
-
-int smx_dev_cross_wta_pair(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
-                           const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
-                           float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
-    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: %s", CROSS_RANGES);
-    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: needs w, h >= 1 and w*h < 2^31");
-    SMX_ARG(s_begin >= 0 && s_end > s_begin && d_keys);
-    SMX_ARG((d_cost_l || d_cost_r) && !d_guide_l == !d_cost_l && !d_guide_r == !d_cost_r);
-    const int nviews = d_cost_l && d_cost_r ? 2 : 1;
-    const int chunk = d_ws ? cross_chunk(w, h, nviews, ws_bytes, s_end - s_begin, thread_max_chunk()) : 0;
-    if (chunk < 1)
-        return fail(SMX_E_WS, "smx_dev_cross_wta_pair: workspace of %zu bytes, %zu needed for one slice in flight",
-                    d_ws ? ws_bytes : (size_t)0, cross_workspace_bytes(w, h, 1, nviews));
-    return launch_cross_wta_pair(p, d_guide_l, d_guide_r, channels, d_cost_l, d_cost_r, w, h, s_begin, s_end, d_keys, d_agg,
-                                 d_nbr, d_uq, d_ws, chunk, (hipStream_t)stream);
-}
-
-int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int channels, const float* cost, float* filter_cost,
-                        float* disp_map, float* agg, int w, int h, int size_d, int dmin) {
-    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_cross_aggregate: %s", CROSS_RANGES);
-    SMX_ARG(guide && cost && filter_cost && disp_map && size_d >= 1);
-    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_cross_aggregate: needs w, h >= 1 and w*h < 2^31");
-    const size_t n = (size_t)w * h, fb = n * sizeof(float), vb = fb * size_d;
-    // every slice in flight, but at most ~2 GiB of them
-    const size_t one = cross_workspace_bytes(w, h, 1, 1), all = cross_workspace_bytes(w, h, size_d, 1), cap = (size_t)2 << 30;
-    const size_t ws_bytes = all <= cap ? all : one > cap ? one : cap;
-    DevBuf dI, dC, dBest, dMap, dKeys, dAgg, ws;
-    SMX_HIP(dI.upload(guide, n * channels));
-    SMX_HIP(dC.upload(cost, vb));
-    SMX_HIP(dBest.upload(filter_cost, fb));
-    SMX_HIP(dMap.upload(disp_map, fb));
-    SMX_HIP(dKeys.ensure(n * sizeof(int64_t)));
-    if (agg) SMX_HIP(dAgg.ensure(vb));
-    SMX_HIP(ws.ensure(ws_bytes));
-    int rc;
-    if ((rc = smx_dev_init_keys(dKeys.as<int64_t>(), (int64_t)n, nullptr))) return rc;
-    if ((rc = smx_dev_cross_wta_pair(p, dI.as<uint8_t>(), nullptr, channels, dC.as<float>(), nullptr, w, h, 0, size_d,
-                                     dKeys.as<int64_t>(), agg ? dAgg.as<float>() : nullptr, nullptr, nullptr, ws.p, ws_bytes,
-                                     nullptr)))
-        return rc;
-    if ((rc = smx_dev_apply_keys(dKeys.as<int64_t>(), (int64_t)n, dmin, dBest.as<float>(), dMap.as<float>(), nullptr))) return rc;
-    SMX_HIP(hipDeviceSynchronize());
-    SMX_HIP(dBest.download(filter_cost, fb));
-    SMX_HIP(dMap.download(disp_map, fb));
-    if (agg) SMX_HIP(dAgg.download(agg, vb));
-    return SMX_OK;
-}
-
-}  // extern "C"

@@ -23,13 +23,12 @@ struct smx_ctx {
     int subpix = 0;
     bool sub_valid = false;     // the maps belong to the last synchronous pair
     DevBuf nbr, sub, subf;
-    // census cost (smx_ctx_set_cost): the codes [2][h][w]; without whole volumes, one chunk of both views [2][census_chunk][h][w]
+    // census cost (smx_ctx_set_cost): the codes [2][h][w]
     int cost_mode = SMX_COST_REFERENCE;
     smx_census_params census;
-    int census_chunk = 0;
-    DevBuf codes, ccost;
-    // AD-Census cost (smx_ctx_set_adcensus): it takes the place of the census cost in every flow, with the same codes and chunk
-    // buffers, and its table on the device
+    DevBuf codes;
+    // AD-Census cost (smx_ctx_set_adcensus): it takes the place of the census cost in every flow, with the same codes, and its
+    // table on the device
     bool adcensus = false;
     bool adc_tab_valid = false; // the device table holds the tables of `adc`
     smx_adcensus_params adc;
@@ -39,27 +38,27 @@ struct smx_ctx {
     bool spk_valid = false;     // the map belongs to the last synchronous pair
     smx_speckle_params spk_params;
     DevBuf spk, spk_ws;
-    // semi-global matching (smx_ctx_set_aggregation): its workspace for both views; it reads the whole volumes costL / costR
+    // semi-global matching (smx_ctx_set_aggregation): it reads the whole volumes costL / costR
     int agg_mode = SMX_AGG_GUIDED;
     smx_sgm_params sgm;
-    DevBuf sgm_ws;
     // uniqueness filtering (smx_ctx_set_uniqueness): the state [2][3][h][w], the filtered left map and the margins [h][w]
     float uniq = 0.0f;          // the ratio; 0 = off
     bool uq_valid = false;      // the maps belong to the last synchronous pair
     DevBuf uq, uq_map, uq_margin;
-    // colour guidance (smx_ctx_set_guidance): the two colour images [2][h][w][4], the colour-guided filter's workspace for both
-    // views and, without whole volumes, one chunk of both views' cost slices [2][cgf_chunk][h][w]
+    // colour guidance (smx_ctx_set_guidance): the two colour images [2][h][w][4]
     int guide_mode = SMX_GUIDE_GRAY;
-    int cgf_chunk = 0;
-    size_t cgf_ws_bytes = 0;
-    DevBuf rgb, cgf_ws, cgf_cost;
-    // cross-based aggregation (smx_ctx_set_cross): its workspace for both views and, without whole volumes, one chunk of both
-    // views' cost slices [2][cross_chunk][h][w]
+    DevBuf rgb;
+    // cross-based aggregation (smx_ctx_set_cross)
     bool cross = false;
     smx_cross_params cross_params;
-    int cross_chunk = 0;
-    size_t cross_ws_bytes = 0;
-    DevBuf cross_ws, cross_cost;
+    // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
+    // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
+    // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
+    // slices ctx_aggregate_chunks takes at a time; chunk_cost: without whole volumes, one chunk of both views' cost slices
+    // [2][chunk][h][w].
+    int chunk = 0;
+    size_t mode_ws_bytes = 0;
+    DevBuf mode_ws, chunk_cost;
     // pipelined entry: two slots of device inputs / results and pinned staging, created on first use.  Staging of a slot:
     // [gray_l | gray_r] going up; [best_l best_r dmap_l dmap_r occlusion filled | mean_l mean_r | status word] coming down.
     struct Slot {
@@ -90,40 +89,38 @@ struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cros
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
+// The most slices in flight whose workspace for both views -- and chunk of cost slices, without whole volumes -- stay within
+// ~2 GiB, by halving
+static int halved_chunk(const smx_ctx* c, size_t (*ws_bytes)(int, int, int, int), bool whole) {
+    const size_t cap = (size_t)2 << 30, fb = c->n * sizeof(float);
+    int k = c->size_d;
+    while (k > 1 && ws_bytes(c->w, c->h, k, 2) + (whole ? 0 : 2 * (size_t)k * fb) > cap) k = (k + 1) / 2;
+    return k;
+}
+
 // Every buffer `need` asks for, each under its own guard: after a failed allocation the next call simply retries.
 static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     const size_t fb = c->n * sizeof(float), vb = fb * c->size_d;
-    if (need.sgm) SMX_HIP(c->sgm_ws.ensure(sgm_workspace_bytes(c->w, c->h, c->size_d, 2)));
     if (need.cost) { SMX_HIP(c->costL.ensure(vb)); SMX_HIP(c->costR.ensure(vb)); }
     if (need.agg) SMX_HIP(c->aggLR.ensure(2 * vb));
     if (need.subpix) { SMX_HIP(c->nbr.ensure(6 * fb)); SMX_HIP(c->sub.ensure(2 * fb)); SMX_HIP(c->subf.ensure(fb)); }
     if (need.census) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
-    if (need.census && !need.cost) {
-        const size_t fit = ((size_t)1 << 30) / (2 * fb);     // the chunk's two cost buffers: at most 1 GiB, at least one slice
-        c->census_chunk = (int)(fit < 1 ? 1 : fit > (size_t)c->size_d ? (size_t)c->size_d : fit);
-        SMX_HIP(c->ccost.ensure(2 * (size_t)c->census_chunk * fb));
-    }
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
     if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
-    if (need.cgf) {
-        // the most slices in flight whose workspace (and chunk of cost slices, without whole volumes) stay within ~2 GiB
-        const size_t cap = (size_t)2 << 30;
-        int k = c->size_d;
-        while (k > 1 && cgf_workspace_bytes(c->w, c->h, k, 2) + (need.cost ? 0 : 2 * (size_t)k * fb) > cap) k = (k + 1) / 2;
-        c->cgf_chunk = k;
-        c->cgf_ws_bytes = cgf_workspace_bytes(c->w, c->h, k, 2);
-        SMX_HIP(c->cgf_ws.ensure(c->cgf_ws_bytes));
-        if (!need.cost) SMX_HIP(c->cgf_cost.ensure(2 * (size_t)k * fb));
+    // The chunk of ctx_aggregate_chunks.  Colour guide and cross: the halving rule on their workspace.  The guided flow from
+    // census codes: every slice with whole volumes, else what fits 1 GiB of cost slices exactly (at least one).  Then the
+    // calling thread's smx_set_max_slices_per_launch bounds it, like the chunks inside every entry.
+    size_t (*const mode_bytes)(int, int, int, int) = need.cgf ? cgf_workspace_bytes : need.cross ? cross_workspace_bytes : nullptr;
+    c->chunk = c->size_d;
+    if (mode_bytes) c->chunk = halved_chunk(c, mode_bytes, need.cost);
+    else if (need.census && !need.cost) {
+        const size_t fit = ((size_t)1 << 30) / (2 * fb);
+        c->chunk = (int)(fit < 1 ? 1 : fit > (size_t)c->size_d ? (size_t)c->size_d : fit);
     }
-    if (need.cross) {
-        const size_t cap = (size_t)2 << 30;
-        int k = c->size_d;
-        while (k > 1 && cross_workspace_bytes(c->w, c->h, k, 2) + (need.cost ? 0 : 2 * (size_t)k * fb) > cap) k = (k + 1) / 2;
-        c->cross_chunk = k;
-        c->cross_ws_bytes = cross_workspace_bytes(c->w, c->h, k, 2);
-        SMX_HIP(c->cross_ws.ensure(c->cross_ws_bytes));
-        if (!need.cost) SMX_HIP(c->cross_cost.ensure(2 * (size_t)k * fb));
-    }
+    if (const int bound = thread_max_chunk(); bound > 0 && bound < c->chunk) c->chunk = bound;
+    c->mode_ws_bytes = need.sgm ? sgm_workspace_bytes(c->w, c->h, c->size_d, 2) : mode_bytes ? mode_bytes(c->w, c->h, c->chunk, 2) : 0;
+    if (c->mode_ws_bytes) SMX_HIP(c->mode_ws.ensure(c->mode_ws_bytes));
+    if ((mode_bytes || need.census) && !need.cost) SMX_HIP(c->chunk_cost.ensure(2 * (size_t)c->chunk * fb));
     return SMX_OK;
 }
 
@@ -148,89 +145,48 @@ static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int
                                       in.dminr, s0, s1, st);
 }
 
-// Census mode of ctx_enqueue: census cost chunk -> aggregation from that chunk, over ascending contiguous chunks of `call`'s
-// slices, into the whole volumes where the context holds them, else into the chunk buffer.  Chunks after the first accumulate.
-static int ctx_census_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, bool whole) {
+// The opt-in aggregations of ctx_enqueue that go chunk by chunk -- the guided filter from census codes, the colour-guided
+// filter, cross-based aggregation -- over ascending contiguous chunks [s0, s1) of the slices.  Per chunk: its cost slices of
+// both views (from the codes, or the reference's; nothing where the whole reference volumes were built up front) into the
+// whole volumes where the context holds them, else into the chunk buffer; then its aggregation, which accumulates into the
+// keys and the states of `call`.
+static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
     const size_t n = c->n;
-    const int chunk = whole ? c->size_d : c->census_chunk;
-    int rc;
-    for (int s0 = call.s_begin; s0 < call.s_end; s0 += chunk) {
-        const int s1 = s0 + chunk < call.s_end ? s0 + chunk : call.s_end;
-        float* cl = whole ? c->costL.as<float>() + (size_t)s0 * n : c->ccost.as<float>();
-        float* cr = whole ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
-        if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
-        AggCall part = call;
-        part.s_begin = s0; part.s_end = s1;
-        part.cost[0] = cl; part.cost[1] = cr;
-        for (int v = 0; v < 2; ++v)
-            if (call.agg[v]) part.agg[v] = call.agg[v] + (size_t)(s0 - call.s_begin) * n;
-        if ((rc = run_aggregation(part, c->agg_path, s0 != call.s_begin))) return rc;
-    }
-    return SMX_OK;
-}
-
-// Colour-guided mode of ctx_enqueue: cost chunk (census or the reference's; the whole volumes where the context holds them) ->
-// smx_dev_cgf_wta_pair from that chunk, over ascending contiguous chunks, accumulating into the keys and the states.  With the
-// aggregated volumes wanted, a chunk goes view by view: the pair form lays its two views a chunk apart, the context a volume.
-static int ctx_cgf_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
-    const size_t n = c->n;
-    const int w = c->w, h = c->h, chunk = c->cgf_chunk;
+    const int w = c->w, h = c->h, chunk = c->chunk;
+    // cross-based: the guide is the colour pair where the pair came as colour images, else the gray pair
+    const bool gray = need.cross && !in.channels;
+    const uint8_t* gl = gray ? in.left : in.rgb_l;
+    const uint8_t* gr = gray ? in.right : in.rgb_r;
+    const int ch = gray ? 1 : in.channels;
     int rc;
     for (int s0 = 0; s0 < c->size_d; s0 += chunk) {
         const int s1 = s0 + chunk < c->size_d ? s0 + chunk : c->size_d;
-        float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->cgf_cost.as<float>();
+        float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->chunk_cost.as<float>();
         float* cr = need.cost ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
         if (need.census) {
             if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
-        } else if (!need.cost) {        // (whole reference volumes were built up front)
+        } else if (!need.cost) {
             if ((rc = smx_dev_cost_volume(&c->p, in.left, in.right, cl, w, w, h, in.dminl, s0, s1, call.st))) return rc;
             if ((rc = smx_dev_cost_volume(&c->p, in.right, in.left, cr, w, w, h, in.dminr, s0, s1, call.st))) return rc;
         }
-        if (!need.agg) {
-            rc = smx_dev_cgf_wta_pair(&c->p, in.rgb_l, in.rgb_r, in.channels, cl, cr, w, h, s0, s1, call.keys[0], nullptr, call.nbr[0],
-                                      call.uq[0], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
+        float* agg[2] = {call.agg[0] ? call.agg[0] + (size_t)s0 * n : nullptr, call.agg[1] ? call.agg[1] + (size_t)s0 * n : nullptr};
+        if (!need.cgf && !need.cross) {
+            AggCall part = call;
+            part.s_begin = s0; part.s_end = s1;
+            part.cost[0] = cl; part.cost[1] = cr;
+            part.agg[0] = agg[0]; part.agg[1] = agg[1];
+            rc = run_aggregation(part, c->agg_path, s0 != 0);
         } else {
-            rc = smx_dev_cgf_wta_pair(&c->p, in.rgb_l, nullptr, in.channels, cl, nullptr, w, h, s0, s1, call.keys[0],
-                                      call.agg[0] + (size_t)s0 * n, call.nbr[0], call.uq[0], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
-            if (!rc)
-                rc = smx_dev_cgf_wta_pair(&c->p, nullptr, in.rgb_r, in.channels, nullptr, cr, w, h, s0, s1, call.keys[1],
-                                          call.agg[1] + (size_t)s0 * n, call.nbr[1], call.uq[1], c->cgf_ws.p, c->cgf_ws_bytes, call.st);
-        }
-        if (rc) return rc;
-    }
-    return SMX_OK;
-}
-
-// Cross-based mode of ctx_enqueue: the flow of ctx_cgf_aggregate with smx_dev_cross_wta_pair; the guide is the colour pair where
-// the pair came as colour images, else the gray pair.
-static int ctx_cross_aggregate(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
-    const size_t n = c->n;
-    const int w = c->w, h = c->h, chunk = c->cross_chunk;
-    const uint8_t* gl = in.channels ? in.rgb_l : in.left;
-    const uint8_t* gr = in.channels ? in.rgb_r : in.right;
-    const int ch = in.channels ? in.channels : 1;
-    const smx_cross_params* cp = &c->cross_params;
-    int rc;
-    for (int s0 = 0; s0 < c->size_d; s0 += chunk) {
-        const int s1 = s0 + chunk < c->size_d ? s0 + chunk : c->size_d;
-        float* cl = need.cost ? c->costL.as<float>() + (size_t)s0 * n : c->cross_cost.as<float>();
-        float* cr = need.cost ? c->costR.as<float>() + (size_t)s0 * n : cl + (size_t)chunk * n;
-        if (need.census) {
-            if ((rc = ctx_code_cost(c, in, cl, cr, s0, s1, call.st))) return rc;
-        } else if (!need.cost) {        // (whole reference volumes were built up front)
-            if ((rc = smx_dev_cost_volume(&c->p, in.left, in.right, cl, w, w, h, in.dminl, s0, s1, call.st))) return rc;
-            if ((rc = smx_dev_cost_volume(&c->p, in.right, in.left, cr, w, w, h, in.dminr, s0, s1, call.st))) return rc;
-        }
-        if (!need.agg) {
-            rc = smx_dev_cross_wta_pair(cp, gl, gr, ch, cl, cr, w, h, s0, s1, call.keys[0], nullptr, call.nbr[0], call.uq[0],
-                                        c->cross_ws.p, c->cross_ws_bytes, call.st);
-        } else {
-            rc = smx_dev_cross_wta_pair(cp, gl, nullptr, ch, cl, nullptr, w, h, s0, s1, call.keys[0], call.agg[0] + (size_t)s0 * n,
-                                        call.nbr[0], call.uq[0], c->cross_ws.p, c->cross_ws_bytes, call.st);
-            if (!rc)
-                rc = smx_dev_cross_wta_pair(cp, nullptr, gr, ch, nullptr, cr, w, h, s0, s1, call.keys[1],
-                                            call.agg[1] + (size_t)s0 * n, call.nbr[1], call.uq[1], c->cross_ws.p,
-                                            c->cross_ws_bytes, call.st);
+            // views l / r of the chunk into the outputs of view v; mode_ws_bytes, not the buffer's size: see smx_ctx
+            auto views = [&](const uint8_t* l, const uint8_t* r, const float* kl, const float* kr, int v) {
+                return need.cgf ? smx_dev_cgf_wta_pair(&c->p, l, r, ch, kl, kr, w, h, s0, s1, call.keys[v], agg[v], call.nbr[v],
+                                                       call.uq[v], c->mode_ws.p, c->mode_ws_bytes, call.st)
+                                : smx_dev_cross_wta_pair(&c->cross_params, l, r, ch, kl, kr, w, h, s0, s1, call.keys[v], agg[v],
+                                                         call.nbr[v], call.uq[v], c->mode_ws.p, c->mode_ws_bytes, call.st);
+            };
+            // with the aggregated volumes wanted, view by view: the pair form lays its two views a chunk apart, the context a volume
+            if (!need.agg) rc = views(gl, gr, cl, cr, 0);
+            else if (!(rc = views(gl, nullptr, cl, nullptr, 0))) rc = views(nullptr, gr, nullptr, cr, 1);
         }
         if (rc) return rc;
     }
@@ -266,13 +222,11 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
         if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
-        const size_t sgm_bytes = sgm_workspace_bytes(w, h, size_d, 2);
-        if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->sgm_ws.p,
-                                                          sgm_bytes, st)
-                                : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->sgm_ws.p, sgm_bytes, st);
-    } else if (need.cgf) rc = ctx_cgf_aggregate(c, in, call, need);
-    else if (need.cross) rc = ctx_cross_aggregate(c, in, call, need);
-    else if (need.census) rc = ctx_census_aggregate(c, in, call, need.cost);
+        if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->mode_ws.p,
+                                                          c->mode_ws_bytes, st)
+                                : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->mode_ws.p,
+                                                       c->mode_ws_bytes, st);
+    } else if (need.cgf || need.cross || need.census) rc = ctx_aggregate_chunks(c, in, call, need);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
     // main.cu:112-118 presets, winning slices, main.cu:140-155

@@ -9,10 +9,39 @@
 
 using namespace smx;
 
-size_t smx::pick_ws_bytes(int w, int h, int size_d) {
-    // every slice in flight, but at most ~2 GiB of them
-    const size_t one = smx_agg_workspace_bytes(w, h, 1), all = smx_agg_workspace_bytes(w, h, size_d), cap = (size_t)2 << 30;
+// every slice in flight, but at most ~2 GiB of them; bytes(k): a stage's workspace for k slices in flight
+template <class Bytes> static size_t capped_ws_bytes(Bytes bytes, int size_d) {
+    const size_t one = bytes(1), all = bytes(size_d), cap = (size_t)2 << 30;
     return all <= cap ? all : one > cap ? one : cap;
+}
+
+size_t smx::pick_ws_bytes(int w, int h, int size_d) {
+    return capped_ws_bytes([=](int k) { return smx_agg_workspace_bytes(w, h, k); }, size_d);
+}
+
+// The body of smx_colour_guided_filter and smx_cross_aggregate behind their argument checks: guide, cost and the caller's
+// presets up; fresh keys; entry(guide, cost, keys, agg, ws): the stage's one-view device entry; the keys onto the presets; down.
+template <class Entry>
+static int guide_aggregate_host(const uint8_t* guide, int channels, const float* cost, float* filter_cost, float* disp_map,
+                                float* agg, int w, int h, int size_d, int dmin, size_t ws_bytes, Entry entry) {
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), vb = fb * size_d;
+    DevBuf dI, dC, dBest, dMap, dKeys, dAgg, ws;
+    SMX_HIP(dI.upload(guide, n * channels));
+    SMX_HIP(dC.upload(cost, vb));
+    SMX_HIP(dBest.upload(filter_cost, fb));
+    SMX_HIP(dMap.upload(disp_map, fb));
+    SMX_HIP(dKeys.ensure(n * sizeof(int64_t)));
+    if (agg) SMX_HIP(dAgg.ensure(vb));
+    SMX_HIP(ws.ensure(ws_bytes));
+    int rc;
+    if ((rc = smx_dev_init_keys(dKeys.as<int64_t>(), (int64_t)n, nullptr))) return rc;
+    if ((rc = entry(dI.as<uint8_t>(), dC.as<float>(), dKeys.as<int64_t>(), agg ? dAgg.as<float>() : nullptr, ws.p))) return rc;
+    if ((rc = smx_dev_apply_keys(dKeys.as<int64_t>(), (int64_t)n, dmin, dBest.as<float>(), dMap.as<float>(), nullptr))) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dBest.download(filter_cost, fb));
+    SMX_HIP(dMap.download(disp_map, fb));
+    if (agg) SMX_HIP(dAgg.download(agg, vb));
+    return SMX_OK;
 }
 
 extern "C" {
@@ -241,31 +270,28 @@ int smx_colour_guided_filter(const smx_params* p, const uint8_t* rgb, int channe
                              float* disp_map, float* agg, int w, int h, int size_d, int dmin) {
     SMX_ARG(p && rgb && cost && filter_cost && disp_map && size_d >= 1 && w >= 1 && h >= 1);
     SMX_ARG(p->radius >= 0 && (channels == 3 || channels == 4));
-    const size_t n = (size_t)w * h, fb = n * sizeof(float), vb = fb * size_d;
-    // every slice in flight, but at most ~2 GiB of them
-    const size_t one = smx_cgf_workspace_bytes(w, h, 1, 1), all = smx_cgf_workspace_bytes(w, h, size_d, 1), cap = (size_t)2 << 30;
+    const size_t one = smx_cgf_workspace_bytes(w, h, 1, 1);
     SMX_ARG(one != 0);
-    const size_t ws_bytes = all <= cap ? all : one > cap ? one : cap;
-    DevBuf dI, dC, dBest, dMap, dKeys, dAgg, ws;
-    SMX_HIP(dI.upload(rgb, n * channels));
-    SMX_HIP(dC.upload(cost, vb));
-    SMX_HIP(dBest.upload(filter_cost, fb));
-    SMX_HIP(dMap.upload(disp_map, fb));
-    SMX_HIP(dKeys.ensure(n * sizeof(int64_t)));
-    if (agg) SMX_HIP(dAgg.ensure(vb));
-    SMX_HIP(ws.ensure(ws_bytes));
-    int rc;
-    if ((rc = smx_dev_init_keys(dKeys.as<int64_t>(), (int64_t)n, nullptr))) return rc;
-    if ((rc = smx_dev_cgf_wta_pair(p, dI.as<uint8_t>(), nullptr, channels, dC.as<float>(), nullptr, w, h, 0, size_d,
-                                   dKeys.as<int64_t>(), agg ? dAgg.as<float>() : nullptr, nullptr, nullptr, ws.p, ws_bytes,
-                                   nullptr)))
-        return rc;
-    if ((rc = smx_dev_apply_keys(dKeys.as<int64_t>(), (int64_t)n, dmin, dBest.as<float>(), dMap.as<float>(), nullptr))) return rc;
-    SMX_HIP(hipDeviceSynchronize());
-    SMX_HIP(dBest.download(filter_cost, fb));
-    SMX_HIP(dMap.download(disp_map, fb));
-    if (agg) SMX_HIP(dAgg.download(agg, vb));
-    return SMX_OK;
+    const size_t ws_bytes = capped_ws_bytes([=](int k) { return cgf_workspace_bytes(w, h, k, 1); }, size_d);
+    return guide_aggregate_host(rgb, channels, cost, filter_cost, disp_map, agg, w, h, size_d, dmin, ws_bytes,
+                                [=](const uint8_t* d_rgb, const float* d_cost, int64_t* d_keys, float* d_agg, void* d_ws) {
+                                    return smx_dev_cgf_wta_pair(p, d_rgb, nullptr, channels, d_cost, nullptr, w, h, 0, size_d, d_keys,
+                                                                d_agg, nullptr, nullptr, d_ws, ws_bytes, nullptr);
+                                });
+}
+
+int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int channels, const float* cost, float* filter_cost,
+                        float* disp_map, float* agg, int w, int h, int size_d, int dmin) {
+    if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_cross_aggregate: %s", CROSS_RANGES);
+    SMX_ARG(guide && cost && filter_cost && disp_map && size_d >= 1);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_cross_aggregate: needs w, h >= 1 and w*h < 2^31");
+    const size_t ws_bytes = capped_ws_bytes([=](int k) { return cross_workspace_bytes(w, h, k, 1); }, size_d);
+    return guide_aggregate_host(guide, channels, cost, filter_cost, disp_map, agg, w, h, size_d, dmin, ws_bytes,
+                                [=](const uint8_t* d_guide, const float* d_cost, int64_t* d_keys, float* d_agg, void* d_ws) {
+                                    return smx_dev_cross_wta_pair(p, d_guide, nullptr, channels, d_cost, nullptr, w, h, 0, size_d,
+                                                                  d_keys, d_agg, nullptr, nullptr, d_ws, ws_bytes, nullptr);
+                                });
 }
 
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {

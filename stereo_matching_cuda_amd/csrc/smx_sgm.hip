@@ -25,6 +25,7 @@
 // k_sgm_select: a workgroup per 64 pixels of a row stages their S (one contiguous piece of S16) in LDS, writes the f32
 // volume [z][y][x] from it (lanes along x: coalesced) and lets one lane per pixel run the tie rule over ascending d.
 #include "smx_launch.h"
+#include "smx_wta.h"
 
 namespace smx {
 namespace {
@@ -288,22 +289,16 @@ int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const fl
                         int64_t* keys, float* agg, float* nbr, float* uq, void* ws, hipStream_t st) {
     const int64_t n = (int64_t)w * h;
     SgmArgs a = {};
-    int nviews = 0;
+    const ViewSlots s = view_slots(cost_l, cost_r, keys, agg, nbr, uq, size_d, n);
+    const int nviews = s.V;
     const float* costs[2] = {cost_l, cost_r};
     const size_t plane = sgm_plane_bytes(w, h, size_d);
     uint8_t* base = reinterpret_cast<uint8_t*>(align_up((size_t)ws, 256));
-    for (int view = 0; view < 2; ++view) {
-        if (!costs[view]) continue;
-        a.cost[nviews] = costs[view];
-        // with both views the outputs hold the left view first; the one-view form has the one view at the front
-        const int slot = cost_l && cost_r ? view : 0;
-        a.keys[nviews] = keys + slot * n;
-        a.agg[nviews] = agg ? agg + (int64_t)slot * size_d * n : nullptr;
-        a.nbr[nviews] = nbr ? nbr + (int64_t)slot * 3 * n : nullptr;
-        a.uq[nviews] = uq ? uq + (int64_t)slot * 3 * n : nullptr;
-        a.c8[nviews] = base + (size_t)nviews * 3 * plane;
-        a.s16[nviews] = reinterpret_cast<uint16_t*>(base + (size_t)nviews * 3 * plane + plane);
-        ++nviews;
+    s.put(a);
+    for (int k = 0; k < nviews; ++k) {
+        a.cost[k] = costs[s.view[k]];
+        a.c8[k] = base + (size_t)k * 3 * plane;
+        a.s16[k] = reinterpret_cast<uint16_t*>(base + (size_t)k * 3 * plane + plane);
     }
     a.w = w; a.h = h; a.size_d = size_d; a.dp = sgm_padded_d(size_d); a.p1 = p1; a.p2 = p2;
     a.xtiles = (w + SGM_TILE - 1) / SGM_TILE;

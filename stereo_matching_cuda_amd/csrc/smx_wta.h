@@ -135,6 +135,34 @@ struct WtaPassUq : WtaPass {
     float* uq[2];
 };
 
+// The views of a pair call (smx_dev_sgm_wta_pair, _cgf_, _cross_) as its kernels index them: view k of the V given ones is the
+// caller's view[k] (0 left, 1 right).  With both views the outputs hold the left view first; the one-view form has the one
+// view at the front.  agg holds `count` planes a view.
+struct ViewSlots {
+    int V, view[2];
+    int64_t* keys[2];
+    float *agg[2], *nbr[2], *uq[2];
+    template <class Args> void put(Args& a) const {     // into a kernel's argument struct
+        for (int k = 0; k < V; ++k) { a.keys[k] = keys[k]; a.agg[k] = agg[k]; a.nbr[k] = nbr[k]; a.uq[k] = uq[k]; }
+    }
+};
+inline ViewSlots view_slots(const float* cost_l, const float* cost_r, int64_t* keys, float* agg, float* nbr, float* uq, int count,
+                            int64_t n) {
+    ViewSlots s = {};
+    const float* costs[2] = {cost_l, cost_r};
+    for (int view = 0; view < 2; ++view) {
+        if (!costs[view]) continue;
+        const int64_t slot = cost_l && cost_r ? view : 0;
+        s.view[s.V] = view;
+        s.keys[s.V] = keys + slot * n;
+        s.agg[s.V] = agg ? agg + slot * count * n : nullptr;
+        s.nbr[s.V] = nbr ? nbr + slot * 3 * n : nullptr;
+        s.uq[s.V] = uq ? uq + slot * 3 * n : nullptr;
+        ++s.V;
+    }
+    return s;
+}
+
 // The one launcher: `nviews` views, q planes `plane` floats apart, nbr == NULL and uq == NULL for the plain pass, either or
 // both for the passes that keep state.  Natural order takes two pixels per lane where every plane can be read in 8-byte
 // units (one with nbr); comb order takes four and wants 16-byte aligned planes (SMX_E_ARG otherwise).  count < 1: no launch.

@@ -383,6 +383,40 @@ def test_context(orc):
         L.smx_destroy(ctx)
 
 
+def test_context_chunks_do_not_change_a_bit(orc):
+    """The context's chunk loop of the guided flow from census codes under smx_set_max_slices_per_launch: at 16 slices, 5 gives
+    chunks of 5, 5, 5 and a ragged last one of a single slice, 16 one chunk, 1 every slice alone; every chunk after the first
+    accumulates into the keys.  Through the chunk buffer, then with the whole volumes, where the aggregated slices go to
+    their offsets.  Against the reference chain of test_context."""
+    w, h, D, dminl = 129, 70, 16, -15
+    Il, Ir = synth.gen_pair(w, h, D, w + h)
+    e = expected(orc, Il, Ir, D, dminl, 0, 9, tag="129x70x16")
+    L = smx.lib()
+    names = {"best_l": "bestl", "best_r": "bestr", "dmap_l": "dmapl", "dmap_r": "dmapr", "occlusion": "occlusion",
+             "filled": "filled", "mean_l": "meanl", "mean_r": "meanr", "cost_l": "costl", "cost_r": "costr",
+             "agg_l": "aggl", "agg_r": "aggr"}
+    maps = [k for k in names if not k.startswith(("cost", "agg"))]
+    ctx = C.c_void_p()
+    _lib.check(L.smx_create(C.byref(smx.default_params()), w, h, D, C.byref(ctx)))
+    try:
+        _lib.check(L.smx_ctx_set_cost(ctx, _lib.COST_MODES["census"], None))
+        for k in (1, 5, 16):
+            for fields in (maps, list(names)):
+                bufs = {f: np.empty(e[names[f]].shape, e[names[f]].dtype) for f in fields}
+                out = _lib.PairOut(**{f: v.ctypes.data for f, v in bufs.items()})
+                _lib.check(L.smx_set_max_slices_per_launch(k))
+                try:
+                    rc = L.smx_ctx_stereo_pair(ctx, Il.ctypes.data, Ir.ctypes.data, dminl, 0, C.byref(out))
+                finally:
+                    L.smx_set_max_slices_per_launch(0)
+                _lib.check(rc)
+                for f, v in bufs.items():
+                    _eq(v, e[names[f]], f"census ctx, at most {k} slices, {len(fields)} planes: {f}")
+    finally:
+        L.smx_destroy(ctx)
+    assert len(np.unique(e["dmapl"])) > 3
+
+
 def test_pair_step_is_capturable_in_a_hip_graph(orc):
     import torch
     w, h, D = 129, 70, 70

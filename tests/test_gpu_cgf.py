@@ -381,15 +381,19 @@ def _spk():
 
 
 def chain(orc, rgb_l, rgb_r, census):
-    """The whole pair in numpy: gray -> cost -> cgf_ref -> the references of the later stages."""
+    """The whole pair in numpy: gray -> cost (census: False the reference's, True census, "adcensus") -> cgf_ref -> the
+    references of the later stages."""
+    import adcensus_ref
     import speckle_ref
     import subpix_ref
     import uniq_ref
     import wmf_ref
     Il, Ir = orc.gray(rgb_l), orc.gray(rgb_r)
-    cost = (lambda a, b, dmin: census_ref.census_cost(a, b, PD, dmin)) if census else \
+    cost = (lambda a, b, dmin: adcensus_ref.gray_cost(a, b, PD, dmin)) if census == "adcensus" else \
+           (lambda a, b, dmin: census_ref.census_cost(a, b, PD, dmin)) if census else \
            (lambda a, b, dmin: orc.cost_volume(a, b, PD, dmin))
-    r = {"Il": Il, "Ir": Ir, "aggl": ref.aggregate(rgb_l, cost(Il, Ir, PDMINL)), "aggr": ref.aggregate(rgb_r, cost(Ir, Il, 0))}
+    r = {"Il": Il, "Ir": Ir, "costl": cost(Il, Ir, PDMINL), "costr": cost(Ir, Il, 0)}
+    r["aggl"], r["aggr"] = ref.aggregate(rgb_l, r["costl"]), ref.aggregate(rgb_r, r["costr"])
     sl, sr = ref.states(r["aggl"]), ref.states(r["aggr"])
     r["keys"] = np.stack((sl["keys"], sr["keys"]))
     r["bestl"], r["bestr"] = sl["best"], sr["best"]
@@ -412,6 +416,11 @@ def chain(orc, rgb_l, rgb_r, census):
 def colour_scene(orc):
     rgb_l, rgb_r = ref.colour_pair(PW, PH, PD, 4711)
     return rgb_l, rgb_r, {census: chain(orc, rgb_l, rgb_r, census) for census in (False, True)}
+
+
+@pytest.fixture(scope="module")
+def adcensus_want(colour_scene, orc):
+    return chain(orc, colour_scene[0], colour_scene[1], "adcensus")
 
 
 def _pipe(rgb_l, rgb_r, Il, Ir, **kw):
@@ -543,16 +552,40 @@ def _ctx_pair(ctx, entry, imgs, channels, want_vol, mean=False):
     return entry(ctx, *args), bufs
 
 
+CTX_NAMES = (("best_l", "bestl"), ("best_r", "bestr"), ("dmap_l", "dmapl"), ("dmap_r", "dmapr"), ("occlusion", "occlusion"),
+             ("filled", "filled"))
+CTX_VOLUMES = (("agg_l", "aggl"), ("agg_r", "aggr"), ("cost_l", "costl"), ("cost_r", "costr"))
+
+
+def _ctx_create():
+    ctx = C.c_void_p()
+    _lib.check(smx.lib().smx_create(C.byref(smx.default_params()), PW, PH, PD, C.byref(ctx)))
+    return ctx
+
+
+def _check_ctx_stages(ctx, got, want, want_vol, label):
+    """The planes and the maps of a context pair that ran with sub-pixel, uniqueness and speckle removal on, against `chain`"""
+    L = smx.lib()
+    for k, name in CTX_NAMES + ((("agg_l", "aggl"), ("agg_r", "aggr")) if want_vol else ()):
+        _eq(got[k], want[name], f"{label} {name} (volumes {want_vol})")
+    sub = [np.empty((PH, PW), np.float32) for _ in range(3)]
+    _lib.check(L.smx_ctx_subpixel_maps(ctx, *(s.ctypes.data for s in sub)))
+    for s, name in zip(sub, ("subpixl", "subpixr", "subpix_filled")):
+        _eq(s, want[name], f"{label} {name}")
+    desp, uni, margin = (np.empty((PH, PW), np.float32) for _ in range(3))
+    _lib.check(L.smx_ctx_speckle_map(ctx, desp.ctypes.data))
+    _lib.check(L.smx_ctx_uniqueness_map(ctx, uni.ctypes.data, margin.ctypes.data))
+    _eq(desp, want["despeckled"], label + " despeckled")
+    _eq(uni, want["unique"], label + " unique")
+    _eq(margin, want["margin"], label + " margin")
+
+
 @pytest.mark.parametrize("census", [False, True])
 def test_context(colour_scene, orc, census):
     rgb_l, rgb_r, wants = colour_scene
     want = wants[census]
     L = smx.lib()
-    P = smx.default_params()
-    ctx = C.c_void_p()
-    _lib.check(L.smx_create(C.byref(P), PW, PH, PD, C.byref(ctx)))
-    names = (("best_l", "bestl"), ("best_r", "bestr"), ("dmap_l", "dmapl"), ("dmap_r", "dmapr"), ("occlusion", "occlusion"),
-             ("filled", "filled"))
+    ctx = _ctx_create()
     try:
         assert L.smx_ctx_set_guidance(ctx, 2) == -1
         if census:
@@ -574,18 +607,7 @@ def test_context(colour_scene, orc, census):
         for want_vol in (True, False):
             rc, got = _ctx_pair(ctx, L.smx_ctx_stereo_pair_rgb, (rgb_l, rgb_r), 3, want_vol)
             _lib.check(rc)
-            for k, name in names + ((("agg_l", "aggl"), ("agg_r", "aggr")) if want_vol else ()):
-                _eq(got[k], want[name], f"ctx {name} (volumes {want_vol})")
-            sub = [np.empty((PH, PW), np.float32) for _ in range(3)]
-            _lib.check(L.smx_ctx_subpixel_maps(ctx, *(s.ctypes.data for s in sub)))
-            for s, name in zip(sub, ("subpixl", "subpixr", "subpix_filled")):
-                _eq(s, want[name], "ctx " + name)
-            desp, uni, margin = (np.empty((PH, PW), np.float32) for _ in range(3))
-            _lib.check(L.smx_ctx_speckle_map(ctx, desp.ctypes.data))
-            _lib.check(L.smx_ctx_uniqueness_map(ctx, uni.ctypes.data, margin.ctypes.data))
-            _eq(desp, want["despeckled"], "ctx despeckled")
-            _eq(uni, want["unique"], "ctx unique")
-            _eq(margin, want["margin"], "ctx margin")
+            _check_ctx_stages(ctx, got, want, want_vol, "ctx")
         # four channels: the same bits
         rgba = [np.concatenate((x, np.full((PH, PW, 1), 9, np.uint8)), axis=2) for x in (rgb_l, rgb_r)]
         rc, got4 = _ctx_pair(ctx, L.smx_ctx_stereo_pair_rgb, rgba, 4, False)
@@ -602,5 +624,34 @@ def test_context(colour_scene, orc, census):
         _lib.check(L.smx_ctx_set_aggregation(ctx, 1, None))
         rc, _ = _ctx_pair(ctx, L.smx_ctx_stereo_pair_rgb, (rgb_l, rgb_r), 3, False)
         assert rc == -1 and b"semi-global" in L.smx_last_error()
+    finally:
+        L.smx_destroy(ctx)
+
+
+@pytest.mark.parametrize("cost", [None, "adcensus"])
+def test_context_chunks_do_not_change_a_bit(colour_scene, adcensus_want, orc, cost):
+    """The context's chunk loop under smx_set_max_slices_per_launch: 5 gives chunks of 5, 5, 5 and a ragged last one of a single
+    slice, 16 one chunk, 1 every slice alone.  With the volumes the chunks go view by view into the whole volumes at their
+    slice offsets; without them in the pair form from the chunk buffer.  Everything against the numpy references of the
+    fixtures; without the later stages the filled map is the fill of the occlusion map."""
+    rgb_l, rgb_r, wants = colour_scene
+    want = dict(adcensus_want if cost == "adcensus" else wants[False])
+    want["filled"] = orc.fill_occlusion(want["occlusion"], PDMINL)
+    L = smx.lib()
+    ctx = _ctx_create()
+    try:
+        _lib.check(L.smx_ctx_set_guidance(ctx, 1))
+        if cost == "adcensus":
+            _lib.check(L.smx_ctx_set_adcensus(ctx, C.byref(smx.default_adcensus_params())))
+        for k in (1, 5, 16):
+            for want_vol in (True, False):
+                _lib.check(L.smx_set_max_slices_per_launch(k))
+                try:
+                    rc, got = _ctx_pair(ctx, L.smx_ctx_stereo_pair_rgb, (rgb_l, rgb_r), 3, want_vol)
+                finally:
+                    L.smx_set_max_slices_per_launch(0)
+                _lib.check(rc)
+                for key, name in CTX_NAMES + (CTX_VOLUMES if want_vol else ()):
+                    _eq(got[key], want[name], f"ctx cost {cost}, at most {k} slices, volumes {want_vol}: {name}")
     finally:
         L.smx_destroy(ctx)

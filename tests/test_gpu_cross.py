@@ -642,13 +642,65 @@ def _ctx_pair(ctx, entry, imgs, channels, want_vol, mean=False):
     return entry(ctx, *args), bufs
 
 
+CTX_NAMES = (("best_l", "bestl"), ("best_r", "bestr"), ("dmap_l", "dmapl"), ("dmap_r", "dmapr"), ("occlusion", "occlusion"),
+             ("filled", "filled"))
+CTX_VOLUMES = (("agg_l", "aggl"), ("agg_r", "aggr"), ("cost_l", "costl"), ("cost_r", "costr"))
+
+
+def _ctx_want(orc, scene, cost, guide):
+    """What a context pair with cross-based aggregation hands out, in numpy: the six planes and the four volumes (kept in the
+    scene: every test of the context compares against the same arrays)"""
+    key = ("ctx want", cost, guide)
+    if key not in scene:
+        import subpix_ref
+        aggl, aggr = scene["agg"][(cost, guide)]
+        sl, sr = cgf_ref.states(aggl), cgf_ref.states(aggr)
+        want = {"aggl": aggl, "aggr": aggr, "costl": scene["cost"][cost][0], "costr": scene["cost"][cost][1],
+                "bestl": sl["best"], "bestr": sr["best"],
+                "dmapl": subpix_ref.dmap_of(sl["z"], sl["best"], PDMINL), "dmapr": subpix_ref.dmap_of(sr["z"], sr["best"], 0)}
+        want["occlusion"] = orc.detect_occlusion(want["dmapl"], want["dmapr"], PDMINL - 100)
+        want["filled"] = orc.fill_occlusion(want["occlusion"], PDMINL)
+        scene[key] = want
+    return scene[key]
+
+
+def _check_ctx_stages(ctx, got, want, label):
+    """The planes and the maps of a context pair that ran with sub-pixel, uniqueness and speckle removal on, against `chain`"""
+    L = smx.lib()
+    for k, name in CTX_NAMES:
+        _eq(got[k], want[name], f"{label} {name}")
+    sub = [np.empty((PH, PW), np.float32) for _ in range(3)]
+    _lib.check(L.smx_ctx_subpixel_maps(ctx, *(s.ctypes.data for s in sub)))
+    for s, name in zip(sub, ("subpixl", "subpixr", "subpix_filled")):
+        _eq(s, want[name], f"{label} {name}")
+    uni, margin = (np.empty((PH, PW), np.float32) for _ in range(2))
+    _lib.check(L.smx_ctx_uniqueness_map(ctx, uni.ctypes.data, margin.ctypes.data))
+    _eq(uni, want["unique"], label + " unique")
+    _eq(margin, want["margin"], label + " margin")
+
+
+def _ctx_create():
+    ctx = C.c_void_p()
+    _lib.check(smx.lib().smx_create(C.byref(smx.default_params()), PW, PH, PD, C.byref(ctx)))
+    return ctx
+
+
+def _bounded_pair(k, *args):
+    """_ctx_pair with at most k slices per launch on this thread, checked"""
+    L = smx.lib()
+    _lib.check(L.smx_set_max_slices_per_launch(k))
+    try:
+        rc, got = _ctx_pair(*args)
+    finally:
+        L.smx_set_max_slices_per_launch(0)
+    _lib.check(rc)
+    return got
+
+
 def test_context(orc, scene):
     L = smx.lib()
-    P = smx.default_params()
-    ctx = C.c_void_p()
-    _lib.check(L.smx_create(C.byref(P), PW, PH, PD, C.byref(ctx)))
-    names = (("best_l", "bestl"), ("best_r", "bestr"), ("dmap_l", "dmapl"), ("dmap_r", "dmapr"), ("occlusion", "occlusion"),
-             ("filled", "filled"))
+    ctx = _ctx_create()
+    names = CTX_NAMES
     gray, rgb = (scene["Il"], scene["Ir"]), scene["rgb"]
     try:
         # off: the context is the oracle's pair
@@ -672,13 +724,7 @@ def test_context(orc, scene):
             elif cost == "adcensus":
                 _lib.check(L.smx_ctx_set_adcensus(ctx, C.byref(smx.default_adcensus_params())))
             for guide, entry, imgs, ch in (("gray", L.smx_ctx_stereo_pair, gray, 0), ("rgb", L.smx_ctx_stereo_pair_rgb, rgb, 3)):
-                aggl, aggr = scene["agg"][(cost, guide)]
-                import subpix_ref
-                sl, sr = cgf_ref.states(aggl), cgf_ref.states(aggr)
-                want = {"aggl": aggl, "aggr": aggr, "bestl": sl["best"], "bestr": sr["best"],
-                        "dmapl": subpix_ref.dmap_of(sl["z"], sl["best"], PDMINL), "dmapr": subpix_ref.dmap_of(sr["z"], sr["best"], 0)}
-                want["occlusion"] = orc.detect_occlusion(want["dmapl"], want["dmapr"], PDMINL - 100)
-                want["filled"] = orc.fill_occlusion(want["occlusion"], PDMINL)
+                want = _ctx_want(orc, scene, cost, guide)
                 for want_vol in (True, False):
                     rc, got = _ctx_pair(ctx, entry, imgs, ch, want_vol)
                     _lib.check(rc)
@@ -693,16 +739,7 @@ def test_context(orc, scene):
         want = chain(orc, scene["Il"], *scene["agg"][("adcensus", "rgb")])
         rc, got = _ctx_pair(ctx, L.smx_ctx_stereo_pair_rgb, rgb, 3, False)
         _lib.check(rc)
-        for k, name in names:
-            _eq(got[k], want[name], "ctx stages " + name)
-        sub = [np.empty((PH, PW), np.float32) for _ in range(3)]
-        _lib.check(L.smx_ctx_subpixel_maps(ctx, *(s.ctypes.data for s in sub)))
-        for s, name in zip(sub, ("subpixl", "subpixr", "subpix_filled")):
-            _eq(s, want[name], "ctx " + name)
-        uni, margin = (np.empty((PH, PW), np.float32) for _ in range(2))
-        _lib.check(L.smx_ctx_uniqueness_map(ctx, uni.ctypes.data, margin.ctypes.data))
-        _eq(uni, want["unique"], "ctx unique")
-        _eq(margin, want["margin"], "ctx margin")
+        _check_ctx_stages(ctx, got, want, "ctx stages")
         _lib.check(L.smx_ctx_set_subpixel(ctx, 0))
         _lib.check(L.smx_ctx_set_uniqueness(ctx, 0.0))
         _lib.check(L.smx_ctx_set_speckle(ctx, None))
@@ -722,5 +759,51 @@ def test_context(orc, scene):
         _lib.check(rc)
         for k, name in names:
             _eq(again[k], plain[name], "off again " + name)
+    finally:
+        L.smx_destroy(ctx)
+
+
+@pytest.mark.parametrize("guide", ["gray", "rgb"])
+@pytest.mark.parametrize("cost", [None, "adcensus"])
+def test_context_chunks_do_not_change_a_bit(orc, scene, cost, guide):
+    """The context's chunk loop under smx_set_max_slices_per_launch: 5 gives chunks of 5, 5, 5 and a ragged last one of a single
+    slice, 16 one chunk, 1 every slice alone.  With the volumes the chunks go view by view into the whole volumes at their
+    slice offsets; without them in the pair form from the chunk buffer.  Everything against the numpy references."""
+    L = smx.lib()
+    want = _ctx_want(orc, scene, cost, guide)
+    entry, imgs, ch = (L.smx_ctx_stereo_pair, (scene["Il"], scene["Ir"]), 0) if guide == "gray" else \
+                      (L.smx_ctx_stereo_pair_rgb, scene["rgb"], 3)
+    ctx = _ctx_create()
+    try:
+        _lib.check(L.smx_ctx_set_cross(ctx, C.byref(_p(**PIPE_PARAMS))))
+        if cost == "adcensus":
+            _lib.check(L.smx_ctx_set_adcensus(ctx, C.byref(smx.default_adcensus_params())))
+        for k in (1, 5, 16):
+            for want_vol in (True, False):
+                got = _bounded_pair(k, ctx, entry, imgs, ch, want_vol)
+                for key, name in CTX_NAMES + (CTX_VOLUMES if want_vol else ()):
+                    _eq(got[key], want[name], f"ctx cost {cost} guide {guide}, at most {k} slices, volumes {want_vol}: {name}")
+    finally:
+        L.smx_destroy(ctx)
+
+
+def test_context_chunks_carry_the_states_of_the_later_stages(orc, scene):
+    """Chunks of 5, 5, 5, 1 with sub-pixel, uniqueness and speckle removal on: the nbr / uq states accumulate across the
+    context's chunks.  Against the chain that test_context compares with."""
+    L = smx.lib()
+    want = chain(orc, scene["Il"], *scene["agg"][("adcensus", "rgb")])
+    ctx = _ctx_create()
+    try:
+        _lib.check(L.smx_ctx_set_cross(ctx, C.byref(_p(**PIPE_PARAMS))))
+        _lib.check(L.smx_ctx_set_adcensus(ctx, C.byref(smx.default_adcensus_params())))
+        _lib.check(L.smx_ctx_set_subpixel(ctx, 1))
+        _lib.check(L.smx_ctx_set_uniqueness(ctx, RATIO))
+        _lib.check(L.smx_ctx_set_speckle(ctx, C.byref(_spk())))
+        for want_vol in (False, True):
+            got = _bounded_pair(5, ctx, L.smx_ctx_stereo_pair_rgb, scene["rgb"], 3, want_vol)
+            _check_ctx_stages(ctx, got, want, f"ctx stages in chunks of 5 (volumes {want_vol})")
+            if want_vol:
+                _eq(got["agg_l"], want["aggl"], "ctx stages in chunks of 5 aggl")
+                _eq(got["agg_r"], want["aggr"], "ctx stages in chunks of 5 aggr")
     finally:
         L.smx_destroy(ctx)

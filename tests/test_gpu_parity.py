@@ -1164,7 +1164,7 @@ def test_one_context_through_changing_settings():
     the opt-in stages: a buffer a later step needs and an earlier one did not, or one kept from an earlier step, must not
     change a result.  The fresh contexts are themselves pinned to the oracle and the numpy references by the test_context tests
     of the stages.  At this shape the census chunk equals size_d, so the multi-chunk loop of the context is NOT exercised here;
-    test_chunks_and_split_calls covers that logic through the device API.  The caller's buffers are pre-filled differently for
+    the test_context_chunks_do_not_change_a_bit tests of the stages do that.  The caller's buffers are pre-filled differently for
     the two contexts, so a plane that is not written at all cannot pass."""
     from stereo_matching_cuda_amd import _lib
     L = smx.lib()
@@ -1241,6 +1241,78 @@ def test_one_context_through_changing_settings():
         same(bufs, seen["a"], "pipelined round against a")
     finally:
         smx.check(L.smx_destroy(one))
+
+
+@pytest.mark.gpu
+def test_one_context_through_the_aggregation_modes(orc):
+    """ONE context through SGM, cross-based aggregation, the colour guide, then cross and SGM once more and everything off.  The
+    three modes share one workspace and one chunk buffer, which only grow: the second cross and SGM pairs find the colour
+    guide's larger workspace, and the second cross pair, bounded to 5 slices a chunk, a chunk buffer of 16 slices.  Each pair's
+    six planes, and its aggregated volumes where asked, against the numpy reference of its mode."""
+    from stereo_matching_cuda_amd import _lib
+    import cgf_ref
+    import cross_ref
+    import sgm_ref
+    import subpix_ref
+    L = smx.lib()
+    w, h, D, dminl = 129, 70, 16, -15
+    rgb = cgf_ref.colour_pair(w, h, D, 4711)
+    gray = (orc.gray(rgb[0]), orc.gray(rgb[1]))
+    cost = (orc.cost_volume(gray[0], gray[1], D, dminl), orc.cost_volume(gray[1], gray[0], D, 0))
+    cross_kw = dict(l1=17, l2=8, tau1=20, tau2=6, iterations=2)
+
+    def planes(agg, z, best, dmap_of):
+        r = {"agg_l": agg[0], "agg_r": agg[1], "best_l": best[0], "best_r": best[1], "dmap_l": dmap_of(z[0], best[0], dminl),
+             "dmap_r": dmap_of(z[1], best[1], 0)}
+        r["occlusion"] = orc.detect_occlusion(r["dmap_l"], r["dmap_r"], dminl - 100)
+        r["filled"] = orc.fill_occlusion(r["occlusion"], dminl)
+        return r
+
+    def from_q(q):
+        st = [cgf_ref.states(x) for x in q]
+        return planes(q, [x["z"] for x in st], [x["best"] for x in st], subpix_ref.dmap_of)
+
+    sg = [sgm_ref.outputs(c) for c in cost]
+    plain = orc.stereo_pair(gray[0], gray[1], D, dminl=dminl, dminr=0)
+    want = {"sgm": planes([x["agg"] for x in sg], [x["z"] for x in sg], [x["best"] for x in sg],
+                          lambda z, best, dmin: (dmin + z).astype(np.float32)),
+            "cross": from_q([cross_ref.aggregate(g[:, :, None], c, **cross_kw) for g, c in zip(gray, cost)]),
+            "cgf": from_q([cgf_ref.aggregate(g, c) for g, c in zip(rgb, cost)]),
+            "off": {k + "_" + v: plain[k + v] for k in ("best", "dmap") for v in "lr"}}
+    want["off"].update(occlusion=plain["occlusion"], filled=plain["filled"])
+    cp = _lib.CrossParams()
+    for k, v in cross_kw.items():
+        setattr(cp, k, v)
+    maps = ("best_l", "best_r", "dmap_l", "dmap_r", "occlusion", "filled")
+    #        mode, the aggregated volumes asked, slices per launch
+    steps = [("sgm", True, 0), ("cross", False, 0), ("cgf", True, 0), ("cross", True, 5), ("sgm", False, 0), ("cgf", False, 0),
+             ("off", False, 0)]
+    ctx = C.c_void_p()
+    smx.check(L.smx_create(C.byref(smx.default_params()), w, h, D, C.byref(ctx)))
+    try:
+        for i, (mode, vol, bound) in enumerate(steps):
+            smx.check(L.smx_ctx_set_aggregation(ctx, _lib.AGG_MODES["sgm" if mode == "sgm" else "guided"], None))
+            smx.check(L.smx_ctx_set_cross(ctx, C.byref(cp) if mode == "cross" else None))
+            smx.check(L.smx_ctx_set_guidance(ctx, 1 if mode == "cgf" else 0))
+            names = maps + (("agg_l", "agg_r") if vol else ())
+            bufs = {k: np.full((D, h, w) if k.startswith("agg") else (h, w), np.nan, np.float32) for k in names}
+            out = _lib.PairOut(**{k: v.ctypes.data for k, v in bufs.items()})
+            smx.check(L.smx_set_max_slices_per_launch(bound))
+            try:
+                if mode == "cgf":
+                    rc = L.smx_ctx_stereo_pair_rgb(ctx, rgb[0].ctypes.data, rgb[1].ctypes.data, 3, dminl, 0, C.byref(out))
+                else:
+                    rc = L.smx_ctx_stereo_pair(ctx, gray[0].ctypes.data, gray[1].ctypes.data, dminl, 0, C.byref(out))
+            finally:
+                L.smx_set_max_slices_per_launch(0)
+            smx.check(rc)
+            for k in names:
+                ref = np.asarray(want[mode][k], np.float32).reshape(bufs[k].shape)
+                assert np.array_equal(bufs[k].view(np.uint32), ref.view(np.uint32)), (i, mode, k)
+        assert not np.array_equal(want["sgm"]["dmap_l"], want["cross"]["dmap_l"])
+        assert not np.array_equal(want["cross"]["dmap_l"], want["cgf"]["dmap_l"])
+    finally:
+        smx.check(L.smx_destroy(ctx))
 
 
 @pytest.mark.gpu
