@@ -44,6 +44,16 @@ bool report_mismatches(const T* expected, const T* got, int len) {
     }
     return mismatches == 0;
 }
+
+// What the aggregation wrappers' host_gpu_compare ends with: the twin's best costs, labels and (where asked for) aggregated
+// volume against the GPU's, and the stage's line if all agree.
+void compare_aggregation(const char* stage, std::vector<float>& tb, std::vector<float>& td, std::vector<float>& ta, float* best,
+                         float* disp_map, float* agg, int n, int size_d) {
+    bool ok = check_errors(tb.data(), best, n);
+    ok = check_errors(td.data(), disp_map, n) && ok;
+    if (agg) ok = check_errors(ta.data(), agg, n * size_d) && ok;
+    if (ok) cout << stage << " ok!" << endl;
+}
 }  // namespace
 
 bool check_errors(float* resCPU, float* resGPU, int len) { return report_mismatches(resCPU, resGPU, len); }
@@ -190,10 +200,7 @@ void compute_colour_guided_filter(unsigned char* rgb, int channels, float* cost,
         std::vector<float> ta(agg ? (size_t)w * h * size_d : 0);
         colour_guided_filterOnCPU(rgb, channels, cost, tb.data(), td.data(), agg ? ta.data() : nullptr, w, h, size_d, dmin,
                                   smx_config().params.radius, smx_config().params.eps);
-        bool ok = check_errors(tb.data(), filter_cost, w * h);
-        ok = check_errors(td.data(), disp_map, w * h) && ok;
-        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
-        if (ok) cout << "Colour guided filter ok!" << endl;
+        compare_aggregation("Colour guided filter", tb, td, ta, filter_cost, disp_map, agg, w * h, size_d);
     }
 }
 
@@ -209,10 +216,7 @@ void cross_aggregate(unsigned char* guide, int channels, float* cost, float* fil
     if (host_gpu_compare) {
         std::vector<float> ta(agg ? (size_t)w * h * size_d : 0);
         cross_aggregateOnCPU(guide, channels, cost, tb.data(), td.data(), agg ? ta.data() : nullptr, w, h, size_d, dmin, p);
-        bool ok = check_errors(tb.data(), filter_cost, w * h);
-        ok = check_errors(td.data(), disp_map, w * h) && ok;
-        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
-        if (ok) cout << "Cross-based aggregation ok!" << endl;
+        compare_aggregation("Cross-based aggregation", tb, td, ta, filter_cost, disp_map, agg, w * h, size_d);
     }
 }
 
@@ -223,9 +227,6 @@ void sgm_aggregate(float* cost, float* agg, float* best, float* disp_map, const 
     if (host_gpu_compare) {
         std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
         sgm_aggregateOnCPU(cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d, dmin, p);
-        bool ok = check_errors(tb.data(), best, w * h);
-        ok = check_errors(td.data(), disp_map, w * h) && ok;
-        if (agg) ok = check_errors(ta.data(), agg, w * h * size_d) && ok;
-        if (ok) cout << "Semi-global matching ok!" << endl;
+        compare_aggregation("Semi-global matching", tb, td, ta, best, disp_map, agg, w * h, size_d);
     }
 }

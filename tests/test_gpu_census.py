@@ -8,8 +8,6 @@ k_census works on 64 x 8 tiles, k_census_cost_pair on 256 columns x 16 slices: t
 Run on the GPU box:  python -m pytest tests -m gpu -q -k census
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import stereo_matching_cuda_amd as smx
 from stereo_matching_cuda_amd import _lib, synth
 
 import census_ref as ref
+from main_harness import main_cases  # noqa: F401  (a fixture)
 import subpix_ref
 import wmf_ref
 
@@ -464,13 +463,6 @@ def test_the_default_cost_is_unchanged(orc):
 # ---------------------------------------------------------------------------------------------
 # smx_main --cost census
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def main_cases():
-    import test_gpu_main_cases as mc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(mc.ROOT, "stereo_matching_cuda_amd", "host")])
-    return mc
-
-
 def _rgb_pair(orc):
     w, h, D = 129, 70, 24
     gl, gr = synth.gen_pair(w, h, D, 77)

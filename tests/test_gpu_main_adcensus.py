@@ -7,28 +7,19 @@ check_errors wiring of host/stages.cpp around it.
 
 Run on the GPU box:  python -m pytest tests -m gpu -q -k main_adcensus
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import adcensus_ref as ref
 import sgm_ref
-from test_gpu_adcensus import _finish, expected
+from main_harness import (assert_refused, check_disparity_files, check_ok_lines, check_twelve, finish_chain, main_cases,  # noqa: F401
+                          run_ok, same_bits)
+from test_gpu_adcensus import expected
 from test_gpu_census import _rgb_pair
 
 pytestmark = pytest.mark.gpu
 
 W, H = 129, 70
-
-
-@pytest.fixture(scope="module")
-def main_cases():
-    import test_gpu_main_cases as mc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(mc.ROOT, "stereo_matching_cuda_amd", "host")])
-    assert os.path.exists(mc.BIN)
-    return mc
 
 
 def _volumes(left, right, gl, gr, D, rgb, **kw):
@@ -47,21 +38,17 @@ CASES = {
 @pytest.mark.parametrize("host_compare", [False, True], ids=["plain", "host_compare"])
 @pytest.mark.parametrize("case", list(CASES))
 def test_main_writes_the_adcensus_maps(orc, main_cases, tmp_path, case, host_compare):
-    mc = main_cases
     flags, rgb, kw = CASES[case]
     left, right, gl, gr, D = _rgb_pair(orc)
     costs = _volumes(left, right, gl, gr, D, rgb, **kw)
     e = dict(expected(orc, gl, gr, D, -(D - 1), 0, 9, costs=costs, tag="main " + case))
     e.update(grayl=gl, grayr=gr, cost0l=e["costl"][0].copy(), cost0r=e["costr"][0].copy())
-    r, files = mc.run_main(mc.BIN, tmp_path, left, right, [-(D - 1), 0], flags + (["--host-compare"] if host_compare else []),
-                           timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    mc.check_twelve(orc, files, e, " ".join(flags))
-    mc.check_disparity_files(files, e["filled"], W, H, " ".join(flags))
+    r, files = run_ok(tmp_path, left, right, [-(D - 1), 0], flags + (["--host-compare"] if host_compare else []))
+    check_twelve(orc, files, e, " ".join(flags))
+    check_disparity_files(files, e["filled"], W, H, " ".join(flags))
     assert len(np.unique(e["dmapl"])) > 3 and (e["occlusion"] == -(D - 1) - 100).any()
-    for line, count in {"Grayscale ok!": 2, "AD-Census cost ok!": 2, "Occlusion ok!": 1}.items():
-        assert r.stdout.count(line) == (count if host_compare else 0), (line, r.stdout[-2000:])
+    check_ok_lines(r, {line: count if host_compare else 0 for line, count in
+                       {"Grayscale ok!": 2, "AD-Census cost ok!": 2, "Occlusion ok!": 1}.items()})
 
 
 def test_the_two_cases_differ(orc):
@@ -75,20 +62,16 @@ def test_the_two_cases_differ(orc):
 
 def test_main_adcensus_with_semi_global_matching(orc, main_cases, tmp_path):
     """--cost adcensus keeps its cost under --aggregation sgm (which implies census only where no --cost is given)."""
-    mc = main_cases
     left, right, gl, gr, D = _rgb_pair(orc)
     cl, cr = _volumes(left, right, gl, gr, D, False)
     sl, sr = sgm_ref.outputs(cl), sgm_ref.outputs(cr)
-    e = _finish(orc, dict(bestl=sl["best"], bestr=sr["best"], dmapl=(-(D - 1) + sl["z"]).astype(np.float32),
-                          dmapr=sr["z"].astype(np.float32)), -(D - 1))
+    e = finish_chain(orc, dict(bestl=sl["best"], bestr=sr["best"], dmapl=(-(D - 1) + sl["z"]).astype(np.float32),
+                               dmapr=sr["z"].astype(np.float32)), -(D - 1), D)
     e.update(grayl=gl, grayr=gr, meanl=np.zeros_like(gl), meanr=np.zeros_like(gr), cost0l=cl[0].copy(), cost0r=cr[0].copy())
-    r, files = mc.run_main(mc.BIN, tmp_path, left, right, [-(D - 1), 0], ["--cost", "adcensus", "--aggregation", "sgm",
-                                                                          "--host-compare"], timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    mc.check_twelve(orc, files, e, "adcensus sgm")
-    mc.check_disparity_files(files, e["filled"], W, H, "adcensus sgm")
-    assert r.stdout.count("Semi-global matching ok!") == 1 and r.stdout.count("AD-Census cost ok!") == 2
+    r, files = run_ok(tmp_path, left, right, [-(D - 1), 0], ["--cost", "adcensus", "--aggregation", "sgm", "--host-compare"])
+    check_twelve(orc, files, e, "adcensus sgm")
+    check_disparity_files(files, e["filled"], W, H, "adcensus sgm")
+    check_ok_lines(r, {"Semi-global matching ok!": 1, "AD-Census cost ok!": 2})
 
 
 def test_main_adcensus_colour_with_the_colour_guide_and_the_later_stages(orc, main_cases, tmp_path):
@@ -96,7 +79,6 @@ def test_main_adcensus_colour_with_the_colour_guide_and_the_later_stages(orc, ma
     and the references of the later stages (the chain of tests/test_gpu_adcensus.py); --pfm / --png16 hold the sub-pixel map."""
     import cgf_ref
     from test_gpu_adcensus import SPK, chain
-    mc = main_cases
     pct = 13.0
     left, right, gl, gr, D = _rgb_pair(orc)
     cl, cr = _volumes(left, right, gl, gr, D, True)
@@ -105,16 +87,13 @@ def test_main_adcensus_colour_with_the_colour_guide_and_the_later_stages(orc, ma
     e.update(grayl=gl, grayr=gr, meanl=np.zeros_like(gl), meanr=np.zeros_like(gr), cost0l=cl[0].copy(), cost0r=cr[0].copy())
     flags = ["--cost", "adcensus", "--ad", "rgb", "--guidance", "rgb", "--uniqueness", str(pct), "--speckle", "%d,%g" % SPK,
              "--subpixel", "parabola", "--host-compare"]
-    r, files = mc.run_main(mc.BIN, tmp_path, left, right, [-(D - 1), 0], flags, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    mc.check_twelve(orc, files, e, " ".join(flags))
+    r, files = run_ok(tmp_path, left, right, [-(D - 1), 0], flags)
+    check_twelve(orc, files, e, " ".join(flags))
     for key, fname in (("unique", "occlu_mapl_unique"), ("despeckled", "occlu_mapl_despeckled")):
-        mc.same_bits(files["png"][fname], orc.write_mat_u8(e[key]), fname)
-    mc.check_disparity_files(files, e["subpix_filled"], W, H, " ".join(flags))
+        same_bits(files["png"][fname], orc.write_mat_u8(e[key]), fname)
+    check_disparity_files(files, e["subpix_filled"], W, H, " ".join(flags))
     assert np.any(e["unique"] != e["occlusion"]) and np.any(e["subpix_filled"] != np.trunc(e["subpix_filled"]))
-    for line, count in {"AD-Census cost ok!": 2, "Colour guided filter ok!": 1, "Uniqueness ok!": 1, "Occlusion ok!": 1}.items():
-        assert r.stdout.count(line) == count, (line, r.stdout[-2000:])
+    check_ok_lines(r, {"AD-Census cost ok!": 2, "Colour guided filter ok!": 1, "Uniqueness ok!": 1, "Occlusion ok!": 1})
 
 
 REFUSED = {
@@ -135,11 +114,7 @@ REFUSED = {
 
 @pytest.mark.parametrize("case", list(REFUSED))
 def test_main_refuses(orc, main_cases, tmp_path, case):
-    mc = main_cases
     left, right, _, _, D = _rgb_pair(orc)
-    r, files = mc.run_main(mc.BIN, tmp_path, left, right, [-(D - 1), 0], REFUSED[case], timeout=60)
-    assert r.returncode == 2, (r.returncode, r.stdout + r.stderr)
-    assert any(o in r.stderr for o in ("--cost", "--adcensus", "--ad ", "--census")), r.stderr
+    r = assert_refused(tmp_path, left, right, [-(D - 1), 0], REFUSED[case], ("--cost", "--adcensus", "--ad ", "--census"))
     if case in ("ngpu", "pipeline", "unknown_cost"):
         assert "--cost" in r.stderr, r.stderr
-    assert not files["png"] and "pfm" not in files and "png16" not in files

@@ -15,15 +15,12 @@ import subprocess
 
 import numpy as np
 import pytest
-from PIL import Image
 
 import ref_fixtures as rf
 import subpix_ref
 import wmf_ref
+from main_harness import PNGS, binary, check_disparity_files, check_twelve, run_main, run_ok, same_bits, write_png  # noqa: F401  (a fixture)
 from oracle import ref_cases as rc
-
-ROOT = rf.ROOT
-BIN = os.path.join(ROOT, "stereo_matching_cuda_amd", "_build", "smx_main")
 
 CLI = [n for n in rf.names("pair") if n.startswith("cli_")]
 ONE_LABEL = "cli_one_64x9"
@@ -35,10 +32,6 @@ FLOAT_MAPS = ("bestl", "bestr", "dmapl", "dmapr", "occlusion", "filled")
 BASE_FLAGS = [[], ["--fused"]]
 MODE_FLAGS = [["--host-compare"], ["--fused", "--host-compare"], ["--ngpu", "1"], ["--fused", "--pairs", "3"],
               ["--fused", "--pairs", "3", "--pipeline"]]
-# file name -> the expected map it is the image of (u8 maps are written as they are, f32 maps through the normaliser)
-PNGS = {"image_left": "grayl", "image_right": "grayr", "image_mean_left": "meanl", "image_mean_right": "meanr",
-        "best_costl": "bestl", "best_costr": "bestr", "cost_lminus15": "cost0l", "cost_rminus15": "cost0r",
-        "occlu_mapl": "occlusion", "disparity_mapl": "dmapl", "disparity_mapr": "dmapr", "occlu_mapl_filled": "filled"}
 
 
 def test_the_case_table_holds_what_this_module_needs():
@@ -113,81 +106,10 @@ def test_recorded_maps_reach_the_wrapped_levels_of_the_normaliser(orc):
 
 
 # ---- running the binary -------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def binary():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "stereo_matching_cuda_amd", "host")])
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def write_png(path, a):
-    """(h, w) u8 -> gray, (h, w, 3) -> RGB, (h, w, 4) -> RGBA"""
-    a = np.ascontiguousarray(a, dtype=np.uint8)
-    assert a.ndim == 2 or a.shape[2] in (3, 4), a.shape
-    Image.fromarray(a).save(path)
-    return str(path)
-
-
-def read_pfm(path):
-    """(header lines, rows top-down).  The file holds the rows bottom-up."""
-    raw = open(path, "rb").read()
-    parts = raw.split(b"\n", 3)
-    w, h = (int(t) for t in parts[1].split())
-    assert len(parts[3]) == 4 * w * h, (len(parts[3]), w, h)
-    return parts[:3], np.ascontiguousarray(np.frombuffer(parts[3], "<f4").reshape(h, w)[::-1])
-
-
-def run_main(binary, tmp_path, left, right, positional, flags=(), cwd=None, outdir=None, timeout=300):
-    """Writes the pair as PNGs, runs `smx_main L R <positional> [flags] --pfm F --png16 G`, returns the finished process and
-    the decoded files: {"png": {name: array}, "pfm": (header, map), "png16": array} (whatever exists)."""
-    ldir = tmp_path / "in"
-    ldir.mkdir(exist_ok=True)
-    L, R = write_png(ldir / "left.png", left), write_png(ldir / "right.png", right)
-    out = outdir if outdir is not None else tmp_path / "out"
-    out.mkdir(exist_ok=True)
-    pfm, p16 = tmp_path / "disp.pfm", tmp_path / "disp16.png"
-    cmd = [binary, L, R] + [str(a) for a in positional] + ([str(out)] if outdir is None else []) + list(flags) + \
-          ["--pfm", str(pfm), "--png16", str(p16)]
-    r = subprocess.run(cmd, cwd=cwd or tmp_path, capture_output=True, text=True, timeout=timeout)
-    files = {"png": {f[:-4]: np.asarray(Image.open(out / f)) for f in sorted(os.listdir(out)) if f.endswith(".png")}}
-    if pfm.exists():
-        files["pfm"] = read_pfm(pfm)
-    if p16.exists():
-        a = np.asarray(Image.open(p16))
-        assert a.min() >= 0 and a.max() <= 65535
-        files["png16"] = a.astype(np.uint16)
-    return r, files
-
-
-def same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    assert got.tobytes() == want.tobytes(), f"{what}: {rf.first_difference(got, want)}"
-
-
-def check_twelve(orc, files, e, what):
-    assert set(PNGS) <= set(files["png"]), (what, sorted(files["png"]))
-    for fname, key in PNGS.items():
-        want = e[key] if e[key].dtype == np.uint8 else orc.write_mat_u8(e[key])
-        same_bits(files["png"][fname], want, f"{what} {fname}.png")
-
-
-def check_disparity_files(files, final, w, h, what):
-    """--pfm: header Pf / w h / a negative scale, rows bottom-up, -final bit for bit; --png16: clip(-final * 256, 0, 65535),
-    truncated."""
-    head, d = files["pfm"]
-    assert head[0] == b"Pf" and head[1] == b"%d %d" % (w, h) and float(head[2]) < 0, (what, head)
-    same_bits(d, -np.asarray(final, np.float32), what + " pfm")
-    want16 = np.clip(-np.asarray(final, np.float32) * np.float32(256.0), np.float32(0.0), np.float32(65535.0)).astype(np.uint16)
-    same_bits(files["png16"], want16, what + " png16")
-
-
 def run_case(orc, binary, tmp_path, name, flags):
     e = expected(orc, name)
     m = e["case"]["macros"]
-    r, files = run_main(binary, tmp_path, e["left"], e["right"], [m["D_MIN"], m["D_MAX"]], flags)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
+    r, files = run_ok(tmp_path, e["left"], e["right"], [m["D_MIN"], m["D_MAX"]], flags, timeout=300)
     assert f"Resolution : {e['case']['w']}x{e['case']['h']}" in r.stdout
     return e, r, files
 

@@ -8,18 +8,14 @@ wiring of host/main.cpp around it.
 
 Run on the GPU box:  python -m pytest tests -m gpu -q -k main_cgf
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import census_ref
 import cgf_ref
-import speckle_ref
 import subpix_ref
-import uniq_ref
-import wmf_ref
+from main_harness import (assert_refused, assert_same_files_as_plain, check_ok_lines, check_outputs, finish_chain, main_cases,  # noqa: F401
+                          run_ok)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,17 +24,9 @@ PCT = 13.0                                  # --uniqueness PCT
 W, H, D_LO, D_HI = 97, 41, -11, 0
 
 
-@pytest.fixture(scope="module")
-def main_cases():
-    import test_gpu_main_cases as mc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(mc.ROOT, "stereo_matching_cuda_amd", "host")])
-    assert os.path.exists(mc.BIN)
-    return mc
-
-
 def chain(orc, left, right, d_lo, d_hi, cost="reference", uniqueness=None, speckle=None, subpixel=None, wmf=None):
     """What smx_main --guidance rgb computes, from the references alone: {key: array}, the keys of PNGS of
-    tests/test_gpu_main_cases.py plus unique / despeckled / sub_filled / refined / final where the options ask for them."""
+    tests/main_harness.py plus unique / despeckled / sub_filled / refined / final where the options ask for them."""
     D = d_hi - d_lo + 1
     dmin = (d_lo, -d_hi)
     gl, gr = orc.gray(left), orc.gray(right)
@@ -50,22 +38,8 @@ def chain(orc, left, right, d_lo, d_hi, cost="reference", uniqueness=None, speck
     e = {"grayl": gl, "grayr": gr, "meanl": np.zeros_like(gl), "meanr": np.zeros_like(gr),      # no mean images
          "cost0l": vols[0][0].copy(), "cost0r": vols[1][0].copy(), "bestl": sl["best"], "bestr": sr["best"],
          "dmapl": subpix_ref.dmap_of(sl["z"], sl["best"], dmin[0]), "dmapr": subpix_ref.dmap_of(sr["z"], sr["best"], dmin[1])}
-    e["occlusion"] = orc.detect_occlusion(e["dmapl"], e["dmapr"], d_lo - 100)
-    kept = e["occlusion"]
-    if uniqueness:
-        ratio = np.float32(uniqueness) / (np.float32(100.0) - np.float32(uniqueness))       # main.cpp: pct / (100.0f - pct)
-        kept = e["unique"] = uniq_ref.apply(kept, sl["z"] >= 0, sl["best"], sl["uq"][0], ratio, d_lo, d_lo - 100)[0]
-    if speckle:
-        kept = e["despeckled"] = speckle_ref.speckle_filter(kept, d_lo, d_lo - 100, *speckle)
-    e["filled"] = e["final"] = orc.fill_occlusion(kept, d_lo)
-    if subpixel:
-        _, e["sub_filled"] = subpix_ref.maps(subpix_ref.MODES[subpixel], sl["z"], sl["best"], sl["nbr"][0], sl["nbr"][1],
-                                             e["dmapl"], kept, e["filled"], d_lo)
-        e["final"] = e["sub_filled"]
-    if wmf:
-        e["refined"] = wmf_ref.weighted_median(gl, e["filled"], d_lo, D, kept if wmf == "occluded" else None)
-        e["final"] = e["refined"]
-    return e
+    return finish_chain(orc, e, d_lo, D, z=sl["z"], best=sl["best"], sec=sl["uq"][0], nbr=sl["nbr"], uniqueness=uniqueness,
+                        speckle=speckle, subpixel=subpixel, wmf=wmf)
 
 
 @pytest.fixture(scope="module")
@@ -89,23 +63,13 @@ def scene(orc):
     return left, right, e
 
 
-def run(mc, tmp_path, scene, flags, left=None, right=None):
-    r, files = mc.run_main(mc.BIN, tmp_path, scene[0] if left is None else left, scene[1] if right is None else right,
-                           [D_LO, D_HI], ["--guidance", "rgb"] + flags, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    return r, files
+def run(tmp_path, scene, flags, left=None, right=None):
+    return run_ok(tmp_path, scene[0] if left is None else left, scene[1] if right is None else right, [D_LO, D_HI],
+                  ["--guidance", "rgb"] + flags)
 
 
-def check_all(orc, mc, files, e, what):
-    mc.check_twelve(orc, files, e, what)
-    assert not files["png"]["image_mean_left"].any() and not files["png"]["image_mean_right"].any(), what
-    for key, fname in (("unique", "occlu_mapl_unique"), ("despeckled", "occlu_mapl_despeckled"), ("refined", "occlu_mapl_wmf")):
-        if key in e:
-            mc.same_bits(files["png"][fname], orc.write_mat_u8(e[key]), f"{what} {fname}.png")
-        else:
-            assert fname not in files["png"], (what, fname)
-    mc.check_disparity_files(files, e["final"], W, H, what)
+def check_all(orc, files, e, what):
+    check_outputs(orc, files, e, W, H, what, mean_empty=True)
 
 
 SELF_CHECKS = {"Grayscale ok!": 2, "Colour guided filter ok!": 1, "Occlusion ok!": 1}
@@ -113,47 +77,33 @@ SELF_CHECKS = {"Grayscale ok!": 2, "Colour guided filter ok!": 1, "Occlusion ok!
 
 @pytest.mark.parametrize("host_compare", [False, True], ids=["plain", "host_compare"])
 def test_main_cgf_defaults(orc, main_cases, scene, tmp_path, host_compare):
-    r, files = run(main_cases, tmp_path, scene, ["--host-compare"] if host_compare else [])
-    check_all(orc, main_cases, files, scene[2]["default"], "cgf")
-    for line, count in SELF_CHECKS.items():
-        assert r.stdout.count(line) == (count if host_compare else 0), (line, r.stdout[-2000:])
+    r, files = run(tmp_path, scene, ["--host-compare"] if host_compare else [])
+    check_all(orc, files, scene[2]["default"], "cgf")
+    check_ok_lines(r, {line: count if host_compare else 0 for line, count in SELF_CHECKS.items()})
 
 
 def test_main_cgf_four_channels(orc, main_cases, scene, tmp_path):
     rgba = [np.concatenate((x, np.full((H, W, 1), 200, np.uint8)), axis=2) for x in scene[:2]]
-    r, files = run(main_cases, tmp_path, scene, [], *rgba)
-    check_all(orc, main_cases, files, scene[2]["default"], "cgf rgba")
+    r, files = run(tmp_path, scene, [], *rgba)
+    check_all(orc, files, scene[2]["default"], "cgf rgba")
 
 
 def test_main_cgf_census_uniqueness_speckle_subpixel(orc, main_cases, scene, tmp_path):
-    r, files = run(main_cases, tmp_path, scene, ["--cost", "census", "--uniqueness", str(PCT), "--speckle", "30,1", "--subpixel",
+    r, files = run(tmp_path, scene, ["--cost", "census", "--uniqueness", str(PCT), "--speckle", "30,1", "--subpixel",
                                                  "parabola", "--host-compare"])
-    check_all(orc, main_cases, files, scene[2]["census_all"], "cgf census uniqueness speckle subpixel")
-    for line, count in dict(SELF_CHECKS, **{"Uniqueness ok!": 1}).items():
-        assert r.stdout.count(line) == count, (line, r.stdout[-2000:])
+    check_all(orc, files, scene[2]["census_all"], "cgf census uniqueness speckle subpixel")
+    check_ok_lines(r, dict(SELF_CHECKS, **{"Uniqueness ok!": 1}))
 
 
 def test_main_cgf_uniqueness_speckle_wmf_pairs(orc, main_cases, scene, tmp_path):
-    r, files = run(main_cases, tmp_path, scene, ["--uniqueness", str(PCT), "--speckle", "30", "--wmf", "occluded", "--pairs", "2"])
+    r, files = run(tmp_path, scene, ["--uniqueness", str(PCT), "--speckle", "30", "--wmf", "occluded", "--pairs", "2"])
     assert "pairs 1 on one context" in r.stdout
-    check_all(orc, main_cases, files, scene[2]["uniq_spk_wmf"], "cgf uniqueness speckle wmf")
+    check_all(orc, files, scene[2]["uniq_spk_wmf"], "cgf uniqueness speckle wmf")
 
 
 def test_main_guidance_gray_is_the_default(main_cases, scene, tmp_path):
     """--guidance gray: every file byte for byte what a run without the option writes."""
-    blobs = []
-    for sub, flags in (("plain", []), ("gray", ["--guidance", "gray"])):
-        d = tmp_path / sub
-        d.mkdir()
-        r, _ = main_cases.run_main(main_cases.BIN, d, scene[0], scene[1], [D_LO, D_HI], flags, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        names = sorted(os.listdir(d / "out"))
-        assert len(names) == 12, names
-        blobs.append({n: (d / "out" / n).read_bytes() for n in names})
-        blobs[-1].update({n: (d / n).read_bytes() for n in ("disp.pfm", "disp16.png")})
-    assert blobs[0].keys() == blobs[1].keys()
-    for n in blobs[0]:
-        assert blobs[0][n] == blobs[1][n], n
+    assert_same_files_as_plain(tmp_path, scene[0], scene[1], [D_LO, D_HI], ["--guidance", "gray"])
 
 
 REFUSED = {
@@ -166,7 +116,4 @@ REFUSED = {
 
 @pytest.mark.parametrize("case", list(REFUSED))
 def test_main_cgf_refuses(main_cases, scene, tmp_path, case):
-    r, files = main_cases.run_main(main_cases.BIN, tmp_path, scene[0], scene[1], [D_LO, D_HI], REFUSED[case], timeout=60)
-    assert r.returncode == 2, (r.returncode, r.stdout + r.stderr)
-    assert "--guidance" in r.stderr, r.stderr
-    assert not files["png"] and "pfm" not in files and "png16" not in files
+    assert_refused(tmp_path, scene[0], scene[1], [D_LO, D_HI], REFUSED[case], "--guidance")

@@ -7,9 +7,6 @@ tests/test_host_cross_cpu.py) and the check_errors wiring of host/main.cpp aroun
 
 Run on the GPU box:  python -m pytest tests -m gpu -q -k main_cross
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -17,10 +14,9 @@ import adcensus_ref
 import census_ref
 import cgf_ref
 import cross_ref
-import speckle_ref
 import subpix_ref
-import uniq_ref
-import wmf_ref
+from main_harness import (assert_refused, assert_same_files_as_plain, check_ok_lines, check_outputs, finish_chain, main_cases,  # noqa: F401
+                          run_ok)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,17 +27,9 @@ OPTIONS = dict(l1=17, l2=8, tau1=25, tau2=8, iterations=2)
 OPTION_FLAGS = ["--cross-arms", "17,8", "--cross-tau", "25,8", "--cross-iterations", "2"]
 
 
-@pytest.fixture(scope="module")
-def main_cases():
-    import test_gpu_main_cases as mc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(mc.ROOT, "stereo_matching_cuda_amd", "host")])
-    assert os.path.exists(mc.BIN)
-    return mc
-
-
 def chain(orc, left, right, d_lo, d_hi, cost="reference", params=None, uniqueness=None, speckle=None, subpixel=None, wmf=None):
     """What smx_main --aggregation cross computes, from the references alone: {key: array}, the keys of PNGS of
-    tests/test_gpu_main_cases.py plus unique / despeckled / sub_filled / refined / final where the options ask for them."""
+    tests/main_harness.py plus unique / despeckled / sub_filled / refined / final where the options ask for them."""
     D = d_hi - d_lo + 1
     dmin = (d_lo, -d_hi)
     gl, gr = orc.gray(left), orc.gray(right)
@@ -53,22 +41,8 @@ def chain(orc, left, right, d_lo, d_hi, cost="reference", params=None, uniquenes
     e = {"grayl": gl, "grayr": gr, "meanl": np.zeros_like(gl), "meanr": np.zeros_like(gr),      # no mean images
          "cost0l": vols[0][0].copy(), "cost0r": vols[1][0].copy(), "bestl": sl["best"], "bestr": sr["best"],
          "dmapl": subpix_ref.dmap_of(sl["z"], sl["best"], dmin[0]), "dmapr": subpix_ref.dmap_of(sr["z"], sr["best"], dmin[1])}
-    e["occlusion"] = orc.detect_occlusion(e["dmapl"], e["dmapr"], d_lo - 100)
-    kept = e["occlusion"]
-    if uniqueness:
-        ratio = np.float32(uniqueness) / (np.float32(100.0) - np.float32(uniqueness))       # main.cpp: pct / (100.0f - pct)
-        kept = e["unique"] = uniq_ref.apply(kept, sl["z"] >= 0, sl["best"], sl["uq"][0], ratio, d_lo, d_lo - 100)[0]
-    if speckle:
-        kept = e["despeckled"] = speckle_ref.speckle_filter(kept, d_lo, d_lo - 100, *speckle)
-    e["filled"] = e["final"] = orc.fill_occlusion(kept, d_lo)
-    if subpixel:
-        _, e["sub_filled"] = subpix_ref.maps(subpix_ref.MODES[subpixel], sl["z"], sl["best"], sl["nbr"][0], sl["nbr"][1],
-                                             e["dmapl"], kept, e["filled"], d_lo)
-        e["final"] = e["sub_filled"]
-    if wmf:
-        e["refined"] = wmf_ref.weighted_median(gl, e["filled"], d_lo, D, kept if wmf == "occluded" else None)
-        e["final"] = e["refined"]
-    return e
+    return finish_chain(orc, e, d_lo, D, z=sl["z"], best=sl["best"], sec=sl["uq"][0], nbr=sl["nbr"], uniqueness=uniqueness,
+                        speckle=speckle, subpixel=subpixel, wmf=wmf)
 
 
 @pytest.fixture(scope="module")
@@ -87,23 +61,13 @@ def scene(orc):
     return left, right, e
 
 
-def run(mc, tmp_path, scene, flags, left=None, right=None):
-    r, files = mc.run_main(mc.BIN, tmp_path, scene[0] if left is None else left, scene[1] if right is None else right,
-                           [D_LO, D_HI], ["--aggregation", "cross"] + flags, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    return r, files
+def run(tmp_path, scene, flags, left=None, right=None):
+    return run_ok(tmp_path, scene[0] if left is None else left, scene[1] if right is None else right, [D_LO, D_HI],
+                  ["--aggregation", "cross"] + flags)
 
 
-def check_all(orc, mc, files, e, what):
-    mc.check_twelve(orc, files, e, what)
-    assert not files["png"]["image_mean_left"].any() and not files["png"]["image_mean_right"].any(), what
-    for key, fname in (("unique", "occlu_mapl_unique"), ("despeckled", "occlu_mapl_despeckled"), ("refined", "occlu_mapl_wmf")):
-        if key in e:
-            mc.same_bits(files["png"][fname], orc.write_mat_u8(e[key]), f"{what} {fname}.png")
-        else:
-            assert fname not in files["png"], (what, fname)
-    mc.check_disparity_files(files, e["final"], W, H, what)
+def check_all(orc, files, e, what):
+    check_outputs(orc, files, e, W, H, what, mean_empty=True)
 
 
 SELF_CHECKS = {"Grayscale ok!": 2, "Cross-based aggregation ok!": 1, "Occlusion ok!": 1}
@@ -111,47 +75,33 @@ SELF_CHECKS = {"Grayscale ok!": 2, "Cross-based aggregation ok!": 1, "Occlusion 
 
 @pytest.mark.parametrize("host_compare", [False, True], ids=["plain", "host_compare"])
 def test_main_cross_defaults(orc, main_cases, scene, tmp_path, host_compare):
-    r, files = run(main_cases, tmp_path, scene, ["--host-compare"] if host_compare else [])
-    check_all(orc, main_cases, files, scene[2]["default"], "cross")
-    for line, count in SELF_CHECKS.items():
-        assert r.stdout.count(line) == (count if host_compare else 0), (line, r.stdout[-2000:])
+    r, files = run(tmp_path, scene, ["--host-compare"] if host_compare else [])
+    check_all(orc, files, scene[2]["default"], "cross")
+    check_ok_lines(r, {line: count if host_compare else 0 for line, count in SELF_CHECKS.items()})
 
 
 def test_main_cross_four_channels(orc, main_cases, scene, tmp_path):
     rgba = [np.concatenate((x, np.full((H, W, 1), 200, np.uint8)), axis=2) for x in scene[:2]]
-    r, files = run(main_cases, tmp_path, scene, [], *rgba)
-    check_all(orc, main_cases, files, scene[2]["default"], "cross rgba")
+    r, files = run(tmp_path, scene, [], *rgba)
+    check_all(orc, files, scene[2]["default"], "cross rgba")
 
 
 def test_main_cross_every_option_with_adcensus_uniqueness_speckle_subpixel(orc, main_cases, scene, tmp_path):
-    r, files = run(main_cases, tmp_path, scene, OPTION_FLAGS + ["--cost", "adcensus", "--uniqueness", str(PCT), "--speckle", "30,1",
+    r, files = run(tmp_path, scene, OPTION_FLAGS + ["--cost", "adcensus", "--uniqueness", str(PCT), "--speckle", "30,1",
                                                                 "--subpixel", "parabola", "--host-compare"])
-    check_all(orc, main_cases, files, scene[2]["options"], "cross options adcensus uniqueness speckle subpixel")
-    for line, count in dict(SELF_CHECKS, **{"Uniqueness ok!": 1}).items():
-        assert r.stdout.count(line) == count, (line, r.stdout[-2000:])
+    check_all(orc, files, scene[2]["options"], "cross options adcensus uniqueness speckle subpixel")
+    check_ok_lines(r, dict(SELF_CHECKS, **{"Uniqueness ok!": 1}))
 
 
 def test_main_cross_census_wmf_pairs(orc, main_cases, scene, tmp_path):
-    r, files = run(main_cases, tmp_path, scene, OPTION_FLAGS + ["--cost", "census", "--wmf", "occluded", "--pairs", "2"])
+    r, files = run(tmp_path, scene, OPTION_FLAGS + ["--cost", "census", "--wmf", "occluded", "--pairs", "2"])
     assert "pairs 1 on one context" in r.stdout
-    check_all(orc, main_cases, files, scene[2]["census_wmf"], "cross census wmf")
+    check_all(orc, files, scene[2]["census_wmf"], "cross census wmf")
 
 
 def test_main_aggregation_guided_is_the_default(main_cases, scene, tmp_path):
     """--aggregation guided: every file byte for byte what a run without the option writes."""
-    blobs = []
-    for sub, flags in (("plain", []), ("guided", ["--aggregation", "guided"])):
-        d = tmp_path / sub
-        d.mkdir()
-        r, _ = main_cases.run_main(main_cases.BIN, d, scene[0], scene[1], [D_LO, D_HI], flags, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        names = sorted(os.listdir(d / "out"))
-        assert len(names) == 12, names
-        blobs.append({n: (d / "out" / n).read_bytes() for n in names})
-        blobs[-1].update({n: (d / n).read_bytes() for n in ("disp.pfm", "disp16.png")})
-    assert blobs[0].keys() == blobs[1].keys()
-    for n in blobs[0]:
-        assert blobs[0][n] == blobs[1][n], n
+    assert_same_files_as_plain(tmp_path, scene[0], scene[1], [D_LO, D_HI], ["--aggregation", "guided"])
 
 
 X = ["--aggregation", "cross"]
@@ -181,8 +131,4 @@ REFUSED = {   # flags -> the option stderr names
 @pytest.mark.parametrize("case", list(REFUSED))
 def test_main_cross_refuses(main_cases, scene, tmp_path, case):
     flags, name = REFUSED[case]
-    r, files = main_cases.run_main(main_cases.BIN, tmp_path, scene[0], scene[1], [D_LO, D_HI], flags, timeout=60)
-    assert r.returncode == 2, (r.returncode, r.stdout + r.stderr)
-    assert name in r.stderr, r.stderr
-    assert not files["png"] and "pfm" not in files and "png16" not in files
-
+    assert_refused(tmp_path, scene[0], scene[1], [D_LO, D_HI], flags, name)

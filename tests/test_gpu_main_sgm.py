@@ -17,9 +17,8 @@ from stereo_matching_cuda_amd import synth
 
 import census_ref
 import sgm_ref
-import speckle_ref
-import subpix_ref
-import wmf_ref
+from main_harness import (Image, assert_refused, assert_same_files_as_plain, build_main, check_ok_lines, check_outputs,
+                          finish_chain, main_cases, run_ok, write_png)  # noqa: F401  (main_cases: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +27,6 @@ SPK = (30, 1.0)
 SCENES = {"main": (129, 70, 70, 4711, -69, 0),        # the shape of the scene of tests/test_gpu_sgm.py
           "x0": (61, 23, 6, 11, -5, 6),               # d_hi != 0: the right volume starts at -d_hi, not at 0
           "d256": (40, 6, 16, 5, -255, 0)}            # 256 labels: the largest the gate admits (4 values per lane)
-
-
-@pytest.fixture(scope="module")
-def main_cases():
-    import test_gpu_main_cases as mc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(mc.ROOT, "stereo_matching_cuda_amd", "host")])
-    assert os.path.exists(mc.BIN)
-    return mc
 
 
 def rgb_pair(orc, name):
@@ -51,7 +42,7 @@ def rgb_pair(orc, name):
 def chain(orc, gl, gr, d_lo, d_hi, cost="census", cp=census_ref.DEFAULTS, sp=(10, 120, 8), speckle=None, subpixel=None,
           wmf=None):
     """What smx_main --aggregation sgm computes, from the references alone: {key: array}, the keys of PNGS of
-    tests/test_gpu_main_cases.py plus despeckled / sub_filled / refined / final where the options ask for them."""
+    tests/main_harness.py plus despeckled / sub_filled / refined / final where the options ask for them."""
     D = d_hi - d_lo + 1
     dmin = (d_lo, -d_hi)
     if cost == "census":
@@ -62,19 +53,7 @@ def chain(orc, gl, gr, d_lo, d_hi, cost="census", cp=census_ref.DEFAULTS, sp=(10
     e = {"grayl": gl, "grayr": gr, "meanl": np.zeros_like(gl), "meanr": np.zeros_like(gr),      # SGM has no mean images
          "cost0l": vols[0][0].copy(), "cost0r": vols[1][0].copy(), "bestl": sl["best"], "bestr": sr["best"],
          "dmapl": (dmin[0] + sl["z"]).astype(np.float32), "dmapr": (dmin[1] + sr["z"]).astype(np.float32)}
-    e["occlusion"] = orc.detect_occlusion(e["dmapl"], e["dmapr"], d_lo - 100)
-    kept = e["occlusion"]
-    if speckle:
-        kept = e["despeckled"] = speckle_ref.speckle_filter(e["occlusion"], d_lo, d_lo - 100, *speckle)
-    e["filled"] = e["final"] = orc.fill_occlusion(kept, d_lo)
-    if subpixel:
-        _, e["sub_filled"] = subpix_ref.maps(subpix_ref.MODES[subpixel], sl["z"], sl["best"], sl["nbr"][0], sl["nbr"][1],
-                                             e["dmapl"], kept, e["filled"], d_lo)
-        e["final"] = e["sub_filled"]
-    if wmf:
-        e["refined"] = wmf_ref.weighted_median(gl, e["filled"], d_lo, D, kept if wmf == "occluded" else None)
-        e["final"] = e["refined"]
-    return e
+    return finish_chain(orc, e, d_lo, D, z=sl["z"], best=sl["best"], nbr=sl["nbr"], speckle=speckle, subpixel=subpixel, wmf=wmf)
 
 
 def build_scenes(orc):
@@ -118,28 +97,13 @@ def scenes(orc):
     return build_scenes(orc)
 
 
-def run(mc, tmp_path, scene, flags, timeout=120):
+def run(tmp_path, scene, flags, timeout=120):
     left, right, _, _, d_lo, d_hi, _ = scene
-    r, files = mc.run_main(mc.BIN, tmp_path, left, right, [d_lo, d_hi], flags, timeout=timeout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "error at element" not in r.stdout, r.stdout[-2000:]
-    return r, files
+    return run_ok(tmp_path, left, right, [d_lo, d_hi], flags, timeout=timeout)
 
 
-def check_all(orc, mc, files, e, gl, what):
-    mc.check_twelve(orc, files, e, what)
-    assert not files["png"]["image_mean_left"].any() and not files["png"]["image_mean_right"].any(), what
-    for key, fname in (("despeckled", "occlu_mapl_despeckled"), ("refined", "occlu_mapl_wmf")):
-        if key in e:
-            mc.same_bits(files["png"][fname], orc.write_mat_u8(e[key]), f"{what} {fname}.png")
-        else:
-            assert fname not in files["png"], (what, fname)
-    mc.check_disparity_files(files, e["final"], gl.shape[1], gl.shape[0], what)
-
-
-def check_ok_lines(r, lines):
-    for line, count in lines.items():
-        assert r.stdout.count(line) == count, (line, count, r.stdout[-2000:])
+def check_all(orc, files, e, gl, what):
+    check_outputs(orc, files, e, gl.shape[1], gl.shape[0], what, mean_empty=True)
 
 
 SELF_CHECKS = {"Grayscale ok!": 2, "Semi-global matching ok!": 1, "Occlusion ok!": 1}
@@ -150,24 +114,24 @@ SELF_CHECKS = {"Grayscale ok!": 2, "Semi-global matching ok!": 1, "Occlusion ok!
 def test_main_sgm_defaults(orc, main_cases, scenes, tmp_path, host_compare):
     """Census 9x7 th 62, p 10,120, 8 paths: the twelve images, empty mean images, the census cost slices."""
     scene = scenes["main"]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm"] + (["--host-compare"] if host_compare else []))
-    check_all(orc, main_cases, files, scene[6]["default"], scene[2], "sgm")
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm"] + (["--host-compare"] if host_compare else []))
+    check_all(orc, files, scene[6]["default"], scene[2], "sgm")
     check_ok_lines(r, SELF_CHECKS if host_compare else {k: 0 for k in SELF_CHECKS})
 
 
 def test_main_sgm_reference_cost(orc, main_cases, scenes, tmp_path):
     scene = scenes["main"]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm", "--cost", "reference", "--sgm-p", "5,40",
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm", "--cost", "reference", "--sgm-p", "5,40",
                                                  "--sgm-paths", "4", "--host-compare"])
-    check_all(orc, main_cases, files, scene[6]["reference"], scene[2], "sgm on the reference cost")
+    check_all(orc, files, scene[6]["reference"], scene[2], "sgm on the reference cost")
     check_ok_lines(r, SELF_CHECKS)
 
 
 def test_main_sgm_census_options_speckle_subpixel(orc, main_cases, scenes, tmp_path):
     scene = scenes["main"]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm", "--census-window", "5x3", "--census-th", "9",
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm", "--census-window", "5x3", "--census-th", "9",
                                                  "--speckle", "30,1", "--subpixel", "parabola", "--host-compare"])
-    check_all(orc, main_cases, files, scene[6]["spk_sub"], scene[2], "sgm speckle subpixel")
+    check_all(orc, files, scene[6]["spk_sub"], scene[2], "sgm speckle subpixel")
     check_ok_lines(r, SELF_CHECKS)
 
 
@@ -177,42 +141,32 @@ def test_main_sgm_census_options_speckle_subpixel(orc, main_cases, scenes, tmp_p
     ids=["speckle_wmf_occluded", "wmf_all_host_compare"])
 def test_main_sgm_weighted_median(orc, main_cases, scenes, tmp_path, flags, key, lines):
     scene = scenes["main"]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm"] + flags)
-    check_all(orc, main_cases, files, scene[6][key], scene[2], "sgm " + " ".join(flags))
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm"] + flags)
+    check_all(orc, files, scene[6][key], scene[2], "sgm " + " ".join(flags))
     check_ok_lines(r, lines)
 
 
 def test_main_sgm_pairs_on_one_context(orc, main_cases, scenes, tmp_path):
     """--pairs 3: the context's SGM volumes and workspace are used three times; the files are those of one pair."""
     scene = scenes["main"]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm", "--pairs", "3"])
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm", "--pairs", "3"])
     assert "pairs 2 on one context" in r.stdout and "(pipelined entry)" not in r.stdout, r.stdout
-    check_all(orc, main_cases, files, scene[6]["default"], scene[2], "sgm pairs 3")
+    check_all(orc, files, scene[6]["default"], scene[2], "sgm pairs 3")
 
 
 @pytest.mark.parametrize("name", ["x0", "d256"])
 def test_main_sgm_other_ranges(orc, main_cases, scenes, tmp_path, name):
     scene = scenes[name]
-    r, files = run(main_cases, tmp_path, scene, ["--aggregation", "sgm", "--host-compare"])
-    check_all(orc, main_cases, files, scene[6]["default"], scene[2], "sgm " + name)
+    r, files = run(tmp_path, scene, ["--aggregation", "sgm", "--host-compare"])
+    check_all(orc, files, scene[6]["default"], scene[2], "sgm " + name)
     check_ok_lines(r, SELF_CHECKS)
 
 
 def test_main_aggregation_guided_is_the_default(main_cases, scenes, tmp_path):
     """--aggregation guided: every file byte for byte what a run without the option writes."""
-    blobs = []
-    for sub, flags in (("plain", []), ("guided", ["--aggregation", "guided"])):
-        d = tmp_path / sub
-        d.mkdir()
-        run(main_cases, d, scenes["main"], flags)
-        names = sorted(os.listdir(d / "out"))
-        assert len(names) == 12, names
-        blobs.append({n: (d / "out" / n).read_bytes() for n in names})
-        blobs[-1].update({n: (d / n).read_bytes() for n in ("disp.pfm", "disp16.png")})
-    assert blobs[0].keys() == blobs[1].keys()
-    for n in blobs[0]:
-        assert blobs[0][n] == blobs[1][n], n
-    assert np.asarray(main_cases.Image.open(tmp_path / "plain" / "out" / "image_mean_left.png")).any()
+    left, right, _, _, d_lo, d_hi, _ = scenes["main"]
+    plain = assert_same_files_as_plain(tmp_path, left, right, [d_lo, d_hi], ["--aggregation", "guided"])
+    assert np.asarray(Image.open(plain / "out" / "image_mean_left.png")).any()
 
 
 # ---- runs that must be refused -------------------------------------------------------------------------------------------
@@ -237,18 +191,15 @@ REFUSED = {
 def test_main_sgm_refuses(main_cases, scenes, tmp_path, case):
     flags, rng = REFUSED[case]
     left, right = scenes["x0"][:2]
-    r, files = main_cases.run_main(main_cases.BIN, tmp_path, left, right, list(rng or (-5, 6)), flags, timeout=60)
-    assert r.returncode == 2, (r.returncode, r.stdout + r.stderr)
-    assert "--aggregation" in r.stderr or "--sgm" in r.stderr, r.stderr
-    assert not files["png"] and "pfm" not in files and "png16" not in files
+    assert_refused(tmp_path, left, right, list(rng or (-5, 6)), flags, ("--aggregation", "--sgm"))
 
 
 def test_main_refuses_aggregation_without_a_value(main_cases, scenes, tmp_path):
     left, right = scenes["x0"][:2]
-    L, R = main_cases.write_png(tmp_path / "left.png", left), main_cases.write_png(tmp_path / "right.png", right)
+    L, R = write_png(tmp_path / "left.png", left), write_png(tmp_path / "right.png", right)
     out = tmp_path / "out"
     out.mkdir()
-    r = subprocess.run([main_cases.BIN, L, R, "-5", "6", str(out), "--aggregation"], cwd=tmp_path, capture_output=True,
+    r = subprocess.run([build_main(), L, R, "-5", "6", str(out), "--aggregation"], cwd=tmp_path, capture_output=True,
                        text=True, timeout=60)
     assert r.returncode == 2 and "--aggregation needs a value" in r.stderr, (r.returncode, r.stdout + r.stderr)
     assert not os.listdir(out)

@@ -16,13 +16,13 @@ from stereo_matching_cuda_amd import _lib, synth
 import speckle_ref as ref
 import subpix_ref
 import wmf_ref
+from main_harness import binary  # noqa: F401  (a fixture)
 from guarded import Guarded
 from test_gpu_wmf import _eq, _messy
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "stereo_matching_cuda_amd", "_build", "smx_main")
 
 
 def _geometry():
@@ -348,12 +348,6 @@ def test_context(pairs):
 # ---------------------------------------------------------------------------------------------
 INDEPENDENT = ["image_left", "image_right", "image_mean_left", "image_mean_right", "best_costl", "best_costr",
                "cost_lminus15", "cost_rminus15", "occlu_mapl", "disparity_mapl", "disparity_mapr"]
-
-
-@pytest.fixture(scope="module")
-def binary():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "stereo_matching_cuda_amd", "host")])
-    return BIN
 
 
 @pytest.mark.parametrize("flags", [["--fused"], ["--host-compare"]])

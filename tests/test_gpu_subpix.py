@@ -16,11 +16,11 @@ import stereo_matching_cuda_amd as smx
 from stereo_matching_cuda_amd import _lib, synth
 
 import subpix_ref as ref
+from main_harness import binary  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "stereo_matching_cuda_amd", "_build", "smx_main")
 MODES = ["parabola", "equiangular"]
 
 
@@ -295,12 +295,6 @@ def test_kitti_pipeline():
 OUTPUTS = ["image_left", "image_right", "image_mean_left", "image_mean_right", "best_costl",
            "best_costr", "cost_lminus15", "cost_rminus15", "occlu_mapl", "disparity_mapl",
            "disparity_mapr", "occlu_mapl_filled"]
-
-
-@pytest.fixture(scope="module")
-def binary():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "stereo_matching_cuda_amd", "host")])
-    return BIN
 
 
 def _stage(tmp_path):

@@ -11,9 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from main_harness import binary  # noqa: F401  (a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "stereo_matching_cuda_amd", "host")
-BIN = os.path.join(ROOT, "stereo_matching_cuda_amd", "_build", "smx_main")
 
 REFERENCE_SIGNATURES = {   # reference header -> host function names it must still declare
     "rgb_to_grayscale.cuh": ["rgb_to_grayscale", "sumArraysOnHost", "check_errors_grayscale"],
@@ -32,13 +33,6 @@ REFERENCE_SIGNATURES = {   # reference header -> host function names it must sti
 OUTPUTS = ["image_left", "image_right", "image_mean_left", "image_mean_right", "best_costl",
            "best_costr", "cost_lminus15", "cost_rminus15", "occlu_mapl", "disparity_mapl",
            "disparity_mapr", "occlu_mapl_filled"]
-
-
-@pytest.fixture(scope="module")
-def binary():
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    assert os.path.exists(BIN)
-    return BIN
 
 
 def test_headers_keep_the_reference_names():
