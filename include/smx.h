@@ -288,7 +288,8 @@ int smx_dev_agg_fallback(const void* d_workspace, int* ring_walker_reran);
  *   0 = auto: the fused single-kernel aggregation when radius <= 9 and -- where the costs are built from the images --
  *       th_color <= 59745 and th_grad <= 59872 (the cost of a partner outside the image comes from a sentinel cell of
  *       60000 that must saturate both truncations), else the multi-kernel path; the fused call picks the comb walker
- *       (smx_agg_v5.hip: radius 9, costs built from the images, th_color <= 59744) or the ring walker
+ *       (smx_agg_v5.hip: radius 9, 1 <= eps < 1e30, costs built from the images, alpha in [0, 1], th_color <= 59744 and
+ *       both thresholds exact in fp16) or the ring walker
  *       (smx_agg_v4.hip: any radius <= 9, materialised cost volumes)
  *   1 = force multi-kernel            2 = force fused (error where no walker applies), walker chosen as in auto
  *   3 = fused, ring walker forced     5 = fused, comb walker forced (error where it does not apply)
