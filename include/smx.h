@@ -781,6 +781,90 @@ int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int cha
  * smx_ctx_stereo_pair_async while it is on.  The workspace and the chunk buffers are allocated on first use. */
 int smx_ctx_set_cross(smx_ctx* ctx, const smx_cross_params* p);
 
+/* ------------------------------------------------------------------------------------
+ * Region voting and 16-direction interpolation on the cross arms (not a stage of the reference; opt-in, behind speckle removal)
+ * ---------------------------------------------------------------------------------- */
+
+/* The outlier refinement of Mei et al. 2011 on the support regions of smx_dev_cross_arms: an invalid pixel takes the most
+ * frequent valid label of its own cross region (iterative region voting), what is left looks along 16 directions for its
+ * nearest valid pixels (proper interpolation), and what neither reaches is left to the scan-line fill.  Integers only: the
+ * result is the same bits in every run and under every schedule.  tests/vote_ref.py is this definition in numpy; the result
+ * equals it bit for bit.
+ *
+ * Inputs.
+ *   disp     f32 [h][w]: the left map behind the LR check, uniqueness and speckle stages
+ *   arms     u32 [h][w], as smx_dev_cross_arms packs them (l | r << 8 | u << 16 | d << 24).  A region is cut at the image
+ *            border whatever its arms say (the arms of smx_dev_cross_arms never reach across it).
+ *   guide    u8 [h][w][channels], channels 1, 3 or 4, a fourth byte ignored, with the cross aggregation's D(p, q); read for
+ *            the mismatches only: it may be NULL with interpolate == 0 or disp_r == NULL
+ *   disp_r   optional f32 [h][w]: the right WTA map
+ *   dmin, size_d   the label range
+ *   d_lr     from smx_params
+ *
+ * Which pixels are valid and which vote.
+ *   valid:   a pixel is valid iff it "counts" by the speckle filter's rule with vmin = (float)dmin: finite and
+ *            (float)(int)disp[p] >= vmin, with the truncation and saturation written there.
+ *   outlier: every other pixel.
+ *   voter:   a valid pixel votes iff its bin b = (int)disp[p] - dmin lies in 0 .. size_d - 1.  A valid pixel outside that
+ *            range stays as it is and casts no vote.
+ *   The call is total on any bits: NaN, +-inf, -0, fractions, values beyond int.
+ *
+ * Region of p = (y, x): the aggregation's horizontal-first region, all (y', x') with y - u(p) <= y' <= y + d(p) and
+ * x - l(y', x) <= x' <= x + r(y', x).  With every pixel a voter its count is area_HV.
+ *
+ * Voting, `iterations` rounds.  The rounds are Jacobi: round k reads map M_k only and writes M_{k+1}, with M_0 = disp.
+ *   For an outlier p of M_k, H_p(b) is the number of voters of M_k in its region with bin b, and S_p the sum over b.
+ *   b* is the largest b among those with the largest count (the project's "last slice of equal costs wins").
+ *   The vote is accepted iff S_p > tau_s and 100 * H_p(b*) > tau_h_pct * S_p, in exact integers.
+ *   On acceptance M_{k+1}[p] = (float)(dmin + b*).  Every other pixel, a valid one included, is copied bit for bit.
+ *
+ * Interpolation: one pass over M_iterations as a snapshot; skipped with interpolate == 0.
+ *   directions: for every remaining outlier p and each of the 16 directions, in this order: (dx, dy) = (1,0), (2,1), (1,1),
+ *               (1,2), (0,1), (-1,2), (-1,1), (-2,1), (-1,0), (-2,-1), (-1,-1), (-1,-2), (0,-1), (1,-2), (1,-1), (2,-1).
+ *   candidate:  the candidate of a direction is the first q_j = p + j (dx, dy), j = 1, 2, ..., inside the image that is a voter.
+ *   mismatch:   p is a mismatch iff disp_r is given and some s in 0 .. size_d - 1 has, with d = dmin + s, 0 <= x + d < w and
+ *               fabsf((float)d + disp_r[y][x + d]) <= d_lr: the LR check's own test and sign convention, in f32.  A NaN fails it.
+ *   occlusion:  every other remaining outlier.  With disp_r == NULL every outlier is one.
+ *   value:      an occlusion takes the largest candidate value, which is the background as fill_occlusion sees it (of equal
+ *               values, +0 and -0 among them, the first in the order above).  A mismatch takes the candidate with the smallest
+ *               D(p, q), the first in the order above among equals.  The candidate's bits are copied.
+ *   no candidate: the pixel is copied unchanged.
+ *
+ * Defaults (tau_s, tau_h_pct, iterations: Mei's values): tau_s 20, tau_h_pct 40, iterations 5, interpolate 1.  Valid:
+ * tau_s >= 0, 0 <= tau_h_pct <= 99, 0 <= iterations <= 8, interpolate 0 or 1, 1 <= size_d <= 512, channels 1, 3 or 4,
+ * w, h >= 1, w*h < 2^31; anything else is SMX_E_ARG before any device call.
+ *
+ * smx_dev_region_vote: device pointers; max(iterations, 1) + 1 kernel launches on `stream` (one per round -- a copy where there
+ * is none -- and the interpolation, which with interpolate == 0 is the copy into d_out), no allocation, no synchronisation
+ * (graph-capturable).  d_out == d_disp is allowed.  The memory contract is that of the other stages: nothing is written outside
+ * [0, smx_vote_workspace_bytes(w, h)) of d_ws (two maps of n floats plus 255 bytes; 0 for invalid w, h) and the w*h floats of
+ * d_out; the workspace may hold anything and needs no alignment; a smaller one is SMX_E_WS before any launch; the inputs are
+ * not modified.
+ * smx_region_vote: host pointers, synchronous; it builds the arms from cross' l1, l2, tau1, tau2 (iterations ignored; NULL:
+ * the defaults) with smx_dev_cross_arms on `guide`, which it therefore needs always. */
+typedef struct smx_vote_params { int tau_s, tau_h_pct, iterations, interpolate; } smx_vote_params;
+void smx_default_vote_params(smx_vote_params* p);
+size_t smx_vote_workspace_bytes(int w, int h);
+int smx_dev_region_vote(const smx_vote_params* p, const uint32_t* d_arms, const uint8_t* d_guide, int channels, const float* d_disp,
+                        const float* d_disp_r, float* d_out, int w, int h, int dmin, int size_d, int d_lr, void* d_ws,
+                        size_t ws_bytes, void* stream);
+int smx_region_vote(const smx_vote_params* p, const smx_cross_params* cross, const uint8_t* guide, int channels, const float* disp,
+                    const float* disp_r, float* out, int w, int h, int dmin, int size_d, int d_lr);
+/* Test hook, NOT part of the stable contract (it may change or go with the kernels): the tile of the voting kernel (columns,
+ * rows), so that the tests put their shapes and outliers on the seams between tiles. */
+int smx_vote_geometry(int* tile_cols, int* tile_rows);
+/* Region voting of this context.  vote NULL switches it off (the default); cross NULL means smx_default_cross_params (its
+ * iterations are ignored).  While it is on, smx_ctx_stereo_pair / _rgb builds the arms of the left guide -- the gray left image,
+ * or the colour one through the _rgb entry -- and runs smx_dev_region_vote behind LR check -> uniqueness -> speckle removal,
+ * with the right winner-take-all map as disp_r; out->filled becomes the scan-line fill of the voted map.  The validity map is
+ * NOT replaced: the sub-pixel fit's test and wmf "occluded" keep taking the map they take without it, so a voted pixel gets no
+ * sub-pixel offset (its label is not its winner's) and stays a pixel for the weighted median to refine.  It works with every
+ * aggregation and every cost.  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on.  smx_ctx_vote_map copies the voted
+ * map of the last synchronous pair of the context (n floats); SMX_E_ARG if that pair ran without it.  Buffers are allocated on
+ * first use. */
+int smx_ctx_set_vote(smx_ctx* ctx, const smx_vote_params* vote, const smx_cross_params* cross);
+int smx_ctx_vote_map(smx_ctx* ctx, float* voted);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

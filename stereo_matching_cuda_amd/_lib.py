@@ -67,6 +67,11 @@ class CrossParams(C.Structure):
     _fields_ = [("l1", C.c_int), ("l2", C.c_int), ("tau1", C.c_int), ("tau2", C.c_int), ("iterations", C.c_int)]
 
 
+class VoteParams(C.Structure):
+    """smx_vote_params: region voting and interpolation on the cross arms (not a stage of the reference)."""
+    _fields_ = [("tau_s", C.c_int), ("tau_h_pct", C.c_int), ("iterations", C.c_int), ("interpolate", C.c_int)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -95,6 +100,7 @@ _AP = C.POINTER(AdCensusParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
 _XP = C.POINTER(CrossParams)
+_VP = C.POINTER(VoteParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -197,6 +203,13 @@ SIGNATURES = {
     "smx_dev_cross_wta_pair": (_i, [_XP, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "smx_cross_aggregate": (_i, [_XP, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_cross": (_i, [_vp, _XP]),
+    "smx_default_vote_params": (None, [_VP]),
+    "smx_vote_workspace_bytes": (_sz, [_i, _i]),
+    "smx_dev_region_vote": (_i, [_VP, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "smx_region_vote": (_i, [_VP, _XP, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "smx_vote_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "smx_ctx_set_vote": (_i, [_vp, _VP, _XP]),
+    "smx_ctx_vote_map": (_i, [_vp, _vp]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -298,6 +311,12 @@ def default_sgm_params():
 def default_cross_params():
     p = CrossParams()
     lib().smx_default_cross_params(C.byref(p))
+    return p
+
+
+def default_vote_params():
+    p = VoteParams()
+    lib().smx_default_vote_params(C.byref(p))
     return p
 
 

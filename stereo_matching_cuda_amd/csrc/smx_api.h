@@ -48,6 +48,10 @@ bool sgm_shape_ok(int w, int h, int size_d);
 bool cross_params_ok(const smx_cross_params* p);       // (smx_cross.hip, beside the limits of its kernels)
 bool cross_shape_ok(int w, int h);
 constexpr const char* CROSS_RANGES = "needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and 1 <= iterations <= 4";
+bool vote_params_ok(const smx_vote_params* p);         // (smx_vote.hip, beside the limits of its kernels)
+bool vote_shape_ok(int w, int h, int size_d);
+constexpr const char* VOTE_RANGES = "needs tau_s >= 0, 0 <= tau_h_pct <= 99, 0 <= iterations <= 8 and interpolate 0 or 1";
+constexpr const char* VOTE_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

@@ -743,6 +743,35 @@ int smx_dev_cross_wta_pair(const smx_cross_params* p, const uint8_t* d_guide_l, 
                                  d_nbr, d_uq, d_ws, chunk, (hipStream_t)stream);
 }
 
+// ---- region voting on the cross arms (not in the reference; smx_vote.hip) -------------------------------------------
+void smx_default_vote_params(smx_vote_params* p) {
+    if (!p) return;
+    p->tau_s = 20; p->tau_h_pct = 40; p->iterations = 5; p->interpolate = 1;
+}
+
+size_t smx_vote_workspace_bytes(int w, int h) { return vote_shape_ok(w, h, 1) ? vote_workspace_bytes(w, h) : 0; }
+
+int smx_vote_geometry(int* tile_cols, int* tile_rows) {
+    SMX_ARG(tile_cols && tile_rows);
+    vote_tile(tile_cols, tile_rows);
+    return SMX_OK;
+}
+
+int smx_dev_region_vote(const smx_vote_params* p, const uint32_t* d_arms, const uint8_t* d_guide, int channels, const float* d_disp,
+                        const float* d_disp_r, float* d_out, int w, int h, int dmin, int size_d, int d_lr, void* d_ws,
+                        size_t ws_bytes, void* stream) {
+    if (!vote_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_region_vote: %s", VOTE_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!vote_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_region_vote: %s", VOTE_SHAPES);
+    SMX_ARG(d_arms && d_disp && d_out);
+    SMX_ARG(d_guide || !p->interpolate || !d_disp_r);
+    if (!d_ws || ws_bytes < vote_workspace_bytes(w, h))
+        return fail(SMX_E_WS, "smx_dev_region_vote: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
+                    vote_workspace_bytes(w, h));
+    return launch_region_vote(p, d_arms, d_guide, channels, d_disp, d_disp_r, d_out, w, h, dmin, size_d, d_lr, d_ws,
+                              (hipStream_t)stream);
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);

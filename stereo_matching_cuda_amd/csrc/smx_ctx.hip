@@ -51,6 +51,12 @@ struct smx_ctx {
     // cross-based aggregation (smx_ctx_set_cross)
     bool cross = false;
     smx_cross_params cross_params;
+    // region voting (smx_ctx_set_vote): the arms of the left guide [h][w], the voted left map [h][w] and the stage's workspace
+    bool vote = false;
+    bool vote_valid = false;    // the map belongs to the last synchronous pair
+    smx_vote_params vote_params;
+    smx_cross_params vote_arms;
+    DevBuf varms, voted, vote_ws;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -85,7 +91,7 @@ struct smx_ctx {
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -107,6 +113,11 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     if (need.census) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
     if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
+    if (need.vote) {
+        SMX_HIP(c->varms.ensure(c->n * sizeof(uint32_t)));
+        SMX_HIP(c->voted.ensure(fb));
+        SMX_HIP(c->vote_ws.ensure(vote_workspace_bytes(c->w, c->h)));
+    }
     // The chunk of ctx_aggregate_chunks.  Colour guide and cross: the halving rule on their workspace.  The guided flow from
     // census codes: every slice with whole volumes, else what fits 1 GiB of cost slices exactly (at least one).  Then the
     // calling thread's smx_set_max_slices_per_launch bounds it, like the chunks inside every entry.
@@ -253,6 +264,19 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
         kept = spk;
     }
+    if (need.vote) {
+        // the outliers of that map take the vote of their cross regions on the left guide, then the 16-direction interpolation;
+        // the fill starts over from the voted map, and `kept` stays the map whose validity test the later stages read
+        const uint8_t* guide = in.channels ? in.rgb_l : in.left;
+        const int ch = in.channels ? in.channels : 1;
+        uint32_t* arms = c->varms.as<uint32_t>();
+        float* voted = c->voted.as<float>();
+        if ((rc = smx_dev_cross_arms(&c->vote_arms, guide, nullptr, ch, w, h, arms, st))) return rc;
+        if ((rc = smx_dev_region_vote(&c->vote_params, arms, guide, ch, kept, out.map + n, voted, w, h, in.dminl, size_d, p->d_lr,
+                                      c->vote_ws.p, vote_workspace_bytes(w, h), st)))
+            return rc;
+        if ((rc = launch_fill_occlusion(voted, out.fil, w, h, (float)in.dminl, st))) return rc;
+    }
     if (!need.subpix) return SMX_OK;
     return smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl, c->sub.as<float>(),
                                  c->subf.as<float>(), st);
@@ -351,7 +375,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
                                "smx_ctx_stereo_pair_rgb", who);
     const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross};
+                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote};
     if ((rc = ctx_reserve(c, need))) return rc;
     if (c->adcensus && !c->adc_tab_valid) {
         SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
@@ -359,7 +383,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         c->adc_tab_valid = true;
     }
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
-    c->sub_valid = c->spk_valid = c->uq_valid = false;
+    c->sub_valid = c->spk_valid = c->uq_valid = c->vote_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     uint8_t* rgbL = channels ? c->rgb.as<uint8_t>() : nullptr;
     uint8_t* rgbR = channels ? rgbL + n * (size_t)channels : nullptr;
@@ -391,6 +415,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
+    c->vote_valid = need.vote;
     return SMX_OK;
 }
 
@@ -505,6 +530,30 @@ int smx_ctx_speckle_map(smx_ctx* c, float* despeckled) {
     return SMX_OK;
 }
 
+int smx_ctx_set_vote(smx_ctx* c, const smx_vote_params* vote, const smx_cross_params* cross) {
+    SMX_ARG(c);
+    if (vote) {
+        if (!vote_params_ok(vote)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_RANGES);
+        smx_cross_params cp;
+        smx_default_cross_params(&cp);
+        if (cross) { cp = *cross; cp.iterations = 1; }
+        if (!cross_params_ok(&cp)) return fail(SMX_E_ARG, "smx_ctx_set_vote: the arms: %s", CROSS_RANGES);
+        if (!vote_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_SHAPES);
+        c->vote_params = *vote;
+        c->vote_arms = cp;
+    }
+    c->vote = vote != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_vote_map(smx_ctx* c, float* voted) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
+    if (!c->vote_valid) return fail(SMX_E_ARG, "smx_ctx_vote_map: the last smx_ctx_stereo_pair ran without region voting");
+    if (voted) SMX_HIP(c->voted.download(voted, c->n * sizeof(float)));
+    return SMX_OK;
+}
+
 int smx_ctx_set_uniqueness(smx_ctx* c, float ratio) {
     SMX_ARG(c);
     if (!uniq_ratio_ok(ratio)) return fail(SMX_E_ARG, "smx_ctx_set_uniqueness: the ratio must be finite and >= 0 (0 = off)");
@@ -556,6 +605,7 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
     if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
+    if (c->vote) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: region voting is on (smx_ctx_set_vote): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)

@@ -294,6 +294,33 @@ int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int cha
                                 });
 }
 
+int smx_region_vote(const smx_vote_params* p, const smx_cross_params* cross, const uint8_t* guide, int channels, const float* disp,
+                    const float* disp_r, float* out, int w, int h, int dmin, int size_d, int d_lr) {
+    if (!vote_params_ok(p)) return fail(SMX_E_ARG, "smx_region_vote: %s", VOTE_RANGES);
+    smx_cross_params cp;
+    smx_default_cross_params(&cp);
+    if (cross) { cp = *cross; cp.iterations = 1; }
+    if (!cross_params_ok(&cp)) return fail(SMX_E_ARG, "smx_region_vote: the arms: %s", CROSS_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!vote_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_region_vote: %s", VOTE_SHAPES);
+    SMX_ARG(guide && disp && out);
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), wsb = vote_workspace_bytes(w, h);
+    DevBuf dG, dA, dD, dR, dW;
+    SMX_HIP(dG.upload(guide, n * channels));
+    SMX_HIP(dA.ensure(n * sizeof(uint32_t)));
+    SMX_HIP(dD.upload(disp, fb));
+    if (disp_r) SMX_HIP(dR.upload(disp_r, fb));
+    SMX_HIP(dW.ensure(wsb));
+    int rc;
+    if ((rc = smx_dev_cross_arms(&cp, dG.as<uint8_t>(), nullptr, channels, w, h, dA.as<uint32_t>(), nullptr))) return rc;
+    if ((rc = smx_dev_region_vote(p, dA.as<uint32_t>(), dG.as<uint8_t>(), channels, dD.as<float>(), disp_r ? dR.as<float>() : nullptr,
+                                  dD.as<float>(), w, h, dmin, size_d, d_lr, dW.p, wsb, nullptr)))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dD.download(out, fb));
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -75,4 +75,9 @@ int launch_cross_arms(const smx_cross_params* p, const uint8_t* guide_l, const u
 int launch_cross_wta_pair(const smx_cross_params* p, const uint8_t* guide_l, const uint8_t* guide_r, int ch, const float* cost_l,
                           const float* cost_r, int w, int h, int s_begin, int s_end, int64_t* keys, float* agg, float* nbr,
                           float* uq, void* ws, int chunk, hipStream_t st);
+// smx_vote.hip: region voting and interpolation on the cross arms (smx_dev_region_vote); ws: vote_workspace_bytes(w, h) bytes
+size_t vote_workspace_bytes(int w, int h);
+int launch_region_vote(const smx_vote_params* p, const uint32_t* arms, const uint8_t* guide, int ch, const float* disp,
+                       const float* disp_r, float* out, int w, int h, int dmin, int size_d, int d_lr, void* ws, hipStream_t st);
+void vote_tile(int* tw, int* th);
 }  // namespace smx

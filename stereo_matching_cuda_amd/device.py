@@ -26,7 +26,8 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None):
+                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
+                 vote=None, vote_arms=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -74,7 +75,14 @@ class PairPipeline:
         cross_params: CrossParams, None = the defaults): the flow and the buffers of guidance="rgb" -- cost chunk (the
         reference's cost into self.cross_cost, census or AD-Census) -> smx_dev_cross_wta_pair over chunks of
         `slices_in_flight` slices, with the workspace self.cross_ws -- and slice sub-ranges are allowed.  The guide is the
-        colour pair rgb_l=, rgb_r= of aggregate() / run() where it is given, else the gray pair.  Not with guidance="rgb"."""
+        colour pair rgb_l=, rgb_r= of aggregate() / run() where it is given, else the gray pair.  Not with guidance="rgb".
+        vote: None, True (the defaults) or VoteParams -- region voting and 16-direction interpolation on the cross arms (not a
+        stage of the reference; include/smx.h smx_dev_region_vote behind the finish; vote_arms: CrossParams whose l1, l2, tau1,
+        tau2 build the support regions, None = the defaults): region_vote() behind despeckle() builds the arms of the left guide
+        -- the colour image where this aggregate() took one, else the gray one -- into self.vote_arms_plane and votes on the last
+        of occlusion / unique / despeckled with self.dmap[1] as the right map, into self.voted; self.filled becomes the fill of
+        self.voted.  The validity map is not replaced: the sub-pixel fit and wmf="occluded" take the map they take without
+        it.  Works with every aggregation and cost; size_d <= 512.  With None nothing is allocated or launched."""
         if guidance not in (None, "rgb"):
             raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
         if guidance and aggregation:
@@ -98,6 +106,12 @@ class PairPipeline:
             raise ValueError(f"subpixel must be None, 'parabola' or 'equiangular', not {subpixel!r}")
         if speckle is not None and speckle is not True and not isinstance(speckle, _lib.SpeckleParams):
             raise ValueError(f"speckle must be None, True or SpeckleParams, not {speckle!r}")
+        if vote is not None and vote is not True and not isinstance(vote, _lib.VoteParams):
+            raise ValueError(f"vote must be None, True or VoteParams, not {vote!r}")
+        if vote_arms is not None and not isinstance(vote_arms, _lib.CrossParams):
+            raise ValueError(f"vote_arms must be None or CrossParams, not {vote_arms!r}")
+        if vote_arms is not None and vote is None:
+            raise ValueError("vote_arms belongs to vote=: region voting is off")
         self.lib = _lib.lib()
         self.w, self.h, self.size_d = int(w), int(h), int(size_d)
         self.n = self.w * self.h
@@ -183,6 +197,18 @@ class PairPipeline:
         self.despeckled = torch.empty((self.h, self.w), **f) if self.speckle else None
         self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
         self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
+        self.vote = _lib.default_vote_params() if vote is True else vote
+        self.vote_arms = self.voted = self.vote_arms_plane = self.vote_ws = None
+        self.vote_ws_bytes = 0
+        if self.vote:
+            self.vote_arms = _lib.CrossParams.from_buffer_copy(vote_arms) if vote_arms is not None else _lib.default_cross_params()
+            self.vote_arms.iterations = 1              # (not read by the arms)
+            self.vote_ws_bytes = int(self.lib.smx_vote_workspace_bytes(self.w, self.h))
+            if self.vote_ws_bytes == 0 or not 1 <= self.size_d <= 512:
+                raise ValueError(f"region voting does not take {self.w} x {self.h} x {self.size_d} (w*h < 2^31, size_d <= 512)")
+            self.voted = torch.empty((self.h, self.w), **f)
+            self.vote_arms_plane = torch.empty((self.h, self.w), dtype=torch.int32, device=dev)
+            self.vote_ws = torch.empty(self.vote_ws_bytes, dtype=torch.uint8, device=dev)
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
         self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm else None
         if cost == "adcensus":
@@ -217,6 +243,7 @@ class PairPipeline:
         rank's slices, both views.  Leaves packed keys in self.keys.  rgb_l / rgb_r: the colour guides of
         guidance="rgb" and the images of the AD term of cost="adcensus" with colour 1 (required then, refused otherwise)."""
         colour_cost = self.cost == "adcensus" and bool(self.adcensus_params.colour)
+        self._rgb = None                # (the colour pair of THIS aggregation, where it takes one)
         if self.guidance:
             if rgb_l is None or rgb_r is None:
                 raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
@@ -480,6 +507,8 @@ class PairPipeline:
             self.uniqueness_filter()
         if self.speckle:
             self.despeckle()
+        if self.vote:
+            self.region_vote()
         if self.subpixel:
             self.subpixel_maps()
         if self.wmf:
@@ -510,6 +539,23 @@ class PairPipeline:
             self.filled.copy_(self.despeckled)
             _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
 
+    def region_vote(self):
+        """self.voted = the last of the LR-checked / uniqueness-filtered / despeckled left maps with its outliers voted on by
+        their cross regions and interpolated along 16 directions (smx_dev_cross_arms on the left guide of the last
+        aggregate(), then smx_dev_region_vote), and self.filled rewritten as the fill of that map."""
+        if self._guide is None:
+            raise RuntimeError("region_vote() needs the left image: run an aggregation first")
+        guide, ch = (self._rgb[0], int(self._rgb[0].shape[2])) if self._rgb is not None else (self._guide, 1)
+        with self._on_device():
+            L, st = self.lib, self._stream()
+            _lib.check(L.smx_dev_cross_arms(C.byref(self.vote_arms), _dp(guide), None, ch, self.w, self.h, _dp(self.vote_arms_plane),
+                                            st))
+            _lib.check(L.smx_dev_region_vote(C.byref(self.vote), _dp(self.vote_arms_plane), _dp(guide), ch, _dp(self._kept()),
+                                             _dp(self.dmap[1]), _dp(self.voted), self.w, self.h, self.dminl, self.size_d,
+                                             int(self.params.d_lr), _dp(self.vote_ws), self.vote_ws_bytes, st))
+            self.filled.copy_(self.voted)
+            _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+
     def _kept(self):
         """The map whose validity test tells which pixels the fill replaced."""
         return self.despeckled if self.speckle else self.unique if self.uniqueness else self.occlusion
@@ -537,7 +583,7 @@ class PairPipeline:
 
     def finish_per_call(self):
         """The same through the per-stage entry points (the reference's call sequence, seven launches); with the uniqueness
-        test or speckle removal on, uniqueness_filter() / despeckle() behind them, as in finish().  The sub-pixel fit and the
+        test or speckle removal on, uniqueness_filter() / despeckle() / region_vote() behind them, as in finish().  The sub-pixel fit and the
         weighted median are not run."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
@@ -555,6 +601,8 @@ class PairPipeline:
             self.uniqueness_filter()
         if self.speckle:
             self.despeckle()
+        if self.vote:
+            self.region_vote()
 
     def run(self, gray_l, gray_r, rgb_l=None, rgb_r=None):
         self.aggregate(gray_l, gray_r, rgb_l=rgb_l, rgb_r=rgb_r)
@@ -583,6 +631,8 @@ class PairPipeline:
             r["unique"], r["margin"] = c(self.unique), c(self.margin)
         if self.speckle:
             r["despeckled"] = c(self.despeckled)
+        if self.vote:
+            r["voted"] = c(self.voted)
         if self.subpixel:
             r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.sub[0]), c(self.sub[1]), c(self.sub_filled)
         return r

@@ -6,6 +6,7 @@
 // correct twin (the reference's version writes pixel indices as labels and divides in double,
 // SURVEY.md section 4), so that check_errors() can hold it against the GPU result bit for bit.
 // Everything is plain f32 arithmetic in source order; build with -ffp-contract=off.
+#include <climits>
 #include <limits>
 #include <vector>
 
@@ -17,6 +18,7 @@
 #include "guidedFilter.cuh"
 #include "integral.cuh"
 #include "occlusion.cuh"
+#include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
@@ -355,6 +357,88 @@ void cross_aggregateOnCPU(const unsigned char* guide, int channels, const float*
         if (agg) std::memcpy(agg + (size_t)z * n, q.data(), n * sizeof(float));
         dispSelectOnCPU(q.data(), filter_cost, disp_map, (int)n, dmin + z);
     }
+}
+
+// ---- regionVoting.cuh (not in the reference) -----------------------------------------------------
+// The definition of include/smx.h (above smx_vote_workspace_bytes) pixel by pixel: per outlier one histogram over its region,
+// walked row by row and pixel by pixel; per remaining outlier the 16 directions one after the other.
+void region_voteOnCPU(const unsigned char* guide, int channels, const float* disparity, const float* disparity_right, float* out,
+                      const int w, const int h, const int dmin, const int size_d, const smx_vote_params& p,
+                      const smx_cross_params& arms) {
+    const size_t n = (size_t)w * h;
+    const int nc = channels == 1 ? 1 : 3;
+    const float vmin = (float)dmin, d_lr = (float)smx_config().params.d_lr;
+    static const int dir[4][2] = {{-1, 0}, {1, 0}, {0, -1}, {0, 1}};       // left, right, up, down
+    vector<int> arm[4];
+    for (int e = 0; e < 4; ++e) {
+        arm[e].resize(n);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) arm[e][(size_t)y * w + x] = cross_arm(guide, channels, nc, w, h, x, y, dir[e][0], dir[e][1], arms);
+    }
+    auto trunc_sat = [](float v) { return v >= 2147483648.0f ? INT_MAX : v < -2147483648.0f ? INT_MIN : (int)v; };
+    auto valid = [&](float v) { return std::fabs(v) <= 3.402823466e38f && (float)trunc_sat(v) >= vmin; };
+    auto bin = [&](float v) -> int {            // of a voter, else -1
+        if (!valid(v)) return -1;
+        const long long b = (long long)trunc_sat(v) - dmin;
+        return b >= 0 && b < size_d ? (int)b : -1;
+    };
+    vector<float> cur(disparity, disparity + n), next(n);
+    vector<int> hist(size_d, 0);
+    for (int k = 0; k < p.iterations; ++k) {
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t id = (size_t)y * w + x;
+                next[id] = cur[id];
+                if (valid(cur[id])) continue;
+                long long total = 0;
+                for (int yy = y - arm[2][id]; yy <= y + arm[3][id]; ++yy) {
+                    const size_t c = (size_t)yy * w + x;
+                    for (int xx = x - arm[0][c]; xx <= x + arm[1][c]; ++xx) {
+                        const int b = bin(cur[(size_t)yy * w + xx]);
+                        if (b >= 0) { ++hist[b]; ++total; }
+                    }
+                }
+                int top = 0;
+                for (int b = 0; b < size_d; ++b)
+                    if (hist[b] >= hist[top]) top = b;         // the largest bin among the largest counts
+                if (total > p.tau_s && 100ll * hist[top] > (long long)p.tau_h_pct * total) next[id] = (float)(int)((long long)dmin + top);
+                std::fill(hist.begin(), hist.end(), 0);
+            }
+        cur.swap(next);
+    }
+    static const int step[16][2] = {{1, 0},  {2, 1},   {1, 1},   {1, 2},   {0, 1},  {-1, 2}, {-1, 1}, {-2, 1},
+                                    {-1, 0}, {-2, -1}, {-1, -1}, {-1, -2}, {0, -1}, {1, -2}, {1, -1}, {2, -1}};     // (dx, dy)
+    for (size_t id = 0; id < n; ++id) out[id] = cur[id];
+    if (!p.interpolate) return;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t id = (size_t)y * w + x;
+            if (valid(cur[id])) continue;
+            bool mismatch = false;
+            if (disparity_right)
+                for (int s = 0; s < size_d && !mismatch; ++s) {
+                    const long long d = (long long)dmin + s, xr = x + d;
+                    if (xr < 0 || xr >= w) continue;
+                    volatile float sum = (float)(int)d + disparity_right[(size_t)y * w + (size_t)xr];      // one rounded f32 sum
+                    mismatch = std::fabs(sum) <= d_lr;
+                }
+            bool has = false;
+            float best_v = 0.0f;
+            int best_d = 0;
+            for (int e = 0; e < 16; ++e)
+                for (int qx = x + step[e][0], qy = y + step[e][1]; qx >= 0 && qx < w && qy >= 0 && qy < h;
+                     qx += step[e][0], qy += step[e][1]) {
+                    const size_t q = (size_t)qy * w + qx;
+                    if (bin(cur[q]) < 0) continue;
+                    const int dist = cross_dist(guide + q * channels, guide + id * channels, nc);
+                    // strict comparisons: the first in the order among equals
+                    if (!has || (mismatch ? dist < best_d : cur[q] > best_v)) out[id] = cur[q];
+                    if (!has || dist < best_d) best_d = dist;
+                    if (!has || cur[q] > best_v) best_v = cur[q];
+                    has = true;
+                    break;
+                }
+        }
 }
 
 // ---- occlusion.cuh -------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //                                    D_MIN..D_MAX from the macros, outputs into ./data/
 //   smx_main L.png R.png [dmin dmax [outdir]] [options]
 // options (not in the reference).  The opt-in costs, aggregations and stages (--cost census / adcensus, --aggregation sgm /
-// cross, --guidance rgb, --uniqueness, --speckle, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
+// cross, --guidance rgb, --uniqueness, --speckle, --vote, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
 // an entry says otherwise; none of them goes with --ngpu or --pipeline:
 //   --fused           one device-resident call for everything after the gray conversion
 //                     (smx_stereo_pair: cost built on the fly inside the fused aggregation) instead of
@@ -43,6 +43,17 @@
 //                     most DIFF (default 1) are invalidated like LR failures.  Writes occlu_mapl_despeckled.png beside
 //                     the 12 images; occlu_mapl_filled.png (and --wmf occluded, --subpixel, --pfm, --png16 behind it) then
 //                     come from the despeckled map
+//   --vote [S,PCT[,N]]  region voting and 16-direction interpolation behind speckle removal (smx_region_vote,
+//                     smx_ctx_set_vote; Mei et al.'s outlier refinement, not in the reference), on every single-GPU path: an
+//                     invalid pixel takes the most frequent valid label of its cross region if the region holds more than S
+//                     valid pixels (default 20) and the label more than PCT percent of them (0 .. 99; default 40), in N rounds
+//                     (0 .. 8; default 5); what is left looks along 16 directions (--vote-interpolate 0|1, default 1).  The
+//                     value is optional: a word that starts with a digit behind --vote is taken as it.  --vote-arms L1,L2 and
+//                     --vote-tau T1,T2 give the support regions (the ranges and defaults of --cross-arms / --cross-tau); their
+//                     guide is the left colour image where the pair runs through the colour entry, else the gray one.  Writes
+//                     occlu_mapl_voted.png beside the 12 images; occlu_mapl_filled.png (and --wmf, --subpixel, --pfm, --png16
+//                     behind it) then come from the voted map, while the validity test of --subpixel and --wmf occluded stays
+//                     the one without it.  At most 512 labels.  With --host-compare the CPU twin (region_voteOnCPU) redoes it
 //   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
 //                     census cost, --census-window / --census-th included, unless --cost reference is given): the same
 //                     twelve images, the two mean images empty.
@@ -94,6 +105,7 @@
 #include "helpers.cuh"
 #include "occlusion.cuh"
 #include "png_io.h"
+#include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "crossAggregation.cuh"
 #include "sgm.cuh"
@@ -123,6 +135,9 @@ struct Options {
     smx_cross_params cross_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
+    bool vote = false;       // --vote
+    smx_vote_params vote_params;
+    smx_cross_params vote_arms;
     bool rgb = false;        // --guidance rgb
     float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
@@ -234,12 +249,34 @@ const ValueOption value_options[] = {
          const int got = std::sscanf(v.c_str(), "%d%c%f%c", &size, &comma, &diff, &rest);
          o.speckle = true;
          return (got == 1 || (got == 3 && comma == ',')) && size >= 0 && diff >= 0.0f && diff <= 3.4e38f; }},
+    {"--vote-interpolate", "0 or 1", [](auto& v, auto& o) {
+         o.vote_params.interpolate = word(v, {"0", "1"});
+         return o.vote_params.interpolate >= 0; }},
+    {"--vote-arms", "L1,L2 with 1 <= L1 <= 63 and 0 <= L2 <= L1", [](auto& v, auto& o) {
+         int& l1 = o.vote_arms.l1; int& l2 = o.vote_arms.l2;
+         return pair_of(v, ',', l1, l2) && l1 >= 1 && l1 <= 63 && l2 >= 0 && l2 <= l1; }},
+    {"--vote-tau", "T1,T2 with 1 <= T2 <= T1 <= 256", [](auto& v, auto& o) {
+         int& t1 = o.vote_arms.tau1; int& t2 = o.vote_arms.tau2;
+         return pair_of(v, ',', t1, t2) && t2 >= 1 && t2 <= t1 && t1 <= 256; }},
     {"--uniqueness", "a percentage PCT with 0 <= PCT < 100", [](auto& v, auto& o) {
          char* end = nullptr;
          const float pct = std::strtof(v.c_str(), &end);
          o.uniqueness = pct / (100.0f - pct);
          return !v.empty() && !*end && pct >= 0.0f && pct < 100.0f; }},
     {"--guidance", "`gray` or `rgb`", [](auto& v, auto& o) { const int k = word(v, {"gray", "rgb"}); o.rgb = k == 1; return k >= 0; }},
+};
+
+// An option whose value may be left out: the next word is its value iff it starts with a digit.  `set` gets "" without one.
+const ValueOption optional_value_options[] = {
+    {"--vote", "S,PCT[,N] with S >= 0, 0 <= PCT <= 99 and 0 <= N <= 8", [](auto& v, auto& o) {
+         smx_vote_params& p = o.vote_params;
+         o.vote = true;
+         if (v.empty()) return true;
+         char c1 = 0, c2 = 0, rest = 0;
+         p.tau_s = p.tau_h_pct = -1;
+         const int got = std::sscanf(v.c_str(), "%d%c%d%c%d%c", &p.tau_s, &c1, &p.tau_h_pct, &c2, &p.iterations, &rest);
+         return ((got == 3 && c1 == ',') || (got == 5 && c1 == ',' && c2 == ',')) && p.tau_s >= 0 && p.tau_h_pct >= 0 &&
+                p.tau_h_pct <= 99 && p.iterations >= 0 && p.iterations <= 8; }},
 };
 
 // A row of a table of refusals: the first row that holds prints its message, and the exit status is 2.
@@ -252,6 +289,8 @@ Options parse(int argc, char** argv) {
     smx_default_sgm_params(&o.sgm_params);
     smx_default_cross_params(&o.cross_params);
     smx_default_adcensus_params(&o.adc_params);
+    smx_default_vote_params(&o.vote_params);
+    smx_default_cross_params(&o.vote_arms);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -259,6 +298,14 @@ Options parse(int argc, char** argv) {
         o.given.push_back(a);
         const Switch* s = std::find_if(std::begin(switches), std::end(switches), [&](const Switch& row) { return a == row.name; });
         if (s != std::end(switches)) { o.*(s->target) = true; continue; }
+        const ValueOption* opt_k = std::find_if(std::begin(optional_value_options), std::end(optional_value_options),
+                                                [&](const ValueOption& row) { return a == row.name; });
+        if (opt_k != std::end(optional_value_options)) {
+            const bool has_value = i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9';
+            const std::string v = has_value ? argv[++i] : "";
+            if (!opt_k->set(v, o)) return refuse(a + " needs " + opt_k->needs + ", not `" + v + "`");
+            continue;
+        }
         const ValueOption* k = std::find_if(std::begin(value_options), std::end(value_options),
                                             [&](const ValueOption& row) { return a == row.name; });
         if (k == std::end(value_options)) return refuse("unknown option " + a);
@@ -278,7 +325,9 @@ Options parse(int argc, char** argv) {
          "--adcensus-lambda, --adcensus-scale and --ad need --cost adcensus"},
         {o.saw({"--sgm-p", "--sgm-paths"}) && !o.sgm, "--sgm-p and --sgm-paths need --aggregation sgm"},
         {o.saw({"--cross-arms", "--cross-tau", "--cross-iterations"}) && !o.cross,
-         "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross"}};
+         "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross"},
+        {o.saw({"--vote-interpolate", "--vote-arms", "--vote-tau"}) && !o.vote,
+         "--vote-interpolate, --vote-arms and --vote-tau need --vote"}};
     for (const Rule& r : rules)
         if (r.refused) return refuse(r.message);
     return o;
@@ -314,6 +363,7 @@ struct Maps {
     std::vector<unsigned char> mean[2];
     std::vector<float> occlusion, filled;
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
+    std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
     std::vector<float> unique;         // --uniqueness: the LR-checked left map without its ambiguous winners
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
     std::vector<float> refined;        // --wmf: the weighted median of the filled left map
@@ -393,6 +443,17 @@ void check_finish_twins(const Job& j, Maps& m, std::vector<float>& agg_l) {
         ok = check_errors(twin.data(), m.despeckled.data(), n) && ok;
         lr = twin;
     }
+    if (opt.vote) {
+        // (the guide of the context: the left colour image where the pair ran through the colour entry)
+        const bool colour = opt.rgb || opt.ad_rgb || opt.cross;
+        std::vector<float> twin(n);
+        region_voteOnCPU(colour ? j.in.rgb[0] : j.gray[0], colour ? j.in.channels[0] : 1, lr.data(), m.dmap[1].data(), twin.data(),
+                         j.w, j.h, j.d_lo, j.size_d, opt.vote_params, opt.vote_arms);
+        const bool same = check_errors(twin.data(), m.voted.data(), n);
+        if (same) std::cout << "Region voting ok!" << std::endl;
+        ok = same && ok;
+        lr = twin;
+    }
     fill_occlusionOnCPU(lr.data(), j.w, j.h, vmin);
     ok = check_errors(lr.data(), m.filled.data(), n) && ok;
     if (ok) std::cout << "Occlusion ok!" << std::endl;
@@ -423,6 +484,12 @@ void run_stage_by_stage(const Job& j, Maps& m) {
                        host_compare);
     }
     m.filled = opt.speckle ? m.despeckled : m.occlusion;
+    if (opt.vote) {
+        m.voted.resize(n);
+        region_vote(j.gray[0], 1, m.filled.data(), m.dmap[1].data(), m.voted.data(), w, h, j.d_lo, j.size_d, opt.vote_params,
+                    opt.vote_arms, host_compare);
+        m.filled = m.voted;
+    }
     fill_occlusion(m.filled.data(), w, h, (float)j.d_lo);                                // main.cu:154-155
 }
 
@@ -476,6 +543,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.adcensus) CHECK(smx_ctx_set_adcensus(ctx, &opt.adc_params));
     if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
     if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
+    if (opt.vote) CHECK(smx_ctx_set_vote(ctx, &opt.vote_params, &opt.vote_arms));
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
@@ -516,6 +584,10 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
         m.despeckled.resize(n);
         CHECK(smx_ctx_speckle_map(ctx, m.despeckled.data()));
     }
+    if (opt.vote) {
+        m.voted.resize(n);
+        CHECK(smx_ctx_vote_map(ctx, m.voted.data()));
+    }
     if (uniq) {
         m.unique.resize(n);
         CHECK(smx_ctx_uniqueness_map(ctx, m.unique.data(), nullptr));
@@ -544,6 +616,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"occlu_mapl.png", m.occlusion},     {"disparity_mapl.png", m.dmap[0]},
                                   {"disparity_mapr.png", m.dmap[1]},   {"occlu_mapl_filled.png", m.filled},
                                   {"occlu_mapl_despeckled.png", m.despeckled}, {"occlu_mapl_unique.png", m.unique},
+                                  {"occlu_mapl_voted.png", m.voted},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
     for (const U8Out& o : u8_outputs)
@@ -621,6 +694,8 @@ int main(int argc, char** argv) {
         {opt.sgm && labels > SMX_SGM_MAX_D, "--aggregation sgm takes at most " + std::to_string(SMX_SGM_MAX_D) + " labels"},
         {opt.speckle && multi, "--speckle" + with_multi},
         {uniq && multi, "--uniqueness" + with_multi},
+        {opt.vote && multi, "--vote" + with_multi},
+        {opt.vote && labels > 512, "--vote takes at most 512 labels"},
         {opt.ngpu < 0 || opt.ngpu > smx_device_count(),
          "--ngpu " + std::to_string(opt.ngpu) + ": this node shows " + std::to_string(smx_device_count()) + " HIP device(s)"}};
     for (const Rule& r : refusals)

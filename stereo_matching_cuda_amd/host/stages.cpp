@@ -11,6 +11,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "colourGuidedFilter.cuh"
 #include "sgm.cuh"
+#include "regionVoting.cuh"
 #include "speckle.cuh"
 #include "wmf.cuh"
 
@@ -184,6 +185,19 @@ void speckle_filter(float* disparity, float* out, const int w, const int h, floa
         std::vector<float> twin((size_t)w * h);
         speckle_filterOnCPU(disparity, twin.data(), w, h, vmin, new_val, p);
         if (check_errors(twin.data(), out, w * h)) cout << "Speckle filter ok!" << endl;
+    }
+}
+
+// not in the reference: region voting and interpolation behind speckle removal (smx_main --vote)
+void region_vote(unsigned char* guide, int channels, float* disparity, float* disparity_right, float* out, const int w,
+                 const int h, const int dmin, const int size_d, const smx_vote_params& p, const smx_cross_params& arms,
+                 bool host_gpu_compare) {
+    CHECK(smx_region_vote(&p, &arms, guide, channels, disparity, disparity_right, out, w, h, dmin, size_d,
+                          smx_config().params.d_lr));
+    if (host_gpu_compare) {
+        std::vector<float> twin((size_t)w * h);
+        region_voteOnCPU(guide, channels, disparity, disparity_right, twin.data(), w, h, dmin, size_d, p, arms);
+        if (check_errors(twin.data(), out, w * h)) cout << "Region voting ok!" << endl;
     }
 }
 

@@ -44,8 +44,9 @@ class ShardedPair:
     """D-sharded stereo pair: local aggregation of this rank's slices, ONE all-reduce of both
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
     The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
-    cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError.  Nor
-    is semi-global matching, which needs a pixel's whole disparity range on one rank: aggregation="sgm" raises ValueError."""
+    cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError, and so
+    does region voting (PairPipeline(vote=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
+    one rank: aggregation="sgm" raises ValueError."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -57,6 +58,8 @@ class ShardedPair:
                              f"PairPipeline(cost={kw['cost']!r})")
         if kw.get("speckle") is not None:
             raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
+        if kw.get("vote") is not None or kw.get("vote_arms") is not None:
+            raise ValueError("region voting is not part of the sharded driver: use PairPipeline(vote=...)")
         if kw.get("aggregation") is not None:
             raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
         self.rank, self.world, self.group = rank, world, group

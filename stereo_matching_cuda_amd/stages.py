@@ -202,6 +202,35 @@ def speckle_filter(disparity, vmin, new_val, params=None):
     return out
 
 
+def region_vote(disparity, guide, dmin, size_d, disparity_right=None, d_lr=None, params=None, arms=None):
+    """Region voting and 16-direction interpolation of a disparity map on the cross arms of `guide` (include/smx.h
+    smx_region_vote; not a stage of the reference).  guide: the (h, w) gray or (h, w, 1, 3 or 4) uint8 image of the view the
+    map belongs to; labels [dmin, dmin + size_d); disparity_right: the right view's winner-take-all map, or None (every
+    remaining outlier is then an occlusion); d_lr: None takes smx_params' default; params: VoteParams; arms: CrossParams
+    whose l1, l2, tau1, tau2 build the support regions (None: the defaults).  Returns a new (h, w) float32 array."""
+    d = _c(disparity, np.float32)
+    g = _c(guide, np.uint8)
+    if d.ndim != 2:
+        raise ValueError("region_vote expects an (h, w) float32 map")
+    if g.ndim not in (2, 3) or g.shape[:2] != d.shape or (g.ndim == 3 and g.shape[2] not in (1, 3, 4)):
+        raise ValueError("region_vote expects an (h, w) or (h, w, 1, 3 or 4) uint8 guide of the map's shape")
+    r = None if disparity_right is None else _c(disparity_right, np.float32)
+    if r is not None and r.shape != d.shape:
+        raise ValueError("disparity_right must have the map's shape")
+    if params is not None and not isinstance(params, _lib.VoteParams):
+        raise ValueError(f"params must be None or VoteParams, not {params!r}")
+    if arms is not None and not isinstance(arms, _lib.CrossParams):
+        raise ValueError(f"arms must be None or CrossParams, not {arms!r}")
+    h, w = d.shape
+    ch = 1 if g.ndim == 2 else g.shape[2]
+    out = np.empty((h, w), np.float32)
+    p = params if params is not None else _lib.default_vote_params()
+    lr = _lib.default_params().d_lr if d_lr is None else int(d_lr)
+    _lib.check(_lib.lib().smx_region_vote(C.byref(p), None if arms is None else C.byref(arms), _ptr(g), ch, _ptr(d), _ptr(r),
+                                          _ptr(out), w, h, int(dmin), int(size_d), lr))
+    return out
+
+
 def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
     """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
     reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
