@@ -865,6 +865,64 @@ int smx_vote_geometry(int* tile_cols, int* tile_rows);
 int smx_ctx_set_vote(smx_ctx* ctx, const smx_vote_params* vote, const smx_cross_params* cross);
 int smx_ctx_vote_map(smx_ctx* ctx, float* voted);
 
+/* ------------------------------------------------------------------------------------
+ * Scan-line optimisation with colour-adaptive penalties (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The scan-line optimiser of Mei et al. 2011, the step between the cross-based aggregation and the winners: the recurrence of
+ * smx_dev_sgm_wta_pair with penalties that are lowered where the step of a path crosses a colour edge in BOTH views, which is
+ * where a real depth step is.  A constant p2 large enough to carry a weakly textured surface through its noise erases a thin
+ * foreground object (entering and leaving it costs 2 p2); lowered at the object's colour edges it does not.
+ * tests/scanline_ref.py is this definition in numpy; the result equals it bit for bit.
+ * Defaults: p1 127, p2 382, tau_so 15, paths 4 (Mei's Pi1 = 1.0, Pi2 = 3.0, tau_SO = 15 and four directions, at the AD-Census
+ * default scale of 127.5).  Valid: 0 <= p1 <= p2 <= 4095, 1 <= tau_so <= 256, paths 4 or 8; w, h >= 1, w*h < 2^31,
+ * 1 <= size_d <= SMX_SGM_MAX_D, channels 1, 3 or 4, any int for dminl / dminr; anything else is SMX_E_ARG before any device call.
+ *   costs, directions, restart rule, tie rule, d_keys (OUT only), d_agg, d_nbr, d_uq: those of smx_dev_sgm_wta_pair (_uq); the
+ *            directions in the order (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,1) (1,-1) (-1,-1), the first four for paths 4.  A cost is
+ *            read through the clamp C = c >= 0 ? (c <= 255 ? (int)c : 255) : 0, so the q of smx_dev_cross_wta_pair, which has four
+ *            fractional bits, is truncated to its integer part.  d_uq is optional here (NULL, or 3n floats per view).
+ *   guides:  u8 [h][w][channels]; D(p, q) = the maximum over the first three channels of |I_c(p) - I_c(q)|, the distance of
+ *            smx_dev_cross_arms (a fourth byte is ignored).
+ *   flags:   for a view v, a pixel p = (x, y), a direction r and a slice z the label is d = dmin_v + z and the partner of p is
+ *            q = (x + d, y) in the OTHER view (the convention of the cost entries).
+ *              e1 = [D_own(p, p - r) >= tau_so]
+ *              e2 = [D_other(q, q - r) >= tau_so] if q and q - r both lie inside the image, else 0
+ *              k  = e1 + e2: e2 depends on z, so the penalties are per label.  tau_so = 256 never flags an edge.
+ *   penalties of (p, z): (P1, P2) = (p1, p2) for k = 0, (p1 / 4, p2 / 4) for k = 1, (p1 / 10, p2 / 10) for k = 2, in floor division.
+ *   recurrence: L_r(p, z) = C(p, z) where p - r lies outside the image; otherwise, with m = min_j L_r(p - r, j),
+ *              L_r(p, z) = C(p, z) + min(L_r(p-r, z), L_r(p-r, z-1) + P1, L_r(p-r, z+1) + P1, m + P2) - m
+ *            with the terms of z - 1 < 0 and z + 1 >= size_d left out.  P2 <= 4095, so the bounds of smx_dev_sgm_wta_pair hold: S
+ *            fits u16, (float)S is exact, and the result is the same bits in every run.  With tau_so = 256 the outputs equal
+ *            smx_dev_sgm_wta_pair's bit for bit.
+ * smx_dev_scanline_wta_pair: BOTH guides are always required (a view's e2 reads the other guide); either cost pointer may be
+ * NULL (not both), the one-view form, whose outputs hold that one view as for SGM.  A fixed sequence of kernel launches on
+ * `stream` (the SGM sequence plus one: 6 for paths 4, 10 for paths 8), no allocation, no synchronisation (graph-capturable).
+ * d_ws needs no alignment and may hold anything; fewer than smx_scanline_workspace_bytes(w, h, size_d, nviews) bytes is SMX_E_WS
+ * before anything is launched (the SGM workspace plus, for each of the two views whatever nviews is, one byte per pixel of edge
+ * flags with 8 bytes of padding a row; 0 for invalid sizes or nviews other than 1, 2).  Nothing is written outside the workspace
+ * and the stated extents; the inputs are not modified.
+ * smx_scanline_optimize: host pointers, synchronous, one view with label offset dmin; guide_own is that view's guide, guide_other
+ * the other view's.  agg, best, disp_map as for smx_sgm_aggregate. */
+typedef struct smx_scanline_params { int p1, p2, tau_so, paths; } smx_scanline_params;
+void smx_default_scanline_params(smx_scanline_params* p);
+size_t smx_scanline_workspace_bytes(int w, int h, int size_d, int nviews);
+int smx_dev_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
+                              const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d, int dminl, int dminr,
+                              int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_scanline_optimize(const smx_scanline_params* p, const uint8_t* guide_own, const uint8_t* guide_other, int channels,
+                          const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d, int dmin);
+/* The scan-line optimiser of this context.  Non-NULL switches it on, NULL switches it off again.
+ * Alone: the flow of SMX_AGG_SGM -- both whole cost volumes (the reference's, census or AD-Census), smx_dev_scanline_wta_pair,
+ * then the usual finish; agg_l / agg_r receive S.
+ * With smx_ctx_set_cross on: the chain of Mei et al.  smx_dev_cross_wta_pair runs over its chunks with its q collected into two
+ * whole volumes and its keys discarded, then the optimiser runs on those volumes.  It reads them through the clamp, so the four
+ * fractional bits of q are truncated; agg_l / agg_r receive S, not q.
+ * The guide is the gray pair through smx_ctx_stereo_pair and the colour pair through smx_ctx_stereo_pair_rgb.  The uniqueness,
+ * speckle, vote, sub-pixel stages run behind it unchanged.  mean_l / mean_r are not produced (SMX_E_ARG if requested).  Together
+ * with SMX_AGG_SGM or SMX_GUIDE_RGB, or with more than SMX_SGM_MAX_D labels, the pair call returns SMX_E_ARG, and so does
+ * smx_ctx_stereo_pair_async while it is on.  The workspace and the volumes are allocated on first use. */
+int smx_ctx_set_scanline(smx_ctx* ctx, const smx_scanline_params* p);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -62,6 +62,11 @@ class SgmParams(C.Structure):
     _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("paths", C.c_int)]
 
 
+class ScanlineParams(C.Structure):
+    """smx_scanline_params: the scan-line optimiser with colour-adaptive penalties (not a stage of the reference)."""
+    _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("tau_so", C.c_int), ("paths", C.c_int)]
+
+
 class CrossParams(C.Structure):
     """smx_cross_params: cross-based aggregation (not a stage of the reference)."""
     _fields_ = [("l1", C.c_int), ("l2", C.c_int), ("tau1", C.c_int), ("tau2", C.c_int), ("iterations", C.c_int)]
@@ -101,6 +106,7 @@ _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
 _XP = C.POINTER(CrossParams)
 _VP = C.POINTER(VoteParams)
+_LP = C.POINTER(ScanlineParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -210,6 +216,11 @@ SIGNATURES = {
     "smx_vote_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "smx_ctx_set_vote": (_i, [_vp, _VP, _XP]),
     "smx_ctx_vote_map": (_i, [_vp, _vp]),
+    "smx_default_scanline_params": (None, [_LP]),
+    "smx_scanline_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_scanline_wta_pair": (_i, [_LP, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_scanline_optimize": (_i, [_LP, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_scanline": (_i, [_vp, _LP]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -311,6 +322,12 @@ def default_sgm_params():
 def default_cross_params():
     p = CrossParams()
     lib().smx_default_cross_params(C.byref(p))
+    return p
+
+
+def default_scanline_params():
+    p = ScanlineParams()
+    lib().smx_default_scanline_params(C.byref(p))
     return p
 
 

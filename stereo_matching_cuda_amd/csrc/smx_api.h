@@ -45,6 +45,8 @@ bool uniq_ratio_ok(float ratio);
 bool speckle_shape_ok(int w, int h);
 bool sgm_params_ok(const smx_sgm_params* p);
 bool sgm_shape_ok(int w, int h, int size_d);
+bool scanline_params_ok(const smx_scanline_params* p);
+constexpr const char* SCANLINE_RANGES = "needs 0 <= p1 <= p2 <= 4095, 1 <= tau_so <= 256 and paths 4 or 8";
 bool cross_params_ok(const smx_cross_params* p);       // (smx_cross.hip, beside the limits of its kernels)
 bool cross_shape_ok(int w, int h);
 constexpr const char* CROSS_RANGES = "needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and 1 <= iterations <= 4";

@@ -112,6 +112,9 @@ bool speckle_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * 
 bool sgm_params_ok(const smx_sgm_params* p) {
     return p && p->p1 >= 0 && p->p1 <= p->p2 && p->p2 <= 4095 && (p->paths == 4 || p->paths == 8);
 }
+bool scanline_params_ok(const smx_scanline_params* p) {
+    return p && p->p1 >= 0 && p->p1 <= p->p2 && p->p2 <= 4095 && p->tau_so >= 1 && p->tau_so <= 256 && (p->paths == 4 || p->paths == 8);
+}
 bool sgm_shape_ok(int w, int h, int size_d) {
     return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= SMX_SGM_MAX_D;
 }
@@ -682,6 +685,31 @@ int smx_dev_sgm_wta_pair_uq(const smx_sgm_params* p, const float* d_cost_l, cons
     SMX_ARG(d_uq);
     return sgm_wta_pair("smx_dev_sgm_wta_pair_uq", p, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_uq, d_ws, ws_bytes,
                         stream);
+}
+
+// ---- scan-line optimisation with colour-adaptive penalties (not in the reference; smx_scanline.hip) -----------------
+void smx_default_scanline_params(smx_scanline_params* p) {
+    if (!p) return;
+    p->p1 = 127; p->p2 = 382; p->tau_so = 15; p->paths = 4;
+}
+
+size_t smx_scanline_workspace_bytes(int w, int h, int size_d, int nviews) {
+    return sgm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? scanline_workspace_bytes(w, h, size_d, nviews) : 0;
+}
+
+int smx_dev_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
+                              const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d, int dminl, int dminr,
+                              int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_scanline_wta_pair: %s", SCANLINE_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_dev_scanline_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    SMX_ARG(d_guide_l && d_guide_r && (d_cost_l || d_cost_r) && d_keys);
+    const size_t need = scanline_workspace_bytes(w, h, size_d, d_cost_l && d_cost_r ? 2 : 1);
+    if (!d_ws || ws_bytes < need)
+        return fail(SMX_E_WS, "smx_dev_scanline_wta_pair: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0, need);
+    return launch_scanline_wta_pair(p, d_guide_l, d_guide_r, channels, d_cost_l, d_cost_r, w, h, size_d, dminl, dminr, d_keys,
+                                    d_agg, d_nbr, d_uq, d_ws, (hipStream_t)stream);
 }
 
 // ---- colour-guided filter aggregation (not in the reference; smx_cgf.hip) -----------------------------------------

@@ -51,6 +51,11 @@ struct smx_ctx {
     // cross-based aggregation (smx_ctx_set_cross)
     bool cross = false;
     smx_cross_params cross_params;
+    // the scan-line optimiser (smx_ctx_set_scanline): its workspace and, behind cross-based aggregation, the two volumes of q
+    // [2][size_d][h][w] that it reads
+    bool so = false;
+    smx_scanline_params so_params;
+    DevBuf so_ws, so_vol;
     // region voting (smx_ctx_set_vote): the arms of the left guide [h][w], the voted left map [h][w] and the stage's workspace
     bool vote = false;
     bool vote_valid = false;    // the map belongs to the last synchronous pair
@@ -91,7 +96,7 @@ struct smx_ctx {
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -113,6 +118,10 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     if (need.census) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
     if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
+    if (need.so) {
+        SMX_HIP(c->so_ws.ensure(scanline_workspace_bytes(c->w, c->h, c->size_d, 2)));
+        if (need.cross) SMX_HIP(c->so_vol.ensure(2 * vb));
+    }
     if (need.vote) {
         SMX_HIP(c->varms.ensure(c->n * sizeof(uint32_t)));
         SMX_HIP(c->voted.ensure(fb));
@@ -237,6 +246,25 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
                                                           c->mode_ws_bytes, st)
                                 : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->mode_ws.p,
                                                        c->mode_ws_bytes, st);
+    } else if (need.so) {
+        // the scan-line optimiser reads whole volumes: the cost volumes, as SGM does, or behind cross-based aggregation the
+        // two volumes of its q, collected over the chunks with the keys of that pass discarded (the optimiser's are OUT only)
+        const uint8_t* gl = in.channels ? in.rgb_l : in.left;
+        const uint8_t* gr = in.channels ? in.rgb_r : in.right;
+        const float* vl = costL;
+        const float* vr = costR;
+        if (need.cross) {
+            float* vol = c->so_vol.as<float>();
+            AggCall chain = call;
+            PairNeeds cn = need;
+            cn.agg = true;
+            chain.agg[0] = vol; chain.agg[1] = vol + (size_t)size_d * n;
+            chain.nbr[0] = chain.nbr[1] = chain.uq[0] = chain.uq[1] = nullptr;
+            rc = ctx_aggregate_chunks(c, in, chain, cn);
+            vl = vol; vr = vol + (size_t)size_d * n;
+        } else if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
+        if (!rc) rc = smx_dev_scanline_wta_pair(&c->so_params, gl, gr, in.channels ? in.channels : 1, vl, vr, w, h, size_d, in.dminl,
+                                                in.dminr, keysL, aggL, nbrL, uqL, c->so_ws.p, c->so_ws.bytes, st);
     } else if (need.cgf || need.cross || need.census) rc = ctx_aggregate_chunks(c, in, call, need);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
@@ -371,11 +399,19 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     if (cross && (out->mean_l || out->mean_r))
         return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) produces no mean images", who);
     if (cross && !cross_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "%s: cross-based aggregation needs w*h < 2^31", who);
+    const bool so = c->so;
+    if (so && sgm) return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) and semi-global matching are both on", who);
+    if (so && cgf) return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) and colour guidance are both on", who);
+    if (so && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) produces no mean images", who);
+    if (so && !sgm_shape_ok(c->w, c->h, c->size_d))
+        return fail(SMX_E_ARG, "%s: the scan-line optimiser needs w*h < 2^31 and size_d <= %d", who, SMX_SGM_MAX_D);
     if (c->adcensus && c->adc.colour && !channels)
         return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
                                "smx_ctx_stereo_pair_rgb", who);
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm, out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote};
+    // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q)
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r, c->subpix != 0,
+                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so};
     if ((rc = ctx_reserve(c, need))) return rc;
     if (c->adcensus && !c->adc_tab_valid) {
         SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
@@ -411,7 +447,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
     // (the SGM, colour-guided and cross-based kernels wait for nothing)
-    if (!need.sgm && !need.cgf && !need.cross && (rc = smx_dev_agg_status(c->ws.p))) return rc;
+    if (!need.sgm && !need.cgf && !need.cross && !need.so && (rc = smx_dev_agg_status(c->ws.p))) return rc;
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
@@ -450,6 +486,16 @@ int smx_ctx_set_cross(smx_ctx* c, const smx_cross_params* p) {
         c->cross_params = *p;
     }
     c->cross = p != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_set_scanline(smx_ctx* c, const smx_scanline_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_scanline: %s", SCANLINE_RANGES);
+        c->so_params = *p;
+    }
+    c->so = p != nullptr;
     return SMX_OK;
 }
 
@@ -614,6 +660,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb");
     if (c->cross)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-based aggregation is on (smx_ctx_set_cross): use smx_ctx_stereo_pair");
+    if (c->so)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the scan-line optimiser is on (smx_ctx_set_scanline): use smx_ctx_stereo_pair");
     if (c->cost_mode != SMX_COST_REFERENCE)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
     if (c->adcensus)

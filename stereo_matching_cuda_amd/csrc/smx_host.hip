@@ -266,6 +266,41 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
     return SMX_OK;
 }
 
+int smx_scanline_optimize(const smx_scanline_params* p, const uint8_t* guide_own, const uint8_t* guide_other, int channels,
+                          const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d, int dmin) {
+    if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_scanline_optimize: %s", SCANLINE_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_scanline_optimize: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    SMX_ARG(guide_own && guide_other && cost);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = scanline_workspace_bytes(w, h, size_d, 1);
+    DevBuf dG, dH, dC, dA, dK, dW;
+    SMX_HIP(dG.upload(guide_own, n * channels));
+    SMX_HIP(dH.upload(guide_other, n * channels));
+    SMX_HIP(dC.upload(cost, vb));
+    if (agg) SMX_HIP(dA.ensure(vb));
+    SMX_HIP(dK.ensure(n * sizeof(int64_t)));
+    SMX_HIP(dW.ensure(wsb));
+    // the one view goes in as the left one: its partners lie in `guide_other`
+    if (int rc = smx_dev_scanline_wta_pair(p, dG.as<uint8_t>(), dH.as<uint8_t>(), channels, dC.as<float>(), nullptr, w, h, size_d,
+                                           dmin, 0, dK.as<int64_t>(), agg ? dA.as<float>() : nullptr, nullptr, nullptr, dW.p,
+                                           wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (agg) SMX_HIP(dA.download(agg, vb));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(dK.download(keys.data(), n * sizeof(int64_t)));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
 int smx_colour_guided_filter(const smx_params* p, const uint8_t* rgb, int channels, const float* cost, float* filter_cost,
                              float* disp_map, float* agg, int w, int h, int size_d, int dmin) {
     SMX_ARG(p && rgb && cost && filter_cost && disp_map && size_d >= 1 && w >= 1 && h >= 1);

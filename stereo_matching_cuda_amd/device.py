@@ -27,7 +27,7 @@ class PairPipeline:
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
                  aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
-                 vote=None, vote_arms=None):
+                 vote=None, vote_arms=None, scanline_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -82,7 +82,17 @@ class PairPipeline:
         -- the colour image where this aggregate() took one, else the gray one -- into self.vote_arms_plane and votes on the last
         of occlusion / unique / despeckled with self.dmap[1] as the right map, into self.voted; self.filled becomes the fill of
         self.voted.  The validity map is not replaced: the sub-pixel fit and wmf="occluded" take the map they take without
-        it.  Works with every aggregation and cost; size_d <= 512.  With None nothing is allocated or launched."""
+        it.  Works with every aggregation and cost; size_d <= 512.  With None nothing is allocated or launched.
+        aggregation="scanline" is the scan-line optimiser with colour-adaptive penalties (not a stage of the reference;
+        include/smx.h smx_dev_scanline_wta_pair; scanline_params: ScanlineParams, None = the defaults): the flow of "sgm" --
+        both WHOLE cost volumes (the caller's, the reference's cost, census or AD-Census) into self.so_cost (2, size_d, h, w),
+        then the one call into self.keys (and self.agg = S, self.nbr, self.uq) with the workspace self.so_ws.  The guide is
+        the colour pair rgb_l=, rgb_r= of aggregate() / run() where it is given, else the gray pair.
+        aggregation="cross-scanline" is Mei's chain: smx_dev_cross_wta_pair (cross_params) over chunks of `slices_in_flight`
+        slices with its q collected into self.so_cost and its keys discarded, then the scan-line optimiser on those volumes,
+        which it reads through the clamp: q's four fractional bits are truncated.  max_ws_bytes counts the volumes, the
+        workspaces and the chunk buffers; a slice sub-range, more than 256 labels or a size that does not fit raises
+        ValueError."""
         if guidance not in (None, "rgb"):
             raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
         if guidance and aggregation:
@@ -95,9 +105,12 @@ class PairPipeline:
             # winners it does not belong to)
             if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
                 raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
-        if aggregation not in (None, "sgm", "cross"):
-            raise ValueError(f"aggregation must be None, 'sgm' or 'cross', not {aggregation!r}")
-        sgm, cross = aggregation == "sgm", aggregation == "cross"
+        if aggregation not in (None, "sgm", "cross", "scanline", "cross-scanline"):
+            raise ValueError(f"aggregation must be None, 'sgm', 'cross', 'scanline' or 'cross-scanline', not {aggregation!r}")
+        sgm, cross = aggregation == "sgm", aggregation in ("cross", "cross-scanline")
+        so = aggregation in ("scanline", "cross-scanline")
+        if scanline_params is not None and not so:
+            raise ValueError("scanline_params belongs to aggregation='scanline' / 'cross-scanline'")
         if cost not in (None, "census", "adcensus"):
             raise ValueError(f"cost must be None, 'census' or 'adcensus', not {cost!r}")
         if wmf not in (None, "occluded", "all"):
@@ -135,6 +148,20 @@ class PairPipeline:
             if self.sgm_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
                 raise ValueError(f"semi-global matching needs {self.sgm_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
                                  f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
+        self.so_params = self.so_cost = self.so_ws = self._so_chunk = None
+        self.so_ws_bytes = 0
+        if so:
+            if self.s_begin != 0 or self.s_end != self.size_d:
+                raise ValueError("the scan-line optimiser needs a pixel's whole disparity range: no slice sub-range")
+            self.so_params = scanline_params if scanline_params is not None else _lib.default_scanline_params()
+            self.so_ws_bytes = int(self.lib.smx_scanline_workspace_bytes(self.w, self.h, self.size_d, 2))
+            if self.so_ws_bytes == 0:
+                raise ValueError(f"the scan-line optimiser does not take {self.w} x {self.h} x {self.size_d} "
+                                 "(w*h < 2^31, size_d <= 256)")
+            if self.so_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
+                raise ValueError(f"the scan-line optimiser needs {self.so_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
+                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
+            max_ws_bytes -= self.so_ws_bytes + 2 * self.size_d * self.n * 4       # what is left for the chain's cross stage
         local = max(1, self.s_end - self.s_begin)
         sif = local if slices_in_flight is None else max(1, min(local, int(slices_in_flight)))
         # workspace of the path these parameters run (smx_agg_workspace_bytes_for follows the library's choice: a fused
@@ -156,7 +183,9 @@ class PairPipeline:
             self.cross_params = cross_params if cross_params is not None else _lib.default_cross_params()
             if self.lib.smx_cross_workspace_bytes(self.w, self.h, 1, 2) == 0:
                 raise ValueError(f"cross-based aggregation does not take {self.w} x {self.h} (w*h < 2^31)")
-            need = lambda n: (self.lib.smx_cross_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
+            # (the chain also holds a chunk of q on its way into the whole volumes)
+            need = lambda n: (self.lib.smx_cross_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4) +
+                              (2 * n * self.n * 4 if so and n < local else 0)) // 2
         self.cost = cost
         self.adcensus_params = self.adcensus_table = self._rgb = None
         if cost == "adcensus":
@@ -167,6 +196,8 @@ class PairPipeline:
         chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
         while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
+        if so and cross and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
+            raise ValueError("the chain of cross-based aggregation and the scan-line optimiser does not fit max_ws_bytes")
         self.slices_in_flight = sif
         # pair calls (both views per launch) need twice the single-view workspace (SGM does not use it)
         self.ws_bytes = 0 if aggregation or guidance else 2 * int(need(sif))
@@ -210,7 +241,7 @@ class PairPipeline:
             self.vote_arms_plane = torch.empty((self.h, self.w), dtype=torch.int32, device=dev)
             self.vote_ws = torch.empty(self.vote_ws_bytes, dtype=torch.uint8, device=dev)
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
-        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm else None
+        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and aggregation != "scanline" else None
         if cost == "adcensus":
             self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
             with self._on_device():     # a set-up call: it waits for its copy, and stays outside any graph capture
@@ -219,6 +250,10 @@ class PairPipeline:
         if sgm:
             self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
+        if so:
+            self.so_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
+            self.so_ws = torch.empty(self.so_ws_bytes, dtype=torch.uint8, device=dev)
+            self._so_chunk = torch.empty((2, sif, self.h, self.w), **f) if cross and sif < local else None
         if guidance:
             self.cgf_ws_bytes = int(self.lib.smx_cgf_workspace_bytes(self.w, self.h, sif, 2))
             self.cgf_ws = torch.empty(self.cgf_ws_bytes, dtype=torch.uint8, device=dev)
@@ -229,7 +264,7 @@ class PairPipeline:
             self.cross_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
         self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
-            if (cost or guidance or cross) and want_agg and sif < local and not sgm else None
+            if (cost or guidance or cross) and want_agg and sif < local and not sgm and not so else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -249,7 +284,7 @@ class PairPipeline:
                 raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
             self._rgb = (rgb_l, rgb_r)
             return self._aggregate_cgf(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
-        if self.aggregation == "cross":
+        if self.aggregation in ("cross", "scanline", "cross-scanline"):
             if (rgb_l is None) != (rgb_r is None):
                 raise ValueError("pass both colour guides or neither")
             if colour_cost and rgb_l is None:
@@ -257,6 +292,8 @@ class PairPipeline:
             if rgb_l is not None:
                 self._check_rgb(rgb_l, rgb_r)
                 self._rgb = (rgb_l, rgb_r)
+            if self.aggregation == "scanline":
+                return self._aggregate_scanline(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
             return self._aggregate_cross(gray_l, gray_r, rgb_l, rgb_r, cost_l, cost_r)
         if colour_cost:
             if rgb_l is None or rgb_r is None:
@@ -353,11 +390,50 @@ class PairPipeline:
         """The cross-based flow: that of the colour guide with smx_dev_cross_wta_pair; the guide is the colour pair where it is
         given, else the gray pair."""
         gl, gr, ch = (rgb_l, rgb_r, int(rgb_l.shape[2])) if rgb_l is not None else (gray_l, gray_r, 1)
+        chain = self.aggregation == "cross-scanline"
         self._aggregate_chunks(gray_l, gray_r, cost_l, cost_r, self.cross_cost, self.lib.smx_dev_cross_wta_pair,
-                               C.byref(self.cross_params), gl, gr, ch, self.cross_ws, self.cross_ws_bytes)
+                               C.byref(self.cross_params), gl, gr, ch, self.cross_ws, self.cross_ws_bytes,
+                               into=(self.so_cost, self._so_chunk) if chain else None)
+        if chain:
+            # (the keys of the cross pass are overwritten: the optimiser's are OUT only)
+            self._scanline(gl, gr, ch, self.so_cost[0], self.so_cost[1])
 
-    def _aggregate_chunks(self, gray_l, gray_r, cost_l, cost_r, own_cost, entry, params, guide_l, guide_r, ch, ws, ws_bytes):
-        """Fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views (the caller's volumes, census /
+    def _aggregate_scanline(self, gray_l, gray_r, rgb_l, rgb_r, cost_l=None, cost_r=None):
+        """The scan-line flow: both whole cost volumes (the caller's, census / AD-Census, or the reference's cost), as for SGM,
+        and the one smx_dev_scanline_wta_pair call; the guide is the colour pair where it is given, else the gray pair."""
+        if (cost_l is None) != (cost_r is None):
+            raise ValueError("pass both cost volumes or neither")
+        if self.cost and cost_l is not None:
+            raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
+        self._guide = gray_l
+        L, w, h = self.lib, self.w, self.h
+        cl, cr = (cost_l, cost_r) if cost_l is not None else (self.so_cost[0], self.so_cost[1])
+        with self._on_device():
+            st = self._stream()
+            if self.cost:
+                P = C.byref(self.census_params)
+                for v, g in enumerate((gray_l, gray_r)):
+                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, st))
+                self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
+            elif cost_l is None:
+                P = C.byref(self.params)
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
+        gl, gr, ch = (rgb_l, rgb_r, int(rgb_l.shape[2])) if rgb_l is not None else (gray_l, gray_r, 1)
+        self._scanline(gl, gr, ch, cl, cr)
+
+    def _scanline(self, guide_l, guide_r, ch, cl, cr):
+        with self._on_device():
+            _lib.check(self.lib.smx_dev_scanline_wta_pair(
+                C.byref(self.so_params), _dp(guide_l), _dp(guide_r), ch, _dp(cl), _dp(cr), self.w, self.h, self.size_d, self.dminl,
+                self.dminr, _dp(self.keys), _dp(self.agg), _dp(self.nbr), _dp(self.uq), _dp(self.so_ws), self.so_ws_bytes,
+                self._stream()))
+
+    def _aggregate_chunks(self, gray_l, gray_r, cost_l, cost_r, own_cost, entry, params, guide_l, guide_r, ch, ws, ws_bytes,
+                          into=None):
+        """into: None, or (volumes, chunk buffer or None) of the chain: the aggregated slices go there whatever want_agg says,
+        and the neighbour / second-best states are not kept (they belong to the stage behind).
+        Fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views (the caller's volumes, census /
         AD-Census into self.census_cost, or the reference's cost into own_cost) and `entry` -- smx_dev_cgf_wta_pair or
         smx_dev_cross_wta_pair -- from them, which accumulates into the keys (and the neighbour / second-best states)."""
         if (cost_l is None) != (cost_r is None):
@@ -387,19 +463,21 @@ class PairPipeline:
                     P = C.byref(self.params)
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, c0, c1, st))
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, c0, c1, st))
-            whole = self.agg is None or self._agg_chunk is None
+            agg, chunk = (self.agg, self._agg_chunk) if into is None else into
+            nbr, uq = (self.nbr, self.uq) if into is None else (None, None)
+            whole = agg is None or chunk is None
             with self._on_device():
                 _lib.check(L.smx_set_max_slices_per_launch(sif))
                 try:
                     _lib.check(entry(params, _dp(guide_l), _dp(guide_r), ch, _dp(cl), _dp(cr), w, h, c0, c1, _dp(self.keys),
-                                     _dp(self.agg if whole else self._agg_chunk), _dp(self.nbr), _dp(self.uq), _dp(ws), ws_bytes,
+                                     _dp(agg if whole else chunk), _dp(nbr), _dp(uq), _dp(ws), ws_bytes,
                                      self._stream()))
                 finally:
                     L.smx_set_max_slices_per_launch(0)
             if not whole:
                 # (the call wrote its two views c1 - c0 slices apart, whatever the buffer holds)
-                flat = self._agg_chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, h, w)
-                self.agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
+                flat = chunk.view(-1)[:2 * (c1 - c0) * self.n].view(2, c1 - c0, h, w)
+                agg[:, c0 - self.s_begin:c1 - self.s_begin].copy_(flat)
 
     def _aggregate_sgm(self, gray_l, gray_r, cost_l=None, cost_r=None):
         """The SGM flow: both whole cost volumes (the caller's, census, or the reference's cost) and the one

@@ -20,6 +20,7 @@
 #include "occlusion.cuh"
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "scanlineOptimization.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
 #include "uniqueness.cuh"
@@ -672,6 +673,77 @@ void sgm_aggregateOnCPU(const float* cost, float* agg, float* best, float* disp_
                         int t = prev[d] < m + p.p2 ? prev[d] : m + p.p2;
                         if (d - 1 >= 0 && prev[d - 1] + p.p1 < t) t = prev[d - 1] + p.p1;
                         if (d + 1 < size_d && prev[d + 1] + p.p1 < t) t = prev[d + 1] + p.p1;
+                        cur[d] = c[d] + t - m;
+                    }
+                }
+                int* s = &S[((size_t)y * w + x) * size_d];
+                for (int d = 0; d < size_d; ++d) s[d] += cur[d];
+            }
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const int* s = &S[i * size_d];
+        int z = 0;
+        for (int d = 1; d < size_d; ++d)
+            if (s[d] <= s[z]) z = d;                 // the last slice of equal sums wins
+        if (best) best[i] = (float)s[z];
+        if (disp_map) disp_map[i] = (float)(dmin + z);
+        if (agg)
+            for (int d = 0; d < size_d; ++d) agg[(size_t)d * n + i] = (float)s[d];
+    }
+}
+
+// ---- scanlineOptimization.cuh (not in the reference) -----------------------------------------
+// The scan-line optimiser by the definition in include/smx.h: sgm_aggregateOnCPU with the two edge flags looked up, and the
+// penalties chosen, for every pixel, direction and label.
+void scanline_optimizeOnCPU(const unsigned char* guide_own, const unsigned char* guide_other, int channels, const float* cost,
+                            float* agg, float* best, float* disp_map, const int w, const int h, const int size_d, const int dmin,
+                            const smx_scanline_params& p) {
+    static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
+    const size_t n = (size_t)w * h;
+    const int nch = channels < 3 ? channels : 3;
+    const int P1[3] = {p.p1, p.p1 / 4, p.p1 / 10}, P2[3] = {p.p2, p.p2 / 4, p.p2 / 10};
+    // [D(a, b) >= tau_so] for two pixels of one guide, both inside the image
+    auto edge = [&](const unsigned char* g, long long ax, int ay, long long bx, int by) {
+        const unsigned char* a = g + ((size_t)ay * w + (size_t)ax) * channels;
+        const unsigned char* b = g + ((size_t)by * w + (size_t)bx) * channels;
+        int d = 0;
+        for (int c = 0; c < nch; ++c) {
+            const int e = (int)a[c] - (int)b[c];
+            d = (e < 0 ? -e : e) > d ? (e < 0 ? -e : e) : d;
+        }
+        return d >= p.tau_so ? 1 : 0;
+    };
+    vector<int> C(n * size_d), L(n * size_d), S(n * size_d, 0);     // [pixel][d]
+    for (int d = 0; d < size_d; ++d)
+        for (size_t i = 0; i < n; ++i) {
+            const float c = cost[(size_t)d * n + i];
+            C[i * size_d + d] = c >= 0.0f ? (c <= 255.0f ? (int)c : 255) : 0;
+        }
+    for (int r = 0; r < p.paths; ++r) {
+        const int dx = dirs[r][0], dy = dirs[r][1];
+        for (int iy = 0; iy < h; ++iy) {
+            const int y = dy >= 0 ? iy : h - 1 - iy;
+            for (int ix = 0; ix < w; ++ix) {
+                const int x = dx >= 0 ? ix : w - 1 - ix;
+                const int px = x - dx, py = y - dy;
+                int* cur = &L[((size_t)y * w + x) * size_d];
+                const int* c = &C[((size_t)y * w + x) * size_d];
+                if (px < 0 || px >= w || py < 0 || py >= h) {
+                    for (int d = 0; d < size_d; ++d) cur[d] = c[d];
+                } else {
+                    const int* prev = &L[((size_t)py * w + px) * size_d];
+                    const int e1 = edge(guide_own, x, y, px, py);
+                    int m = prev[0];
+                    for (int d = 1; d < size_d; ++d) m = prev[d] < m ? prev[d] : m;
+                    for (int d = 0; d < size_d; ++d) {
+                        // the partner of the label in the other view and its predecessor; py is inside already
+                        const long long qx = (long long)x + dmin + d;
+                        const int e2 = qx >= 0 && qx < w && qx - dx >= 0 && qx - dx < w ? edge(guide_other, qx, y, qx - dx, py) : 0;
+                        const int p1 = P1[e1 + e2], p2 = P2[e1 + e2];
+                        int t = prev[d] < m + p2 ? prev[d] : m + p2;
+                        if (d - 1 >= 0 && prev[d - 1] + p1 < t) t = prev[d - 1] + p1;
+                        if (d + 1 < size_d && prev[d + 1] + p1 < t) t = prev[d + 1] + p1;
                         cur[d] = c[d] + t - m;
                     }
                 }

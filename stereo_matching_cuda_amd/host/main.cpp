@@ -9,7 +9,7 @@
 //                                    D_MIN..D_MAX from the macros, outputs into ./data/
 //   smx_main L.png R.png [dmin dmax [outdir]] [options]
 // options (not in the reference).  The opt-in costs, aggregations and stages (--cost census / adcensus, --aggregation sgm /
-// cross, --guidance rgb, --uniqueness, --speckle, --vote, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
+// cross / scanline / cross-scanline, --guidance rgb, --uniqueness, --speckle, --vote, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
 // an entry says otherwise; none of them goes with --ngpu or --pipeline:
 //   --fused           one device-resident call for everything after the gray conversion
 //                     (smx_stereo_pair: cost built on the fly inside the fused aggregation) instead of
@@ -78,6 +78,17 @@
 //                     20,6), --cross-iterations N the iterations (1 .. 4; default 4).  With --host-compare the CPU twin
 //                     (cross_aggregateOnCPU) redoes both views from the cost volumes and check_errors compares.  Not with
 //                     --guidance rgb
+//   --aggregation scanline  the scan-line optimiser with colour-adaptive penalties instead of the guided filter
+//                     (smx_ctx_set_scanline, smx_ctx_stereo_pair_rgb; Mei et al.'s step between the aggregation and the winners,
+//                     not in the reference; implies --fused): semi-global matching whose penalties drop to a quarter where the
+//                     step of a path crosses a colour edge of one view and to a tenth where it crosses one in both; the guide is
+//                     the colour pair.  --aggregation cross-scanline is Mei's chain: cross-based aggregation (with its --cross-*
+//                     options) and then the optimiser on its result, whose four fractional bits are truncated.  The same twelve
+//                     images, the two mean images empty.  --so-p P1,P2 gives the penalties (0 <= P1 <= P2 <= 4095; default
+//                     127,382, which fit --cost adcensus at its default scale), --so-tau T the colour threshold (1 .. 256; default
+//                     15; 256 never lowers a penalty), --so-paths 4|8 the number of directions (default 4).  With --host-compare
+//                     the CPU twins (cross_aggregateOnCPU, scanline_optimizeOnCPU) redo both views from the cost volumes and
+//                     check_errors compares.  At most 256 labels.  Not with --guidance rgb
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -107,6 +118,7 @@
 #include "png_io.h"
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
+#include "scanlineOptimization.cuh"
 #include "crossAggregation.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
@@ -131,8 +143,10 @@ struct Options {
     smx_adcensus_params adc_params;     // (its census part is filled from census_params after the parse)
     bool sgm = false;        // --aggregation sgm
     smx_sgm_params sgm_params;
-    bool cross = false;      // --aggregation cross
+    bool cross = false;      // --aggregation cross, and the first stage of cross-scanline
     smx_cross_params cross_params;
+    bool so = false;         // --aggregation scanline, and the second stage of cross-scanline
+    smx_scanline_params so_params;
     bool speckle = false;    // --speckle
     smx_speckle_params speckle_params;
     bool vote = false;       // --vote
@@ -222,9 +236,21 @@ const ValueOption value_options[] = {
          const bool good = number(v, 1L, 1000000L, th);
          o.census_params.th = (int)th;
          return good; }},
-    {"--aggregation", "`guided`, `sgm` or `cross`", [](auto& v, auto& o) {         // (the last one wins)
-         const int k = word(v, {"guided", "sgm", "cross"});
-         o.sgm = k == 1; o.cross = k == 2;
+    {"--aggregation", "`guided`, `sgm`, `cross`, `scanline` or `cross-scanline`", [](auto& v, auto& o) {    // (the last one wins)
+         const int k = word(v, {"guided", "sgm", "cross", "scanline", "cross-scanline"});
+         o.sgm = k == 1; o.cross = k == 2 || k == 4; o.so = k == 3 || k == 4;
+         return k >= 0; }},
+    {"--so-p", "P1,P2 with 0 <= P1 <= P2 <= 4095", [](auto& v, auto& o) {
+         int& p1 = o.so_params.p1; int& p2 = o.so_params.p2;
+         return pair_of(v, ',', p1, p2) && p1 >= 0 && p1 <= p2 && p2 <= 4095; }},
+    {"--so-tau", "a threshold T with 1 <= T <= 256", [](auto& v, auto& o) {
+         long t = 0;
+         const bool good = number(v, 1L, 256L, t);
+         o.so_params.tau_so = (int)t;
+         return good; }},
+    {"--so-paths", "4 or 8", [](auto& v, auto& o) {
+         const int k = word(v, {"4", "8"});
+         o.so_params.paths = k == 1 ? 8 : 4;
          return k >= 0; }},
     {"--cross-arms", "L1,L2 with 1 <= L1 <= 63 and 0 <= L2 <= L1", [](auto& v, auto& o) {
          int& l1 = o.cross_params.l1; int& l2 = o.cross_params.l2;
@@ -288,6 +314,7 @@ Options parse(int argc, char** argv) {
     smx_default_speckle_params(&o.speckle_params);
     smx_default_sgm_params(&o.sgm_params);
     smx_default_cross_params(&o.cross_params);
+    smx_default_scanline_params(&o.so_params);
     smx_default_adcensus_params(&o.adc_params);
     smx_default_vote_params(&o.vote_params);
     smx_default_cross_params(&o.vote_arms);
@@ -325,7 +352,9 @@ Options parse(int argc, char** argv) {
          "--adcensus-lambda, --adcensus-scale and --ad need --cost adcensus"},
         {o.saw({"--sgm-p", "--sgm-paths"}) && !o.sgm, "--sgm-p and --sgm-paths need --aggregation sgm"},
         {o.saw({"--cross-arms", "--cross-tau", "--cross-iterations"}) && !o.cross,
-         "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross"},
+         "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross or cross-scanline"},
+        {o.saw({"--so-p", "--so-tau", "--so-paths"}) && !o.so,
+         "--so-p, --so-tau and --so-paths need --aggregation scanline or cross-scanline"},
         {o.saw({"--vote-interpolate", "--vote-arms", "--vote-tau"}) && !o.vote,
          "--vote-interpolate, --vote-arms and --vote-tau need --vote"}};
     for (const Rule& r : rules)
@@ -394,7 +423,7 @@ void build_cost(const Job& j, int v, int slices, float* dst, bool host_compare) 
     }
 }
 
-// --host-compare of --aggregation sgm / cross and --guidance rgb: the mode's twin redoes both views from whole cost volumes
+// --host-compare of --aggregation sgm / cross / scanline / cross-scanline and --guidance rgb: the mode's twin redoes both views from whole cost volumes
 // built by the stage wrappers, from the reference's presets.
 void check_aggregation_twin(const Job& j, Maps& m) {
     const Options& opt = j.opt;
@@ -406,7 +435,16 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         build_cost(j, v, j.size_d, vol.data(), false);
         if (opt.sgm)
             sgm_aggregateOnCPU(vol.data(), nullptr, tb.data(), td.data(), j.w, j.h, j.size_d, j.dmin[v], opt.sgm_params);
-        else if (opt.rgb)
+        else if (opt.so) {
+            // alone on the cost volume; in the chain on the q of the cross twin, whose own winners are discarded
+            std::vector<float> q(opt.cross ? vol.size() : 0), ub(n), ud(n, 0.0f);
+            std::memset(ub.data(), 0x7F, sizeof(float) * n);
+            if (opt.cross)
+                cross_aggregateOnCPU(j.in.rgb[v], j.in.channels[v], vol.data(), ub.data(), ud.data(), q.data(), j.w, j.h, j.size_d,
+                                     j.dmin[v], opt.cross_params);
+            scanline_optimizeOnCPU(j.in.rgb[v], j.in.rgb[1 - v], j.in.channels[v], opt.cross ? q.data() : vol.data(), nullptr,
+                                   tb.data(), td.data(), j.w, j.h, j.size_d, j.dmin[v], opt.so_params);
+        } else if (opt.rgb)
             colour_guided_filterOnCPU(j.in.rgb[v], j.in.channels[v], vol.data(), tb.data(), td.data(), nullptr, j.w, j.h,
                                       j.size_d, j.dmin[v], smx_config().params.radius, smx_config().params.eps);
         else
@@ -416,7 +454,8 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         ok = check_errors(td.data(), m.dmap[v].data(), n) && ok;
     }
     if (ok)
-        std::cout << (opt.sgm ? "Semi-global matching" : opt.rgb ? "Colour guided filter" : "Cross-based aggregation") << " ok!"
+        std::cout << (opt.sgm ? "Semi-global matching" : opt.so ? "Scan-line optimisation" : opt.rgb ? "Colour guided filter"
+                                                                                                      : "Cross-based aggregation") << " ok!"
                   << std::endl;
 }
 
@@ -445,7 +484,7 @@ void check_finish_twins(const Job& j, Maps& m, std::vector<float>& agg_l) {
     }
     if (opt.vote) {
         // (the guide of the context: the left colour image where the pair ran through the colour entry)
-        const bool colour = opt.rgb || opt.ad_rgb || opt.cross;
+        const bool colour = opt.rgb || opt.ad_rgb || opt.cross || opt.so;
         std::vector<float> twin(n);
         region_voteOnCPU(colour ? j.in.rgb[0] : j.gray[0], colour ? j.in.channels[0] : 1, lr.data(), m.dmap[1].data(), twin.data(),
                          j.w, j.h, j.d_lo, j.size_d, opt.vote_params, opt.vote_arms);
@@ -513,7 +552,7 @@ struct Sharded {
 bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms& stage_ms) {
     const Options& opt = j.opt;
     const bool host_compare = opt.host_compare, uniq = opt.uniqueness > 0.0f;
-    const bool colour = opt.rgb || opt.ad_rgb || opt.cross;     // the entry that takes the colour pair
+    const bool colour = opt.rgb || opt.ad_rgb || opt.cross || opt.so;     // the entry that takes the colour pair
     const int w = j.w, h = j.h, n = j.n;
     std::cout << "Cost Volume ..." << std::endl;
     for (int v = 0; v < 2; ++v) m.cost[v].resize((size_t)n);
@@ -525,8 +564,8 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     std::memset(&out, 0, sizeof(out));
     out.best_l = m.best[0].data(); out.best_r = m.best[1].data();
     out.dmap_l = m.dmap[0].data(); out.dmap_r = m.dmap[1].data();
-    // (SGM, the colour guide and cross-based aggregation have no mean images)
-    if (!opt.sgm && !opt.rgb && !opt.cross) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
+    // (SGM, the colour guide, cross-based aggregation and the scan-line optimiser have no mean images)
+    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
     std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness twin reads
     if (uniq && host_compare) {
@@ -547,6 +586,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
+    if (opt.so) CHECK(smx_ctx_set_scanline(ctx, &opt.so_params));         // (behind the cross stage where that is on too)
     if (!sh.create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
     auto run_pair = [&]() {
         return sh.create ? sh.run(sctx, j.gray[0], j.gray[1], j.dmin[0], j.dmin[1], &out)
@@ -595,7 +635,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (sh.create) CHECK(sh.destroy(sctx));
     else CHECK(smx_destroy(ctx));
     std::cout << "guided filter ok" << std::endl;
-    if (host_compare && (opt.sgm || opt.rgb || opt.cross)) check_aggregation_twin(j, m);
+    if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
     if (host_compare) check_finish_twins(j, m, agg_l);
     return have_stage_ms;
 }
@@ -688,6 +728,10 @@ int main(int argc, char** argv) {
          "--subpixel cannot be combined with --wmf (the median works on integer labels), --ngpu or --pipeline"},
         {opt.sgm && multi, "--aggregation sgm" + with_multi},
         {opt.rgb && (opt.sgm || multi), "--guidance rgb cannot be combined with --aggregation sgm, --ngpu or --pipeline"},
+        {opt.so && (opt.rgb || multi), std::string("--aggregation ") + (opt.cross ? "cross-scanline" : "scanline") +
+                                           " cannot be combined with --guidance rgb, --ngpu or --pipeline"},
+        {opt.so && labels > SMX_SGM_MAX_D, std::string("--aggregation ") + (opt.cross ? "cross-scanline" : "scanline") +
+                                               " takes at most " + std::to_string(SMX_SGM_MAX_D) + " labels"},
         {opt.cross && (opt.rgb || multi), "--aggregation cross cannot be combined with --guidance rgb, --ngpu or --pipeline"},
         {opt.census && multi, "--cost census" + with_multi},
         {opt.adcensus && multi, "--cost adcensus" + with_multi},
@@ -709,7 +753,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
-                       opt.cross;
+                       opt.cross || opt.so;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;
@@ -724,9 +768,9 @@ int main(int argc, char** argv) {
         return 1;
     }
     const int w = job.w = in.w, h = job.h = in.h, n = job.n = w * h;
-    if ((opt.rgb || opt.ad_rgb || opt.cross) && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
+    if ((opt.rgb || opt.ad_rgb || opt.cross || opt.so) && (in.channels[0] != in.channels[1] || in.channels[0] > 4)) {
         std::fprintf(stderr, "%s needs two images of 3 or of 4 channels, not %d and %d\n",
-                     opt.rgb ? "--guidance rgb" : opt.cross ? "--aggregation cross" : "--ad rgb",
+                     opt.rgb ? "--guidance rgb" : opt.so ? "--aggregation scanline" : opt.cross ? "--aggregation cross" : "--ad rgb",
                      in.channels[0], in.channels[1]);
         return 1;
     }

@@ -10,6 +10,7 @@
 #include "occlusion.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "colourGuidedFilter.cuh"
+#include "scanlineOptimization.cuh"
 #include "sgm.cuh"
 #include "regionVoting.cuh"
 #include "speckle.cuh"
@@ -242,5 +243,18 @@ void sgm_aggregate(float* cost, float* agg, float* best, float* disp_map, const 
         std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
         sgm_aggregateOnCPU(cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d, dmin, p);
         compare_aggregation("Semi-global matching", tb, td, ta, best, disp_map, agg, w * h, size_d);
+    }
+}
+
+// not in the reference: the scan-line optimiser with colour-adaptive penalties (smx_main --aggregation scanline / cross-scanline)
+void scanline_optimize(unsigned char* guide_own, unsigned char* guide_other, int channels, float* cost, float* agg, float* best,
+                       float* disp_map, const int w, const int h, const int size_d, const int dmin, const smx_scanline_params& p,
+                       bool host_gpu_compare) {
+    CHECK(smx_scanline_optimize(&p, guide_own, guide_other, channels, cost, agg, best, disp_map, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
+        scanline_optimizeOnCPU(guide_own, guide_other, channels, cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d,
+                               dmin, p);
+        compare_aggregation("Scan-line optimisation", tb, td, ta, best, disp_map, agg, w * h, size_d);
     }
 }

@@ -46,7 +46,7 @@ class ShardedPair:
     The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
     cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError, and so
     does region voting (PairPipeline(vote=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
-    one rank: aggregation="sgm" raises ValueError."""
+    one rank: aggregation="sgm" raises ValueError, and so do the scan-line optimiser's "scanline" / "cross-scanline"."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -60,6 +60,9 @@ class ShardedPair:
             raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
         if kw.get("vote") is not None or kw.get("vote_arms") is not None:
             raise ValueError("region voting is not part of the sharded driver: use PairPipeline(vote=...)")
+        if kw.get("aggregation") in ("scanline", "cross-scanline") or kw.get("scanline_params") is not None:
+            raise ValueError("the scan-line optimiser is not part of the sharded driver: use "
+                             f"PairPipeline(aggregation={kw.get('aggregation')!r})")
         if kw.get("aggregation") is not None:
             raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
         self.rank, self.world, self.group = rank, world, group

@@ -332,6 +332,27 @@ def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
     return agg, best, disp
 
 
+def scanline_optimize(guide_own, guide_other, cost, dmin=0, params=None, want_agg=True):
+    """Scan-line optimisation with colour-adaptive penalties of one view's (size_d, h, w) float32 cost volume
+    (smx_scanline_optimize; include/smx.h has the definition).  guide_own is that view's guide and guide_other the other
+    view's, both (h, w) or (h, w, 1 | 3 | 4) uint8; the partner of (x, y) at slice z is (x + dmin + z, y) in guide_other.
+    Returns (agg, best, disp_map) as sgm_aggregate does."""
+    c = _c(cost, np.float32)
+    g, o = _c(guide_own, np.uint8), _c(guide_other, np.uint8)
+    if c.ndim != 3:
+        raise ValueError("scanline_optimize expects a (size_d, h, w) float32 volume")
+    size_d, h, w = c.shape
+    if g.ndim not in (2, 3) or g.shape[:2] != (h, w) or o.shape != g.shape:
+        raise ValueError("scanline_optimize expects two (h, w) or two (h, w, channels) uint8 guides of the volume's shape")
+    ch = 1 if g.ndim == 2 else g.shape[2]
+    p = params if params is not None else _lib.default_scanline_params()
+    agg = np.empty((size_d, h, w), np.float32) if want_agg else None
+    best, disp = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_scanline_optimize(C.byref(p), _ptr(g), _ptr(o), ch, _ptr(c), None if agg is None else _ptr(agg),
+                                                _ptr(best), _ptr(disp), w, h, size_d, int(dmin)))
+    return agg, best, disp
+
+
 def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, want_agg=False,
                 params=None):
     """main.cu:65-155 on two gray images, device-resident between the stages."""
