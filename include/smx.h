@@ -923,6 +923,69 @@ int smx_scanline_optimize(const smx_scanline_params* p, const uint8_t* guide_own
  * smx_ctx_stereo_pair_async while it is on.  The workspace and the volumes are allocated on first use. */
 int smx_ctx_set_scanline(smx_ctx* ctx, const smx_scanline_params* p);
 
+/* ------------------------------------------------------------------------------------
+ * Depth-discontinuity adjustment of a label map from the aggregated costs (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The depth-discontinuity adjustment of Mei et al. 2011, the step between the interpolation and the sub-pixel fit: a pixel
+ * beside a step of the label map takes a neighbour's label where the aggregated volume says that label costs it less.  The
+ * stages behind the winner-take-all pass put labels in without asking the costs (the vote, the interpolation, the fill); at a
+ * depth step the fill carries one surface's label across the band that the LR check rejected, and this stage moves the edge
+ * back to where the costs have it.  Integers and comparisons only, apart from the one f32 formula of the sub-pixel map: the
+ * result is the same bits in every run.  tests/adjust_ref.py is this definition in numpy; the result equals it bit for bit.
+ *
+ * Inputs.
+ *   disp     f32 [h][w]: a label map of one view (n = w*h floats)
+ *   A        f32 [size_d][h][w]: that view's aggregated volume, the layout of d_agg / agg_l of every aggregation
+ *   dmin, size_d   the label range
+ *
+ * Labelled pixel: p is labelled iff disp[p] is finite, integer-valued and 0 <= disp[p] - dmin < size_d; its slice is
+ *   z(p) = disp[p] - dmin.  The LR marker dmin - 100, NaN, +-inf and fractional values are not labelled; -0 is the label 0.  An
+ *   unlabelled pixel is copied bit for bit and is nobody's candidate.
+ * Candidates of a labelled p = (x, y), in this order: (x-1, y), (x+1, y) and, with vertical == 1, (x, y-1), (x, y+1); only those
+ *   that lie inside the image, are labelled and have |z(q) - z(p)| >= tau_e, in integers.  A pixel without a candidate is
+ *   copied bit for bit: it is not on a discontinuity.
+ * Choice: best = A[z(p)][p]; for each candidate q in order, if A[z(q)][p] < best (plain f32 comparison, false for a NaN) then
+ *   best = A[z(q)][p] and p takes disp[q], the candidate's bits.  The own label wins ties, among equal candidates the first
+ *   wins, a NaN cost never wins and a NaN own cost is never replaced.
+ * Rounds: `iterations` Jacobi rounds, each reads the map of the round before as a snapshot and writes another.  A pixel changed
+ *   in round k is a candidate in round k + 1, so an edge moves at most one pixel a round.  A pixel's own cost never rises.
+ *   There is no early exit.
+ * Sub-pixel map: d_sub NULL, or n floats IN/OUT with subpix_mode SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR.  A pixel whose
+ *   final label differs from its input label gets sub[p] = out[p] + smx_subpixel_delta(mode, A[z'][p], A[z'-1][p], A[z'+1][p])
+ *   with z' its final slice and NaN for a neighbour outside 0 .. size_d - 1 (delta 0 then); every other pixel of d_sub is left
+ *   untouched.  With d_sub NULL subpix_mode must be 0 or one of the two.
+ *
+ * Defaults: tau_e 2, vertical 1, iterations 1 (Mei's single pass).  Valid: 1 <= tau_e <= 512, vertical 0 or 1,
+ * 1 <= iterations <= 8, 1 <= size_d <= 512, w, h >= 1, w*h < 2^31, any int for dmin; anything else is SMX_E_ARG before any
+ * device call.
+ *
+ * smx_dev_discontinuity_adjust: device pointers; `iterations` kernel launches on `stream`, and in front of them one
+ * device-to-device copy of the map into the workspace where d_out == d_disp (the only overlap allowed); no allocation, no
+ * synchronisation (graph-capturable).  Nothing is written outside [0, smx_adjust_workspace_bytes(w, h)) of d_ws (two maps of n
+ * floats plus 255 bytes; 0 for invalid w, h), the n floats of d_out and the changed pixels of d_sub; the workspace may hold
+ * anything and needs no alignment; a smaller one is SMX_E_WS before any launch; d_agg is not modified, and d_disp only as d_out.
+ * smx_discontinuity_adjust: host pointers, synchronous; sub NULL or n floats IN/OUT. */
+typedef struct smx_adjust_params { int tau_e, vertical, iterations; } smx_adjust_params;
+void smx_default_adjust_params(smx_adjust_params* p);
+size_t smx_adjust_workspace_bytes(int w, int h);
+int smx_dev_discontinuity_adjust(const smx_adjust_params* p, const float* d_disp, const float* d_agg, float* d_out, int w, int h,
+                                 int dmin, int size_d, int subpix_mode, float* d_sub, void* d_ws, size_t ws_bytes, void* stream);
+int smx_discontinuity_adjust(const smx_adjust_params* p, const float* disp, const float* agg, float* out, int w, int h, int dmin,
+                             int size_d, int subpix_mode, float* sub);
+/* Test hook, NOT part of the stable contract (it may change or go with the kernel): the footprint of a workgroup of the round
+ * kernel (columns, rows), so that the tests put their shapes and depth steps on the seams between workgroups. */
+int smx_adjust_geometry(int* cols, int* rows);
+/* The adjustment of this context.  NULL switches it off (the default).  While it is on, smx_ctx_stereo_pair / _rgb keeps the
+ * aggregated volumes as when agg_l is requested, through whichever aggregation is set (every aggregation of the context
+ * delivers whole volumes: the guided filter, SGM, the colour guide, cross-based aggregation, the scan-line optimiser and the
+ * chain), and runs smx_dev_discontinuity_adjust on the filled left map with the left volume, behind LR check -> uniqueness ->
+ * speckle -> vote -> fill -> sub-pixel fit: out->filled becomes the adjusted map, and with smx_ctx_set_subpixel on the
+ * context's sub-pixel filled map carries the changed pixels' own fits.  The validity map is NOT replaced.  A context of more than
+ * 512 labels cannot deliver the stage its label range: the setter returns SMX_E_ARG with a message (the pair call checks it
+ * again).  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on.  Buffers are allocated on first use. */
+int smx_ctx_set_adjust(smx_ctx* ctx, const smx_adjust_params* p);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -13,10 +13,10 @@ Layout
 Importing the package does not load the HIP library; the first compute call does, and fails
 loudly if it has not been built.
 """
-from ._lib import (AdCensusParams, CensusParams, CrossParams, Params, ScanlineParams, SgmParams, SmxError, SpeckleParams, VoteParams, WmfParams, build, check,  # noqa: F401
-                   default_adcensus_params, default_census_params, default_cross_params, default_params, default_scanline_params, default_sgm_params, default_speckle_params, default_vote_params, default_wmf_params, lib,
+from ._lib import (AdCensusParams, AdjustParams, CensusParams, CrossParams, Params, ScanlineParams, SgmParams, SmxError, SpeckleParams, VoteParams, WmfParams, build, check,  # noqa: F401
+                   default_adcensus_params, default_adjust_params, default_census_params, default_cross_params, default_params, default_scanline_params, default_sgm_params, default_speckle_params, default_vote_params, default_wmf_params, lib,
                    subpixel_delta)
-from .stages import (adcensus_cost, adcensus_tables, census_cost, census_transform, colour_guided_filter, compute_cost, cross_aggregate, compute_guided_filter, detect_occlusion,  # noqa: F401
+from .stages import (adcensus_cost, adcensus_tables, census_cost, census_transform, colour_guided_filter, compute_cost, cross_aggregate, compute_guided_filter, detect_occlusion, discontinuity_adjust,  # noqa: F401
                      fill_occlusion, filter, init_wta, integral, region_vote, rgb_to_grayscale, scanline_optimize, sgm_aggregate, speckle_filter, stereo_pair,
                      uniqueness_filter, weighted_median, wmf_weights, write_mat)
 
@@ -28,4 +28,5 @@ __all__ = ["Params", "SmxError", "build", "default_params", "lib", "rgb_to_grays
            "SgmParams", "default_sgm_params", "sgm_aggregate", "uniqueness_filter", "colour_guided_filter",
            "AdCensusParams", "default_adcensus_params", "adcensus_tables", "adcensus_cost",
            "CrossParams", "default_cross_params", "cross_aggregate", "VoteParams", "default_vote_params", "region_vote",
-           "ScanlineParams", "default_scanline_params", "scanline_optimize"]
+           "ScanlineParams", "default_scanline_params", "scanline_optimize",
+           "AdjustParams", "default_adjust_params", "discontinuity_adjust"]

@@ -77,6 +77,11 @@ class VoteParams(C.Structure):
     _fields_ = [("tau_s", C.c_int), ("tau_h_pct", C.c_int), ("iterations", C.c_int), ("interpolate", C.c_int)]
 
 
+class AdjustParams(C.Structure):
+    """smx_adjust_params: the depth-discontinuity adjustment from the aggregated costs (not a stage of the reference)."""
+    _fields_ = [("tau_e", C.c_int), ("vertical", C.c_int), ("iterations", C.c_int)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -107,6 +112,7 @@ _GP = C.POINTER(SgmParams)
 _XP = C.POINTER(CrossParams)
 _VP = C.POINTER(VoteParams)
 _LP = C.POINTER(ScanlineParams)
+_JP = C.POINTER(AdjustParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -221,6 +227,12 @@ SIGNATURES = {
     "smx_dev_scanline_wta_pair": (_i, [_LP, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "smx_scanline_optimize": (_i, [_LP, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_scanline": (_i, [_vp, _LP]),
+    "smx_default_adjust_params": (None, [_JP]),
+    "smx_adjust_workspace_bytes": (_sz, [_i, _i]),
+    "smx_dev_discontinuity_adjust": (_i, [_JP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "smx_discontinuity_adjust": (_i, [_JP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "smx_adjust_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "smx_ctx_set_adjust": (_i, [_vp, _JP]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -334,6 +346,12 @@ def default_scanline_params():
 def default_vote_params():
     p = VoteParams()
     lib().smx_default_vote_params(C.byref(p))
+    return p
+
+
+def default_adjust_params():
+    p = AdjustParams()
+    lib().smx_default_adjust_params(C.byref(p))
     return p
 
 

@@ -54,6 +54,10 @@ bool vote_params_ok(const smx_vote_params* p);         // (smx_vote.hip, beside 
 bool vote_shape_ok(int w, int h, int size_d);
 constexpr const char* VOTE_RANGES = "needs tau_s >= 0, 0 <= tau_h_pct <= 99, 0 <= iterations <= 8 and interpolate 0 or 1";
 constexpr const char* VOTE_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
+bool adjust_params_ok(const smx_adjust_params* p);     // (smx_adjust.hip, beside the limits of its kernel)
+bool adjust_shape_ok(int w, int h, int size_d);
+constexpr const char* ADJUST_RANGES = "needs 1 <= tau_e <= 512, vertical 0 or 1 and 1 <= iterations <= 8";
+constexpr const char* ADJUST_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

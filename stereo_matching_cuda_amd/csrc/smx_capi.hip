@@ -800,6 +800,34 @@ int smx_dev_region_vote(const smx_vote_params* p, const uint32_t* d_arms, const 
                               (hipStream_t)stream);
 }
 
+// ---- depth-discontinuity adjustment from the aggregated costs (not in the reference; smx_adjust.hip) -------------------
+void smx_default_adjust_params(smx_adjust_params* p) {
+    if (!p) return;
+    p->tau_e = 2; p->vertical = 1; p->iterations = 1;
+}
+
+size_t smx_adjust_workspace_bytes(int w, int h) { return adjust_shape_ok(w, h, 1) ? adjust_workspace_bytes(w, h) : 0; }
+
+int smx_adjust_geometry(int* cols, int* rows) {
+    SMX_ARG(cols && rows);
+    adjust_tile(cols, rows);
+    return SMX_OK;
+}
+
+int smx_dev_discontinuity_adjust(const smx_adjust_params* p, const float* d_disp, const float* d_agg, float* d_out, int w, int h,
+                                 int dmin, int size_d, int subpix_mode, float* d_sub, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: %s", ADJUST_RANGES);
+    if (!adjust_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: %s", ADJUST_SHAPES);
+    SMX_ARG(d_disp && d_agg && d_out);
+    if (d_sub ? !subpix_mode_ok(subpix_mode) : subpix_mode != 0 && !subpix_mode_ok(subpix_mode))
+        return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: subpix_mode must be SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR "
+                               "(or 0 without d_sub)");
+    if (!d_ws || ws_bytes < adjust_workspace_bytes(w, h))
+        return fail(SMX_E_WS, "smx_dev_discontinuity_adjust: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
+                    adjust_workspace_bytes(w, h));
+    return launch_discontinuity_adjust(p, d_disp, d_agg, d_out, w, h, dmin, size_d, subpix_mode, d_sub, d_ws, (hipStream_t)stream);
+}
+
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,
                    float* d_var, void* stream) {
     SMX_ARG(p && d_image && d_mean && d_var && w >= 1 && h >= 1 && p->radius >= 0);

@@ -62,6 +62,10 @@ struct smx_ctx {
     smx_vote_params vote_params;
     smx_cross_params vote_arms;
     DevBuf varms, voted, vote_ws;
+    // depth-discontinuity adjustment (smx_ctx_set_adjust): the stage's workspace; it reads the left volume of aggLR
+    bool adjust = false;
+    smx_adjust_params adj_params;
+    DevBuf adj_ws;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -96,7 +100,7 @@ struct smx_ctx {
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so; };
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -127,6 +131,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
         SMX_HIP(c->voted.ensure(fb));
         SMX_HIP(c->vote_ws.ensure(vote_workspace_bytes(c->w, c->h)));
     }
+    if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
     // The chunk of ctx_aggregate_chunks.  Colour guide and cross: the halving rule on their workspace.  The guided flow from
     // census codes: every slice with whole volumes, else what fits 1 GiB of cost slices exactly (at least one).  Then the
     // calling thread's smx_set_max_slices_per_launch bounds it, like the chunks inside every entry.
@@ -305,9 +310,14 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
             return rc;
         if ((rc = launch_fill_occlusion(voted, out.fil, w, h, (float)in.dminl, st))) return rc;
     }
-    if (!need.subpix) return SMX_OK;
-    return smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl, c->sub.as<float>(),
-                                 c->subf.as<float>(), st);
+    if (need.subpix && (rc = smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl,
+                                                   c->sub.as<float>(), c->subf.as<float>(), st)))
+        return rc;
+    if (!need.adjust) return SMX_OK;
+    // the filled map looks at the left volume again: a pixel beside a depth step takes the neighbour's label where that costs
+    // it less, in place, and its entry of the sub-pixel filled map becomes its own fit; `kept` is not replaced
+    return smx_dev_discontinuity_adjust(&c->adj_params, out.fil, aggL, out.fil, w, h, in.dminl, size_d, c->subpix,
+                                        need.subpix ? c->subf.as<float>() : nullptr, c->adj_ws.p, adjust_workspace_bytes(w, h), st);
 }
 
 static int ctx_check_device(smx_ctx* c, const char* who) {
@@ -409,9 +419,13 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     if (c->adcensus && c->adc.colour && !channels)
         return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
                                "smx_ctx_stereo_pair_rgb", who);
-    // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q)
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so};
+    if (c->adjust && !adjust_shape_ok(c->w, c->h, c->size_d))
+        return fail(SMX_E_ARG, "%s: the depth-discontinuity adjustment (smx_ctx_set_adjust) %s", who, ADJUST_SHAPES);
+    // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
+    // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust, c->subpix != 0,
+                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
+                            c->adjust};
     if ((rc = ctx_reserve(c, need))) return rc;
     if (c->adcensus && !c->adc_tab_valid) {
         SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
@@ -592,6 +606,17 @@ int smx_ctx_set_vote(smx_ctx* c, const smx_vote_params* vote, const smx_cross_pa
     return SMX_OK;
 }
 
+int smx_ctx_set_adjust(smx_ctx* c, const smx_adjust_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_adjust: %s", ADJUST_RANGES);
+        if (!adjust_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "smx_ctx_set_adjust: %s", ADJUST_SHAPES);
+        c->adj_params = *p;
+    }
+    c->adjust = p != nullptr;
+    return SMX_OK;
+}
+
 int smx_ctx_vote_map(smx_ctx* c, float* voted) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
@@ -652,6 +677,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
     if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
     if (c->vote) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: region voting is on (smx_ctx_set_vote): use smx_ctx_stereo_pair");
+    if (c->adjust)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the depth-discontinuity adjustment is on (smx_ctx_set_adjust): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)

@@ -356,6 +356,29 @@ int smx_region_vote(const smx_vote_params* p, const smx_cross_params* cross, con
     return SMX_OK;
 }
 
+int smx_discontinuity_adjust(const smx_adjust_params* p, const float* disp, const float* agg, float* out, int w, int h, int dmin,
+                             int size_d, int subpix_mode, float* sub) {
+    if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_discontinuity_adjust: %s", ADJUST_RANGES);
+    if (!adjust_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_discontinuity_adjust: %s", ADJUST_SHAPES);
+    SMX_ARG(disp && agg && out);
+    if (sub ? !subpix_mode_ok(subpix_mode) : subpix_mode != 0 && !subpix_mode_ok(subpix_mode))
+        return fail(SMX_E_ARG, "smx_discontinuity_adjust: subpix_mode must be SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR (or 0 "
+                               "without sub)");
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), wsb = adjust_workspace_bytes(w, h);
+    DevBuf dD, dA, dS, dW;
+    SMX_HIP(dD.upload(disp, fb));
+    SMX_HIP(dA.upload(agg, fb * size_d));
+    if (sub) SMX_HIP(dS.upload(sub, fb));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_discontinuity_adjust(p, dD.as<float>(), dA.as<float>(), dD.as<float>(), w, h, dmin, size_d, subpix_mode,
+                                              sub ? dS.as<float>() : nullptr, dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dD.download(out, fb));
+    if (sub) SMX_HIP(dS.download(sub, fb));
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -85,4 +85,10 @@ size_t vote_workspace_bytes(int w, int h);
 int launch_region_vote(const smx_vote_params* p, const uint32_t* arms, const uint8_t* guide, int ch, const float* disp,
                        const float* disp_r, float* out, int w, int h, int dmin, int size_d, int d_lr, void* ws, hipStream_t st);
 void vote_tile(int* tw, int* th);
+// smx_adjust.hip: depth-discontinuity adjustment from the aggregated costs (smx_dev_discontinuity_adjust); ws:
+// adjust_workspace_bytes(w, h) bytes
+size_t adjust_workspace_bytes(int w, int h);
+int launch_discontinuity_adjust(const smx_adjust_params* p, const float* disp, const float* vol, float* out, int w, int h, int dmin,
+                                int size_d, int mode, float* sub, void* ws, hipStream_t st);
+void adjust_tile(int* tw, int* th);
 }  // namespace smx

@@ -27,7 +27,7 @@ class PairPipeline:
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
                  aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
-                 vote=None, vote_arms=None, scanline_params=None):
+                 vote=None, vote_arms=None, scanline_params=None, adjust=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -92,7 +92,25 @@ class PairPipeline:
         slices with its q collected into self.so_cost and its keys discarded, then the scan-line optimiser on those volumes,
         which it reads through the clamp: q's four fractional bits are truncated.  max_ws_bytes counts the volumes, the
         workspaces and the chunk buffers; a slice sub-range, more than 256 labels or a size that does not fit raises
-        ValueError."""
+        ValueError.
+        adjust: None, True (the defaults) or AdjustParams -- the depth-discontinuity adjustment from the aggregated costs (not a
+        stage of the reference; include/smx.h smx_dev_discontinuity_adjust): the aggregation keeps its volumes in self.agg as
+        with want_agg, whichever aggregation is set, and discontinuity_adjust() runs behind LR check -> uniqueness -> speckle ->
+        vote -> fill -> sub-pixel fit and in front of the weighted median, on self.filled with the left volume, into
+        self.adjusted; self.filled is rewritten with it, and with subpixel on self.sub_filled carries the changed pixels' own
+        fits.  The validity map is not replaced.  max_ws_bytes counts the volumes and the stage's workspace; a slice sub-range
+        (a D-shard has no whole volume), more than 512 labels or a size that does not fit raises ValueError.  With None nothing
+        is allocated or launched."""
+        if adjust is not None and adjust is not True and not isinstance(adjust, _lib.AdjustParams):
+            raise ValueError(f"adjust must be None, True or AdjustParams, not {adjust!r}")
+        if isinstance(adjust, _lib.AdjustParams) and not (1 <= adjust.tau_e <= 512 and adjust.vertical in (0, 1) and
+                                                          1 <= adjust.iterations <= 8):
+            raise ValueError("adjust needs 1 <= tau_e <= 512, vertical 0 or 1 and 1 <= iterations <= 8")
+        if adjust is not None:
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("the depth-discontinuity adjustment reads a pixel's whole aggregated column: no slice sub-range")
+            if not 1 <= int(size_d) <= 512:
+                raise ValueError("the depth-discontinuity adjustment takes 1 .. 512 labels")
         if guidance not in (None, "rgb"):
             raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
         if guidance and aggregation:
@@ -135,6 +153,19 @@ class PairPipeline:
         self.device = torch.device(device)
         self.params = params if params is not None else _lib.default_params()
         self.aggregation = aggregation
+        self.adjust = self.adjusted = self.adjust_ws = None
+        self.adjust_ws_bytes = 0
+        if adjust is not None:
+            self.adjust_ws_bytes = int(self.lib.smx_adjust_workspace_bytes(self.w, self.h))
+            if self.adjust_ws_bytes == 0:
+                raise ValueError(f"the depth-discontinuity adjustment does not take {self.w} x {self.h} (w*h < 2^31)")
+            held = 2 * self.size_d * self.n * 4 + self.adjust_ws_bytes
+            if held > max_ws_bytes:
+                raise ValueError(f"the depth-discontinuity adjustment needs {held} bytes for the two aggregated volumes and its "
+                                 f"workspace: more than max_ws_bytes = {max_ws_bytes}")
+            max_ws_bytes -= held                # what is left for the aggregation
+            want_agg = True
+            self.adjust = _lib.default_adjust_params() if adjust is True else adjust
         self.sgm_params = self.sgm_cost = self.sgm_ws = None
         self.sgm_ws_bytes = 0
         if sgm:
@@ -240,6 +271,9 @@ class PairPipeline:
             self.voted = torch.empty((self.h, self.w), **f)
             self.vote_arms_plane = torch.empty((self.h, self.w), dtype=torch.int32, device=dev)
             self.vote_ws = torch.empty(self.vote_ws_bytes, dtype=torch.uint8, device=dev)
+        if self.adjust:
+            self.adjusted = torch.empty((self.h, self.w), **f)
+            self.adjust_ws = torch.empty(self.adjust_ws_bytes, dtype=torch.uint8, device=dev)
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
         self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and aggregation != "scanline" else None
         if cost == "adcensus":
@@ -589,6 +623,8 @@ class PairPipeline:
             self.region_vote()
         if self.subpixel:
             self.subpixel_maps()
+        if self.adjust:
+            self.discontinuity_adjust()
         if self.wmf:
             self.refine()
 
@@ -648,6 +684,18 @@ class PairPipeline:
                                                       self.h, self.dminl, _dp(self.sub), _dp(self.sub_filled),
                                                       self._stream()))
 
+    def discontinuity_adjust(self):
+        """self.adjusted = self.filled with the pixels beside its depth steps moved to the neighbour's label where the left
+        aggregated volume says that costs them less (smx_dev_discontinuity_adjust, one launch a round); self.filled is
+        rewritten with it, and with subpixel on the changed pixels of self.sub_filled become their own fits."""
+        with self._on_device():
+            mode = _lib.SUBPIX_MODES[self.subpixel] if self.subpixel else 0
+            _lib.check(self.lib.smx_dev_discontinuity_adjust(C.byref(self.adjust), _dp(self.filled), _dp(self.agg[0]),
+                                                             _dp(self.adjusted), self.w, self.h, self.dminl, self.size_d, mode,
+                                                             _dp(self.sub_filled), _dp(self.adjust_ws), self.adjust_ws_bytes,
+                                                             self._stream()))
+            self.filled.copy_(self.adjusted)
+
     def refine(self):
         """The weighted median of the filled left map, guided by the left image the last aggregate() saw, into
         self.refined (smx_dev_weighted_median; labels dminl .. dminl + size_d - 1)."""
@@ -661,8 +709,8 @@ class PairPipeline:
 
     def finish_per_call(self):
         """The same through the per-stage entry points (the reference's call sequence, seven launches); with the uniqueness
-        test or speckle removal on, uniqueness_filter() / despeckle() / region_vote() behind them, as in finish().  The sub-pixel fit and the
-        weighted median are not run."""
+        test or speckle removal on, uniqueness_filter() / despeckle() / region_vote() behind them, as in finish().  The sub-pixel fit, the
+        depth-discontinuity adjustment behind it and the weighted median are not run."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             _lib.check(L.smx_dev_init_wta(_dp(self.best), _dp(self.dmap), 2 * self.n, st))
@@ -711,6 +759,8 @@ class PairPipeline:
             r["despeckled"] = c(self.despeckled)
         if self.vote:
             r["voted"] = c(self.voted)
+        if self.adjust:
+            r["adjusted"] = c(self.adjusted)
         if self.subpixel:
             r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.sub[0]), c(self.sub[1]), c(self.sub_filled)
         return r

@@ -14,6 +14,7 @@
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
 #include "crossAggregation.cuh"
+#include "discontinuityAdjustment.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "integral.cuh"
@@ -440,6 +441,57 @@ void region_voteOnCPU(const unsigned char* guide, int channels, const float* dis
                     break;
                 }
         }
+}
+
+// ---- discontinuityAdjustment.cuh (not in the reference) ------------------------------------------
+// The definition of include/smx.h (above smx_adjust_workspace_bytes) pixel by pixel: per round a snapshot, per labelled pixel its
+// up to four candidates in the order left, right, up, down.  The sub-pixel formula is smx_subpixel_delta's, restated.
+static float subpixel_deltaOnCPU(int mode, float c0, float lo, float hi) {
+    if (lo != lo || hi != hi) return 0.0f;
+    const float a = lo - c0, b = hi - c0;
+    const float den = mode == SMX_SUBPIX_PARABOLA ? a + b : fmaxf(a, b);
+    const float d = (a - b) / (2.0f * den);
+    return d - d == 0.0f ? d : 0.0f;
+}
+
+void discontinuityAdjustOnCPU(const float* disparity, const float* agg, float* out, const int w, const int h, const int dmin,
+                              const int size_d, const smx_adjust_params& p, int subpix_mode, float* sub) {
+    const size_t n = (size_t)w * h;
+    auto slice = [&](float v) -> int {          // of a labelled value, else -1
+        if (!(std::fabs(v) < 1099511627776.0f) || v != std::trunc(v)) return -1;
+        const long long z = (long long)v - dmin;
+        return z >= 0 && z < size_d ? (int)z : -1;
+    };
+    static const int step[4][2] = {{-1, 0}, {1, 0}, {0, -1}, {0, 1}};      // (dx, dy): left, right, up, down
+    vector<float> cur(disparity, disparity + n), next(n);
+    for (int k = 0; k < p.iterations; ++k) {
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t id = (size_t)y * w + x;
+                next[id] = cur[id];
+                const int z = slice(cur[id]);
+                if (z < 0) continue;
+                float best = agg[(size_t)z * n + id];
+                int zb = z;
+                for (int e = 0; e < (p.vertical ? 4 : 2); ++e) {
+                    const int qx = x + step[e][0], qy = y + step[e][1];
+                    if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                    const size_t q = (size_t)qy * w + qx;
+                    const int zq = slice(cur[q]);
+                    if (zq < 0 || std::abs(zq - z) < p.tau_e) continue;
+                    const float c = agg[(size_t)zq * n + id];
+                    if (c < best) { best = c; zb = zq; next[id] = cur[q]; }
+                }
+                if (zb != z && sub) {
+                    const float nan = std::numeric_limits<float>::quiet_NaN();
+                    const float lo = zb > 0 ? agg[(size_t)(zb - 1) * n + id] : nan;
+                    const float hi = zb + 1 < size_d ? agg[(size_t)(zb + 1) * n + id] : nan;
+                    sub[id] = next[id] + subpixel_deltaOnCPU(subpix_mode, best, lo, hi);
+                }
+            }
+        cur.swap(next);
+    }
+    for (size_t id = 0; id < n; ++id) out[id] = cur[id];
 }
 
 // ---- occlusion.cuh -------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //                                    D_MIN..D_MAX from the macros, outputs into ./data/
 //   smx_main L.png R.png [dmin dmax [outdir]] [options]
 // options (not in the reference).  The opt-in costs, aggregations and stages (--cost census / adcensus, --aggregation sgm /
-// cross / scanline / cross-scanline, --guidance rgb, --uniqueness, --speckle, --vote, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
+// cross / scanline / cross-scanline, --guidance rgb, --uniqueness, --speckle, --vote, --adjust, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
 // an entry says otherwise; none of them goes with --ngpu or --pipeline:
 //   --fused           one device-resident call for everything after the gray conversion
 //                     (smx_stereo_pair: cost built on the fly inside the fused aggregation) instead of
@@ -54,6 +54,16 @@
 //                     occlu_mapl_voted.png beside the 12 images; occlu_mapl_filled.png (and --wmf, --subpixel, --pfm, --png16
 //                     behind it) then come from the voted map, while the validity test of --subpixel and --wmf occluded stays
 //                     the one without it.  At most 512 labels.  With --host-compare the CPU twin (region_voteOnCPU) redoes it
+//   --adjust [TAU[,N]]  depth-discontinuity adjustment of the filled left map from the left aggregated volume
+//                     (smx_ctx_set_adjust; Mei et al.'s step behind the interpolation, not in the reference; implies --fused): a
+//                     pixel beside a step of at least TAU labels (1 .. 512; default 2) takes the neighbour's label where the
+//                     aggregated volume says that label costs it less, in N rounds (1 .. 8; default 1), so that an edge which the
+//                     fill carried across a rejected band moves back by a pixel a round.  The value is optional, like --vote's.
+//                     --adjust-vertical 0|1 leaves out or takes the neighbours above and below (default 1).  It runs behind
+//                     the fill and --subpixel and in front of --wmf, through every aggregation: occlu_mapl_filled.png, --wmf,
+//                     --pfm and --png16 then come from the adjusted map, which occlu_mapl_adjusted.png holds too, and with
+//                     --subpixel the changed pixels carry their own fits.  At most 512 labels.  With --host-compare the CPU twin
+//                     (discontinuityAdjustOnCPU) redoes it from the twin of the fill
 //   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
 //                     census cost, --census-window / --census-th included, unless --cost reference is given): the same
 //                     twelve images, the two mean images empty.
@@ -120,6 +130,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "scanlineOptimization.cuh"
 #include "crossAggregation.cuh"
+#include "discontinuityAdjustment.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
 #include "uniqueness.cuh"
@@ -152,6 +163,8 @@ struct Options {
     bool vote = false;       // --vote
     smx_vote_params vote_params;
     smx_cross_params vote_arms;
+    bool adjust = false;     // --adjust
+    smx_adjust_params adjust_params;
     bool rgb = false;        // --guidance rgb
     float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
@@ -284,6 +297,9 @@ const ValueOption value_options[] = {
     {"--vote-tau", "T1,T2 with 1 <= T2 <= T1 <= 256", [](auto& v, auto& o) {
          int& t1 = o.vote_arms.tau1; int& t2 = o.vote_arms.tau2;
          return pair_of(v, ',', t1, t2) && t2 >= 1 && t2 <= t1 && t1 <= 256; }},
+    {"--adjust-vertical", "0 or 1", [](auto& v, auto& o) {
+         o.adjust_params.vertical = word(v, {"0", "1"});
+         return o.adjust_params.vertical >= 0; }},
     {"--uniqueness", "a percentage PCT with 0 <= PCT < 100", [](auto& v, auto& o) {
          char* end = nullptr;
          const float pct = std::strtof(v.c_str(), &end);
@@ -303,6 +319,14 @@ const ValueOption optional_value_options[] = {
          const int got = std::sscanf(v.c_str(), "%d%c%d%c%d%c", &p.tau_s, &c1, &p.tau_h_pct, &c2, &p.iterations, &rest);
          return ((got == 3 && c1 == ',') || (got == 5 && c1 == ',' && c2 == ',')) && p.tau_s >= 0 && p.tau_h_pct >= 0 &&
                 p.tau_h_pct <= 99 && p.iterations >= 0 && p.iterations <= 8; }},
+    {"--adjust", "TAU[,N] with 1 <= TAU <= 512 and 1 <= N <= 8", [](auto& v, auto& o) {
+         smx_adjust_params& p = o.adjust_params;
+         o.adjust = true;
+         if (v.empty()) return true;
+         char comma = 0, rest = 0;
+         p.tau_e = 0;
+         const int got = std::sscanf(v.c_str(), "%d%c%d%c", &p.tau_e, &comma, &p.iterations, &rest);
+         return (got == 1 || (got == 3 && comma == ',')) && p.tau_e >= 1 && p.tau_e <= 512 && p.iterations >= 1 && p.iterations <= 8; }},
 };
 
 // A row of a table of refusals: the first row that holds prints its message, and the exit status is 2.
@@ -318,6 +342,7 @@ Options parse(int argc, char** argv) {
     smx_default_adcensus_params(&o.adc_params);
     smx_default_vote_params(&o.vote_params);
     smx_default_cross_params(&o.vote_arms);
+    smx_default_adjust_params(&o.adjust_params);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -356,7 +381,8 @@ Options parse(int argc, char** argv) {
         {o.saw({"--so-p", "--so-tau", "--so-paths"}) && !o.so,
          "--so-p, --so-tau and --so-paths need --aggregation scanline or cross-scanline"},
         {o.saw({"--vote-interpolate", "--vote-arms", "--vote-tau"}) && !o.vote,
-         "--vote-interpolate, --vote-arms and --vote-tau need --vote"}};
+         "--vote-interpolate, --vote-arms and --vote-tau need --vote"},
+        {o.saw({"--adjust-vertical"}) && !o.adjust, "--adjust-vertical needs --adjust"}};
     for (const Rule& r : rules)
         if (r.refused) return refuse(r.message);
     return o;
@@ -393,6 +419,7 @@ struct Maps {
     std::vector<float> occlusion, filled;
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
+    std::vector<float> adjusted;       // --adjust: the filled left map with the pixels beside its depth steps adjusted (= filled)
     std::vector<float> unique;         // --uniqueness: the LR-checked left map without its ambiguous winners
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
     std::vector<float> refined;        // --wmf: the weighted median of the filled left map
@@ -460,7 +487,7 @@ void check_aggregation_twin(const Job& j, Maps& m) {
 }
 
 // --host-compare of the device-resident flow behind the winners: LR check, uniqueness (from the left aggregated volume), speckle
-// removal and fill, each twin from the twin before it.
+// removal, region voting, fill and depth-discontinuity adjustment, each twin from the twin before it.
 void check_finish_twins(const Job& j, Maps& m, std::vector<float>& agg_l) {
     const Options& opt = j.opt;
     const int n = j.n;
@@ -494,7 +521,15 @@ void check_finish_twins(const Job& j, Maps& m, std::vector<float>& agg_l) {
         lr = twin;
     }
     fill_occlusionOnCPU(lr.data(), j.w, j.h, vmin);
-    ok = check_errors(lr.data(), m.filled.data(), n) && ok;
+    if (opt.adjust) {
+        // (the context hands out the adjusted map only: the twin of the fill goes through the twin of the adjustment)
+        std::vector<float> twin(n);
+        discontinuityAdjustOnCPU(lr.data(), agg_l.data(), twin.data(), j.w, j.h, j.d_lo, j.size_d, opt.adjust_params, 0, nullptr);
+        lr = twin;
+    }
+    const bool same_filled = check_errors(lr.data(), m.filled.data(), n);
+    if (opt.adjust && same_filled) std::cout << "Discontinuity adjustment ok!" << std::endl;
+    ok = same_filled && ok;
     if (ok) std::cout << "Occlusion ok!" << std::endl;
 }
 
@@ -567,8 +602,8 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     // (SGM, the colour guide, cross-based aggregation and the scan-line optimiser have no mean images)
     if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
-    std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness twin reads
-    if (uniq && host_compare) {
+    std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness and adjustment twins read
+    if ((uniq || opt.adjust) && host_compare) {
         agg_l.resize((size_t)n * j.size_d);
         out.agg_l = agg_l.data();
     }
@@ -583,6 +618,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
     if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
     if (opt.vote) CHECK(smx_ctx_set_vote(ctx, &opt.vote_params, &opt.vote_arms));
+    if (opt.adjust) CHECK(smx_ctx_set_adjust(ctx, &opt.adjust_params));
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
@@ -632,6 +668,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
         m.unique.resize(n);
         CHECK(smx_ctx_uniqueness_map(ctx, m.unique.data(), nullptr));
     }
+    if (opt.adjust) m.adjusted = m.filled;
     if (sh.create) CHECK(sh.destroy(sctx));
     else CHECK(smx_destroy(ctx));
     std::cout << "guided filter ok" << std::endl;
@@ -656,7 +693,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"occlu_mapl.png", m.occlusion},     {"disparity_mapl.png", m.dmap[0]},
                                   {"disparity_mapr.png", m.dmap[1]},   {"occlu_mapl_filled.png", m.filled},
                                   {"occlu_mapl_despeckled.png", m.despeckled}, {"occlu_mapl_unique.png", m.unique},
-                                  {"occlu_mapl_voted.png", m.voted},
+                                  {"occlu_mapl_voted.png", m.voted}, {"occlu_mapl_adjusted.png", m.adjusted},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
     for (const U8Out& o : u8_outputs)
@@ -740,6 +777,8 @@ int main(int argc, char** argv) {
         {uniq && multi, "--uniqueness" + with_multi},
         {opt.vote && multi, "--vote" + with_multi},
         {opt.vote && labels > 512, "--vote takes at most 512 labels"},
+        {opt.adjust && multi, "--adjust" + with_multi},
+        {opt.adjust && labels > 512, "--adjust takes at most 512 labels"},
         {opt.ngpu < 0 || opt.ngpu > smx_device_count(),
          "--ngpu " + std::to_string(opt.ngpu) + ": this node shows " + std::to_string(smx_device_count()) + " HIP device(s)"}};
     for (const Rule& r : refusals)
@@ -753,7 +792,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
-                       opt.cross || opt.so;
+                       opt.cross || opt.so || opt.adjust;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;

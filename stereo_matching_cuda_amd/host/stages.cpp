@@ -5,6 +5,7 @@
 #include "census.cuh"
 #include "costVolume.cuh"
 #include "crossAggregation.cuh"
+#include "discontinuityAdjustment.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
@@ -199,6 +200,21 @@ void region_vote(unsigned char* guide, int channels, float* disparity, float* di
         std::vector<float> twin((size_t)w * h);
         region_voteOnCPU(guide, channels, disparity, disparity_right, twin.data(), w, h, dmin, size_d, p, arms);
         if (check_errors(twin.data(), out, w * h)) cout << "Region voting ok!" << endl;
+    }
+}
+
+// not in the reference: depth-discontinuity adjustment of a label map from the aggregated costs (smx_main --adjust)
+void discontinuity_adjust(float* disparity, float* agg, float* out, const int w, const int h, const int dmin, const int size_d,
+                          const smx_adjust_params& p, int subpix_mode, float* sub, bool host_gpu_compare) {
+    std::vector<float> ts;
+    if (host_gpu_compare && sub) ts.assign(sub, sub + (size_t)w * h);      // (sub is IN/OUT: the twin starts from what the GPU starts from)
+    CHECK(smx_discontinuity_adjust(&p, disparity, agg, out, w, h, dmin, size_d, subpix_mode, sub));
+    if (host_gpu_compare) {
+        std::vector<float> twin((size_t)w * h);
+        discontinuityAdjustOnCPU(disparity, agg, twin.data(), w, h, dmin, size_d, p, subpix_mode, sub ? ts.data() : nullptr);
+        bool ok = check_errors(twin.data(), out, w * h);
+        if (sub) ok = check_errors(ts.data(), sub, w * h) && ok;
+        if (ok) cout << "Discontinuity adjustment ok!" << endl;
     }
 }
 

@@ -45,7 +45,7 @@ class ShardedPair:
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
     The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
     cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError, and so
-    does region voting (PairPipeline(vote=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
+    do region voting (PairPipeline(vote=...)) and the depth-discontinuity adjustment (PairPipeline(adjust=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
     one rank: aggregation="sgm" raises ValueError, and so do the scan-line optimiser's "scanline" / "cross-scanline"."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
@@ -60,6 +60,9 @@ class ShardedPair:
             raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
         if kw.get("vote") is not None or kw.get("vote_arms") is not None:
             raise ValueError("region voting is not part of the sharded driver: use PairPipeline(vote=...)")
+        if kw.get("adjust") is not None:
+            # (a D-shard holds no whole aggregated volume)
+            raise ValueError("the depth-discontinuity adjustment is not part of the sharded driver: use PairPipeline(adjust=...)")
         if kw.get("aggregation") in ("scanline", "cross-scanline") or kw.get("scanline_params") is not None:
             raise ValueError("the scan-line optimiser is not part of the sharded driver: use "
                              f"PairPipeline(aggregation={kw.get('aggregation')!r})")

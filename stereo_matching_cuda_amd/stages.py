@@ -231,6 +231,35 @@ def region_vote(disparity, guide, dmin, size_d, disparity_right=None, d_lr=None,
     return out
 
 
+def discontinuity_adjust(disparity, agg, dmin, params=None, subpixel=None, sub=None):
+    """Depth-discontinuity adjustment of a label map from its view's aggregated volume (include/smx.h
+    smx_discontinuity_adjust; not a stage of the reference).  disparity: (h, w) float32; agg: (size_d, h, w) float32, slice z
+    the label dmin + z; params: AdjustParams (None: the defaults).  subpixel: None, "parabola" or "equiangular" with sub, an
+    (h, w) float32 sub-pixel map: the pixels whose label changed get their own fit, every other one is kept.  Returns a new
+    (h, w) float32 array, or (map, sub) with sub given."""
+    d = _c(disparity, np.float32)
+    a = _c(agg, np.float32)
+    if d.ndim != 2:
+        raise ValueError("discontinuity_adjust expects an (h, w) float32 map")
+    if a.ndim != 3 or a.shape[1:] != d.shape:
+        raise ValueError("discontinuity_adjust expects a (size_d, h, w) float32 volume of the map's shape")
+    if params is not None and not isinstance(params, _lib.AdjustParams):
+        raise ValueError(f"params must be None or AdjustParams, not {params!r}")
+    if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
+        raise ValueError(f"subpixel must be None, 'parabola' or 'equiangular', not {subpixel!r}")
+    if (sub is None) != (subpixel is None):
+        raise ValueError("sub and subpixel go together")
+    s = None if sub is None else np.array(sub, dtype=np.float32, order="C")
+    if s is not None and s.shape != d.shape:
+        raise ValueError("sub must have the map's shape")
+    h, w = d.shape
+    out = np.empty((h, w), np.float32)
+    p = params if params is not None else _lib.default_adjust_params()
+    _lib.check(_lib.lib().smx_discontinuity_adjust(C.byref(p), _ptr(d), _ptr(a), _ptr(out), w, h, int(dmin), int(a.shape[0]),
+                                                   _lib.SUBPIX_MODES[subpixel] if subpixel else 0, _ptr(s)))
+    return out if s is None else (out, s)
+
+
 def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
     """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
     reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
