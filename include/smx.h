@@ -986,6 +986,100 @@ int smx_adjust_geometry(int* cols, int* rows);
  * again).  smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on.  Buffers are allocated on first use. */
 int smx_ctx_set_adjust(smx_ctx* ctx, const smx_adjust_params* p);
 
+/* ------------------------------------------------------------------------------------
+ * Cross-scale cost aggregation (Zhang et al., CVPR 2014; not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* A window filter fails on textureless surfaces wider than its window.  Cross-scale aggregation is the guided filter's own
+ * remedy: the pair is aggregated at every level of an image pyramid with the UNCHANGED aggregation, and a quadratic inter-scale
+ * regulariser ties the levels together.  Its closed form makes the regularised finest cost a fixed linear combination of the
+ * levels' aggregated costs at the pixel's and the label's ancestors.  tests/cscale_ref.py is this definition in numpy; the
+ * results equal it bit for bit.
+ *
+ * Parameters.  scales: 1 .. SMX_CSCALE_MAX_SCALES levels (1 = level 0 alone); lambda: the regulariser's weight, finite and >= 0.
+ * Defaults 4 and 1.0; the paper runs 5 scales and lambda = 0.3 with small windows.  Anything else is SMX_E_ARG before any device
+ * call.
+ *
+ * Pyramid.  pyr_down of a u8 image [h][w][channels] (channels 1, 3 or 4, interleaved, each channel by itself) is
+ * [(h+1)/2][(w+1)/2][channels]: taps 1 4 6 4 1 along x on integers without rounding, the same taps along y on those sums, taken
+ * at the even source coordinates, value (t + 128) >> 8.  Borders are reflect-101 (i < 0 -> -i, i >= N -> 2(N-1) - i), then
+ * clamped to [0, N-1], which matters for N of 1 or 2.  Level s is pyr_down applied s times.  A level's gray image is the pyramid
+ * of the level-0 gray image, not the gray of the level's colour image; the colour pyramid serves the colour guide and the
+ * colour AD term only.
+ *
+ * Labels.  A view with labels dmin .. dmin + size_d - 1 has at level s the labels dmin_s .. dmax_s with dmin_s = dmin >> s and
+ * dmax_s = (dmin + size_d - 1) >> s (arithmetic shifts: floor for negative labels), size_d_s = dmax_s - dmin_s + 1.
+ * smx_cscale_level gives a level's geometry (s >= 0; SMX_E_ARG for w, h, size_d < 1 or s < 0 or s > 30).
+ *
+ * Per-level volumes.  A_s [size_d_s][h_s][w_s] is the aggregated volume of the level-s pair with labels dmin_s .. of the view,
+ * from the same cost, aggregation and parameters at every level (the same radius, eps and thresholds, as in the paper).
+ *
+ * Weights.  M is the scales x scales tridiagonal matrix with -lambda beside the diagonal and 1 + lambda * (number of
+ * neighbouring levels) on it; wt[s] = (float)(M^-1)[0][s], computed on the host in double by the Thomas elimination
+ * (smx_cscale_weights writes `scales` floats).  lambda == 0 gives 1, 0, ...; they sum to 1.
+ *
+ * Combination.  For slice z and pixel (x, y) of level 0: t_s = wt[s] * A_s[((dmin + z) >> s) - dmin_s][y >> s][x >> s], each
+ * product rounded to f32; out = t_0, then out = out + t_s for s = 1 .. scales-1 in this order, each sum rounded to f32, no fused
+ * multiply-add.  A NaN or an infinity propagates as IEEE 754 says.  With scales == 1 (wt = 1) out equals A_0 bit for bit.
+ *
+ * Winners.  From out through the packed key's rule with the slices ascending: smallest cost, the last slice among equal costs,
+ * a NaN never.
+ *
+ * What it cannot do: a label of level s stands for 2^s labels of level 0, so the coarse levels say nothing about which of those
+ * is right.  Inside a textureless band the winners come to within 2^(scales-1) of the truth, not onto it; the sub-pixel fit and
+ * the weighted median are the stages for the rest.
+ *
+ * smx_dev_pyr_down: one launch on `stream`; writes the ((w+1)/2) * ((h+1)/2) * channels bytes of d_dst and nothing else; d_src
+ * and d_dst must not overlap.  w, h >= 1, w*h < 2^31.  smx_pyr_down: host pointers, synchronous.
+ *
+ * smx_dev_cscale_wta_pair: the combination and the winner-take-all pass over it in ONE launch on `stream`; no allocation, no
+ * synchronisation (graph-capturable).  d_agg_l / d_agg_r: HOST arrays of `scales` device pointers, entry s the whole volume A_s
+ * of that view (they are read during the call only); either may be NULL for a one-view call.  Outputs as in the other pair
+ * entries: with both views the left view's first, the right view's behind it; the one view of a one-view call at the front.
+ *   d_keys  OUT  int64 [views][h][w]: the packed keys of out (written fresh: what the buffer held is ignored)
+ *   d_out   OUT  f32 [views][size_d][h][w] or NULL: the combined volumes.  A view's part may BE that view's level-0 volume (in
+ *                place); no other overlap between any two buffers of the call is allowed
+ *   d_nbr   OUT  f32 [views][3][h][w] or NULL: the winners' neighbour state (lo, hi, last) as smx_dev_aggregate_wta_nbr leaves it
+ *   d_uq    OUT  f32 [views][3][h][w] or NULL: the second-best state (sec, rest, last) as smx_dev_aggregate_wta_pair_uq leaves it
+ * Nothing else is written.  w, h >= 1, w*h < 2^31, 1 <= size_d <= 2^20, |dminl|, |dminr| <= 2^29 (every level's labels stay ints);
+ * every volume 4-byte aligned (level 0 and d_out are
+ * read and written in 16- or 8-byte units where w and the pointers allow).
+ *
+ * smx_cscale_combine: host pointers, one view, synchronous.  agg: `scales` host pointers to the levels' volumes; out (the
+ * combined volume), best (the winners' costs) and disp_map (dmin + winning slice) may each be NULL. */
+#define SMX_CSCALE_MAX_SCALES 5
+typedef struct smx_cscale_params { int scales; double lambda; } smx_cscale_params;
+void smx_default_cscale_params(smx_cscale_params* p);
+int smx_cscale_weights(const smx_cscale_params* p, float* wt);
+int smx_cscale_level(int w, int h, int dmin, int size_d, int s, int* w_s, int* h_s, int* dmin_s, int* size_d_s);
+int smx_dev_pyr_down(const uint8_t* d_src, uint8_t* d_dst, int w, int h, int channels, void* stream);
+int smx_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int channels);
+int smx_dev_cscale_wta_pair(const smx_cscale_params* p, const float* const* d_agg_l, const float* const* d_agg_r, int w, int h,
+                            int dminl, int dminr, int size_d, int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq,
+                            void* stream);
+int smx_cscale_combine(const smx_cscale_params* p, const float* const* agg, int w, int h, int dmin, int size_d, float* out,
+                       float* best, float* disp_map);
+/* Test hook, NOT part of the stable contract: the footprint of a workgroup of the pyramid kernel in output pixels. */
+int smx_pyr_down_geometry(int* cols, int* rows);
+/* Cross-scale aggregation of this context.  NULL switches it off (the default: nothing is allocated or launched).  While it is
+ * on, smx_ctx_stereo_pair / _rgb builds the pyramids of both views, aggregates levels 1 .. scales-1 at their own geometry with
+ * this context's cost, guide and smx_params, keeps level 0's volumes as when agg_l is requested, and replaces the plain winners
+ * by smx_dev_cscale_wta_pair, which overwrites the level-0 volumes with the combined ones.  Everything behind runs unchanged on
+ * the combined keys and volumes: best_*, dmap_*, the sub-pixel neighbours, the uniqueness state, LR check, speckle removal, vote,
+ * fill, the depth-discontinuity adjustment (it reads the combined left volume) and the weighted median; out->agg_l / agg_r
+ * return the combined volumes.  All levels' volumes stay resident: at most 8/7 of the two level-0 volumes.
+ * Supported: the guided filter with the gray or the colour guide under the reference, census and AD-Census costs (AD-Census with
+ * colour 1 reads the colour pyramid).  The pair call returns SMX_E_ARG with a message for SGM, cross-based aggregation and the
+ * scan-line optimiser (their integer volumes and fixed penalties do not rescale across levels), for out->mean_l / mean_r
+ * (ambiguous across levels), for a pyramid whose coarsest level is narrower than 2 pixels, and smx_ctx_stereo_pair_async
+ * returns it while the setting is on.  The sharded and multi-GPU drivers do not take it.  The levels' contexts and volumes are
+ * allocated by the first pair that runs with it on and are released by smx_destroy only: switching it off, or lowering `scales`,
+ * keeps them for the next time. */
+int smx_ctx_set_cross_scale(smx_ctx* ctx, const smx_cscale_params* p);
+/* Test hook, NOT part of the stable contract: the levels above 0 that the context holds for cross-scale and the device bytes of
+ * their buffers.  0 and 0 for a context whose pairs never ran with cross-scale on. */
+int smx_ctx_cscale_held(const smx_ctx* ctx, int* levels, size_t* bytes);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -82,6 +82,11 @@ class AdjustParams(C.Structure):
     _fields_ = [("tau_e", C.c_int), ("vertical", C.c_int), ("iterations", C.c_int)]
 
 
+class CScaleParams(C.Structure):
+    """smx_cscale_params: cross-scale cost aggregation (not a stage of the reference)."""
+    _fields_ = [("scales", C.c_int), ("lambda_", C.c_double)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -113,6 +118,8 @@ _XP = C.POINTER(CrossParams)
 _VP = C.POINTER(VoteParams)
 _LP = C.POINTER(ScanlineParams)
 _JP = C.POINTER(AdjustParams)
+_KP = C.POINTER(CScaleParams)
+_ip = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -233,6 +240,16 @@ SIGNATURES = {
     "smx_discontinuity_adjust": (_i, [_JP, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "smx_adjust_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "smx_ctx_set_adjust": (_i, [_vp, _JP]),
+    "smx_default_cscale_params": (None, [_KP]),
+    "smx_cscale_weights": (_i, [_KP, _vp]),
+    "smx_cscale_level": (_i, [_i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
+    "smx_dev_pyr_down": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "smx_pyr_down": (_i, [_vp, _vp, _i, _i, _i]),
+    "smx_dev_cscale_wta_pair": (_i, [_KP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "smx_cscale_combine": (_i, [_KP, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "smx_pyr_down_geometry": (_i, [_ip, _ip]),
+    "smx_ctx_set_cross_scale": (_i, [_vp, _KP]),
+    "smx_ctx_cscale_held": (_i, [_vp, _ip, C.POINTER(_sz)]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -353,6 +370,26 @@ def default_adjust_params():
     p = AdjustParams()
     lib().smx_default_adjust_params(C.byref(p))
     return p
+
+
+def default_cscale_params():
+    p = CScaleParams()
+    lib().smx_default_cscale_params(C.byref(p))
+    return p
+
+
+def cscale_level(w, h, dmin, size_d, s):
+    """(w_s, h_s, dmin_s, size_d_s): the geometry of level s of a cross-scale pyramid (smx_cscale_level)."""
+    out = [C.c_int() for _ in range(4)]
+    check(lib().smx_cscale_level(int(w), int(h), int(dmin), int(size_d), int(s), *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
+
+
+def cscale_weights(params):
+    """The levels' weights (smx_cscale_weights) as a list of `scales` floats."""
+    wt = (C.c_float * 5)()
+    check(lib().smx_cscale_weights(C.byref(params), wt))
+    return list(wt)[:params.scales]
 
 
 def subpixel_delta(mode, c0, lo, hi):

@@ -2,6 +2,7 @@
 // and smx_ctx.hip (the persistent context) share.  The thread's state itself stays inside smx_capi.hip.
 #pragma once
 #include "smx_agg.h"
+#include "smx_cscale_host.h"
 
 namespace smx {
 
@@ -58,6 +59,9 @@ bool adjust_params_ok(const smx_adjust_params* p);     // (smx_adjust.hip, besid
 bool adjust_shape_ok(int w, int h, int size_d);
 constexpr const char* ADJUST_RANGES = "needs 1 <= tau_e <= 512, vertical 0 or 1 and 1 <= iterations <= 8";
 constexpr const char* ADJUST_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
+bool cscale_shape_ok(int w, int h, int size_d);
+constexpr const char* CSCALE_RANGES = "needs 1 <= scales <= 5 and a finite lambda >= 0";
+constexpr const char* CSCALE_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 2^20";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

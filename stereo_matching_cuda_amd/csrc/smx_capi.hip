@@ -12,6 +12,7 @@
 #include "smx_agg_v4.h"
 #include "smx_agg_v5.h"
 #include "smx_launch.h"
+#include "smx_wta.h"
 
 namespace smx {
 
@@ -826,6 +827,68 @@ int smx_dev_discontinuity_adjust(const smx_adjust_params* p, const float* d_disp
         return fail(SMX_E_WS, "smx_dev_discontinuity_adjust: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
                     adjust_workspace_bytes(w, h));
     return launch_discontinuity_adjust(p, d_disp, d_agg, d_out, w, h, dmin, size_d, subpix_mode, d_sub, d_ws, (hipStream_t)stream);
+}
+
+// ---- cross-scale cost aggregation (not in the reference; smx_cscale.hip) -----------------------------------------------
+void smx_default_cscale_params(smx_cscale_params* p) {
+    if (!p) return;
+    p->scales = 4; p->lambda = 1.0;
+}
+
+int smx_cscale_weights(const smx_cscale_params* p, float* wt) {
+    if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_cscale_weights: %s", CSCALE_RANGES);
+    SMX_ARG(wt != nullptr);
+    cscale_weights(p, wt);
+    return SMX_OK;
+}
+
+int smx_cscale_level(int w, int h, int dmin, int size_d, int s, int* w_s, int* h_s, int* dmin_s, int* size_d_s) {
+    SMX_ARG(w >= 1 && h >= 1 && size_d >= 1 && s >= 0 && s <= 30 && w_s && h_s && dmin_s && size_d_s);
+    cscale_level(w, h, dmin, size_d, s, w_s, h_s, dmin_s, size_d_s);
+    return SMX_OK;
+}
+
+int smx_pyr_down_geometry(int* cols, int* rows) {
+    SMX_ARG(cols && rows);
+    pyr_down_tile(cols, rows);
+    return SMX_OK;
+}
+
+int smx_dev_pyr_down(const uint8_t* d_src, uint8_t* d_dst, int w, int h, int channels, void* stream) {
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!cscale_shape_ok(w, h, 1)) return fail(SMX_E_ARG, "smx_dev_pyr_down: needs w, h >= 1 and w*h < 2^31");
+    SMX_ARG(d_src && d_dst);
+    return launch_pyr_down(d_src, d_dst, w, h, channels, (hipStream_t)stream);
+}
+
+int smx_dev_cscale_wta_pair(const smx_cscale_params* p, const float* const* d_agg_l, const float* const* d_agg_r, int w, int h,
+                            int dminl, int dminr, int size_d, int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq,
+                            void* stream) {
+    if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: %s", CSCALE_RANGES);
+    if (!cscale_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: %s", CSCALE_SHAPES);
+    SMX_ARG((d_agg_l || d_agg_r) && d_keys);
+    const float* const* views[2] = {d_agg_l, d_agg_r};
+    const int dmins[2] = {dminl, dminr};
+    for (int v = 0; v < 2; ++v) {
+        if (!views[v]) continue;
+        // (the label range of every level must exist as ints)
+        if (dmins[v] < -(1 << 29) || dmins[v] > (1 << 29))
+            return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: the labels of view %d start at %d, outside +-2^29", v, dmins[v]);
+        for (int s = 0; s < p->scales; ++s)
+            if (!views[v][s] || ((uintptr_t)views[v][s] & 3) != 0)
+                return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: the level-%d volume of view %d is NULL or not 4-byte aligned", s, v);
+    }
+    return launch_cscale_wta_pair(p, d_agg_l, d_agg_r, w, h, dminl, dminr, size_d, d_keys, d_out, d_nbr, d_uq, (hipStream_t)stream);
+}
+
+// Test hook (not in include/smx.h): the natural-order winner-take-all pass of the aggregations (wta_launch, smx_wta.h) over one
+// materialised volume d_q [count][h][w], fresh keys out -- what tests/test_gpu_cscale.py holds the one-scale combination to.
+__attribute__((visibility("default"))) int smx_debug_wta_natural(const float* d_q, int w, int h, int count, int64_t* d_keys,
+                                                                 void* stream) {
+    SMX_ARG(d_q && d_keys && count >= 1);
+    if (!cscale_shape_ok(w, h, count)) return fail(SMX_E_ARG, "smx_debug_wta_natural: %s", CSCALE_SHAPES);
+    return wta_launch(WTA_NATURAL, 1, &d_q, &d_keys, nullptr, nullptr, w, h, (size_t)w * h, count, 0, nullptr, 0, true,
+                      (hipStream_t)stream);
 }
 
 int smx_dev_filter(const smx_params* p, const uint8_t* d_image, int w, int h, uint8_t* d_mean,

@@ -66,6 +66,13 @@ struct smx_ctx {
     bool adjust = false;
     smx_adjust_params adj_params;
     DevBuf adj_ws;
+    // cross-scale aggregation (smx_ctx_set_cross_scale): a child context per level 1 .. scales-1, created on first use at the
+    // level's geometry, on this context's stream (owns_st false: the stream is the parent's).  A child holds its level's
+    // images (dL, dR, rgb) and aggregated volumes (aggLR), and is made anew where a pair's label ranges ask for another size_d
+    bool cscale = false;
+    smx_cscale_params cs_params;
+    smx_ctx* cs_child[SMX_CSCALE_MAX_SCALES] = {};
+    bool owns_st = true;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -85,6 +92,8 @@ struct smx_ctx {
     hipStream_t st_up = nullptr, st_dn = nullptr;
     uint64_t submitted = 0, waited = 0;
     ~smx_ctx() {
+        for (smx_ctx* k : cs_child) delete k;
+        if (!owns_st) st = nullptr;
         for (Slot& sl : slot) {
             if (sl.h_in) (void)hipHostFree(sl.h_in);
             if (sl.h_out) (void)hipHostFree(sl.h_out);
@@ -100,7 +109,9 @@ struct smx_ctx {
 // (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust; };
+// cscale: the winners come from the cross-scale combination; level: this pair is a level of another context's pyramid, which
+// wants its aggregated volumes and nothing behind them.
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -238,11 +249,15 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         if ((rc = smx_dev_cost_volume(p, in.right, in.left, costR, w, w, h, in.dminr, 0, size_d, st))) return rc;
     }
     if ((rc = smx_dev_init_keys(keysL, 2 * (int64_t)n, st))) return rc;
+    // (with cross-scale the states come from the combination pass: the level-0 aggregation keeps none.  Its keys are
+    // overwritten too, but the fused aggregation has no form without its winner-take-all pass.)
+    float* const nbrA = need.cscale ? nullptr : nbrL;
+    float* const uqA = need.cscale ? nullptr : uqL;
     // main.cu:133-134, both views per call, on the context's own path
     const AggCall call = {"smx_ctx_stereo_pair", p, 2, {in.left, in.right}, {in.right, in.left}, {costL, costR},
                           {in.dminl, in.dminr}, {keysL, keysL + n}, {out.mean, out.mean + n},
-                          {aggL, need.agg ? aggL + (size_t)size_d * n : nullptr}, {nbrL, need.subpix ? nbrL + 3 * n : nullptr},
-                          {uqL, need.uniq ? uqL + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
+                          {aggL, need.agg ? aggL + (size_t)size_d * n : nullptr}, {nbrA, nbrA ? nbrA + 3 * n : nullptr},
+                          {uqA, uqA ? uqA + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
     if (need.census && (rc = ctx_census_codes(c, call))) return rc;
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
@@ -273,6 +288,20 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     } else if (need.cgf || need.cross || need.census) rc = ctx_aggregate_chunks(c, in, call, need);
     else rc = run_aggregation(call, c->agg_path, false);
     if (rc) return rc;
+    if (need.level) return SMX_OK;
+    if (need.cscale) {
+        // the levels' volumes are on the stream already (ctx_cscale_levels): the combination goes over the level-0 volumes,
+        // and its winners and states take the place of the plain ones
+        const float* al[SMX_CSCALE_MAX_SCALES] = {aggL};
+        const float* ar[SMX_CSCALE_MAX_SCALES] = {aggL + (size_t)size_d * n};
+        for (int s = 1; s < c->cs_params.scales; ++s) {
+            smx_ctx* k = c->cs_child[s];
+            al[s] = k->aggLR.as<float>();
+            ar[s] = al[s] + (size_t)k->size_d * k->n;
+        }
+        if ((rc = smx_dev_cscale_wta_pair(&c->cs_params, al, ar, w, h, in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, st)))
+            return rc;
+    }
     // main.cu:112-118 presets, winning slices, main.cu:140-155
     if ((rc = smx_dev_finish_pair(p, keysL, w, h, in.dminl, in.dminr, in.dminl - 100, (float)in.dminl, out.best, out.map,
                                   out.occ, out.fil, st)))
@@ -320,6 +349,60 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
                                         need.subpix ? c->subf.as<float>() : nullptr, c->adj_ws.p, adjust_workspace_bytes(w, h), st);
 }
 
+static int ctx_create(const smx_params* p, int w, int h, int size_d, hipStream_t shared, smx_ctx** out);
+static int ctx_adcensus_table(smx_ctx* c);
+
+// Levels 1 .. scales-1 of a cross-scale pair: each level's images from the level below (the gray pyramid from the gray images,
+// the colour pyramid from the colour images), then the level's pair through ctx_enqueue on a child context that takes this
+// context's settings.  Both views of a level run with the larger of the two views' slice counts; the slices past a view's own
+// range are not read by the combination.
+static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, const PairNeeds& need) {
+    int rc;
+    const smx_ctx* below = c;
+    PairIn src = in;
+    for (int s = 1; s < c->cs_params.scales; ++s) {
+        int ws, hs, dl, dr, sl, sr;
+        cscale_level(c->w, c->h, in.dminl, c->size_d, s, &ws, &hs, &dl, &sl);
+        cscale_level(c->w, c->h, in.dminr, c->size_d, s, &ws, &hs, &dr, &sr);
+        const int sd = sl > sr ? sl : sr;
+        if (ws < 2) return fail(SMX_E_ARG, "%s: cross-scale level %d of a %d x %d pair is narrower than 2 pixels", who, s, c->w, c->h);
+        smx_ctx*& k = c->cs_child[s];
+        if (k && k->size_d != sd) { delete k; k = nullptr; }
+        if (!k && (rc = ctx_create(&c->p, ws, hs, sd, c->st, &k))) return rc;
+        k->p = c->p;
+        k->agg_path = c->agg_path;
+        k->cost_mode = c->cost_mode;
+        k->census = c->census;
+        k->guide_mode = c->guide_mode;
+        if (c->adcensus && (!k->adcensus || memcmp(&k->adc, &c->adc, sizeof(k->adc)) != 0)) { k->adc = c->adc; k->adc_tab_valid = false; }
+        k->adcensus = c->adcensus;
+        PairNeeds kn = {};
+        kn.agg = kn.level = true;
+        kn.census = need.census;
+        kn.cgf = need.cgf;
+        if (kn.cgf && smx_cgf_workspace_bytes(ws, hs, 1, 2) == 0)
+            return fail(SMX_E_ARG, "%s: the colour-guided filter does not take cross-scale level %d", who, s);
+        if ((rc = ctx_reserve(k, kn))) return rc;
+        if ((rc = ctx_adcensus_table(k))) return rc;
+        uint8_t* gl = k->dL.as<uint8_t>(); uint8_t* gr = k->dR.as<uint8_t>();
+        if ((rc = smx_dev_pyr_down(src.left, gl, below->w, below->h, 1, c->st))) return rc;
+        if ((rc = smx_dev_pyr_down(src.right, gr, below->w, below->h, 1, c->st))) return rc;
+        uint8_t *cl = nullptr, *cr = nullptr;
+        if (in.channels) {
+            SMX_HIP(k->rgb.ensure(2 * k->n * (size_t)in.channels));
+            cl = k->rgb.as<uint8_t>(); cr = cl + k->n * (size_t)in.channels;
+            if ((rc = smx_dev_pyr_down(src.rgb_l, cl, below->w, below->h, in.channels, c->st))) return rc;
+            if ((rc = smx_dev_pyr_down(src.rgb_r, cr, below->w, below->h, in.channels, c->st))) return rc;
+        }
+        src = {gl, gr, dl, dr, cl, cr, in.channels};
+        if ((rc = ctx_enqueue(k, src, kn, {k->best.as<float>(), k->map.as<float>(), k->mean.as<uint8_t>(), k->occ.as<float>(),
+                                           k->fil.as<float>()})))
+            return rc;
+        below = k;
+    }
+    return SMX_OK;
+}
+
 static int ctx_check_device(smx_ctx* c, const char* who) {
     int dev = -1;
     SMX_HIP(hipGetDevice(&dev));
@@ -336,10 +419,8 @@ static std::array<PlaneRef, 12> pair_planes(const smx_pair_out& o, size_t size_d
              {o.filled, f}, {o.cost_l, v}, {o.cost_r, v}, {o.agg_l, v}, {o.agg_r, v}}};
 }
 
-extern "C" {
-
-int smx_create(const smx_params* p, int w, int h, int size_d, smx_ctx** out) {
-    SMX_ARG(p && out && w >= 2 && h >= 1 && size_d >= 1 && p->radius >= 0);
+// shared: NULL, or the stream of the context this one is a pyramid level of
+static int ctx_create(const smx_params* p, int w, int h, int size_d, hipStream_t shared, smx_ctx** out) {
     *out = nullptr;
     smx_ctx* c = new (std::nothrow) smx_ctx;
     if (!c) return fail(SMX_E_HIP, "smx_create: out of host memory");
@@ -349,7 +430,8 @@ int smx_create(const smx_params* p, int w, int h, int size_d, smx_ctx** out) {
     c->n = (size_t)w * h;
     const size_t n = c->n, fb = n * sizeof(float);
     SMX_HIP(hipGetDevice(&c->dev));
-    SMX_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+    if (shared) { c->st = shared; c->owns_st = false; }
+    else SMX_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
     c->ws_bytes = 2 * pick_ws_bytes(w, h, size_d);     // both views per launch
     SMX_HIP(c->dL.ensure(n)); SMX_HIP(c->dR.ensure(n));
     SMX_HIP(c->keys.ensure(2 * n * 8));
@@ -360,6 +442,22 @@ int smx_create(const smx_params* p, int w, int h, int size_d, smx_ctx** out) {
     guard.c = nullptr;
     *out = c;
     return SMX_OK;
+}
+
+// The device table of the AD-Census cost, built where the context's parameters changed
+static int ctx_adcensus_table(smx_ctx* c) {
+    if (!c->adcensus || c->adc_tab_valid) return SMX_OK;
+    SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
+    if (int rc = smx_dev_adcensus_tables(&c->adc, c->adc_tab.as<float>(), c->st)) return rc;
+    c->adc_tab_valid = true;
+    return SMX_OK;
+}
+
+extern "C" {
+
+int smx_create(const smx_params* p, int w, int h, int size_d, smx_ctx** out) {
+    SMX_ARG(p && out && w >= 2 && h >= 1 && size_d >= 1 && p->radius >= 0);
+    return ctx_create(p, w, h, size_d, nullptr, out);
 }
 
 int smx_ctx_set_agg_path(smx_ctx* c, int path) {
@@ -421,17 +519,21 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
                                "smx_ctx_stereo_pair_rgb", who);
     if (c->adjust && !adjust_shape_ok(c->w, c->h, c->size_d))
         return fail(SMX_E_ARG, "%s: the depth-discontinuity adjustment (smx_ctx_set_adjust) %s", who, ADJUST_SHAPES);
+    const bool cscale = c->cscale;
+    if (cscale && (sgm || cross || so))
+        return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) belongs to the guided filter: the integer "
+                               "volumes and fixed penalties of %s do not rescale across levels", who,
+                    sgm ? "semi-global matching" : so ? "the scan-line optimiser" : "cross-based aggregation");
+    if (cscale && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) produces no mean images", who);
+    if (cscale && !cscale_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: cross-scale aggregation %s", who, CSCALE_SHAPES);
     // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
     // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust, c->subpix != 0,
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale, c->subpix != 0,
                             c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
-                            c->adjust};
+                            c->adjust, cscale, false};
     if ((rc = ctx_reserve(c, need))) return rc;
-    if (c->adcensus && !c->adc_tab_valid) {
-        SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
-        if ((rc = smx_dev_adcensus_tables(&c->adc, c->adc_tab.as<float>(), st))) return rc;
-        c->adc_tab_valid = true;
-    }
+    if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
     c->sub_valid = c->spk_valid = c->uq_valid = c->vote_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
@@ -450,6 +552,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     stage_mark(ST_UPLOAD, st);
     float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
     uint8_t* mean = c->mean.as<uint8_t>();
+    if (cscale && (rc = ctx_cscale_levels(c, who, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need))) return rc;
     if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need,
                           {best, map, mean, c->occ.as<float>(), c->fil.as<float>()})))
         return rc;
@@ -461,7 +564,11 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
     // (the SGM, colour-guided and cross-based kernels wait for nothing)
-    if (!need.sgm && !need.cgf && !need.cross && !need.so && (rc = smx_dev_agg_status(c->ws.p))) return rc;
+    if (!need.sgm && !need.cgf && !need.cross && !need.so) {
+        if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
+        for (int s = 1; cscale && s < c->cs_params.scales; ++s)
+            if ((rc = smx_dev_agg_status(c->cs_child[s]->ws.p))) return rc;
+    }
     c->sub_valid = need.subpix;
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
@@ -617,6 +724,31 @@ int smx_ctx_set_adjust(smx_ctx* c, const smx_adjust_params* p) {
     return SMX_OK;
 }
 
+int smx_ctx_set_cross_scale(smx_ctx* c, const smx_cscale_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_cross_scale: %s", CSCALE_RANGES);
+        c->cs_params = *p;
+    }
+    c->cscale = p != nullptr;
+    return SMX_OK;
+}
+
+// Test hook (include/smx.h): what cross-scale holds on the device
+int smx_ctx_cscale_held(const smx_ctx* c, int* levels, size_t* bytes) {
+    SMX_ARG(c && levels && bytes);
+    *levels = 0;
+    *bytes = 0;
+    for (const smx_ctx* k : c->cs_child) {
+        if (!k) continue;
+        ++*levels;
+        for (const DevBuf* b : {&k->dL, &k->dR, &k->keys, &k->best, &k->map, &k->mean, &k->occ, &k->fil, &k->ws, &k->aggLR, &k->codes,
+                                &k->adc_tab, &k->rgb, &k->mode_ws, &k->chunk_cost})
+            *bytes += b->p ? b->bytes : 0;
+    }
+    return SMX_OK;
+}
+
 int smx_ctx_vote_map(smx_ctx* c, float* voted) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
@@ -679,6 +811,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     if (c->vote) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: region voting is on (smx_ctx_set_vote): use smx_ctx_stereo_pair");
     if (c->adjust)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the depth-discontinuity adjustment is on (smx_ctx_set_adjust): use smx_ctx_stereo_pair");
+    if (c->cscale)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-scale aggregation is on (smx_ctx_set_cross_scale): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)

@@ -379,6 +379,55 @@ int smx_discontinuity_adjust(const smx_adjust_params* p, const float* disp, cons
     return SMX_OK;
 }
 
+int smx_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int channels) {
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!cscale_shape_ok(w, h, 1)) return fail(SMX_E_ARG, "smx_pyr_down: needs w, h >= 1 and w*h < 2^31");
+    SMX_ARG(src && dst);
+    const size_t in = (size_t)w * h * channels, out = (size_t)((w + 1) / 2) * ((h + 1) / 2) * channels;
+    DevBuf dS, dD;
+    SMX_HIP(dS.upload(src, in));
+    SMX_HIP(dD.ensure(out));
+    if (int rc = smx_dev_pyr_down(dS.as<uint8_t>(), dD.as<uint8_t>(), w, h, channels, nullptr)) return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dD.download(dst, out));
+    return SMX_OK;
+}
+
+int smx_cscale_combine(const smx_cscale_params* p, const float* const* agg, int w, int h, int dmin, int size_d, float* out,
+                       float* best, float* disp_map) {
+    if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_cscale_combine: %s", CSCALE_RANGES);
+    if (!cscale_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_cscale_combine: %s", CSCALE_SHAPES);
+    SMX_ARG(agg != nullptr);
+    for (int s = 0; s < p->scales; ++s) SMX_ARG(agg[s] != nullptr);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float);
+    DevBuf dA[SMX_CSCALE_MAX_SCALES], dK;
+    const float* levels[SMX_CSCALE_MAX_SCALES] = {};
+    for (int s = 0; s < p->scales; ++s) {
+        int ws, hs, d0, ds;
+        cscale_level(w, h, dmin, size_d, s, &ws, &hs, &d0, &ds);
+        SMX_HIP(dA[s].upload(agg[s], (size_t)ws * hs * ds * sizeof(float)));
+        levels[s] = dA[s].as<float>();
+    }
+    SMX_HIP(dK.ensure(n * sizeof(int64_t)));
+    // (the combined volume goes over the uploaded level 0)
+    if (int rc = smx_dev_cscale_wta_pair(p, levels, nullptr, w, h, dmin, 0, size_d, dK.as<int64_t>(), out ? dA[0].as<float>() : nullptr,
+                                         nullptr, nullptr, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (out) SMX_HIP(dA[0].download(out, vb));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(dK.download(keys.data(), n * sizeof(int64_t)));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -91,4 +91,11 @@ size_t adjust_workspace_bytes(int w, int h);
 int launch_discontinuity_adjust(const smx_adjust_params* p, const float* disp, const float* vol, float* out, int w, int h, int dmin,
                                 int size_d, int mode, float* sub, void* ws, hipStream_t st);
 void adjust_tile(int* tw, int* th);
+// smx_cscale.hip: cross-scale aggregation -- one level of the u8 pyramid, and the combination with its winner-take-all pass
+// (smx_dev_cscale_wta_pair; agg_l / agg_r: host arrays of p->scales device pointers, either may be NULL).  The host arithmetic
+// (a level's geometry, the weights) is smx_cscale_host.h
+int launch_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int ch, hipStream_t st);
+void pyr_down_tile(int* tw, int* th);
+int launch_cscale_wta_pair(const smx_cscale_params* p, const float* const* agg_l, const float* const* agg_r, int w, int h, int dminl,
+                           int dminr, int size_d, int64_t* keys, float* out, float* nbr, float* uq, hipStream_t st);
 }  // namespace smx

@@ -27,7 +27,7 @@ class PairPipeline:
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
                  aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
-                 vote=None, vote_arms=None, scanline_params=None, adjust=None):
+                 vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -100,7 +100,30 @@ class PairPipeline:
         self.adjusted; self.filled is rewritten with it, and with subpixel on self.sub_filled carries the changed pixels' own
         fits.  The validity map is not replaced.  max_ws_bytes counts the volumes and the stage's workspace; a slice sub-range
         (a D-shard has no whole volume), more than 512 labels or a size that does not fit raises ValueError.  With None nothing
-        is allocated or launched."""
+        is allocated or launched.
+        cross_scale: None, True (the defaults: 4 scales, lambda 1.0) or CScaleParams -- cross-scale cost aggregation (Zhang et
+        al. 2014; not a stage of the reference; include/smx.h smx_dev_cscale_wta_pair): the guided filter's remedy for
+        textureless surfaces wider than its window.  aggregate() keeps the level-0 volumes in self.agg as with want_agg, builds
+        the u8 pyramids of both views (smx_dev_pyr_down; the gray pyramid from the gray images, the colour pyramid from the
+        colour images), runs levels 1 .. scales-1 through pipelines of their own (self.cs_levels: the same cost, guide and
+        params at the level's geometry, both views with the larger of the two views' label counts) and replaces the plain
+        winners by the combination pass, which overwrites self.agg with the combined volumes and self.keys, self.nbr and
+        self.uq with the winners and states of those.  Everything in finish() runs unchanged behind it.  With the guided filter
+        only (gray or rgb guide; the reference, census and AD-Census costs): aggregation= raises ValueError, and so do a slice
+        sub-range, caller's cost volumes and a pyramid whose coarsest level is narrower than 2 pixels.  self.mean is level
+        0's.  max_ws_bytes bounds each level's pipeline by itself.  With None nothing is allocated or launched."""
+        if cross_scale is not None and cross_scale is not True and not isinstance(cross_scale, _lib.CScaleParams):
+            raise ValueError(f"cross_scale must be None, True or CScaleParams, not {cross_scale!r}")
+        if isinstance(cross_scale, _lib.CScaleParams) and not (1 <= cross_scale.scales <= 5 and
+                                                               0.0 <= cross_scale.lambda_ < float("inf")):
+            raise ValueError("cross_scale needs 1 <= scales <= 5 and a finite lambda >= 0")
+        if cross_scale is not None:
+            if aggregation is not None:
+                raise ValueError(f"cross-scale aggregation belongs to the guided filter: not with aggregation={aggregation!r} "
+                                 "(integer volumes and fixed penalties do not rescale across levels)")
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("cross-scale aggregation combines whole volumes: no slice sub-range")
+            want_agg = True
         if adjust is not None and adjust is not True and not isinstance(adjust, _lib.AdjustParams):
             raise ValueError(f"adjust must be None, True or AdjustParams, not {adjust!r}")
         if isinstance(adjust, _lib.AdjustParams) and not (1 <= adjust.tau_e <= 512 and adjust.vertical in (0, 1) and
@@ -296,6 +319,21 @@ class PairPipeline:
             self.cross_ws_bytes = int(self.lib.smx_cross_workspace_bytes(self.w, self.h, sif, 2))
             self.cross_ws = torch.empty(self.cross_ws_bytes, dtype=torch.uint8, device=dev)
             self.cross_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
+        self.cross_scale = _lib.default_cscale_params() if cross_scale is True else cross_scale
+        self.cs_levels, self.cs_gray, self.cs_rgb = [], [], []
+        if self.cross_scale:
+            colour = bool(guidance) or (cost == "adcensus" and bool(self.adcensus_params.colour))
+            for s in range(1, self.cross_scale.scales):
+                ws, hs, dl, sl = _lib.cscale_level(self.w, self.h, self.dminl, self.size_d, s)
+                _, _, dr, sr = _lib.cscale_level(self.w, self.h, self.dminr, self.size_d, s)
+                if ws < 2:
+                    raise ValueError(f"cross-scale level {s} of a {self.w} x {self.h} pair is narrower than 2 pixels")
+                self.cs_levels.append(PairPipeline(ws, hs, max(sl, sr), dminl=dl, dminr=dr, device=device, want_agg=True,
+                                                   params=self.params, max_ws_bytes=max_ws_bytes, multi_kernel=multi_kernel,
+                                                   cost=cost, census_params=census_params, guidance=guidance,
+                                                   adcensus_params=adcensus_params))
+                self.cs_gray.append(torch.empty((2, hs, ws), dtype=torch.uint8, device=dev))
+                self.cs_rgb.append(torch.empty(2 * hs * ws * 4, dtype=torch.uint8, device=dev) if colour else None)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
         self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
             if (cost or guidance or cross) and want_agg and sif < local and not sgm and not so else None
@@ -308,6 +346,43 @@ class PairPipeline:
 
     # -- stages ------------------------------------------------------------------------------
     def aggregate(self, gray_l, gray_r, cost_l=None, cost_r=None, rgb_l=None, rgb_r=None):
+        """The aggregation of this pipeline (_aggregate_level), and with cross_scale on the pyramid's other levels and the
+        combination behind it (_cross_scale)."""
+        if self.cross_scale and (cost_l is not None or cost_r is not None):
+            raise ValueError("cross-scale aggregation builds every level's cost from the pyramid: pass the images only")
+        self._aggregate_level(gray_l, gray_r, cost_l, cost_r, rgb_l, rgb_r)
+        if self.cross_scale:
+            self._cross_scale(gray_l, gray_r)
+
+    def _cross_scale(self, gray_l, gray_r):
+        """Levels 1 .. of both views' pyramids through self.cs_levels, then smx_dev_cscale_wta_pair over every level's volumes:
+        self.agg becomes the combined volumes, self.keys (self.nbr, self.uq) their winners (and states)."""
+        L = self.lib
+        below, bw, bh = ((gray_l, gray_r), self._rgb), self.w, self.h
+        for k, gray, buf in zip(self.cs_levels, self.cs_gray, self.cs_rgb):
+            rgb = None
+            with self._on_device():
+                st = self._stream()
+                for v in range(2):
+                    _lib.check(L.smx_dev_pyr_down(_dp(below[0][v]), _dp(gray[v]), bw, bh, 1, st))
+                if below[1] is not None:
+                    ch = int(below[1][0].shape[2])
+                    rgb = buf[:2 * k.n * ch].view(2, k.h, k.w, ch)
+                    for v in range(2):
+                        _lib.check(L.smx_dev_pyr_down(_dp(below[1][v]), _dp(rgb[v]), bw, bh, ch, st))
+            if rgb is None:
+                k.aggregate(gray[0], gray[1])
+            else:
+                k.aggregate(gray[0], gray[1], rgb_l=rgb[0], rgb_r=rgb[1])
+            below, bw, bh = ((gray[0], gray[1]), None if rgb is None else (rgb[0], rgb[1])), k.w, k.h
+        S = self.cross_scale.scales
+        views = [(C.c_void_p * S)(*([self.agg[v].data_ptr()] + [k.agg[v].data_ptr() for k in self.cs_levels])) for v in range(2)]
+        with self._on_device():
+            _lib.check(L.smx_dev_cscale_wta_pair(C.byref(self.cross_scale), views[0], views[1], self.w, self.h, self.dminl,
+                                                 self.dminr, self.size_d, _dp(self.keys), _dp(self.agg), _dp(self.nbr),
+                                                 _dp(self.uq), self._stream()))
+
+    def _aggregate_level(self, gray_l, gray_r, cost_l=None, cost_r=None, rgb_l=None, rgb_r=None):
         """Cost build (fused unless cost_* given) + guided-filter aggregation + running WTA of this
         rank's slices, both views.  Leaves packed keys in self.keys.  rgb_l / rgb_r: the colour guides of
         guidance="rgb" and the images of the AD term of cost="adcensus" with colour 1 (required then, refused otherwise)."""
@@ -737,6 +812,8 @@ class PairPipeline:
     def check_status(self):
         """Raise if a workgroup of the fused aggregation gave up waiting for a neighbour."""
         torch.cuda.synchronize(self.device)
+        for k in self.cs_levels:
+            k.check_status()
         if self.aggregation or self.guidance:            # (the SGM, colour-guided and cross-based kernels wait for nothing)
             return
         with self._on_device():

@@ -14,6 +14,8 @@
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
 #include "crossAggregation.cuh"
+#include "crossScale.cuh"
+#include "../csrc/smx_cscale_host.h"      // the library's own host arithmetic of the levels: no HIP in it
 #include "discontinuityAdjustment.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
@@ -492,6 +494,63 @@ void discontinuityAdjustOnCPU(const float* disparity, const float* agg, float* o
         cur.swap(next);
     }
     for (size_t id = 0; id < n; ++id) out[id] = cur[id];
+}
+
+// ---- crossScale.cuh (not in the reference) ---------------------------------------------------------
+// The definition of include/smx.h (above smx_cscale_params), scalar: the pyramid on integers, the combination as one f32 product
+// per level and f32 sums in the order of the levels, the winner by `best >= q` over ascending slices.
+void pyrDownOnCPU(const unsigned char* src, unsigned char* dst, const int w, const int h, const int channels) {
+    static const int tap[5] = {1, 4, 6, 4, 1};
+    auto at = [](int i, int n) {            // reflect-101, then clamped (n of 1 or 2)
+        i = i < 0 ? -i : i;
+        i = i >= n ? 2 * (n - 1) - i : i;
+        return i < 0 ? 0 : i > n - 1 ? n - 1 : i;
+    };
+    const int wo = (w + 1) / 2, ho = (h + 1) / 2;
+    for (int yo = 0; yo < ho; ++yo)
+        for (int xo = 0; xo < wo; ++xo)
+            for (int c = 0; c < channels; ++c) {
+                int t = 0;
+                for (int j = 0; j < 5; ++j) {
+                    const size_t row = (size_t)at(2 * yo - 2 + j, h) * w;
+                    int r = 0;
+                    for (int i = 0; i < 5; ++i) r += tap[i] * (int)src[(row + at(2 * xo - 2 + i, w)) * channels + c];
+                    t += tap[j] * r;
+                }
+                dst[((size_t)yo * wo + xo) * channels + c] = (unsigned char)((t + 128) >> 8);
+            }
+}
+
+void crossScaleOnCPU(const float* const* levels, float* out, float* best, float* disp_map, const int w, const int h, const int dmin,
+                     const int size_d, const smx_cscale_params& p) {
+    float wt[SMX_CSCALE_MAX_SCALES];
+    if (!smx::cscale_params_ok(&p)) return;
+    smx::cscale_weights(&p, wt);        // (what smx_cscale_weights and smx_cscale_level run)
+    int ws[SMX_CSCALE_MAX_SCALES], hs[SMX_CSCALE_MAX_SCALES], lo[SMX_CSCALE_MAX_SCALES], ds[SMX_CSCALE_MAX_SCALES];
+    for (int s = 0; s < p.scales; ++s) smx::cscale_level(w, h, dmin, size_d, s, &ws[s], &hs[s], &lo[s], &ds[s]);
+    const size_t n = (size_t)w * h;
+    const uint32_t none = 0x7FFFFFFFu;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t id = (size_t)y * w + x;
+            float m = std::numeric_limits<float>::infinity();
+            int zm = -1;
+            for (int z = 0; z < size_d; ++z) {
+                float o = wt[0] * levels[0][(size_t)z * n + id];
+                for (int s = 1; s < p.scales; ++s) {
+                    const size_t cell = ((size_t)(((dmin + z) >> s) - lo[s]) * hs[s] + (size_t)(y >> s)) * ws[s] + (size_t)(x >> s);
+                    const float t = wt[s] * levels[s][cell];
+                    o = o + t;
+                }
+                out[(size_t)z * n + id] = o;
+                if (o <= m) { m = o; zm = z; }
+            }
+            if (best) {
+                if (zm < 0) memcpy(&best[id], &none, 4);
+                else best[id] = m == 0.0f ? 0.0f : m;
+            }
+            if (disp_map) disp_map[id] = (float)(dmin + (zm < 0 ? 0 : zm));
+        }
 }
 
 // ---- occlusion.cuh -------------------------------------------------------------------------

@@ -64,6 +64,16 @@
 //                     --pfm and --png16 then come from the adjusted map, which occlu_mapl_adjusted.png holds too, and with
 //                     --subpixel the changed pixels carry their own fits.  At most 512 labels.  With --host-compare the CPU twin
 //                     (discontinuityAdjustOnCPU) redoes it from the twin of the fill
+//   --cross-scale [S[,LAMBDA]]  cross-scale cost aggregation for the guided filter (smx_ctx_set_cross_scale; Zhang et al. 2014, not
+//                     in the reference; implies --fused): the pair is aggregated at S levels of an image pyramid (1 .. 5; default
+//                     4) with the unchanged aggregation, and the winners come from the levels' volumes combined under an
+//                     inter-scale regulariser of weight LAMBDA (finite, >= 0; default 1.0).  It helps on textureless surfaces
+//                     wider than the filter's window; a coarse label stands for 2^s fine ones, which it cannot split.  The value
+//                     is optional, like --vote's.  With the gray or the colour guide and every --cost; the twelve images come
+//                     from the combined winners, the two mean images are empty, and disparity_mapl_cscale.png holds the left
+//                     map once more.  With --host-compare the CPU twins (pyrDownOnCPU, the cost and guided-filter twins at every
+//                     level, crossScaleOnCPU) redo both views and check_errors compares.  Not with --aggregation sgm | cross |
+//                     scanline | cross-scanline, --ngpu or --pipeline
 //   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
 //                     census cost, --census-window / --census-th included, unless --cost reference is given): the same
 //                     twelve images, the two mean images empty.
@@ -130,6 +140,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "scanlineOptimization.cuh"
 #include "crossAggregation.cuh"
+#include "crossScale.cuh"
 #include "discontinuityAdjustment.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
@@ -165,6 +176,8 @@ struct Options {
     smx_cross_params vote_arms;
     bool adjust = false;     // --adjust
     smx_adjust_params adjust_params;
+    bool cscale = false;     // --cross-scale
+    smx_cscale_params cs_params;
     bool rgb = false;        // --guidance rgb
     float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
@@ -319,6 +332,15 @@ const ValueOption optional_value_options[] = {
          const int got = std::sscanf(v.c_str(), "%d%c%d%c%d%c", &p.tau_s, &c1, &p.tau_h_pct, &c2, &p.iterations, &rest);
          return ((got == 3 && c1 == ',') || (got == 5 && c1 == ',' && c2 == ',')) && p.tau_s >= 0 && p.tau_h_pct >= 0 &&
                 p.tau_h_pct <= 99 && p.iterations >= 0 && p.iterations <= 8; }},
+    {"--cross-scale", "S[,LAMBDA] with 1 <= S <= 5 and a finite LAMBDA >= 0", [](auto& v, auto& o) {
+         smx_cscale_params& p = o.cs_params;
+         o.cscale = true;
+         if (v.empty()) return true;
+         char comma = 0, rest = 0;
+         p.scales = 0;
+         const int got = std::sscanf(v.c_str(), "%d%c%lf%c", &p.scales, &comma, &p.lambda, &rest);
+         return (got == 1 || (got == 3 && comma == ',')) && p.scales >= 1 && p.scales <= SMX_CSCALE_MAX_SCALES &&
+                std::isfinite(p.lambda) && p.lambda >= 0.0; }},
     {"--adjust", "TAU[,N] with 1 <= TAU <= 512 and 1 <= N <= 8", [](auto& v, auto& o) {
          smx_adjust_params& p = o.adjust_params;
          o.adjust = true;
@@ -343,6 +365,7 @@ Options parse(int argc, char** argv) {
     smx_default_vote_params(&o.vote_params);
     smx_default_cross_params(&o.vote_arms);
     smx_default_adjust_params(&o.adjust_params);
+    smx_default_cscale_params(&o.cs_params);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -419,6 +442,7 @@ struct Maps {
     std::vector<float> occlusion, filled;
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
+    std::vector<float> cscale;         // --cross-scale: the left map of the combined winners (= dmap[0])
     std::vector<float> adjusted;       // --adjust: the filled left map with the pixels beside its depth steps adjusted (= filled)
     std::vector<float> unique;         // --uniqueness: the LR-checked left map without its ambiguous winners
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
@@ -484,6 +508,93 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         std::cout << (opt.sgm ? "Semi-global matching" : opt.so ? "Scan-line optimisation" : opt.rgb ? "Colour guided filter"
                                                                                                       : "Cross-based aggregation") << " ok!"
                   << std::endl;
+}
+
+// --host-compare of --cross-scale: per view and level the pyramid twin, the cost of the options at the level's geometry and the
+// guided-filter twin slice by slice (from the preset, a slice's filtered cost is its aggregated plane), then the combination twin;
+// its winners against the pair's, and the left combined volume against the context's where that was fetched.
+void check_cross_scale_twin(const Job& j, Maps& m, std::vector<float>& agg_l) {
+    const Options& opt = j.opt;
+    const int S = opt.cs_params.scales;
+    const bool colour = opt.rgb || opt.ad_rgb;
+    const int ch = j.in.channels[0];
+    // the pyramids: level 0 is the pair itself
+    std::vector<std::vector<unsigned char>> gray[2], rgb[2];
+    std::vector<Job> level(S, Job{opt});
+    for (int s = 0; s < S; ++s) {
+        Job& l = level[s];
+        int size_l, size_r;
+        smx_cscale_level(j.w, j.h, j.dmin[0], j.size_d, s, &l.w, &l.h, &l.dmin[0], &size_l);
+        smx_cscale_level(j.w, j.h, j.dmin[1], j.size_d, s, &l.w, &l.h, &l.dmin[1], &size_r);
+        l.n = l.w * l.h;
+        l.in.w = l.w; l.in.h = l.h;
+        for (int v = 0; v < 2; ++v) {
+            l.in.channels[v] = j.in.channels[v];
+            if (s == 0) { l.gray[v] = j.gray[v]; l.in.rgb[v] = j.in.rgb[v]; continue; }
+            const Job& b = level[s - 1];
+            gray[v].emplace_back((size_t)l.n);
+            pyrDownOnCPU(b.gray[v], gray[v].back().data(), b.w, b.h, 1);
+            l.gray[v] = gray[v].back().data();
+            if (colour) {
+                rgb[v].emplace_back((size_t)l.n * ch);
+                pyrDownOnCPU(b.in.rgb[v], rgb[v].back().data(), b.w, b.h, ch);
+                l.in.rgb[v] = rgb[v].back().data();
+            }
+        }
+    }
+    bool ok = true;
+    for (int v = 0; v < 2; ++v) {
+        std::vector<std::vector<float>> vols(S);
+        const float* ptrs[SMX_CSCALE_MAX_SCALES] = {};
+        for (int s = 0; s < S; ++s) {
+            Job& l = level[s];
+            int ws, hs, lo;
+            smx_cscale_level(j.w, j.h, j.dmin[v], j.size_d, s, &ws, &hs, &lo, &l.size_d);
+            const size_t n = (size_t)l.n;
+            std::vector<float> cost(n * l.size_d), tb(n), td(n);
+            std::vector<unsigned char> mean(n);
+            vols[s].resize(n * l.size_d);
+            if (opt.adcensus && opt.ad_rgb) {
+                // (the stage wrapper makes the gray images of the census codes from the colour images it is given; a level's gray
+                // image is the pyramid of the gray image, so the cost twin takes both pyramids here)
+                std::vector<float> table(SMX_ADCENSUS_TABLE_FLOATS);
+                CHECK(smx_adcensus_tables(&opt.adc_params, table.data()));
+                adcensus_costOnCPU(l.in.rgb[v], l.in.rgb[1 - v], l.gray[v], l.gray[1 - v], ch, cost.data(), l.w, l.h, l.size_d,
+                                   l.dmin[v], opt.adc_params, table.data());
+            } else {
+                build_cost(l, v, l.size_d, cost.data(), false);
+            }
+            if (opt.rgb) {
+                std::memset(tb.data(), 0x7F, sizeof(float) * n);
+                colour_guided_filterOnCPU(l.in.rgb[v], ch, cost.data(), tb.data(), td.data(), vols[s].data(), l.w, l.h, l.size_d,
+                                          l.dmin[v], smx_config().params.radius, smx_config().params.eps);
+            } else {
+                std::memset(vols[s].data(), 0x7F, sizeof(float) * vols[s].size());
+                for (int z = 0; z < l.size_d; ++z)
+                    guided_filter_onCpu(l.gray[v], cost.data() + z * n, vols[s].data() + z * n, td.data(), mean.data(), l.w, l.h, 1,
+                                        l.dmin[v] + z);
+            }
+            ptrs[s] = vols[s].data();
+        }
+        const size_t n = (size_t)j.n;
+        std::vector<float> out(n * j.size_d), best(n), disp(n), tb(n), td(n, 0.0f);
+        crossScaleOnCPU(ptrs, out.data(), best.data(), disp.data(), j.w, j.h, j.dmin[v], j.size_d, opt.cs_params);
+        // the winners through the reference's presets, as the pair's finish takes them
+        std::memset(tb.data(), 0x7F, sizeof(float) * n);
+        for (size_t i = 0; i < n; ++i)
+            if (tb[i] >= best[i]) { tb[i] = best[i]; td[i] = disp[i]; }
+        ok = check_errors(tb.data(), m.best[v].data(), j.n) && ok;
+        ok = check_errors(td.data(), m.dmap[v].data(), j.n) && ok;
+        if (v == 0 && !agg_l.empty()) {
+            for (size_t i = 0; i < out.size(); ++i)
+                if (std::memcmp(&out[i], &agg_l[i], 4) != 0 && !(out[i] != out[i] && agg_l[i] != agg_l[i])) {
+                    std::cout << "error at element " << i << " of the combined left volume" << std::endl;
+                    ok = false;
+                    break;
+                }
+        }
+    }
+    if (ok) std::cout << "Cross-scale ok!" << std::endl;
 }
 
 // --host-compare of the device-resident flow behind the winners: LR check, uniqueness (from the left aggregated volume), speckle
@@ -599,11 +710,11 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     std::memset(&out, 0, sizeof(out));
     out.best_l = m.best[0].data(); out.best_r = m.best[1].data();
     out.dmap_l = m.dmap[0].data(); out.dmap_r = m.dmap[1].data();
-    // (SGM, the colour guide, cross-based aggregation and the scan-line optimiser have no mean images)
-    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
+    // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser and cross-scale have no mean images)
+    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
     std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness and adjustment twins read
-    if ((uniq || opt.adjust) && host_compare) {
+    if ((uniq || opt.adjust || opt.cscale) && host_compare) {
         agg_l.resize((size_t)n * j.size_d);
         out.agg_l = agg_l.data();
     }
@@ -619,6 +730,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
     if (opt.vote) CHECK(smx_ctx_set_vote(ctx, &opt.vote_params, &opt.vote_arms));
     if (opt.adjust) CHECK(smx_ctx_set_adjust(ctx, &opt.adjust_params));
+    if (opt.cscale) CHECK(smx_ctx_set_cross_scale(ctx, &opt.cs_params));
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
@@ -669,10 +781,13 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
         CHECK(smx_ctx_uniqueness_map(ctx, m.unique.data(), nullptr));
     }
     if (opt.adjust) m.adjusted = m.filled;
+    if (opt.cscale) m.cscale = m.dmap[0];
     if (sh.create) CHECK(sh.destroy(sctx));
     else CHECK(smx_destroy(ctx));
     std::cout << "guided filter ok" << std::endl;
-    if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
+    // (with --cross-scale the winners are the combination's: its twin redoes the colour guide's aggregation at every level)
+    if (host_compare && opt.cscale) check_cross_scale_twin(j, m, agg_l);
+    else if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
     if (host_compare) check_finish_twins(j, m, agg_l);
     return have_stage_ms;
 }
@@ -694,6 +809,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"disparity_mapr.png", m.dmap[1]},   {"occlu_mapl_filled.png", m.filled},
                                   {"occlu_mapl_despeckled.png", m.despeckled}, {"occlu_mapl_unique.png", m.unique},
                                   {"occlu_mapl_voted.png", m.voted}, {"occlu_mapl_adjusted.png", m.adjusted},
+                                  {"disparity_mapl_cscale.png", m.cscale},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
     for (const U8Out& o : u8_outputs)
@@ -777,6 +893,9 @@ int main(int argc, char** argv) {
         {uniq && multi, "--uniqueness" + with_multi},
         {opt.vote && multi, "--vote" + with_multi},
         {opt.vote && labels > 512, "--vote takes at most 512 labels"},
+        {opt.cscale && (opt.sgm || opt.cross || opt.so),
+         "--cross-scale belongs to the guided filter: it cannot be combined with --aggregation sgm, cross, scanline or cross-scanline"},
+        {opt.cscale && multi, "--cross-scale" + with_multi},
         {opt.adjust && multi, "--adjust" + with_multi},
         {opt.adjust && labels > 512, "--adjust takes at most 512 labels"},
         {opt.ngpu < 0 || opt.ngpu > smx_device_count(),
@@ -792,7 +911,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
-                       opt.cross || opt.so || opt.adjust;
+                       opt.cross || opt.so || opt.adjust || opt.cscale;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;

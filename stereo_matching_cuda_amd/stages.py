@@ -260,6 +260,48 @@ def discontinuity_adjust(disparity, agg, dmin, params=None, subpixel=None, sub=N
     return out if s is None else (out, s)
 
 
+def pyr_down(image):
+    """One level of the cross-scale pyramid (include/smx.h smx_pyr_down; not a stage of the reference).  image: (h, w) or
+    (h, w, 1 | 3 | 4) uint8 -> ((h+1)//2, (w+1)//2[, channels]) uint8: taps 1 4 6 4 1 on integers, reflect-101 borders."""
+    a = _c(image, np.uint8)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3, 4)) or a.size == 0:
+        raise ValueError("pyr_down expects an (h, w) or (h, w, 1 | 3 | 4) uint8 image")
+    h, w = a.shape[:2]
+    out = np.empty(((h + 1) // 2, (w + 1) // 2) + a.shape[2:], np.uint8)
+    _lib.check(_lib.lib().smx_pyr_down(_ptr(a), _ptr(out), w, h, 1 if a.ndim == 2 else a.shape[2]))
+    return out
+
+
+def cross_scale_combine(levels, dmin, params=None):
+    """The cross-scale combination of one view's per-level aggregated volumes and its winners (include/smx.h
+    smx_cscale_combine; not a stage of the reference).  levels: `scales` float32 volumes, levels[s] of shape
+    (size_d_s, h_s, w_s) -- the geometry of smx_cscale_level for the level-0 shape and labels dmin ..; params: CScaleParams
+    whose scales is len(levels) (None: the default lambda).  Returns (combined (size_d, h, w) float32, best (h, w) float32,
+    label map (h, w) float32)."""
+    if params is not None and not isinstance(params, _lib.CScaleParams):
+        raise ValueError(f"params must be None or CScaleParams, not {params!r}")
+    vols = [_c(v, np.float32) for v in levels]
+    if not 1 <= len(vols) <= 5 or any(v.ndim != 3 or v.size == 0 for v in vols):
+        raise ValueError("cross_scale_combine expects 1 .. 5 float32 volumes (size_d_s, h_s, w_s)")
+    p = _lib.default_cscale_params()
+    if params is not None:
+        p.lambda_ = params.lambda_
+        if params.scales != len(vols):
+            raise ValueError(f"params.scales is {params.scales}, but {len(vols)} levels are given")
+    p.scales = len(vols)
+    size_d, h, w = vols[0].shape
+    for s, v in enumerate(vols):
+        ws, hs, _, ds = _lib.cscale_level(w, h, dmin, size_d, s)
+        if v.shape != (ds, hs, ws):
+            raise ValueError(f"level {s} must have shape {(ds, hs, ws)}, not {v.shape}")
+    ptrs = (C.c_void_p * len(vols))(*[v.ctypes.data for v in vols])
+    out = np.empty((size_d, h, w), np.float32)
+    best = np.empty((h, w), np.float32)
+    disp = np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_cscale_combine(C.byref(p), ptrs, w, h, int(dmin), size_d, _ptr(out), _ptr(best), _ptr(disp)))
+    return out, best, disp
+
+
 def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
     """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
     reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
