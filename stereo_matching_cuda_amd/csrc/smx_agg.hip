@@ -209,9 +209,15 @@ static v5::Args comb_args(const v4::Args& a, const AggLayout& L, char* base, boo
     return b;
 }
 
-// Image planes and guidance statistics of the call (guidedFilter.cu:58-123) in three launches: (mean_I, 1/(var_I + eps)), the
-// optional u8 mean image, the comb walker's comb-ordered copies.  *out: the planes the walkers read.
-static int guidance(const AggLayout& L, char* base, const AggCall& c, v4::Guidance* out) {
+// (dev / test hook, smx_debug_set_guidance_path: 0 = choose, 1 = the comb walker's guidance in three launches whatever the height)
+static thread_local int g_guid_path = 0;
+static thread_local int g_last_guid_bw = -1;      // the last fused call of this thread: columns per guidance block, 0 = three launches
+
+// Image planes and guidance statistics of the call (guidedFilter.cu:58-123): (mean_I, 1/(var_I + eps)), the optional u8 mean
+// image, the comb walker's comb-ordered copies.  Two launches on the comb-walker path where a column block's integral images
+// fit the LDS (v5::guid_block_width: row prefixes, then k_v5_guid_block), else three (row prefixes, column prefixes,
+// statistics).  *out: the planes the walkers read; *launches: how many it took.
+static int guidance(const AggLayout& L, char* base, const AggCall& c, v4::Guidance* out, int* launches) {
     const int nviews = L.nviews, w = c.w, h = c.h;
     const smx_params* const p = c.p;
     hipStream_t st = c.st;
@@ -228,13 +234,17 @@ static int guidance(const AggLayout& L, char* base, const AggCall& c, v4::Guidan
     // (the status words and the first chunk's control block are cleared here: no memset in front of the first walker)
     g.zero[0] = (unsigned*)(base + L.status); g.nzero[0] = 64;
     g.zero[1] = (unsigned*)(base + L.ctrl); g.nzero[1] = (unsigned)(L.ctrl_bytes / 4);
-    int rc = v4_guidance_launch(g, nviews, w, h, p->radius, p->eps, !L.comb, st);
+    const int bw = L.comb && g_guid_path != 1 ? v5::guid_block_width(h) : 0;
+    g_last_guid_bw = bw;
+    *launches = bw ? 2 : 3;
+    int rc = v4_guidance_launch(g, nviews, w, h, p->radius, p->eps, !L.comb, bw == 0, st);
     if (rc || !L.comb) return rc;
     // (the comb walker's planes: the statistics are evaluated where the comb-ordered copy is written, and G / the u8
     // mean leave from there too -- one launch and one round trip of G less than finish + permute)
     aggdev::f2* g1p[2] = {nullptr, nullptr};
     unsigned* i2p[2] = {nullptr, nullptr};
     for (int v = 0; v < nviews; ++v) { g1p[v] = (aggdev::f2*)(base + L.g1p[v]); i2p[v] = (unsigned*)(base + L.i2p[v]); }
+    if (bw) return v5_guid_block_launch(bw, nviews, g.S0, g.S1, g.G, g.mean_u8, g.FG, g1p, i2p, w, h, p->eps, st);
     return v5_perm_launch(nviews, g.S0, g.S1, g.G, g.mean_u8, g.FG, g1p, i2p, w, h, p->eps, st);
 }
 
@@ -260,8 +270,8 @@ static int aggregate_fused(const AggCall& c, const AggOpts& opt, AggInfo* info) 
     unsigned* const status = (unsigned*)(base + L.status);
     char* const ctrl = base + L.ctrl;
     v4::Guidance g;
-    if ((rc = guidance(L, base, c, &g))) return rc;
-    int nl = 3;
+    int nl = 0;
+    if ((rc = guidance(L, base, c, &g, &nl))) return rc;
     stage_mark(ST_GUIDANCE, st);
 
     v4::Args a0;
@@ -443,3 +453,24 @@ int aggregate(const AggCall& c, int forced, const AggOpts& opt, AggInfo* info) {
 }
 
 }  // namespace smx
+
+// (dev / test hooks, not in smx.h: the guidance launches of the calling thread's fused aggregations on the comb-walker path --
+// 0 = choose (two launches where v5::guid_block_width(h) > 0), 1 = three launches whatever the height; what the thread's last
+// fused call ran with: *bw = columns per guidance block, 0 = three launches, -1 = no call yet; and the choice itself, pure host
+// arithmetic: the block width for h rows, 0 = none fits, and the LDS bytes of that block)
+extern "C" __attribute__((visibility("default"))) int smx_debug_set_guidance_path(int path) {
+    if (path < 0 || path > 1) return smx::fail(SMX_E_ARG, "smx_debug_set_guidance_path: path must be 0 or 1");
+    smx::g_guid_path = path;
+    return SMX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int smx_debug_last_guidance_block(int* bw) {
+    SMX_ARG(bw);
+    *bw = smx::g_last_guid_bw;
+    return SMX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int smx_debug_guidance_block(int h, int* bw, uint64_t* lds_bytes) {
+    SMX_ARG(h >= 1 && bw);
+    *bw = smx::v5::guid_block_width(h);
+    if (lds_bytes) *lds_bytes = *bw ? (uint64_t)smx::v5::guid_block_lds(h, *bw) : 0;
+    return SMX_OK;
+}

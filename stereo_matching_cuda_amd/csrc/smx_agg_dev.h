@@ -51,26 +51,29 @@ __device__ __forceinline__ bool div_needs_exact(float x) {
 
 // Guidance statistics of one pixel from the integral images S0 (of I) and S1 (of I*I): mean_I = box(S0),
 // var = box(S1) - mean_I*mean_I, 1/(var + eps) in double as the reference's compute_ak_and_bk (guidedFilter.cu:350).
-// Returns (mean_I, 1/(var_I + eps)).
-__device__ __forceinline__ f2 guid_point(const float* __restrict__ S0, const float* __restrict__ S1, int x, int y, int w, int h,
-                                         int R, double eps) {
+// Returns (mean_I, 1/(var_I + eps)).  The integral images are read through ld(plane, row, column) -- from wherever the caller
+// keeps them -- and only at taps that exist: the arithmetic has this one definition.
+template <class Ld>
+__device__ __forceinline__ f2 guid_point_at(Ld ld, int x, int y, int w, int h, int R, double eps) {
     const int ymin = max(-1, y - R - 1), ymax = min(h - 1, y + R);
     const int xmin = max(-1, x - R - 1), xmax = min(w - 1, x + R);
     const bool hx = xmin >= 0, hy = ymin >= 0;
-    const size_t i11 = (size_t)ymax * w + xmax, i10 = (size_t)ymax * w + (hx ? xmin : 0);
-    const size_t i01 = (size_t)(hy ? ymin : 0) * w + xmax, i00 = (size_t)(hy ? ymin : 0) * w + (hx ? xmin : 0);
     const float area = (float)((xmax - xmin) * (ymax - ymin));
-    auto box = [&](const float* __restrict__ S) {      // computeBoxFilterOnGPU guidedFilter.cu:305-318
-        float val = S[i11];
-        if (hx) val -= S[i10];
-        if (hy) val -= S[i01];
-        if (hx && hy) val += S[i00];
+    auto box = [&](int pl) {                            // computeBoxFilterOnGPU guidedFilter.cu:305-318
+        float val = ld(pl, ymax, xmax);
+        if (hx) val -= ld(pl, ymax, xmin);
+        if (hy) val -= ld(pl, ymin, xmax);
+        if (hx && hy) val += ld(pl, ymin, xmin);
         return 1.0f * val / area;
     };
-    const float m = box(S0), sq = box(S1);
+    const float m = box(0), sq = box(1);
     const float m2 = m * m;                             // pixelMultOnGPU(mean, mean) :112
     const float var = sq - m2;                          // pixelSousOnGPU :121
     return (f2){m, (float)(1.0f / ((double)var + eps))};
+}
+__device__ __forceinline__ f2 guid_point(const float* __restrict__ S0, const float* __restrict__ S1, int x, int y, int w, int h,
+                                         int R, double eps) {
+    return guid_point_at([&](int pl, int yy, int xx) { return (pl ? S1 : S0)[(size_t)yy * w + xx]; }, x, y, w, h, R, eps);
 }
 __device__ __forceinline__ uint8_t mean_to_u8(float m) {   // flToChOnGPU guidedFilter.cu:451-458
     const int ci = (int)m;

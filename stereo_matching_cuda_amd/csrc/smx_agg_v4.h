@@ -62,8 +62,9 @@ struct Guidance {
 
 bool v4_supported(const smx_params* p);          // radius 0 .. RMAX
 // Image planes and guidance statistics of one call: k_v4_guid_rows, k_v4_guid_cols and -- `finish` -- k_v4_guid_finish
-// (G, mean_u8 from the integrals).  finish == false: the caller's v5_perm_launch takes the third launch's place.
-int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, hipStream_t st);
+// (G, mean_u8 from the integrals).  finish == false: the caller's v5_perm_launch takes the third launch's place.  cols == false
+// (with finish == false): k_v4_guid_rows alone -- S0 / S1 are left as ROW prefixes for the caller's v5_guid_block_launch.
+int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, bool cols, hipStream_t st);
 // the walker over a.nitems items: costs from a.v[].cost or built from the image planes; fast: the FAST mode (not bit-exact)
 int v4_walk_launch(const v4::Args& a, bool use_cost, bool fast, hipStream_t st);
 

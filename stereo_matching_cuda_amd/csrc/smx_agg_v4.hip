@@ -121,7 +121,36 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
     float* P1 = gr_lds + rows * wpad;
     // (1) the rows of this workgroup, 16 loads per thread in flight
     const int total = rows * wr;
-    for (int e0 = 0; e0 < total; e0 += 16 * GR_NT) {
+    const int nr = min(rows, h - y0);
+    // The rows of a workgroup are one contiguous byte range of the image: where it starts and ends on a 4-byte boundary, four
+    // pixels per load.  What lies behind a row's w columns and behind the image's last row is scanned but never stored: zeros.
+    const bool quads = (((size_t)Iu + (size_t)y0 * w) & 3) == 0 && ((nr * w) & 3) == 0;
+    if (quads) {
+        const unsigned* __restrict__ I4 = (const unsigned*)(Iu + (size_t)y0 * w);
+        const int ndw = nr * w / 4;
+        for (int i0 = 0; i0 < ndw; i0 += 4 * GR_NT) {
+            unsigned u[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) u[k] = I4[min(i0 + k * GR_NT + tid, ndw - 1)];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = i0 + k * GR_NT + tid;
+                if (i < ndw) {
+                    int r = 4 * i / w, x = 4 * i - r * w;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const float f = 1.0f * (float)(int)((u[k] >> (8 * b)) & 255u);     // chToFlOnGPU guidedFilter.cu:442-449
+                        P0[r * wpad + x] = f;
+                        P1[r * wpad + x] = f * f;                                       // pixelMultOnGPU(d_im, d_im) :111
+                        if (++x == w) { x = 0; ++r; }
+                    }
+                }
+            }
+        }
+        for (int r = 0; r < rows; ++r)
+            for (int x = (r < nr ? w : 0) + tid; x < wr; x += GR_NT) { P0[r * wpad + x] = 0.0f; P1[r * wpad + x] = 0.0f; }
+    }
+    for (int e0 = quads ? total : 0; e0 < total; e0 += 16 * GR_NT) {
         float v[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -145,20 +174,21 @@ __global__ __launch_bounds__(GR_NT) void k_v4_guid_rows(GuidArgs ga, int w, int 
     // (From global memory, a cell per loop trip, this part cost 5 us: its byte loads were waited for trip by trip.)
     if (view < ga.nimg) {
         fg_t* __restrict__ FGo = ga.prep.FG[view];
-        const int nr = min(rows, h - y0);
-        for (int e = tid; e < nr * wp; e += GR_NT) {
-            const int r = e / wp, xp = e - r * wp, x = xp - PADX;
-            float f = 60000.0f, g = 60000.0f;
-            if (x >= 0 && x < w) {
-                const float* pr = P0 + r * wpad;
-                f = pr[x];
-                const float c1 = pr[x + 1 < w ? x + 1 : x], c2 = pr[x - 1 >= 0 ? x - 1 : x];     // (w >= 2)
-                g = 1.0f * (c2 - c1) / 2;
+        for (int r = 0; r < nr; ++r) {
+            const float* pr = P0 + r * wpad;
+            for (int xp = tid; xp < wp; xp += GR_NT) {
+                const int x = xp - PADX;
+                float f = 60000.0f, g = 60000.0f;
+                if (x >= 0 && x < w) {
+                    f = pr[x];
+                    const float c1 = pr[x + 1 < w ? x + 1 : x], c2 = pr[x - 1 >= 0 ? x - 1 : x];     // (w >= 2)
+                    g = 1.0f * (c2 - c1) / 2;
+                }
+                fg_t v;
+                v.x = (_Float16)f;
+                v.y = (_Float16)g;
+                FGo[(size_t)(y0 + r) * wp + xp] = v;
             }
-            fg_t v;
-            v.x = (_Float16)f;
-            v.y = (_Float16)g;
-            FGo[(size_t)(y0 + r) * wp + xp] = v;
         }
     }
     if (view >= ga.nviews) return;          // (an image that is only the other view's partner: no statistics)
@@ -1062,7 +1092,7 @@ static inline unsigned cdivu4(int64_t a, int64_t b) { return (unsigned)((a + b -
 
 bool v4_supported(const smx_params* p) { return p->radius >= 0 && p->radius <= v4::RMAX; }
 
-int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, hipStream_t st) {
+int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, double eps, bool finish, bool cols, hipStream_t st) {
     v4::GuidArgs ga;
     memset(&ga, 0, sizeof(ga));
     for (int v = 0; v < nviews; ++v) {
@@ -1089,7 +1119,7 @@ int v4_guidance_launch(const v4::Guidance& g, int nviews, int w, int h, int R, d
     SMX_HIP(lim.ensure((const void*)v4::k_v4_guid_rows, 160 * 1024));
     hipLaunchKernelGGL(v4::k_v4_guid_rows, dim3(cdivu4(h, rows), nimg > nviews ? nimg : nviews), dim3(v4::GR_NT), (size_t)8 * rows * wpad, st,
                        ga, w, h, rows);
-    hipLaunchKernelGGL(v4::k_v4_guid_cols, dim3(cdivu4(w, 64), 2, nviews), dim3(64 * v4::GC_NW), 0, st, ga, w, h);
+    if (cols || finish) hipLaunchKernelGGL(v4::k_v4_guid_cols, dim3(cdivu4(w, 64), 2, nviews), dim3(64 * v4::GC_NW), 0, st, ga, w, h);
     if (finish) hipLaunchKernelGGL(v4::k_v4_guid_finish, dim3(cdivu4(w, 256), h, nviews), dim3(256), 0, st, ga, w, h, R, eps);
     SMX_HIP(hipGetLastError());
     return SMX_OK;

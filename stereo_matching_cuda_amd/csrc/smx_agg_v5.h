@@ -98,6 +98,28 @@ inline int period(int h, int K) {
 }
 inline size_t sv_hand_floats(int h) { return (size_t)2 * records(h) * REC_U * 4; }   // parity x records
 
+// k_v5_guid_block: a workgroup keeps both integral planes of its bw a/b columns and their HW halo columns, all h rows, in
+// LDS, and GB_TAIL bytes of hand-over words behind them.  The host takes the widest block that fits the 160 KiB of a CU; 0:
+// none does (the call keeps the column-scan and permutation launches).
+constexpr int GB_TAIL = 1024;
+constexpr size_t GB_LDS_MAX = 160 * 1024;
+inline size_t guid_block_lds(int h, int bw) { return (size_t)2 * h * (bw + HW) * 4 + GB_TAIL; }
+inline int guid_block_width(int h) {
+    for (int bw = 32; bw >= 8; bw /= 2)
+        if (guid_block_lds(h, bw) <= GB_LDS_MAX) return bw;
+    return 0;
+}
+// Workgroups that share a block, each with a range of the band grid's `npair` row pairs: two where that keeps the launch's
+// nblocks (all views) within the 256 CUs of the chip, with at least 8 row pairs each.  (KITTI shape, 78 blocks: 20.6 us with
+// one, 18.0 with two, 19.8 with three -- every workgroup runs the column prefix down to its last row, and with the
+// workgroups of the comb-ordered image values the launch then has more workgroups than the chip holds at once.)
+inline int guid_block_split(int nblocks, int npair) {
+    int ns = 256 / (nblocks > 0 ? nblocks : 1);
+    ns = ns > 2 ? 2 : ns;
+    ns = ns > npair / 8 ? npair / 8 : ns;
+    return ns < 1 ? 1 : ns;
+}
+
 }  // namespace v5
 
 // radius 9, and parameters for which no window sum of the matching cost can be tiny without being zero (the
@@ -112,5 +134,10 @@ int v5_launch(const v5::Args& a, hipStream_t st);
 int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G, uint8_t* const* mean_u8,
                    const aggdev::fg_t* const* FG, aggdev::f2* const* g1p, unsigned* const* i2p, int w, int h, double eps,
                    hipStream_t st);
+// the same planes from the ROW prefixes S0, S1 of k_v4_guid_rows in one launch: column prefix, statistics and comb-ordered
+// copies per block of bw = v5::guid_block_width(h) > 0 columns (S0, S1 are read only)
+int v5_guid_block_launch(int bw, int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G,
+                         uint8_t* const* mean_u8, const aggdev::fg_t* const* FG, aggdev::f2* const* g1p, unsigned* const* i2p, int w,
+                         int h, double eps, hipStream_t st);
 
 }  // namespace smx

@@ -1125,14 +1125,37 @@ struct PermArgs {
     f2* g1p[2];
     unsigned* i2p[2];
 };
-__global__ __launch_bounds__(CLP) void k_v5_perm(PermArgs pa, int w, int h, int K, int NI) {
-    const int cl = threadIdx.x, cw = cl >> 6, ln = cl & 63;
+// a/b column of stage-1 comb lane cl of strip k (the q column of stage-2 lane cl is R to the left); false: the lane idles
+__device__ __forceinline__ bool comb_lane_col(int cl, int k, int* x1) {
+    const int cw = cl >> 6, ln = cl & 63;
     const int rho = ln / L < CPW ? CPW * cw + ln / L : HW, il = ln % L;
+    *x1 = OWS * k - R - 1 + HW * il + rho;
+    return rho < HW;
+}
+// stage 2: the q rows 10 (ib - 1) - 18 + 2 j, + 1 of band ib: image values as an fp16 pair (row pairs clamped like the
+// loads they replace; a row behind the image holds 0); pairs 0 .. 3 of a band form a u32x4, pair 4 lies behind them
+__device__ __forceinline__ void perm_i2_pair(const PermArgs& pa, int v, int k, int ib, int j, int cl, int xq, bool on2, int w, int h,
+                                             int K, int NI) {
+    const int yp = min(max((BH * (ib - 1) - 2 * R) / 2 + j, 0), (h - 1) / 2), y = 2 * yp;
+    fg_t p2 = {(_Float16)0.0f, (_Float16)0.0f};
+    if (on2) {
+        p2.x = pa.FG[v][(size_t)y * (w + 2 * PADX) + PADX + xq].x;
+        if (y + 1 < h) p2.y = pa.FG[v][(size_t)(y + 1) * (w + 2 * PADX) + PADX + xq].x;
+    }
+    const unsigned pr = __builtin_bit_cast(unsigned, p2);
+    unsigned* const i2a = pa.i2p[v];
+    unsigned* const i2b = pa.i2p[v] + (size_t)K * NI * CLP * 4;
+    const size_t e = ((size_t)k * NI + ib) * CLP + cl;
+    if (j < 4) i2a[4 * e + j] = pr; else i2b[e] = pr;
+}
+__global__ __launch_bounds__(CLP) void k_v5_perm(PermArgs pa, int w, int h, int K, int NI) {
+    const int cl = threadIdx.x;
     const int kb = blockIdx.x / (BH / 2), j = blockIdx.x - kb * (BH / 2);   // one row pair of a band per workgroup
     const int k = kb / NI, ib = kb - k * NI, v = blockIdx.y;
-    const int x1 = OWS * k - R - 1 + HW * il + rho;     // a/b column of stage-1 comb lane cl
+    int x1;                                             // a/b column of stage-1 comb lane cl
+    const bool lane_on = comb_lane_col(cl, k, &x1);
     const int xq = x1 - R;                              // q column of stage-2 comb lane cl
-    const bool on1 = rho < HW && x1 >= 0 && x1 < w, on2 = rho < HW && xq >= 0 && xq < w;
+    const bool on1 = lane_on && x1 >= 0 && x1 < w, on2 = lane_on && xq >= 0 && xq < w;
     // stage 1: the a/b rows 10 ib - 9 + 2 j, + 1 of band ib (rows clamped into the image; the a_k, b_k of rows outside it are
     // replaced by -0 whatever their guidance)
     {
@@ -1153,20 +1176,126 @@ __global__ __launch_bounds__(CLP) void k_v5_perm(PermArgs pa, int w, int h, int 
         }
         ((f4*)pa.g1p[v])[((size_t)k * (5 * NI) + 5 * ib + j) * CLP + cl] = g;
     }
-    // stage 2: the q rows 10 (ib - 1) - 18 + 2 j, + 1 of band ib: image values as an fp16 pair (row pairs clamped like the
-    // loads they replace; a row behind the image holds 0); pairs 0 .. 3 of a band form a u32x4, pair 4 lies behind them
-    {
-        const int yp = min(max((BH * (ib - 1) - 2 * R) / 2 + j, 0), (h - 1) / 2), y = 2 * yp;
-        fg_t p2 = {(_Float16)0.0f, (_Float16)0.0f};
-        if (on2) {
-            p2.x = pa.FG[v][(size_t)y * (w + 2 * PADX) + PADX + xq].x;
-            if (y + 1 < h) p2.y = pa.FG[v][(size_t)(y + 1) * (w + 2 * PADX) + PADX + xq].x;
+    perm_i2_pair(pa, v, k, ib, j, cl, xq, on2, w, h, K, NI);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// k_v4_guid_cols and k_v5_perm in one launch, the integral images in LDS: grid (nb ns + nh, nviews), block GB_NT, dynamic LDS
+// guid_block_lds(h, bw).
+// Workgroups 0 .. nb ns - 1: a block of bw consecutive a/b columns c0 .. c0 + bw - 1 of one view is shared by ns workgroups, each
+// with a range of the band grid's row pairs (the division is the long part, and nb workgroups leave most of the chip idle:
+// guid_block_split; the later ranges come first in the grid).  Each of them: (1) reads the ROW prefixes of columns
+// c0 - 10 .. c0 + bw + 8 (clamped into the image; what a clamped column holds is never a tap) of both planes, from row 0 to the
+// last row its windows reach; (2) runs the column prefix on them -- the reference's top -> bottom order (colSum
+// integral.cu:121-131), one running sum per lane from -0, the chain handed from wave to wave over segments of GB_SEG rows as in
+// k_v4_guid_cols (a plane's eight waves take its segments round robin; s_turn: whose segment it is) -- into LDS as
+// [plane][row][bw + 19]; (3) guid_point's
+// arithmetic for every (column, row pair of the band grid) -> G, the u8 mean and every g1p slot the column maps to: the
+// lane of its strip and, for the 19 columns two strips share, the halo lane of the next strip.
+// Workgroups nb ns .. write what does not depend on the integrals, a (strip, band, lane) per thread: i2p out of FG, and zeros
+// into the g1p slots of lanes without an a/b column in the image.
+// Together: every word k_v5_perm writes, with the same contents; S0 / S1 are read only.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int GB_NT = 1024, GB_NW = GB_NT / 64, GB_SEG = 32;
+static_assert(32 + HW <= 64 && GB_TAIL >= (2 * 64 + 2) * 4, "a plane's columns are the lanes of one wave; hand-over words");
+__global__ __launch_bounds__(GB_NT) void k_v5_guid_block(PermArgs pa, int w, int h, int K, int NI, int bw, int nb, int ns) {
+    extern __shared__ __attribute__((aligned(16))) float gb_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, v = blockIdx.y;
+    if ((int)blockIdx.x >= nb * ns) {
+        const int id = ((int)blockIdx.x - nb * ns) * GB_NT + tid;
+        if (id >= K * NI * CLP) return;
+        const int kb = id / CLP, cl = id - kb * CLP, k = kb / NI, ib = kb - k * NI;
+        int x1;
+        const bool lane_on = comb_lane_col(cl, k, &x1);
+        const int xq = x1 - R;
+        const bool on1 = lane_on && x1 >= 0 && x1 < w, on2 = lane_on && xq >= 0 && xq < w;
+#pragma unroll
+        for (int j = 0; j < BH / 2; ++j) {
+            perm_i2_pair(pa, v, k, ib, j, cl, xq, on2, w, h, K, NI);
+            if (!on1) ((f4*)pa.g1p[v])[((size_t)k * (5 * NI) + 5 * ib + j) * CLP + cl] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
         }
-        const unsigned pr = __builtin_bit_cast(unsigned, p2);
-        unsigned* const i2a = pa.i2p[v];
-        unsigned* const i2b = pa.i2p[v] + (size_t)K * NI * CLP * 4;
-        const size_t e = ((size_t)k * NI + ib) * CLP + cl;
-        if (j < 4) i2a[4 * e + j] = pr; else i2b[e] = pr;
+        return;
+    }
+    const int npair = 5 * NI, sp = ns - 1 - (int)blockIdx.x / nb, blk = (int)blockIdx.x % nb;
+    const int Pb = sp * npair / ns, Pe = (sp + 1) * npair / ns;      // this workgroup's row pairs: a/b rows 2 P - 9, 2 P - 8
+    const int hn = min(h, 2 * Pe);                                  // ... whose windows end in front of row 2 Pe
+    const int nc = bw + HW, c0 = blk * bw, cl0 = c0 - R - 1;
+    float* const s_acc = gb_lds + 2 * h * nc;           // [plane][64]
+    int* const s_turn = (int*)(s_acc + 2 * 64);         // [plane]
+    if (tid < 2) s_turn[tid] = 0;
+    // (1), (2) lane = column, waves 2 g + plane: the rows of a wave's segment global -> registers, the chain, -> LDS; the rows of its
+    // next segment are in flight while it waits for and runs the chain of this one
+    {
+        const int pl = wv & 1, cj = min(lane, nc - 1);
+        const float* __restrict__ const src = (pl ? pa.S1[v] : pa.S0[v]) + min(max(cl0 + cj, 0), w - 1);
+        float* const col = gb_lds + pl * h * nc + cj;
+        const int nseg = (hn + GB_SEG - 1) / GB_SEG;
+        auto fetch = [&](float (&s)[GB_SEG], int seg) {
+#pragma unroll
+            for (int t = 0; t < GB_SEG; ++t) s[t] = src[(size_t)min(seg * GB_SEG + t, hn - 1) * w];
+        };
+        auto chain = [&](float (&s)[GB_SEG], int seg) {
+            const int y0 = seg * GB_SEG;
+            while (__hip_atomic_load(&s_turn[pl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seg) __builtin_amdgcn_s_sleep(1);
+            float acc = seg == 0 ? -0.0f : s_acc[64 * pl + lane];     // -0: the exact additive identity
+#pragma unroll
+            for (int t = 0; t < GB_SEG; ++t) { acc = s[t] + acc; s[t] = acc; }
+            s_acc[64 * pl + lane] = acc;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_store(&s_turn[pl], seg + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            // (the next wave is on the chain already while this one stores)
+            if (lane < nc) {
+#pragma unroll
+                for (int t = 0; t < GB_SEG; ++t)
+                    if (y0 + t < hn) col[(y0 + t) * nc] = s[t];
+            }
+        };
+        constexpr int NG = GB_NW / 2;
+        float sa[GB_SEG], sb[GB_SEG];
+        int seg = wv >> 1;
+        if (seg < nseg) fetch(sa, seg);
+        wg_barrier();                                   // (s_turn; orders LDS only: the loads stay in flight)
+        for (; seg < nseg; seg += 2 * NG) {
+            if (seg + NG < nseg) fetch(sb, seg + NG);
+            chain(sa, seg);
+            if (seg + NG < nseg) {
+                if (seg + 2 * NG < nseg) fetch(sa, seg + 2 * NG);
+                chain(sb, seg + NG);
+            }
+        }
+    }
+    __syncthreads();
+    // (3) thread = (column, row pairs P, P + GB_NT / bw, ..)
+    const int x = c0 + (tid & (bw - 1));
+    if (x >= w) return;
+    auto ld = [&](int pl, int yy, int xx) { return gb_lds[(pl * h + yy) * nc + (xx - cl0)]; };
+    // the strips whose a/b columns hold x, and its comb lane there: x = OWS k - 10 + 19 il + rho
+    const int kq = (x + R + 1) / OWS;
+    int slot[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int k = kq - s, t = x + R + 1 - OWS * k;
+        slot[s] = -1;
+        if (k >= 0 && k < K && t < SWU) {
+            const int il = t / HW, rho = t - HW * il;
+            slot[s] = k * (5 * NI) * CLP + 64 * (rho / CPW) + L * (rho % CPW) + il;
+        }
+    }
+    for (int P = Pb + tid / bw; P < Pe; P += GB_NT / bw) {
+        // the a/b rows 2 P - 9, 2 P - 8 (rows clamped into the image, as k_v5_perm's)
+        const int ya = min(max(2 * P - R, 0), h - 1), yb = min(max(2 * P - R + 1, 0), h - 1);
+        const f2 a = guid_point_at(ld, x, ya, w, h, R, pa.eps);
+        const f2 b = yb == ya ? a : guid_point_at(ld, x, yb, w, h, R, pa.eps);
+        pa.G[v][(size_t)ya * w + x] = a;
+        pa.G[v][(size_t)yb * w + x] = b;
+        if (pa.mean_u8[v]) {
+            pa.mean_u8[v][(size_t)ya * w + x] = mean_to_u8(a.x);
+            pa.mean_u8[v][(size_t)yb * w + x] = mean_to_u8(b.x);
+        }
+        const f4 g = {a.x, a.y, b.x, b.y};
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if (slot[s] >= 0) ((f4*)pa.g1p[v])[(size_t)slot[s] + (size_t)P * CLP] = g;
     }
 }
 
@@ -1184,6 +1313,30 @@ int v5_perm_launch(int nviews, const float* const* S0, const float* const* S1, a
     pa.eps = eps;
     const int K = v5::strips(w), NI = v5::bands(h);
     hipLaunchKernelGGL(v5::k_v5_perm, dim3((unsigned)(K * NI * (v5::BH / 2)), (unsigned)nviews), dim3(v5::CLP), 0, st, pa, w, h, K, NI);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
+int v5_guid_block_launch(int bw, int nviews, const float* const* S0, const float* const* S1, aggdev::f2* const* G,
+                         uint8_t* const* mean_u8, const aggdev::fg_t* const* FG, aggdev::f2* const* g1p, unsigned* const* i2p, int w,
+                         int h, double eps, hipStream_t st) {
+    if (!(bw == 8 || bw == 16 || bw == 32) || v5::guid_block_lds(h, bw) > v5::GB_LDS_MAX)
+        return fail(SMX_E_ARG, "aggregate_fused: a guidance block of %d columns x %d rows does not fit the LDS", bw, h);
+    v5::PermArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    for (int v = 0; v < nviews; ++v) {
+        pa.S0[v] = S0[v]; pa.S1[v] = S1[v]; pa.G[v] = G[v]; pa.mean_u8[v] = mean_u8[v];
+        pa.FG[v] = FG[v]; pa.g1p[v] = g1p[v]; pa.i2p[v] = i2p[v];
+    }
+    pa.eps = eps;
+    const int K = v5::strips(w), NI = v5::bands(h);
+    const int nb = (w + bw - 1) / bw;                                                         // column blocks
+    const int ns = v5::guid_block_split(nb * nviews, 5 * NI);                                 // workgroups per block
+    const int nh = (int)(((int64_t)K * NI * v5::CLP + v5::GB_NT - 1) / v5::GB_NT);            // a (strip, band, lane) per thread
+    static LdsLimitOnce lim;
+    SMX_HIP(lim.ensure((const void*)v5::k_v5_guid_block, (int)v5::GB_LDS_MAX));
+    hipLaunchKernelGGL(v5::k_v5_guid_block, dim3((unsigned)(nb * ns + nh), (unsigned)nviews), dim3(v5::GB_NT), v5::guid_block_lds(h, bw), st,
+                       pa, w, h, K, NI, bw, nb, ns);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }
