@@ -284,7 +284,6 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         int xw = 1;                                                 // window width of this lane's output column
         float rcp_i = 1.0f;                                         // 1 / (19 xw): interior rows
         unsigned vo = OOB;                                          // stage 2: byte offset of the q column in a q row (stage 1: unused)
-        unsigned vg = 0;                                            // byte offset of this lane in a row of the comb-ordered guidance plane
         bool col_ok = false;
         f2 ca_i = {1.0f, 1.0f};                                     // interior rows: (1/area, area)
         uint64_t okmask = 0;                                        // lanes with an output
@@ -299,14 +298,10 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             col_ok = comb_rho() < HW && xo >= 0 && xo < w && (!ST2 || il >= 1);
             xw = col_ok ? min(w - 1, xo + R) - max(-1, xo - R - 1) : 1;
             rcp_i = rcp_s[HW * xw];
-            {
-                const int cl = 64 * (wave - (st2w ? NS1 : 0)) + lane;          // slot in a row of the comb-ordered planes
-                vg = (unsigned)cl * (ST2 ? 4u : 16u);
-                // comb-ordered scratch: 8 rho + (i - 1): the eight outputs of a comb are 32 contiguous bytes.  The LAST strip
-                // is stored in column order instead (19 (i - 1) + rho = the local column), so that what lies outside the image is
-                // one contiguous tail of its rows that the WTA pass never reads.
-                vo = !col_ok ? OOB : (QPERM ? (unsigned)(k + 1 < K ? (L - 1) * comb_rho() + il - 1 : HW * (il - 1) + comb_rho()) * 8u : (unsigned)xo * 4u);
-            }
+            // comb-ordered scratch: 8 rho + (i - 1): the eight outputs of a comb are 32 contiguous bytes.  The LAST strip
+            // is stored in column order instead (19 (i - 1) + rho = the local column), so that what lies outside the image is
+            // one contiguous tail of its rows that the WTA pass never reads.
+            vo = !col_ok ? OOB : (QPERM ? (unsigned)(k + 1 < K ? (L - 1) * comb_rho() + il - 1 : HW * (il - 1) + comb_rho()) * 8u : (unsigned)xo * 4u);
             ca_i = (f2){rcp_i, (float)(HW * xw)};
             okmask = __builtin_amdgcn_ballot_w64(col_ok);
             jw = (comb_rho() < HW && !(pred && comb_il() == 0)) ? jt : SW + (lane & 15);
@@ -520,6 +515,18 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                     cw_finish(ib, dst, std::integral_constant<int, NB>{}, EDGEc, SRCc);
                 }
             };
+            // a band behind the image (the last bands of an item: stage 1 still takes their rows into its column sums): -0 in
+            // every cell, nothing loaded, evaluated or checked
+            if (BH * ib >= h) {
+                char* const dstb = (char*)dst;
+                const f4 nz4 = {-0.0f, -0.0f, -0.0f, -0.0f};
+#pragma unroll
+                for (int r = 0; r < CWN; ++r) {
+                    *(f4*)(dstb + cw_t[r]) = nz4;
+                    *(f4*)(dstb + cw_t[r] + P1 * 4) = nz4;
+                }
+                return;
+            }
             // (versions of the whole band: the interior one has no trace of the edge handling, the cost-volume one none of the
             // cost evaluation)
             const bool edge = xedge || BH * ib + BH > h;
@@ -548,6 +555,8 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             const int ibc = __builtin_amdgcn_readfirstlane(min(max(ib, 0), NI - 1));
             if constexpr (ST2) {
                 // (yq0 = 10 (ib - 1) - 18 at every call site: the band grid of the planes)
+                // (the lane's offset in a row of the plane re-derived from the lane index, as in g1_load)
+                const unsigned vg = (unsigned)(64 * (wave - NS1) + opaque(lane)) * 4u;
                 const u4 a = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(r_fix, (int)(vg * 4u), o_i2p + ibc * (CLP * 16), 0));
                 gI[0] = a.x; gI[1] = a.y; gI[2] = a.z; gI[3] = a.w;
                 gI[4] = ldu(r_fix, vg, o_i2b + ibc * (CLP * 4));
@@ -627,15 +636,21 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         // is not on the path of the division
         // (rows outside the image get SOME valid table index -- their outputs are dropped; few scalar instructions matter here: a
         // border pair that re-derived both its own and the next pair's areas ran 300 cycles longer than an interior one)
-        auto area_ix = [&](int y) {
+        // What travels from pair to pair is the two reciprocals (vector registers) and the two window HEIGHTS (wave-uniform:
+        // scalar registers, nothing re-derived); the area as a float is xw x height again where it is used, two vector
+        // instructions per row.  (With the areas in vector registers too -- two pairs of them live through a pair -- stage 2
+        // spilled once the pairs of a border slot were chosen by branches.)
+        struct RcpPair { f2 r; unsigned h0, h1; };
+        auto win_h = [&](int y) {
             const unsigned yh = min((unsigned)(min(y + R, h - 1) - max(y - R - 1, -1)), (unsigned)HW);
-            return (int)__umul24((unsigned)xw, max(yh, 1u));
+            return max(yh, 1u);
         };
+        auto area_of = [&](unsigned yh) { return (int)__umul24((unsigned)xw, yh); };
         auto rcp_pair = [&](int y) {
-            const int a0 = area_ix(y), a1 = area_ix(y + 1);
-            return (f4){rcp_s[a0], (float)a0, rcp_s[a1], (float)a1};
+            const unsigned h0 = win_h(y), h1 = win_h(y + 1);
+            return RcpPair{(f2){rcp_s[area_of(h0)], rcp_s[area_of(h1)]}, h0, h1};
         };
-        f4 rcb = {1.0f, 1.0f, 1.0f, 1.0f};   // border bands: (1/area, area) of rows a and b of the NEXT row pair
+        RcpPair rcb = {{1.0f, 1.0f}, 1u, 1u};   // border bands: 1/area and window height of rows a and b of the NEXT row pair
 
         // stage-1 role: tile 2 of a band's parity is free once every stage-2 wave has taken the a/b band two bands back out
         // of it (they do that first thing in the slot and count up s_x1); waited for right in front of the first a/b store
@@ -653,7 +668,7 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
         // item's 43 slots -- 8 % of the kernel.)
         auto rows1_pair = [&](auto N0c, auto EDGEc, auto BORDERc, auto WAITc, int i, const float* t1, f2& rv) {
             f2 caa = ca_i, cab = ca_i;
-            f4 rcn = {1.0f, 1.0f, 1.0f, 1.0f};
+            RcpPair rcn = {{1.0f, 1.0f}, 1u, 1u};
             constexpr int N0 = decltype(N0c)::value, T0 = N0 % BH, GS = (N0 / BH + T0 / 2) & 1;
             constexpr bool BORDER = decltype(BORDERc)::value;
             constexpr bool EDGE = decltype(EDGEc)::value || BORDER;   // strip 0 or one with columns outside the image
@@ -662,8 +677,8 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             const f2 rvn = tile_rd(t1 + (T0 + 2 < BH ? T0 + 2 : T0 + 1) * RS + jt);
             const int ya = BH * i - R + T0;            // a/b rows ya, ya + 1
             if constexpr (decltype(BORDERc)::value) {
-                caa = (f2){rcb.x, rcb.y};
-                cab = (f2){rcb.z, rcb.w};
+                caa = (f2){rcb.r.x, (float)area_of(rcb.h0)};
+                cab = (f2){rcb.r.y, (float)area_of(rcb.h1)};
                 rcn = rcp_pair(ya + 2);
             }
             const f2 old_a = ring[S01a];               // (slot S01a == SLb: the top taps of row a are what row b overwrites)
@@ -715,8 +730,30 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             // the pair that takes this ring entry next (the band's last pair leaves that to the end of the slot, behind the
             // hand-in, whose wait for the record -- the compiler makes it a wait for every load in flight -- then finds only
             // the load of the pair before, issued ~500 cycles earlier)
-            if constexpr (T0 != BH - 2) g1_load(5 * i + T0 / 2 + 2, std::integral_constant<int, GS>{});
+            // (a border slot chooses each pair's form by a scalar branch and issues this load behind it: g1_next)
+            if constexpr (T0 != BH - 2 && !BORDER) g1_load(5 * i + T0 / 2 + 2, std::integral_constant<int, GS>{});
             if constexpr (BORDER) rcb = rcn;
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto g1_next = [&](auto N0c, int i) {
+            constexpr int N0 = decltype(N0c)::value, T0 = N0 % BH, GS = (N0 / BH + T0 / 2) & 1;
+            if constexpr (T0 != BH - 2) g1_load(5 * i + T0 / 2 + 2, std::integral_constant<int, GS>{});
+        };
+        // OUTSIDE: both a/b rows of the pair lie outside the image (rows < 0 of an item's first band, rows >= h of its last
+        // ones).  Rows further down read the two column sums as their top taps; the row scan, the copy-out and the hand-off
+        // record read the -0 in tile 2.  Nothing else of the pair is needed: no box, no division, no area look-up (rcb stays
+        // what the slot set it to: the areas of its first pair with a row inside the image).
+        auto rows1_out = [&](auto N0c, auto WAITc, const float* t1, f2& rv) {
+            constexpr int N0 = decltype(N0c)::value, T0 = N0 % BH;
+            constexpr int SLa = N0, SLb = N0 + 1, SLPa = (N0 + RD - 1) % RD;
+            const f2 rvb = tile_rd(t1 + (T0 + 1) * RS + jt);
+            const f2 rvn = tile_rd(t1 + (T0 + 2 < BH ? T0 + 2 : T0 + 1) * RS + jt);
+            ring[SLa] = rv + ring[SLPa];
+            ring[SLb] = rvb + ring[SLa];
+            if constexpr (decltype(WAITc)::value) wait_x1();
+            tile_wr(tile2 + T0 * RS + jw, NZ2);
+            tile_wr(tile2 + (T0 + 1) * RS + jw, NZ2);
+            rv = rvn;
             __builtin_amdgcn_sched_barrier(0);
         };
         // the same for stage 2; one vote on tiny window sums for both rows.  BORDER: per-row window areas, only the q rows
@@ -727,10 +764,10 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
             const int yq = BH * (i - 2) - 2 * R + T0;
             const bool va = !BORDER || (yq >= 0 && yq < h), vb = !BORDER || (yq + 1 >= 0 && yq + 1 < h);
             f2 caa = ca_i, cab = ca_i;
-            f4 rcn = {1.0f, 1.0f, 1.0f, 1.0f};
+            RcpPair rcn = {{1.0f, 1.0f}, 1u, 1u};
             if constexpr (BORDER) {
-                caa = (f2){rcb.x, rcb.y};
-                cab = (f2){rcb.z, rcb.w};
+                caa = (f2){rcb.r.x, (float)area_of(rcb.h0)};
+                cab = (f2){rcb.r.y, (float)area_of(rcb.h1)};
                 rcn = rcp_pair(yq + 2);
             }
             constexpr int SLa = (BH * PAR + T0 + 11) % RD, SLb = (SLa + 1) % RD, SLPa = (SLa + RD - 1) % RD, S01a = SLb, S01b = (SLb + 1) % RD;
@@ -786,6 +823,14 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                 if (vb) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, qvb), r_q, (int)vo, q_row0 + (yq + 1) * q_pitch, AUX_NT);
             }
             if constexpr (BORDER) rcb = rcn;
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // OUTSIDE (see rows1_out): both q rows lie outside the image -- the two column sums and nothing else
+        auto rows2_out = [&](auto N0c) {
+            constexpr int N0 = decltype(N0c)::value, T0 = N0 % BH, PAR = N0 / BH;
+            constexpr int SLa = (BH * PAR + T0 + 11) % RD, SLb = (SLa + 1) % RD, SLPa = (SLa + RD - 1) % RD;
+            ring[SLa] = r2[T0] + ring[SLPa];
+            ring[SLb] = r2[T0 + 1] + ring[SLa];
             __builtin_amdgcn_sched_barrier(0);
         };
 
@@ -866,13 +911,23 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                     __builtin_amdgcn_sched_barrier(0);
 #define V5_P1(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::false_type{}, std::false_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
 #define V5_P1E(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, std::false_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
-#define V5_P1B(TT) rows1_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, std::true_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv);
-                    if (border) { rcb = rcp_pair(BH * sl - R); V5_P1B(0) V5_STAMP(6); V5_P1B(2) V5_STAMP(7); V5_P1B(4) V5_STAMP(8); V5_P1B(6) V5_STAMP(9); V5_P1B(8) V5_STAMP(10); }
+                    // a border slot: pairs with both a/b rows outside the image take the OUTSIDE form, by a scalar branch around
+                    // the whole pair (the rows of the slot are wave-uniform); the pairs with a row inside the image are one run, and
+                    // its first pair finds its areas in rcb (a/b rows of a pair: odd, even -- the first pair with a row >= 0 is (-1, 0))
+#define V5_P1X(TT) { constexpr auto N0c = std::integral_constant<int, BH * PAR + TT>{}; \
+                     if (ya0 + TT + 1 < 0 || ya0 + TT >= h) rows1_out(N0c, std::integral_constant<bool, TT == 0>{}, t1, rv); \
+                     else rows1_pair(N0c, std::true_type{}, std::true_type{}, std::integral_constant<bool, TT == 0>{}, sl, t1, rv); \
+                     g1_next(N0c, sl); }
+                    if (border) {
+                        const int ya0 = BH * sl - R;
+                        rcb = rcp_pair(max(ya0, -1));
+                        V5_P1X(0) V5_STAMP(6); V5_P1X(2) V5_STAMP(7); V5_P1X(4) V5_STAMP(8); V5_P1X(6) V5_STAMP(9); V5_P1X(8) V5_STAMP(10);
+                    }
                     else if (xedge || k == 0) { V5_P1E(0) V5_P1E(2) V5_P1E(4) V5_P1E(6) V5_P1E(8) }
                     else { V5_MARK("s1rows begin"); V5_P1(0) V5_STAMP(6); V5_P1(2) V5_STAMP(7); V5_P1(4) V5_STAMP(8); V5_P1(6) V5_STAMP(9); V5_P1(8) V5_STAMP(10); V5_MARK("s1rows end"); }
 #undef V5_P1
 #undef V5_P1E
-#undef V5_P1B
+#undef V5_P1X
                     __builtin_amdgcn_s_setprio(0);
                     V5_STAMP(11);
                 }
@@ -928,11 +983,14 @@ __global__ __launch_bounds__(NT, WPE) void k_v5_walk(Args A) {
                     s2_interior = !border && sl != q_last;
                     __builtin_amdgcn_sched_barrier(0);
 #define V5_P2(TT) rows2_pair(std::integral_constant<int, BH * PAR + TT>{}, std::false_type{}, sl);
-#define V5_P2B(TT) rows2_pair(std::integral_constant<int, BH * PAR + TT>{}, std::true_type{}, sl);
-                    if (border) { rcb = rcp_pair(yq0); V5_P2B(0) V5_STAMP(6); V5_P2B(2) V5_STAMP(7); V5_P2B(4) V5_STAMP(8); V5_P2B(6) V5_STAMP(9); V5_P2B(8) V5_STAMP(10); }
+                    // (as in slot_s1: pairs with both q rows outside the image take the OUTSIDE form -- all five in local slot 2; the
+                    // q rows of a pair are even, odd, so the first pair with a row >= 0 is (0, 1))
+#define V5_P2X(TT) { constexpr auto N0c = std::integral_constant<int, BH * PAR + TT>{}; \
+                     if (yq0 + TT + 1 < 0 || yq0 + TT >= h) rows2_out(N0c); else rows2_pair(N0c, std::true_type{}, sl); }
+                    if (border) { rcb = rcp_pair(max(yq0, 0)); V5_P2X(0) V5_STAMP(6); V5_P2X(2) V5_STAMP(7); V5_P2X(4) V5_STAMP(8); V5_P2X(6) V5_STAMP(9); V5_P2X(8) V5_STAMP(10); }
                     else { V5_MARK("s2rows begin"); V5_P2(0) V5_STAMP(6); V5_P2(2) V5_STAMP(7); V5_P2(4) V5_STAMP(8); V5_P2(6) V5_STAMP(9); V5_P2(8) V5_STAMP(10); V5_MARK("s2rows end"); }
 #undef V5_P2
-#undef V5_P2B
+#undef V5_P2X
                 }
                 issue_guid(sl, BH * (sl - 1) - 2 * R);
                 // the record stored above is complete in memory before the barrier behind which it is published

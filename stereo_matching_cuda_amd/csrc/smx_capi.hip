@@ -135,7 +135,7 @@ void smx_default_params(smx_params* p) {
 
 const char* smx_last_error(void) { return g_err.c_str(); }
 
-const char* smx_version(void) { return "smx-hip gfx950 0.11 (sub-pixel disparity from the winner's neighbouring costs: smx_dev_subpixel_pair; weighted-median refinement of the filled map: smx_weighted_median; comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker; WTA winner in the float domain; guidance in two launches where a column block's integral images fit the LDS, else three; two 512-thread workgroups per CU)"; }
+const char* smx_version(void) { return "smx-hip gfx950 0.11 (sub-pixel disparity from the winner's neighbouring costs: smx_dev_subpixel_pair; weighted-median refinement of the filled map: smx_weighted_median; comb walker: items pipelined across tickets, q scratch in row pairs, cost volumes on the comb walker, row pairs outside the image reduced to their column sums; WTA winner in the float domain; guidance in two launches where a column block's integral images fit the LDS, else three; two 512-thread workgroups per CU)"; }
 
 int smx_device_count(void) {
     int n = 0;

@@ -154,12 +154,16 @@ static void run_strip(int k, int K, int NI, const std::vector<Rec>* rin, std::ve
                     const f2 rv = tile1[t * SW + lane_j(lane)];
                     l1[lane].ring[slot] = f2{rv.x + l1[lane].ring[slotp].x, rv.y + l1[lane].ring[slotp].y};
                 }
-                std::vector<f2> u(SW);
-                for (int lane = 0; lane < SW; ++lane) u[lane] = box(l1, lane, slot, slot01, k == 0);   // ... then the taps
+                // an a/b row outside the image takes the column sums above and nothing else: no box, no division, -0 into
+                // tile 2 (the kernel's OUTSIDE form of a row pair, rows1_out; it decides per pair, the data flow is per row)
+                const bool row_in = y1 - R >= 0 && y1 - R < h;
+                std::vector<f2> u(SW, f2{NAN, NAN});
+                if (row_in)
+                    for (int lane = 0; lane < SW; ++lane) u[lane] = box(l1, lane, slot, slot01, k == 0);   // ... then the taps
                 for (int lane = 0; lane < SW; ++lane) {
                     const int y = y1 - R, x = base1 + lane_j(lane) - R;
                     f2 ab{NZ, NZ};
-                    if (y >= 0 && y < h && x >= 0 && x < w) {
+                    if (row_in && x >= 0 && x < w) {
                         const int ar = area_of(x, y);
                         const float mp = fastdiv(u[lane].x, (float)ar, rcp_area(ar));
                         const float mIp = fastdiv(u[lane].y, (float)ar, rcp_area(ar));
@@ -180,12 +184,15 @@ static void run_strip(int k, int K, int NI, const std::vector<Rec>* rin, std::ve
                     const f2 rv = tile2[t * SW + lane_j(lane)];
                     l2[lane].ring[slot] = f2{rv.x + l2[lane].ring[slotp].x, rv.y + l2[lane].ring[slotp].y};
                 }
-                std::vector<f2> u(SW);
-                for (int lane = 0; lane < SW; ++lane) u[lane] = box(l2, lane, slot, slot01, false);
+                // (a q row outside the image: the column sums only, rows2_out)
+                const bool row_in = y2 - R >= 0 && y2 - R < h;
+                std::vector<f2> u(SW, f2{NAN, NAN});
+                if (row_in)
+                    for (int lane = 0; lane < SW; ++lane) u[lane] = box(l2, lane, slot, slot01, false);
                 for (int lane = 0; lane < SW; ++lane) {
                     const int il = lane % L;
                     const int y = y2 - R, x = base2 + lane_j(lane) - R;
-                    if (il >= 1 && y >= 0 && y < h && x >= 0 && x < w) {
+                    if (il >= 1 && row_in && x >= 0 && x < w) {
                         const int ar = area_of(x, y);
                         const float ma = fastdiv(u[lane].x, (float)ar, rcp_area(ar));
                         const float mb = fastdiv(u[lane].y, (float)ar, rcp_area(ar));
@@ -246,8 +253,13 @@ static int check(int w, int h, int d, unsigned seed) {
     return bad ? 1 : 0;
 }
 
-int main() {
+// without arguments: the shapes below; with arguments `w h [w h ...]`: those shapes (tests/test_rows_outside_model.py)
+int main(int argc, char** argv) {
     int rc = 0;
+    if (argc > 1) {
+        for (int a = 1; a + 1 < argc; a += 2) rc |= check(atoi(argv[a]), atoi(argv[a + 1]), -3, 1234u + (unsigned)atoi(argv[a]));
+        return rc;
+    }
     const int shapes[][2] = {{384, 288}, {285, 40}, {286, 41}, {284, 39}, {570, 25}, {571, 10}, {600, 9}, {40, 30},
                              {19, 19}, {10, 10}, {1, 1}, {3, 50}, {1242, 375}, {865, 61}, {300, 20}, {295, 11}};
     for (auto& s : shapes) rc |= check(s[0], s[1], -3, 1234u + s[0]);
