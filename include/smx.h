@@ -1080,6 +1080,117 @@ int smx_ctx_set_cross_scale(smx_ctx* ctx, const smx_cscale_params* p);
  * their buffers.  0 and 0 for a context whose pairs never ran with cross-scale on. */
 int smx_ctx_cscale_held(const smx_ctx* ctx, int* levels, size_t* bytes);
 
+/* ------------------------------------------------------------------------------------
+ * PatchMatch stereo: slanted support windows (Bleyer, Rhemann, Rother, BMVC 2011; not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* Every other matcher here scores one integer label per pixel over a fronto-parallel window.  On a slanted surface that window
+ * mixes several disparities: the winner is biased and the sub-pixel fit moves it by at most half a label.  PatchMatch stereo
+ * gives each pixel a disparity PLANE (a, b, d0), scores it with the reference's truncated absolute difference plus gradient
+ * summed over an adaptive-weight window that lies in the plane, and searches the planes by random initialisation, propagation
+ * and refinement.  There is no cost volume: memory does not grow with size_d.  tests/patchmatch_ref.py is this definition in
+ * numpy; every output equals it bit for bit, in every run and whatever the launch geometry.
+ *
+ * Arithmetic.  IEEE f32, every operation rounded on its own in the order written here, nothing contracted; no transcendental,
+ * square root or division on the device.  alpha, th_color and th_grad come from smx_params as in the cost volume (oma = 1 -
+ * alpha, border = oma * th_color + alpha * th_grad, all f32).
+ *
+ * Views.  View v (0 left, 1 right) has the labels dmin_v .. dmax_v = dmin_v + size_d - 1; pixel (x, y) with disparity d
+ * matches x + d in the other view.  A pixel's state is its plane (a, b, d0) and the plane's cost m.  The plane's disparity at
+ * (x + dx, y + dy) is (d0 + a * (float)dx) + b * (float)dy: d0 is the disparity at the pixel itself.
+ *
+ * Matching cost rho of a tap q = (qx, qy) under disparity d.  I, G: gray and x gradient of the tap's view, Io, Go of the other
+ * view, as f32; the gradient is the cost volume's (I[x-1] - I[x+1]) / 2, one-sided at both row ends, and 0 in an image one
+ * column wide.  xs = (float)qx + d.  Unless dmin <= d <= dmax and 0 <= xs <= w - 1 (a NaN fails), rho = border.  Otherwise
+ * i = floor(xs), t = xs - i, i1 = min(i + 1, w - 1), I' = Io[i] + t * (Io[i1] - Io[i]), G' likewise on Go, and
+ * rho = oma * min(|I_q - I'|, th_color) + alpha * min(|G_q - G'|, th_grad), min(v, th) being v < th ? v : th.  For an integer d
+ * this is the cell of the reference's cost volume, bit for bit.
+ *
+ * Plane cost.  m(p, f) = sum over the taps q of the (2 radius + 1)^2 window of tab[|I_p - I_q|] * rho(q, f(q)), with
+ * tab[k] = (float)exp(-k / gamma), k = 0 .. 255, computed on the host in double (smx_pm_weights).  Taps outside the image are
+ * skipped.  ORDER: one accumulator from +0, rows dy = -radius .. radius, in a row dx = -radius .. radius; each product rounded,
+ * then added.
+ *
+ * Random numbers.  hash(seed, view, pixel, draw) = fmix32(fmix32(fmix32(seed + 0x9E3779B9 * (view + 1)) ^ pixel) ^ draw) with
+ * fmix32 the 32-bit finaliser of MurmurHash3 (Appleby): h ^= h >> 16, h *= 0x85EBCA6B, h ^= h >> 13, h *= 0xC2B2AE35,
+ * h ^= h >> 16; pixel = y * w + x.  U = (float)(hash >> 8) * 2^-24, in [0, 1).  smx_pm_hash is the host copy.  Draws 0, 1, 2
+ * initialise d0, a, b; step k of the refinement of iteration `it` draws 3 + 3 * (32 * it + k) + {0, 1, 2} for d0, a, b.
+ *
+ * Search.
+ *   1. Init, every pixel: d0 = dmin + U * (float)(size_d - 1), a = (2 U - 1) * max_slope, b likewise; m = its cost.
+ *   2. For it = 0 .. iterations - 1:
+ *      a. Red-black: a pixel's colour is (x + y) & 1.  The pass over colour it & 1 runs first, then the other colour; only
+ *         the pixels of the pass's colour change.  The two views do not read each other in a pass.
+ *      b. Spatial propagation.  Candidates: the planes of the pixels at (dx, dy) = (-1,0) (1,0) (0,-1) (0,1) (-5,0) (5,0)
+ *         (0,-5) (0,5), in this order; all have the other colour.  A candidate (a_n, b_n, d0_n) of neighbour (nx, ny) is
+ *         re-centred: d0' = (d0_n + a_n * (float)(x - nx)) + b_n * (float)(y - ny), slopes unchanged.  A neighbour outside the
+ *         image gives none, nor does a d0' outside [dmin, dmax].  In order, a candidate whose cost is strictly lower than the
+ *         pixel's current cost replaces plane and cost.
+ *      c. Refinement.  dd = (float)(size_d - 1) * 0.5, ds = max_slope * 0.5.  While dd >= 0.1: d0' = clamp(d0 + (2 U - 1) * dd,
+ *         dmin, dmax), a' = clamp(a + (2 U - 1) * ds, -max_slope, max_slope), b' likewise (clamp(v, lo, hi) = v < lo ? lo : v > hi ?
+ *         hi : v, so a zero keeps its sign); adopted if strictly lower; then both halve.  A step perturbs what the step before left.  size_d 1: no step.
+ *      d. View propagation, after both colours, left then right, both reading the other view's planes as they were before
+ *         either changed: for pixel (x, y) with x' = clamp((int)floor(((float)x + d0) + 0.5), 0, w - 1) the candidate is
+ *         (-a', -b', -d0') of the other view's pixel (x', y).  This sign-flipped plane is a simplification of the exact
+ *         transform (which re-centres by x - x' - d0' and rescales the slopes by 1 / (1 + a')): the cost test decides.  No
+ *         candidate where -d0' lies outside [dmin, dmax]; adopted if strictly lower.
+ *   3. Outputs per view: the planes [3][h][w] (a, b, d0), m, disp = d0, label = clamp(floor(d0 + 0.5), dmin, dmax) as f32.
+ *
+ * Defaults: radius 8, gamma 10, iterations 4, max_slope 2, seed 0 -- a starting point, not measured on real data.  Valid:
+ * 0 <= radius <= 17, gamma finite and > 0, 1 <= iterations <= 16, 0 <= max_slope <= 8, w, h >= 1, w < 2^24, w*h < 2^31,
+ * 1 <= size_d <= 2^20, |dminl|, |dminr| <= 2^20; anything else is SMX_E_ARG before any device call.
+ *
+ * smx_dev_patchmatch_pair: device pointers, gray u8 views [h][w]; 3 + 4 * iterations launches and `iterations` device-to-device
+ * copies on `stream`; no allocation, no synchronisation (graph-capturable).  Layouts, the left view first:
+ *   d_planes OUT f32 [2][3][h][w]     d_cost, d_disp, d_label OUT f32 [2][h][w]
+ * Nothing is written outside them and [0, smx_pm_workspace_bytes(w, h)) of d_ws (0 for an invalid w, h); the workspace may hold
+ * anything and needs no alignment; a smaller one is SMX_E_WS before any launch.  No two buffers may overlap.
+ * smx_dev_pm_plane_cost: the costs m of GIVEN planes of both views (d_planes IN, d_cost OUT), no search, two launches: scores
+ * any plane map, such as a ground truth or another matcher's (0, 0, label).  A plane with a NaN or an infinity costs the border
+ * constant at the taps where its disparity is not a number in range.
+ * smx_patchmatch, smx_pm_plane_cost: host pointers, synchronous. */
+typedef struct smx_pm_params { int radius; double gamma; int iterations; double max_slope; uint32_t seed; } smx_pm_params;
+void smx_default_pm_params(smx_pm_params* p);
+int smx_pm_weights(const smx_pm_params* p, float* tab /* [256] */);
+uint32_t smx_pm_hash(uint32_t seed, uint32_t view, uint32_t pixel, uint32_t draw);
+size_t smx_pm_workspace_bytes(int w, int h);
+int smx_dev_patchmatch_pair(const smx_params* p, const smx_pm_params* pm, const uint8_t* d_left, const uint8_t* d_right, int w,
+                            int h, int size_d, int dminl, int dminr, float* d_planes, float* d_cost, float* d_disp,
+                            float* d_label, void* d_ws, size_t ws_bytes, void* stream);
+int smx_dev_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uint8_t* d_left, const uint8_t* d_right, int w, int h,
+                          int size_d, int dminl, int dminr, const float* d_planes, float* d_cost, void* d_ws, size_t ws_bytes,
+                          void* stream);
+int smx_patchmatch(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h, int size_d,
+                   int dminl, int dminr, float* planes, float* cost, float* disp, float* label);
+int smx_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h,
+                      int size_d, int dminl, int dminr, const float* planes, float* cost);
+/* The fractional filled map of a pair that ran PatchMatch, by the rule of smx_dev_subpixel_pair: d_out = d_disp (the left view's
+ * disp) where d_kept -- the LR-checked left map, or the last map of the outlier stages -- passes fill_occlusion's validity
+ * test, d_filled elsewhere.  One launch; n floats each; d_out may be none of the inputs. */
+int smx_dev_pm_sub_filled(const float* d_disp, const float* d_kept, const float* d_filled, int w, int h, int dminl, float* d_out,
+                          void* stream);
+/* Test hook, NOT part of the stable contract: the pixels a workgroup of the search kernels takes (columns, rows; in the
+ * red-black pass the columns are pixels of one colour). */
+int smx_pm_geometry(int* cols, int* rows);
+/* PatchMatch stereo of this context.  NULL switches it off (the default: nothing is allocated or launched).  While it is on,
+ * smx_ctx_stereo_pair / _rgb (the gray images of the colour pair) runs smx_dev_patchmatch_pair in place of cost, aggregation
+ * and winner-take-all: out->dmap_l / dmap_r are the labels and out->best_l / best_r the plane costs.  The LR check and the fill
+ * of the reference run on the labels, speckle removal and region voting behind them unchanged.  smx_ctx_patchmatch_maps copies
+ * out what the last pair left (SMX_E_ARG if it ran without PatchMatch; any pointer may be NULL): the planes [3][h][w] of either
+ * view, sub_l / sub_r = disp, and sub_filled, which follows smx_dev_subpixel_pair's rule: disp where the LR check (and the
+ * outlier stages) kept the pixel, the filled label elsewhere.  It is the map for the weighted median, as the sub-pixel fit's
+ * filled map is.
+ * There is no cost volume, so the stages that read one are refused, and some combinations are deliberately out of scope: the
+ * pair call returns SMX_E_ARG with a message for the census and AD-Census costs, colour guidance, SGM, cross-based aggregation,
+ * the scan-line optimiser, cross-scale aggregation, the depth-discontinuity adjustment, the uniqueness test, a non-zero
+ * smx_ctx_set_subpixel mode and for out->cost_*, agg_* or mean_*; smx_ctx_stereo_pair_async returns it while the setting is on.
+ * The sharded and multi-GPU drivers do not take it.  The buffers are allocated by the first pair that runs with it on. */
+int smx_ctx_set_patchmatch(smx_ctx* ctx, const smx_pm_params* p);
+int smx_ctx_patchmatch_maps(smx_ctx* ctx, float* planes_l, float* planes_r, float* sub_l, float* sub_r, float* sub_filled);
+/* Test hook, NOT part of the stable contract: the device bytes the context holds for PatchMatch stereo (planes, disp and
+ * workspace).  0 for a context whose pairs never ran with it on. */
+int smx_ctx_pm_held(const smx_ctx* ctx, size_t* bytes);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

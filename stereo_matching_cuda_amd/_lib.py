@@ -87,6 +87,12 @@ class CScaleParams(C.Structure):
     _fields_ = [("scales", C.c_int), ("lambda_", C.c_double)]
 
 
+class PMParams(C.Structure):
+    """smx_pm_params: PatchMatch stereo, a disparity plane per pixel (not a stage of the reference)."""
+    _fields_ = [("radius", C.c_int), ("gamma", C.c_double), ("iterations", C.c_int), ("max_slope", C.c_double),
+                ("seed", C.c_uint32)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -117,6 +123,7 @@ _GP = C.POINTER(SgmParams)
 _XP = C.POINTER(CrossParams)
 _VP = C.POINTER(VoteParams)
 _LP = C.POINTER(ScanlineParams)
+_MP = C.POINTER(PMParams)
 _JP = C.POINTER(AdjustParams)
 _KP = C.POINTER(CScaleParams)
 _ip = C.POINTER(C.c_int)
@@ -250,6 +257,19 @@ SIGNATURES = {
     "smx_pyr_down_geometry": (_i, [_ip, _ip]),
     "smx_ctx_set_cross_scale": (_i, [_vp, _KP]),
     "smx_ctx_cscale_held": (_i, [_vp, _ip, C.POINTER(_sz)]),
+    "smx_default_pm_params": (None, [_MP]),
+    "smx_pm_weights": (_i, [_MP, _vp]),
+    "smx_pm_hash": (_u32, [_u32, _u32, _u32, _u32]),
+    "smx_pm_workspace_bytes": (_sz, [_i, _i]),
+    "smx_dev_patchmatch_pair": (_i, [_PP, _MP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_dev_pm_plane_cost": (_i, [_PP, _MP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "smx_patchmatch": (_i, [_PP, _MP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "smx_pm_plane_cost": (_i, [_PP, _MP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "smx_pm_geometry": (_i, [_ip, _ip]),
+    "smx_dev_pm_sub_filled": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "smx_ctx_set_patchmatch": (_i, [_vp, _MP]),
+    "smx_ctx_patchmatch_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "smx_ctx_pm_held": (_i, [_vp, C.POINTER(_sz)]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -376,6 +396,24 @@ def default_cscale_params():
     p = CScaleParams()
     lib().smx_default_cscale_params(C.byref(p))
     return p
+
+
+def default_pm_params():
+    p = PMParams()
+    lib().smx_default_pm_params(C.byref(p))
+    return p
+
+
+def pm_weights(params):
+    """The 256 adaptive weights exp(-k / gamma) of PatchMatch stereo (smx_pm_weights) as a list of floats."""
+    tab = (C.c_float * 256)()
+    check(lib().smx_pm_weights(C.byref(params), tab))
+    return list(tab)
+
+
+def pm_hash(seed, view, pixel, draw):
+    """The counter-based hash behind PatchMatch stereo's random numbers (smx_pm_hash)."""
+    return int(lib().smx_pm_hash(int(seed) & 0xFFFFFFFF, int(view), int(pixel), int(draw)))
 
 
 def cscale_level(w, h, dmin, size_d, s):

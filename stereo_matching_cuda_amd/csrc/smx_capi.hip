@@ -881,6 +881,61 @@ int smx_dev_cscale_wta_pair(const smx_cscale_params* p, const float* const* d_ag
     return launch_cscale_wta_pair(p, d_agg_l, d_agg_r, w, h, dminl, dminr, size_d, d_keys, d_out, d_nbr, d_uq, (hipStream_t)stream);
 }
 
+// ---- PatchMatch stereo (not in the reference; smx_patchmatch.hip) --------------------------------------------------------
+void smx_default_pm_params(smx_pm_params* p) {
+    if (!p) return;
+    p->radius = 8; p->gamma = 10.0; p->iterations = 4; p->max_slope = 2.0; p->seed = 0;
+}
+
+int smx_pm_weights(const smx_pm_params* p, float* tab) {
+    if (!pm_params_ok(p)) return fail(SMX_E_ARG, "smx_pm_weights: %s", PM_RANGES);
+    SMX_ARG(tab != nullptr);
+    pm_weights(p, tab);
+    return SMX_OK;
+}
+
+uint32_t smx_pm_hash(uint32_t seed, uint32_t view, uint32_t pixel, uint32_t draw) { return pm_hash_host(seed, view, pixel, draw); }
+
+size_t smx_pm_workspace_bytes(int w, int h) { return pm_shape_ok(w, h, 1, 0, 0) ? pm_workspace_bytes(w, h) : 0; }
+
+int smx_pm_geometry(int* cols, int* rows) {
+    SMX_ARG(cols && rows);
+    pm_tile(cols, rows);
+    return SMX_OK;
+}
+
+int smx_dev_patchmatch_pair(const smx_params* p, const smx_pm_params* pm, const uint8_t* d_left, const uint8_t* d_right, int w,
+                            int h, int size_d, int dminl, int dminr, float* d_planes, float* d_cost, float* d_disp,
+                            float* d_label, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!pm_params_ok(pm)) return fail(SMX_E_ARG, "smx_dev_patchmatch_pair: %s", PM_RANGES);
+    if (!pm_shape_ok(w, h, size_d, dminl, dminr)) return fail(SMX_E_ARG, "smx_dev_patchmatch_pair: %s", PM_SHAPES);
+    SMX_ARG(p && d_left && d_right && d_planes && d_cost && d_disp && d_label);
+    if (!d_ws || ws_bytes < pm_workspace_bytes(w, h))
+        return fail(SMX_E_WS, "smx_dev_patchmatch_pair: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
+                    pm_workspace_bytes(w, h));
+    return launch_patchmatch_pair(p, pm, d_left, d_right, w, h, size_d, dminl, dminr, d_planes, d_cost, d_disp, d_label, d_ws,
+                                  (hipStream_t)stream);
+}
+
+int smx_dev_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uint8_t* d_left, const uint8_t* d_right, int w, int h,
+                          int size_d, int dminl, int dminr, const float* d_planes, float* d_cost, void* d_ws, size_t ws_bytes,
+                          void* stream) {
+    if (!pm_params_ok(pm)) return fail(SMX_E_ARG, "smx_dev_pm_plane_cost: %s", PM_RANGES);
+    if (!pm_shape_ok(w, h, size_d, dminl, dminr)) return fail(SMX_E_ARG, "smx_dev_pm_plane_cost: %s", PM_SHAPES);
+    SMX_ARG(p && d_left && d_right && d_planes && d_cost);
+    if (!d_ws || ws_bytes < pm_workspace_bytes(w, h))
+        return fail(SMX_E_WS, "smx_dev_pm_plane_cost: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
+                    pm_workspace_bytes(w, h));
+    return launch_pm_plane_cost(p, pm, d_left, d_right, w, h, size_d, dminl, dminr, d_planes, d_cost, d_ws, (hipStream_t)stream);
+}
+
+int smx_dev_pm_sub_filled(const float* d_disp, const float* d_kept, const float* d_filled, int w, int h, int dminl, float* d_out,
+                          void* stream) {
+    if (!pm_shape_ok(w, h, 1, dminl, 0)) return fail(SMX_E_ARG, "smx_dev_pm_sub_filled: %s", PM_SHAPES);
+    SMX_ARG(d_disp && d_kept && d_filled && d_out);
+    return launch_pm_sub_filled(d_disp, d_kept, d_filled, (size_t)w * h, dminl, d_out, (hipStream_t)stream);
+}
+
 // Test hook (not in include/smx.h): the natural-order winner-take-all pass of the aggregations (wta_launch, smx_wta.h) over one
 // materialised volume d_q [count][h][w], fresh keys out -- what tests/test_gpu_cscale.py holds the one-scale combination to.
 __attribute__((visibility("default"))) int smx_debug_wta_natural(const float* d_q, int w, int h, int count, int64_t* d_keys,

@@ -73,6 +73,12 @@ struct smx_ctx {
     smx_cscale_params cs_params;
     smx_ctx* cs_child[SMX_CSCALE_MAX_SCALES] = {};
     bool owns_st = true;
+    // PatchMatch stereo (smx_ctx_set_patchmatch): it takes the place of cost and aggregation.  The planes [2][3][h][w], disp
+    // [2][h][w] and the search's workspace; its sub-pixel filled map lies in subf
+    bool pm = false;
+    bool pm_valid = false;      // the maps belong to the last synchronous pair
+    smx_pm_params pm_params;
+    DevBuf pm_planes, pm_disp, pm_ws;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -110,8 +116,8 @@ struct smx_ctx {
 // census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
 // device (best / map / mean: left view first, right view behind it).
 // cscale: the winners come from the cross-scale combination; level: this pair is a level of another context's pyramid, which
-// wants its aggregated volumes and nothing behind them.
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level; };
+// wants its aggregated volumes and nothing behind them.  pm: PatchMatch stereo in place of cost, aggregation and winners.
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm; };
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -143,6 +149,12 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
         SMX_HIP(c->vote_ws.ensure(vote_workspace_bytes(c->w, c->h)));
     }
     if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
+    if (need.pm) {
+        SMX_HIP(c->pm_planes.ensure(6 * fb));
+        SMX_HIP(c->pm_disp.ensure(2 * fb));
+        SMX_HIP(c->pm_ws.ensure(pm_workspace_bytes(c->w, c->h)));
+        SMX_HIP(c->subf.ensure(fb));
+    }
     // The chunk of ctx_aggregate_chunks.  Colour guide and cross: the halving rule on their workspace.  The guided flow from
     // census codes: every slice with whole volumes, else what fits 1 GiB of cost slices exactly (at least one).  Then the
     // calling thread's smx_set_max_slices_per_launch bounds it, like the chunks inside every entry.
@@ -229,8 +241,75 @@ static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& cal
     return SMX_OK;
 }
 
+// The stages between the LR check and the sub-pixel maps: uniqueness, speckle removal, region voting, each followed by a fill
+// that starts over from its map.  *kept: the map whose validity test says which pixels the fill replaced.
+static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out, const int64_t* keysL,
+                              const float* uqL, const float** kept_out) {
+    const smx_params* p = &c->p;
+    const int w = c->w, h = c->h, size_d = c->size_d;
+    const size_t n = c->n;
+    hipStream_t st = c->st;
+    int rc;
+    const float* kept = out.occ;
+    if (need.uniq) {
+        // the ambiguous winners of the LR-checked left map join the invalidated pixels; the fill starts over from that map
+        // (unless speckle removal follows, which does it)
+        float* um = c->uq_map.as<float>();
+        if ((rc = smx_dev_uniqueness(c->uniq, keysL, uqL, out.occ, um, c->uq_margin.as<float>(), w, h, (float)in.dminl,
+                                     (float)(in.dminl - 100), st)))
+            return rc;
+        if (!need.speckle && (rc = launch_fill_occlusion(um, out.fil, w, h, (float)in.dminl, st))) return rc;
+        kept = um;
+    }
+    if (need.speckle) {
+        // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
+        float* spk = c->spk.as<float>();
+        if ((rc = smx_dev_speckle_filter(&c->spk_params, kept, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
+                                         c->spk_ws.p, speckle_workspace_bytes(w, h), st)))
+            return rc;
+        if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
+        kept = spk;
+    }
+    if (need.vote) {
+        // the outliers of that map take the vote of their cross regions on the left guide, then the 16-direction interpolation;
+        // the fill starts over from the voted map, and `kept` stays the map whose validity test the later stages read
+        const uint8_t* guide = in.channels ? in.rgb_l : in.left;
+        const int ch = in.channels ? in.channels : 1;
+        uint32_t* arms = c->varms.as<uint32_t>();
+        float* voted = c->voted.as<float>();
+        if ((rc = smx_dev_cross_arms(&c->vote_arms, guide, nullptr, ch, w, h, arms, st))) return rc;
+        if ((rc = smx_dev_region_vote(&c->vote_params, arms, guide, ch, kept, out.map + n, voted, w, h, in.dminl, size_d, p->d_lr,
+                                      c->vote_ws.p, vote_workspace_bytes(w, h), st)))
+            return rc;
+        if ((rc = launch_fill_occlusion(voted, out.fil, w, h, (float)in.dminl, st))) return rc;
+    }
+    *kept_out = kept;
+    return SMX_OK;
+}
+
+// A PatchMatch pair: the search gives both views' labels (dmap) and plane costs (best) directly; the LR check and the fill of
+// main.cu:140-155 run on the labels, the outlier stages behind them unchanged, and the sub-pixel filled map is the left disp
+// where the pixel was kept, the filled label elsewhere (the rule of smx_dev_subpixel_pair).
+static int ctx_enqueue_pm(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
+    const int w = c->w, h = c->h;
+    const size_t n = c->n;
+    hipStream_t st = c->st;
+    int rc;
+    float* disp = c->pm_disp.as<float>();
+    if ((rc = smx_dev_patchmatch_pair(&c->p, &c->pm_params, in.left, in.right, w, h, c->size_d, in.dminl, in.dminr,
+                                      c->pm_planes.as<float>(), out.best, disp, out.map, c->pm_ws.p, pm_workspace_bytes(w, h), st)))
+        return rc;
+    SMX_HIP(hipMemcpyAsync(out.occ, out.map, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_detect_occlusion(&c->p, out.occ, out.map + n, in.dminl - 100, w, h, st))) return rc;
+    if ((rc = launch_fill_occlusion(out.occ, out.fil, w, h, (float)in.dminl, st))) return rc;
+    const float* kept = nullptr;
+    if ((rc = ctx_outlier_stages(c, in, need, out, nullptr, nullptr, &kept))) return rc;
+    return launch_pm_sub_filled(disp, kept, out.fil, n, in.dminl, c->subf.as<float>(), st);
+}
+
 // The path of one pair on the context's stream: device images in, the eight result planes (+ the context's volumes) out.
 static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
+    if (need.pm) return ctx_enqueue_pm(c, in, need, out);
     const smx_params* p = &c->p;
     const int w = c->w, h = c->h, size_d = c->size_d;
     const size_t n = c->n;
@@ -306,39 +385,8 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     if ((rc = smx_dev_finish_pair(p, keysL, w, h, in.dminl, in.dminr, in.dminl - 100, (float)in.dminl, out.best, out.map,
                                   out.occ, out.fil, st)))
         return rc;
-    const float* kept = out.occ;    // the map whose validity test says which pixels the fill replaced
-    if (need.uniq) {
-        // the ambiguous winners of the LR-checked left map join the invalidated pixels; the fill starts over from that map
-        // (unless speckle removal follows, which does it)
-        float* um = c->uq_map.as<float>();
-        if ((rc = smx_dev_uniqueness(c->uniq, keysL, uqL, out.occ, um, c->uq_margin.as<float>(), w, h, (float)in.dminl,
-                                     (float)(in.dminl - 100), st)))
-            return rc;
-        if (!need.speckle && (rc = launch_fill_occlusion(um, out.fil, w, h, (float)in.dminl, st))) return rc;
-        kept = um;
-    }
-    if (need.speckle) {
-        // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
-        float* spk = c->spk.as<float>();
-        if ((rc = smx_dev_speckle_filter(&c->spk_params, kept, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
-                                         c->spk_ws.p, speckle_workspace_bytes(w, h), st)))
-            return rc;
-        if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
-        kept = spk;
-    }
-    if (need.vote) {
-        // the outliers of that map take the vote of their cross regions on the left guide, then the 16-direction interpolation;
-        // the fill starts over from the voted map, and `kept` stays the map whose validity test the later stages read
-        const uint8_t* guide = in.channels ? in.rgb_l : in.left;
-        const int ch = in.channels ? in.channels : 1;
-        uint32_t* arms = c->varms.as<uint32_t>();
-        float* voted = c->voted.as<float>();
-        if ((rc = smx_dev_cross_arms(&c->vote_arms, guide, nullptr, ch, w, h, arms, st))) return rc;
-        if ((rc = smx_dev_region_vote(&c->vote_params, arms, guide, ch, kept, out.map + n, voted, w, h, in.dminl, size_d, p->d_lr,
-                                      c->vote_ws.p, vote_workspace_bytes(w, h), st)))
-            return rc;
-        if ((rc = launch_fill_occlusion(voted, out.fil, w, h, (float)in.dminl, st))) return rc;
-    }
+    const float* kept = nullptr;
+    if ((rc = ctx_outlier_stages(c, in, need, out, keysL, uqL, &kept))) return rc;
     if (need.subpix && (rc = smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl,
                                                    c->sub.as<float>(), c->subf.as<float>(), st)))
         return rc;
@@ -527,15 +575,36 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     if (cscale && (out->mean_l || out->mean_r))
         return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) produces no mean images", who);
     if (cscale && !cscale_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: cross-scale aggregation %s", who, CSCALE_SHAPES);
+    const bool pm = c->pm;
+    if (pm) {
+        // PatchMatch keeps no cost volume: every stage that reads one has nothing to read, and the rest is out of scope
+        const char* with = c->cost_mode != SMX_COST_REFERENCE ? "the census cost (smx_ctx_set_cost)"
+                           : c->adcensus                      ? "the AD-Census cost (smx_ctx_set_adcensus)"
+                           : cgf                              ? "colour guidance (smx_ctx_set_guidance)"
+                           : sgm                              ? "semi-global matching (smx_ctx_set_aggregation)"
+                           : cross                            ? "cross-based aggregation (smx_ctx_set_cross)"
+                           : so                               ? "the scan-line optimiser (smx_ctx_set_scanline)"
+                           : cscale                           ? "cross-scale aggregation (smx_ctx_set_cross_scale)"
+                           : c->adjust                        ? "the depth-discontinuity adjustment (smx_ctx_set_adjust)"
+                           : c->uniq > 0.0f                   ? "the uniqueness test (smx_ctx_set_uniqueness)"
+                           : c->subpix                        ? "the sub-pixel fit (smx_ctx_set_subpixel; the planes are sub-pixel already)"
+                                                              : nullptr;
+        if (with) return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) is on, and so is %s", who, with);
+        if (out->cost_l || out->cost_r || out->agg_l || out->agg_r || out->mean_l || out->mean_r)
+            return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) produces no cost volumes, aggregated volumes or "
+                                   "mean images", who);
+        if (!pm_shape_ok(c->w, c->h, c->size_d, dminl, dminr))
+            return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) %s", who, PM_SHAPES);
+    }
     // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
     // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
     const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale, c->subpix != 0,
                             c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
-                            c->adjust, cscale, false};
+                            c->adjust, cscale, false, pm};
     if ((rc = ctx_reserve(c, need))) return rc;
     if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
-    c->sub_valid = c->spk_valid = c->uq_valid = c->vote_valid = false;
+    c->sub_valid = c->spk_valid = c->uq_valid = c->vote_valid = c->pm_valid = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     uint8_t* rgbL = channels ? c->rgb.as<uint8_t>() : nullptr;
     uint8_t* rgbR = channels ? rgbL + n * (size_t)channels : nullptr;
@@ -563,8 +632,8 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    // (the SGM, colour-guided and cross-based kernels wait for nothing)
-    if (!need.sgm && !need.cgf && !need.cross && !need.so) {
+    // (the SGM, colour-guided, cross-based and PatchMatch kernels wait for nothing)
+    if (!need.sgm && !need.cgf && !need.cross && !need.so && !need.pm) {
         if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
         for (int s = 1; cscale && s < c->cs_params.scales; ++s)
             if ((rc = smx_dev_agg_status(c->cs_child[s]->ws.p))) return rc;
@@ -573,6 +642,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     c->spk_valid = need.speckle;
     c->uq_valid = need.uniq;
     c->vote_valid = need.vote;
+    c->pm_valid = need.pm;
     return SMX_OK;
 }
 
@@ -749,6 +819,40 @@ int smx_ctx_cscale_held(const smx_ctx* c, int* levels, size_t* bytes) {
     return SMX_OK;
 }
 
+int smx_ctx_set_patchmatch(smx_ctx* c, const smx_pm_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!pm_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_patchmatch: %s", PM_RANGES);
+        if (!pm_shape_ok(c->w, c->h, c->size_d, 0, 0)) return fail(SMX_E_ARG, "smx_ctx_set_patchmatch: %s", PM_SHAPES);
+        c->pm_params = *p;
+    }
+    c->pm = p != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_patchmatch_maps(smx_ctx* c, float* planes_l, float* planes_r, float* sub_l, float* sub_r, float* sub_filled) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_patchmatch_maps")) return rc;
+    if (!c->pm_valid) return fail(SMX_E_ARG, "smx_ctx_patchmatch_maps: the last smx_ctx_stereo_pair ran without PatchMatch stereo");
+    const size_t n = c->n, fb = n * sizeof(float);
+    const float* pl = c->pm_planes.as<float>();
+    const float* disp = c->pm_disp.as<float>();
+    if (planes_l) SMX_HIP(hipMemcpy(planes_l, pl, 3 * fb, hipMemcpyDeviceToHost));
+    if (planes_r) SMX_HIP(hipMemcpy(planes_r, pl + 3 * n, 3 * fb, hipMemcpyDeviceToHost));
+    if (sub_l) SMX_HIP(hipMemcpy(sub_l, disp, fb, hipMemcpyDeviceToHost));
+    if (sub_r) SMX_HIP(hipMemcpy(sub_r, disp + n, fb, hipMemcpyDeviceToHost));
+    if (sub_filled) SMX_HIP(c->subf.download(sub_filled, fb));
+    return SMX_OK;
+}
+
+// Test hook (include/smx.h): what PatchMatch stereo holds on the device
+int smx_ctx_pm_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = 0;
+    for (const DevBuf* b : {&c->pm_planes, &c->pm_disp, &c->pm_ws}) *bytes += b->p ? b->bytes : 0;
+    return SMX_OK;
+}
+
 int smx_ctx_vote_map(smx_ctx* c, float* voted) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
@@ -813,6 +917,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the depth-discontinuity adjustment is on (smx_ctx_set_adjust): use smx_ctx_stereo_pair");
     if (c->cscale)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-scale aggregation is on (smx_ctx_set_cross_scale): use smx_ctx_stereo_pair");
+    if (c->pm)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: PatchMatch stereo is on (smx_ctx_set_patchmatch): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
     if (c->agg_mode != SMX_AGG_GUIDED)

@@ -428,6 +428,49 @@ int smx_cscale_combine(const smx_cscale_params* p, const float* const* agg, int 
     return SMX_OK;
 }
 
+int smx_patchmatch(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h, int size_d,
+                   int dminl, int dminr, float* planes, float* cost, float* disp, float* label) {
+    if (!pm_params_ok(pm)) return fail(SMX_E_ARG, "smx_patchmatch: %s", PM_RANGES);
+    if (!pm_shape_ok(w, h, size_d, dminl, dminr)) return fail(SMX_E_ARG, "smx_patchmatch: %s", PM_SHAPES);
+    SMX_ARG(p && left && right && planes && cost && disp && label);
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), wsb = pm_workspace_bytes(w, h);
+    DevBuf dL, dR, dO, dW;                       // dO: planes | cost | disp | label
+    SMX_HIP(dL.upload(left, n));
+    SMX_HIP(dR.upload(right, n));
+    SMX_HIP(dO.ensure(12 * fb));
+    SMX_HIP(dW.ensure(wsb));
+    float* o = dO.as<float>();
+    if (int rc = smx_dev_patchmatch_pair(p, pm, dL.as<uint8_t>(), dR.as<uint8_t>(), w, h, size_d, dminl, dminr, o, o + 6 * n, o + 8 * n,
+                                         o + 10 * n, dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(hipMemcpy(planes, o, 6 * fb, hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(cost, o + 6 * n, 2 * fb, hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(disp, o + 8 * n, 2 * fb, hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(label, o + 10 * n, 2 * fb, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
+int smx_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h,
+                      int size_d, int dminl, int dminr, const float* planes, float* cost) {
+    if (!pm_params_ok(pm)) return fail(SMX_E_ARG, "smx_pm_plane_cost: %s", PM_RANGES);
+    if (!pm_shape_ok(w, h, size_d, dminl, dminr)) return fail(SMX_E_ARG, "smx_pm_plane_cost: %s", PM_SHAPES);
+    SMX_ARG(p && left && right && planes && cost);
+    const size_t n = (size_t)w * h, fb = n * sizeof(float), wsb = pm_workspace_bytes(w, h);
+    DevBuf dL, dR, dP, dC, dW;
+    SMX_HIP(dL.upload(left, n));
+    SMX_HIP(dR.upload(right, n));
+    SMX_HIP(dP.upload(planes, 6 * fb));
+    SMX_HIP(dC.ensure(2 * fb));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_pm_plane_cost(p, pm, dL.as<uint8_t>(), dR.as<uint8_t>(), w, h, size_d, dminl, dminr, dP.as<float>(),
+                                       dC.as<float>(), dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dC.download(cost, 2 * fb));
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -98,4 +98,17 @@ int launch_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int ch, hipS
 void pyr_down_tile(int* tw, int* th);
 int launch_cscale_wta_pair(const smx_cscale_params* p, const float* const* agg_l, const float* const* agg_r, int w, int h, int dminl,
                            int dminr, int size_d, int64_t* keys, float* out, float* nbr, float* uq, hipStream_t st);
+// smx_patchmatch.hip: PatchMatch stereo (smx_dev_patchmatch_pair, smx_dev_pm_plane_cost); ws: pm_workspace_bytes(w, h) bytes.
+// planes [2][3][h][w], cost / disp / label [2][h][w], the left view first
+size_t pm_workspace_bytes(int w, int h);
+void pm_weights(const smx_pm_params* p, float* tab);
+uint32_t pm_hash_host(uint32_t seed, uint32_t view, uint32_t pix, uint32_t draw);
+int launch_patchmatch_pair(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h,
+                           int size_d, int dminl, int dminr, float* planes, float* cost, float* disp, float* label, void* ws,
+                           hipStream_t st);
+int launch_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uint8_t* left, const uint8_t* right, int w, int h,
+                         int size_d, int dminl, int dminr, const float* planes, float* cost, void* ws, hipStream_t st);
+void pm_tile(int* tw, int* th);
+// (a pair's sub-pixel filled map from PatchMatch: disp where `kept` passes fill_occlusion's validity test, `filled` elsewhere)
+int launch_pm_sub_filled(const float* disp, const float* kept, const float* filled, size_t n, int dminl, float* out, hipStream_t st);
 }  // namespace smx

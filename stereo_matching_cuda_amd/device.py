@@ -27,7 +27,7 @@ class PairPipeline:
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
                  aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
-                 vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None):
+                 vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None, pm_params=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -111,7 +111,32 @@ class PairPipeline:
         self.uq with the winners and states of those.  Everything in finish() runs unchanged behind it.  With the guided filter
         only (gray or rgb guide; the reference, census and AD-Census costs): aggregation= raises ValueError, and so do a slice
         sub-range, caller's cost volumes and a pyramid whose coarsest level is narrower than 2 pixels.  self.mean is level
-        0's.  max_ws_bytes bounds each level's pipeline by itself.  With None nothing is allocated or launched."""
+        0's.  max_ws_bytes bounds each level's pipeline by itself.  With None nothing is allocated or launched.
+        aggregation="patchmatch" is PatchMatch stereo (Bleyer et al. 2011; not a stage of the reference; include/smx.h
+        smx_dev_patchmatch_pair; pm_params: PMParams, None = the defaults): a disparity plane per pixel in place of cost,
+        aggregation and winner-take-all.  aggregate() runs the search into self.pm_planes (2, 3, h, w), self.best (the plane
+        costs), self.pm_disp (2, h, w) and self.dmap (the labels); finish() runs the LR check and the fill on the labels,
+        speckle removal and region voting behind them unchanged, then self.sub_filled = the left disp where the pixel was
+        kept, the filled label elsewhere (smx_dev_pm_sub_filled), then the weighted median.  There is no cost volume: cost=,
+        guidance=, cross_scale=, adjust=, uniqueness=, subpixel=, want_agg=, caller's cost volumes and a slice sub-range raise
+        ValueError.  self.mean stays zero and self.keys is not written."""
+        pm = aggregation == "patchmatch"
+        if pm_params is not None and not pm:
+            raise ValueError("pm_params belongs to aggregation='patchmatch'")
+        if pm:
+            if pm_params is not None and not isinstance(pm_params, _lib.PMParams):
+                raise ValueError(f"pm_params must be None or PMParams, not {pm_params!r}")
+            q = pm_params
+            if q is not None and not (0 <= q.radius <= 17 and 0.0 < q.gamma < float("inf") and 1 <= q.iterations <= 16 and
+                                      0.0 <= q.max_slope <= 8.0):
+                raise ValueError("pm_params needs 0 <= radius <= 17, a finite gamma > 0, 1 <= iterations <= 16 and "
+                                 "0 <= max_slope <= 8")
+            for name, value in (("cost", cost), ("guidance", guidance), ("cross_scale", cross_scale), ("adjust", adjust),
+                                ("uniqueness", uniqueness), ("subpixel", subpixel), ("want_agg", want_agg or None)):
+                if value is not None:
+                    raise ValueError(f"PatchMatch stereo keeps no cost volume and its planes are sub-pixel already: not with {name}=")
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("PatchMatch stereo searches a pixel's whole disparity range: no slice sub-range")
         if cross_scale is not None and cross_scale is not True and not isinstance(cross_scale, _lib.CScaleParams):
             raise ValueError(f"cross_scale must be None, True or CScaleParams, not {cross_scale!r}")
         if isinstance(cross_scale, _lib.CScaleParams) and not (1 <= cross_scale.scales <= 5 and
@@ -146,8 +171,8 @@ class PairPipeline:
             # winners it does not belong to)
             if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
                 raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
-        if aggregation not in (None, "sgm", "cross", "scanline", "cross-scanline"):
-            raise ValueError(f"aggregation must be None, 'sgm', 'cross', 'scanline' or 'cross-scanline', not {aggregation!r}")
+        if aggregation not in (None, "sgm", "cross", "scanline", "cross-scanline", "patchmatch"):
+            raise ValueError(f"aggregation must be None, 'sgm', 'cross', 'scanline', 'cross-scanline' or 'patchmatch', not {aggregation!r}")
         sgm, cross = aggregation == "sgm", aggregation in ("cross", "cross-scanline")
         so = aggregation in ("scanline", "cross-scanline")
         if scanline_params is not None and not so:
@@ -319,6 +344,21 @@ class PairPipeline:
             self.cross_ws_bytes = int(self.lib.smx_cross_workspace_bytes(self.w, self.h, sif, 2))
             self.cross_ws = torch.empty(self.cross_ws_bytes, dtype=torch.uint8, device=dev)
             self.cross_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
+        self.pm_params = self.pm_planes = self.pm_disp = self.pm_ws = None
+        self.pm_ws_bytes = 0
+        if pm:
+            self.pm_params = pm_params if pm_params is not None else _lib.default_pm_params()
+            self.pm_ws_bytes = int(self.lib.smx_pm_workspace_bytes(self.w, self.h))
+            if self.pm_ws_bytes == 0 or not (1 <= self.size_d <= 1 << 20 and abs(self.dminl) <= 1 << 20 and abs(self.dminr) <= 1 << 20):
+                raise ValueError(f"PatchMatch stereo does not take {self.w} x {self.h} x {self.size_d} from {self.dminl} / "
+                                 f"{self.dminr} (w < 2^24, w*h < 2^31, size_d and |dmin| <= 2^20)")
+            if self.pm_ws_bytes + 8 * self.n * 4 > max_ws_bytes:
+                raise ValueError(f"PatchMatch stereo needs {self.pm_ws_bytes + 8 * self.n * 4} bytes for its planes and workspace: "
+                                 f"more than max_ws_bytes = {max_ws_bytes}")
+            self.pm_planes = torch.empty((2, 3, self.h, self.w), **f)
+            self.pm_disp = torch.empty((2, self.h, self.w), **f)
+            self.pm_ws = torch.empty(self.pm_ws_bytes, dtype=torch.uint8, device=dev)
+            self.sub_filled = torch.empty((self.h, self.w), **f)
         self.cross_scale = _lib.default_cscale_params() if cross_scale is True else cross_scale
         self.cs_levels, self.cs_gray, self.cs_rgb = [], [], []
         if self.cross_scale:
@@ -388,6 +428,15 @@ class PairPipeline:
         guidance="rgb" and the images of the AD term of cost="adcensus" with colour 1 (required then, refused otherwise)."""
         colour_cost = self.cost == "adcensus" and bool(self.adcensus_params.colour)
         self._rgb = None                # (the colour pair of THIS aggregation, where it takes one)
+        if self.aggregation == "patchmatch":
+            if cost_l is not None or cost_r is not None:
+                raise ValueError("PatchMatch stereo reads no cost volume: pass the images only")
+            if (rgb_l is None) != (rgb_r is None):
+                raise ValueError("pass both colour guides or neither")
+            if rgb_l is not None:           # (the guide of region voting; the search itself is gray)
+                self._check_rgb(rgb_l, rgb_r)
+                self._rgb = (rgb_l, rgb_r)
+            return self._patchmatch(gray_l, gray_r)
         if self.guidance:
             if rgb_l is None or rgb_r is None:
                 raise ValueError("guidance='rgb' needs the colour images: pass rgb_l= and rgb_r=")
@@ -643,6 +692,16 @@ class PairPipeline:
                                              self.s_begin, self.s_end, st))
         return cl, cr
 
+    def _patchmatch(self, gray_l, gray_r):
+        """The PatchMatch search of both views (smx_dev_patchmatch_pair): planes, plane costs into self.best, disp, and the
+        labels into self.dmap."""
+        self._guide = gray_l
+        with self._on_device():
+            _lib.check(self.lib.smx_dev_patchmatch_pair(C.byref(self.params), C.byref(self.pm_params), _dp(gray_l), _dp(gray_r),
+                                                        self.w, self.h, self.size_d, self.dminl, self.dminr, _dp(self.pm_planes),
+                                                        _dp(self.best), _dp(self.pm_disp), _dp(self.dmap), _dp(self.pm_ws),
+                                                        self.pm_ws_bytes, self._stream()))
+
     def aggregate_pair(self, gray_l, gray_r):
         """Both views per kernel launch (smx_dev_aggregate_wta_pair)."""
         self._guide = gray_l
@@ -684,12 +743,31 @@ class PairPipeline:
 
     def finish(self):
         """Keys -> best/dmap (reference presets, dispSelect rule), LR check, filling: main.cu:112-155 in one
-        call (smx_dev_finish_pair: one launch, a row per workgroup)."""
+        call (smx_dev_finish_pair: one launch, a row per workgroup).  Behind PatchMatch stereo best and dmap are there
+        already: the LR check and the fill run on the labels (main.cu:141-155), and the fractional filled map closes the
+        outlier stages."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
-            _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
-                                             self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
-                                             _dp(self.occlusion), _dp(self.filled), st))
+            if self.aggregation == "patchmatch":
+                self.occlusion.copy_(self.dmap[0])
+                _lib.check(L.smx_dev_detect_occlusion(P, _dp(self.occlusion), _dp(self.dmap[1]), self.dminl - 100, self.w, self.h, st))
+                self.filled.copy_(self.occlusion)
+                _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+            else:
+                _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
+                                                 self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
+                                                 _dp(self.occlusion), _dp(self.filled), st))
+        if self.aggregation == "patchmatch":
+            if self.speckle:
+                self.despeckle()
+            if self.vote:
+                self.region_vote()
+            with self._on_device():
+                _lib.check(self.lib.smx_dev_pm_sub_filled(_dp(self.pm_disp[0]), _dp(self._kept()), _dp(self.filled), self.w, self.h,
+                                                          self.dminl, _dp(self.sub_filled), self._stream()))
+            if self.wmf:
+                self.refine()
+            return
         if self.uniqueness:
             self.uniqueness_filter()
         if self.speckle:
@@ -840,4 +918,7 @@ class PairPipeline:
             r["adjusted"] = c(self.adjusted)
         if self.subpixel:
             r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.sub[0]), c(self.sub[1]), c(self.sub_filled)
+        if self.aggregation == "patchmatch":
+            r["pm_planes"] = c(self.pm_planes)
+            r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.pm_disp[0]), c(self.pm_disp[1]), c(self.sub_filled)
         return r

@@ -21,6 +21,7 @@
 #include "guidedFilter.cuh"
 #include "integral.cuh"
 #include "occlusion.cuh"
+#include "patchMatch.cuh"
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "scanlineOptimization.cuh"
@@ -550,6 +551,200 @@ void crossScaleOnCPU(const float* const* levels, float* out, float* best, float*
                 else best[id] = m == 0.0f ? 0.0f : m;
             }
             if (disp_map) disp_map[id] = (float)(dmin + (zm < 0 ? 0 : zm));
+        }
+}
+
+// ---- patchMatch.cuh (not in the reference) ---------------------------------------------------------
+// The definition of include/smx.h (above smx_pm_params), scalar and sequential: a pixel of one colour reads pixels of the other
+// colour only, so a pass may run in place.
+namespace {
+
+uint32_t pm_fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+float pm_uniform(uint32_t seed, uint32_t view, uint32_t pix, uint32_t draw) {
+    const uint32_t h = pm_fmix32(pm_fmix32(pm_fmix32(seed + 0x9E3779B9u * (view + 1u)) ^ pix) ^ draw);
+    return (float)(h >> 8) * 5.9604644775390625e-08f;
+}
+float pm_clamp(float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+struct PmView {
+    const unsigned char* own;
+    vector<float> g, io, go;       // the own gradient; gray and gradient of the other view as f32
+    int w, h, r, size_d, view;
+    float dmin, dmax, alpha, oma, th_color, th_grad, border;
+    const float* tab;
+    float *a, *b, *d0, *m;         // the state [h][w] each
+};
+
+vector<float> pm_xgrad(const unsigned char* img, int w, int h) {
+    vector<float> g((size_t)w * h, 0.0f);
+    if (w < 2) return g;
+    for (int y = 0; y < h; ++y) {
+        const unsigned char* r = img + (size_t)y * w;
+        for (int x = 0; x < w; ++x) {
+            const int c1 = x + 1 < w ? r[x + 1] : r[x], c2 = x - 1 >= 0 ? r[x - 1] : r[x];
+            g[(size_t)y * w + x] = 1.0f * (float)(c2 - c1) / 2;
+        }
+    }
+    return g;
+}
+
+float pm_plane_cost(const PmView& v, int x, int y, float a, float b, float d0) {
+    const int w = v.w, h = v.h, r = v.r;
+    const int ip = v.own[(size_t)y * w + x];
+    float acc = 0.0f;
+    for (int dy = -r; dy <= r; ++dy) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= h) continue;
+        const size_t row = (size_t)qy * w;
+        const float bdy = b * (float)dy;
+        for (int dx = -r; dx <= r; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= w) continue;
+            const int iq = v.own[row + qx];
+            const float wgt = v.tab[std::abs(ip - iq)];
+            const float d = (d0 + a * (float)dx) + bdy;
+            const float xs = (float)qx + d;
+            float rho = v.border;
+            if (d >= v.dmin && d <= v.dmax && xs >= 0.0f && xs <= (float)(w - 1)) {
+                const float fl = std::floor(xs);
+                const int i = (int)fl, i1 = i + 1 < w ? i + 1 : w - 1;
+                const float t = xs - fl;
+                const float ii = v.io[row + i] + t * (v.io[row + i1] - v.io[row + i]);
+                const float gi = v.go[row + i] + t * (v.go[row + i1] - v.go[row + i]);
+                const float t1 = std::fabs((float)iq - ii), t2 = std::fabs(v.g[row + qx] - gi);
+                const float m1 = t1 < v.th_color ? t1 : v.th_color, m2 = t2 < v.th_grad ? t2 : v.th_grad;
+                const float ca = v.oma * m1, cb = v.alpha * m2;
+                rho = ca + cb;
+            }
+            const float term = wgt * rho;
+            acc = acc + term;
+        }
+    }
+    return acc;
+}
+
+PmView pm_view(const unsigned char* own, const unsigned char* other, int view, int w, int h, int size_d, int dmin,
+               const smx_pm_params& p, const float* tab, float* planes, float* cost) {
+    const smx_params& P = smx_config().params;
+    const size_t n = (size_t)w * h;
+    PmView v;
+    v.own = own;
+    v.g = pm_xgrad(own, w, h);
+    v.go = pm_xgrad(other, w, h);
+    v.io.assign(other, other + n);
+    v.w = w; v.h = h; v.r = p.radius; v.size_d = size_d; v.view = view;
+    v.dmin = (float)dmin; v.dmax = (float)(dmin + size_d - 1);
+    v.alpha = 1.0f * P.alpha; v.oma = 1.0f - v.alpha;
+    v.th_color = 1.0f * P.th_color; v.th_grad = 1.0f * P.th_grad;
+    const float ca = v.oma * v.th_color, cb = 1.0f * v.alpha * v.th_grad;
+    v.border = ca + cb;
+    v.tab = tab;
+    v.a = planes; v.b = planes + n; v.d0 = planes + 2 * n; v.m = cost;
+    return v;
+}
+
+void pm_try(const PmView& v, size_t id, int x, int y, float a, float b, float d0) {
+    const float c = pm_plane_cost(v, x, y, a, b, d0);
+    if (c < v.m[id]) { v.a[id] = a; v.b[id] = b; v.d0[id] = d0; v.m[id] = c; }
+}
+
+void pm_pass(const PmView& v, const smx_pm_params& p, int it, int colour) {
+    static const int nb[8][2] = {{-1, 0}, {1, 0}, {0, -1}, {0, 1}, {-5, 0}, {5, 0}, {0, -5}, {0, 5}};      // (dx, dy)
+    const int w = v.w, h = v.h;
+    const float ms = (float)p.max_slope;
+    for (int y = 0; y < h; ++y)
+        for (int x = (y + colour) & 1; x < w; x += 2) {
+            const size_t id = (size_t)y * w + x;
+            for (const auto& e : nb) {
+                const int nx = x + e[0], ny = y + e[1];
+                if (nx < 0 || nx >= w || ny < 0 || ny >= h) continue;
+                const size_t q = (size_t)ny * w + nx;
+                const float d = (v.d0[q] + v.a[q] * (float)(x - nx)) + v.b[q] * (float)(y - ny);
+                if (d >= v.dmin && d <= v.dmax) pm_try(v, id, x, y, v.a[q], v.b[q], d);
+            }
+            float dd = (float)(v.size_d - 1) * 0.5f, ds = ms * 0.5f;
+            for (int k = 0; dd >= 0.1f; ++k) {
+                const uint32_t base = 3u + 3u * (uint32_t)(it * 32 + k);
+                const float r0 = 2.0f * pm_uniform(p.seed, v.view, (uint32_t)id, base) - 1.0f;
+                const float r1 = 2.0f * pm_uniform(p.seed, v.view, (uint32_t)id, base + 1u) - 1.0f;
+                const float r2 = 2.0f * pm_uniform(p.seed, v.view, (uint32_t)id, base + 2u) - 1.0f;
+                pm_try(v, id, x, y, pm_clamp(v.a[id] + r1 * ds, -ms, ms), pm_clamp(v.b[id] + r2 * ds, -ms, ms),
+                       pm_clamp(v.d0[id] + r0 * dd, v.dmin, v.dmax));
+                dd = dd * 0.5f;
+                ds = ds * 0.5f;
+            }
+        }
+}
+
+void pm_view_propagation(const PmView& v, const vector<float>& other) {      // other: the other view's planes [3][h][w], a snapshot
+    const int w = v.w, h = v.h;
+    const size_t n = (size_t)w * h;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t id = (size_t)y * w + x;
+            int xo = (int)std::floor(((float)x + v.d0[id]) + 0.5f);
+            xo = xo < 0 ? 0 : xo > w - 1 ? w - 1 : xo;
+            const size_t q = (size_t)y * w + xo;
+            const float d = -other[2 * n + q];
+            if (d >= v.dmin && d <= v.dmax) pm_try(v, id, x, y, -other[q], -other[n + q], d);
+        }
+}
+
+vector<float> pm_table(const smx_pm_params& p) {
+    vector<float> tab(256);
+    for (int k = 0; k < 256; ++k) tab[k] = (float)std::exp(-(double)k / p.gamma);
+    return tab;
+}
+
+}  // namespace
+
+void pmPlaneCostOnCPU(const unsigned char* left, const unsigned char* right, const float* planes, float* cost, const int w,
+                      const int h, const int size_d, const int dminl, const int dminr, const smx_pm_params& p) {
+    const size_t n = (size_t)w * h;
+    const vector<float> tab = pm_table(p);
+    for (int view = 0; view < 2; ++view) {
+        const PmView v = pm_view(view ? right : left, view ? left : right, view, w, h, size_d, view ? dminr : dminl, p, tab.data(),
+                                 const_cast<float*>(planes) + 3 * n * view, cost + n * view);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t id = (size_t)y * w + x;
+                v.m[id] = pm_plane_cost(v, x, y, v.a[id], v.b[id], v.d0[id]);
+            }
+    }
+}
+
+void patchMatchOnCPU(const unsigned char* left, const unsigned char* right, float* planes, float* cost, float* disp, float* label,
+                     const int w, const int h, const int size_d, const int dminl, const int dminr, const smx_pm_params& p) {
+    const size_t n = (size_t)w * h;
+    const vector<float> tab = pm_table(p);
+    const float ms = (float)p.max_slope;
+    PmView views[2] = {pm_view(left, right, 0, w, h, size_d, dminl, p, tab.data(), planes, cost),
+                       pm_view(right, left, 1, w, h, size_d, dminr, p, tab.data(), planes + 3 * n, cost + n)};
+    for (const PmView& v : views)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t id = (size_t)y * w + x;
+                v.d0[id] = v.dmin + pm_uniform(p.seed, v.view, (uint32_t)id, 0) * (float)(size_d - 1);
+                v.a[id] = (2.0f * pm_uniform(p.seed, v.view, (uint32_t)id, 1) - 1.0f) * ms;
+                v.b[id] = (2.0f * pm_uniform(p.seed, v.view, (uint32_t)id, 2) - 1.0f) * ms;
+                v.m[id] = pm_plane_cost(v, x, y, v.a[id], v.b[id], v.d0[id]);
+            }
+    for (int it = 0; it < p.iterations; ++it) {
+        for (const PmView& v : views) {
+            pm_pass(v, p, it, it & 1);
+            pm_pass(v, p, it, (it & 1) ^ 1);
+        }
+        const vector<float> snap_l(planes, planes + 3 * n), snap_r(planes + 3 * n, planes + 6 * n);
+        pm_view_propagation(views[0], snap_r);
+        pm_view_propagation(views[1], snap_l);
+    }
+    for (const PmView& v : views)
+        for (size_t id = 0; id < n; ++id) {
+            disp[n * v.view + id] = v.d0[id];
+            label[n * v.view + id] = pm_clamp(std::floor(v.d0[id] + 0.5f), v.dmin, v.dmax);
         }
 }
 

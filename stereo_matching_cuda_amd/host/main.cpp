@@ -9,7 +9,7 @@
 //                                    D_MIN..D_MAX from the macros, outputs into ./data/
 //   smx_main L.png R.png [dmin dmax [outdir]] [options]
 // options (not in the reference).  The opt-in costs, aggregations and stages (--cost census / adcensus, --aggregation sgm /
-// cross / scanline / cross-scanline, --guidance rgb, --uniqueness, --speckle, --vote, --adjust, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
+// cross / scanline / cross-scanline / patchmatch, --guidance rgb, --uniqueness, --speckle, --vote, --adjust, --subpixel) compose with each other and with --wmf, --pfm and --png16 unless
 // an entry says otherwise; none of them goes with --ngpu or --pipeline:
 //   --fused           one device-resident call for everything after the gray conversion
 //                     (smx_stereo_pair: cost built on the fly inside the fused aggregation) instead of
@@ -109,6 +109,17 @@
 //                     15; 256 never lowers a penalty), --so-paths 4|8 the number of directions (default 4).  With --host-compare
 //                     the CPU twins (cross_aggregateOnCPU, scanline_optimizeOnCPU) redo both views from the cost volumes and
 //                     check_errors compares.  At most 256 labels.  Not with --guidance rgb
+//   --aggregation patchmatch  PatchMatch stereo instead of cost volume, aggregation and winner-take-all (smx_ctx_set_patchmatch;
+//                     Bleyer et al. 2011, not in the reference; implies --fused): every pixel gets a disparity plane, scored with
+//                     the reference's cost over an adaptive-weight window that lies in the plane, so that a slanted surface is
+//                     matched as one.  --pm-radius R gives the window (0 .. 17; default 8), --pm-gamma G the colour weight's
+//                     scale (> 0; default 10), --pm-iterations N the iterations (1 .. 16; default 4), --pm-slope S the largest
+//                     slope (0 .. 8; default 2; 0 is a fronto-parallel search), --pm-seed K the seed (default 0).  The twelve
+//                     images come from its labels and plane costs, the two mean images are empty, disparity_mapl_patchmatch.png
+//                     holds the fractional left map, and --pfm / --png16 carry the fractional filled map.  --speckle, --vote and
+//                     --wmf run behind it on the labels.  With --host-compare the CPU twin (patchMatchOnCPU) redoes both views and
+//                     check_errors compares planes, costs, fractional maps and labels.  Not with --cost census | adcensus,
+//                     --guidance rgb, --cross-scale, --adjust, --uniqueness, --subpixel, --ngpu or --pipeline
 //   --ngpu N          disparity-shard the aggregation over N GPUs of this node: every GPU aggregates
 //                     its slice range, ONE RCCL MIN reduce of the packed keys reassembles the map on GPU 0
 //                     (the persistent context smx_sharded_create / _run / _destroy of libsmx_rccl.so,
@@ -135,6 +146,7 @@
 #include "guidedFilter.cuh"
 #include "helpers.cuh"
 #include "occlusion.cuh"
+#include "patchMatch.cuh"
 #include "png_io.h"
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
@@ -178,6 +190,8 @@ struct Options {
     smx_adjust_params adjust_params;
     bool cscale = false;     // --cross-scale
     smx_cscale_params cs_params;
+    bool pm = false;         // --aggregation patchmatch
+    smx_pm_params pm_params;
     bool rgb = false;        // --guidance rgb
     float uniqueness = 0.0f; // --uniqueness PCT as the ratio PCT / (100 - PCT); 0 = off
     int ngpu = 0;            // 0 = not given: the single-GPU paths
@@ -262,10 +276,28 @@ const ValueOption value_options[] = {
          const bool good = number(v, 1L, 1000000L, th);
          o.census_params.th = (int)th;
          return good; }},
-    {"--aggregation", "`guided`, `sgm`, `cross`, `scanline` or `cross-scanline`", [](auto& v, auto& o) {    // (the last one wins)
-         const int k = word(v, {"guided", "sgm", "cross", "scanline", "cross-scanline"});
-         o.sgm = k == 1; o.cross = k == 2 || k == 4; o.so = k == 3 || k == 4;
+    {"--aggregation", "`guided`, `sgm`, `cross`, `scanline`, `cross-scanline` or `patchmatch`", [](auto& v, auto& o) {    // (the last one wins)
+         const int k = word(v, {"guided", "sgm", "cross", "scanline", "cross-scanline", "patchmatch"});
+         o.sgm = k == 1; o.cross = k == 2 || k == 4; o.so = k == 3 || k == 4; o.pm = k == 5;
          return k >= 0; }},
+    {"--pm-radius", "a radius R with 0 <= R <= 17", [](auto& v, auto& o) {
+         long r = -1;
+         const bool good = number(v, 0L, 17L, r);
+         o.pm_params.radius = (int)r;
+         return good; }},
+    {"--pm-gamma", "a finite G > 0", [](auto& v, auto& o) {
+         return number(v, 0.0, 1.7976931348623157e308, o.pm_params.gamma) && o.pm_params.gamma > 0.0; }},
+    {"--pm-iterations", "a count N with 1 <= N <= 16", [](auto& v, auto& o) {
+         long k = 0;
+         const bool good = number(v, 1L, 16L, k);
+         o.pm_params.iterations = (int)k;
+         return good; }},
+    {"--pm-slope", "a slope S with 0 <= S <= 8", [](auto& v, auto& o) { return number(v, 0.0, 8.0, o.pm_params.max_slope); }},
+    {"--pm-seed", "a seed K with 0 <= K <= 4294967295", [](auto& v, auto& o) {
+         long k = -1;
+         const bool good = number(v, 0L, 4294967295L, k);
+         o.pm_params.seed = (uint32_t)k;
+         return good; }},
     {"--so-p", "P1,P2 with 0 <= P1 <= P2 <= 4095", [](auto& v, auto& o) {
          int& p1 = o.so_params.p1; int& p2 = o.so_params.p2;
          return pair_of(v, ',', p1, p2) && p1 >= 0 && p1 <= p2 && p2 <= 4095; }},
@@ -366,6 +398,7 @@ Options parse(int argc, char** argv) {
     smx_default_cross_params(&o.vote_arms);
     smx_default_adjust_params(&o.adjust_params);
     smx_default_cscale_params(&o.cs_params);
+    smx_default_pm_params(&o.pm_params);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -405,7 +438,9 @@ Options parse(int argc, char** argv) {
          "--so-p, --so-tau and --so-paths need --aggregation scanline or cross-scanline"},
         {o.saw({"--vote-interpolate", "--vote-arms", "--vote-tau"}) && !o.vote,
          "--vote-interpolate, --vote-arms and --vote-tau need --vote"},
-        {o.saw({"--adjust-vertical"}) && !o.adjust, "--adjust-vertical needs --adjust"}};
+        {o.saw({"--adjust-vertical"}) && !o.adjust, "--adjust-vertical needs --adjust"},
+        {o.saw({"--pm-radius", "--pm-gamma", "--pm-iterations", "--pm-slope", "--pm-seed"}) && !o.pm,
+         "--pm-radius, --pm-gamma, --pm-iterations, --pm-slope and --pm-seed need --aggregation patchmatch"}};
     for (const Rule& r : rules)
         if (r.refused) return refuse(r.message);
     return o;
@@ -443,6 +478,7 @@ struct Maps {
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
     std::vector<float> cscale;         // --cross-scale: the left map of the combined winners (= dmap[0])
+    std::vector<float> pm_disp;        // --aggregation patchmatch: the fractional left map (the planes' d0)
     std::vector<float> adjusted;       // --adjust: the filled left map with the pixels beside its depth steps adjusted (= filled)
     std::vector<float> unique;         // --uniqueness: the LR-checked left map without its ambiguous winners
     std::vector<float> sub_filled;     // --subpixel: the sub-pixel filled left map
@@ -597,6 +633,22 @@ void check_cross_scale_twin(const Job& j, Maps& m, std::vector<float>& agg_l) {
     if (ok) std::cout << "Cross-scale ok!" << std::endl;
 }
 
+// --host-compare of --aggregation patchmatch: the twin redoes the search of both views; its planes, plane costs, fractional maps
+// and labels against the context's.
+void check_patchmatch_twin(const Job& j, Maps& m, std::vector<float>& planes, std::vector<float>& disp) {
+    const size_t n = (size_t)j.n;
+    std::vector<float> tp(6 * n), tc(2 * n), td(2 * n), tl(2 * n);
+    patchMatchOnCPU(j.gray[0], j.gray[1], tp.data(), tc.data(), td.data(), tl.data(), j.w, j.h, j.size_d, j.dmin[0], j.dmin[1],
+                    j.opt.pm_params);
+    bool ok = check_errors(tp.data(), planes.data(), (int)(6 * n));
+    ok = check_errors(td.data(), disp.data(), (int)(2 * n)) && ok;
+    for (int v = 0; v < 2; ++v) {
+        ok = check_errors(tc.data() + v * n, m.best[v].data(), j.n) && ok;
+        ok = check_errors(tl.data() + v * n, m.dmap[v].data(), j.n) && ok;
+    }
+    if (ok) std::cout << "PatchMatch ok!" << std::endl;
+}
+
 // --host-compare of the device-resident flow behind the winners: LR check, uniqueness (from the left aggregated volume), speckle
 // removal, region voting, fill and depth-discontinuity adjustment, each twin from the twin before it.
 void check_finish_twins(const Job& j, Maps& m, std::vector<float>& agg_l) {
@@ -710,8 +762,8 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     std::memset(&out, 0, sizeof(out));
     out.best_l = m.best[0].data(); out.best_r = m.best[1].data();
     out.dmap_l = m.dmap[0].data(); out.dmap_r = m.dmap[1].data();
-    // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser and cross-scale have no mean images)
-    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
+    // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser, cross-scale and PatchMatch have no mean images)
+    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale && !opt.pm) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
     std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness and adjustment twins read
     if ((uniq || opt.adjust || opt.cscale) && host_compare) {
@@ -735,6 +787,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
     if (opt.so) CHECK(smx_ctx_set_scanline(ctx, &opt.so_params));         // (behind the cross stage where that is on too)
+    if (opt.pm) CHECK(smx_ctx_set_patchmatch(ctx, &opt.pm_params));
     if (!sh.create) CHECK(smx_set_timing(1));     // per-stage device times of the last pair (smx_stage_times)
     auto run_pair = [&]() {
         return sh.create ? sh.run(sctx, j.gray[0], j.gray[1], j.dmin[0], j.dmin[1], &out)
@@ -782,12 +835,22 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     }
     if (opt.adjust) m.adjusted = m.filled;
     if (opt.cscale) m.cscale = m.dmap[0];
+    std::vector<float> pm_planes, pm_disp;      // both views' planes and fractional maps: what the twin is compared with
+    if (opt.pm) {
+        pm_planes.resize((size_t)6 * n);
+        pm_disp.resize((size_t)2 * n);
+        m.sub_filled.resize(n);
+        CHECK(smx_ctx_patchmatch_maps(ctx, pm_planes.data(), pm_planes.data() + (size_t)3 * n, pm_disp.data(), pm_disp.data() + n,
+                                      m.sub_filled.data()));
+        m.pm_disp.assign(pm_disp.begin(), pm_disp.begin() + n);
+    }
     if (sh.create) CHECK(sh.destroy(sctx));
     else CHECK(smx_destroy(ctx));
     std::cout << "guided filter ok" << std::endl;
     // (with --cross-scale the winners are the combination's: its twin redoes the colour guide's aggregation at every level)
     if (host_compare && opt.cscale) check_cross_scale_twin(j, m, agg_l);
     else if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
+    else if (host_compare && opt.pm) check_patchmatch_twin(j, m, pm_planes, pm_disp);
     if (host_compare) check_finish_twins(j, m, agg_l);
     return have_stage_ms;
 }
@@ -810,6 +873,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"occlu_mapl_despeckled.png", m.despeckled}, {"occlu_mapl_unique.png", m.unique},
                                   {"occlu_mapl_voted.png", m.voted}, {"occlu_mapl_adjusted.png", m.adjusted},
                                   {"disparity_mapl_cscale.png", m.cscale},
+                                  {"disparity_mapl_patchmatch.png", m.pm_disp},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
     for (const U8Out& o : u8_outputs)
@@ -896,6 +960,13 @@ int main(int argc, char** argv) {
         {opt.cscale && (opt.sgm || opt.cross || opt.so),
          "--cross-scale belongs to the guided filter: it cannot be combined with --aggregation sgm, cross, scanline or cross-scanline"},
         {opt.cscale && multi, "--cross-scale" + with_multi},
+        {opt.pm && (opt.census || opt.adcensus), "--aggregation patchmatch scores planes with the reference's cost: it cannot be "
+                                                 "combined with --cost census or adcensus"},
+        {opt.pm && (opt.rgb || opt.cscale || opt.adjust || uniq),
+         "--aggregation patchmatch keeps no cost volume: it cannot be combined with --guidance rgb, --cross-scale, --adjust or "
+         "--uniqueness"},
+        {opt.pm && opt.subpixel, "--aggregation patchmatch cannot be combined with --subpixel: its planes are sub-pixel already"},
+        {opt.pm && multi, "--aggregation patchmatch" + with_multi},
         {opt.adjust && multi, "--adjust" + with_multi},
         {opt.adjust && labels > 512, "--adjust takes at most 512 labels"},
         {opt.ngpu < 0 || opt.ngpu > smx_device_count(),
@@ -911,7 +982,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
-                       opt.cross || opt.so || opt.adjust || opt.cscale;
+                       opt.cross || opt.so || opt.adjust || opt.cscale || opt.pm;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;

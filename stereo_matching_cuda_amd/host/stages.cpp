@@ -9,6 +9,7 @@
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
+#include "patchMatch.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "colourGuidedFilter.cuh"
 #include "scanlineOptimization.cuh"
@@ -215,6 +216,22 @@ void discontinuity_adjust(float* disparity, float* agg, float* out, const int w,
         bool ok = check_errors(twin.data(), out, w * h);
         if (sub) ok = check_errors(ts.data(), sub, w * h) && ok;
         if (ok) cout << "Discontinuity adjustment ok!" << endl;
+    }
+}
+
+// not in the reference: PatchMatch stereo, a disparity plane per pixel (smx_main --aggregation patchmatch)
+void patch_match(unsigned char* left, unsigned char* right, float* planes, float* cost, float* disp, float* label, const int w,
+                 const int h, const int size_d, const int dminl, const int dminr, const smx_pm_params& p, bool host_gpu_compare) {
+    CHECK(smx_patchmatch(&smx_config().params, &p, left, right, w, h, size_d, dminl, dminr, planes, cost, disp, label));
+    if (host_gpu_compare) {
+        const size_t n = (size_t)w * h;
+        std::vector<float> tp(6 * n), tc(2 * n), td(2 * n), tl(2 * n);
+        patchMatchOnCPU(left, right, tp.data(), tc.data(), td.data(), tl.data(), w, h, size_d, dminl, dminr, p);
+        bool ok = check_errors(tp.data(), planes, (int)(6 * n));
+        ok = check_errors(tc.data(), cost, (int)(2 * n)) && ok;
+        ok = check_errors(td.data(), disp, (int)(2 * n)) && ok;
+        ok = check_errors(tl.data(), label, (int)(2 * n)) && ok;
+        if (ok) cout << "PatchMatch ok!" << endl;
     }
 }
 

@@ -69,6 +69,9 @@ class ShardedPair:
         if kw.get("aggregation") in ("scanline", "cross-scanline") or kw.get("scanline_params") is not None:
             raise ValueError("the scan-line optimiser is not part of the sharded driver: use "
                              f"PairPipeline(aggregation={kw.get('aggregation')!r})")
+        if kw.get("aggregation") == "patchmatch" or kw.get("pm_params") is not None:
+            # (there are no slices to shard: the search has no cost volume)
+            raise ValueError("PatchMatch stereo is not part of the sharded driver: use PairPipeline(aggregation='patchmatch')")
         if kw.get("aggregation") is not None:
             raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
         self.rank, self.world, self.group = rank, world, group

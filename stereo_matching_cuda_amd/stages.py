@@ -455,6 +455,46 @@ def stereo_pair(gray_l, gray_r, size_d, dminl=None, dminr=0, want_cost=False, wa
     return r
 
 
+def _pm_views(gray_l, gray_r, who):
+    gl, gr = _c(gray_l, np.uint8), _c(gray_r, np.uint8)
+    if gl.ndim != 2 or gr.shape != gl.shape:
+        raise ValueError(f"{who} expects two (h, w) uint8 images of one shape")
+    return gl, gr
+
+
+def patchmatch(gray_l, gray_r, size_d, dminl=None, dminr=0, pm_params=None, params=None):
+    """PatchMatch stereo on two gray images (include/smx.h smx_patchmatch; not a stage of the reference): a disparity plane
+    per pixel instead of a label.  -> dict: planes (2, 3, h, w) = (a, b, d0) of the left and the right view, cost, disp and
+    label (2, h, w), all float32.  pm_params: PMParams or None for the defaults."""
+    gl, gr = _pm_views(gray_l, gray_r, "patchmatch")
+    h, w = gl.shape
+    if dminl is None:
+        dminl = -(size_d - 1)
+    pm = pm_params if pm_params is not None else _lib.default_pm_params()
+    r = {"planes": np.empty((2, 3, h, w), np.float32), "cost": np.empty((2, h, w), np.float32),
+         "disp": np.empty((2, h, w), np.float32), "label": np.empty((2, h, w), np.float32)}
+    _lib.check(_lib.lib().smx_patchmatch(C.byref(_params(params)), C.byref(pm), _ptr(gl), _ptr(gr), w, h, int(size_d), int(dminl),
+                                         int(dminr), _ptr(r["planes"]), _ptr(r["cost"]), _ptr(r["disp"]), _ptr(r["label"])))
+    return r
+
+
+def pm_plane_cost(gray_l, gray_r, planes, size_d, dminl=None, dminr=0, pm_params=None, params=None):
+    """The PatchMatch plane cost of given planes of both views, no search (smx_pm_plane_cost).  planes: (2, 3, h, w) float32,
+    (a, b, d0) of the left and the right view.  -> (2, h, w) float32."""
+    gl, gr = _pm_views(gray_l, gray_r, "pm_plane_cost")
+    h, w = gl.shape
+    pl = _c(planes, np.float32)
+    if pl.shape != (2, 3, h, w):
+        raise ValueError("pm_plane_cost expects planes of shape (2, 3, h, w)")
+    if dminl is None:
+        dminl = -(size_d - 1)
+    pm = pm_params if pm_params is not None else _lib.default_pm_params()
+    cost = np.empty((2, h, w), np.float32)
+    _lib.check(_lib.lib().smx_pm_plane_cost(C.byref(_params(params)), C.byref(pm), _ptr(gl), _ptr(gr), w, h, int(size_d),
+                                            int(dminl), int(dminr), _ptr(pl), _ptr(cost)))
+    return cost
+
+
 def write_mat(mat):
     """Host-side float -> u8 normaliser of main.cu:13-35 (PNG writer input).  The reference's
     loop only lowers `min` on elements that did not raise `max` (`else if`, main.cu:22).
