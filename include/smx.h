@@ -1191,6 +1191,91 @@ int smx_ctx_patchmatch_maps(smx_ctx* ctx, float* planes_l, float* planes_r, floa
  * workspace).  0 for a context whose pairs never ran with it on. */
 int smx_ctx_pm_held(const smx_ctx* ctx, size_t* bytes);
 
+/* ------------------------------------------------------------------------------------
+ * The information permeability filter (Cigla, Alatan, Signal Processing: Image Communication 28, 2013; not a stage of the
+ * reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* Every other aggregation here has a bounded support.  The permeability filter's support is the whole image at full label
+ * resolution, at O(1) per cell: four one-dimensional first-order recurrences per slice (the separable recursive structure of
+ * Gastal and Oliveira's domain transform).  A cost reaches a pixel along an L-shaped path with the product of the permeabilities
+ * on the way as its weight: a flat surface passes information as far as it extends, a gray or colour edge stops it.
+ * tests/perm_ref.py is this definition in numpy; the results equal it bit for bit.
+ *
+ * Parameters.  sigma: finite and > 0; anything else is SMX_E_ARG before any device call.  The default 32.0 is a starting point
+ * chosen on a synthetic textureless band, not measured on real data.
+ *
+ * Table.  t[k] = (float)exp(-(double)k / sigma), k = 0 .. 255, computed on the host in double (smx_perm_table); t[0] == 1.
+ * The kernels hold no transcendental and no floating-point division.
+ *
+ * Guide.  u8 [h][w][channels], channels 1, 3 or 4, interleaved.  diff of two neighbouring pixels: |dI| for one channel, the
+ * maximum of |dI| over R, G, B for 3 or 4 channels (the paper's choice; alpha is ignored).
+ *   mu_h[y][x] = t[diff(I[y][x], I[y][x-1])] for x >= 1;   mu_v[y][x] = t[diff(I[y][x], I[y-1][x])] for y >= 1.
+ *
+ * Per slice C [h][w] of an f32 volume [size_d][h][w], every product and every sum rounded to f32 on its own, no fused
+ * multiply-add; NaN, infinities and subnormals as IEEE 754 says.  Along every row:
+ *   LR[0] = C[0],      LR[x] = C[x] + mu_h[x] * LR[x-1]     x ascending
+ *   RL[w-1] = C[w-1],  RL[x] = C[x] + mu_h[x+1] * RL[x+1]   x descending
+ *   Hh[x] = (LR[x] + RL[x]) - C[x]
+ * and the same three lines along every column of Hh with mu_v: TB, BT, out = (TB + BT) - Hh.
+ *
+ * The output is NOT normalised, as in the paper: a pixel's total weight depends on the guide only and is the same for every
+ * label, so the winners, the parabola and equiangular sub-pixel fits, the uniqueness ratio and the comparisons of the
+ * depth-discontinuity adjustment are what they would be on the normalised volume.  The filtered costs (best_*, agg_*) are
+ * weighted SUMS, not means.
+ *
+ * Winners.  From out by the packed key's rule with the slices ascending: smallest cost, the last slice among equal costs, a NaN
+ * never -- the natural-order winner-take-all pass of the aggregations.
+ *
+ * What it cannot do alone: on hard random texture every permeability is near 0 and a pixel keeps its own cost.  The context
+ * therefore runs it BEHIND the guided filter, which supplies the local support; the permeability pass supplies the reach.
+ *
+ * smx_perm_workspace_bytes: the workspace with which a call on nviews views of size_d slices runs as one chunk whatever its
+ * outputs (0 for w, h or size_d < 1, w*h >= 2^31, size_d > 2^20 or nviews not 1 or 2): per view two weight planes, and per slice
+ * a scratch plane (LR, then TB) and a plane of the filtered slice, which a call with d_out == NULL keeps there.  A smaller
+ * workspace makes the call go in chunks of slices, with the same bits; one that does not hold one slice -- nviews * w * h * 4 *
+ * 3 bytes with d_out, * 4 without -- is SMX_E_WS before anything is launched.
+ *
+ * smx_dev_permeability_wta_pair: on `stream`; no allocation, no synchronisation (graph-capturable); a weight launch, then per
+ * chunk the horizontal pass, the vertical pass and the winner-take-all pass.  d_vol_r and d_guide_r may both be NULL for a
+ * one-view call (or d_vol_l and d_guide_l).  Outputs as in the other pair entries: with both views the left view's first, the
+ * right view's behind it; the one view of a one-view call at the front.
+ *   d_out   OUT  f32 [views][size_d][h][w] or NULL: the filtered volumes.  A view's part may BE that view's input volume (in
+ *                place); no other overlap between any two buffers of the call is allowed
+ *   d_keys  OUT  int64 [views][h][w] or NULL: the packed keys of out (written fresh).  NULL: no winner-take-all pass, and d_nbr
+ *                and d_uq must be NULL
+ *   d_nbr   OUT  f32 [views][3][h][w] or NULL: the winners' neighbour state as smx_dev_aggregate_wta_nbr leaves it
+ *   d_uq    OUT  f32 [views][3][h][w] or NULL: the second-best state as smx_dev_aggregate_wta_pair_uq leaves it
+ * Nothing else is written but [0, ws_bytes) of d_ws.  dminl / dminr: the views' first labels (the keys hold slices: they are
+ * checked and otherwise unused).  w, h >= 1, w*h < 2^31, 1 <= size_d <= 2^20; volumes and workspace 4-byte aligned.
+ * smx_set_max_slices_per_launch of the calling thread bounds the chunk too.
+ *
+ * smx_permeability_filter: host pointers, one view, synchronous.  out (the filtered volume), best (the winners' costs) and
+ * disp_map (dmin + winning slice) may each be NULL. */
+typedef struct smx_perm_params { double sigma; } smx_perm_params;
+void smx_default_perm_params(smx_perm_params* p);
+int smx_perm_table(const smx_perm_params* p, float* t /* [256] */);
+size_t smx_perm_workspace_bytes(int w, int h, int size_d, int nviews);
+int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l, const float* d_vol_r, const uint8_t* d_guide_l,
+                                  const uint8_t* d_guide_r, int channels, int w, int h, int dminl, int dminr, int size_d,
+                                  int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_permeability_filter(const smx_perm_params* p, const float* volume, const uint8_t* guide, int channels, int w, int h, int dmin,
+                            int size_d, float* out, float* best, float* disp_map);
+/* The permeability filter of this context.  NULL switches it off (the default: nothing is allocated or launched).  While it is
+ * on, smx_ctx_stereo_pair / _rgb keeps the aggregated volumes as when agg_l is requested, runs smx_dev_permeability_wta_pair in
+ * place over them and replaces the plain winners.  Everything behind runs unchanged on the new keys and volumes: best_*, dmap_*,
+ * the sub-pixel neighbours, the uniqueness state, LR check, speckle removal, vote, fill, the depth-discontinuity adjustment (it
+ * reads the filtered left volume) and the weighted median; out->agg_l / agg_r return the filtered volumes.  Guide: the context's
+ * gray images, or the colour pair under SMX_GUIDE_RGB.  Supported: the guided filter with either guide under the reference,
+ * census and AD-Census costs.  The pair call returns SMX_E_ARG with a message for SGM, cross-based aggregation and the scan-line
+ * optimiser (integer [y][x][d] volumes), PatchMatch (no volume), cross-scale aggregation (not built yet) and out->mean_l /
+ * mean_r; smx_ctx_stereo_pair_async returns it while the setting is on.  The sharded and multi-GPU drivers do not take it.  The
+ * workspace is allocated by the first pair that runs with it on (at most ~1 GiB: the pass goes in chunks of slices). */
+int smx_ctx_set_permeability(smx_ctx* ctx, const smx_perm_params* p);
+/* Test hook, NOT part of the stable contract: the device bytes the context holds for the permeability filter.  0 for a context
+ * whose pairs never ran with it on. */
+int smx_ctx_perm_held(const smx_ctx* ctx, size_t* bytes);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

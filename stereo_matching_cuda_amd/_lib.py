@@ -93,6 +93,11 @@ class PMParams(C.Structure):
                 ("seed", C.c_uint32)]
 
 
+class PermParams(C.Structure):
+    """smx_perm_params: the information permeability filter (not a stage of the reference)."""
+    _fields_ = [("sigma", C.c_double)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -127,6 +132,7 @@ _MP = C.POINTER(PMParams)
 _JP = C.POINTER(AdjustParams)
 _KP = C.POINTER(CScaleParams)
 _ip = C.POINTER(C.c_int)
+_EP = C.POINTER(PermParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -270,6 +276,13 @@ SIGNATURES = {
     "smx_ctx_set_patchmatch": (_i, [_vp, _MP]),
     "smx_ctx_patchmatch_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "smx_ctx_pm_held": (_i, [_vp, C.POINTER(_sz)]),
+    "smx_default_perm_params": (None, [_EP]),
+    "smx_perm_table": (_i, [_EP, _vp]),
+    "smx_perm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_permeability_wta_pair": (_i, [_EP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_permeability_filter": (_i, [_EP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "smx_ctx_set_permeability": (_i, [_vp, _EP]),
+    "smx_ctx_perm_held": (_i, [_vp, C.POINTER(_sz)]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -402,6 +415,19 @@ def default_pm_params():
     p = PMParams()
     lib().smx_default_pm_params(C.byref(p))
     return p
+
+
+def default_perm_params():
+    p = PermParams()
+    lib().smx_default_perm_params(C.byref(p))
+    return p
+
+
+def perm_table(params):
+    """The 256 permeabilities exp(-k / sigma) of the permeability filter (smx_perm_table) as a list of floats."""
+    t = (C.c_float * 256)()
+    check(lib().smx_perm_table(C.byref(params), t))
+    return list(t)
 
 
 def pm_weights(params):

@@ -3,6 +3,7 @@
 #pragma once
 #include "smx_agg.h"
 #include "smx_cscale_host.h"
+#include "smx_perm_host.h"
 
 namespace smx {
 
@@ -66,6 +67,9 @@ bool pm_params_ok(const smx_pm_params* p);             // (smx_patchmatch.hip, b
 bool pm_shape_ok(int w, int h, int size_d, int dminl, int dminr);
 constexpr const char* PM_RANGES = "needs 0 <= radius <= 17, a finite gamma > 0, 1 <= iterations <= 16 and 0 <= max_slope <= 8";
 constexpr const char* PM_SHAPES = "needs w, h >= 1, w < 2^24, w*h < 2^31, 1 <= size_d <= 2^20 and |dminl|, |dminr| <= 2^20";
+bool perm_shape_ok(int w, int h, int size_d);          // (smx_perm.hip)
+constexpr const char* PERM_RANGES = "needs a finite sigma > 0";
+constexpr const char* PERM_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 2^20";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

@@ -936,6 +936,45 @@ int smx_dev_pm_sub_filled(const float* d_disp, const float* d_kept, const float*
     return launch_pm_sub_filled(d_disp, d_kept, d_filled, (size_t)w * h, dminl, d_out, (hipStream_t)stream);
 }
 
+// ---- the permeability filter (not in the reference; smx_perm.hip) ---------------------------------------------------------
+void smx_default_perm_params(smx_perm_params* p) {
+    if (!p) return;
+    p->sigma = 32.0;
+}
+
+int smx_perm_table(const smx_perm_params* p, float* t) {
+    if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_perm_table: %s", PERM_RANGES);
+    SMX_ARG(t != nullptr);
+    perm_table(p, t);
+    return SMX_OK;
+}
+
+size_t smx_perm_workspace_bytes(int w, int h, int size_d, int nviews) {
+    return perm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? perm_workspace_bytes(w, h, size_d, nviews) : 0;
+}
+
+int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l, const float* d_vol_r, const uint8_t* d_guide_l,
+                                  const uint8_t* d_guide_r, int channels, int w, int h, int dminl, int dminr, int size_d,
+                                  int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: %s", PERM_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!perm_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: %s", PERM_SHAPES);
+    SMX_ARG((d_vol_l || d_vol_r) && !d_guide_l == !d_vol_l && !d_guide_r == !d_vol_r);
+    SMX_ARG(d_keys || (!d_nbr && !d_uq));
+    SMX_ARG(dminl >= -(1 << 29) && dminl <= (1 << 29) && dminr >= -(1 << 29) && dminr <= (1 << 29));
+    if ((((uintptr_t)d_vol_l | (uintptr_t)d_vol_r | (uintptr_t)d_out | (uintptr_t)d_ws) & 3) != 0)
+        return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: a volume or the workspace is not 4-byte aligned");
+    const int nviews = d_vol_l && d_vol_r ? 2 : 1;
+    const int chunk = d_ws ? perm_chunk(w, h, nviews, ws_bytes, size_d, d_out == nullptr, g_max_chunk) : 0;
+    if (chunk < 1)
+        return fail(SMX_E_WS, "smx_dev_permeability_wta_pair: workspace of %zu bytes, %zu needed for one slice in flight",
+                    d_ws ? ws_bytes : (size_t)0, (size_t)nviews * w * h * sizeof(float) * (d_out ? 3 : 4));
+    float table[256];
+    perm_table(p, table);
+    return launch_perm_wta_pair(table, d_vol_l, d_vol_r, d_guide_l, d_guide_r, channels, w, h, size_d, d_keys, d_out, d_nbr, d_uq,
+                                d_ws, chunk, (hipStream_t)stream);
+}
+
 // Test hook (not in include/smx.h): the natural-order winner-take-all pass of the aggregations (wta_launch, smx_wta.h) over one
 // materialised volume d_q [count][h][w], fresh keys out -- what tests/test_gpu_cscale.py holds the one-scale combination to.
 __attribute__((visibility("default"))) int smx_debug_wta_natural(const float* d_q, int w, int h, int count, int64_t* d_keys,

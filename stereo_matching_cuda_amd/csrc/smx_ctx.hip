@@ -79,6 +79,10 @@ struct smx_ctx {
     bool pm_valid = false;      // the maps belong to the last synchronous pair
     smx_pm_params pm_params;
     DevBuf pm_planes, pm_disp, pm_ws;
+    // the permeability filter (smx_ctx_set_permeability): it runs in place over both volumes of aggLR; its workspace
+    bool perm = false;
+    smx_perm_params perm_params;
+    DevBuf perm_ws;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -117,7 +121,17 @@ struct smx_ctx {
 // device (best / map / mean: left view first, right view behind it).
 // cscale: the winners come from the cross-scale combination; level: this pair is a level of another context's pyramid, which
 // wants its aggregated volumes and nothing behind them.  pm: PatchMatch stereo in place of cost, aggregation and winners.
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm; };
+// perm: the winners come from the permeability filter over the aggregated volumes.
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm, perm; };
+
+// The permeability filter's workspace for both views: every slice at once where that stays within ~1 GiB, else what does, and one
+// slice at least (the pass goes in chunks of slices over the volumes it filters in place)
+static size_t ctx_perm_ws_bytes(const smx_ctx* c) {
+    const size_t cap = (size_t)1 << 30, per = 2 * c->n * sizeof(float);
+    size_t k = cap / per > 2 ? cap / per - 2 : 1;
+    if (k > (size_t)c->size_d) k = (size_t)c->size_d;
+    return per * (2 + k);
+}
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -149,6 +163,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
         SMX_HIP(c->vote_ws.ensure(vote_workspace_bytes(c->w, c->h)));
     }
     if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
+    if (need.perm) SMX_HIP(c->perm_ws.ensure(ctx_perm_ws_bytes(c)));
     if (need.pm) {
         SMX_HIP(c->pm_planes.ensure(6 * fb));
         SMX_HIP(c->pm_disp.ensure(2 * fb));
@@ -328,10 +343,10 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         if ((rc = smx_dev_cost_volume(p, in.right, in.left, costR, w, w, h, in.dminr, 0, size_d, st))) return rc;
     }
     if ((rc = smx_dev_init_keys(keysL, 2 * (int64_t)n, st))) return rc;
-    // (with cross-scale the states come from the combination pass: the level-0 aggregation keeps none.  Its keys are
+    // (with cross-scale or the permeability filter the states come from that pass: the aggregation keeps none.  Its keys are
     // overwritten too, but the fused aggregation has no form without its winner-take-all pass.)
-    float* const nbrA = need.cscale ? nullptr : nbrL;
-    float* const uqA = need.cscale ? nullptr : uqL;
+    float* const nbrA = need.cscale || need.perm ? nullptr : nbrL;
+    float* const uqA = need.cscale || need.perm ? nullptr : uqL;
     // main.cu:133-134, both views per call, on the context's own path
     const AggCall call = {"smx_ctx_stereo_pair", p, 2, {in.left, in.right}, {in.right, in.left}, {costL, costR},
                           {in.dminl, in.dminr}, {keysL, keysL + n}, {out.mean, out.mean + n},
@@ -379,6 +394,14 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
             ar[s] = al[s] + (size_t)k->size_d * k->n;
         }
         if ((rc = smx_dev_cscale_wta_pair(&c->cs_params, al, ar, w, h, in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, st)))
+            return rc;
+    }
+    if (need.perm) {
+        // the filter goes over both aggregated volumes in place; its winners and states take the place of the plain ones
+        const bool colour = need.cgf;
+        if ((rc = smx_dev_permeability_wta_pair(&c->perm_params, aggL, aggL + (size_t)size_d * n, colour ? in.rgb_l : in.left,
+                                                colour ? in.rgb_r : in.right, colour ? in.channels : 1, w, h, in.dminl, in.dminr,
+                                                size_d, keysL, aggL, nbrL, uqL, c->perm_ws.p, ctx_perm_ws_bytes(c), st)))
             return rc;
     }
     // main.cu:112-118 presets, winning slices, main.cu:140-155
@@ -575,6 +598,17 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     if (cscale && (out->mean_l || out->mean_r))
         return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) produces no mean images", who);
     if (cscale && !cscale_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: cross-scale aggregation %s", who, CSCALE_SHAPES);
+    const bool perm = c->perm;
+    if (perm && (sgm || cross || so))
+        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) runs behind the guided filter: %s keeps "
+                               "integer [y][x][d] volumes", who,
+                    sgm ? "semi-global matching" : so ? "the scan-line optimiser" : "cross-based aggregation");
+    if (perm && cscale)
+        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) and cross-scale aggregation "
+                               "(smx_ctx_set_cross_scale) are both on: not built yet", who);
+    if (perm && (out->mean_l || out->mean_r))
+        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) produces no mean images", who);
+    if (perm && !perm_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: the permeability filter %s", who, PERM_SHAPES);
     const bool pm = c->pm;
     if (pm) {
         // PatchMatch keeps no cost volume: every stage that reads one has nothing to read, and the rest is out of scope
@@ -585,6 +619,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
                            : cross                            ? "cross-based aggregation (smx_ctx_set_cross)"
                            : so                               ? "the scan-line optimiser (smx_ctx_set_scanline)"
                            : cscale                           ? "cross-scale aggregation (smx_ctx_set_cross_scale)"
+                           : c->perm                          ? "the permeability filter (smx_ctx_set_permeability)"
                            : c->adjust                        ? "the depth-discontinuity adjustment (smx_ctx_set_adjust)"
                            : c->uniq > 0.0f                   ? "the uniqueness test (smx_ctx_set_uniqueness)"
                            : c->subpix                        ? "the sub-pixel fit (smx_ctx_set_subpixel; the planes are sub-pixel already)"
@@ -598,9 +633,9 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     }
     // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
     // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale, c->subpix != 0,
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale || perm, c->subpix != 0,
                             c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
-                            c->adjust, cscale, false, pm};
+                            c->adjust, cscale, false, pm, perm};
     if ((rc = ctx_reserve(c, need))) return rc;
     if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
@@ -658,6 +693,23 @@ int smx_ctx_stereo_pair_rgb(smx_ctx* c, const uint8_t* rgb_l, const uint8_t* rgb
                             const smx_pair_out* out) {
     SMX_ARG(c && rgb_l && rgb_r && out && (channels == 3 || channels == 4));
     return ctx_pair(c, "smx_ctx_stereo_pair_rgb", rgb_l, rgb_r, channels, dminl, dminr, out);
+}
+
+int smx_ctx_set_permeability(smx_ctx* c, const smx_perm_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_permeability: %s", PERM_RANGES);
+        c->perm_params = *p;
+    }
+    c->perm = p != nullptr;
+    return SMX_OK;
+}
+
+// Test hook (include/smx.h): what the permeability filter holds on the device
+int smx_ctx_perm_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = c->perm_ws.p ? c->perm_ws.bytes : 0;
+    return SMX_OK;
 }
 
 int smx_ctx_set_guidance(smx_ctx* c, int mode) {
@@ -917,6 +969,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the depth-discontinuity adjustment is on (smx_ctx_set_adjust): use smx_ctx_stereo_pair");
     if (c->cscale)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-scale aggregation is on (smx_ctx_set_cross_scale): use smx_ctx_stereo_pair");
+    if (c->perm)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the permeability filter is on (smx_ctx_set_permeability): use smx_ctx_stereo_pair");
     if (c->pm)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: PatchMatch stereo is on (smx_ctx_set_patchmatch): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)

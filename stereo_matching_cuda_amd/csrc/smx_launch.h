@@ -111,4 +111,12 @@ int launch_pm_plane_cost(const smx_params* p, const smx_pm_params* pm, const uin
 void pm_tile(int* tw, int* th);
 // (a pair's sub-pixel filled map from PatchMatch: disp where `kept` passes fill_occlusion's validity test, `filled` elsewhere)
 int launch_pm_sub_filled(const float* disp, const float* kept, const float* filled, size_t n, int dminl, float* out, hipStream_t st);
+// smx_perm.hip: the permeability filter and the winner-take-all pass over it (smx_dev_permeability_wta_pair); table: the 256
+// weights on the host (smx_perm_host.h); ws: perm_workspace_bytes bytes for the slices in flight, chunk: perm_chunk of that
+// workspace (>= 1; own_out: the call keeps no volume, so the filtered slices live in the workspace too)
+size_t perm_workspace_bytes(int w, int h, int nslices, int nviews);
+int perm_chunk(int w, int h, int nviews, size_t ws_bytes, int count, bool own_out, int max_chunk);
+int launch_perm_wta_pair(const float* table, const float* vol_l, const float* vol_r, const uint8_t* guide_l, const uint8_t* guide_r,
+                         int ch, int w, int h, int size_d, int64_t* keys, float* out, float* nbr, float* uq, void* ws, int chunk,
+                         hipStream_t st);
 }  // namespace smx

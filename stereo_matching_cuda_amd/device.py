@@ -27,7 +27,8 @@ class PairPipeline:
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
                  aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
-                 vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None, pm_params=None):
+                 vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None, pm_params=None,
+                 permeability=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
         the reference; smx_dev_weighted_median behind the finish on the same stream, into self.refined): "occluded"
         filters the pixels the LR check invalidated, "all" every pixel.  With None nothing is allocated or launched.
@@ -119,7 +120,28 @@ class PairPipeline:
         speckle removal and region voting behind them unchanged, then self.sub_filled = the left disp where the pixel was
         kept, the filled label elsewhere (smx_dev_pm_sub_filled), then the weighted median.  There is no cost volume: cost=,
         guidance=, cross_scale=, adjust=, uniqueness=, subpixel=, want_agg=, caller's cost volumes and a slice sub-range raise
-        ValueError.  self.mean stays zero and self.keys is not written."""
+        ValueError.  self.mean stays zero and self.keys is not written.
+        permeability: None, True (the default sigma 32.0, a starting point chosen on a synthetic band) or PermParams -- the
+        information permeability filter (Cigla & Alatan 2013; not a stage of the reference; include/smx.h
+        smx_dev_permeability_wta_pair): full-image edge-aware aggregation behind the guided filter.  aggregate() keeps the
+        aggregated volumes in self.agg as with want_agg, runs the filter in place over them (guide: the gray images, or the
+        colour pair with guidance="rgb") and replaces self.keys, self.nbr and self.uq with the winners and states of the
+        filtered volumes, whose costs are weighted sums, not means.  Everything in finish() runs unchanged behind it.  With the
+        guided filter only (either guide; the reference, census and AD-Census costs): aggregation= and cross_scale= raise
+        ValueError, and so does a slice sub-range.  Its workspace (self.perm_ws, at most ~1 GiB: the pass goes in chunks of
+        slices) is not counted in max_ws_bytes.  With None nothing is allocated or launched."""
+        if permeability is not None and permeability is not True and not isinstance(permeability, _lib.PermParams):
+            raise ValueError(f"permeability must be None, True or PermParams, not {permeability!r}")
+        if isinstance(permeability, _lib.PermParams) and not (0.0 < permeability.sigma < float("inf")):
+            raise ValueError("permeability needs a finite sigma > 0")
+        if permeability is not None:
+            if aggregation is not None:
+                raise ValueError(f"the permeability filter runs behind the guided filter: not with aggregation={aggregation!r}")
+            if cross_scale is not None:
+                raise ValueError("the permeability filter is not built behind cross-scale aggregation: not with cross_scale=")
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("the permeability filter runs over whole volumes: no slice sub-range")
+            want_agg = True
         pm = aggregation == "patchmatch"
         if pm_params is not None and not pm:
             raise ValueError("pm_params belongs to aggregation='patchmatch'")
@@ -359,6 +381,16 @@ class PairPipeline:
             self.pm_disp = torch.empty((2, self.h, self.w), **f)
             self.pm_ws = torch.empty(self.pm_ws_bytes, dtype=torch.uint8, device=dev)
             self.sub_filled = torch.empty((self.h, self.w), **f)
+        self.permeability = _lib.default_perm_params() if permeability is True else permeability
+        self.perm_ws, self.perm_ws_bytes = None, 0
+        if self.permeability:
+            if self.lib.smx_perm_workspace_bytes(self.w, self.h, self.size_d, 2) == 0:
+                raise ValueError(f"the permeability filter does not take {self.w} x {self.h} x {self.size_d} "
+                                 "(w*h < 2^31, size_d <= 2^20)")
+            # both views: two weight planes and a scratch plane per slice in flight, every slice at once within ~1 GiB
+            per = 2 * self.n * 4
+            self.perm_ws_bytes = per * (2 + min(self.size_d, max(1, (1 << 30) // per - 2)))
+            self.perm_ws = torch.empty(self.perm_ws_bytes, dtype=torch.uint8, device=dev)
         self.cross_scale = _lib.default_cscale_params() if cross_scale is True else cross_scale
         self.cs_levels, self.cs_gray, self.cs_rgb = [], [], []
         if self.cross_scale:
@@ -393,6 +425,18 @@ class PairPipeline:
         self._aggregate_level(gray_l, gray_r, cost_l, cost_r, rgb_l, rgb_r)
         if self.cross_scale:
             self._cross_scale(gray_l, gray_r)
+        if self.permeability:
+            self._permeability(gray_l, gray_r)
+
+    def _permeability(self, gray_l, gray_r):
+        """smx_dev_permeability_wta_pair in place over self.agg: the filtered volumes, and self.keys (self.nbr, self.uq) their
+        winners (and states).  Guide: the colour pair of this aggregation under guidance="rgb", else the gray images."""
+        gl, gr, ch = (self._rgb[0], self._rgb[1], int(self._rgb[0].shape[2])) if self.guidance else (gray_l, gray_r, 1)
+        with self._on_device():
+            _lib.check(self.lib.smx_dev_permeability_wta_pair(C.byref(self.permeability), _dp(self.agg[0]), _dp(self.agg[1]),
+                                                              _dp(gl), _dp(gr), ch, self.w, self.h, self.dminl, self.dminr,
+                                                              self.size_d, _dp(self.keys), _dp(self.agg), _dp(self.nbr),
+                                                              _dp(self.uq), _dp(self.perm_ws), self.perm_ws_bytes, self._stream()))
 
     def _cross_scale(self, gray_l, gray_r):
         """Levels 1 .. of both views' pyramids through self.cs_levels, then smx_dev_cscale_wta_pair over every level's volumes:

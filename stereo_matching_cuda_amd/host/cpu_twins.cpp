@@ -22,6 +22,8 @@
 #include "integral.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
+#include "permeability.cuh"
+#include "../csrc/smx_perm_host.h"        // the library's own weight table: no HIP in it
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "scanlineOptimization.cuh"
@@ -746,6 +748,86 @@ void patchMatchOnCPU(const unsigned char* left, const unsigned char* right, floa
             disp[n * v.view + id] = v.d0[id];
             label[n * v.view + id] = pm_clamp(std::floor(v.d0[id] + 0.5f), v.dmin, v.dmax);
         }
+}
+
+// ---- permeability.cuh (not in the reference) -------------------------------------------------------
+// The definition of include/smx.h (above smx_perm_params), scalar: per slice and row LR, RL and Hh, then per column of Hh TB, BT
+// and out; every product and sum an f32 of its own (the file is compiled with -ffp-contract=off).  The winner by `best >= q`
+// over ascending slices.
+void permeabilityOnCPU(const float* volume, const unsigned char* guide, const int channels, float* out, float* best, float* disp_map,
+                       const int w, const int h, const int dmin, const int size_d, const smx_perm_params& p) {
+    if (!smx::perm_params_ok(&p)) return;
+    float t[256];
+    smx::perm_table(&p, t);              // (what smx_perm_table runs)
+    const size_t n = (size_t)w * h;
+    auto diff = [&](size_t a, size_t b) {
+        int d = 0;
+        for (int c = 0; c < (channels == 1 ? 1 : 3); ++c) {
+            const int e = std::abs((int)guide[a * channels + c] - (int)guide[b * channels + c]);
+            d = e > d ? e : d;
+        }
+        return d;
+    };
+    std::vector<float> mu_h(n, 0.0f), mu_v(n, 0.0f), hh(n), fwd((size_t)(w > h ? w : h)), slice(n);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t id = (size_t)y * w + x;
+            if (x >= 1) mu_h[id] = t[diff(id, id - 1)];
+            if (y >= 1) mu_v[id] = t[diff(id, id - (size_t)w)];
+        }
+    std::vector<float> m(n, std::numeric_limits<float>::infinity());
+    std::vector<int> zm(n, -1);
+    for (int z = 0; z < size_d; ++z) {
+        const float* C = volume + (size_t)z * n;
+        for (int y = 0; y < h; ++y) {
+            const float* c = C + (size_t)y * w;
+            const float* mu = mu_h.data() + (size_t)y * w;
+            fwd[0] = c[0];
+            for (int x = 1; x < w; ++x) {
+                const float pr = mu[x] * fwd[(size_t)x - 1];
+                fwd[(size_t)x] = c[x] + pr;
+            }
+            float rl = c[w - 1];
+            for (int x = w - 1; x >= 0; --x) {
+                if (x < w - 1) {
+                    const float pr = mu[x + 1] * rl;
+                    rl = c[x] + pr;
+                }
+                const float s = fwd[(size_t)x] + rl;
+                hh[(size_t)y * w + x] = s - c[x];
+            }
+        }
+        for (int x = 0; x < w; ++x) {
+            fwd[0] = hh[(size_t)x];
+            for (int y = 1; y < h; ++y) {
+                const float pr = mu_v[(size_t)y * w + x] * fwd[(size_t)y - 1];
+                fwd[(size_t)y] = hh[(size_t)y * w + x] + pr;
+            }
+            float bt = hh[(size_t)(h - 1) * w + x];
+            for (int y = h - 1; y >= 0; --y) {
+                const size_t id = (size_t)y * w + x;
+                if (y < h - 1) {
+                    const float pr = mu_v[id + (size_t)w] * bt;
+                    bt = hh[id] + pr;
+                }
+                const float s = fwd[(size_t)y] + bt;
+                slice[id] = s - hh[id];
+            }
+        }
+        for (size_t id = 0; id < n; ++id) {
+            const float o = slice[id];
+            if (out) out[(size_t)z * n + id] = o;
+            if (o <= m[id]) { m[id] = o; zm[id] = z; }
+        }
+    }
+    const uint32_t none = 0x7FFFFFFFu;
+    for (size_t id = 0; id < n; ++id) {
+        if (best) {
+            if (zm[id] < 0) memcpy(&best[id], &none, 4);
+            else best[id] = m[id] == 0.0f ? 0.0f : m[id];
+        }
+        if (disp_map) disp_map[id] = (float)(dmin + (zm[id] < 0 ? 0 : zm[id]));
+    }
 }
 
 // ---- occlusion.cuh -------------------------------------------------------------------------

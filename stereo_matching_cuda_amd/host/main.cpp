@@ -74,6 +74,15 @@
 //                     map once more.  With --host-compare the CPU twins (pyrDownOnCPU, the cost and guided-filter twins at every
 //                     level, crossScaleOnCPU) redo both views and check_errors compares.  Not with --aggregation sgm | cross |
 //                     scanline | cross-scanline, --ngpu or --pipeline
+//   --permeability [SIGMA]  the information permeability filter behind the guided filter (smx_ctx_set_permeability; Cigla & Alatan
+//                     2013, not in the reference; implies --fused): full-image edge-aware aggregation of the aggregated volumes
+//                     by four recurrences per slice, with exp(-|dI| / SIGMA) between neighbours (finite, > 0; default 32, a
+//                     starting point chosen on a synthetic band, not measured on real data).  The value is optional, like
+//                     --vote's.  With the gray or the colour guide and every --cost; the twelve images come from the filtered
+//                     winners (their costs are weighted sums, not means), the two mean images are empty, and
+//                     disparity_mapl_perm.png holds the left map once more.  With --host-compare the CPU twins (the cost and
+//                     guided-filter twins, permeabilityOnCPU) redo both views and check_errors compares.  Not with --aggregation
+//                     sgm | cross | scanline | cross-scanline | patchmatch, --cross-scale, --ngpu or --pipeline
 //   --aggregation sgm semi-global matching instead of the guided filter (smx_ctx_set_aggregation; implies --fused, and the
 //                     census cost, --census-window / --census-th included, unless --cost reference is given): the same
 //                     twelve images, the two mean images empty.
@@ -147,6 +156,7 @@
 #include "helpers.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
+#include "permeability.cuh"
 #include "png_io.h"
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
@@ -188,6 +198,8 @@ struct Options {
     smx_cross_params vote_arms;
     bool adjust = false;     // --adjust
     smx_adjust_params adjust_params;
+    bool perm = false;       // --permeability
+    smx_perm_params perm_params;
     bool cscale = false;     // --cross-scale
     smx_cscale_params cs_params;
     bool pm = false;         // --aggregation patchmatch
@@ -364,6 +376,12 @@ const ValueOption optional_value_options[] = {
          const int got = std::sscanf(v.c_str(), "%d%c%d%c%d%c", &p.tau_s, &c1, &p.tau_h_pct, &c2, &p.iterations, &rest);
          return ((got == 3 && c1 == ',') || (got == 5 && c1 == ',' && c2 == ',')) && p.tau_s >= 0 && p.tau_h_pct >= 0 &&
                 p.tau_h_pct <= 99 && p.iterations >= 0 && p.iterations <= 8; }},
+    {"--permeability", "a finite SIGMA > 0", [](auto& v, auto& o) {
+         o.perm = true;
+         if (v.empty()) return true;
+         char rest = 0;
+         const int got = std::sscanf(v.c_str(), "%lf%c", &o.perm_params.sigma, &rest);
+         return got == 1 && std::isfinite(o.perm_params.sigma) && o.perm_params.sigma > 0.0; }},
     {"--cross-scale", "S[,LAMBDA] with 1 <= S <= 5 and a finite LAMBDA >= 0", [](auto& v, auto& o) {
          smx_cscale_params& p = o.cs_params;
          o.cscale = true;
@@ -398,6 +416,7 @@ Options parse(int argc, char** argv) {
     smx_default_cross_params(&o.vote_arms);
     smx_default_adjust_params(&o.adjust_params);
     smx_default_cscale_params(&o.cs_params);
+    smx_default_perm_params(&o.perm_params);
     smx_default_pm_params(&o.pm_params);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
@@ -440,7 +459,11 @@ Options parse(int argc, char** argv) {
          "--vote-interpolate, --vote-arms and --vote-tau need --vote"},
         {o.saw({"--adjust-vertical"}) && !o.adjust, "--adjust-vertical needs --adjust"},
         {o.saw({"--pm-radius", "--pm-gamma", "--pm-iterations", "--pm-slope", "--pm-seed"}) && !o.pm,
-         "--pm-radius, --pm-gamma, --pm-iterations, --pm-slope and --pm-seed need --aggregation patchmatch"}};
+         "--pm-radius, --pm-gamma, --pm-iterations, --pm-slope and --pm-seed need --aggregation patchmatch"},
+        {o.perm && (o.sgm || o.cross || o.so || o.pm),
+         "--permeability runs behind the guided filter: it cannot be combined with --aggregation sgm, cross, scanline, "
+         "cross-scanline or patchmatch"},
+        {o.perm && o.cscale, "--permeability cannot be combined with --cross-scale"}};
     for (const Rule& r : rules)
         if (r.refused) return refuse(r.message);
     return o;
@@ -477,6 +500,7 @@ struct Maps {
     std::vector<float> occlusion, filled;
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
+    std::vector<float> perm;           // --permeability: the left map of the filtered winners (= dmap[0])
     std::vector<float> cscale;         // --cross-scale: the left map of the combined winners (= dmap[0])
     std::vector<float> pm_disp;        // --aggregation patchmatch: the fractional left map (the planes' d0)
     std::vector<float> adjusted;       // --adjust: the filled left map with the pixels beside its depth steps adjusted (= filled)
@@ -544,6 +568,50 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         std::cout << (opt.sgm ? "Semi-global matching" : opt.so ? "Scan-line optimisation" : opt.rgb ? "Colour guided filter"
                                                                                                       : "Cross-based aggregation") << " ok!"
                   << std::endl;
+}
+
+// --host-compare of --permeability: per view the cost of the options and the guided-filter twin slice by slice (from the preset,
+// a slice's filtered cost is its aggregated plane) or the colour-guided twin, then the permeability twin on the context's guide;
+// its winners against the pair's, and the left filtered volume against the context's where that was fetched.
+void check_permeability_twin(const Job& j, Maps& m, std::vector<float>& agg_l) {
+    const Options& opt = j.opt;
+    const int ch = j.in.channels[0];
+    const size_t n = (size_t)j.n;
+    bool ok = true;
+    for (int v = 0; v < 2; ++v) {
+        std::vector<float> cost(n * j.size_d), vol(n * j.size_d), tb(n), td(n);
+        std::vector<unsigned char> mean(n);
+        build_cost(j, v, j.size_d, cost.data(), false);
+        if (opt.rgb) {
+            std::memset(tb.data(), 0x7F, sizeof(float) * n);
+            colour_guided_filterOnCPU(j.in.rgb[v], ch, cost.data(), tb.data(), td.data(), vol.data(), j.w, j.h, j.size_d, j.dmin[v],
+                                      smx_config().params.radius, smx_config().params.eps);
+        } else {
+            std::memset(vol.data(), 0x7F, sizeof(float) * vol.size());
+            for (int z = 0; z < j.size_d; ++z)
+                guided_filter_onCpu(j.gray[v], cost.data() + z * n, vol.data() + z * n, td.data(), mean.data(), j.w, j.h, 1,
+                                    j.dmin[v] + z);
+        }
+        std::vector<float> out(n * j.size_d), best(n), disp(n);
+        permeabilityOnCPU(vol.data(), opt.rgb ? j.in.rgb[v] : j.gray[v], opt.rgb ? ch : 1, out.data(), best.data(), disp.data(), j.w,
+                          j.h, j.dmin[v], j.size_d, opt.perm_params);
+        // the winners through the reference's presets, as the pair's finish takes them
+        std::fill(td.begin(), td.end(), 0.0f);
+        std::memset(tb.data(), 0x7F, sizeof(float) * n);
+        for (size_t i = 0; i < n; ++i)
+            if (tb[i] >= best[i]) { tb[i] = best[i]; td[i] = disp[i]; }
+        ok = check_errors(tb.data(), m.best[v].data(), j.n) && ok;
+        ok = check_errors(td.data(), m.dmap[v].data(), j.n) && ok;
+        if (v == 0 && !agg_l.empty()) {
+            for (size_t i = 0; i < out.size(); ++i)
+                if (std::memcmp(&out[i], &agg_l[i], 4) != 0 && !(out[i] != out[i] && agg_l[i] != agg_l[i])) {
+                    std::cout << "error at element " << i << " of the filtered left volume" << std::endl;
+                    ok = false;
+                    break;
+                }
+        }
+    }
+    if (ok) std::cout << "Permeability ok!" << std::endl;
 }
 
 // --host-compare of --cross-scale: per view and level the pyramid twin, the cost of the options at the level's geometry and the
@@ -762,11 +830,12 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     std::memset(&out, 0, sizeof(out));
     out.best_l = m.best[0].data(); out.best_r = m.best[1].data();
     out.dmap_l = m.dmap[0].data(); out.dmap_r = m.dmap[1].data();
-    // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser, cross-scale and PatchMatch have no mean images)
-    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale && !opt.pm) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
+    // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser, cross-scale, the permeability filter and PatchMatch have no
+    // mean images)
+    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale && !opt.pm && !opt.perm) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
     std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness and adjustment twins read
-    if ((uniq || opt.adjust || opt.cscale) && host_compare) {
+    if ((uniq || opt.adjust || opt.cscale || opt.perm) && host_compare) {
         agg_l.resize((size_t)n * j.size_d);
         out.agg_l = agg_l.data();
     }
@@ -783,6 +852,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.vote) CHECK(smx_ctx_set_vote(ctx, &opt.vote_params, &opt.vote_arms));
     if (opt.adjust) CHECK(smx_ctx_set_adjust(ctx, &opt.adjust_params));
     if (opt.cscale) CHECK(smx_ctx_set_cross_scale(ctx, &opt.cs_params));
+    if (opt.perm) CHECK(smx_ctx_set_permeability(ctx, &opt.perm_params));
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
@@ -835,6 +905,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     }
     if (opt.adjust) m.adjusted = m.filled;
     if (opt.cscale) m.cscale = m.dmap[0];
+    if (opt.perm) m.perm = m.dmap[0];
     std::vector<float> pm_planes, pm_disp;      // both views' planes and fractional maps: what the twin is compared with
     if (opt.pm) {
         pm_planes.resize((size_t)6 * n);
@@ -848,7 +919,9 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     else CHECK(smx_destroy(ctx));
     std::cout << "guided filter ok" << std::endl;
     // (with --cross-scale the winners are the combination's: its twin redoes the colour guide's aggregation at every level)
-    if (host_compare && opt.cscale) check_cross_scale_twin(j, m, agg_l);
+    // (and with --permeability the filter's: its twin redoes the aggregation of either guide in front of it)
+    if (host_compare && opt.perm) check_permeability_twin(j, m, agg_l);
+    else if (host_compare && opt.cscale) check_cross_scale_twin(j, m, agg_l);
     else if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
     else if (host_compare && opt.pm) check_patchmatch_twin(j, m, pm_planes, pm_disp);
     if (host_compare) check_finish_twins(j, m, agg_l);
@@ -873,6 +946,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"occlu_mapl_despeckled.png", m.despeckled}, {"occlu_mapl_unique.png", m.unique},
                                   {"occlu_mapl_voted.png", m.voted}, {"occlu_mapl_adjusted.png", m.adjusted},
                                   {"disparity_mapl_cscale.png", m.cscale},
+                                  {"disparity_mapl_perm.png", m.perm},
                                   {"disparity_mapl_patchmatch.png", m.pm_disp},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
@@ -960,6 +1034,7 @@ int main(int argc, char** argv) {
         {opt.cscale && (opt.sgm || opt.cross || opt.so),
          "--cross-scale belongs to the guided filter: it cannot be combined with --aggregation sgm, cross, scanline or cross-scanline"},
         {opt.cscale && multi, "--cross-scale" + with_multi},
+        {opt.perm && multi, "--permeability" + with_multi},
         {opt.pm && (opt.census || opt.adcensus), "--aggregation patchmatch scores planes with the reference's cost: it cannot be "
                                                  "combined with --cost census or adcensus"},
         {opt.pm && (opt.rgb || opt.cscale || opt.adjust || uniq),
@@ -982,7 +1057,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
-                       opt.cross || opt.so || opt.adjust || opt.cscale || opt.pm;
+                       opt.cross || opt.so || opt.adjust || opt.cscale || opt.pm || opt.perm;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");
         return 2;

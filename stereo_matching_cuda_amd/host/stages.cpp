@@ -10,6 +10,7 @@
 #include "guidedFilter.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
+#include "permeability.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "colourGuidedFilter.cuh"
 #include "scanlineOptimization.cuh"
@@ -232,6 +233,21 @@ void patch_match(unsigned char* left, unsigned char* right, float* planes, float
         ok = check_errors(td.data(), disp, (int)(2 * n)) && ok;
         ok = check_errors(tl.data(), label, (int)(2 * n)) && ok;
         if (ok) cout << "PatchMatch ok!" << endl;
+    }
+}
+
+// not in the reference: the information permeability filter of one volume (smx_main --permeability runs it inside the context)
+void permeability_filter(float* volume, unsigned char* guide, int channels, float* out, float* best, float* disp_map, const int w,
+                         const int h, const int dmin, const int size_d, const smx_perm_params& p, bool host_gpu_compare) {
+    CHECK(smx_permeability_filter(&p, volume, guide, channels, w, h, dmin, size_d, out, best, disp_map));
+    if (host_gpu_compare) {
+        const size_t n = (size_t)w * h;
+        std::vector<float> to(n * size_d), tb(n), td(n);
+        permeabilityOnCPU(volume, guide, channels, to.data(), tb.data(), td.data(), w, h, dmin, size_d, p);
+        bool ok = !out || check_errors(to.data(), out, (int)(n * size_d));
+        ok = (!best || check_errors(tb.data(), best, (int)n)) && ok;
+        ok = (!disp_map || check_errors(td.data(), disp_map, (int)n)) && ok;
+        if (ok) cout << "Permeability ok!" << endl;
     }
 }
 

@@ -63,6 +63,9 @@ class ShardedPair:
         if kw.get("adjust") is not None:
             # (a D-shard holds no whole aggregated volume)
             raise ValueError("the depth-discontinuity adjustment is not part of the sharded driver: use PairPipeline(adjust=...)")
+        if kw.get("permeability") is not None:
+            # (the filter runs over whole aggregated volumes)
+            raise ValueError("the permeability filter is not part of the sharded driver: use PairPipeline(permeability=...)")
         if kw.get("cross_scale") is not None:
             # (the combination reads whole volumes of every level)
             raise ValueError("cross-scale aggregation is not part of the sharded driver: use PairPipeline(cross_scale=...)")

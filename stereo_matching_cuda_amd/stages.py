@@ -302,6 +302,34 @@ def cross_scale_combine(levels, dmin, params=None):
     return out, best, disp
 
 
+def permeability_filter(volume, guide, sigma=None, dmin=0):
+    """The information permeability filter of one f32 volume and its winners (include/smx.h smx_permeability_filter; Cigla &
+    Alatan 2013; not a stage of the reference).  volume: (size_d, h, w) float32 -- any volume: an aggregated one, or a raw cost
+    volume for the paper's own form; guide: (h, w) or (h, w, 1 | 3 | 4) uint8; sigma: None (the default 32.0, a starting point
+    chosen on a synthetic band), a float or PermParams.  Returns (filtered (size_d, h, w) float32 -- weighted sums, not means --,
+    best (h, w) float32, label map (h, w) float32 = dmin + winning slice)."""
+    p = _lib.default_perm_params()
+    if isinstance(sigma, _lib.PermParams):
+        p.sigma = sigma.sigma
+    elif sigma is not None:
+        p.sigma = float(sigma)
+    if not (0.0 < p.sigma < float("inf")):
+        raise ValueError(f"permeability_filter needs a finite sigma > 0, not {p.sigma!r}")
+    v = _c(volume, np.float32)
+    g = _c(guide, np.uint8)
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError("permeability_filter expects a (size_d, h, w) float32 volume")
+    size_d, h, w = v.shape
+    if g.ndim not in (2, 3) or g.shape[:2] != (h, w) or (g.ndim == 3 and g.shape[2] not in (1, 3, 4)):
+        raise ValueError(f"the guide must be ({h}, {w}) or ({h}, {w}, 1 | 3 | 4) uint8, not {g.shape}")
+    out = np.empty((size_d, h, w), np.float32)
+    best = np.empty((h, w), np.float32)
+    disp = np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_permeability_filter(C.byref(p), _ptr(v), _ptr(g), 1 if g.ndim == 2 else g.shape[2], w, h, int(dmin),
+                                                  size_d, _ptr(out), _ptr(best), _ptr(disp)))
+    return out, best, disp
+
+
 def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
     """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
     reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
