@@ -524,6 +524,68 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
 int smx_ctx_set_aggregation(smx_ctx* ctx, int mode, const smx_sgm_params* sgm);
 
 /* ------------------------------------------------------------------------------------
+ * Hierarchical belief propagation (not a stage of the reference; opt-in alternative to the guided-filter aggregation)
+ * ---------------------------------------------------------------------------------- */
+
+/* Min-sum loopy belief propagation on the 4-connected pixel grid with a truncated-linear smoothness term, after Felzenszwalb
+ * and Huttenlocher, "Efficient Belief Propagation for Early Vision" (IJCV 2006): O(D) messages, a checkerboard schedule that
+ * updates in place, a coarse-to-fine pyramid.  Integers throughout, so the result is the same bits in every run.
+ *   parameters: step 20, trunc 60, iterations 5, levels 4, data_scale 1.0f by default (chosen on synthetic scenes, not measured
+ *               on real data).  Valid: 0 <= step <= 4095, 0 <= trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8,
+ *               data_scale finite and > 0; w, h >= 1, w*h < 2^31, 1 <= size_d <= SMX_BP_MAX_D.  Anything else is SMX_E_ARG
+ *               before any device call.
+ *   data term:  one f32 cost volume per view, [z][y][x].  t = c * data_scale is one f32 product and
+ *               C = t >= 0 ? (t <= 255 ? (int)t : 255) : 0, so a NaN gives 0: the call is total on any bits.  Level 0 is the
+ *               image with D_0 = C.  Level l+1 has size (ceil(w_l / 2), ceil(h_l / 2)); its data term is the sum of the up to
+ *               four children (2x .. 2x+1, 2y .. 2y+1) that exist.  D_l <= 255 * 4^l.
+ *   smoothness: V(z, z') = min(step * |z - z'|, trunc).
+ *   messages:   every pixel p of a level holds four incoming messages, from its left, right, upper and lower neighbour.  A
+ *               message from outside the image is 0 and is never updated.  One update of the message q -> p, p a neighbour of q:
+ *                 h(z)  = D_l(q, z) + sum of m_{r->q}(z) over the neighbours r of q other than p
+ *                 m'(z) = min over z' of (h(z') + V(z, z'))
+ *                 m_{q->p}(z) = m'(z) - min_k m'(k)
+ *               hence 0 <= m <= trunc, exact in u16; h <= 255 * 4^l + 3 * trunc and every intermediate fits i32.
+ *   schedule:   at the coarsest level all messages start at 0.  At every level run iterations t = 1 .. iterations; iteration t
+ *               replaces exactly the messages INTO the pixels with (x + y + t) even, each computed from the current messages
+ *               into its neighbours (all of the other parity and untouched in that iteration, so the order does not matter).
+ *               Going from level l+1 to l, pixel (x, y) takes all four messages of (x >> 1, y >> 1).  With iterations == 0, or
+ *               step == trunc == 0, all messages are 0.
+ *   belief:     S(p, z) = D_0(p, z) + the four incoming messages at level 0; S <= 255 + 4 * 4095 = 16635, exact in u16 and f32.
+ *   outputs:    d_keys, d_agg, d_nbr and d_uq carry, word for word, the meanings they have for smx_dev_sgm_wta_pair(_uq) with
+ *               this S: keys are OUT only and the largest z of minimal S wins; d_agg is (float)S in [z][y][x]; d_nbr holds
+ *               lo / hi / last with NaN at the ends; d_uq is the state of one run over the whole range.  As for SGM there is no
+ *               s_begin / s_end, no accumulation into existing keys and no combination across D-shards.
+ * smx_dev_bp_wta_pair: either cost pointer may be NULL (not both), the one-view form, whose outputs are laid out as SGM's;
+ * d_agg, d_nbr and d_uq are optional.  A fixed sequence of kernel launches on `stream`, a function of levels and iterations
+ * only (4 + 2 * (levels - 1) + levels * iterations), no allocation, no synchronisation (graph-capturable).  d_ws needs no
+ * alignment and may hold anything; fewer than smx_bp_workspace_bytes(w, h, size_d, levels, nviews) bytes is SMX_E_WS before
+ * anything is launched.  With Dp = size_d rounded up to 64, n_l = w_l * h_l and A(b) = b rounded up to 256 that is
+ *   255 + nviews * (A(2 * n_0 * Dp) + sum over l < levels of (A((l ? 4 : 1) * n_l * Dp) + A(8 * n_l * Dp)))
+ * bytes: the u16 belief, and per level the data term (u8 at level 0, u32 above) and four u16 message planes -- about 11 bytes
+ * per pixel and label at level 0 and a third of 12 more for the coarse levels; 0 for invalid sizes, levels outside 1 .. 8 or
+ * nviews other than 1, 2.  Nothing is written outside the workspace and the stated extents; the inputs are not modified.
+ * smx_bp_aggregate: host pointers, synchronous, one view; agg, best, disp_map as for smx_sgm_aggregate. */
+#define SMX_BP_MAX_D 256
+typedef struct smx_bp_params { int step, trunc; int iterations; int levels; float data_scale; } smx_bp_params;
+void smx_default_bp_params(smx_bp_params* p);
+size_t smx_bp_workspace_bytes(int w, int h, int size_d, int levels, int nviews);
+int smx_dev_bp_wta_pair(const smx_bp_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                        int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_bp_aggregate(const smx_bp_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
+                     int size_d, int dmin);
+/* Belief propagation as the aggregation of this context (p: the parameters; NULL = off, the default).  The flow of SMX_AGG_SGM:
+ * smx_ctx_stereo_pair builds both whole cost volumes (the reference's, census or AD-Census), runs one smx_dev_bp_wta_pair (with
+ * the neighbour and uniqueness states when sub-pixel and uniqueness are on), then the unchanged finish: LR check, uniqueness,
+ * speckle, vote, fill, adjustment on agg_l, sub-pixel.  agg_l / agg_r of smx_pair_out receive S; radius and eps of smx_params
+ * are unused.  The pair call returns SMX_E_ARG with a message together with SMX_AGG_SGM, cross-based aggregation, the
+ * scan-line optimiser, colour guidance, cross-scale aggregation, the permeability filter or PatchMatch, when mean_l / mean_r
+ * are requested, and with more than SMX_BP_MAX_D labels; smx_ctx_stereo_pair_async returns SMX_E_ARG while it is on.  The
+ * workspace is allocated on the first pair that runs with it on: a context that never does holds and launches nothing new.
+ * smx_ctx_bp_held (a test hook): the bytes of that workspace, 0 before. */
+int smx_ctx_set_bp(smx_ctx* ctx, const smx_bp_params* p);
+int smx_ctx_bp_held(const smx_ctx* ctx, size_t* bytes);
+
+/* ------------------------------------------------------------------------------------
  * Uniqueness (peak-ratio) filtering (not a stage of the reference; opt-in, between the LR check and speckle removal)
  * ---------------------------------------------------------------------------------- */
 

@@ -62,6 +62,11 @@ class SgmParams(C.Structure):
     _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("paths", C.c_int)]
 
 
+class BpParams(C.Structure):
+    """smx_bp_params: hierarchical belief propagation (not a stage of the reference)."""
+    _fields_ = [("step", C.c_int), ("trunc", C.c_int), ("iterations", C.c_int), ("levels", C.c_int), ("data_scale", C.c_float)]
+
+
 class ScanlineParams(C.Structure):
     """smx_scanline_params: the scan-line optimiser with colour-adaptive penalties (not a stage of the reference)."""
     _fields_ = [("p1", C.c_int), ("p2", C.c_int), ("tau_so", C.c_int), ("paths", C.c_int)]
@@ -125,6 +130,7 @@ _CP = C.POINTER(CensusParams)
 _AP = C.POINTER(AdCensusParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
+_BP = C.POINTER(BpParams)
 _XP = C.POINTER(CrossParams)
 _VP = C.POINTER(VoteParams)
 _LP = C.POINTER(ScanlineParams)
@@ -217,6 +223,12 @@ SIGNATURES = {
     "smx_dev_sgm_wta_pair": (_i, [_GP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "smx_sgm_aggregate": (_i, [_GP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_aggregation": (_i, [_vp, _i, _GP]),
+    "smx_default_bp_params": (None, [_BP]),
+    "smx_bp_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "smx_dev_bp_wta_pair": (_i, [_BP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_bp_aggregate": (_i, [_BP, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_bp": (_i, [_vp, _BP]),
+    "smx_ctx_bp_held": (_i, [_vp, C.POINTER(_sz)]),
     "smx_dev_aggregate_wta_pair_uq": (_i, [_PP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
                                           _vp, _vp]),
     "smx_dev_sgm_wta_pair_uq": (_i, [_GP, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -378,6 +390,12 @@ def default_speckle_params():
 def default_sgm_params():
     p = SgmParams()
     lib().smx_default_sgm_params(C.byref(p))
+    return p
+
+
+def default_bp_params():
+    p = BpParams()
+    lib().smx_default_bp_params(C.byref(p))
     return p
 
 

@@ -47,6 +47,7 @@ bool uniq_ratio_ok(float ratio);
 bool speckle_shape_ok(int w, int h);
 bool sgm_params_ok(const smx_sgm_params* p);
 bool sgm_shape_ok(int w, int h, int size_d);
+bool bp_params_ok(const smx_bp_params* p);
 bool scanline_params_ok(const smx_scanline_params* p);
 constexpr const char* SCANLINE_RANGES = "needs 0 <= p1 <= p2 <= 4095, 1 <= tau_so <= 256 and paths 4 or 8";
 bool cross_params_ok(const smx_cross_params* p);       // (smx_cross.hip, beside the limits of its kernels)

@@ -116,6 +116,10 @@ bool sgm_params_ok(const smx_sgm_params* p) {
 bool scanline_params_ok(const smx_scanline_params* p) {
     return p && p->p1 >= 0 && p->p1 <= p->p2 && p->p2 <= 4095 && p->tau_so >= 1 && p->tau_so <= 256 && (p->paths == 4 || p->paths == 8);
 }
+bool bp_params_ok(const smx_bp_params* p) {
+    return p && p->step >= 0 && p->step <= 4095 && p->trunc >= 0 && p->trunc <= 4095 && p->iterations >= 0 && p->iterations <= 64 &&
+           p->levels >= 1 && p->levels <= 8 && isfinite(p->data_scale) && p->data_scale > 0;
+}
 bool sgm_shape_ok(int w, int h, int size_d) {
     return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= SMX_SGM_MAX_D;
 }
@@ -686,6 +690,31 @@ int smx_dev_sgm_wta_pair_uq(const smx_sgm_params* p, const float* d_cost_l, cons
     SMX_ARG(d_uq);
     return sgm_wta_pair("smx_dev_sgm_wta_pair_uq", p, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_uq, d_ws, ws_bytes,
                         stream);
+}
+
+// ---- hierarchical belief propagation (not in the reference; smx_bp.hip) ---------------------------------------------
+void smx_default_bp_params(smx_bp_params* p) {
+    if (!p) return;
+    p->step = 20; p->trunc = 60; p->iterations = 5; p->levels = 4; p->data_scale = 1.0f;
+}
+
+size_t smx_bp_workspace_bytes(int w, int h, int size_d, int levels, int nviews) {
+    return sgm_shape_ok(w, h, size_d) && levels >= 1 && levels <= 8 && (nviews == 1 || nviews == 2)
+               ? bp_workspace_bytes(w, h, size_d, levels, nviews) : 0;
+}
+
+int smx_dev_bp_wta_pair(const smx_bp_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
+                        int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!bp_params_ok(p))
+        return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
+                               "finite data_scale > 0");
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_BP_MAX_D);
+    SMX_ARG((d_cost_l || d_cost_r) && d_keys);
+    const size_t need = bp_workspace_bytes(w, h, size_d, p->levels, d_cost_l && d_cost_r ? 2 : 1);
+    if (!d_ws || ws_bytes < need)
+        return fail(SMX_E_WS, "smx_dev_bp_wta_pair: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0, need);
+    return launch_bp_wta_pair(p, d_cost_l, d_cost_r, w, h, size_d, d_keys, d_agg, d_nbr, d_uq, d_ws, (hipStream_t)stream);
 }
 
 // ---- scan-line optimisation with colour-adaptive penalties (not in the reference; smx_scanline.hip) -----------------

@@ -83,6 +83,10 @@ struct smx_ctx {
     bool perm = false;
     smx_perm_params perm_params;
     DevBuf perm_ws;
+    // hierarchical belief propagation (smx_ctx_set_bp): it reads the whole volumes costL / costR, as SGM does; its workspace
+    bool bp = false;
+    smx_bp_params bp_params;
+    DevBuf bp_ws;
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -122,7 +126,8 @@ struct smx_ctx {
 // cscale: the winners come from the cross-scale combination; level: this pair is a level of another context's pyramid, which
 // wants its aggregated volumes and nothing behind them.  pm: PatchMatch stereo in place of cost, aggregation and winners.
 // perm: the winners come from the permeability filter over the aggregated volumes.
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm, perm; };
+// bp: the winners come from belief propagation on the whole cost volumes.
+struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm, perm, bp; };
 
 // The permeability filter's workspace for both views: every slice at once where that stays within ~1 GiB, else what does, and one
 // slice at least (the pass goes in chunks of slices over the volumes it filters in place)
@@ -164,6 +169,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     }
     if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
     if (need.perm) SMX_HIP(c->perm_ws.ensure(ctx_perm_ws_bytes(c)));
+    if (need.bp) SMX_HIP(c->bp_ws.ensure(bp_workspace_bytes(c->w, c->h, c->size_d, c->bp_params.levels, 2)));
     if (need.pm) {
         SMX_HIP(c->pm_planes.ensure(6 * fb));
         SMX_HIP(c->pm_disp.ensure(2 * fb));
@@ -360,6 +366,10 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
                                                           c->mode_ws_bytes, st)
                                 : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->mode_ws.p,
                                                        c->mode_ws_bytes, st);
+    } else if (need.bp) {
+        // belief propagation instead of the guided filter: the flow of SGM, the uniqueness state from the same call
+        if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
+        if (!rc) rc = smx_dev_bp_wta_pair(&c->bp_params, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->bp_ws.p, c->bp_ws.bytes, st);
     } else if (need.so) {
         // the scan-line optimiser reads whole volumes: the cost volumes, as SGM does, or behind cross-based aggregation the
         // two volumes of its q, collected over the chunks with the keys of that pass discarded (the optimiser's are OUT only)
@@ -609,6 +619,21 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     if (perm && (out->mean_l || out->mean_r))
         return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) produces no mean images", who);
     if (perm && !perm_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: the permeability filter %s", who, PERM_SHAPES);
+    const bool bp = c->bp;
+    if (bp) {
+        const char* with = sgm      ? "semi-global matching (smx_ctx_set_aggregation)"
+                           : cgf    ? "colour guidance (smx_ctx_set_guidance)"
+                           : cross  ? "cross-based aggregation (smx_ctx_set_cross)"
+                           : so     ? "the scan-line optimiser (smx_ctx_set_scanline)"
+                           : cscale ? "cross-scale aggregation (smx_ctx_set_cross_scale)"
+                           : perm   ? "the permeability filter (smx_ctx_set_permeability)"
+                           : c->pm  ? "PatchMatch stereo (smx_ctx_set_patchmatch)"
+                                    : nullptr;
+        if (with) return fail(SMX_E_ARG, "%s: belief propagation (smx_ctx_set_bp) is on, and so is %s", who, with);
+        if (out->mean_l || out->mean_r) return fail(SMX_E_ARG, "%s: belief propagation (smx_ctx_set_bp) produces no mean images", who);
+        if (!sgm_shape_ok(c->w, c->h, c->size_d))
+            return fail(SMX_E_ARG, "%s: belief propagation needs w*h < 2^31 and size_d <= %d", who, SMX_BP_MAX_D);
+    }
     const bool pm = c->pm;
     if (pm) {
         // PatchMatch keeps no cost volume: every stage that reads one has nothing to read, and the rest is out of scope
@@ -633,9 +658,9 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     }
     // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
     // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale || perm, c->subpix != 0,
+    const PairNeeds need = {out->cost_l || out->cost_r || sgm || bp || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale || perm, c->subpix != 0,
                             c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
-                            c->adjust, cscale, false, pm, perm};
+                            c->adjust, cscale, false, pm, perm, bp};
     if ((rc = ctx_reserve(c, need))) return rc;
     if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
@@ -667,8 +692,8 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    // (the SGM, colour-guided, cross-based and PatchMatch kernels wait for nothing)
-    if (!need.sgm && !need.cgf && !need.cross && !need.so && !need.pm) {
+    // (the SGM, belief-propagation, colour-guided, cross-based and PatchMatch kernels wait for nothing)
+    if (!need.sgm && !need.bp && !need.cgf && !need.cross && !need.so && !need.pm) {
         if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
         for (int s = 1; cscale && s < c->cs_params.scales; ++s)
             if ((rc = smx_dev_agg_status(c->cs_child[s]->ws.p))) return rc;
@@ -702,6 +727,25 @@ int smx_ctx_set_permeability(smx_ctx* c, const smx_perm_params* p) {
         c->perm_params = *p;
     }
     c->perm = p != nullptr;
+    return SMX_OK;
+}
+
+int smx_ctx_set_bp(smx_ctx* c, const smx_bp_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!bp_params_ok(p))
+            return fail(SMX_E_ARG, "smx_ctx_set_bp: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a finite "
+                                   "data_scale > 0");
+        c->bp_params = *p;
+    }
+    c->bp = p != nullptr;
+    return SMX_OK;
+}
+
+// Test hook (include/smx.h): what belief propagation holds on the device
+int smx_ctx_bp_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = c->bp_ws.p ? c->bp_ws.bytes : 0;
     return SMX_OK;
 }
 
@@ -971,6 +1015,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-scale aggregation is on (smx_ctx_set_cross_scale): use smx_ctx_stereo_pair");
     if (c->perm)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the permeability filter is on (smx_ctx_set_permeability): use smx_ctx_stereo_pair");
+    if (c->bp)
+        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: belief propagation is on (smx_ctx_set_bp): use smx_ctx_stereo_pair");
     if (c->pm)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: PatchMatch stereo is on (smx_ctx_set_patchmatch): use smx_ctx_stereo_pair");
     if (c->uniq > 0.0f)

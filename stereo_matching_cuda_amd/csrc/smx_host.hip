@@ -266,6 +266,38 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
     return SMX_OK;
 }
 
+int smx_bp_aggregate(const smx_bp_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d,
+                     int dmin) {
+    if (!bp_params_ok(p))
+        return fail(SMX_E_ARG, "smx_bp_aggregate: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
+                               "finite data_scale > 0");
+    if (!sgm_shape_ok(w, h, size_d))
+        return fail(SMX_E_ARG, "smx_bp_aggregate: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_BP_MAX_D);
+    SMX_ARG(cost != nullptr);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = bp_workspace_bytes(w, h, size_d, p->levels, 1);
+    DevBuf dC, dA, dK, dW;
+    SMX_HIP(dC.upload(cost, vb));
+    if (agg) SMX_HIP(dA.ensure(vb));
+    SMX_HIP(dK.ensure(n * sizeof(int64_t)));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_bp_wta_pair(p, dC.as<float>(), nullptr, w, h, size_d, dK.as<int64_t>(), agg ? dA.as<float>() : nullptr,
+                                     nullptr, nullptr, dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (agg) SMX_HIP(dA.download(agg, vb));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(dK.download(keys.data(), n * sizeof(int64_t)));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
 int smx_scanline_optimize(const smx_scanline_params* p, const uint8_t* guide_own, const uint8_t* guide_other, int channels,
                           const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d, int dmin) {
     if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_scanline_optimize: %s", SCANLINE_RANGES);

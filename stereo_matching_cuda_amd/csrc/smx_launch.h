@@ -56,6 +56,10 @@ int sgm_padded_d(int size_d);
 size_t sgm_workspace_bytes(int w, int h, int size_d, int nviews);
 int launch_sgm_wta_pair(int p1, int p2, int paths, const float* cost_l, const float* cost_r, int w, int h, int size_d,
                         int64_t* keys, float* agg, float* nbr, float* uq, void* ws, hipStream_t st);
+// smx_bp.hip: hierarchical belief propagation of one or both whole cost volumes (smx_dev_bp_wta_pair); ws: bp_workspace_bytes bytes
+size_t bp_workspace_bytes(int w, int h, int size_d, int levels, int nviews);
+int launch_bp_wta_pair(const smx_bp_params* p, const float* cost_l, const float* cost_r, int w, int h, int size_d, int64_t* keys,
+                       float* agg, float* nbr, float* uq, void* ws, hipStream_t st);
 // smx_scanline.hip: the scan-line optimiser with colour-adaptive penalties (smx_dev_scanline_wta_pair); both guides always
 size_t scanline_workspace_bytes(int w, int h, int size_d, int nviews);
 int launch_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* guide_l, const uint8_t* guide_r, int ch,

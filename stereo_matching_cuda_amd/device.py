@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
+                 aggregation=None, sgm_params=None, bp_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
                  vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None, pm_params=None,
                  permeability=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
@@ -58,6 +58,10 @@ class PairPipeline:
         self.nbr).  The pipeline owns the volumes and the SGM workspace self.sgm_ws; max_ws_bytes counts both, and a
         slice sub-range or a size that does not fit raises ValueError.  No guided-filter workspace is allocated, self.mean
         stays zero, and radius / eps of `params` are unused.  With None nothing is allocated or launched.
+        aggregation="bp" is hierarchical belief propagation (not a stage of the reference; include/smx.h smx_dev_bp_wta_pair;
+        bp_params: BpParams, None = the defaults): the flow of "sgm" with the one smx_dev_bp_wta_pair call in its place, the
+        whole cost volumes in self.bp_cost and the workspace in self.bp_ws (about 15 bytes per pixel and padded label and view
+        at four levels); self.agg receives the belief S.  The same refusals as "sgm".
         uniqueness: None or a ratio > 0 -- the uniqueness (peak-ratio) test (not a stage of the reference; include/smx.h
         smx_dev_uniqueness; OpenCV's uniquenessRatio u is ratio = u / (100 - u)): the aggregation keeps the winners'
         second-best cost in self.uq (2, 3, h, w) through the _uq entries, and finish() runs the test on the LR-checked left map
@@ -193,9 +197,12 @@ class PairPipeline:
             # winners it does not belong to)
             if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
                 raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
-        if aggregation not in (None, "sgm", "cross", "scanline", "cross-scanline", "patchmatch"):
-            raise ValueError(f"aggregation must be None, 'sgm', 'cross', 'scanline', 'cross-scanline' or 'patchmatch', not {aggregation!r}")
+        if aggregation not in (None, "sgm", "bp", "cross", "scanline", "cross-scanline", "patchmatch"):
+            raise ValueError(f"aggregation must be None, 'sgm', 'bp', 'cross', 'scanline', 'cross-scanline' or 'patchmatch', not {aggregation!r}")
         sgm, cross = aggregation == "sgm", aggregation in ("cross", "cross-scanline")
+        bp = aggregation == "bp"
+        if bp_params is not None and not bp:
+            raise ValueError("bp_params belongs to aggregation='bp'")
         so = aggregation in ("scanline", "cross-scanline")
         if scanline_params is not None and not so:
             raise ValueError("scanline_params belongs to aggregation='scanline' / 'cross-scanline'")
@@ -248,6 +255,24 @@ class PairPipeline:
                                  "(w*h < 2^31, size_d <= 256)")
             if self.sgm_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
                 raise ValueError(f"semi-global matching needs {self.sgm_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
+                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
+        self.bp_params = self.bp_cost = self.bp_ws = None
+        self.bp_ws_bytes = 0
+        if bp:
+            if self.s_begin != 0 or self.s_end != self.size_d:
+                raise ValueError("belief propagation needs a pixel's whole disparity range: no slice sub-range")
+            self.bp_params = bp_params if bp_params is not None else _lib.default_bp_params()
+            q = self.bp_params
+            if not (0 <= q.step <= 4095 and 0 <= q.trunc <= 4095 and 0 <= q.iterations <= 64 and 1 <= q.levels <= 8 and
+                    0 < q.data_scale < float("inf")):
+                raise ValueError("belief propagation needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
+                                 "finite data_scale > 0")
+            self.bp_ws_bytes = int(self.lib.smx_bp_workspace_bytes(self.w, self.h, self.size_d, q.levels, 2))
+            if self.bp_ws_bytes == 0:
+                raise ValueError(f"belief propagation does not take {self.w} x {self.h} x {self.size_d} "
+                                 "(w*h < 2^31, size_d <= 256)")
+            if self.bp_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
+                raise ValueError(f"belief propagation needs {self.bp_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
                                  f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
         self.so_params = self.so_cost = self.so_ws = self._so_chunk = None
         self.so_ws_bytes = 0
@@ -345,7 +370,7 @@ class PairPipeline:
             self.adjusted = torch.empty((self.h, self.w), **f)
             self.adjust_ws = torch.empty(self.adjust_ws_bytes, dtype=torch.uint8, device=dev)
         self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
-        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and aggregation != "scanline" else None
+        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and not bp and aggregation != "scanline" else None
         if cost == "adcensus":
             self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
             with self._on_device():     # a set-up call: it waits for its copy, and stays outside any graph capture
@@ -354,6 +379,9 @@ class PairPipeline:
         if sgm:
             self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
+        if bp:
+            self.bp_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
+            self.bp_ws = torch.empty(self.bp_ws_bytes, dtype=torch.uint8, device=dev)
         if so:
             self.so_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
             self.so_ws = torch.empty(self.so_ws_bytes, dtype=torch.uint8, device=dev)
@@ -408,7 +436,7 @@ class PairPipeline:
                 self.cs_rgb.append(torch.empty(2 * hs * ws * 4, dtype=torch.uint8, device=dev) if colour else None)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
         self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
-            if (cost or guidance or cross) and want_agg and sif < local and not sgm and not so else None
+            if (cost or guidance or cross) and want_agg and sif < local and not sgm and not bp and not so else None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -507,7 +535,7 @@ class PairPipeline:
         # (no smx_dev_init_keys launch: the aggregation presets the keys itself, smx_set_keys_fresh)
         if self.cost and (cost_l is not None or cost_r is not None):
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
-        if self.aggregation == "sgm":
+        if self.aggregation in ("sgm", "bp"):
             return self._aggregate_sgm(gray_l, gray_r, cost_l, cost_r)
         self.lib.smx_set_keys_fresh(1)
         try:
@@ -683,12 +711,14 @@ class PairPipeline:
 
     def _aggregate_sgm(self, gray_l, gray_r, cost_l=None, cost_r=None):
         """The SGM flow: both whole cost volumes (the caller's, census, or the reference's cost) and the one
-        smx_dev_sgm_wta_pair call, which writes the keys (and S, the neighbour state) of both views."""
+        smx_dev_sgm_wta_pair call, which writes the keys (and S, the neighbour state) of both views.  aggregation="bp" runs the
+        same flow with smx_dev_bp_wta_pair in that call's place."""
         if (cost_l is None) != (cost_r is None):
             raise ValueError("pass both cost volumes or neither")
         self._guide = gray_l
         L, w, h = self.lib, self.w, self.h
-        cl, cr = (cost_l, cost_r) if cost_l is not None else (self.sgm_cost[0], self.sgm_cost[1])
+        whole = self.bp_cost if self.aggregation == "bp" else self.sgm_cost
+        cl, cr = (cost_l, cost_r) if cost_l is not None else (whole[0], whole[1])
         with self._on_device():
             st = self._stream()
             if self.cost:
@@ -700,6 +730,11 @@ class PairPipeline:
                 P = C.byref(self.params)
                 _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
                 _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
+            if self.aggregation == "bp":
+                _lib.check(L.smx_dev_bp_wta_pair(C.byref(self.bp_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys),
+                                                 _dp(self.agg), _dp(self.nbr), _dp(self.uq) if self.uniqueness else None,
+                                                 _dp(self.bp_ws), self.bp_ws_bytes, st))
+                return
             head = (C.byref(self.sgm_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys), _dp(self.agg), _dp(self.nbr))
             if self.uniqueness:
                 _lib.check(L.smx_dev_sgm_wta_pair_uq(*head, _dp(self.uq), _dp(self.sgm_ws), self.sgm_ws_bytes, st))

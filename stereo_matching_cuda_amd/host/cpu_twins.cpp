@@ -27,6 +27,7 @@
 #include "regionVoting.cuh"
 #include "rgb_to_grayscale.cuh"
 #include "scanlineOptimization.cuh"
+#include "beliefPropagation.cuh"
 #include "sgm.cuh"
 #include "speckle.cuh"
 #include "uniqueness.cuh"
@@ -1078,6 +1079,87 @@ void sgm_aggregateOnCPU(const float* cost, float* agg, float* best, float* disp_
         if (disp_map) disp_map[i] = (float)(dmin + z);
         if (agg)
             for (int d = 0; d < size_d; ++d) agg[(size_t)d * n + i] = (float)s[d];
+    }
+}
+
+// ---- beliefPropagation.cuh (not in the reference) --------------------------------------------
+// Hierarchical belief propagation by the definition in include/smx.h: the pyramid of data terms, then level by level the
+// checkerboard iterations, every message from the sender's data term and its other three messages through the two-pass
+// distance transform; integers throughout.  Messages: [level][slot][pixel][z], slot 0 from the left, 1 right, 2 upper, 3 lower.
+void beliefPropagationOnCPU(const float* cost, float* agg, float* best, float* disp_map, const int w, const int h,
+                            const int size_d, const int dmin, const smx_bp_params& p) {
+    const size_t n = (size_t)w * h;
+    const int D = size_d;
+    vector<int> lw(p.levels), lh(p.levels);
+    vector<vector<int>> data(p.levels);
+    lw[0] = w; lh[0] = h;
+    for (int l = 1; l < p.levels; ++l) { lw[l] = (lw[l - 1] + 1) / 2; lh[l] = (lh[l - 1] + 1) / 2; }
+    data[0].resize(n * D);
+    for (int d = 0; d < D; ++d)
+        for (size_t i = 0; i < n; ++i) {
+            const float t = cost[(size_t)d * n + i] * p.data_scale;
+            data[0][i * D + d] = t >= 0.0f ? (t <= 255.0f ? (int)t : 255) : 0;
+        }
+    for (int l = 1; l < p.levels; ++l) {
+        data[l].assign((size_t)lw[l] * lh[l] * D, 0);
+        for (int y = 0; y < lh[l - 1]; ++y)
+            for (int x = 0; x < lw[l - 1]; ++x) {
+                const int* src = &data[l - 1][((size_t)y * lw[l - 1] + x) * D];
+                int* dst = &data[l][((size_t)(y / 2) * lw[l] + x / 2) * D];
+                for (int d = 0; d < D; ++d) dst[d] += src[d];
+            }
+    }
+    static const int from[4][2] = {{-1, 0}, {1, 0}, {0, -1}, {0, 1}};
+    vector<int> msg, coarse, out(D);
+    for (int l = p.levels - 1; l >= 0; --l) {
+        const int cw = lw[l], ch = lh[l];
+        const size_t cells = (size_t)cw * ch;
+        msg.assign(4 * cells * D, 0);
+        if (l < p.levels - 1) {
+            const size_t pcells = (size_t)lw[l + 1] * lh[l + 1];
+            for (int k = 0; k < 4; ++k)
+                for (int y = 0; y < ch; ++y)
+                    for (int x = 0; x < cw; ++x)
+                        for (int d = 0; d < D; ++d)
+                            msg[(k * cells + (size_t)y * cw + x) * D + d] =
+                                coarse[(k * pcells + (size_t)(y / 2) * lw[l + 1] + x / 2) * D + d];
+        }
+        for (int t = 1; t <= p.iterations; ++t)
+            for (int y = 0; y < ch; ++y)
+                for (int x = 0; x < cw; ++x) {
+                    if ((x + y + t) % 2 == 0) continue;           // the other parity sends
+                    const size_t q = (size_t)y * cw + x;
+                    for (int k = 0; k < 4; ++k) {
+                        // to the neighbour on side k: everything but what came from there, into its slot of the opposite side
+                        const int nx = x + from[k][0], ny = y + from[k][1];
+                        if (nx < 0 || nx >= cw || ny < 0 || ny >= ch) continue;
+                        int low = 0;
+                        for (int d = 0; d < D; ++d) {
+                            int v = data[l][q * D + d];
+                            for (int r = 0; r < 4; ++r)
+                                if (r != k) v += msg[(r * cells + q) * D + d];
+                            out[d] = v;
+                            low = d == 0 || v < low ? v : low;
+                        }
+                        for (int d = 1; d < D; ++d) out[d] = out[d - 1] + p.step < out[d] ? out[d - 1] + p.step : out[d];
+                        for (int d = D - 2; d >= 0; --d) out[d] = out[d + 1] + p.step < out[d] ? out[d + 1] + p.step : out[d];
+                        int* dst = &msg[((size_t)(k ^ 1) * cells + (size_t)ny * cw + nx) * D];
+                        for (int d = 0; d < D; ++d) dst[d] = (out[d] < low + p.trunc ? out[d] : low + p.trunc) - low;
+                    }
+                }
+        coarse.swap(msg);
+    }
+    const vector<int>& m0 = coarse;      // (the messages of level 0)
+    for (size_t i = 0; i < n; ++i) {
+        int z = 0, sz = 0;
+        for (int d = 0; d < D; ++d) {
+            int s = data[0][i * D + d];
+            for (int k = 0; k < 4; ++k) s += m0[(k * n + i) * D + d];
+            if (d == 0 || s <= sz) { z = d; sz = s; }            // the last slice of equal beliefs wins
+            if (agg) agg[(size_t)d * n + i] = (float)s;
+        }
+        if (best) best[i] = (float)sz;
+        if (disp_map) disp_map[i] = (float)(dmin + z);
     }
 }
 

@@ -89,6 +89,15 @@
 //                     --sgm-p P1,P2 gives the penalties (0 <= P1 <= P2 <= 4095; default 10,120), --sgm-paths 4|8 the number
 //                     of directions (default 8).  With --host-compare the CPU twin (sgm_aggregateOnCPU) redoes both
 //                     views from the cost volumes and check_errors compares.  At most 256 labels
+//   --aggregation bp  hierarchical belief propagation instead of the guided filter (smx_ctx_set_bp; Felzenszwalb & Huttenlocher
+//                     2006, not in the reference; implies --fused): min-sum message passing on the 4-connected grid with the
+//                     smoothness term min(STEP |z - z'|, TRUNC), coarse to fine.  --bp-step STEP and --bp-trunc TRUNC (0 .. 4095;
+//                     default 20 and 60), --bp-iterations N per level (0 .. 64; default 5), --bp-levels L (1 .. 8; default 4),
+//                     --bp-scale S the factor in front of the clamp of the cost to 0 .. 255 (finite, > 0; default 1).  With every
+//                     --cost; the same twelve images, the two mean images empty, and disparity_mapl_bp.png holds the left map
+//                     once more.  With --host-compare the CPU twin (beliefPropagationOnCPU) redoes both views from the cost
+//                     volumes and check_errors compares the winners and the left volume.  At most 256 labels.  Not with
+//                     --guidance rgb, --cross-scale, --permeability, --ngpu or --pipeline
 //   --uniqueness PCT  the uniqueness (peak-ratio) test between the LR check and speckle removal (smx_ctx_set_uniqueness; not
 //                     in the reference; implies --fused): 0 <= PCT < 100 is OpenCV's uniquenessRatio, i.e. the ratio
 //                     PCT / (100 - PCT); 0 is off.  A left pixel whose winner has a non-neighbouring disparity that costs less
@@ -148,6 +157,7 @@
 #include <vector>
 
 #include "adcensus.cuh"
+#include "beliefPropagation.cuh"
 #include "census.cuh"
 #include "colourGuidedFilter.cuh"
 #include "costVolume.cuh"
@@ -187,6 +197,8 @@ struct Options {
     smx_adcensus_params adc_params;     // (its census part is filled from census_params after the parse)
     bool sgm = false;        // --aggregation sgm
     smx_sgm_params sgm_params;
+    bool bp = false;         // --aggregation bp
+    smx_bp_params bp_params;
     bool cross = false;      // --aggregation cross, and the first stage of cross-scanline
     smx_cross_params cross_params;
     bool so = false;         // --aggregation scanline, and the second stage of cross-scanline
@@ -288,10 +300,35 @@ const ValueOption value_options[] = {
          const bool good = number(v, 1L, 1000000L, th);
          o.census_params.th = (int)th;
          return good; }},
-    {"--aggregation", "`guided`, `sgm`, `cross`, `scanline`, `cross-scanline` or `patchmatch`", [](auto& v, auto& o) {    // (the last one wins)
-         const int k = word(v, {"guided", "sgm", "cross", "scanline", "cross-scanline", "patchmatch"});
-         o.sgm = k == 1; o.cross = k == 2 || k == 4; o.so = k == 3 || k == 4; o.pm = k == 5;
+    {"--aggregation", "`guided`, `sgm`, `cross`, `scanline`, `cross-scanline`, `patchmatch` or `bp`", [](auto& v, auto& o) {    // (the last one wins)
+         const int k = word(v, {"guided", "sgm", "cross", "scanline", "cross-scanline", "patchmatch", "bp"});
+         o.sgm = k == 1; o.cross = k == 2 || k == 4; o.so = k == 3 || k == 4; o.pm = k == 5; o.bp = k == 6;
          return k >= 0; }},
+    {"--bp-step", "a step STEP with 0 <= STEP <= 4095", [](auto& v, auto& o) {
+         long k = -1;
+         const bool good = number(v, 0L, 4095L, k);
+         o.bp_params.step = (int)k;
+         return good; }},
+    {"--bp-trunc", "a truncation TRUNC with 0 <= TRUNC <= 4095", [](auto& v, auto& o) {
+         long k = -1;
+         const bool good = number(v, 0L, 4095L, k);
+         o.bp_params.trunc = (int)k;
+         return good; }},
+    {"--bp-iterations", "a count N with 0 <= N <= 64", [](auto& v, auto& o) {
+         long k = -1;
+         const bool good = number(v, 0L, 64L, k);
+         o.bp_params.iterations = (int)k;
+         return good; }},
+    {"--bp-levels", "a count L with 1 <= L <= 8", [](auto& v, auto& o) {
+         long k = 0;
+         const bool good = number(v, 1L, 8L, k);
+         o.bp_params.levels = (int)k;
+         return good; }},
+    {"--bp-scale", "a finite S > 0", [](auto& v, auto& o) {
+         double s = 0.0;
+         const bool good = number(v, 0.0, 3.4e38, s) && (float)s > 0.0f;
+         o.bp_params.data_scale = (float)s;
+         return good; }},
     {"--pm-radius", "a radius R with 0 <= R <= 17", [](auto& v, auto& o) {
          long r = -1;
          const bool good = number(v, 0L, 17L, r);
@@ -418,6 +455,7 @@ Options parse(int argc, char** argv) {
     smx_default_cscale_params(&o.cs_params);
     smx_default_perm_params(&o.perm_params);
     smx_default_pm_params(&o.pm_params);
+    smx_default_bp_params(&o.bp_params);
     auto refuse = [&o](const std::string& message) { std::fprintf(stderr, "%s\n", message.c_str()); o.ok = false; return o; };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -460,9 +498,11 @@ Options parse(int argc, char** argv) {
         {o.saw({"--adjust-vertical"}) && !o.adjust, "--adjust-vertical needs --adjust"},
         {o.saw({"--pm-radius", "--pm-gamma", "--pm-iterations", "--pm-slope", "--pm-seed"}) && !o.pm,
          "--pm-radius, --pm-gamma, --pm-iterations, --pm-slope and --pm-seed need --aggregation patchmatch"},
-        {o.perm && (o.sgm || o.cross || o.so || o.pm),
+        {o.saw({"--bp-step", "--bp-trunc", "--bp-iterations", "--bp-levels", "--bp-scale"}) && !o.bp,
+         "--bp-step, --bp-trunc, --bp-iterations, --bp-levels and --bp-scale need --aggregation bp"},
+        {o.perm && (o.sgm || o.cross || o.so || o.pm || o.bp),
          "--permeability runs behind the guided filter: it cannot be combined with --aggregation sgm, cross, scanline, "
-         "cross-scanline or patchmatch"},
+         "cross-scanline, patchmatch or bp"},
         {o.perm && o.cscale, "--permeability cannot be combined with --cross-scale"}};
     for (const Rule& r : rules)
         if (r.refused) return refuse(r.message);
@@ -501,6 +541,7 @@ struct Maps {
     std::vector<float> despeckled;     // --speckle: the LR-checked left map without its small components
     std::vector<float> voted;          // --vote: the last of these maps with its outliers voted on and interpolated
     std::vector<float> perm;           // --permeability: the left map of the filtered winners (= dmap[0])
+    std::vector<float> bp;             // --aggregation bp: the left map of its winners (= dmap[0])
     std::vector<float> cscale;         // --cross-scale: the left map of the combined winners (= dmap[0])
     std::vector<float> pm_disp;        // --aggregation patchmatch: the fractional left map (the planes' d0)
     std::vector<float> adjusted;       // --adjust: the filled left map with the pixels beside its depth steps adjusted (= filled)
@@ -536,7 +577,7 @@ void build_cost(const Job& j, int v, int slices, float* dst, bool host_compare) 
 
 // --host-compare of --aggregation sgm / cross / scanline / cross-scanline and --guidance rgb: the mode's twin redoes both views from whole cost volumes
 // built by the stage wrappers, from the reference's presets.
-void check_aggregation_twin(const Job& j, Maps& m) {
+void check_aggregation_twin(const Job& j, Maps& m, std::vector<float>& agg_l) {
     const Options& opt = j.opt;
     const int n = j.n;
     bool ok = true;
@@ -546,7 +587,13 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         build_cost(j, v, j.size_d, vol.data(), false);
         if (opt.sgm)
             sgm_aggregateOnCPU(vol.data(), nullptr, tb.data(), td.data(), j.w, j.h, j.size_d, j.dmin[v], opt.sgm_params);
-        else if (opt.so) {
+        else if (opt.bp) {
+            // (the left belief too, where the pair fetched it)
+            std::vector<float> ta(v == 0 ? agg_l.size() : 0);
+            beliefPropagationOnCPU(vol.data(), ta.empty() ? nullptr : ta.data(), tb.data(), td.data(), j.w, j.h, j.size_d, j.dmin[v],
+                                   opt.bp_params);
+            if (!ta.empty()) ok = check_errors(ta.data(), agg_l.data(), (int)ta.size()) && ok;
+        } else if (opt.so) {
             // alone on the cost volume; in the chain on the q of the cross twin, whose own winners are discarded
             std::vector<float> q(opt.cross ? vol.size() : 0), ub(n), ud(n, 0.0f);
             std::memset(ub.data(), 0x7F, sizeof(float) * n);
@@ -565,7 +612,7 @@ void check_aggregation_twin(const Job& j, Maps& m) {
         ok = check_errors(td.data(), m.dmap[v].data(), n) && ok;
     }
     if (ok)
-        std::cout << (opt.sgm ? "Semi-global matching" : opt.so ? "Scan-line optimisation" : opt.rgb ? "Colour guided filter"
+        std::cout << (opt.sgm ? "Semi-global matching" : opt.bp ? "Belief propagation" : opt.so ? "Scan-line optimisation" : opt.rgb ? "Colour guided filter"
                                                                                                       : "Cross-based aggregation") << " ok!"
                   << std::endl;
 }
@@ -832,10 +879,10 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     out.dmap_l = m.dmap[0].data(); out.dmap_r = m.dmap[1].data();
     // (SGM, the colour guide, cross-based aggregation, the scan-line optimiser, cross-scale, the permeability filter and PatchMatch have no
     // mean images)
-    if (!opt.sgm && !opt.rgb && !opt.cross && !opt.so && !opt.cscale && !opt.pm && !opt.perm) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
+    if (!opt.sgm && !opt.bp && !opt.rgb && !opt.cross && !opt.so && !opt.cscale && !opt.pm && !opt.perm) { out.mean_l = m.mean[0].data(); out.mean_r = m.mean[1].data(); }
     out.occlusion = m.occlusion.data(); out.filled = m.filled.data();
     std::vector<float> agg_l;          // the left aggregated volume: what the uniqueness and adjustment twins read
-    if ((uniq || opt.adjust || opt.cscale || opt.perm) && host_compare) {
+    if ((uniq || opt.adjust || opt.cscale || opt.perm || opt.bp) && host_compare) {
         agg_l.resize((size_t)n * j.size_d);
         out.agg_l = agg_l.data();
     }
@@ -854,6 +901,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.cscale) CHECK(smx_ctx_set_cross_scale(ctx, &opt.cs_params));
     if (opt.perm) CHECK(smx_ctx_set_permeability(ctx, &opt.perm_params));
     if (opt.sgm) CHECK(smx_ctx_set_aggregation(ctx, SMX_AGG_SGM, &opt.sgm_params));
+    if (opt.bp) CHECK(smx_ctx_set_bp(ctx, &opt.bp_params));
     if (opt.rgb) CHECK(smx_ctx_set_guidance(ctx, SMX_GUIDE_RGB));
     if (opt.cross) CHECK(smx_ctx_set_cross(ctx, &opt.cross_params));      // (its guide: the colour pair)
     if (opt.so) CHECK(smx_ctx_set_scanline(ctx, &opt.so_params));         // (behind the cross stage where that is on too)
@@ -906,6 +954,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.adjust) m.adjusted = m.filled;
     if (opt.cscale) m.cscale = m.dmap[0];
     if (opt.perm) m.perm = m.dmap[0];
+    if (opt.bp) m.bp = m.dmap[0];
     std::vector<float> pm_planes, pm_disp;      // both views' planes and fractional maps: what the twin is compared with
     if (opt.pm) {
         pm_planes.resize((size_t)6 * n);
@@ -922,7 +971,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     // (and with --permeability the filter's: its twin redoes the aggregation of either guide in front of it)
     if (host_compare && opt.perm) check_permeability_twin(j, m, agg_l);
     else if (host_compare && opt.cscale) check_cross_scale_twin(j, m, agg_l);
-    else if (host_compare && (opt.sgm || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m);
+    else if (host_compare && (opt.sgm || opt.bp || opt.rgb || opt.cross || opt.so)) check_aggregation_twin(j, m, agg_l);
     else if (host_compare && opt.pm) check_patchmatch_twin(j, m, pm_planes, pm_disp);
     if (host_compare) check_finish_twins(j, m, agg_l);
     return have_stage_ms;
@@ -947,6 +996,7 @@ int write_outputs(const Job& j, const Maps& m, const std::string& outdir) {
                                   {"occlu_mapl_voted.png", m.voted}, {"occlu_mapl_adjusted.png", m.adjusted},
                                   {"disparity_mapl_cscale.png", m.cscale},
                                   {"disparity_mapl_perm.png", m.perm},
+                                  {"disparity_mapl_bp.png", m.bp},
                                   {"disparity_mapl_patchmatch.png", m.pm_disp},
                                   {"occlu_mapl_wmf.png", m.refined}};
     int write_failures = 0;
@@ -1018,6 +1068,9 @@ int main(int argc, char** argv) {
         {opt.subpixel && (!opt.wmf.empty() || multi),
          "--subpixel cannot be combined with --wmf (the median works on integer labels), --ngpu or --pipeline"},
         {opt.sgm && multi, "--aggregation sgm" + with_multi},
+        {opt.bp && (opt.rgb || opt.cscale || multi),
+         "--aggregation bp cannot be combined with --guidance rgb, --cross-scale, --ngpu or --pipeline"},
+        {opt.bp && labels > SMX_BP_MAX_D, "--aggregation bp takes at most " + std::to_string(SMX_BP_MAX_D) + " labels"},
         {opt.rgb && (opt.sgm || multi), "--guidance rgb cannot be combined with --aggregation sgm, --ngpu or --pipeline"},
         {opt.so && (opt.rgb || multi), std::string("--aggregation ") + (opt.cross ? "cross-scanline" : "scanline") +
                                            " cannot be combined with --guidance rgb, --ngpu or --pipeline"},
@@ -1056,7 +1109,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--ngpu: cannot load the sharded context of libsmx_rccl.so (%s)\n", dlerror());
         return 1;
     }
-    const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || uniq || opt.rgb ||
+    const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || opt.bp || uniq || opt.rgb ||
                        opt.cross || opt.so || opt.adjust || opt.cscale || opt.pm || opt.perm;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");

@@ -14,6 +14,7 @@
 #include "rgb_to_grayscale.cuh"
 #include "colourGuidedFilter.cuh"
 #include "scanlineOptimization.cuh"
+#include "beliefPropagation.cuh"
 #include "sgm.cuh"
 #include "regionVoting.cuh"
 #include "speckle.cuh"
@@ -292,6 +293,17 @@ void sgm_aggregate(float* cost, float* agg, float* best, float* disp_map, const 
         std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
         sgm_aggregateOnCPU(cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d, dmin, p);
         compare_aggregation("Semi-global matching", tb, td, ta, best, disp_map, agg, w * h, size_d);
+    }
+}
+
+// not in the reference: hierarchical belief propagation instead of the guided filter (smx_main --aggregation bp)
+void belief_propagation(float* cost, float* agg, float* best, float* disp_map, const int w, const int h, const int size_d,
+                        const int dmin, const smx_bp_params& p, bool host_gpu_compare) {
+    CHECK(smx_bp_aggregate(&p, cost, agg, best, disp_map, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        std::vector<float> tb((size_t)w * h), td((size_t)w * h), ta(agg ? (size_t)w * h * size_d : 0);
+        beliefPropagationOnCPU(cost, agg ? ta.data() : nullptr, tb.data(), td.data(), w, h, size_d, dmin, p);
+        compare_aggregation("Belief propagation", tb, td, ta, best, disp_map, agg, w * h, size_d);
     }
 }
 

@@ -46,7 +46,7 @@ class ShardedPair:
     The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
     cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError, and so
     do region voting (PairPipeline(vote=...)) and the depth-discontinuity adjustment (PairPipeline(adjust=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
-    one rank: aggregation="sgm" raises ValueError, and so do the scan-line optimiser's "scanline" / "cross-scanline"."""
+    one rank: aggregation="sgm" and aggregation="bp" raise ValueError, and so do the scan-line optimiser's "scanline" / "cross-scanline"."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
@@ -75,6 +75,9 @@ class ShardedPair:
         if kw.get("aggregation") == "patchmatch" or kw.get("pm_params") is not None:
             # (there are no slices to shard: the search has no cost volume)
             raise ValueError("PatchMatch stereo is not part of the sharded driver: use PairPipeline(aggregation='patchmatch')")
+        if kw.get("aggregation") == "bp" or kw.get("bp_params") is not None:
+            # (a message needs every label of a pixel: there are no slices to shard)
+            raise ValueError("belief propagation is not part of the sharded driver: use PairPipeline(aggregation='bp')")
         if kw.get("aggregation") is not None:
             raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
         self.rank, self.world, self.group = rank, world, group

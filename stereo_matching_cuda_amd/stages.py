@@ -431,6 +431,21 @@ def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
     return agg, best, disp
 
 
+def bp_aggregate(cost, dmin=0, params=None, want_agg=True):
+    """Hierarchical belief propagation on one (size_d, h, w) float32 cost volume (smx_bp_aggregate; include/smx.h has the
+    definition).  Returns (agg, best, disp_map) as sgm_aggregate does, with the belief S in the place of SGM's sum."""
+    c = _c(cost, np.float32)
+    if c.ndim != 3:
+        raise ValueError("bp_aggregate expects a (size_d, h, w) float32 volume")
+    size_d, h, w = c.shape
+    p = params if params is not None else _lib.default_bp_params()
+    agg = np.empty((size_d, h, w), np.float32) if want_agg else None
+    best, disp = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_bp_aggregate(C.byref(p), _ptr(c), None if agg is None else _ptr(agg), _ptr(best), _ptr(disp),
+                                           w, h, size_d, int(dmin)))
+    return agg, best, disp
+
+
 def scanline_optimize(guide_own, guide_other, cost, dmin=0, params=None, want_agg=True):
     """Scan-line optimisation with colour-adaptive penalties of one view's (size_d, h, w) float32 cost volume
     (smx_scanline_optimize; include/smx.h has the definition).  guide_own is that view's guide and guide_other the other
