@@ -23,8 +23,7 @@ namespace {
 
 constexpr int ADJ_TW = 64;              // columns of a workgroup = lanes of a wave
 constexpr int ADJ_TH = 4;               // rows of a workgroup = its waves
-constexpr int ADJ_MAX_D = 512;
-constexpr int ADJ_MAX_TAU = 512;
+constexpr int ADJ_MAX_TAU = 512;        // (ADJ_MAX_D: smx_ctx_plan.h, beside shape_ok)
 constexpr int ADJ_MAX_ITER = 8;
 
 // the slice of a labelled value, or -1.  |v| < 2^40 converts exactly; beyond it v - dmin cannot lie in 0 .. 511
@@ -81,10 +80,6 @@ __global__ __launch_bounds__(ADJ_TW * ADJ_TH) void k_adjust_round(const float* _
 bool adjust_params_ok(const smx_adjust_params* p) {
     return p && p->tau_e >= 1 && p->tau_e <= ADJ_MAX_TAU && (p->vertical == 0 || p->vertical == 1) && p->iterations >= 1 &&
            p->iterations <= ADJ_MAX_ITER;
-}
-
-bool adjust_shape_ok(int w, int h, int size_d) {
-    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= ADJ_MAX_D;
 }
 
 size_t adjust_workspace_bytes(int w, int h) { return 255 + 2 * sizeof(float) * (size_t)w * h; }

@@ -3,6 +3,7 @@
 #pragma once
 #include "smx_agg.h"
 #include "smx_cscale_host.h"
+#include "smx_ctx_plan.h"
 #include "smx_perm_host.h"
 
 namespace smx {
@@ -40,37 +41,30 @@ int agg_status_error(unsigned status);  // a workspace's status word [0] -> SMX_
 struct TimingPause { int saved; TimingPause(); ~TimingPause(); };   // while one lives, stage_mark records nothing
 bool subpix_mode_ok(int mode);
 bool wmf_params_ok(const smx_wmf_params* p);
+// (the shape limits, shape_ok and the *_SHAPES texts: smx_ctx_plan.h)
 bool census_params_ok(const smx_census_params* p);
+constexpr const char* CENSUS_RANGES = "census needs 1 <= rx <= 4, 1 <= ry <= 3, th >= 1";
 bool adcensus_params_ok(const smx_adcensus_params* p);
+constexpr const char* ADCENSUS_RANGES = "needs a valid census window, 0 < lambda <= 1e6, 2^-20 <= scale <= 2^20 and colour 0 or 1";
 bool speckle_params_ok(const smx_speckle_params* p);
+constexpr const char* SPECKLE_RANGES = "needs max_size >= 0 and a finite max_diff >= 0";
 bool uniq_ratio_ok(float ratio);
-bool speckle_shape_ok(int w, int h);
 bool sgm_params_ok(const smx_sgm_params* p);
-bool sgm_shape_ok(int w, int h, int size_d);
+constexpr const char* SGM_RANGES = "needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8";
 bool bp_params_ok(const smx_bp_params* p);
+constexpr const char* BP_RANGES = "needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a finite data_scale > 0";
 bool scanline_params_ok(const smx_scanline_params* p);
 constexpr const char* SCANLINE_RANGES = "needs 0 <= p1 <= p2 <= 4095, 1 <= tau_so <= 256 and paths 4 or 8";
 bool cross_params_ok(const smx_cross_params* p);       // (smx_cross.hip, beside the limits of its kernels)
-bool cross_shape_ok(int w, int h);
 constexpr const char* CROSS_RANGES = "needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and 1 <= iterations <= 4";
 bool vote_params_ok(const smx_vote_params* p);         // (smx_vote.hip, beside the limits of its kernels)
-bool vote_shape_ok(int w, int h, int size_d);
 constexpr const char* VOTE_RANGES = "needs tau_s >= 0, 0 <= tau_h_pct <= 99, 0 <= iterations <= 8 and interpolate 0 or 1";
-constexpr const char* VOTE_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
 bool adjust_params_ok(const smx_adjust_params* p);     // (smx_adjust.hip, beside the limits of its kernel)
-bool adjust_shape_ok(int w, int h, int size_d);
 constexpr const char* ADJUST_RANGES = "needs 1 <= tau_e <= 512, vertical 0 or 1 and 1 <= iterations <= 8";
-constexpr const char* ADJUST_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 512";
-bool cscale_shape_ok(int w, int h, int size_d);
 constexpr const char* CSCALE_RANGES = "needs 1 <= scales <= 5 and a finite lambda >= 0";
-constexpr const char* CSCALE_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 2^20";
 bool pm_params_ok(const smx_pm_params* p);             // (smx_patchmatch.hip, beside the limits of its kernels)
-bool pm_shape_ok(int w, int h, int size_d, int dminl, int dminr);
 constexpr const char* PM_RANGES = "needs 0 <= radius <= 17, a finite gamma > 0, 1 <= iterations <= 16 and 0 <= max_slope <= 8";
-constexpr const char* PM_SHAPES = "needs w, h >= 1, w < 2^24, w*h < 2^31, 1 <= size_d <= 2^20 and |dminl|, |dminr| <= 2^20";
-bool perm_shape_ok(int w, int h, int size_d);          // (smx_perm.hip)
 constexpr const char* PERM_RANGES = "needs a finite sigma > 0";
-constexpr const char* PERM_SHAPES = "needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= 2^20";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

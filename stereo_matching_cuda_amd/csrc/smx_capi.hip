@@ -109,7 +109,6 @@ bool adcensus_params_ok(const smx_adcensus_params* p) {
 }
 bool uniq_ratio_ok(float ratio) { return isfinite(ratio) && ratio >= 0.0f; }
 bool speckle_params_ok(const smx_speckle_params* p) { return p && p->max_size >= 0 && isfinite(p->max_diff) && p->max_diff >= 0.0f; }
-bool speckle_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
 bool sgm_params_ok(const smx_sgm_params* p) {
     return p && p->p1 >= 0 && p->p1 <= p->p2 && p->p2 <= 4095 && (p->paths == 4 || p->paths == 8);
 }
@@ -119,9 +118,6 @@ bool scanline_params_ok(const smx_scanline_params* p) {
 bool bp_params_ok(const smx_bp_params* p) {
     return p && p->step >= 0 && p->step <= 4095 && p->trunc >= 0 && p->trunc <= 4095 && p->iterations >= 0 && p->iterations <= 64 &&
            p->levels >= 1 && p->levels <= 8 && isfinite(p->data_scale) && p->data_scale > 0;
-}
-bool sgm_shape_ok(int w, int h, int size_d) {
-    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= SMX_SGM_MAX_D;
 }
 
 }  // namespace smx
@@ -573,7 +569,7 @@ void smx_default_speckle_params(smx_speckle_params* p) {
     p->max_size = 200; p->max_diff = 1.0f;
 }
 
-size_t smx_speckle_workspace_bytes(int w, int h) { return speckle_shape_ok(w, h) ? speckle_workspace_bytes(w, h) : 0; }
+size_t smx_speckle_workspace_bytes(int w, int h) { return shape_ok(w, h, 1, 1) ? speckle_workspace_bytes(w, h) : 0; }
 
 int smx_speckle_geometry(int* tile_cols, int* tile_rows) {
     SMX_ARG(tile_cols && tile_rows);
@@ -583,7 +579,7 @@ int smx_speckle_geometry(int* tile_cols, int* tile_rows) {
 
 int smx_dev_speckle_filter(const smx_speckle_params* p, const float* d_disp, float* d_out, int w, int h, float vmin,
                            float new_val, void* d_ws, size_t ws_bytes, void* stream) {
-    SMX_ARG(speckle_params_ok(p) && d_disp && d_out && speckle_shape_ok(w, h));
+    SMX_ARG(speckle_params_ok(p) && d_disp && d_out && shape_ok(w, h, 1, 1));
     if (!d_ws || ws_bytes < speckle_workspace_bytes(w, h))
         return fail(SMX_E_WS, "smx_dev_speckle_filter: workspace of %zu bytes, %zu needed", d_ws ? ws_bytes : (size_t)0,
                     speckle_workspace_bytes(w, h));
@@ -660,16 +656,16 @@ void smx_default_sgm_params(smx_sgm_params* p) {
 }
 
 size_t smx_sgm_workspace_bytes(int w, int h, int size_d, int nviews) {
-    return sgm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? sgm_workspace_bytes(w, h, size_d, nviews) : 0;
+    return shape_ok(w, h, size_d, SMX_SGM_MAX_D) && (nviews == 1 || nviews == 2) ? sgm_workspace_bytes(w, h, size_d, nviews) : 0;
 }
 
 static int sgm_wta_pair(const char* who, const smx_sgm_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h,
                         int size_d, int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes,
                         void* stream) {
     if (!sgm_params_ok(p))
-        return fail(SMX_E_ARG, "%s: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8", who);
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "%s: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", who, SMX_SGM_MAX_D);
+        return fail(SMX_E_ARG, "%s: %s", who, SGM_RANGES);
+    if (!shape_ok(w, h, size_d, SMX_SGM_MAX_D))
+        return fail(SMX_E_ARG, "%s: %s", who, SGM_SHAPES);
     SMX_ARG((d_cost_l || d_cost_r) && d_keys);
     const size_t need = sgm_workspace_bytes(w, h, size_d, d_cost_l && d_cost_r ? 2 : 1);
     if (!d_ws || ws_bytes < need)
@@ -699,17 +695,15 @@ void smx_default_bp_params(smx_bp_params* p) {
 }
 
 size_t smx_bp_workspace_bytes(int w, int h, int size_d, int levels, int nviews) {
-    return sgm_shape_ok(w, h, size_d) && levels >= 1 && levels <= 8 && (nviews == 1 || nviews == 2)
+    return shape_ok(w, h, size_d, SMX_BP_MAX_D) && levels >= 1 && levels <= 8 && (nviews == 1 || nviews == 2)
                ? bp_workspace_bytes(w, h, size_d, levels, nviews) : 0;
 }
 
 int smx_dev_bp_wta_pair(const smx_bp_params* p, const float* d_cost_l, const float* d_cost_r, int w, int h, int size_d,
                         int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
     if (!bp_params_ok(p))
-        return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
-                               "finite data_scale > 0");
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_BP_MAX_D);
+        return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: %s", BP_RANGES);
+    if (!shape_ok(w, h, size_d, SMX_BP_MAX_D)) return fail(SMX_E_ARG, "smx_dev_bp_wta_pair: %s", BP_SHAPES);
     SMX_ARG((d_cost_l || d_cost_r) && d_keys);
     const size_t need = bp_workspace_bytes(w, h, size_d, p->levels, d_cost_l && d_cost_r ? 2 : 1);
     if (!d_ws || ws_bytes < need)
@@ -724,7 +718,7 @@ void smx_default_scanline_params(smx_scanline_params* p) {
 }
 
 size_t smx_scanline_workspace_bytes(int w, int h, int size_d, int nviews) {
-    return sgm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? scanline_workspace_bytes(w, h, size_d, nviews) : 0;
+    return shape_ok(w, h, size_d, SMX_SGM_MAX_D) && (nviews == 1 || nviews == 2) ? scanline_workspace_bytes(w, h, size_d, nviews) : 0;
 }
 
 int smx_dev_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels,
@@ -732,8 +726,7 @@ int smx_dev_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* d_gui
                               int64_t* d_keys, float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
     if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_scanline_wta_pair: %s", SCANLINE_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_dev_scanline_wta_pair: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    if (!shape_ok(w, h, size_d, SMX_SGM_MAX_D)) return fail(SMX_E_ARG, "smx_dev_scanline_wta_pair: %s", SGM_SHAPES);
     SMX_ARG(d_guide_l && d_guide_r && (d_cost_l || d_cost_r) && d_keys);
     const size_t need = scanline_workspace_bytes(w, h, size_d, d_cost_l && d_cost_r ? 2 : 1);
     if (!d_ws || ws_bytes < need)
@@ -743,7 +736,7 @@ int smx_dev_scanline_wta_pair(const smx_scanline_params* p, const uint8_t* d_gui
 }
 
 // ---- colour-guided filter aggregation (not in the reference; smx_cgf.hip) -----------------------------------------
-static bool cgf_shape_ok(int w, int h) { return w >= 1 && h >= 1 && h <= 65535 && (long long)w * h < (1ll << 31); }
+static bool cgf_shape_ok(int w, int h) { return shape_ok(w, h, 1, 1) && h <= CGF_MAX_H; }
 
 size_t smx_cgf_workspace_bytes(int w, int h, int nslices, int nviews) {
     return cgf_shape_ok(w, h) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cgf_workspace_bytes(w, h, nslices, nviews) : 0;
@@ -753,7 +746,7 @@ int smx_dev_cgf_wta_pair(const smx_params* p, const uint8_t* d_rgb_l, const uint
                          const float* d_cost_l, const float* d_cost_r, int w, int h, int s_begin, int s_end, int64_t* d_keys,
                          float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
     SMX_ARG(p && p->radius >= 0 && (channels == 3 || channels == 4));
-    if (!cgf_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cgf_wta_pair: needs w >= 1, 1 <= h <= 65535 and w*h < 2^31");
+    if (!cgf_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cgf_wta_pair: %s", CGF_SHAPES);
     SMX_ARG(s_begin >= 0 && s_end > s_begin && d_keys);
     SMX_ARG((d_cost_l || d_cost_r) && !d_rgb_l == !d_cost_l && !d_rgb_r == !d_cost_r);
     const int nviews = d_cost_l && d_cost_r ? 2 : 1;
@@ -772,14 +765,14 @@ void smx_default_cross_params(smx_cross_params* p) {
 }
 
 size_t smx_cross_workspace_bytes(int w, int h, int nslices, int nviews) {
-    return cross_shape_ok(w, h) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cross_workspace_bytes(w, h, nslices, nviews) : 0;
+    return shape_ok(w, h, 1, 1) && nslices >= 1 && (nviews == 1 || nviews == 2) ? cross_workspace_bytes(w, h, nslices, nviews) : 0;
 }
 
 int smx_dev_cross_arms(const smx_cross_params* p, const uint8_t* d_guide_l, const uint8_t* d_guide_r, int channels, int w, int h,
                        uint32_t* d_arms, void* stream) {
     if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_arms: %s", CROSS_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_arms: needs w, h >= 1 and w*h < 2^31");
+    if (!shape_ok(w, h, 1, 1)) return fail(SMX_E_ARG, "smx_dev_cross_arms: %s", PLANE_SHAPES);
     SMX_ARG((d_guide_l || d_guide_r) && d_arms);
     return launch_cross_arms(p, d_guide_l, d_guide_r, channels, w, h, d_arms, (hipStream_t)stream);
 }
@@ -789,7 +782,7 @@ int smx_dev_cross_wta_pair(const smx_cross_params* p, const uint8_t* d_guide_l, 
                            float* d_agg, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
     if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: %s", CROSS_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: needs w, h >= 1 and w*h < 2^31");
+    if (!shape_ok(w, h, 1, 1)) return fail(SMX_E_ARG, "smx_dev_cross_wta_pair: %s", PLANE_SHAPES);
     SMX_ARG(s_begin >= 0 && s_end > s_begin && d_keys);
     SMX_ARG((d_cost_l || d_cost_r) && !d_guide_l == !d_cost_l && !d_guide_r == !d_cost_r);
     const int nviews = d_cost_l && d_cost_r ? 2 : 1;
@@ -807,7 +800,7 @@ void smx_default_vote_params(smx_vote_params* p) {
     p->tau_s = 20; p->tau_h_pct = 40; p->iterations = 5; p->interpolate = 1;
 }
 
-size_t smx_vote_workspace_bytes(int w, int h) { return vote_shape_ok(w, h, 1) ? vote_workspace_bytes(w, h) : 0; }
+size_t smx_vote_workspace_bytes(int w, int h) { return shape_ok(w, h, 1, VOTE_MAX_D) ? vote_workspace_bytes(w, h) : 0; }
 
 int smx_vote_geometry(int* tile_cols, int* tile_rows) {
     SMX_ARG(tile_cols && tile_rows);
@@ -820,7 +813,7 @@ int smx_dev_region_vote(const smx_vote_params* p, const uint32_t* d_arms, const 
                         size_t ws_bytes, void* stream) {
     if (!vote_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_region_vote: %s", VOTE_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!vote_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_region_vote: %s", VOTE_SHAPES);
+    if (!shape_ok(w, h, size_d, VOTE_MAX_D)) return fail(SMX_E_ARG, "smx_dev_region_vote: %s", VOTE_SHAPES);
     SMX_ARG(d_arms && d_disp && d_out);
     SMX_ARG(d_guide || !p->interpolate || !d_disp_r);
     if (!d_ws || ws_bytes < vote_workspace_bytes(w, h))
@@ -836,7 +829,7 @@ void smx_default_adjust_params(smx_adjust_params* p) {
     p->tau_e = 2; p->vertical = 1; p->iterations = 1;
 }
 
-size_t smx_adjust_workspace_bytes(int w, int h) { return adjust_shape_ok(w, h, 1) ? adjust_workspace_bytes(w, h) : 0; }
+size_t smx_adjust_workspace_bytes(int w, int h) { return shape_ok(w, h, 1, ADJ_MAX_D) ? adjust_workspace_bytes(w, h) : 0; }
 
 int smx_adjust_geometry(int* cols, int* rows) {
     SMX_ARG(cols && rows);
@@ -847,7 +840,7 @@ int smx_adjust_geometry(int* cols, int* rows) {
 int smx_dev_discontinuity_adjust(const smx_adjust_params* p, const float* d_disp, const float* d_agg, float* d_out, int w, int h,
                                  int dmin, int size_d, int subpix_mode, float* d_sub, void* d_ws, size_t ws_bytes, void* stream) {
     if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: %s", ADJUST_RANGES);
-    if (!adjust_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: %s", ADJUST_SHAPES);
+    if (!shape_ok(w, h, size_d, ADJ_MAX_D)) return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: %s", ADJUST_SHAPES);
     SMX_ARG(d_disp && d_agg && d_out);
     if (d_sub ? !subpix_mode_ok(subpix_mode) : subpix_mode != 0 && !subpix_mode_ok(subpix_mode))
         return fail(SMX_E_ARG, "smx_dev_discontinuity_adjust: subpix_mode must be SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR "
@@ -885,7 +878,7 @@ int smx_pyr_down_geometry(int* cols, int* rows) {
 
 int smx_dev_pyr_down(const uint8_t* d_src, uint8_t* d_dst, int w, int h, int channels, void* stream) {
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cscale_shape_ok(w, h, 1)) return fail(SMX_E_ARG, "smx_dev_pyr_down: needs w, h >= 1 and w*h < 2^31");
+    if (!shape_ok(w, h, 1, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_dev_pyr_down: %s", PLANE_SHAPES);
     SMX_ARG(d_src && d_dst);
     return launch_pyr_down(d_src, d_dst, w, h, channels, (hipStream_t)stream);
 }
@@ -894,7 +887,7 @@ int smx_dev_cscale_wta_pair(const smx_cscale_params* p, const float* const* d_ag
                             int dminl, int dminr, int size_d, int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq,
                             void* stream) {
     if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: %s", CSCALE_RANGES);
-    if (!cscale_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: %s", CSCALE_SHAPES);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_dev_cscale_wta_pair: %s", CSCALE_SHAPES);
     SMX_ARG((d_agg_l || d_agg_r) && d_keys);
     const float* const* views[2] = {d_agg_l, d_agg_r};
     const int dmins[2] = {dminl, dminr};
@@ -979,7 +972,7 @@ int smx_perm_table(const smx_perm_params* p, float* t) {
 }
 
 size_t smx_perm_workspace_bytes(int w, int h, int size_d, int nviews) {
-    return perm_shape_ok(w, h, size_d) && (nviews == 1 || nviews == 2) ? perm_workspace_bytes(w, h, size_d, nviews) : 0;
+    return shape_ok(w, h, size_d, WIDE_MAX_D) && (nviews == 1 || nviews == 2) ? perm_workspace_bytes(w, h, size_d, nviews) : 0;
 }
 
 int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l, const float* d_vol_r, const uint8_t* d_guide_l,
@@ -987,7 +980,7 @@ int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l
                                   int64_t* d_keys, float* d_out, float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
     if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: %s", PERM_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!perm_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: %s", PERM_SHAPES);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_dev_permeability_wta_pair: %s", PERM_SHAPES);
     SMX_ARG((d_vol_l || d_vol_r) && !d_guide_l == !d_vol_l && !d_guide_r == !d_vol_r);
     SMX_ARG(d_keys || (!d_nbr && !d_uq));
     SMX_ARG(dminl >= -(1 << 29) && dminl <= (1 << 29) && dminr >= -(1 << 29) && dminr <= (1 << 29));
@@ -1009,7 +1002,7 @@ int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l
 __attribute__((visibility("default"))) int smx_debug_wta_natural(const float* d_q, int w, int h, int count, int64_t* d_keys,
                                                                  void* stream) {
     SMX_ARG(d_q && d_keys && count >= 1);
-    if (!cscale_shape_ok(w, h, count)) return fail(SMX_E_ARG, "smx_debug_wta_natural: %s", CSCALE_SHAPES);
+    if (!shape_ok(w, h, count, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_debug_wta_natural: %s", CSCALE_SHAPES);
     return wta_launch(WTA_NATURAL, 1, &d_q, &d_keys, nullptr, nullptr, w, h, (size_t)w * h, count, 0, nullptr, 0, true,
                       (hipStream_t)stream);
 }

@@ -267,8 +267,6 @@ bool cross_params_ok(const smx_cross_params* p) {
            p->tau1 <= 256 && p->iterations >= 1 && p->iterations <= 4;
 }
 
-bool cross_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
-
 size_t cross_workspace_bytes(int w, int h, int nslices, int nviews) {
     const size_t c = (size_t)(nslices < CROSS_MAX_CHUNK ? nslices : CROSS_MAX_CHUNK);
     return 255 + (size_t)nviews * (8 + 12 * c) * cells(w, h);

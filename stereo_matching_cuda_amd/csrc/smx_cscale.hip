@@ -210,10 +210,6 @@ void cscale_launch_state(const CsArgs& a, int nviews, bool nbr, bool uq, hipStre
 
 }  // namespace
 
-bool cscale_shape_ok(int w, int h, int size_d) {
-    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= (1 << 20);
-}
-
 void pyr_down_tile(int* tw, int* th) { *tw = PYR_TW; *th = PYR_TH; }
 
 int launch_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int ch, hipStream_t st) {

@@ -1,5 +1,7 @@
-// smx_ctx.hip -- the persistent context of the host-pointer pair entry (smx_create .. smx_ctx_wait, smx_stereo_pair).  A pair's
-// needs are decided once (PairNeeds), reserved in one place (ctx_reserve) and run by ctx_enqueue, which both entries share.
+// smx_ctx.hip -- the persistent context of the host-pointer pair entry (smx_create .. smx_ctx_wait, smx_stereo_pair).  What a
+// pair runs, needs and refuses is decided once by plan_pair (smx_ctx_plan.h: the settings, the stage table, the PairPlan), before
+// anything is allocated; the plan is reserved in one place (ctx_reserve) and run by ctx_enqueue, which both entries share.
+// A new opt-in stage takes a row of that table, its buffers in ctx_reserve, its launch in ctx_enqueue and its setter here.
 #include <string.h>
 
 #include <array>
@@ -18,75 +20,30 @@ struct smx_ctx {
     hipStream_t st = nullptr;
     // keys / best / dmap / mean: left view first, right view behind it (one buffer each)
     DevBuf dL, dR, keys, best, map, mean, occ, fil, ws, costL, costR, aggLR;
-    // The buffers of the opt-in stages are allocated on first use (ctx_reserve).
-    // sub-pixel maps (smx_ctx_set_subpixel): neighbour state [2][3][h][w], maps [2][h][w] and [h][w]
-    int subpix = 0;
-    bool sub_valid = false;     // the maps belong to the last synchronous pair
-    DevBuf nbr, sub, subf;
-    // census cost (smx_ctx_set_cost): the codes [2][h][w]
-    int cost_mode = SMX_COST_REFERENCE;
-    smx_census_params census;
-    DevBuf codes;
-    // AD-Census cost (smx_ctx_set_adcensus): it takes the place of the census cost in every flow, with the same codes, and its
-    // table on the device
-    bool adcensus = false;
-    bool adc_tab_valid = false; // the device table holds the tables of `adc`
-    smx_adcensus_params adc;
+    // The opt-in stages: their settings, the plan of the last synchronous pair that completed (all false while none has: the
+    // smx_ctx_*_map(s) getters read it), and their buffers, allocated on first use (ctx_reserve).
+    CtxSettings s;
+    PairPlan done;
+    DevBuf nbr, sub, subf;      // sub-pixel: neighbour state [2][3][h][w], maps [2][h][w] and [h][w]
+    DevBuf codes;               // census cost, AD-Census: the codes [2][h][w]
+    bool adc_tab_valid = false; // the device table holds the tables of s.adc
     DevBuf adc_tab;
-    // speckle removal (smx_ctx_set_speckle): the despeckled left map [h][w] and the filter's workspace
-    bool speckle = false;
-    bool spk_valid = false;     // the map belongs to the last synchronous pair
-    smx_speckle_params spk_params;
-    DevBuf spk, spk_ws;
-    // semi-global matching (smx_ctx_set_aggregation): it reads the whole volumes costL / costR
-    int agg_mode = SMX_AGG_GUIDED;
-    smx_sgm_params sgm;
-    // uniqueness filtering (smx_ctx_set_uniqueness): the state [2][3][h][w], the filtered left map and the margins [h][w]
-    float uniq = 0.0f;          // the ratio; 0 = off
-    bool uq_valid = false;      // the maps belong to the last synchronous pair
-    DevBuf uq, uq_map, uq_margin;
-    // colour guidance (smx_ctx_set_guidance): the two colour images [2][h][w][4]
-    int guide_mode = SMX_GUIDE_GRAY;
-    DevBuf rgb;
-    // cross-based aggregation (smx_ctx_set_cross)
-    bool cross = false;
-    smx_cross_params cross_params;
-    // the scan-line optimiser (smx_ctx_set_scanline): its workspace and, behind cross-based aggregation, the two volumes of q
-    // [2][size_d][h][w] that it reads
-    bool so = false;
-    smx_scanline_params so_params;
+    DevBuf spk, spk_ws;         // speckle removal: the despeckled left map [h][w] and the filter's workspace
+    DevBuf uq, uq_map, uq_margin;   // uniqueness: the state [2][3][h][w], the filtered left map and the margins [h][w]
+    DevBuf rgb;                 // the two colour images [2][h][w][4]
+    // the scan-line optimiser: its workspace and, behind cross-based aggregation, the two volumes of q [2][size_d][h][w]
     DevBuf so_ws, so_vol;
-    // region voting (smx_ctx_set_vote): the arms of the left guide [h][w], the voted left map [h][w] and the stage's workspace
-    bool vote = false;
-    bool vote_valid = false;    // the map belongs to the last synchronous pair
-    smx_vote_params vote_params;
-    smx_cross_params vote_arms;
-    DevBuf varms, voted, vote_ws;
-    // depth-discontinuity adjustment (smx_ctx_set_adjust): the stage's workspace; it reads the left volume of aggLR
-    bool adjust = false;
-    smx_adjust_params adj_params;
-    DevBuf adj_ws;
-    // cross-scale aggregation (smx_ctx_set_cross_scale): a child context per level 1 .. scales-1, created on first use at the
-    // level's geometry, on this context's stream (owns_st false: the stream is the parent's).  A child holds its level's
-    // images (dL, dR, rgb) and aggregated volumes (aggLR), and is made anew where a pair's label ranges ask for another size_d
-    bool cscale = false;
-    smx_cscale_params cs_params;
+    DevBuf varms, voted, vote_ws;   // region voting: the arms of the left guide [h][w], the voted left map [h][w], the workspace
+    DevBuf adj_ws;              // the adjustment's workspace; it reads the left volume of aggLR
+    // cross-scale aggregation: a child context per level 1 .. scales-1, created on first use at the level's geometry, on this
+    // context's stream (owns_st false: the stream is the parent's).  A child holds its level's images (dL, dR, rgb) and
+    // aggregated volumes (aggLR), and is made anew where a pair's label ranges ask for another size_d
     smx_ctx* cs_child[SMX_CSCALE_MAX_SCALES] = {};
     bool owns_st = true;
-    // PatchMatch stereo (smx_ctx_set_patchmatch): it takes the place of cost and aggregation.  The planes [2][3][h][w], disp
-    // [2][h][w] and the search's workspace; its sub-pixel filled map lies in subf
-    bool pm = false;
-    bool pm_valid = false;      // the maps belong to the last synchronous pair
-    smx_pm_params pm_params;
+    // PatchMatch stereo: the planes [2][3][h][w], disp [2][h][w] and the search's workspace; its sub-pixel filled map lies in subf
     DevBuf pm_planes, pm_disp, pm_ws;
-    // the permeability filter (smx_ctx_set_permeability): it runs in place over both volumes of aggLR; its workspace
-    bool perm = false;
-    smx_perm_params perm_params;
-    DevBuf perm_ws;
-    // hierarchical belief propagation (smx_ctx_set_bp): it reads the whole volumes costL / costR, as SGM does; its workspace
-    bool bp = false;
-    smx_bp_params bp_params;
-    DevBuf bp_ws;
+    DevBuf perm_ws;             // the permeability filter runs in place over both volumes of aggLR; its workspace
+    DevBuf bp_ws;               // belief propagation reads the whole volumes costL / costR, as SGM does; its workspace
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
     // of which this pair's mode and chunk use mode_ws_bytes; the buffer itself only grows, so it may be larger.  chunk: the
@@ -119,16 +76,6 @@ struct smx_ctx {
     }
 };
 
-// What one pair asks of the context beyond the eight result planes, decided once per pair by the entry that was called
-// (cost / agg: the whole volumes; cost: the caller wants them, or SGM reads them; census: a cost built from census codes, the
-// census cost or AD-Census); its device images with the disparity of slice 0 of either view; where its results go on the
-// device (best / map / mean: left view first, right view behind it).
-// cscale: the winners come from the cross-scale combination; level: this pair is a level of another context's pyramid, which
-// wants its aggregated volumes and nothing behind them.  pm: PatchMatch stereo in place of cost, aggregation and winners.
-// perm: the winners come from the permeability filter over the aggregated volumes.
-// bp: the winners come from belief propagation on the whole cost volumes.
-struct PairNeeds { bool cost, agg, subpix, census, sgm, speckle, uniq, cgf, cross, vote, so, adjust, cscale, level, pm, perm, bp; };
-
 // The permeability filter's workspace for both views: every slice at once where that stays within ~1 GiB, else what does, and one
 // slice at least (the pass goes in chunks of slices over the volumes it filters in place)
 static size_t ctx_perm_ws_bytes(const smx_ctx* c) {
@@ -150,7 +97,7 @@ static int halved_chunk(const smx_ctx* c, size_t (*ws_bytes)(int, int, int, int)
 }
 
 // Every buffer `need` asks for, each under its own guard: after a failed allocation the next call simply retries.
-static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
+static int ctx_reserve(smx_ctx* c, const PairPlan& need) {
     const size_t fb = c->n * sizeof(float), vb = fb * c->size_d;
     if (need.cost) { SMX_HIP(c->costL.ensure(vb)); SMX_HIP(c->costR.ensure(vb)); }
     if (need.agg) SMX_HIP(c->aggLR.ensure(2 * vb));
@@ -169,7 +116,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
     }
     if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
     if (need.perm) SMX_HIP(c->perm_ws.ensure(ctx_perm_ws_bytes(c)));
-    if (need.bp) SMX_HIP(c->bp_ws.ensure(bp_workspace_bytes(c->w, c->h, c->size_d, c->bp_params.levels, 2)));
+    if (need.bp) SMX_HIP(c->bp_ws.ensure(bp_workspace_bytes(c->w, c->h, c->size_d, c->s.bp_params.levels, 2)));
     if (need.pm) {
         SMX_HIP(c->pm_planes.ensure(6 * fb));
         SMX_HIP(c->pm_disp.ensure(2 * fb));
@@ -196,7 +143,7 @@ static int ctx_reserve(smx_ctx* c, const PairNeeds& need) {
 // The census codes of both images of `call`: one launch where they lie back to back, else one per image
 static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
     uint64_t* codes = c->codes.as<uint64_t>();
-    const smx_census_params* cp = c->adcensus ? &c->adc.census : &c->census;
+    const smx_census_params* cp = c->s.adcensus ? &c->s.adc.census : &c->s.census;
     if (call.guide[1] == call.guide[0] + c->n) return smx_dev_census(cp, call.guide[0], codes, c->w, c->h, 2, call.st);
     int rc = SMX_OK;
     for (int v = 0; v < 2 && !rc; ++v) rc = smx_dev_census(cp, call.guide[v], codes + v * c->n, c->w, c->h, 1, call.st);
@@ -207,9 +154,9 @@ static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
 // from the colour images of the pair
 static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int s0, int s1, hipStream_t st) {
     const uint64_t* codes = c->codes.as<uint64_t>();
-    if (!c->adcensus) return smx_dev_census_cost_pair(&c->census, codes, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
-    const bool colour = c->adc.colour != 0;
-    return smx_dev_adcensus_cost_pair(&c->adc, c->adc_tab.as<float>(), codes, colour ? in.rgb_l : in.left,
+    if (!c->s.adcensus) return smx_dev_census_cost_pair(&c->s.census, codes, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
+    const bool colour = c->s.adc.colour != 0;
+    return smx_dev_adcensus_cost_pair(&c->s.adc, c->adc_tab.as<float>(), codes, colour ? in.rgb_l : in.left,
                                       colour ? in.rgb_r : in.right, colour ? in.channels : 1, cl, cr, c->w, c->h, in.dminl,
                                       in.dminr, s0, s1, st);
 }
@@ -219,7 +166,7 @@ static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int
 // both views (from the codes, or the reference's; nothing where the whole reference volumes were built up front) into the
 // whole volumes where the context holds them, else into the chunk buffer; then its aggregation, which accumulates into the
 // keys and the states of `call`.
-static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& call, const PairNeeds& need) {
+static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& call, const PairPlan& need) {
     const size_t n = c->n;
     const int w = c->w, h = c->h, chunk = c->chunk;
     // cross-based: the guide is the colour pair where the pair came as colour images, else the gray pair
@@ -250,7 +197,7 @@ static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& cal
             auto views = [&](const uint8_t* l, const uint8_t* r, const float* kl, const float* kr, int v) {
                 return need.cgf ? smx_dev_cgf_wta_pair(&c->p, l, r, ch, kl, kr, w, h, s0, s1, call.keys[v], agg[v], call.nbr[v],
                                                        call.uq[v], c->mode_ws.p, c->mode_ws_bytes, call.st)
-                                : smx_dev_cross_wta_pair(&c->cross_params, l, r, ch, kl, kr, w, h, s0, s1, call.keys[v], agg[v],
+                                : smx_dev_cross_wta_pair(&c->s.cross_params, l, r, ch, kl, kr, w, h, s0, s1, call.keys[v], agg[v],
                                                          call.nbr[v], call.uq[v], c->mode_ws.p, c->mode_ws_bytes, call.st);
             };
             // with the aggregated volumes wanted, view by view: the pair form lays its two views a chunk apart, the context a volume
@@ -264,7 +211,7 @@ static int ctx_aggregate_chunks(smx_ctx* c, const PairIn& in, const AggCall& cal
 
 // The stages between the LR check and the sub-pixel maps: uniqueness, speckle removal, region voting, each followed by a fill
 // that starts over from its map.  *kept: the map whose validity test says which pixels the fill replaced.
-static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out, const int64_t* keysL,
+static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairPlan& need, const PairPlanes& out, const int64_t* keysL,
                               const float* uqL, const float** kept_out) {
     const smx_params* p = &c->p;
     const int w = c->w, h = c->h, size_d = c->size_d;
@@ -276,7 +223,7 @@ static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& nee
         // the ambiguous winners of the LR-checked left map join the invalidated pixels; the fill starts over from that map
         // (unless speckle removal follows, which does it)
         float* um = c->uq_map.as<float>();
-        if ((rc = smx_dev_uniqueness(c->uniq, keysL, uqL, out.occ, um, c->uq_margin.as<float>(), w, h, (float)in.dminl,
+        if ((rc = smx_dev_uniqueness(c->s.uniq, keysL, uqL, out.occ, um, c->uq_margin.as<float>(), w, h, (float)in.dminl,
                                      (float)(in.dminl - 100), st)))
             return rc;
         if (!need.speckle && (rc = launch_fill_occlusion(um, out.fil, w, h, (float)in.dminl, st))) return rc;
@@ -285,7 +232,7 @@ static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& nee
     if (need.speckle) {
         // the small components of the LR-checked map join the invalidated pixels; the fill starts over from that map
         float* spk = c->spk.as<float>();
-        if ((rc = smx_dev_speckle_filter(&c->spk_params, kept, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
+        if ((rc = smx_dev_speckle_filter(&c->s.spk_params, kept, spk, w, h, (float)in.dminl, (float)(in.dminl - 100),
                                          c->spk_ws.p, speckle_workspace_bytes(w, h), st)))
             return rc;
         if ((rc = launch_fill_occlusion(spk, out.fil, w, h, (float)in.dminl, st))) return rc;
@@ -298,8 +245,8 @@ static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& nee
         const int ch = in.channels ? in.channels : 1;
         uint32_t* arms = c->varms.as<uint32_t>();
         float* voted = c->voted.as<float>();
-        if ((rc = smx_dev_cross_arms(&c->vote_arms, guide, nullptr, ch, w, h, arms, st))) return rc;
-        if ((rc = smx_dev_region_vote(&c->vote_params, arms, guide, ch, kept, out.map + n, voted, w, h, in.dminl, size_d, p->d_lr,
+        if ((rc = smx_dev_cross_arms(&c->s.vote_arms, guide, nullptr, ch, w, h, arms, st))) return rc;
+        if ((rc = smx_dev_region_vote(&c->s.vote_params, arms, guide, ch, kept, out.map + n, voted, w, h, in.dminl, size_d, p->d_lr,
                                       c->vote_ws.p, vote_workspace_bytes(w, h), st)))
             return rc;
         if ((rc = launch_fill_occlusion(voted, out.fil, w, h, (float)in.dminl, st))) return rc;
@@ -311,13 +258,13 @@ static int ctx_outlier_stages(smx_ctx* c, const PairIn& in, const PairNeeds& nee
 // A PatchMatch pair: the search gives both views' labels (dmap) and plane costs (best) directly; the LR check and the fill of
 // main.cu:140-155 run on the labels, the outlier stages behind them unchanged, and the sub-pixel filled map is the left disp
 // where the pixel was kept, the filled label elsewhere (the rule of smx_dev_subpixel_pair).
-static int ctx_enqueue_pm(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
+static int ctx_enqueue_pm(smx_ctx* c, const PairIn& in, const PairPlan& need, const PairPlanes& out) {
     const int w = c->w, h = c->h;
     const size_t n = c->n;
     hipStream_t st = c->st;
     int rc;
     float* disp = c->pm_disp.as<float>();
-    if ((rc = smx_dev_patchmatch_pair(&c->p, &c->pm_params, in.left, in.right, w, h, c->size_d, in.dminl, in.dminr,
+    if ((rc = smx_dev_patchmatch_pair(&c->p, &c->s.pm_params, in.left, in.right, w, h, c->size_d, in.dminl, in.dminr,
                                       c->pm_planes.as<float>(), out.best, disp, out.map, c->pm_ws.p, pm_workspace_bytes(w, h), st)))
         return rc;
     SMX_HIP(hipMemcpyAsync(out.occ, out.map, n * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -329,7 +276,7 @@ static int ctx_enqueue_pm(smx_ctx* c, const PairIn& in, const PairNeeds& need, c
 }
 
 // The path of one pair on the context's stream: device images in, the eight result planes (+ the context's volumes) out.
-static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, const PairPlanes& out) {
+static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairPlan& need, const PairPlanes& out) {
     if (need.pm) return ctx_enqueue_pm(c, in, need, out);
     const smx_params* p = &c->p;
     const int w = c->w, h = c->h, size_d = c->size_d;
@@ -362,14 +309,14 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
         if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
-        if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->mode_ws.p,
+        if (!rc) rc = need.uniq ? smx_dev_sgm_wta_pair_uq(&c->s.sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->mode_ws.p,
                                                           c->mode_ws_bytes, st)
-                                : smx_dev_sgm_wta_pair(&c->sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->mode_ws.p,
+                                : smx_dev_sgm_wta_pair(&c->s.sgm, costL, costR, w, h, size_d, keysL, aggL, nbrL, c->mode_ws.p,
                                                        c->mode_ws_bytes, st);
     } else if (need.bp) {
         // belief propagation instead of the guided filter: the flow of SGM, the uniqueness state from the same call
         if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
-        if (!rc) rc = smx_dev_bp_wta_pair(&c->bp_params, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->bp_ws.p, c->bp_ws.bytes, st);
+        if (!rc) rc = smx_dev_bp_wta_pair(&c->s.bp_params, costL, costR, w, h, size_d, keysL, aggL, nbrL, uqL, c->bp_ws.p, c->bp_ws.bytes, st);
     } else if (need.so) {
         // the scan-line optimiser reads whole volumes: the cost volumes, as SGM does, or behind cross-based aggregation the
         // two volumes of its q, collected over the chunks with the keys of that pass discarded (the optimiser's are OUT only)
@@ -380,14 +327,14 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         if (need.cross) {
             float* vol = c->so_vol.as<float>();
             AggCall chain = call;
-            PairNeeds cn = need;
+            PairPlan cn = need;
             cn.agg = true;
             chain.agg[0] = vol; chain.agg[1] = vol + (size_t)size_d * n;
             chain.nbr[0] = chain.nbr[1] = chain.uq[0] = chain.uq[1] = nullptr;
             rc = ctx_aggregate_chunks(c, in, chain, cn);
             vl = vol; vr = vol + (size_t)size_d * n;
         } else if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
-        if (!rc) rc = smx_dev_scanline_wta_pair(&c->so_params, gl, gr, in.channels ? in.channels : 1, vl, vr, w, h, size_d, in.dminl,
+        if (!rc) rc = smx_dev_scanline_wta_pair(&c->s.so_params, gl, gr, in.channels ? in.channels : 1, vl, vr, w, h, size_d, in.dminl,
                                                 in.dminr, keysL, aggL, nbrL, uqL, c->so_ws.p, c->so_ws.bytes, st);
     } else if (need.cgf || need.cross || need.census) rc = ctx_aggregate_chunks(c, in, call, need);
     else rc = run_aggregation(call, c->agg_path, false);
@@ -398,18 +345,18 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         // and its winners and states take the place of the plain ones
         const float* al[SMX_CSCALE_MAX_SCALES] = {aggL};
         const float* ar[SMX_CSCALE_MAX_SCALES] = {aggL + (size_t)size_d * n};
-        for (int s = 1; s < c->cs_params.scales; ++s) {
+        for (int s = 1; s < c->s.cs_params.scales; ++s) {
             smx_ctx* k = c->cs_child[s];
             al[s] = k->aggLR.as<float>();
             ar[s] = al[s] + (size_t)k->size_d * k->n;
         }
-        if ((rc = smx_dev_cscale_wta_pair(&c->cs_params, al, ar, w, h, in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, st)))
+        if ((rc = smx_dev_cscale_wta_pair(&c->s.cs_params, al, ar, w, h, in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, st)))
             return rc;
     }
     if (need.perm) {
         // the filter goes over both aggregated volumes in place; its winners and states take the place of the plain ones
         const bool colour = need.cgf;
-        if ((rc = smx_dev_permeability_wta_pair(&c->perm_params, aggL, aggL + (size_t)size_d * n, colour ? in.rgb_l : in.left,
+        if ((rc = smx_dev_permeability_wta_pair(&c->s.perm_params, aggL, aggL + (size_t)size_d * n, colour ? in.rgb_l : in.left,
                                                 colour ? in.rgb_r : in.right, colour ? in.channels : 1, w, h, in.dminl, in.dminr,
                                                 size_d, keysL, aggL, nbrL, uqL, c->perm_ws.p, ctx_perm_ws_bytes(c), st)))
             return rc;
@@ -420,13 +367,13 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairNeeds& need, cons
         return rc;
     const float* kept = nullptr;
     if ((rc = ctx_outlier_stages(c, in, need, out, keysL, uqL, &kept))) return rc;
-    if (need.subpix && (rc = smx_dev_subpixel_pair(c->subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl,
+    if (need.subpix && (rc = smx_dev_subpixel_pair(c->s.subpix, keysL, nbrL, out.map, kept, out.fil, w, h, in.dminl,
                                                    c->sub.as<float>(), c->subf.as<float>(), st)))
         return rc;
     if (!need.adjust) return SMX_OK;
     // the filled map looks at the left volume again: a pixel beside a depth step takes the neighbour's label where that costs
     // it less, in place, and its entry of the sub-pixel filled map becomes its own fit; `kept` is not replaced
-    return smx_dev_discontinuity_adjust(&c->adj_params, out.fil, aggL, out.fil, w, h, in.dminl, size_d, c->subpix,
+    return smx_dev_discontinuity_adjust(&c->s.adj_params, out.fil, aggL, out.fil, w, h, in.dminl, size_d, c->s.subpix,
                                         need.subpix ? c->subf.as<float>() : nullptr, c->adj_ws.p, adjust_workspace_bytes(w, h), st);
 }
 
@@ -437,11 +384,11 @@ static int ctx_adcensus_table(smx_ctx* c);
 // the colour pyramid from the colour images), then the level's pair through ctx_enqueue on a child context that takes this
 // context's settings.  Both views of a level run with the larger of the two views' slice counts; the slices past a view's own
 // range are not read by the combination.
-static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, const PairNeeds& need) {
+static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, const PairPlan& need) {
     int rc;
     const smx_ctx* below = c;
     PairIn src = in;
-    for (int s = 1; s < c->cs_params.scales; ++s) {
+    for (int s = 1; s < c->s.cs_params.scales; ++s) {
         int ws, hs, dl, dr, sl, sr;
         cscale_level(c->w, c->h, in.dminl, c->size_d, s, &ws, &hs, &dl, &sl);
         cscale_level(c->w, c->h, in.dminr, c->size_d, s, &ws, &hs, &dr, &sr);
@@ -452,16 +399,16 @@ static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, cons
         if (!k && (rc = ctx_create(&c->p, ws, hs, sd, c->st, &k))) return rc;
         k->p = c->p;
         k->agg_path = c->agg_path;
-        k->cost_mode = c->cost_mode;
-        k->census = c->census;
-        k->guide_mode = c->guide_mode;
-        if (c->adcensus && (!k->adcensus || memcmp(&k->adc, &c->adc, sizeof(k->adc)) != 0)) { k->adc = c->adc; k->adc_tab_valid = false; }
-        k->adcensus = c->adcensus;
-        PairNeeds kn = {};
+        k->s.cost_mode = c->s.cost_mode;
+        k->s.census = c->s.census;
+        k->s.guide_mode = c->s.guide_mode;
+        if (c->s.adcensus && (!k->s.adcensus || memcmp(&k->s.adc, &c->s.adc, sizeof(k->s.adc)) != 0)) { k->s.adc = c->s.adc; k->adc_tab_valid = false; }
+        k->s.adcensus = c->s.adcensus;
+        PairPlan kn = {};
         kn.agg = kn.level = true;
         kn.census = need.census;
         kn.cgf = need.cgf;
-        if (kn.cgf && smx_cgf_workspace_bytes(ws, hs, 1, 2) == 0)
+        if (kn.cgf && !stage_shape_ok(STAGES[S_CGF], ws, hs, 1, 0, 0))
             return fail(SMX_E_ARG, "%s: the colour-guided filter does not take cross-scale level %d", who, s);
         if ((rc = ctx_reserve(k, kn))) return rc;
         if ((rc = ctx_adcensus_table(k))) return rc;
@@ -500,7 +447,7 @@ static std::array<PlaneRef, 12> pair_planes(const smx_pair_out& o, size_t size_d
              {o.filled, f}, {o.cost_l, v}, {o.cost_r, v}, {o.agg_l, v}, {o.agg_r, v}}};
 }
 
-// shared: NULL, or the stream of the context this one is a pyramid level of
+// shared: NULL, or the stream of the parent context of this pyramid level
 static int ctx_create(const smx_params* p, int w, int h, int size_d, hipStream_t shared, smx_ctx** out) {
     *out = nullptr;
     smx_ctx* c = new (std::nothrow) smx_ctx;
@@ -527,9 +474,9 @@ static int ctx_create(const smx_params* p, int w, int h, int size_d, hipStream_t
 
 // The device table of the AD-Census cost, built where the context's parameters changed
 static int ctx_adcensus_table(smx_ctx* c) {
-    if (!c->adcensus || c->adc_tab_valid) return SMX_OK;
+    if (!c->s.adcensus || c->adc_tab_valid) return SMX_OK;
     SMX_HIP(c->adc_tab.ensure(SMX_ADCENSUS_TABLE_FLOATS * sizeof(float)));
-    if (int rc = smx_dev_adcensus_tables(&c->adc, c->adc_tab.as<float>(), c->st)) return rc;
+    if (int rc = smx_dev_adcensus_tables(&c->s.adc, c->adc_tab.as<float>(), c->st)) return rc;
     c->adc_tab_valid = true;
     return SMX_OK;
 }
@@ -564,107 +511,23 @@ int smx_destroy(smx_ctx* c) {
 
 // The synchronous pair entry on gray images (channels == 0: img_l / img_r are the gray images) or on colour images, whose
 // gray images for the cost are made on the device.
-static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uint8_t* img_r, int channels, int dminl, int dminr,
-                    const smx_pair_out* out) {
+static int ctx_pair(smx_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int channels, int dminl, int dminr, const smx_pair_out* out) {
+    const PairEntry entry = channels ? ENTRY_RGB : ENTRY_GRAY;
+    const char* who = ENTRY_NAMES[entry];
     const size_t n = c->n;
     int rc;
     if ((rc = ctx_check_device(c, who))) return rc;
     if (c->submitted != c->waited) return fail(SMX_E_ARG, "%s: pipelined pairs are still in flight (smx_ctx_wait)", who);
     hipStream_t st = c->st;
-    const bool sgm = c->agg_mode == SMX_AGG_SGM;
-    const bool cgf = c->guide_mode == SMX_GUIDE_RGB;
-    if (sgm && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: semi-global matching (smx_ctx_set_aggregation) produces no mean images", who);
-    if (cgf && !channels)
-        return fail(SMX_E_ARG, "%s: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb", who);
-    if (cgf && sgm) return fail(SMX_E_ARG, "%s: colour guidance belongs to the guided filter, not to semi-global matching", who);
-    if (cgf && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: the colour-guided filter (smx_ctx_set_guidance) produces no mean images", who);
-    if (cgf && smx_cgf_workspace_bytes(c->w, c->h, 1, 2) == 0)
-        return fail(SMX_E_ARG, "%s: the colour-guided filter needs h <= 65535 and w*h < 2^31", who);
-    const bool cross = c->cross;
-    if (cross && sgm) return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) and semi-global matching are both on", who);
-    if (cross && cgf) return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) and colour guidance are both on", who);
-    if (cross && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: cross-based aggregation (smx_ctx_set_cross) produces no mean images", who);
-    if (cross && !cross_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "%s: cross-based aggregation needs w*h < 2^31", who);
-    const bool so = c->so;
-    if (so && sgm) return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) and semi-global matching are both on", who);
-    if (so && cgf) return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) and colour guidance are both on", who);
-    if (so && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: the scan-line optimiser (smx_ctx_set_scanline) produces no mean images", who);
-    if (so && !sgm_shape_ok(c->w, c->h, c->size_d))
-        return fail(SMX_E_ARG, "%s: the scan-line optimiser needs w*h < 2^31 and size_d <= %d", who, SMX_SGM_MAX_D);
-    if (c->adcensus && c->adc.colour && !channels)
-        return fail(SMX_E_ARG, "%s: the AD-Census cost takes its AD term from the colour images (smx_ctx_set_adcensus): use "
-                               "smx_ctx_stereo_pair_rgb", who);
-    if (c->adjust && !adjust_shape_ok(c->w, c->h, c->size_d))
-        return fail(SMX_E_ARG, "%s: the depth-discontinuity adjustment (smx_ctx_set_adjust) %s", who, ADJUST_SHAPES);
-    const bool cscale = c->cscale;
-    if (cscale && (sgm || cross || so))
-        return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) belongs to the guided filter: the integer "
-                               "volumes and fixed penalties of %s do not rescale across levels", who,
-                    sgm ? "semi-global matching" : so ? "the scan-line optimiser" : "cross-based aggregation");
-    if (cscale && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: cross-scale aggregation (smx_ctx_set_cross_scale) produces no mean images", who);
-    if (cscale && !cscale_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: cross-scale aggregation %s", who, CSCALE_SHAPES);
-    const bool perm = c->perm;
-    if (perm && (sgm || cross || so))
-        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) runs behind the guided filter: %s keeps "
-                               "integer [y][x][d] volumes", who,
-                    sgm ? "semi-global matching" : so ? "the scan-line optimiser" : "cross-based aggregation");
-    if (perm && cscale)
-        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) and cross-scale aggregation "
-                               "(smx_ctx_set_cross_scale) are both on: not built yet", who);
-    if (perm && (out->mean_l || out->mean_r))
-        return fail(SMX_E_ARG, "%s: the permeability filter (smx_ctx_set_permeability) produces no mean images", who);
-    if (perm && !perm_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "%s: the permeability filter %s", who, PERM_SHAPES);
-    const bool bp = c->bp;
-    if (bp) {
-        const char* with = sgm      ? "semi-global matching (smx_ctx_set_aggregation)"
-                           : cgf    ? "colour guidance (smx_ctx_set_guidance)"
-                           : cross  ? "cross-based aggregation (smx_ctx_set_cross)"
-                           : so     ? "the scan-line optimiser (smx_ctx_set_scanline)"
-                           : cscale ? "cross-scale aggregation (smx_ctx_set_cross_scale)"
-                           : perm   ? "the permeability filter (smx_ctx_set_permeability)"
-                           : c->pm  ? "PatchMatch stereo (smx_ctx_set_patchmatch)"
-                                    : nullptr;
-        if (with) return fail(SMX_E_ARG, "%s: belief propagation (smx_ctx_set_bp) is on, and so is %s", who, with);
-        if (out->mean_l || out->mean_r) return fail(SMX_E_ARG, "%s: belief propagation (smx_ctx_set_bp) produces no mean images", who);
-        if (!sgm_shape_ok(c->w, c->h, c->size_d))
-            return fail(SMX_E_ARG, "%s: belief propagation needs w*h < 2^31 and size_d <= %d", who, SMX_BP_MAX_D);
-    }
-    const bool pm = c->pm;
-    if (pm) {
-        // PatchMatch keeps no cost volume: every stage that reads one has nothing to read, and the rest is out of scope
-        const char* with = c->cost_mode != SMX_COST_REFERENCE ? "the census cost (smx_ctx_set_cost)"
-                           : c->adcensus                      ? "the AD-Census cost (smx_ctx_set_adcensus)"
-                           : cgf                              ? "colour guidance (smx_ctx_set_guidance)"
-                           : sgm                              ? "semi-global matching (smx_ctx_set_aggregation)"
-                           : cross                            ? "cross-based aggregation (smx_ctx_set_cross)"
-                           : so                               ? "the scan-line optimiser (smx_ctx_set_scanline)"
-                           : cscale                           ? "cross-scale aggregation (smx_ctx_set_cross_scale)"
-                           : c->perm                          ? "the permeability filter (smx_ctx_set_permeability)"
-                           : c->adjust                        ? "the depth-discontinuity adjustment (smx_ctx_set_adjust)"
-                           : c->uniq > 0.0f                   ? "the uniqueness test (smx_ctx_set_uniqueness)"
-                           : c->subpix                        ? "the sub-pixel fit (smx_ctx_set_subpixel; the planes are sub-pixel already)"
-                                                              : nullptr;
-        if (with) return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) is on, and so is %s", who, with);
-        if (out->cost_l || out->cost_r || out->agg_l || out->agg_r || out->mean_l || out->mean_r)
-            return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) produces no cost volumes, aggregated volumes or "
-                                   "mean images", who);
-        if (!pm_shape_ok(c->w, c->h, c->size_d, dminl, dminr))
-            return fail(SMX_E_ARG, "%s: PatchMatch stereo (smx_ctx_set_patchmatch) %s", who, PM_SHAPES);
-    }
-    // (the optimiser alone reads the whole cost volumes, as SGM does; behind cross-based aggregation it reads that stage's q;
-    // the adjustment reads the left aggregated volume, so the pair keeps the volumes as if the caller had asked for them)
-    const PairNeeds need = {out->cost_l || out->cost_r || sgm || bp || (so && !cross), out->agg_l || out->agg_r || c->adjust || cscale || perm, c->subpix != 0,
-                            c->cost_mode == SMX_COST_CENSUS || c->adcensus, sgm, c->speckle, c->uniq > 0.0f, cgf, cross, c->vote, so,
-                            c->adjust, cscale, false, pm, perm, bp};
+    PairPlan need;
+    char why[512];
+    if (plan_pair(c->s, c->w, c->h, c->size_d, entry, channels, dminl, dminr, out->cost_l || out->cost_r,
+                  out->agg_l || out->agg_r, out->mean_l || out->mean_r, &need, why, sizeof(why)))
+        return fail(SMX_E_ARG, "%s", why);
     if ((rc = ctx_reserve(c, need))) return rc;
     if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
-    c->sub_valid = c->spk_valid = c->uq_valid = c->vote_valid = c->pm_valid = false;
+    c->done = PairPlan{};
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     uint8_t* rgbL = channels ? c->rgb.as<uint8_t>() : nullptr;
     uint8_t* rgbR = channels ? rgbL + n * (size_t)channels : nullptr;
@@ -681,7 +544,7 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
     stage_mark(ST_UPLOAD, st);
     float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
     uint8_t* mean = c->mean.as<uint8_t>();
-    if (cscale && (rc = ctx_cscale_levels(c, who, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need))) return rc;
+    if (need.cscale && (rc = ctx_cscale_levels(c, who, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need))) return rc;
     if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need,
                           {best, map, mean, c->occ.as<float>(), c->fil.as<float>()})))
         return rc;
@@ -692,17 +555,13 @@ static int ctx_pair(smx_ctx* c, const char* who, const uint8_t* img_l, const uin
         if (to[i].p && from[i].p) SMX_HIP(hipMemcpyAsync(to[i].p, from[i].p, n * from[i].elem, hipMemcpyDeviceToHost, st));
     stage_mark(ST_DOWNLOAD, st);
     SMX_HIP(hipStreamSynchronize(st));
-    // (the SGM, belief-propagation, colour-guided, cross-based and PatchMatch kernels wait for nothing)
-    if (!need.sgm && !need.bp && !need.cgf && !need.cross && !need.so && !need.pm) {
+    // (only the fused aggregation waits for a hand-over, and reports one that timed out)
+    if (need.walker_status) {
         if ((rc = smx_dev_agg_status(c->ws.p))) return rc;
-        for (int s = 1; cscale && s < c->cs_params.scales; ++s)
+        for (int s = 1; need.cscale && s < c->s.cs_params.scales; ++s)
             if ((rc = smx_dev_agg_status(c->cs_child[s]->ws.p))) return rc;
     }
-    c->sub_valid = need.subpix;
-    c->spk_valid = need.speckle;
-    c->uq_valid = need.uniq;
-    c->vote_valid = need.vote;
-    c->pm_valid = need.pm;
+    c->done = need;
     return SMX_OK;
 }
 
@@ -711,48 +570,74 @@ extern "C" {
 int smx_ctx_stereo_pair(smx_ctx* c, const uint8_t* gray_l, const uint8_t* gray_r, int dminl, int dminr,
                         const smx_pair_out* out) {
     SMX_ARG(c && gray_l && gray_r && out);
-    return ctx_pair(c, "smx_ctx_stereo_pair", gray_l, gray_r, 0, dminl, dminr, out);
+    return ctx_pair(c, gray_l, gray_r, 0, dminl, dminr, out);
 }
 
 int smx_ctx_stereo_pair_rgb(smx_ctx* c, const uint8_t* rgb_l, const uint8_t* rgb_r, int channels, int dminl, int dminr,
                             const smx_pair_out* out) {
     SMX_ARG(c && rgb_l && rgb_r && out && (channels == 3 || channels == 4));
-    return ctx_pair(c, "smx_ctx_stereo_pair_rgb", rgb_l, rgb_r, channels, dminl, dminr, out);
+    return ctx_pair(c, rgb_l, rgb_r, channels, dminl, dminr, out);
 }
+
+// ---- the setters.  Those that switch a stage on with a params struct and off with NULL share ctx_set_stage: the struct is
+// validated and copied, the stage's shape limit checked where its row says AT_SETTER, and a refused call changes nothing.
+}  // extern "C"
+
+template <class P>
+static int ctx_set_stage(smx_ctx* c, CtxStage id, bool CtxSettings::*on, P CtxSettings::*slot, const P* p, bool (*params_ok)(const P*),
+                         const char* ranges) {
+    SMX_ARG(c);
+    const StageRow& row = STAGES[id];
+    if (p) {
+        if (!params_ok(p)) return fail(SMX_E_ARG, "%s: %s", row.setter, ranges);
+        if ((row.limit.checked & AT_SETTER) && !stage_shape_ok(row, c->w, c->h, c->size_d, 0, 0))
+            return fail(SMX_E_ARG, "%s: %s", row.setter, row.limit.shapes);
+        c->s.*slot = *p;
+    }
+    c->s.*on = p != nullptr;
+    return SMX_OK;
+}
+
+extern "C" {
 
 int smx_ctx_set_permeability(smx_ctx* c, const smx_perm_params* p) {
-    SMX_ARG(c);
-    if (p) {
-        if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_permeability: %s", PERM_RANGES);
-        c->perm_params = *p;
-    }
-    c->perm = p != nullptr;
-    return SMX_OK;
+    return ctx_set_stage(c, S_PERM, &CtxSettings::perm, &CtxSettings::perm_params, p, perm_params_ok, PERM_RANGES);
 }
-
 int smx_ctx_set_bp(smx_ctx* c, const smx_bp_params* p) {
+    return ctx_set_stage(c, S_BP, &CtxSettings::bp, &CtxSettings::bp_params, p, bp_params_ok, BP_RANGES);
+}
+int smx_ctx_set_cross(smx_ctx* c, const smx_cross_params* p) {
+    return ctx_set_stage(c, S_CROSS, &CtxSettings::cross, &CtxSettings::cross_params, p, cross_params_ok, CROSS_RANGES);
+}
+int smx_ctx_set_scanline(smx_ctx* c, const smx_scanline_params* p) {
+    return ctx_set_stage(c, S_SO, &CtxSettings::so, &CtxSettings::so_params, p, scanline_params_ok, SCANLINE_RANGES);
+}
+int smx_ctx_set_speckle(smx_ctx* c, const smx_speckle_params* p) {
+    return ctx_set_stage(c, S_SPECKLE, &CtxSettings::speckle, &CtxSettings::spk_params, p, speckle_params_ok, SPECKLE_RANGES);
+}
+int smx_ctx_set_adjust(smx_ctx* c, const smx_adjust_params* p) {
+    return ctx_set_stage(c, S_ADJUST, &CtxSettings::adjust, &CtxSettings::adj_params, p, adjust_params_ok, ADJUST_RANGES);
+}
+int smx_ctx_set_cross_scale(smx_ctx* c, const smx_cscale_params* p) {
+    return ctx_set_stage(c, S_CSCALE, &CtxSettings::cscale, &CtxSettings::cs_params, p, cscale_params_ok, CSCALE_RANGES);
+}
+int smx_ctx_set_patchmatch(smx_ctx* c, const smx_pm_params* p) {
+    return ctx_set_stage(c, S_PM, &CtxSettings::pm, &CtxSettings::pm_params, p, pm_params_ok, PM_RANGES);
+}
+
+int smx_ctx_set_vote(smx_ctx* c, const smx_vote_params* vote, const smx_cross_params* cross) {
     SMX_ARG(c);
-    if (p) {
-        if (!bp_params_ok(p))
-            return fail(SMX_E_ARG, "smx_ctx_set_bp: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a finite "
-                                   "data_scale > 0");
-        c->bp_params = *p;
+    if (vote) {
+        if (!vote_params_ok(vote)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_RANGES);
+        smx_cross_params cp;
+        smx_default_cross_params(&cp);
+        if (cross) { cp = *cross; cp.iterations = 1; }
+        if (!cross_params_ok(&cp)) return fail(SMX_E_ARG, "smx_ctx_set_vote: the arms: %s", CROSS_RANGES);
+        if (!stage_shape_ok(STAGES[S_VOTE], c->w, c->h, c->size_d, 0, 0)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_SHAPES);
+        c->s.vote_params = *vote;
+        c->s.vote_arms = cp;
     }
-    c->bp = p != nullptr;
-    return SMX_OK;
-}
-
-// Test hook (include/smx.h): what belief propagation holds on the device
-int smx_ctx_bp_held(const smx_ctx* c, size_t* bytes) {
-    SMX_ARG(c && bytes);
-    *bytes = c->bp_ws.p ? c->bp_ws.bytes : 0;
-    return SMX_OK;
-}
-
-// Test hook (include/smx.h): what the permeability filter holds on the device
-int smx_ctx_perm_held(const smx_ctx* c, size_t* bytes) {
-    SMX_ARG(c && bytes);
-    *bytes = c->perm_ws.p ? c->perm_ws.bytes : 0;
+    c->s.vote = vote != nullptr;
     return SMX_OK;
 }
 
@@ -760,29 +645,7 @@ int smx_ctx_set_guidance(smx_ctx* c, int mode) {
     SMX_ARG(c);
     if (mode != SMX_GUIDE_GRAY && mode != SMX_GUIDE_RGB)
         return fail(SMX_E_ARG, "smx_ctx_set_guidance: mode must be SMX_GUIDE_GRAY or SMX_GUIDE_RGB");
-    c->guide_mode = mode;
-    return SMX_OK;
-}
-
-int smx_ctx_set_cross(smx_ctx* c, const smx_cross_params* p) {
-    SMX_ARG(c);
-    if (p) {
-        if (!cross_params_ok(p))
-            return fail(SMX_E_ARG, "smx_ctx_set_cross: needs 1 <= l1 <= 63, 0 <= l2 <= l1, 1 <= tau2 <= tau1 <= 256 and "
-                                   "1 <= iterations <= 4");
-        c->cross_params = *p;
-    }
-    c->cross = p != nullptr;
-    return SMX_OK;
-}
-
-int smx_ctx_set_scanline(smx_ctx* c, const smx_scanline_params* p) {
-    SMX_ARG(c);
-    if (p) {
-        if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_scanline: %s", SCANLINE_RANGES);
-        c->so_params = *p;
-    }
-    c->so = p != nullptr;
+    c->s.guide_mode = mode;
     return SMX_OK;
 }
 
@@ -790,7 +653,14 @@ int smx_ctx_set_subpixel(smx_ctx* c, int mode) {
     SMX_ARG(c);
     if (mode != 0 && !subpix_mode_ok(mode))
         return fail(SMX_E_ARG, "smx_ctx_set_subpixel: mode must be 0, SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR");
-    c->subpix = mode;
+    c->s.subpix = mode;
+    return SMX_OK;
+}
+
+int smx_ctx_set_uniqueness(smx_ctx* c, float ratio) {
+    SMX_ARG(c);
+    if (!uniq_ratio_ok(ratio)) return fail(SMX_E_ARG, "smx_ctx_set_uniqueness: the ratio must be finite and >= 0 (0 = off)");
+    c->s.uniq = ratio;
     return SMX_OK;
 }
 
@@ -802,26 +672,23 @@ int smx_ctx_set_cost(smx_ctx* c, int mode, const smx_census_params* census) {
         smx_census_params p;
         smx_default_census_params(&p);
         if (census) p = *census;
-        if (!census_params_ok(&p))
-            return fail(SMX_E_ARG, "smx_ctx_set_cost: census needs 1 <= rx <= 4, 1 <= ry <= 3, th >= 1");
-        c->census = p;
+        if (!census_params_ok(&p)) return fail(SMX_E_ARG, "smx_ctx_set_cost: %s", CENSUS_RANGES);
+        c->s.census = p;
     }
-    c->cost_mode = mode;
-    c->adcensus = false;
+    c->s.cost_mode = mode;
+    c->s.adcensus = false;
     return SMX_OK;
 }
 
 int smx_ctx_set_adcensus(smx_ctx* c, const smx_adcensus_params* p) {
     SMX_ARG(c);
     if (p) {
-        if (!adcensus_params_ok(p))
-            return fail(SMX_E_ARG, "smx_ctx_set_adcensus: needs a valid census window, 0 < lambda <= 1e6, 2^-20 <= scale <= 2^20 "
-                                   "and colour 0 or 1");
-        c->adc = *p;
+        if (!adcensus_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_adcensus: %s", ADCENSUS_RANGES);
+        c->s.adc = *p;
         c->adc_tab_valid = false;
-        c->cost_mode = SMX_COST_REFERENCE;      // (it replaces whatever smx_ctx_set_cost chose)
+        c->s.cost_mode = SMX_COST_REFERENCE;      // (it replaces whatever smx_ctx_set_cost chose)
     }
-    c->adcensus = p != nullptr;
+    c->s.adcensus = p != nullptr;
     return SMX_OK;
 }
 
@@ -833,103 +700,55 @@ int smx_ctx_set_aggregation(smx_ctx* c, int mode, const smx_sgm_params* sgm) {
         smx_sgm_params p;
         smx_default_sgm_params(&p);
         if (sgm) p = *sgm;
-        if (!sgm_params_ok(&p))
-            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
-        if (!sgm_shape_ok(c->w, c->h, c->size_d))
-            return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM needs w*h < 2^31 and size_d <= %d", SMX_SGM_MAX_D);
-        c->sgm = p;
+        if (!sgm_params_ok(&p)) return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM %s", SGM_RANGES);
+        if (!stage_shape_ok(STAGES[S_SGM], c->w, c->h, c->size_d, 0, 0)) return fail(SMX_E_ARG, "smx_ctx_set_aggregation: SGM %s", SGM_SHAPES);
+        c->s.sgm = p;
     }
-    c->agg_mode = mode;
+    c->s.agg_mode = mode;
     return SMX_OK;
 }
 
-int smx_ctx_set_speckle(smx_ctx* c, const smx_speckle_params* p) {
-    SMX_ARG(c);
-    if (p) {
-        if (!speckle_params_ok(p))
-            return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs max_size >= 0 and a finite max_diff >= 0");
-        if (!speckle_shape_ok(c->w, c->h)) return fail(SMX_E_ARG, "smx_ctx_set_speckle: needs w*h < 2^31");
-        c->spk_params = *p;
-    }
-    c->speckle = p != nullptr;
-    return SMX_OK;
-}
-
+// ---- the maps of the last synchronous pair (c->done says which stages it ran) --------------------------------------------------
 int smx_ctx_speckle_map(smx_ctx* c, float* despeckled) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_speckle_map")) return rc;
-    if (!c->spk_valid) return fail(SMX_E_ARG, "smx_ctx_speckle_map: the last smx_ctx_stereo_pair ran without speckle removal");
+    if (!c->done.speckle) return fail(SMX_E_ARG, "smx_ctx_speckle_map: the last smx_ctx_stereo_pair ran without speckle removal");
     if (despeckled) SMX_HIP(c->spk.download(despeckled, c->n * sizeof(float)));
     return SMX_OK;
 }
 
-int smx_ctx_set_vote(smx_ctx* c, const smx_vote_params* vote, const smx_cross_params* cross) {
+int smx_ctx_vote_map(smx_ctx* c, float* voted) {
     SMX_ARG(c);
-    if (vote) {
-        if (!vote_params_ok(vote)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_RANGES);
-        smx_cross_params cp;
-        smx_default_cross_params(&cp);
-        if (cross) { cp = *cross; cp.iterations = 1; }
-        if (!cross_params_ok(&cp)) return fail(SMX_E_ARG, "smx_ctx_set_vote: the arms: %s", CROSS_RANGES);
-        if (!vote_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "smx_ctx_set_vote: %s", VOTE_SHAPES);
-        c->vote_params = *vote;
-        c->vote_arms = cp;
-    }
-    c->vote = vote != nullptr;
+    if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
+    if (!c->done.vote) return fail(SMX_E_ARG, "smx_ctx_vote_map: the last smx_ctx_stereo_pair ran without region voting");
+    if (voted) SMX_HIP(c->voted.download(voted, c->n * sizeof(float)));
     return SMX_OK;
 }
 
-int smx_ctx_set_adjust(smx_ctx* c, const smx_adjust_params* p) {
+int smx_ctx_uniqueness_map(smx_ctx* c, float* map, float* margin) {
     SMX_ARG(c);
-    if (p) {
-        if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_adjust: %s", ADJUST_RANGES);
-        if (!adjust_shape_ok(c->w, c->h, c->size_d)) return fail(SMX_E_ARG, "smx_ctx_set_adjust: %s", ADJUST_SHAPES);
-        c->adj_params = *p;
-    }
-    c->adjust = p != nullptr;
+    if (int rc = ctx_check_device(c, "smx_ctx_uniqueness_map")) return rc;
+    if (!c->done.uniq) return fail(SMX_E_ARG, "smx_ctx_uniqueness_map: the last smx_ctx_stereo_pair ran without the uniqueness test");
+    if (map) SMX_HIP(c->uq_map.download(map, c->n * sizeof(float)));
+    if (margin) SMX_HIP(c->uq_margin.download(margin, c->n * sizeof(float)));
     return SMX_OK;
 }
 
-int smx_ctx_set_cross_scale(smx_ctx* c, const smx_cscale_params* p) {
+int smx_ctx_subpixel_maps(smx_ctx* c, float* sub_l, float* sub_r, float* sub_filled) {
     SMX_ARG(c);
-    if (p) {
-        if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_cross_scale: %s", CSCALE_RANGES);
-        c->cs_params = *p;
-    }
-    c->cscale = p != nullptr;
-    return SMX_OK;
-}
-
-// Test hook (include/smx.h): what cross-scale holds on the device
-int smx_ctx_cscale_held(const smx_ctx* c, int* levels, size_t* bytes) {
-    SMX_ARG(c && levels && bytes);
-    *levels = 0;
-    *bytes = 0;
-    for (const smx_ctx* k : c->cs_child) {
-        if (!k) continue;
-        ++*levels;
-        for (const DevBuf* b : {&k->dL, &k->dR, &k->keys, &k->best, &k->map, &k->mean, &k->occ, &k->fil, &k->ws, &k->aggLR, &k->codes,
-                                &k->adc_tab, &k->rgb, &k->mode_ws, &k->chunk_cost})
-            *bytes += b->p ? b->bytes : 0;
-    }
-    return SMX_OK;
-}
-
-int smx_ctx_set_patchmatch(smx_ctx* c, const smx_pm_params* p) {
-    SMX_ARG(c);
-    if (p) {
-        if (!pm_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_patchmatch: %s", PM_RANGES);
-        if (!pm_shape_ok(c->w, c->h, c->size_d, 0, 0)) return fail(SMX_E_ARG, "smx_ctx_set_patchmatch: %s", PM_SHAPES);
-        c->pm_params = *p;
-    }
-    c->pm = p != nullptr;
+    if (int rc = ctx_check_device(c, "smx_ctx_subpixel_maps")) return rc;
+    if (!c->done.subpix) return fail(SMX_E_ARG, "smx_ctx_subpixel_maps: the last smx_ctx_stereo_pair ran without sub-pixel");
+    const size_t n = c->n, fb = n * sizeof(float);
+    if (sub_l) SMX_HIP(c->sub.download(sub_l, fb));
+    if (sub_r) SMX_HIP(hipMemcpy(sub_r, c->sub.as<float>() + n, fb, hipMemcpyDeviceToHost));
+    if (sub_filled) SMX_HIP(c->subf.download(sub_filled, fb));
     return SMX_OK;
 }
 
 int smx_ctx_patchmatch_maps(smx_ctx* c, float* planes_l, float* planes_r, float* sub_l, float* sub_r, float* sub_filled) {
     SMX_ARG(c);
     if (int rc = ctx_check_device(c, "smx_ctx_patchmatch_maps")) return rc;
-    if (!c->pm_valid) return fail(SMX_E_ARG, "smx_ctx_patchmatch_maps: the last smx_ctx_stereo_pair ran without PatchMatch stereo");
+    if (!c->done.pm) return fail(SMX_E_ARG, "smx_ctx_patchmatch_maps: the last smx_ctx_stereo_pair ran without PatchMatch stereo");
     const size_t n = c->n, fb = n * sizeof(float);
     const float* pl = c->pm_planes.as<float>();
     const float* disp = c->pm_disp.as<float>();
@@ -941,7 +760,19 @@ int smx_ctx_patchmatch_maps(smx_ctx* c, float* planes_l, float* planes_r, float*
     return SMX_OK;
 }
 
-// Test hook (include/smx.h): what PatchMatch stereo holds on the device
+// ---- test hooks (include/smx.h): what a stage holds on the device --------------------------------------------------------------
+int smx_ctx_bp_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = c->bp_ws.p ? c->bp_ws.bytes : 0;
+    return SMX_OK;
+}
+
+int smx_ctx_perm_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = c->perm_ws.p ? c->perm_ws.bytes : 0;
+    return SMX_OK;
+}
+
 int smx_ctx_pm_held(const smx_ctx* c, size_t* bytes) {
     SMX_ARG(c && bytes);
     *bytes = 0;
@@ -949,38 +780,17 @@ int smx_ctx_pm_held(const smx_ctx* c, size_t* bytes) {
     return SMX_OK;
 }
 
-int smx_ctx_vote_map(smx_ctx* c, float* voted) {
-    SMX_ARG(c);
-    if (int rc = ctx_check_device(c, "smx_ctx_vote_map")) return rc;
-    if (!c->vote_valid) return fail(SMX_E_ARG, "smx_ctx_vote_map: the last smx_ctx_stereo_pair ran without region voting");
-    if (voted) SMX_HIP(c->voted.download(voted, c->n * sizeof(float)));
-    return SMX_OK;
-}
-
-int smx_ctx_set_uniqueness(smx_ctx* c, float ratio) {
-    SMX_ARG(c);
-    if (!uniq_ratio_ok(ratio)) return fail(SMX_E_ARG, "smx_ctx_set_uniqueness: the ratio must be finite and >= 0 (0 = off)");
-    c->uniq = ratio;
-    return SMX_OK;
-}
-
-int smx_ctx_uniqueness_map(smx_ctx* c, float* map, float* margin) {
-    SMX_ARG(c);
-    if (int rc = ctx_check_device(c, "smx_ctx_uniqueness_map")) return rc;
-    if (!c->uq_valid) return fail(SMX_E_ARG, "smx_ctx_uniqueness_map: the last smx_ctx_stereo_pair ran without the uniqueness test");
-    if (map) SMX_HIP(c->uq_map.download(map, c->n * sizeof(float)));
-    if (margin) SMX_HIP(c->uq_margin.download(margin, c->n * sizeof(float)));
-    return SMX_OK;
-}
-
-int smx_ctx_subpixel_maps(smx_ctx* c, float* sub_l, float* sub_r, float* sub_filled) {
-    SMX_ARG(c);
-    if (int rc = ctx_check_device(c, "smx_ctx_subpixel_maps")) return rc;
-    if (!c->sub_valid) return fail(SMX_E_ARG, "smx_ctx_subpixel_maps: the last smx_ctx_stereo_pair ran without sub-pixel");
-    const size_t n = c->n, fb = n * sizeof(float);
-    if (sub_l) SMX_HIP(c->sub.download(sub_l, fb));
-    if (sub_r) SMX_HIP(hipMemcpy(sub_r, c->sub.as<float>() + n, fb, hipMemcpyDeviceToHost));
-    if (sub_filled) SMX_HIP(c->subf.download(sub_filled, fb));
+int smx_ctx_cscale_held(const smx_ctx* c, int* levels, size_t* bytes) {
+    SMX_ARG(c && levels && bytes);
+    *levels = 0;
+    *bytes = 0;
+    for (const smx_ctx* k : c->cs_child) {
+        if (!k) continue;
+        ++*levels;
+        for (const DevBuf* b : {&k->dL, &k->dR, &k->keys, &k->best, &k->map, &k->mean, &k->occ, &k->fil, &k->ws, &k->aggLR, &k->codes,
+                                &k->adc_tab, &k->rgb, &k->mode_ws, &k->chunk_cost})
+            *bytes += b->p ? b->bytes : 0;
+    }
     return SMX_OK;
 }
 
@@ -1006,35 +816,12 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     SMX_ARG(c && gray_l && gray_r);
     int rc;
     if ((rc = ctx_check_device(c, "smx_ctx_stereo_pair_async"))) return rc;
-    if (c->subpix) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: sub-pixel is on (smx_ctx_set_subpixel): use smx_ctx_stereo_pair");
-    if (c->speckle) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: speckle removal is on (smx_ctx_set_speckle): use smx_ctx_stereo_pair");
-    if (c->vote) return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: region voting is on (smx_ctx_set_vote): use smx_ctx_stereo_pair");
-    if (c->adjust)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the depth-discontinuity adjustment is on (smx_ctx_set_adjust): use smx_ctx_stereo_pair");
-    if (c->cscale)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-scale aggregation is on (smx_ctx_set_cross_scale): use smx_ctx_stereo_pair");
-    if (c->perm)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the permeability filter is on (smx_ctx_set_permeability): use smx_ctx_stereo_pair");
-    if (c->bp)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: belief propagation is on (smx_ctx_set_bp): use smx_ctx_stereo_pair");
-    if (c->pm)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: PatchMatch stereo is on (smx_ctx_set_patchmatch): use smx_ctx_stereo_pair");
-    if (c->uniq > 0.0f)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the uniqueness test is on (smx_ctx_set_uniqueness): use smx_ctx_stereo_pair");
-    if (c->agg_mode != SMX_AGG_GUIDED)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: semi-global matching is on (smx_ctx_set_aggregation): use smx_ctx_stereo_pair");
-    if (c->guide_mode != SMX_GUIDE_GRAY)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: colour guidance is on (smx_ctx_set_guidance): use smx_ctx_stereo_pair_rgb");
-    if (c->cross)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: cross-based aggregation is on (smx_ctx_set_cross): use smx_ctx_stereo_pair");
-    if (c->so)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the scan-line optimiser is on (smx_ctx_set_scanline): use smx_ctx_stereo_pair");
-    if (c->cost_mode != SMX_COST_REFERENCE)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the census cost is on (smx_ctx_set_cost): use smx_ctx_stereo_pair");
-    if (c->adcensus)
-        return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: the AD-Census cost is on (smx_ctx_set_adcensus): use smx_ctx_stereo_pair");
     if (c->submitted - c->waited >= 2)
         return fail(SMX_E_ARG, "smx_ctx_stereo_pair_async: two pairs are in flight already (smx_ctx_wait takes the older one)");
+    PairPlan need;
+    char why[512];
+    if (plan_pair(c->s, c->w, c->h, c->size_d, ENTRY_ASYNC, 0, dminl, dminr, false, false, false, &need, why, sizeof(why)))
+        return fail(SMX_E_ARG, "%s", why);
     if ((rc = ctx_async_setup(c))) return rc;
     // no stage marks in the pipelined entry: pairs overlap on three streams, so "the stages of the last call" has no meaning
     // here, and an event record per stage is a bubble on the queue the pipeline exists to keep full
@@ -1049,8 +836,8 @@ int smx_ctx_stereo_pair_async(smx_ctx* c, const uint8_t* gray_l, const uint8_t* 
     SMX_HIP(hipEventRecord(sl.up, c->st_up));
     SMX_HIP(hipStreamWaitEvent(c->st, sl.up, 0));
     float* r = sl.res.as<float>();                       // best_l best_r dmap_l dmap_r occlusion filled
-    // (every opt-in stage was refused above: the pair needs nothing beyond the eight planes)
-    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr}, PairNeeds{}, {r, r + 2 * n, sl.mean.as<uint8_t>(), r + 4 * n, r + 5 * n})))
+    // (the plan of this entry has every opt-in stage off: the pair needs nothing beyond the eight planes)
+    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr}, need, {r, r + 2 * n, sl.mean.as<uint8_t>(), r + 4 * n, r + 5 * n})))
         return rc;
     // status word of this pair's aggregation (the next pair's launch clears it): behind the planes in the staging
     char* status_h = sl.h_out + 6 * fb + 2 * n;

@@ -156,7 +156,7 @@ int smx_weighted_median(const smx_wmf_params* p, const uint8_t* guide, const flo
 }
 
 int smx_speckle_filter(const smx_speckle_params* p, const float* disp, float* out, int w, int h, float vmin, float new_val) {
-    SMX_ARG(speckle_params_ok(p) && disp && out && speckle_shape_ok(w, h));
+    SMX_ARG(speckle_params_ok(p) && disp && out && shape_ok(w, h, 1, 1));
     const size_t bytes = (size_t)w * h * sizeof(float), wsb = speckle_workspace_bytes(w, h);
     DevBuf dD, dW;
     SMX_HIP(dD.upload(disp, bytes));
@@ -238,9 +238,8 @@ int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uin
 
 int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
                       int size_d, int dmin) {
-    if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: needs 0 <= p1 <= p2 <= 4095 and paths 4 or 8");
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_sgm_aggregate: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: %s", SGM_RANGES);
+    if (!shape_ok(w, h, size_d, SMX_SGM_MAX_D)) return fail(SMX_E_ARG, "smx_sgm_aggregate: %s", SGM_SHAPES);
     SMX_ARG(cost != nullptr);
     const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = sgm_workspace_bytes(w, h, size_d, 1);
     DevBuf dC, dA, dK, dW;
@@ -268,11 +267,8 @@ int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, fl
 
 int smx_bp_aggregate(const smx_bp_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d,
                      int dmin) {
-    if (!bp_params_ok(p))
-        return fail(SMX_E_ARG, "smx_bp_aggregate: needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
-                               "finite data_scale > 0");
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_bp_aggregate: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_BP_MAX_D);
+    if (!bp_params_ok(p)) return fail(SMX_E_ARG, "smx_bp_aggregate: %s", BP_RANGES);
+    if (!shape_ok(w, h, size_d, SMX_BP_MAX_D)) return fail(SMX_E_ARG, "smx_bp_aggregate: %s", BP_SHAPES);
     SMX_ARG(cost != nullptr);
     const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = bp_workspace_bytes(w, h, size_d, p->levels, 1);
     DevBuf dC, dA, dK, dW;
@@ -302,8 +298,7 @@ int smx_scanline_optimize(const smx_scanline_params* p, const uint8_t* guide_own
                           const float* cost, float* agg, float* best, float* disp_map, int w, int h, int size_d, int dmin) {
     if (!scanline_params_ok(p)) return fail(SMX_E_ARG, "smx_scanline_optimize: %s", SCANLINE_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!sgm_shape_ok(w, h, size_d))
-        return fail(SMX_E_ARG, "smx_scanline_optimize: needs w, h >= 1, w*h < 2^31 and 1 <= size_d <= %d", SMX_SGM_MAX_D);
+    if (!shape_ok(w, h, size_d, SMX_SGM_MAX_D)) return fail(SMX_E_ARG, "smx_scanline_optimize: %s", SGM_SHAPES);
     SMX_ARG(guide_own && guide_other && cost);
     const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), wsb = scanline_workspace_bytes(w, h, size_d, 1);
     DevBuf dG, dH, dC, dA, dK, dW;
@@ -352,7 +347,7 @@ int smx_cross_aggregate(const smx_cross_params* p, const uint8_t* guide, int cha
     if (!cross_params_ok(p)) return fail(SMX_E_ARG, "smx_cross_aggregate: %s", CROSS_RANGES);
     SMX_ARG(guide && cost && filter_cost && disp_map && size_d >= 1);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cross_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_cross_aggregate: needs w, h >= 1 and w*h < 2^31");
+    if (!shape_ok(w, h, 1, 1)) return fail(SMX_E_ARG, "smx_cross_aggregate: %s", PLANE_SHAPES);
     const size_t ws_bytes = capped_ws_bytes([=](int k) { return cross_workspace_bytes(w, h, k, 1); }, size_d);
     return guide_aggregate_host(guide, channels, cost, filter_cost, disp_map, agg, w, h, size_d, dmin, ws_bytes,
                                 [=](const uint8_t* d_guide, const float* d_cost, int64_t* d_keys, float* d_agg, void* d_ws) {
@@ -369,7 +364,7 @@ int smx_region_vote(const smx_vote_params* p, const smx_cross_params* cross, con
     if (cross) { cp = *cross; cp.iterations = 1; }
     if (!cross_params_ok(&cp)) return fail(SMX_E_ARG, "smx_region_vote: the arms: %s", CROSS_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!vote_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_region_vote: %s", VOTE_SHAPES);
+    if (!shape_ok(w, h, size_d, VOTE_MAX_D)) return fail(SMX_E_ARG, "smx_region_vote: %s", VOTE_SHAPES);
     SMX_ARG(guide && disp && out);
     const size_t n = (size_t)w * h, fb = n * sizeof(float), wsb = vote_workspace_bytes(w, h);
     DevBuf dG, dA, dD, dR, dW;
@@ -391,7 +386,7 @@ int smx_region_vote(const smx_vote_params* p, const smx_cross_params* cross, con
 int smx_discontinuity_adjust(const smx_adjust_params* p, const float* disp, const float* agg, float* out, int w, int h, int dmin,
                              int size_d, int subpix_mode, float* sub) {
     if (!adjust_params_ok(p)) return fail(SMX_E_ARG, "smx_discontinuity_adjust: %s", ADJUST_RANGES);
-    if (!adjust_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_discontinuity_adjust: %s", ADJUST_SHAPES);
+    if (!shape_ok(w, h, size_d, ADJ_MAX_D)) return fail(SMX_E_ARG, "smx_discontinuity_adjust: %s", ADJUST_SHAPES);
     SMX_ARG(disp && agg && out);
     if (sub ? !subpix_mode_ok(subpix_mode) : subpix_mode != 0 && !subpix_mode_ok(subpix_mode))
         return fail(SMX_E_ARG, "smx_discontinuity_adjust: subpix_mode must be SMX_SUBPIX_PARABOLA or SMX_SUBPIX_EQUIANGULAR (or 0 "
@@ -413,7 +408,7 @@ int smx_discontinuity_adjust(const smx_adjust_params* p, const float* disp, cons
 
 int smx_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int channels) {
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!cscale_shape_ok(w, h, 1)) return fail(SMX_E_ARG, "smx_pyr_down: needs w, h >= 1 and w*h < 2^31");
+    if (!shape_ok(w, h, 1, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_pyr_down: %s", PLANE_SHAPES);
     SMX_ARG(src && dst);
     const size_t in = (size_t)w * h * channels, out = (size_t)((w + 1) / 2) * ((h + 1) / 2) * channels;
     DevBuf dS, dD;
@@ -428,7 +423,7 @@ int smx_pyr_down(const uint8_t* src, uint8_t* dst, int w, int h, int channels) {
 int smx_cscale_combine(const smx_cscale_params* p, const float* const* agg, int w, int h, int dmin, int size_d, float* out,
                        float* best, float* disp_map) {
     if (!cscale_params_ok(p)) return fail(SMX_E_ARG, "smx_cscale_combine: %s", CSCALE_RANGES);
-    if (!cscale_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_cscale_combine: %s", CSCALE_SHAPES);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_cscale_combine: %s", CSCALE_SHAPES);
     SMX_ARG(agg != nullptr);
     for (int s = 0; s < p->scales; ++s) SMX_ARG(agg[s] != nullptr);
     const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float);
@@ -507,7 +502,7 @@ int smx_permeability_filter(const smx_perm_params* p, const float* volume, const
                             int size_d, float* out, float* best, float* disp_map) {
     if (!perm_params_ok(p)) return fail(SMX_E_ARG, "smx_permeability_filter: %s", PERM_RANGES);
     SMX_ARG(channels == 1 || channels == 3 || channels == 4);
-    if (!perm_shape_ok(w, h, size_d)) return fail(SMX_E_ARG, "smx_permeability_filter: %s", PERM_SHAPES);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_permeability_filter: %s", PERM_SHAPES);
     SMX_ARG(volume && guide);
     const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float);
     // (the filtered volume goes over the uploaded one; the workspace: every slice at once up to ~1 GiB, one slice at least)

@@ -350,12 +350,6 @@ bool pm_params_ok(const smx_pm_params* p) {
            p->iterations >= 1 && p->iterations <= PM_MAX_ITER && p->max_slope >= 0.0 && p->max_slope <= 8.0;
 }
 
-bool pm_shape_ok(int w, int h, int size_d, int dminl, int dminr) {
-    const int lim = 1 << 20;
-    return w >= 1 && h >= 1 && w < (1 << 24) && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= lim && dminl >= -lim &&
-           dminl <= lim && dminr >= -lim && dminr <= lim;
-}
-
 void pm_weights(const smx_pm_params* p, float* tab) {
     for (int k = 0; k < 256; ++k) tab[k] = (float)exp(-(double)k / p->gamma);
 }

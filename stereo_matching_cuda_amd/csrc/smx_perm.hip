@@ -236,10 +236,6 @@ inline size_t plane_bytes(int w, int h) { return (size_t)w * h * sizeof(float); 
 
 }  // namespace
 
-bool perm_shape_ok(int w, int h, int size_d) {
-    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= (1 << 20);
-}
-
 // Per view: the two weight planes, and per slice in flight a scratch plane (LR, then TB) and a plane of the filtered slice for
 // the calls that keep no volume.  Sized for those: a call with d_out gets by with less.
 size_t perm_workspace_bytes(int w, int h, int nslices, int nviews) {

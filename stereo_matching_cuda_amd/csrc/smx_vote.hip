@@ -30,8 +30,7 @@ namespace {
 
 constexpr int VOTE_TW = 64;             // tile columns = lanes of a wave
 constexpr int VOTE_TH = 4;              // tile rows = waves of a workgroup
-constexpr int VOTE_MAX_D = 512;
-constexpr int VOTE_DIRS = 16;
+constexpr int VOTE_DIRS = 16;          // (VOTE_MAX_D, the labels of a histogram in LDS: smx_ctx_plan.h, beside shape_ok)
 
 // (int)v of a finite v, saturating like the hardware's conversion
 __device__ inline int vote_trunc(float v) {
@@ -214,10 +213,6 @@ __global__ __launch_bounds__(256) void k_vote_interp(const float* __restrict__ i
 bool vote_params_ok(const smx_vote_params* p) {
     return p && p->tau_s >= 0 && p->tau_h_pct >= 0 && p->tau_h_pct <= 99 && p->iterations >= 0 && p->iterations <= 8 &&
            (p->interpolate == 0 || p->interpolate == 1);
-}
-
-bool vote_shape_ok(int w, int h, int size_d) {
-    return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && size_d >= 1 && size_d <= VOTE_MAX_D;
 }
 
 size_t vote_workspace_bytes(int w, int h) { return 255 + 2 * sizeof(float) * (size_t)w * h; }
