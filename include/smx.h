@@ -781,6 +781,85 @@ int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uin
 int smx_ctx_set_adcensus(smx_ctx* ctx, const smx_adcensus_params* p);
 
 /* ------------------------------------------------------------------------------------
+ * Mutual-information matching cost (Hirschmueller's HMI; not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The reference's cost and the AD term need equal gray values in the two views, census needs equal local ORDER.  Mutual
+ * information (Hirschmueller, PAMI 2008) needs only that SOME fixed relation holds between the gray values of corresponding
+ * pixels -- an inverted image, a folded tone curve, another modality -- and learns it from the pair itself: a joint histogram of
+ * the pixels a disparity map pairs up gives a 256 x 256 table, and the cost of a cell is one lookup in it.
+ * tests/mi_ref.py is this definition in numpy; histogram, table and volume equal it bit for bit.
+ *   histogram  H, u32 [256][256], of a left map (f32 [h][w] holding integers that fit an int) with an occlusion mark:
+ *         pixel (y, x) counts iff map[y][x] != mark and 0 <= xx < w with xx = x + (int)map[y][x]; it adds 1 to
+ *         H[L[y][x]][R[y][xx]].  Integer sums: the same bits whatever the order of the atomics.
+ *   table  T, u8 [256][256], from H on the host in double, every operation rounded on its own (no contraction), with
+ *         g = {1, 6, 15, 20, 15, 6, 1} / 64 and conv(v)[j] = sum over t = 0 .. 6, ascending from 0.0, of g[t] * v[j + t - 3],
+ *         v taken as 0.0 outside 0 .. 255; conv2(M) = conv along k of every row (the second index) first, then conv along i:
+ *           n = sum of H (u64);  n == 0: T = 0 everywhere.        P[i][k] = (double)H[i][k] / (double)n
+ *           h12 = conv2(-log(max(conv2(P), 1e-12)))
+ *           p1[i] = sum over k ascending of P[i][k], p2[k] = sum over i ascending of P[i][k]
+ *           h1 = conv(-log(max(conv(p1), 1e-12))), h2 the same from p2
+ *           c[i][k] = (h12[i][k] - h1[i]) - h2[k];  c -= min c;  m = max c;  m == 0: T = 0 everywhere, else
+ *           T[i][k] = (uint8_t)rint((c[i][k] * 255.0) / m)                   (ties to even)
+ *         log is the C library's.  Hirschmueller's factor 1/n is absorbed by the normalisation to 0 .. 255: integers in the
+ *         value set of the comb walker's exactness argument (no fall-back) and of SGM's clamp.
+ *   cost  of view v, slice z: d = dmin_v + z, xx = x + d.  If 0 <= xx < w: the left view has
+ *         cost[z][y][x] = (float)T[L[y][x]][R[y][xx]], the right view cost[z][y][x] = (float)T[L[y][xx]][R[y][x]]; else
+ *         255.0f.  Layout, slice placement and [s_begin, s_end) as for smx_dev_census_cost_pair. */
+#define SMX_MI_INIT_RANDOM 0
+#define SMX_MI_INIT_REFERENCE 1
+#define SMX_MI_LEVELS 256
+typedef struct smx_mi_params {
+    int iterations;   /* tables computed per pair, default 3; 1 .. 16 */
+    int init;         /* SMX_MI_INIT_RANDOM (default) | SMX_MI_INIT_REFERENCE */
+    uint32_t seed;    /* for the random start, default 0 */
+} smx_mi_params;
+void smx_default_mi_params(smx_mi_params* p);
+/* The table of a histogram (both SMX_MI_LEVELS^2 entries).  Host only: works without a GPU. */
+int smx_mi_table(const uint32_t* hist, uint8_t* table);
+/* The same into device memory (d_table: SMX_MI_LEVELS^2 bytes, 16-byte aligned): a set-up call that copies from host memory
+ * and waits for the copy on `stream`.  NOT graph-capturable. */
+int smx_dev_mi_table(const uint32_t* hist, uint8_t* d_table, void* stream);
+/* The histogram of d_map (with its occlusion mark) over the gray pair into d_hist, which the call zeroes first: a memset and
+ * one launch on `stream`, no allocation, no synchronisation (graph-capturable).  w, h >= 1, w*h < 2^31. */
+int smx_dev_mi_histogram(const uint8_t* d_img_l, const uint8_t* d_img_r, const float* d_map, float occlusion_mark,
+                         uint32_t* d_hist, int w, int h, void* stream);
+/* The random start map of a pair: d_map[y][x] = (float)(dmin + hash(seed, y*w + x) % size_d), the hash being the counter-based
+ * one of PatchMatch stereo with view 0 and draw 0 (smx_pm_hash).  One launch, graph-capturable. */
+int smx_dev_mi_random_map(float* d_map, int w, int h, int dmin, int size_d, uint32_t seed, void* stream);
+/* Slices [s_begin, s_end) of the left volume (labels dminl + z) into d_cost_l and of the right volume (labels dminr + z) into
+ * d_cost_r from d_table (as smx_dev_mi_table left it), both in one launch; either cost pointer may be NULL (not both).  One
+ * launch, no allocation, no synchronisation (graph-capturable).  w, h >= 1. */
+int smx_dev_mi_cost_pair(const uint8_t* d_table, const uint8_t* d_img_l, const uint8_t* d_img_r, float* d_cost_l,
+                         float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end, void* stream);
+/* Host pointers, synchronous.  smx_mi_histogram: the histogram of a left map.  smx_mi_cost mirrors smx_census_cost: the
+ * volume of view `right` (0: i1 is the left image and i2 the right one; 1: i1 is the right image, i2 the left one, and the
+ * table is read with the roles swapped), size_d*w*h floats, labels dmin + z. */
+int smx_mi_histogram(const uint8_t* img_l, const uint8_t* img_r, const float* map, float occlusion_mark, uint32_t* hist,
+                     int w, int h);
+int smx_mi_cost(const uint8_t* table, const uint8_t* i1, const uint8_t* i2, int right, float* cost, int w, int h, int size_d,
+                int dmin);
+
+#define SMX_COST_MI 2   /* what smx_ctx_set_mi selects; smx_ctx_set_cost does not take it */
+/* The mutual-information cost of this context.  Non-NULL switches it on and replaces whatever smx_ctx_set_cost or
+ * smx_ctx_set_adcensus chose; NULL switches it off again (the reference's cost), and so does a later smx_ctx_set_cost or
+ * smx_ctx_set_adcensus.  Valid: 1 <= iterations <= 16, init one of the two above.  A pair with it on runs, in order:
+ *   1. the start map: SMX_MI_INIT_RANDOM is smx_dev_mi_random_map(dminl, size_d, seed), every pixel valid;
+ *      SMX_MI_INIT_REFERENCE is the LR-checked left map (`occlusion`) of one pass of the pair with the reference's cost;
+ *   2. for k = 1 .. iterations: the histogram of the current map (occlusion mark dminl - 100), its table on the host (one
+ *      round trip), then the pair in the flows of the census cost (cost chunk -> aggregation) with the MI cost of that table.
+ *      The current map of the next iteration is this pass's LR-checked left map (`occlusion`).
+ * The start pass and the passes before the last stop behind the LR check and the fill: uniqueness, speckle removal, region
+ * voting, sub-pixel and the adjustment run in the last pass only, so their invalidations never reach a histogram.  Every
+ * output, cost_l / cost_r included, is the last pass's.  With cross-scale aggregation the levels take the table of level 0.
+ * It runs in every flow the census cost runs in (not with PatchMatch stereo); smx_ctx_stereo_pair_async returns SMX_E_ARG
+ * while it is on.  The table and the buffers are allocated on first use. */
+int smx_ctx_set_mi(smx_ctx* ctx, const smx_mi_params* p);
+/* The table of the last pass of the last synchronous pair and the histogram it came from (either may be NULL); SMX_E_ARG if
+ * that pair ran without the mutual-information cost. */
+int smx_ctx_mi_table(smx_ctx* ctx, uint8_t* table, uint32_t* hist);
+
+/* ------------------------------------------------------------------------------------
  * Cross-based aggregation: colour-adaptive support regions (not a stage of the reference; opt-in)
  * ---------------------------------------------------------------------------------- */
 

@@ -52,6 +52,15 @@ class AdCensusParams(C.Structure):
 ADCENSUS_TABLE_FLOATS = 64 + 766      # smx.h SMX_ADCENSUS_TABLE_FLOATS
 
 
+class MiParams(C.Structure):
+    """smx_mi_params: the mutual-information matching cost (not a stage of the reference)."""
+    _fields_ = [("iterations", C.c_int), ("init", C.c_int), ("seed", C.c_uint32)]
+
+
+MI_LEVELS = 256                       # smx.h SMX_MI_LEVELS
+MI_INITS = {"random": 0, "reference": 1}
+
+
 class SpeckleParams(C.Structure):
     """smx_speckle_params: the connected-component speckle filter (not a stage of the reference)."""
     _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
@@ -128,6 +137,7 @@ _PP = C.POINTER(Params)
 _WP = C.POINTER(WmfParams)
 _CP = C.POINTER(CensusParams)
 _AP = C.POINTER(AdCensusParams)
+_IP = C.POINTER(MiParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
 _BP = C.POINTER(BpParams)
@@ -211,6 +221,16 @@ SIGNATURES = {
     "smx_dev_adcensus_cost_pair": (_i, [_AP, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "smx_adcensus_cost": (_i, [_AP, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_adcensus": (_i, [_vp, _AP]),
+    "smx_default_mi_params": (None, [_IP]),
+    "smx_mi_table": (_i, [_vp, _vp]),
+    "smx_dev_mi_table": (_i, [_vp, _vp, _vp]),
+    "smx_dev_mi_histogram": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
+    "smx_dev_mi_random_map": (_i, [_vp, _i, _i, _i, _i, _u32, _vp]),
+    "smx_dev_mi_cost_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "smx_mi_histogram": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i]),
+    "smx_mi_cost": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_mi": (_i, [_vp, _IP]),
+    "smx_ctx_mi_table": (_i, [_vp, _vp, _vp]),
     "smx_default_speckle_params": (None, [_SP]),
     "smx_speckle_workspace_bytes": (_sz, [_i, _i]),
     "smx_dev_speckle_filter": (_i, [_SP, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
@@ -372,6 +392,12 @@ def default_wmf_params():
 def default_census_params():
     p = CensusParams()
     lib().smx_default_census_params(C.byref(p))
+    return p
+
+
+def default_mi_params():
+    p = MiParams()
+    lib().smx_default_mi_params(C.byref(p))
     return p
 
 

@@ -649,6 +649,48 @@ int smx_dev_adcensus_cost_pair(const smx_adcensus_params* p, const float* d_tabl
                                      d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end, (hipStream_t)stream);
 }
 
+// ---- mutual-information matching cost (not in the reference; smx_mi.hip) --------------------------------
+void smx_default_mi_params(smx_mi_params* p) {
+    if (!p) return;
+    p->iterations = 3; p->init = SMX_MI_INIT_RANDOM; p->seed = 0;
+}
+
+int smx_mi_table(const uint32_t* hist, uint8_t* table) {
+    SMX_ARG(hist && table);
+    mi_table(hist, table);
+    return SMX_OK;
+}
+
+int smx_dev_mi_table(const uint32_t* hist, uint8_t* d_table, void* stream) {
+    SMX_ARG(hist && d_table && ((uintptr_t)d_table & 15) == 0);
+    std::vector<uint8_t> t((size_t)SMX_MI_LEVELS * SMX_MI_LEVELS);
+    mi_table(hist, t.data());
+    SMX_HIP(hipMemcpyAsync(d_table, t.data(), t.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+    SMX_HIP(hipStreamSynchronize((hipStream_t)stream));     // (t lives in this call)
+    return SMX_OK;
+}
+
+int smx_dev_mi_histogram(const uint8_t* d_img_l, const uint8_t* d_img_r, const float* d_map, float occlusion_mark,
+                         uint32_t* d_hist, int w, int h, void* stream) {
+    SMX_ARG(d_img_l && d_img_r && d_map && d_hist);
+    if (!shape_ok(w, h, 1, 1)) return fail(SMX_E_ARG, "smx_dev_mi_histogram: %s", PLANE_SHAPES);
+    return launch_mi_histogram(d_img_l, d_img_r, d_map, occlusion_mark, d_hist, w, h, (hipStream_t)stream);
+}
+
+int smx_dev_mi_random_map(float* d_map, int w, int h, int dmin, int size_d, uint32_t seed, void* stream) {
+    SMX_ARG(d_map != nullptr);
+    if (!shape_ok(w, h, size_d, INT_MAX)) return fail(SMX_E_ARG, "smx_dev_mi_random_map: %s and size_d >= 1", PLANE_SHAPES);
+    return launch_mi_random_map(d_map, w, h, dmin, size_d, seed, (hipStream_t)stream);
+}
+
+int smx_dev_mi_cost_pair(const uint8_t* d_table, const uint8_t* d_img_l, const uint8_t* d_img_r, float* d_cost_l,
+                         float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end, void* stream) {
+    SMX_ARG(d_table && ((uintptr_t)d_table & 15) == 0 && d_img_l && d_img_r && (d_cost_l || d_cost_r));
+    SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
+    return launch_mi_cost_pair(d_table, d_img_l, d_img_r, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end,
+                               (hipStream_t)stream);
+}
+
 // ---- semi-global matching (not in the reference; smx_sgm.hip) -----------------------------------------
 void smx_default_sgm_params(smx_sgm_params* p) {
     if (!p) return;

@@ -70,6 +70,22 @@ struct LdsLimitOnce {
 enum StageId { ST_BEGIN = 0, ST_UPLOAD, ST_GUIDANCE, ST_WALK, ST_WTA, ST_FINISH, ST_DOWNLOAD, ST_COUNT };
 void stage_mark(int stage, hipStream_t st);
 
+// ---- the counter-based hash of PatchMatch stereo's draws and of the MI cost's random start (smx_pm_hash) ----------------
+// MurmurHash3's 32-bit finaliser (Appleby); the counter (seed, view, pixel, draw) goes in one word at a time
+__host__ __device__ inline uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+__host__ __device__ inline uint32_t pm_hash(uint32_t seed, uint32_t view, uint32_t pix, uint32_t draw) {
+    uint32_t h = fmix32(seed + 0x9E3779B9u * (view + 1u));
+    h = fmix32(h ^ pix);
+    return fmix32(h ^ draw);
+}
+
 // ---- packed WTA key ---------------------------------------------------------------------
 // key = sord(cost) << 32 | (0xFFFFFFFF - slice), compared as SIGNED 64-bit integers: sord = monotone
 // f32 -> i32 (-0 folded to +0), so that the per-pixel reduction of the shards is a plain int64 MIN

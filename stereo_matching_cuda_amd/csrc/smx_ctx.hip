@@ -6,6 +6,7 @@
 
 #include <array>
 #include <new>
+#include <vector>
 
 #include "smx_api.h"
 #include "smx_launch.h"
@@ -28,6 +29,11 @@ struct smx_ctx {
     DevBuf codes;               // census cost, AD-Census: the codes [2][h][w]
     bool adc_tab_valid = false; // the device table holds the tables of s.adc
     DevBuf adc_tab;
+    // the mutual-information cost: the histogram [256][256] u32 and the table [256][256] u8 of the pass in hand; mi_table is
+    // what the cost kernel reads -- this context's table, or in a pyramid level the table of level 0
+    DevBuf mi_hist, mi_tab;
+    const uint8_t* mi_table = nullptr;
+    bool done_mi = false;       // the last synchronous pair that completed ran with it (smx_ctx_mi_table)
     DevBuf spk, spk_ws;         // speckle removal: the despeckled left map [h][w] and the filter's workspace
     DevBuf uq, uq_map, uq_margin;   // uniqueness: the state [2][3][h][w], the filtered left map and the margins [h][w]
     DevBuf rgb;                 // the two colour images [2][h][w][4]
@@ -102,7 +108,13 @@ static int ctx_reserve(smx_ctx* c, const PairPlan& need) {
     if (need.cost) { SMX_HIP(c->costL.ensure(vb)); SMX_HIP(c->costR.ensure(vb)); }
     if (need.agg) SMX_HIP(c->aggLR.ensure(2 * vb));
     if (need.subpix) { SMX_HIP(c->nbr.ensure(6 * fb)); SMX_HIP(c->sub.ensure(2 * fb)); SMX_HIP(c->subf.ensure(fb)); }
-    if (need.census) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
+    const bool mi = c->s.cost_mode == SMX_COST_MI;
+    if (need.census && !mi) SMX_HIP(c->codes.ensure(2 * c->n * sizeof(uint64_t)));
+    if (need.census && mi && !need.level) {
+        SMX_HIP(c->mi_hist.ensure((size_t)SMX_MI_LEVELS * SMX_MI_LEVELS * sizeof(uint32_t)));
+        SMX_HIP(c->mi_tab.ensure((size_t)SMX_MI_LEVELS * SMX_MI_LEVELS));
+        c->mi_table = c->mi_tab.as<uint8_t>();
+    }
     if (need.speckle) { SMX_HIP(c->spk.ensure(fb)); SMX_HIP(c->spk_ws.ensure(speckle_workspace_bytes(c->w, c->h))); }
     if (need.uniq) { SMX_HIP(c->uq.ensure(6 * fb)); SMX_HIP(c->uq_map.ensure(fb)); SMX_HIP(c->uq_margin.ensure(fb)); }
     if (need.so) {
@@ -151,8 +163,10 @@ static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
 }
 
 // Slices [s0, s1) of both views' cost from the codes: the census cost, or AD-Census with its AD term from the gray images or
-// from the colour images of the pair
+// from the colour images of the pair; or, without codes, the mutual-information cost from the table of the pass in hand
 static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int s0, int s1, hipStream_t st) {
+    if (c->s.cost_mode == SMX_COST_MI)
+        return smx_dev_mi_cost_pair(c->mi_table, in.left, in.right, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
     const uint64_t* codes = c->codes.as<uint64_t>();
     if (!c->s.adcensus) return smx_dev_census_cost_pair(&c->s.census, codes, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
     const bool colour = c->s.adc.colour != 0;
@@ -305,7 +319,7 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairPlan& need, const
                           {in.dminl, in.dminr}, {keysL, keysL + n}, {out.mean, out.mean + n},
                           {aggL, need.agg ? aggL + (size_t)size_d * n : nullptr}, {nbrA, nbrA ? nbrA + 3 * n : nullptr},
                           {uqA, uqA ? uqA + 3 * n : nullptr}, w, h, 0, size_d, c->ws.p, c->ws_bytes, st};
-    if (need.census && (rc = ctx_census_codes(c, call))) return rc;
+    if (need.census && c->s.cost_mode != SMX_COST_MI && (rc = ctx_census_codes(c, call))) return rc;
     if (need.sgm) {
         // SGM instead of the guided filter: it reads the whole volumes, the census ones come from one launch
         if (need.census) rc = ctx_code_cost(c, in, costL, costR, 0, size_d, st);
@@ -404,6 +418,7 @@ static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, cons
         k->s.guide_mode = c->s.guide_mode;
         if (c->s.adcensus && (!k->s.adcensus || memcmp(&k->s.adc, &c->s.adc, sizeof(k->s.adc)) != 0)) { k->s.adc = c->s.adc; k->adc_tab_valid = false; }
         k->s.adcensus = c->s.adcensus;
+        k->mi_table = c->mi_table;
         PairPlan kn = {};
         kn.agg = kn.level = true;
         kn.census = need.census;
@@ -528,6 +543,7 @@ static int ctx_pair(smx_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int 
     if ((rc = ctx_adcensus_table(c))) return rc;
     if (channels) SMX_HIP(c->rgb.ensure(2 * n * (size_t)channels));
     c->done = PairPlan{};
+    c->done_mi = false;
     uint8_t* dL = c->dL.as<uint8_t>(); uint8_t* dR = c->dR.as<uint8_t>();
     uint8_t* rgbL = channels ? c->rgb.as<uint8_t>() : nullptr;
     uint8_t* rgbR = channels ? rgbL + n * (size_t)channels : nullptr;
@@ -544,10 +560,37 @@ static int ctx_pair(smx_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int 
     stage_mark(ST_UPLOAD, st);
     float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
     uint8_t* mean = c->mean.as<uint8_t>();
-    if (need.cscale && (rc = ctx_cscale_levels(c, who, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need))) return rc;
-    if ((rc = ctx_enqueue(c, {dL, dR, dminl, dminr, rgbL, rgbR, channels}, need,
-                          {best, map, mean, c->occ.as<float>(), c->fil.as<float>()})))
-        return rc;
+    const PairIn in = {dL, dR, dminl, dminr, rgbL, rgbR, channels};
+    const PairPlanes planes = {best, map, mean, c->occ.as<float>(), c->fil.as<float>()};
+    // one pass of the pair under a plan (the chunk and the workspace's share are per plan: ctx_reserve)
+    auto pass = [&](const PairPlan& pl) {
+        int r = ctx_reserve(c, pl);
+        if (!r && pl.cscale) r = ctx_cscale_levels(c, who, in, pl);
+        return r ? r : ctx_enqueue(c, in, pl, planes);
+    };
+    if (c->s.cost_mode == SMX_COST_MI) {
+        // include/smx.h, smx_ctx_set_mi: the start map, then per table a histogram of the current LR-checked left map, its
+        // table by way of the host, and -- before the last table -- a pass that stops behind the LR check and the fill
+        const smx_mi_params& mp = c->s.mi;
+        const size_t cells = (size_t)SMX_MI_LEVELS * SMX_MI_LEVELS;
+        PairPlan early = need;
+        early.uniq = early.speckle = early.vote = early.subpix = early.adjust = false;
+        if (mp.init == SMX_MI_INIT_REFERENCE) {
+            PairPlan start = early;
+            start.census = false;                       // (no cost from a table: the reference's, in the same flow)
+            rc = pass(start);
+        } else rc = smx_dev_mi_random_map(planes.occ, c->w, c->h, dminl, c->size_d, mp.seed, st);
+        if (rc) return rc;
+        std::vector<uint32_t> hist(cells);
+        for (int k = 1; k <= mp.iterations; ++k) {
+            if ((rc = smx_dev_mi_histogram(dL, dR, planes.occ, (float)(dminl - 100), c->mi_hist.as<uint32_t>(), c->w, c->h, st))) return rc;
+            SMX_HIP(hipMemcpyAsync(hist.data(), c->mi_hist.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            SMX_HIP(hipStreamSynchronize(st));
+            if ((rc = smx_dev_mi_table(hist.data(), c->mi_tab.as<uint8_t>(), st))) return rc;
+            if (k < mp.iterations && (rc = pass(early))) return rc;
+        }
+    }
+    if ((rc = pass(need))) return rc;
     const smx_pair_out dev = {best, best + n, map, map + n, mean, mean + n, c->occ.as<float>(), c->fil.as<float>(),
                               c->costL.as<float>(), c->costR.as<float>(), agg, need.agg ? agg + c->size_d * n : nullptr};
     const auto to = pair_planes(*out, c->size_d), from = pair_planes(dev, c->size_d);
@@ -562,6 +605,7 @@ static int ctx_pair(smx_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int 
             if ((rc = smx_dev_agg_status(c->cs_child[s]->ws.p))) return rc;
     }
     c->done = need;
+    c->done_mi = c->s.cost_mode == SMX_COST_MI;
     return SMX_OK;
 }
 
@@ -692,6 +736,18 @@ int smx_ctx_set_adcensus(smx_ctx* c, const smx_adcensus_params* p) {
     return SMX_OK;
 }
 
+int smx_ctx_set_mi(smx_ctx* c, const smx_mi_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (p->iterations < 1 || p->iterations > 16 || (p->init != SMX_MI_INIT_RANDOM && p->init != SMX_MI_INIT_REFERENCE))
+            return fail(SMX_E_ARG, "smx_ctx_set_mi: needs 1 <= iterations <= 16 and init SMX_MI_INIT_RANDOM or SMX_MI_INIT_REFERENCE");
+        c->s.mi = *p;
+        c->s.cost_mode = SMX_COST_MI;                   // (it replaces whatever smx_ctx_set_cost or smx_ctx_set_adcensus chose)
+        c->s.adcensus = false;
+    } else if (c->s.cost_mode == SMX_COST_MI) c->s.cost_mode = SMX_COST_REFERENCE;
+    return SMX_OK;
+}
+
 int smx_ctx_set_aggregation(smx_ctx* c, int mode, const smx_sgm_params* sgm) {
     SMX_ARG(c);
     if (mode != SMX_AGG_GUIDED && mode != SMX_AGG_SGM)
@@ -731,6 +787,16 @@ int smx_ctx_uniqueness_map(smx_ctx* c, float* map, float* margin) {
     if (!c->done.uniq) return fail(SMX_E_ARG, "smx_ctx_uniqueness_map: the last smx_ctx_stereo_pair ran without the uniqueness test");
     if (map) SMX_HIP(c->uq_map.download(map, c->n * sizeof(float)));
     if (margin) SMX_HIP(c->uq_margin.download(margin, c->n * sizeof(float)));
+    return SMX_OK;
+}
+
+int smx_ctx_mi_table(smx_ctx* c, uint8_t* table, uint32_t* hist) {
+    SMX_ARG(c);
+    if (int rc = ctx_check_device(c, "smx_ctx_mi_table")) return rc;
+    if (!c->done_mi) return fail(SMX_E_ARG, "smx_ctx_mi_table: the last smx_ctx_stereo_pair ran without the mutual-information cost");
+    const size_t cells = (size_t)SMX_MI_LEVELS * SMX_MI_LEVELS;
+    if (table) SMX_HIP(c->mi_tab.download(table, cells));
+    if (hist) SMX_HIP(c->mi_hist.download(hist, cells * sizeof(uint32_t)));
     return SMX_OK;
 }
 

@@ -39,6 +39,7 @@ struct CtxSettings {
     smx_census_params census;
     bool adcensus = false;                  // smx_ctx_set_adcensus: it takes the place of the census cost in every flow
     smx_adcensus_params adc;
+    smx_mi_params mi;                       // smx_ctx_set_mi: cost_mode SMX_COST_MI, the third value, which only that setter writes
     int agg_mode = SMX_AGG_GUIDED;          // smx_ctx_set_aggregation
     smx_sgm_params sgm;
     int guide_mode = SMX_GUIDE_GRAY;        // smx_ctx_set_guidance
@@ -58,8 +59,8 @@ struct CtxSettings {
 };
 
 // What one pair asks of the context beyond the eight result planes, decided once per pair by plan_pair.  cost / agg: the whole
-// volumes, because the caller wants them or a stage reads them; census: a cost built from census codes (the census cost or
-// AD-Census); the rest: the stage runs and its buffers are reserved.  cscale / perm / bp / sgm / so / cross / cgf say where the
+// volumes, because the caller wants them or a stage reads them; census: a cost materialised chunk by chunk (the census cost,
+// AD-Census, or the mutual-information cost, which needs no codes); the rest: the stage runs and its buffers are reserved.  cscale / perm / bp / sgm / so / cross / cgf say where the
 // winners come from, pm that PatchMatch takes the place of cost, aggregation and winners.  level: this pair is a level of
 // another context's pyramid, which wants its aggregated volumes and nothing behind them (ctx_cscale_levels sets it).
 // walker_status: the pair ran the fused aggregation, whose status word the entry reads afterwards.
@@ -143,7 +144,8 @@ static_assert(excludes_are_symmetric(), "STAGES: A must list B exactly when B li
 // The stages that `s` has on, as bits of CtxStage
 inline uint32_t stages_on(const CtxSettings& s) {
     const bool on[N_STAGES] = {s.agg_mode == SMX_AGG_SGM, s.guide_mode == SMX_GUIDE_RGB, s.cross, s.so, s.cscale, s.perm, s.bp, s.pm,
-                               s.adjust, s.uniq > 0.0f, s.subpix != 0, s.speckle, s.vote, s.cost_mode == SMX_COST_CENSUS, s.adcensus};
+                               s.adjust, s.uniq > 0.0f, s.subpix != 0, s.speckle, s.vote, s.cost_mode == SMX_COST_CENSUS || s.cost_mode == SMX_COST_MI,
+                               s.adcensus};
     uint32_t m = 0;
     for (int i = 0; i < N_STAGES; ++i) m |= on[i] ? bit(i) : 0;
     return m;
@@ -165,17 +167,21 @@ inline int plan_pair(const CtxSettings& s, int w, int h, int size_d, PairEntry e
     const uint32_t on = stages_on(s);
     auto is_on = [on](int i) { return (on >> i & 1) != 0; };
     auto refuse = [&](const char* fmt, auto... a) { snprintf(err, errlen, fmt, who, a...); return SMX_E_ARG; };
+    // the mutual-information cost is a mode of the census cost's row: the same flows and exclusions under its own name
+    const bool mi = s.cost_mode == SMX_COST_MI;
+    auto noun = [mi](int i) { return mi && i == S_CENSUS ? "the mutual-information cost" : STAGES[i].noun; };
+    auto setter = [mi](int i) { return mi && i == S_CENSUS ? "smx_ctx_set_mi" : STAGES[i].setter; };
     *plan = PairPlan{};
     plan->walker_status = true;
     // the pipelined entry stages the eight planes only: it takes the state with every opt-in off
     for (int i = 0; entry == ENTRY_ASYNC && i < N_STAGES; ++i)
-        if (is_on(i)) return refuse("%s: %s is on (%s): use %s", STAGES[i].noun, STAGES[i].setter, ENTRY_NAMES[i == S_CGF ? ENTRY_RGB : ENTRY_GRAY]);
+        if (is_on(i)) return refuse("%s: %s is on (%s): use %s", noun(i), setter(i), ENTRY_NAMES[i == S_CGF ? ENTRY_RGB : ENTRY_GRAY]);
     for (int a = 0; a < N_STAGES; ++a)
         for (int b = a + 1; b < N_STAGES; ++b) {
             const StageRow &A = STAGES[a], &B = STAGES[b];
             if (!is_on(a) || !is_on(b) || !(A.excludes >> b & 1)) continue;
             const char* why = B.why ? B.why : A.why;
-            return refuse("%s: %s (%s) and %s (%s) do not run together%s%s", A.noun, A.setter, B.noun, B.setter, why ? ": " : "", why ? why : "");
+            return refuse("%s: %s (%s) and %s (%s) do not run together%s%s", noun(a), setter(a), noun(b), setter(b), why ? ": " : "", why ? why : "");
         }
     if (is_on(S_PM) && (wants_cost || wants_agg))
         return refuse("%s: %s (%s) produces no cost volumes and no aggregated volumes", STAGES[S_PM].noun, STAGES[S_PM].setter);
@@ -187,9 +193,9 @@ inline int plan_pair(const CtxSettings& s, int w, int h, int size_d, PairEntry e
     for (int i = 0; i < N_STAGES; ++i) {
         const StageRow& r = STAGES[i];
         if (!is_on(i)) continue;
-        if ((r.flags & NO_MEAN) && wants_mean) return refuse("%s: %s (%s) produces no mean images", r.noun, r.setter);
+        if ((r.flags & NO_MEAN) && wants_mean) return refuse("%s: %s (%s) produces no mean images", noun(i), setter(i));
         if ((r.limit.checked & PER_PAIR) && !stage_shape_ok(r, w, h, size_d, dminl, dminr))
-            return refuse("%s: %s (%s) %s", r.noun, r.setter, r.limit.shapes);
+            return refuse("%s: %s (%s) %s", noun(i), setter(i), r.limit.shapes);
         plan->*r.runs = true;
         // (behind cross-based aggregation the optimiser reads that stage's q, not the cost volumes)
         plan->cost |= (r.flags & READS_COST) && !(i == S_SO && is_on(S_CROSS));

@@ -236,6 +236,44 @@ int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uin
     return SMX_OK;
 }
 
+int smx_mi_histogram(const uint8_t* img_l, const uint8_t* img_r, const float* map, float occlusion_mark, uint32_t* hist,
+                     int w, int h) {
+    SMX_ARG(img_l && img_r && map && hist);
+    if (!shape_ok(w, h, 1, 1)) return fail(SMX_E_ARG, "smx_mi_histogram: %s", PLANE_SHAPES);
+    const size_t n = (size_t)w * h, hb = (size_t)SMX_MI_LEVELS * SMX_MI_LEVELS * sizeof(uint32_t);
+    DevBuf img, dm, dh;
+    SMX_HIP(img.ensure(2 * n));
+    SMX_HIP(dh.ensure(hb));
+    SMX_HIP(hipMemcpy(img.p, img_l, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + n, img_r, n, hipMemcpyHostToDevice));
+    SMX_HIP(dm.upload(map, n * sizeof(float)));
+    if (int rc = smx_dev_mi_histogram(img.as<uint8_t>(), img.as<uint8_t>() + n, dm.as<float>(), occlusion_mark, dh.as<uint32_t>(),
+                                      w, h, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dh.download(hist, hb));
+    return SMX_OK;
+}
+
+int smx_mi_cost(const uint8_t* table, const uint8_t* i1, const uint8_t* i2, int right, float* cost, int w, int h, int size_d,
+                int dmin) {
+    SMX_ARG(table && i1 && i2 && cost && (right == 0 || right == 1) && w >= 1 && h >= 1 && size_d >= 1);
+    const size_t n = (size_t)w * h;
+    DevBuf img, tab, dc;
+    SMX_HIP(img.ensure(2 * n));
+    SMX_HIP(tab.upload(table, (size_t)SMX_MI_LEVELS * SMX_MI_LEVELS));
+    SMX_HIP(dc.ensure(n * size_d * sizeof(float)));
+    // (the left image first, whichever view is asked for)
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + (right ? n : 0), i1, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + (right ? 0 : n), i2, n, hipMemcpyHostToDevice));
+    if (int rc = smx_dev_mi_cost_pair(tab.as<uint8_t>(), img.as<uint8_t>(), img.as<uint8_t>() + n, right ? nullptr : dc.as<float>(),
+                                      right ? dc.as<float>() : nullptr, w, h, dmin, dmin, 0, size_d, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dc.download(cost, n * size_d * sizeof(float)));
+    return SMX_OK;
+}
+
 int smx_sgm_aggregate(const smx_sgm_params* p, const float* cost, float* agg, float* best, float* disp_map, int w, int h,
                       int size_d, int dmin) {
     if (!sgm_params_ok(p)) return fail(SMX_E_ARG, "smx_sgm_aggregate: %s", SGM_RANGES);

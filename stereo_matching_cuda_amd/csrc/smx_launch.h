@@ -46,6 +46,14 @@ int launch_census_cost_pair(int t, const uint64_t* code, float* cost_l, float* c
 int launch_adcensus_cost_pair(int t, int nch, const float* table, const uint64_t* code, const uint8_t* img_l, const uint8_t* img_r,
                               int ch, float* cost_l, float* cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end,
                               hipStream_t st);
+// smx_mi.hip: the mutual-information cost -- the joint histogram of a left map (the launch zeroes hist first), the table of a
+// histogram on the host, the random start map, and the cost slices [s_begin, s_end) of one or both views from a device table
+int launch_mi_histogram(const uint8_t* img_l, const uint8_t* img_r, const float* map, float mark, uint32_t* hist, int w, int h,
+                        hipStream_t st);
+void mi_table(const uint32_t* hist, uint8_t* table);
+int launch_mi_random_map(float* map, int w, int h, int dmin, int size_d, uint32_t seed, hipStream_t st);
+int launch_mi_cost_pair(const uint8_t* table, const uint8_t* img_l, const uint8_t* img_r, float* cost_l, float* cost_r, int w,
+                        int h, int dminl, int dminr, int s_begin, int s_end, hipStream_t st);
 // smx_speckle.hip: the connected-component filter (smx_dev_speckle_filter); ws: speckle_workspace_bytes(w, h) bytes
 size_t speckle_workspace_bytes(int w, int h);
 int launch_speckle_filter(int max_size, float max_diff, const float* disp, float* out, int w, int h, float vmin,

@@ -46,20 +46,7 @@ struct PmArgs {
     CostConst cc;
 };
 
-// MurmurHash3's 32-bit finaliser (Appleby); the counter (seed, view, pixel, draw) goes in one word at a time
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
-__host__ __device__ inline uint32_t pm_hash(uint32_t seed, uint32_t view, uint32_t pix, uint32_t draw) {
-    uint32_t h = fmix32(seed + 0x9E3779B9u * (view + 1u));
-    h = fmix32(h ^ pix);
-    return fmix32(h ^ draw);
-}
+// (pm_hash, the counter-based hash of the draws: smx_common.h, which the random start of the MI cost shares)
 __device__ inline float pm_uniform(uint32_t seed, uint32_t view, uint32_t pix, uint32_t draw) {
     return (float)(pm_hash(seed, view, pix, draw) >> 8) * 5.9604644775390625e-08f;      // 2^-24
 }

@@ -26,7 +26,7 @@ class PairPipeline:
     def __init__(self, w, h, size_d, dminl=None, dminr=0, s_begin=0, s_end=None, device="cuda:0",
                  slices_in_flight=None, want_agg=False, params=None, max_ws_bytes=64 << 30, multi_kernel=False,
                  wmf=None, wmf_params=None, subpixel=None, cost=None, census_params=None, speckle=None,
-                 aggregation=None, sgm_params=None, bp_params=None, uniqueness=None, guidance=None, adcensus_params=None, cross_params=None,
+                 aggregation=None, sgm_params=None, bp_params=None, uniqueness=None, guidance=None, adcensus_params=None, mi_params=None, cross_params=None,
                  vote=None, vote_arms=None, scanline_params=None, adjust=None, cross_scale=None, pm_params=None,
                  permeability=None):
         """wmf: None, "occluded" or "all" -- the weighted-median refinement of the filled left map (not a stage of
@@ -46,6 +46,12 @@ class PairPipeline:
         adcensus_params: AdCensusParams, None = the defaults): the flows and buffers of the census cost, with the device table
         self.adcensus_table, uploaded here, beside them.  With adcensus_params.colour 1 the AD term comes from the colour
         images: aggregate() / run() need rgb_l=, rgb_r= then, with either guide.
+        cost="mi" is the mutual-information cost (include/smx.h smx_dev_mi_cost_pair, smx_ctx_set_mi; mi_params: MiParams, None =
+        the defaults): the flows and the cost buffer of the census cost without the codes, with self.mi_hist and self.mi_table
+        (256, 256) beside them.  run() learns the table from the pair: the start map (random, or one pass with the reference's
+        cost), then mi_params.iterations times histogram -> table on the host -> pass, the passes before the last stopping behind
+        the LR check; aggregate() alone is one pass with the table that self.mi_table holds.  A host round trip per table:
+        run() is not graph-capturable.  No slice sub-range, no PatchMatch stereo.
         speckle: None, True (the defaults) or SpeckleParams -- speckle removal (not a stage of the reference;
         smx_dev_speckle_filter behind the finish): self.despeckled = self.occlusion without its small connected components
         (vmin = dminl, new_val = dminl - 100), self.filled = the fill of self.despeckled, and the sub-pixel fit and
@@ -206,8 +212,15 @@ class PairPipeline:
         so = aggregation in ("scanline", "cross-scanline")
         if scanline_params is not None and not so:
             raise ValueError("scanline_params belongs to aggregation='scanline' / 'cross-scanline'")
-        if cost not in (None, "census", "adcensus"):
-            raise ValueError(f"cost must be None, 'census' or 'adcensus', not {cost!r}")
+        if cost not in (None, "census", "adcensus", "mi"):
+            raise ValueError(f"cost must be None, 'census', 'adcensus' or 'mi', not {cost!r}")
+        if mi_params is not None and cost != "mi":
+            raise ValueError("mi_params belongs to cost='mi'")
+        if cost == "mi":
+            if aggregation == "patchmatch":
+                raise ValueError("PatchMatch stereo keeps no cost volume: the mutual-information cost does not run with it")
+            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
+                raise ValueError("the mutual-information cost learns its table from a pair's whole disparity range: no slice sub-range")
         if wmf not in (None, "occluded", "all"):
             raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
         if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
@@ -317,8 +330,15 @@ class PairPipeline:
         if cost == "adcensus":
             self.adcensus_params = adcensus_params if adcensus_params is not None else _lib.default_adcensus_params()
             self.census_params = self.adcensus_params.census          # (the codes are those of its census part)
+        elif cost == "mi":
+            self.census_params = None
         else:
             self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
+        self.mi_params = self.mi_hist = self.mi_table = None
+        if cost == "mi":
+            self.mi_params = mi_params if mi_params is not None else _lib.default_mi_params()
+            if not (1 <= self.mi_params.iterations <= 16 and self.mi_params.init in _lib.MI_INITS.values()):
+                raise ValueError("the mutual-information cost needs 1 <= iterations <= 16 and init 0 (random) or 1 (reference)")
         chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
         while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
             sif = (sif + 1) // 2
@@ -369,7 +389,10 @@ class PairPipeline:
         if self.adjust:
             self.adjusted = torch.empty((self.h, self.w), **f)
             self.adjust_ws = torch.empty(self.adjust_ws_bytes, dtype=torch.uint8, device=dev)
-        self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost else None
+        self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost in ("census", "adcensus") else None
+        if cost == "mi":
+            self.mi_hist = torch.empty((_lib.MI_LEVELS, _lib.MI_LEVELS), dtype=torch.int32, device=dev)
+            self.mi_table = torch.empty((_lib.MI_LEVELS, _lib.MI_LEVELS), dtype=torch.uint8, device=dev)
         self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and not bp and aggregation != "scanline" else None
         if cost == "adcensus":
             self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
@@ -432,6 +455,7 @@ class PairPipeline:
                                                    params=self.params, max_ws_bytes=max_ws_bytes, multi_kernel=multi_kernel,
                                                    cost=cost, census_params=census_params, guidance=guidance,
                                                    adcensus_params=adcensus_params))
+                self.cs_levels[-1].mi_table = self.mi_table      # (the levels take the table of level 0)
                 self.cs_gray.append(torch.empty((2, hs, ws), dtype=torch.uint8, device=dev))
                 self.cs_rgb.append(torch.empty(2 * hs * ws * 4, dtype=torch.uint8, device=dev) if colour else None)
         # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
@@ -569,10 +593,19 @@ class PairPipeline:
         if rgb_l.shape[2] != rgb_r.shape[2]:
             raise ValueError("both colour guides need the same number of channels")
 
+    def _census_codes(self, gray_l, gray_r, st):
+        """The codes of both images into self.codes, a launch per image; nothing for a cost without codes (cost="mi")."""
+        for v, g in enumerate((gray_l, gray_r) if self.codes is not None else ()):
+            _lib.check(self.lib.smx_dev_census(C.byref(self.census_params), _dp(g), _dp(self.codes[v]), self.w, self.h, 1, st))
+
     def _code_cost(self, gray_l, gray_r, cl, cr, c0, c1, st):
         """Slices [c0, c1) of both views' cost from self.codes into cl, cr: the census cost, or AD-Census with its AD term from
         the gray images or, with colour 1, from the colour images of this aggregate()."""
         L, w, h = self.lib, self.w, self.h
+        if self.cost == "mi":
+            _lib.check(L.smx_dev_mi_cost_pair(_dp(self.mi_table), _dp(gray_l), _dp(gray_r), _dp(cl), _dp(cr), w, h, self.dminl,
+                                              self.dminr, c0, c1, st))
+            return
         if self.cost == "census":
             _lib.check(L.smx_dev_census_cost_pair(C.byref(self.census_params), _dp(self.codes), _dp(cl), _dp(cr), w, h,
                                                   self.dminl, self.dminr, c0, c1, st))
@@ -586,14 +619,16 @@ class PairPipeline:
         """The census flow, and AD-Census's: the codes of both images once (one launch where the two images lie back to back in
         memory, else one per image), then per chunk of `slices_in_flight` slices the cost (_code_cost) into self.census_cost
         and the aggregation from it.  Only the first chunk takes the keys as fresh; the later ones accumulate."""
-        L, P = self.lib, C.byref(self.census_params)
+        L = self.lib
         with self._on_device():
             st = self._stream()
-            if gray_r.data_ptr() == gray_l.data_ptr() + self.n:
-                _lib.check(L.smx_dev_census(P, _dp(gray_l), _dp(self.codes), self.w, self.h, 2, st))
+            if self.codes is None:          # (the mutual-information cost reads the images themselves)
+                pass
+            elif gray_r.data_ptr() == gray_l.data_ptr() + self.n:
+                _lib.check(L.smx_dev_census(C.byref(self.census_params), _dp(gray_l), _dp(self.codes), self.w, self.h, 2, st))
             else:
                 for v, g in enumerate((gray_l, gray_r)):
-                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), self.w, self.h, 1, st))
+                    _lib.check(L.smx_dev_census(C.byref(self.census_params), _dp(g), _dp(self.codes[v]), self.w, self.h, 1, st))
         sif = self.slices_in_flight
         for c0 in range(self.s_begin, self.s_end, sif):
             c1 = min(self.s_end, c0 + sif)
@@ -641,9 +676,7 @@ class PairPipeline:
         with self._on_device():
             st = self._stream()
             if self.cost:
-                P = C.byref(self.census_params)
-                for v, g in enumerate((gray_l, gray_r)):
-                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, st))
+                self._census_codes(gray_l, gray_r, st)
                 self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
             elif cost_l is None:
                 P = C.byref(self.params)
@@ -674,10 +707,8 @@ class PairPipeline:
         L, w, h = self.lib, self.w, self.h
         self.init_keys()
         if self.cost:
-            P = C.byref(self.census_params)
             with self._on_device():
-                for v, g in enumerate((gray_l, gray_r)):
-                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, self._stream()))
+                self._census_codes(gray_l, gray_r, self._stream())
         sif = self.slices_in_flight
         for c0 in range(self.s_begin, self.s_end, sif):
             c1 = min(self.s_end, c0 + sif)
@@ -689,7 +720,8 @@ class PairPipeline:
                     cl, cr = self.census_cost[0], self.census_cost[1]
                     self._code_cost(gray_l, gray_r, cl, cr, c0, c1, st)
                 else:
-                    cl, cr = own_cost[0], own_cost[1]
+                    # (own_cost is None in the start pass of cost="mi" with the reference's cost: the chunk buffer is there)
+                    cl, cr = (own_cost if own_cost is not None else self.census_cost)[:2]
                     P = C.byref(self.params)
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, c0, c1, st))
                     _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, c0, c1, st))
@@ -722,9 +754,7 @@ class PairPipeline:
         with self._on_device():
             st = self._stream()
             if self.cost:
-                P = C.byref(self.census_params)
-                for v, g in enumerate((gray_l, gray_r)):
-                    _lib.check(L.smx_dev_census(P, _dp(g), _dp(self.codes[v]), w, h, 1, st))
+                self._census_codes(gray_l, gray_r, st)
                 self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
             elif cost_l is None:
                 P = C.byref(self.params)
@@ -825,6 +855,11 @@ class PairPipeline:
         call (smx_dev_finish_pair: one launch, a row per workgroup).  Behind PatchMatch stereo best and dmap are there
         already: the LR check and the fill run on the labels (main.cu:141-155), and the fractional filled map closes the
         outlier stages."""
+        self._finish_maps()
+        self._finish_stages()
+
+    def _finish_maps(self):
+        """The part of finish() up to the LR check and the fill."""
         with self._on_device():
             L, P, st = self.lib, C.byref(self.params), self._stream()
             if self.aggregation == "patchmatch":
@@ -836,6 +871,9 @@ class PairPipeline:
                 _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                                  self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                                  _dp(self.occlusion), _dp(self.filled), st))
+
+    def _finish_stages(self):
+        """The opt-in stages of finish() behind the LR check and the fill."""
         if self.aggregation == "patchmatch":
             if self.speckle:
                 self.despeckle()
@@ -963,8 +1001,40 @@ class PairPipeline:
             self.region_vote()
 
     def run(self, gray_l, gray_r, rgb_l=None, rgb_r=None):
+        if self.cost == "mi":
+            self._mi_passes(gray_l, gray_r, rgb_l, rgb_r)
         self.aggregate(gray_l, gray_r, rgb_l=rgb_l, rgb_r=rgb_r)
         self.finish()
+
+    def _mi_passes(self, gray_l, gray_r, rgb_l, rgb_r):
+        """What a cost="mi" pair runs before its last pass (include/smx.h, smx_ctx_set_mi): the start map into self.occlusion --
+        the random one, or the LR-checked left map of a pass with the reference's cost -- then per table the histogram of
+        self.occlusion, its table by way of the host (smx_dev_mi_table waits for the stream: a pair is not graph-capturable)
+        and, before the last table, a pass that stops behind the LR check and the fill."""
+        L, mp = self.lib, self.mi_params
+        if mp.init == _lib.MI_INITS["reference"]:
+            levels = [self] + self.cs_levels
+            for p in levels:
+                p.cost = None
+            try:
+                self.aggregate(gray_l, gray_r, rgb_l=rgb_l, rgb_r=rgb_r)
+            finally:
+                for p in levels:
+                    p.cost = "mi"
+            self._finish_maps()
+        else:
+            with self._on_device():
+                _lib.check(L.smx_dev_mi_random_map(_dp(self.occlusion), self.w, self.h, self.dminl, self.size_d, mp.seed, self._stream()))
+        for k in range(1, mp.iterations + 1):
+            with self._on_device():
+                st = self._stream()
+                _lib.check(L.smx_dev_mi_histogram(_dp(gray_l), _dp(gray_r), _dp(self.occlusion), float(self.dminl - 100),
+                                                  _dp(self.mi_hist), self.w, self.h, st))
+                hist = self.mi_hist.cpu().numpy()
+                _lib.check(L.smx_dev_mi_table(hist.ctypes.data, _dp(self.mi_table), st))
+            if k < mp.iterations:
+                self.aggregate(gray_l, gray_r, rgb_l=rgb_l, rgb_r=rgb_r)
+                self._finish_maps()
 
     def check_status(self):
         """Raise if a workgroup of the fused aggregation gave up waiting for a neighbour."""

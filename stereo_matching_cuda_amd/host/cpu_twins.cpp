@@ -20,6 +20,7 @@
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "integral.cuh"
+#include "mutualInformation.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
 #include "permeability.cuh"
@@ -1027,6 +1028,36 @@ void adcensus_costOnCPU(const unsigned char* i1, const unsigned char* i2, const 
                     s += d < 0 ? -d : d;
                 }
                 *out = table[hc] + table[64 + s];
+            }
+}
+
+// ---- mutualInformation.cuh (not in the reference) ---------------------------------------------
+// The joint histogram and the cost by the definition in include/smx.h, one pixel and one cell at a time.
+void mi_histogramOnCPU(const unsigned char* left, const unsigned char* right, const float* disp, float mark, unsigned int* hist,
+                       const int w, const int h) {
+    for (size_t i = 0; i < (size_t)SMX_MI_LEVELS * SMX_MI_LEVELS; ++i) hist[i] = 0;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t a = (size_t)y * w + x;
+            if (disp[a] == mark) continue;
+            const long long xx = (long long)x + (long long)(int)disp[a];
+            if (xx < 0 || xx >= w) continue;
+            ++hist[(size_t)left[a] * SMX_MI_LEVELS + right[(size_t)y * w + (size_t)xx]];
+        }
+}
+
+void mi_costOnCPU(const unsigned char* table, const unsigned char* left, const unsigned char* right, int view, float* cost,
+                  const int w, const int h, const int size_d, const int dmin) {
+    const size_t n = (size_t)w * h;
+    for (int z = 0; z < size_d; ++z)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const long long xx = (long long)x + dmin + z;
+                float* out = cost + (size_t)z * n + (size_t)y * w + x;
+                if (xx < 0 || xx >= w) { *out = 255.0f; continue; }
+                const size_t a = (size_t)y * w + x, b = (size_t)y * w + (size_t)xx;
+                // the left view reads T[L[a]][R[b]], the right view T[L[b]][R[a]]
+                *out = (float)(view ? table[(size_t)left[b] * SMX_MI_LEVELS + right[a]] : table[(size_t)left[a] * SMX_MI_LEVELS + right[b]]);
             }
 }
 

@@ -38,6 +38,13 @@
 //                     --adcensus-scale S the scale (2^-20 .. 2^20; default 127.5), --ad gray|rgb the images of the absolute
 //                     difference: the gray ones (default) or R, G, B of the PNGs (smx_ctx_stereo_pair_rgb).  With
 //                     --host-compare the CPU twin (adcensus_costOnCPU) redoes the cost images
+//   --cost mi         the mutual-information cost (smx_ctx_set_mi; implies --fused): the cost for pairs whose gray values are
+//                     related by some fixed mapping that need not be increasing.  The pair learns a 256 x 256 table from itself:
+//                     --mi-iterations N tables (1 .. 16; default 3), from a start map --mi-init random (default; --mi-seed K) or
+//                     reference (one pass with the reference's cost).  The same twelve images, the two cost images from the
+//                     volumes of the last table.  With --host-compare the table is recomputed from its histogram, the CPU twin
+//                     (mi_costOnCPU) redoes the cost images, and the aggregation twins take the last table's volumes.  Not with
+//                     --aggregation patchmatch
 //   --speckle SIZE[,DIFF]  speckle removal between the LR check and the fill (smx_speckle_filter; not in the reference), on
 //                     every single-GPU path: connected components of at most SIZE pixels whose 4-neighbours differ by at
 //                     most DIFF (default 1) are invalidated like LR failures.  Writes occlu_mapl_despeckled.png beside
@@ -164,6 +171,7 @@
 #include "filter.cuh"
 #include "guidedFilter.cuh"
 #include "helpers.cuh"
+#include "mutualInformation.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
 #include "permeability.cuh"
@@ -195,6 +203,8 @@ struct Options {
     bool adcensus = false;   // --cost adcensus
     bool ad_rgb = false;     // --ad rgb: the absolute differences on R, G, B of the colour images
     smx_adcensus_params adc_params;     // (its census part is filled from census_params after the parse)
+    bool mi = false;         // --cost mi
+    smx_mi_params mi_params;
     bool sgm = false;        // --aggregation sgm
     smx_sgm_params sgm_params;
     bool bp = false;         // --aggregation bp
@@ -280,10 +290,24 @@ const ValueOption value_options[] = {
          static_assert(SMX_SUBPIX_PARABOLA == 1 && SMX_SUBPIX_EQUIANGULAR == 2, "the modes follow the words");
          o.subpixel = 1 + word(v, {"parabola", "equiangular"});
          return o.subpixel != 0; }},
-    {"--cost", "`reference`, `census` or `adcensus`", [](auto& v, auto& o) {       // (the last one wins)
-         const int k = word(v, {"reference", "census", "adcensus"});
-         o.census = k == 1; o.adcensus = k == 2;
+    {"--cost", "`reference`, `census`, `adcensus` or `mi`", [](auto& v, auto& o) {       // (the last one wins)
+         const int k = word(v, {"reference", "census", "adcensus", "mi"});
+         o.census = k == 1; o.adcensus = k == 2; o.mi = k == 3;
          return k >= 0; }},
+    {"--mi-iterations", "a number of tables N with 1 <= N <= 16", [](auto& v, auto& o) {
+         long k = 0;
+         const bool good = number(v, 1L, 16L, k);
+         o.mi_params.iterations = (int)k;
+         return good; }},
+    {"--mi-init", "`random` or `reference`", [](auto& v, auto& o) {
+         static_assert(SMX_MI_INIT_RANDOM == 0 && SMX_MI_INIT_REFERENCE == 1, "the modes follow the words");
+         o.mi_params.init = word(v, {"random", "reference"});
+         return o.mi_params.init >= 0; }},
+    {"--mi-seed", "a seed K with 0 <= K < 2^32", [](auto& v, auto& o) {
+         long k = 0;
+         const bool good = number(v, 0L, 4294967295L, k);
+         o.mi_params.seed = (uint32_t)k;
+         return good; }},
     {"--adcensus-lambda", "C,A with 0 < C, A <= 1e6", [](auto& v, auto& o) {
          double& c = o.adc_params.lambda_census; double& a = o.adc_params.lambda_ad;
          return pair_of(v, ',', c, a) && c > 0 && c <= 1e6 && a > 0 && a <= 1e6; }},
@@ -449,6 +473,7 @@ Options parse(int argc, char** argv) {
     smx_default_cross_params(&o.cross_params);
     smx_default_scanline_params(&o.so_params);
     smx_default_adcensus_params(&o.adc_params);
+    smx_default_mi_params(&o.mi_params);
     smx_default_vote_params(&o.vote_params);
     smx_default_cross_params(&o.vote_arms);
     smx_default_adjust_params(&o.adjust_params);
@@ -488,6 +513,9 @@ Options parse(int argc, char** argv) {
          "or --cost adcensus"},
         {o.saw({"--adcensus-lambda", "--adcensus-scale", "--ad"}) && !o.adcensus,
          "--adcensus-lambda, --adcensus-scale and --ad need --cost adcensus"},
+        {o.saw({"--mi-iterations", "--mi-init", "--mi-seed"}) && !o.mi, "--mi-iterations, --mi-init and --mi-seed need --cost mi"},
+        {o.mi && o.pm, "--cost mi cannot be combined with --aggregation patchmatch, which scores planes with the reference's cost "
+                       "and keeps no cost volume"},
         {o.saw({"--sgm-p", "--sgm-paths"}) && !o.sgm, "--sgm-p and --sgm-paths need --aggregation sgm"},
         {o.saw({"--cross-arms", "--cross-tau", "--cross-iterations"}) && !o.cross,
          "--cross-arms, --cross-tau and --cross-iterations need --aggregation cross or cross-scanline"},
@@ -531,6 +559,8 @@ struct Job {
     int w = 0, h = 0, n = 0;
     // left volume: labels d_lo .. d_hi; right volume: labels -d_hi .. -d_lo   (main.cu:79-82)
     int d_lo = 0, d_hi = 0, size_d = 0, dmin[2] = {0, 0};
+    // --cost mi: the table of the pair's last pass (smx_ctx_mi_table), which every cost volume built afterwards reads
+    std::vector<unsigned char> mi_table;
 };
 
 // The maps of the pair, as the stages leave them on the host.
@@ -563,7 +593,9 @@ struct Maps {
 // The first `slices` slices of view v's cost volume, by the cost the options name.
 void build_cost(const Job& j, int v, int slices, float* dst, bool host_compare) {
     const Options& opt = j.opt;
-    if (opt.adcensus) {
+    if (opt.mi) {
+        compute_mi_cost(j.mi_table.data(), j.gray[0], j.gray[1], v, dst, j.w, j.h, slices, j.dmin[v], host_compare);
+    } else if (opt.adcensus) {
         // the images of its absolute differences, and their bytes per pixel
         unsigned char* const* img = opt.ad_rgb ? j.in.rgb : j.gray;
         compute_adcensus_cost(img[v], img[1 - v], opt.ad_rgb ? j.in.channels[0] : 1, dst, j.w, j.h, slices, j.dmin[v],
@@ -681,6 +713,7 @@ void check_cross_scale_twin(const Job& j, Maps& m, std::vector<float>& agg_l) {
         l.in.w = l.w; l.in.h = l.h;
         for (int v = 0; v < 2; ++v) {
             l.in.channels[v] = j.in.channels[v];
+            l.mi_table = j.mi_table;        // (the levels take the table of level 0)
             if (s == 0) { l.gray[v] = j.gray[v]; l.in.rgb[v] = j.in.rgb[v]; continue; }
             const Job& b = level[s - 1];
             gray[v].emplace_back((size_t)l.n);
@@ -862,14 +895,15 @@ struct Sharded {
 
 // Device-resident: one call, the cost slices never leave the CU (only slice 0 of each volume is materialised, for the two cost
 // images the reference writes).  -> whether `stage_ms` holds the device times of the last pair.
-bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms& stage_ms) {
+bool run_device_resident(Job& j, const Sharded& sh, Maps& m, smx_stage_ms& stage_ms) {
     const Options& opt = j.opt;
     const bool host_compare = opt.host_compare, uniq = opt.uniqueness > 0.0f;
     const bool colour = opt.rgb || opt.ad_rgb || opt.cross || opt.so;     // the entry that takes the colour pair
     const int w = j.w, h = j.h, n = j.n;
     std::cout << "Cost Volume ..." << std::endl;
     for (int v = 0; v < 2; ++v) m.cost[v].resize((size_t)n);
-    for (int v = 0; v < 2; ++v) build_cost(j, v, 1, m.cost[v].data(), host_compare);
+    // (the mutual-information cost has its table only behind the pair: its cost images follow the pair below)
+    for (int v = 0; v < 2 && !opt.mi; ++v) build_cost(j, v, 1, m.cost[v].data(), host_compare);
     std::cout << "guided filter ..." << std::endl;
     m.occlusion.resize(n);
     m.filled.resize(n);
@@ -894,6 +928,7 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (opt.subpixel) CHECK(smx_ctx_set_subpixel(ctx, opt.subpixel));
     if (opt.census) CHECK(smx_ctx_set_cost(ctx, SMX_COST_CENSUS, &opt.census_params));
     if (opt.adcensus) CHECK(smx_ctx_set_adcensus(ctx, &opt.adc_params));
+    if (opt.mi) CHECK(smx_ctx_set_mi(ctx, &opt.mi_params));
     if (opt.speckle) CHECK(smx_ctx_set_speckle(ctx, &opt.speckle_params));
     if (uniq) CHECK(smx_ctx_set_uniqueness(ctx, opt.uniqueness));
     if (opt.vote) CHECK(smx_ctx_set_vote(ctx, &opt.vote_params, &opt.vote_arms));
@@ -950,6 +985,20 @@ bool run_device_resident(const Job& j, const Sharded& sh, Maps& m, smx_stage_ms&
     if (uniq) {
         m.unique.resize(n);
         CHECK(smx_ctx_uniqueness_map(ctx, m.unique.data(), nullptr));
+    }
+    if (opt.mi) {
+        // the table the last pass ran with, and the histogram it came from: the twin of the table is the library's own host
+        // arithmetic, so --host-compare checks that the two belong together
+        j.mi_table.resize((size_t)SMX_MI_LEVELS * SMX_MI_LEVELS);
+        std::vector<uint32_t> hist(j.mi_table.size());
+        CHECK(smx_ctx_mi_table(ctx, j.mi_table.data(), hist.data()));
+        if (host_compare) {
+            std::vector<unsigned char> again(j.mi_table.size());
+            CHECK(smx_mi_table(hist.data(), again.data()));
+            if (again == j.mi_table) std::cout << "Mutual-information table ok!" << std::endl;
+            else std::cout << "error in the mutual-information table" << std::endl;
+        }
+        for (int v = 0; v < 2; ++v) build_cost(j, v, 1, m.cost[v].data(), host_compare);
     }
     if (opt.adjust) m.adjusted = m.filled;
     if (opt.cscale) m.cscale = m.dmap[0];
@@ -1079,6 +1128,7 @@ int main(int argc, char** argv) {
         {opt.cross && (opt.rgb || multi), "--aggregation cross cannot be combined with --guidance rgb, --ngpu or --pipeline"},
         {opt.census && multi, "--cost census" + with_multi},
         {opt.adcensus && multi, "--cost adcensus" + with_multi},
+        {opt.mi && multi, "--cost mi" + with_multi},
         {opt.sgm && labels > SMX_SGM_MAX_D, "--aggregation sgm takes at most " + std::to_string(SMX_SGM_MAX_D) + " labels"},
         {opt.speckle && multi, "--speckle" + with_multi},
         {uniq && multi, "--uniqueness" + with_multi},
@@ -1109,7 +1159,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--ngpu: cannot load the sharded context of libsmx_rccl.so (%s)\n", dlerror());
         return 1;
     }
-    const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.sgm || opt.bp || uniq || opt.rgb ||
+    const bool fused = opt.fused || sharded.create || opt.subpixel || opt.census || opt.adcensus || opt.mi || opt.sgm || opt.bp || uniq || opt.rgb ||
                        opt.cross || opt.so || opt.adjust || opt.cscale || opt.pm || opt.perm;
     if (opt.pairs < 1 || (opt.pairs > 1 && !fused)) {
         std::fprintf(stderr, "--pairs needs a count >= 1 and --fused or --ngpu\n");

@@ -8,6 +8,7 @@
 #include "discontinuityAdjustment.cuh"
 #include "filter.cuh"
 #include "guidedFilter.cuh"
+#include "mutualInformation.cuh"
 #include "occlusion.cuh"
 #include "patchMatch.cuh"
 #include "permeability.cuh"
@@ -121,6 +122,32 @@ void compute_adcensus_cost(unsigned char* i1, unsigned char* i2, int channels, f
         bool ok = true;
         for (int z = 0; z < size_d; ++z) ok = check_errors(twin.data() + (size_t)z * n, cost + (size_t)z * n, (int)n) && ok;
         if (ok) cout << "AD-Census cost ok!" << endl;
+    }
+}
+
+// not in the reference: the mutual-information cost (smx_main --cost mi) -- the joint histogram of a left map, and the volume
+// of one view from a table
+void compute_mi_histogram(unsigned char* left, unsigned char* right, float* disp, float mark, unsigned int* hist, int w, int h,
+                          bool host_gpu_compare) {
+    CHECK(smx_mi_histogram(left, right, disp, mark, hist, w, h));
+    if (host_gpu_compare) {
+        std::vector<unsigned int> twin((size_t)SMX_MI_LEVELS * SMX_MI_LEVELS);
+        mi_histogramOnCPU(left, right, disp, mark, twin.data(), w, h);
+        if (std::memcmp(twin.data(), hist, twin.size() * sizeof(unsigned int)) == 0) cout << "Mutual-information histogram ok!" << endl;
+        else cout << "error in the mutual-information histogram" << endl;
+    }
+}
+
+void compute_mi_cost(const unsigned char* table, unsigned char* left, unsigned char* right, int view, float* cost, int w, int h,
+                     int size_d, int dmin, bool host_gpu_compare) {
+    CHECK(smx_mi_cost(table, view ? right : left, view ? left : right, view, cost, w, h, size_d, dmin));
+    if (host_gpu_compare) {
+        const size_t n = (size_t)w * h;
+        std::vector<float> twin(n * size_d);
+        mi_costOnCPU(table, left, right, view, twin.data(), w, h, size_d, dmin);
+        bool ok = true;
+        for (int z = 0; z < size_d; ++z) ok = check_errors(twin.data() + (size_t)z * n, cost + (size_t)z * n, (int)n) && ok;
+        if (ok) cout << "Mutual-information cost ok!" << endl;
     }
 }
 

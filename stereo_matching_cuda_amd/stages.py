@@ -415,6 +415,43 @@ def adcensus_cost(i1, i2, size_d, dmin, params=None):
     return cost
 
 
+def mi_histogram(img_l, img_r, disp, occlusion_mark):
+    """The joint histogram (256, 256) uint32 of the pixels that the left map `disp` pairs up: H[L[y][x]][R[y][x + d]] counts
+    the pixels whose label d is not `occlusion_mark` and whose partner lies inside the image (smx_mi_histogram)."""
+    il, ir, m = _c(img_l, np.uint8), _c(img_r, np.uint8), _c(disp, np.float32)
+    if il.ndim != 2 or ir.shape != il.shape or m.shape != il.shape:
+        raise ValueError("mi_histogram expects two (h, w) uint8 images and an (h, w) float32 map of one shape")
+    h, w = il.shape
+    hist = np.empty((_lib.MI_LEVELS, _lib.MI_LEVELS), np.uint32)
+    _lib.check(_lib.lib().smx_mi_histogram(_ptr(il), _ptr(ir), _ptr(m), float(occlusion_mark), _ptr(hist), w, h))
+    return hist
+
+
+def mi_table(hist):
+    """The cost table (256, 256) uint8 of a joint histogram (smx_mi_table; host only, in double): T[i][k] is the cost of a left
+    pixel of value i against a right pixel of value k.  Any map gives a histogram, so a caller's own start works too."""
+    hist = _c(hist, np.uint32)
+    if hist.shape != (_lib.MI_LEVELS, _lib.MI_LEVELS):
+        raise ValueError("mi_table expects a (256, 256) uint32 histogram")
+    table = np.empty(hist.shape, np.uint8)
+    _lib.check(_lib.lib().smx_mi_table(_ptr(hist), _ptr(table)))
+    return table
+
+
+def mi_cost(table, i1, i2, size_d, dmin, right=False):
+    """Mutual-information cost volume of i1 against i2, [z][y][x], slice z has label dmin + z (smx_mi_cost).  With right=True
+    i1 is the right image and i2 the left one, and the table is read with the roles swapped."""
+    table, i1, i2 = _c(table, np.uint8), _c(i1, np.uint8), _c(i2, np.uint8)
+    if table.shape != (_lib.MI_LEVELS, _lib.MI_LEVELS):
+        raise ValueError("mi_cost expects a (256, 256) uint8 table")
+    if i1.ndim != 2 or i2.shape != i1.shape:
+        raise ValueError("mi_cost expects two (h, w) uint8 images of one shape")
+    h, w = i1.shape
+    cost = np.empty((max(size_d, 0), h, w), np.float32)
+    _lib.check(_lib.lib().smx_mi_cost(_ptr(table), _ptr(i1), _ptr(i2), int(bool(right)), _ptr(cost), w, h, size_d, dmin))
+    return cost
+
+
 def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
     """Semi-global matching of one (size_d, h, w) float32 cost volume (smx_sgm_aggregate; include/smx.h has the
     definition).  Returns (agg, best, disp_map): S as float32 [z][y][x] (None without want_agg), the winner's S and
