@@ -3,7 +3,8 @@
 tests/test_gpu_optin_fuzz.py runs the committed seeds of every stage through the device entries; what it proves depends on what
 those seeds hold.  This file asserts that over exactly those seeds: every draw lies inside the contract of include/smx.h (so
 no case is refused or skipped), the regimes that uniform noise never reaches are reached, and no reference call is slow.  Where
-one of these fails, the generator or the seed base changes -- never what the kernels are held to.
+one of these fails, the generator or the seed base changes -- never what the kernels are held to.  The last section does the
+same for the table family of compositions: its draws against tests/ctx_plan_ref.py, its coverage and its regimes.
 """
 import functools
 import os
@@ -199,3 +200,163 @@ def test_compositions_cover_every_cost_and_aggregation():
         despeckled += "despeckled" in e and bool((e["despeckled"] != e.get("unique", e["occlusion"])).any())
         assert cross_ref.params_ok(**c["opt"]["cross"]) and fs.census_ok(**c["opt"]["census"])
     assert rejected and despeckled, (rejected, despeckled)
+
+
+# ---------------------------------------------------------------------------------------------
+# the table family: what its draws hold, on the references and tests/ctx_plan_ref.py alone
+# ---------------------------------------------------------------------------------------------
+TABLE_SEEDS = range(fs.TABLE_SEEDS)
+TABLE_TIMES = {}
+BEHIND = ("subpixel", "uniqueness", "speckle", "vote", "adjust", "wmf")
+
+
+@functools.lru_cache(maxsize=None)
+def _table_case(seed):
+    return fs.table_composition(seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _table_reference(seed):
+    import oracle
+    oracle.build()
+    t = time.perf_counter()
+    with np.errstate(all="ignore"):
+        e = fs.table_reference(_table_case(seed), oracle)
+    TABLE_TIMES[seed] = time.perf_counter() - t
+    return e
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _plan(c):
+    import ctx_plan_ref
+    o = c["opt"]
+    return ctx_plan_ref.pair(fs.table_settings(c), c["w"], c["h"], c["D"], c["ch"] if c["entry"] == "rgb" else 0, c["dminl"],
+                             c["dminr"], o["volumes"], o["volumes"], False)
+
+
+def test_every_table_draw_is_the_same_twice_and_accepted_with_the_plan_the_chain_assumes():
+    for seed in TABLE_SEEDS:
+        c, again = fs.table_composition(seed), _table_case(seed)
+        assert c["text"] == again["text"] and c["opt"] == again["opt"] and c["order"] == again["order"], seed
+        assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(c["rgb"], again["rgb"])), seed
+        assert (c["w"], c["h"], c["D"]) == tuple(fs.table_setup()[k] for k in "whD")          # one context serves them all
+        assert sorted(c["order"]) == list(range(len(fs.TABLE_SETTERS)))
+        o, s = c["opt"], fs.table_settings(c)
+        assert not fs.table_refusals(c), (seed, c["text"])
+        chain, need, walker = _plan(c)
+        assert not chain.refused(), (seed, c["text"], [(k, st) for cond, k, st in chain.refusals if cond])
+        # the plan is what table_reference assumed: the stages that run, where the winners come from, which volumes exist
+        for k in ("sgm", "cgf", "cross", "so", "cscale", "perm", "bp", "pm", "subpix", "uniq", "speckle", "vote", "adjust"):
+            assert bool(need[k]) == s[k], (seed, k)
+        assert bool(need["census"]) == (o["cost"] != "reference"), seed
+        assert bool(walker) == (o["family"] in ("guided", "guided+cross_scale", "guided+permeability")), seed
+        e = _table_reference(seed)
+        assert ("aggl" in e) == ("costl" in e) == (not s["pm"]) and (e["st"] is None) == s["pm"], seed
+        assert not o["volumes"] or (need["cost"] and need["agg"] and not s["pm"]), seed
+        assert not (s["adjust"] or s["cscale"] or s["perm"]) or need["agg"], seed          # (the stages that read the volume)
+        for k, on in (("unique", s["uniq"]), ("margin", s["uniq"]), ("despeckled", s["speckle"]), ("voted", s["vote"]),
+                      ("adjusted", s["adjust"]), ("refined", bool(o["wmf"])), ("subpixl", s["subpix"] or s["pm"]),
+                      ("subpix_filled", s["subpix"] or s["pm"]), ("mi_table", o["cost"] == "mi"), ("pm_planes", s["pm"])):
+            assert (k in e) == on, (seed, k)
+    assert fs.table_composition(0, base=7)["text"] != fs.table_composition(0)["text"]
+
+
+def test_the_table_of_exclusions_is_the_plan_reference_s():
+    """every two settings on together, nothing else: TABLE_EXCLUDES names the pair exactly when ctx_plan_ref.pair has a conflict"""
+    import ctx_plan_ref
+    s0 = fs.table_setup()
+    names = [k for k in fs.table_settings(_table_case(0)) if k != "adc_colour"]
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            s = dict({k: False for k in names}, adc_colour=False, **{a: True, b: True})
+            chain, _, _ = ctx_plan_ref.pair(s, s0["w"], s0["h"], s0["D"], 3, -3, 0, False, False, False)
+            conflict = any(bool(cond) for cond, kind, _ in chain.refusals if kind == "conflict")
+            assert conflict == bool(fs.table_excluded(s)), (a, b)
+    # and what the entry and the volumes add
+    for s_on, channels, volumes, kind in ((("cgf",), 0, False, "entry"), (("adcensus", "adc_colour"), 0, False, "entry"),
+                                           (("pm",), 3, True, "pm_out")):
+        s = dict({k: False for k in names + ["adc_colour"]}, **{k: True for k in s_on})
+        chain, _, _ = ctx_plan_ref.pair(s, s0["w"], s0["h"], s0["D"], channels, -3, 0, volumes, volumes, False)
+        assert [k for cond, k, _ in chain.refusals if cond] == [kind], s_on
+
+
+def test_the_table_walk_covers_every_accepted_pair_and_every_option_both_ways():
+    cases = [_table_case(s) for s in TABLE_SEEDS]
+    pairs = {(c["opt"]["family"], c["opt"]["cost"]) for c in cases}
+    assert pairs == {(f, k) for f in fs.TABLE_FAMILIES for k in fs.TABLE_COSTS if f != "patchmatch" or k == "reference"}
+    assert len(fs.TABLE_FAMILIES) == 12
+    assert [(c["opt"]["family"], c["opt"]["cost"], c["entry"], c["opt"]["volumes"]) for c in cases] == list(fs.TABLE_WALK)
+    for k in BEHIND:
+        on = sum(bool(c["opt"][k]) for c in cases)
+        assert on >= 5 and len(cases) - on >= 5, (k, on)
+    assert len({c["opt"]["subpixel"] for c in cases}) == 3 == len({c["opt"]["wmf"] for c in cases})
+    free = [c for c in cases if not fs.FAMILIES[c["opt"]["family"]][1] and c["opt"]["cost"] != "adcensus colour"]
+    assert 3 * sum(c["entry"] == "rgb" for c in free) >= len(free)
+    assert all(c["entry"] == "rgb" for c in cases if c not in free)
+    for fam in fs.TABLE_FAMILIES:
+        mine = [c for c in cases if c["opt"]["family"] == fam]
+        if not fs.FAMILIES[fam][1]:
+            assert {c["entry"] for c in mine} == {"gray", "rgb"}, fam
+        if fam != "patchmatch":
+            assert {c["opt"]["volumes"] for c in mine} == {False, True}, fam
+    assert {c["ch"] for c in cases} == {3, 4}
+    assert 4 * sum(0 < c["opt"]["bound"] < c["D"] for c in cases) >= len(cases)
+    inits = [c["opt"]["mi"]["init"] for c in cases if c["opt"]["mi"]]
+    assert inits.count(0) >= 2 and inits.count(1) >= 2 and {c["opt"]["mi"]["iterations"] for c in cases if c["opt"]["mi"]} == {1, 2}
+    # the setters come in many orders; as applied, each of the three setters of the cost comes last of them somewhere, always
+    # the one that switches the drawn cost on
+    assert len({tuple(c["order"]) for c in cases}) == len(cases)
+    last = set()
+    for c in cases:
+        applied = fs.table_applied_order(c)
+        assert sorted(applied) == sorted(fs.TABLE_SETTERS)
+        trio = [k for k in applied if k in ("cost", "adcensus", "mi")]
+        assert trio[-1] == {"census": "cost", "reference": "cost", "mi": "mi"}.get(c["opt"]["cost"], "adcensus"), c["text"]
+        last.add(trio[-1])
+    assert last == {"cost", "adcensus", "mi"}
+
+
+def test_the_table_draws_meet_the_regimes():
+    """conditions on the inputs, each in at least two draws: the stages behind the winners have something to do, cross-scale and
+    the permeability filter move winners, an MI loop's tables differ, a cross-scale child changes its size_d between seeds"""
+    import cgf_ref
+    import vote_ref
+    met = {k: [] for k in ("vote", "adjust", "uniqueness", "speckle", "cross_scale", "permeability", "mi", "child size_d")}
+    before = None
+    for seed in TABLE_SEEDS:
+        c, e = _table_case(seed), _table_reference(seed)
+        o = c["opt"]
+        lr = e["occlusion"]
+        uq = e["unique"] if o["uniqueness"] else lr
+        kept = e["despeckled"] if o["speckle"] else uq
+        if o["vote"] and (_bits(e["voted"]) != _bits(kept)).any() and not vote_ref.valid(e["voted"], c["dminl"]).all():
+            met["vote"].append(seed)
+        if o["adjust"] and (_bits(e["before"]) != _bits(e["adjusted"])).any():
+            met["adjust"].append(seed)
+        if o["uniqueness"] and (_bits(uq) != _bits(lr)).any() and vote_ref.valid(uq, c["dminl"]).any():
+            met["uniqueness"].append(seed)
+        if o["speckle"] and (_bits(kept) != _bits(uq)).any():
+            met["speckle"].append(seed)
+        for k in ("cross_scale", "permeability"):
+            if o[k] and (cgf_ref.states(e["plainl"])["z"] != e["st"][0]["z"]).any():
+                met[k].append(seed)
+        if o["mi"] and len(e["mi_tables"]) > 1 and (e["mi_tables"][0] != e["mi_tables"][1]).any():
+            met["mi"].append(seed)
+        sizes = e.get("child_size_d")
+        if sizes and before and before[0] == seed - 1 and sizes[0] != before[1][0]:
+            met["child size_d"].append(seed)
+        before = (seed, sizes) if sizes else None
+    for k, seeds in met.items():
+        assert len(seeds) >= 2, f"{k}: met by the draws {seeds} only; " + "; ".join(_table_case(s)["text"] for s in seeds)
+
+
+def test_no_table_reference_is_slow():
+    for seed in TABLE_SEEDS:
+        _table_reference(seed)
+        assert TABLE_TIMES[seed] < 2.0, (seed, TABLE_TIMES[seed], _table_case(seed)["text"])
+    slow = sorted(TABLE_TIMES, key=TABLE_TIMES.get)[-3:]
+    print("the slowest table references:", [(s, round(TABLE_TIMES[s], 2)) for s in slow], "all:",
+          round(sum(TABLE_TIMES.values()), 1), "s")

@@ -1,8 +1,16 @@
 """Seeded fuzz of the opt-in stages' device entries against their numpy references: shape, range, parameters, image structure
 and the form of the call vary together (tests/fuzz_scenes.py draws them; tests/test_fuzz_scenes_cpu.py proves on the
 references what the committed seeds hold).  Twelve seeds per stage, one test id each, and twelve compositions of the stages
-through both front ends (the last section).  Every output is held bit for bit to the stage's reference (a NaN's payload and sign are not part of the contract), every buffer lies in a Guarded, workspaces are
-poisoned before every call and inputs must come back unchanged.  tools/fuzz_optin.py runs the same cases at other seed bases.
+through both front ends.  Every output is held bit for bit to the stage's reference (a NaN's payload and sign are not part
+of the contract), every buffer lies in a Guarded, workspaces are poisoned before every call and inputs must come back
+unchanged.  tools/fuzz_optin.py runs the same cases at other seed bases.
+
+The last section is the table family (fuzz_scenes.table_composition): one option set per seed over every row of the context's
+stage table -- twelve aggregation families x five costs, the stages behind the winners drawn on top -- through ONE smx_ctx that
+lives across all seeds and through PairPipeline, against the numpy chain of fuzz_scenes.table_reference.  The context gets its
+whole option set every time, every setter called, in an order the case draws; every plane, volume and getter of a stage that
+ran is compared, every getter of a stage that did not run has to refuse.  test_table_compositions_in_another_order then runs
+every case again on the same context in a permuted order: what an earlier option set left behind shows there.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_optin_fuzz.py -m gpu -q --durations=0
 """
@@ -375,8 +383,88 @@ def run_wmf(c):
     _eq(out.numpy(), want, "weighted median")
 
 
+def run_permeability(c):
+    """tests/test_gpu_perm.py's guarded call: every buffer in a Guarded, the workspace poisoned, inputs unchanged (the volumes
+    too unless the call filters in place), what the call must not write untouched, everything else against the reference"""
+    from test_gpu_perm import _call
+    want = fs.reference("permeability", c)["views"]
+    with _Bound(c["bound"]):
+        _call(c["costs"], c["guides"], want, c["w"], c["h"], c["D"], c["sigma"], c["views"], c["store"], c["nbr"], c["uq"],
+              ws_slices=c["c"])
+
+
+def run_bp(c):
+    """tests/test_gpu_bp.py's guarded call: the drawn views and outputs, the workspace poisoned and misaligned; an output the
+    call does not take stays untouched"""
+    from test_gpu_bp import Call as BpCall, _p as _bp_params
+    views = fs._views(c["views"])
+    want = fs.reference("bp", c)["views"]
+    call = BpCall(*(c["costs"][v] if v in views else None for v in (0, 1)), levels=c["levels"], misalign=c["misalign"])
+    absent = [k for k, on in c["outs"].items() if not on]
+    _lib.check(call.run(_bp_params(c["step"], c["trunc"], c["iterations"], c["levels"], c["data_scale"]),
+                        **{k: False for k in absent}))
+    call.check_memory()
+    for slot, v in enumerate(views):
+        for g, name in call.outs:
+            if name in absent:
+                g.check_untouched(f"d_{name} of a call without it")
+            else:
+                _eq(g.numpy()[slot], want[v][name], f"bp {name} of view {v}")
+
+
+def run_mi(c):
+    """the four device entries of the MI cost, each on guarded buffers: the histogram of the drawn map, its table, the random
+    start map, and the drawn slices and views of the cost from the drawn table"""
+    import torch
+    L = smx.lib()
+    w, h, n = c["w"], c["h"], c["w"] * c["h"]
+    want = fs.reference("mi", c)
+    imgs = [_in(c["Il"], n, misalign=1), _in(c["Ir"], n, misalign=2)]
+    disp = _in(c["disp"], n, misalign=4)
+    hist = _out(np.uint8, (256 * 256 * 4,), n)          # (the 256 x 256 uint32 counters, as bytes)
+    _lib.check(L.smx_dev_mi_histogram(imgs[0].ptr, imgs[1].ptr, disp.ptr, float(c["mark"]), hist.ptr, w, h, _stream()))
+    hist.check("d_hist")
+    H = np.ascontiguousarray(hist.numpy()).view(np.uint32).reshape(256, 256)
+    _eq(H, want["hist"], "histogram")
+    tab = _out(np.uint8, (256, 256), n)          # (the table is read 16 bytes at a time)
+    _lib.check(L.smx_dev_mi_table(H.ctypes.data, tab.ptr, _stream()))
+    torch.cuda.synchronize()
+    tab.check("d_table")
+    _eq(tab.numpy(), want["learned"], "table")
+    rmap = _out(F32, (h, w), n, misalign=8)
+    _lib.check(L.smx_dev_mi_random_map(rmap.ptr, w, h, c["dminl"], c["D"], c["map_seed"], _stream()))
+    rmap.check("d_map")
+    _eq(rmap.numpy(), want["random_map"], "random map")
+    tab.load(want["table"])
+    out = _cost_outputs(c, n)
+    _lib.check(L.smx_dev_mi_cost_pair(tab.ptr, imgs[0].ptr, imgs[1].ptr, _ptr(out[0]), _ptr(out[1]), w, h, c["dminl"],
+                                      c["dminr"], c["s0"], c["s1"], _stream()))
+    _check_costs(c, out, want["cost"], "mi")
+    for g, name in ((tab, "d_table"), (imgs[0], "d_img_l"), (imgs[1], "d_img_r"), (disp, "d_map")):
+        g.check_unchanged(name)
+
+
+def run_patchmatch(c):
+    """tests/test_gpu_patchmatch.py's guarded call: the search with its four outputs, or the cost of the drawn planes alone
+    (planes unchanged, disp and label untouched); the workspace poisoned and misaligned"""
+    from test_gpu_patchmatch import Call as PmCall
+    want = fs.reference("patchmatch", c)
+    pm = _struct(_lib.default_pm_params(), **c["pm"])
+    search = c["entry"] == "search"
+    call = PmCall(c["left"], c["right"], c["D"], c["dminl"], c["dminr"], c["misalign"], planes=None if search else c["planes"])
+    _lib.check(call.search(pm) if search else call.cost(pm))
+    call.check_memory(planes_in=not search)
+    got = call.results()
+    for k in ("planes", "cost", "disp", "label") if search else ("cost",):
+        a, b = np.ascontiguousarray(got[k], F32).view(np.uint32), np.ascontiguousarray(want[k], F32).view(np.uint32)
+        assert a.shape == b.shape and np.array_equal(a, b), f"patchmatch {k}: {int((a != b).sum())} values differ"
+    if not search:
+        for k in ("disp", "label"):
+            call.out[k].check_untouched(f"d_{k} of the plane cost")
+
+
 RUN = dict(census=run_census, adcensus=run_adcensus, cgf=run_cgf, cross=run_cross, sgm=run_sgm, wta=run_wta, speckle=run_speckle,
-           wmf=run_wmf)
+           wmf=run_wmf, permeability=run_permeability, bp=run_bp, mi=run_mi, patchmatch=run_patchmatch)
 
 
 def run(stage, seed, base=None, orc=None):
@@ -425,6 +513,26 @@ def test_speckle_fuzz(seed):
 @pytest.mark.parametrize("seed", SEEDS)
 def test_weighted_median_fuzz(seed):
     run("wmf", seed)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_permeability_fuzz(seed):
+    run("permeability", seed)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_bp_fuzz(seed):
+    run("bp", seed)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_mi_fuzz(seed):
+    run("mi", seed)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_patchmatch_fuzz(seed):
+    run("patchmatch", seed)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -541,3 +649,241 @@ def run_composition(seed, ctx, orc, base=None):
 def test_composition_fuzz(orc, context, seed):
     with np.errstate(all="ignore"):
         run_composition(seed, context, orc)
+
+
+# ---------------------------------------------------------------------------------------------
+# the table family: one option set per seed over every row of the context's stage table (fuzz_scenes.table_composition)
+# through ONE smx_ctx and through PairPipeline, against the numpy chain; then every case again on the same context in
+# another order
+# ---------------------------------------------------------------------------------------------
+TABLE_SEEDS = range(fs.TABLE_SEEDS)
+E_ARG = -1          # SMX_E_ARG
+
+
+def _struct(p, **kw):
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _table_params(c):
+    """the parameter structs of every stage of the case, those of the stages that are off included (None: nothing drawn)"""
+    o = c["opt"]
+    p = smx.default_params()
+    p.radius, p.eps = c["radius"], c["eps"]
+    vote = o["vote"]
+    P = dict(p=p, cp=_cp(**o["census"]),
+             ap=_ap(int(o["cost"] == "adcensus colour"), o["census"]["rx"], o["census"]["ry"], o["census"]["th"],
+                    o["adcensus"]["lambda_census"], o["adcensus"]["lambda_ad"], o["adcensus"]["scale"]),
+             mp=_struct(_lib.default_mi_params(), **o["mi"]) if o["mi"] else None,
+             sp=_sgm_params(**o["sgm"]), xp=_cross_params(**o["cross"]),
+             so=_struct(_lib.default_scanline_params(), **o["scanline"]),
+             bp=_struct(_lib.default_bp_params(), **o["bp"]), pm=_struct(_lib.default_pm_params(), **o["patchmatch"]),
+             cs=_struct(_lib.default_cscale_params(), **o["cross_scale"]) if o["cross_scale"] else None,
+             perm=_struct(_lib.default_perm_params(), **o["permeability"]) if o["permeability"] else None,
+             spk=_speckle_params(*o["speckle"]) if o["speckle"] else None,
+             ratio=fs.ratio_of(o["uniqueness"]) if o["uniqueness"] else None,
+             vp=_struct(_lib.default_vote_params(), tau_s=vote["params"]["tau_s"], tau_h_pct=vote["params"]["tau_h_pct"],
+                        iterations=vote["params"]["iterations"], interpolate=vote["params"]["interpolate_"]) if vote else None,
+             va=_cross_params(iterations=1, **vote["arms"]) if vote else None,
+             adj=_struct(_lib.default_adjust_params(), **o["adjust"]) if o["adjust"] else None)
+    return P
+
+
+def _set_the_whole_option_set(ctx, c, P):
+    """every setter of the context, the stages that are off included, in the order the case draws
+    (fuzz_scenes.table_applied_order)"""
+    L, o = smx.lib(), c["opt"]
+    agg = fs.FAMILIES[o["family"]][0]
+    ref_or_null = lambda on, p: C.byref(p) if on else None
+    cost = o["cost"]
+    calls = {
+        "cost": lambda: L.smx_ctx_set_cost(ctx, 1 if cost == "census" else 0, ref_or_null(cost == "census", P["cp"])),
+        "adcensus": lambda: L.smx_ctx_set_adcensus(ctx, ref_or_null(cost.startswith("adcensus"), P["ap"])),
+        "mi": lambda: L.smx_ctx_set_mi(ctx, ref_or_null(cost == "mi", P["mp"])),
+        "aggregation": lambda: L.smx_ctx_set_aggregation(ctx, 1 if agg == "sgm" else 0, ref_or_null(agg == "sgm", P["sp"])),
+        "guidance": lambda: L.smx_ctx_set_guidance(ctx, int(fs.FAMILIES[o["family"]][1])),
+        "cross": lambda: L.smx_ctx_set_cross(ctx, ref_or_null(agg in ("cross", "cross-scanline"), P["xp"])),
+        "scanline": lambda: L.smx_ctx_set_scanline(ctx, ref_or_null(agg in ("scanline", "cross-scanline"), P["so"])),
+        "bp": lambda: L.smx_ctx_set_bp(ctx, ref_or_null(agg == "bp", P["bp"])),
+        "patchmatch": lambda: L.smx_ctx_set_patchmatch(ctx, ref_or_null(agg == "patchmatch", P["pm"])),
+        "cross_scale": lambda: L.smx_ctx_set_cross_scale(ctx, ref_or_null(P["cs"] is not None, P["cs"])),
+        "permeability": lambda: L.smx_ctx_set_permeability(ctx, ref_or_null(P["perm"] is not None, P["perm"])),
+        "subpixel": lambda: L.smx_ctx_set_subpixel(ctx, subpix_ref.MODES[o["subpixel"]] if o["subpixel"] else 0),
+        "uniqueness": lambda: L.smx_ctx_set_uniqueness(ctx, P["ratio"] or 0.0),
+        "speckle": lambda: L.smx_ctx_set_speckle(ctx, ref_or_null(P["spk"] is not None, P["spk"])),
+        "vote": lambda: L.smx_ctx_set_vote(ctx, ref_or_null(P["vp"] is not None, P["vp"]),
+                                           ref_or_null(P["va"] is not None, P["va"])),
+        "adjust": lambda: L.smx_ctx_set_adjust(ctx, ref_or_null(P["adj"] is not None, P["adj"])),
+    }
+    assert sorted(calls) == sorted(fs.TABLE_SETTERS)
+    order = fs.table_applied_order(c)
+    for k in order:
+        _lib.check(calls[k]())
+    return order
+
+
+TABLE_PLANES = ("best_l", "best_r", "dmap_l", "dmap_r", "occlusion", "filled")
+TABLE_VOLUMES = ("agg_l", "agg_r", "cost_l", "cost_r")
+
+
+def _through_the_table_context(ctx, c, want, P):
+    L, o = smx.lib(), c["opt"]
+    h, w, D = c["h"], c["w"], c["D"]
+    pm = fs.FAMILIES[o["family"]][0] == "patchmatch"
+    _set_the_whole_option_set(ctx, c, P)
+    bufs = {k: np.empty((h, w), F32) for k in TABLE_PLANES}
+    if o["volumes"]:
+        bufs.update({k: np.empty((D, h, w), F32) for k in TABLE_VOLUMES})
+    out = _lib.PairOut(**{k: v.ctypes.data for k, v in bufs.items()})
+    imgs = c["rgb"] if c["entry"] == "rgb" else (want["grayl"], want["grayr"])
+    before = [i.copy() for i in imgs]
+    with _Bound(o["bound"]):
+        if c["entry"] == "rgb":
+            rc = L.smx_ctx_stereo_pair_rgb(ctx, imgs[0].ctypes.data, imgs[1].ctypes.data, c["ch"], c["dminl"], c["dminr"],
+                                           C.byref(out))
+        else:
+            rc = L.smx_ctx_stereo_pair(ctx, imgs[0].ctypes.data, imgs[1].ctypes.data, c["dminl"], c["dminr"], C.byref(out))
+    _lib.check(rc)
+    for a, b in zip(imgs, before):
+        assert a.tobytes() == b.tobytes(), "the context changed a host image"
+    for k, v in bufs.items():
+        _eq(v, want[k.replace("_", "")], "context " + k)
+    plane = lambda: np.empty((h, w), F32)
+    got = dict(bufs)
+
+    def getter(ran, entry, names, arrays, *extra):
+        """the maps of a stage that ran against the chain; SMX_E_ARG from the getter of a stage that did not"""
+        rc = getattr(L, entry)(ctx, *(a.ctypes.data for a in arrays), *extra)
+        if not ran:
+            assert rc == E_ARG, f"{entry} after a pair without its stage: {rc}"
+            return
+        _lib.check(rc)
+        for k, a in zip(names, arrays):
+            _eq(a, want[k], f"context {entry} {k}")
+            got[k] = a
+
+    getter(bool(o["subpixel"]), "smx_ctx_subpixel_maps", ("subpixl", "subpixr", "subpix_filled"), [plane() for _ in range(3)])
+    getter(bool(o["uniqueness"]), "smx_ctx_uniqueness_map", ("unique", "margin"), [plane(), plane()])
+    getter(bool(o["speckle"]), "smx_ctx_speckle_map", ("despeckled",), [plane()])
+    getter(bool(o["vote"]), "smx_ctx_vote_map", ("voted",), [plane()])
+    getter(o["cost"] == "mi", "smx_ctx_mi_table", ("mi_table", "mi_hist"),
+           [np.empty((256, 256), np.uint8), np.empty((256, 256), np.uint32)])
+    if pm:
+        maps = [np.empty((3, h, w), F32), np.empty((3, h, w), F32), plane(), plane(), plane()]
+        _lib.check(L.smx_ctx_patchmatch_maps(ctx, *(m.ctypes.data for m in maps)))
+        _eq(np.stack(maps[:2]), want["pm_planes"], "context smx_ctx_patchmatch_maps planes")
+        for k, a in zip(("subpixl", "subpixr", "subpix_filled"), maps[2:]):
+            _eq(a, want[k], f"context smx_ctx_patchmatch_maps {k}")
+            got[k] = a
+        got["pm_planes"] = np.stack(maps[:2])
+    else:
+        assert L.smx_ctx_patchmatch_maps(ctx, None, None, None, None, None) == E_ARG
+    return got
+
+
+def _through_the_table_pipeline(c, want, P):
+    from stereo_matching_cuda_amd.device import PairPipeline
+    o = c["opt"]
+    agg, cgf, _ = fs.FAMILIES[o["family"]]
+    pm = agg == "patchmatch"
+    kw = dict(dminl=c["dminl"], dminr=c["dminr"], params=P["p"], want_agg=not pm, slices_in_flight=o["sif"],
+              cost={"reference": None, "census": "census", "mi": "mi"}.get(o["cost"], "adcensus"), census_params=P["cp"],
+              adcensus_params=P["ap"], aggregation=None if agg == "guided" else agg, guidance="rgb" if cgf else None,
+              sgm_params=P["sp"], cross_params=P["xp"], subpixel=o["subpixel"], uniqueness=P["ratio"], speckle=P["spk"],
+              wmf=o["wmf"],
+              vote=P["vp"], vote_arms=P["va"], adjust=P["adj"], cross_scale=P["cs"], permeability=P["perm"])
+    for name, on, p in (("mi_params", o["cost"] == "mi", P["mp"]), ("bp_params", agg == "bp", P["bp"]),
+                        ("scanline_params", agg in ("scanline", "cross-scanline"), P["so"]), ("pm_params", pm, P["pm"])):
+        if on:
+            kw[name] = p
+    pipe = PairPipeline(c["w"], c["h"], c["D"], **kw)
+    colour = fs.table_guides(c, "pipeline")["came"]
+    rgb = dict(rgb_l=_t(c["rgb"][0]), rgb_r=_t(c["rgb"][1])) if colour else {}
+    ins = [_t(want["grayl"]), _t(want["grayr"])] + list(rgb.values())
+    keep = [t.clone() for t in ins]
+    pipe.run(ins[0], ins[1], **rgb)
+    got = pipe.results()
+    import torch
+    for a, b in zip(ins, keep):
+        assert torch.equal(a, b), "the pipeline changed an input"
+    keys = ["bestl", "bestr", "dmapl", "dmapr", "occlusion", "filled"] + ["aggl", "aggr"] * (not pm)
+    keys += ["unique", "margin"] * bool(o["uniqueness"]) + ["despeckled"] * bool(o["speckle"]) + ["voted"] * bool(o["vote"])
+    keys += ["adjusted"] * bool(o["adjust"]) + ["refined"] * bool(o["wmf"]) + ["pm_planes"] * pm
+    keys += ["subpixl", "subpixr", "subpix_filled"] * bool(o["subpixel"] or pm)
+    for k in keys:
+        _eq(got[k], want[k], "pipeline " + k)
+    if not pm:
+        _eq(pipe.keys.cpu().numpy(), want["keys"], "pipeline keys")
+    if o["cost"] == "mi":
+        _eq(pipe.mi_hist.cpu().numpy().view(np.uint32).reshape(256, 256), want["mi_hist"], "pipeline mi_hist")
+        _eq(pipe.mi_table.cpu().numpy().reshape(256, 256), want["mi_table"], "pipeline mi_table")
+    return got
+
+
+def create_table_context(base=None):
+    s = fs.table_setup(base)
+    p = smx.default_params()
+    p.radius, p.eps = s["radius"], s["eps"]
+    ctx = C.c_void_p()
+    _lib.check(smx.lib().smx_create(C.byref(p), s["w"], s["h"], s["D"], C.byref(ctx)))
+    return ctx
+
+
+@pytest.fixture(scope="module")
+def table_context():
+    """one context for every table composition and for the second pass over them: its buffers only grow, its cross-scale
+    children live from pair to pair, and a setting left over from whichever case ran before cannot hide"""
+    ctx = create_table_context()
+    yield ctx
+    smx.lib().smx_destroy(ctx)
+
+
+_TABLE = {}          # (base, seed) -> (the case, the chain, what the context gave the first time)
+
+
+def _table_case(seed, orc, base=None):
+    if (base, seed) not in _TABLE:
+        c = fs.table_composition(seed, base)
+        _TABLE[base, seed] = [c, fs.table_reference(c, orc), None]
+    return _TABLE[base, seed]
+
+
+def run_table_composition(seed, ctx, orc, base=None):
+    entry = _table_case(seed, orc, base)
+    c, want = entry[:2]
+    P = _table_params(c)
+    # (PairPipeline's vote takes the colour image only where its aggregation took the colour pair: fuzz_scenes.table_guides)
+    differs = bool(c["opt"]["vote"]) and fs.table_guides(c, "pipeline")["vote"] != fs.table_guides(c)["vote"]
+    pipe = _through_the_table_pipeline(c, fs.table_behind(c, orc, dict(want), "pipeline") if differs else want, P)
+    got = _through_the_table_context(ctx, c, want, P)
+    entry[2] = got
+    names = dict(best_l="bestl", best_r="bestr", dmap_l="dmapl", dmap_r="dmapr", agg_l="aggl", agg_r="aggr")
+    behind_the_vote = ("voted", "filled", "subpix_filled") if differs else ()
+    for k, v in got.items():            # and the two front ends against each other
+        if names.get(k, k) in pipe and k not in behind_the_vote:
+            _eq(v, pipe[names.get(k, k)], f"context against pipeline {k}")
+    return c
+
+
+def run_table_again(seed, ctx, orc, base=None):
+    """the case once more on the context as it stands: the chain's bits, which are the bits of the first time"""
+    c, want, first = _table_case(seed, orc, base)
+    got = _through_the_table_context(ctx, c, want, _table_params(c))
+    for k, v in (first or {}).items():
+        _eq(got[k], v, f"{k} of the second pass against the first")
+
+
+@pytest.mark.parametrize("seed", TABLE_SEEDS)
+def test_table_composition_fuzz(orc, table_context, seed):
+    with np.errstate(all="ignore"):
+        run_table_composition(seed, table_context, orc)
+
+
+def test_table_compositions_in_another_order(orc, table_context):
+    with np.errstate(all="ignore"):
+        for seed in fs.table_order():
+            try:
+                run_table_again(seed, table_context, orc)
+            except AssertionError as e:
+                raise AssertionError(f"seed {seed} ({fs.table_composition(seed)['text']}): {e}") from e

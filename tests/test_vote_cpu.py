@@ -211,6 +211,27 @@ def test_the_directions_are_the_sixteen():
     assert ang == sorted(ang)                                            # one turn, from +x towards +y
 
 
+def test_the_ray_tables_are_the_walk_of_the_definition():
+    """vote_ref._nearest_voters (every pixel's ray at once, a step at a time) against the walk of the definition, pixel by pixel
+    and direction by direction: a voter mask that is dense, sparse, empty and full, on shapes down to one row and one column"""
+    rng = np.random.default_rng(16)
+    for h, w, share in ((1, 1, 0.5), (1, 23, 0.3), (17, 1, 0.3), (9, 14, 0.0), (9, 14, 1.0), (23, 31, 0.02), (31, 23, 0.5),
+                        (40, 57, 0.1)):
+        v = rng.random((h, w)) < share
+        near = ref._nearest_voters(v)
+        assert len(near) == len(ref.DIRECTIONS)
+        for (dx, dy), (qy, qx) in zip(ref.DIRECTIONS, near):
+            for y in range(h):
+                for x in range(w):
+                    py, px, want = y + dy, x + dx, (-1, -1)
+                    while 0 <= py < h and 0 <= px < w:
+                        if v[py, px]:
+                            want = (py, px)
+                            break
+                        py, px = py + dy, px + dx
+                    assert (int(qy[y, x]), int(qx[y, x])) == want, (h, w, share, dx, dy, y, x)
+
+
 def test_the_first_voter_on_a_ray_is_the_candidate():
     d = np.full((9, 9), INV)
     d[4, 5] = D                     # valid, not a voter: passed over

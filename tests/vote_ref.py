@@ -109,6 +109,28 @@ def mismatch(disp_r, y, x, w, dmin, size_d, d_lr):
         return bool((np.abs(d.astype(F32) + np.asarray(disp_r, F32)[y, x + d]) <= F32(d_lr)).any())
 
 
+def _nearest_voters(v):
+    """per direction of DIRECTIONS: (qy, qx) of the first voter on the ray that leaves every pixel in that direction, -1 where
+    the ray leaves the image first.  Every pixel's ray at once, a step at a time: the walk of the definition, not per pixel."""
+    h, w = v.shape
+    ys, xs = np.mgrid[0:h, 0:w]
+    out = []
+    for dx, dy in DIRECTIONS:
+        qy, qx = np.full((h, w), -1, np.int64), np.full((h, w), -1, np.int64)
+        walking = np.ones((h, w), bool)
+        for t in range(1, max(h, w) + 1):
+            py, px = ys + t * dy, xs + t * dx
+            inside = walking & (py >= 0) & (py < h) & (px >= 0) & (px < w)
+            if not inside.any():
+                break
+            hit = inside.copy()
+            hit[inside] = v[py[inside], px[inside]]
+            qy[hit], qx[hit] = py[hit], px[hit]
+            walking = inside & ~hit
+        out.append((qy, qx))
+    return out
+
+
 def interpolate(disp, guide, disp_r, dmin, size_d, d_lr, stats=None):
     """one pass over the map as a snapshot"""
     d = np.ascontiguousarray(disp, F32)
@@ -117,15 +139,10 @@ def interpolate(disp, guide, disp_r, dmin, size_d, d_lr, stats=None):
     out = d.copy()
     v, _ = voters(d, dmin, size_d)
     dr = None if disp_r is None else np.ascontiguousarray(disp_r, F32)
-    for y, x in zip(*np.nonzero(~valid(d, dmin))):
-        cand = []
-        for dx, dy in DIRECTIONS:
-            qy, qx = y + dy, x + dx
-            while 0 <= qy < h and 0 <= qx < w:
-                if v[qy, qx]:
-                    cand.append((qy, qx))
-                    break
-                qy, qx = qy + dy, qx + dx
+    todo = np.nonzero(~valid(d, dmin))
+    near = _nearest_voters(v) if todo[0].size else ()
+    for y, x in zip(*todo):
+        cand = [(int(qy[y, x]), int(qx[y, x])) for qy, qx in near if qy[y, x] >= 0]
         mm = mismatch(dr, y, x, w, dmin, size_d, d_lr)
         if stats is not None:
             k = "no_candidate" if not cand else "mismatch" if mm else "occlusion"
