@@ -7,6 +7,7 @@ Layout
             occlusion.cuh, ...) calling the C-ABI
   stages    numpy front end with the reference's stage names (host pointers in/out)
   device    device-resident pipeline on torch-allocated HBM buffers and HIP streams
+  pipeline_plan  what that pipeline refuses, owns and sizes: one table of the opt-in stages, host arithmetic only
   sharded   disparity-slice sharding over ranks + packed-key min all-reduce (RCCL / gloo)
   synth     seeded synthetic stereo pairs
 

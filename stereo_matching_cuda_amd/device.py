@@ -9,6 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .pipeline_plan import BUFFERS, LEVEL_SHARES, plan_pipeline
 
 
 def _dp(t):
@@ -140,327 +141,40 @@ class PairPipeline:
         guided filter only (either guide; the reference, census and AD-Census costs): aggregation= and cross_scale= raise
         ValueError, and so does a slice sub-range.  Its workspace (self.perm_ws, at most ~1 GiB: the pass goes in chunks of
         slices) is not counted in max_ws_bytes.  With None nothing is allocated or launched."""
-        if permeability is not None and permeability is not True and not isinstance(permeability, _lib.PermParams):
-            raise ValueError(f"permeability must be None, True or PermParams, not {permeability!r}")
-        if isinstance(permeability, _lib.PermParams) and not (0.0 < permeability.sigma < float("inf")):
-            raise ValueError("permeability needs a finite sigma > 0")
-        if permeability is not None:
-            if aggregation is not None:
-                raise ValueError(f"the permeability filter runs behind the guided filter: not with aggregation={aggregation!r}")
-            if cross_scale is not None:
-                raise ValueError("the permeability filter is not built behind cross-scale aggregation: not with cross_scale=")
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("the permeability filter runs over whole volumes: no slice sub-range")
-            want_agg = True
-        pm = aggregation == "patchmatch"
-        if pm_params is not None and not pm:
-            raise ValueError("pm_params belongs to aggregation='patchmatch'")
-        if pm:
-            if pm_params is not None and not isinstance(pm_params, _lib.PMParams):
-                raise ValueError(f"pm_params must be None or PMParams, not {pm_params!r}")
-            q = pm_params
-            if q is not None and not (0 <= q.radius <= 17 and 0.0 < q.gamma < float("inf") and 1 <= q.iterations <= 16 and
-                                      0.0 <= q.max_slope <= 8.0):
-                raise ValueError("pm_params needs 0 <= radius <= 17, a finite gamma > 0, 1 <= iterations <= 16 and "
-                                 "0 <= max_slope <= 8")
-            for name, value in (("cost", cost), ("guidance", guidance), ("cross_scale", cross_scale), ("adjust", adjust),
-                                ("uniqueness", uniqueness), ("subpixel", subpixel), ("want_agg", want_agg or None)):
-                if value is not None:
-                    raise ValueError(f"PatchMatch stereo keeps no cost volume and its planes are sub-pixel already: not with {name}=")
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("PatchMatch stereo searches a pixel's whole disparity range: no slice sub-range")
-        if cross_scale is not None and cross_scale is not True and not isinstance(cross_scale, _lib.CScaleParams):
-            raise ValueError(f"cross_scale must be None, True or CScaleParams, not {cross_scale!r}")
-        if isinstance(cross_scale, _lib.CScaleParams) and not (1 <= cross_scale.scales <= 5 and
-                                                               0.0 <= cross_scale.lambda_ < float("inf")):
-            raise ValueError("cross_scale needs 1 <= scales <= 5 and a finite lambda >= 0")
-        if cross_scale is not None:
-            if aggregation is not None:
-                raise ValueError(f"cross-scale aggregation belongs to the guided filter: not with aggregation={aggregation!r} "
-                                 "(integer volumes and fixed penalties do not rescale across levels)")
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("cross-scale aggregation combines whole volumes: no slice sub-range")
-            want_agg = True
-        if adjust is not None and adjust is not True and not isinstance(adjust, _lib.AdjustParams):
-            raise ValueError(f"adjust must be None, True or AdjustParams, not {adjust!r}")
-        if isinstance(adjust, _lib.AdjustParams) and not (1 <= adjust.tau_e <= 512 and adjust.vertical in (0, 1) and
-                                                          1 <= adjust.iterations <= 8):
-            raise ValueError("adjust needs 1 <= tau_e <= 512, vertical 0 or 1 and 1 <= iterations <= 8")
-        if adjust is not None:
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("the depth-discontinuity adjustment reads a pixel's whole aggregated column: no slice sub-range")
-            if not 1 <= int(size_d) <= 512:
-                raise ValueError("the depth-discontinuity adjustment takes 1 .. 512 labels")
-        if guidance not in (None, "rgb"):
-            raise ValueError(f"guidance must be None or 'rgb', not {guidance!r}")
-        if guidance and aggregation:
-            raise ValueError(f"colour guidance belongs to the guided filter: not with aggregation={aggregation!r}")
-        if uniqueness is not None:
-            uniqueness = float(uniqueness)
-            if not (0.0 < uniqueness < float("inf")):
-                raise ValueError(f"uniqueness must be None or a finite ratio > 0, not {uniqueness!r}")
-            # (the state belongs to the keys of ONE volume: after a key reduction across D-shards it would be tested against
-            # winners it does not belong to)
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("the uniqueness state does not combine across D-shards: no slice sub-range")
-        if aggregation not in (None, "sgm", "bp", "cross", "scanline", "cross-scanline", "patchmatch"):
-            raise ValueError(f"aggregation must be None, 'sgm', 'bp', 'cross', 'scanline', 'cross-scanline' or 'patchmatch', not {aggregation!r}")
-        sgm, cross = aggregation == "sgm", aggregation in ("cross", "cross-scanline")
-        bp = aggregation == "bp"
-        if bp_params is not None and not bp:
-            raise ValueError("bp_params belongs to aggregation='bp'")
-        so = aggregation in ("scanline", "cross-scanline")
-        if scanline_params is not None and not so:
-            raise ValueError("scanline_params belongs to aggregation='scanline' / 'cross-scanline'")
-        if cost not in (None, "census", "adcensus", "mi"):
-            raise ValueError(f"cost must be None, 'census', 'adcensus' or 'mi', not {cost!r}")
-        if mi_params is not None and cost != "mi":
-            raise ValueError("mi_params belongs to cost='mi'")
-        if cost == "mi":
-            if aggregation == "patchmatch":
-                raise ValueError("PatchMatch stereo keeps no cost volume: the mutual-information cost does not run with it")
-            if int(s_begin) != 0 or (s_end is not None and int(s_end) != int(size_d)):
-                raise ValueError("the mutual-information cost learns its table from a pair's whole disparity range: no slice sub-range")
-        if wmf not in (None, "occluded", "all"):
-            raise ValueError(f"wmf must be None, 'occluded' or 'all', not {wmf!r}")
-        if subpixel is not None and subpixel not in _lib.SUBPIX_MODES:
-            raise ValueError(f"subpixel must be None, 'parabola' or 'equiangular', not {subpixel!r}")
-        if speckle is not None and speckle is not True and not isinstance(speckle, _lib.SpeckleParams):
-            raise ValueError(f"speckle must be None, True or SpeckleParams, not {speckle!r}")
-        if vote is not None and vote is not True and not isinstance(vote, _lib.VoteParams):
-            raise ValueError(f"vote must be None, True or VoteParams, not {vote!r}")
-        if vote_arms is not None and not isinstance(vote_arms, _lib.CrossParams):
-            raise ValueError(f"vote_arms must be None or CrossParams, not {vote_arms!r}")
-        if vote_arms is not None and vote is None:
-            raise ValueError("vote_arms belongs to vote=: region voting is off")
-        self.lib = _lib.lib()
-        self.w, self.h, self.size_d = int(w), int(h), int(size_d)
-        self.n = self.w * self.h
-        self.dminl = -(size_d - 1) if dminl is None else int(dminl)
-        self.dminr = int(dminr)
-        self.s_begin = int(s_begin)
-        self.s_end = self.size_d if s_end is None else int(s_end)
-        self.device = torch.device(device)
-        self.params = params if params is not None else _lib.default_params()
-        self.aggregation = aggregation
-        self.adjust = self.adjusted = self.adjust_ws = None
-        self.adjust_ws_bytes = 0
-        if adjust is not None:
-            self.adjust_ws_bytes = int(self.lib.smx_adjust_workspace_bytes(self.w, self.h))
-            if self.adjust_ws_bytes == 0:
-                raise ValueError(f"the depth-discontinuity adjustment does not take {self.w} x {self.h} (w*h < 2^31)")
-            held = 2 * self.size_d * self.n * 4 + self.adjust_ws_bytes
-            if held > max_ws_bytes:
-                raise ValueError(f"the depth-discontinuity adjustment needs {held} bytes for the two aggregated volumes and its "
-                                 f"workspace: more than max_ws_bytes = {max_ws_bytes}")
-            max_ws_bytes -= held                # what is left for the aggregation
-            want_agg = True
-            self.adjust = _lib.default_adjust_params() if adjust is True else adjust
-        self.sgm_params = self.sgm_cost = self.sgm_ws = None
-        self.sgm_ws_bytes = 0
-        if sgm:
-            if self.s_begin != 0 or self.s_end != self.size_d:
-                raise ValueError("semi-global matching needs a pixel's whole disparity range: no slice sub-range")
-            self.sgm_params = sgm_params if sgm_params is not None else _lib.default_sgm_params()
-            self.sgm_ws_bytes = int(self.lib.smx_sgm_workspace_bytes(self.w, self.h, self.size_d, 2))
-            if self.sgm_ws_bytes == 0:
-                raise ValueError(f"semi-global matching does not take {self.w} x {self.h} x {self.size_d} "
-                                 "(w*h < 2^31, size_d <= 256)")
-            if self.sgm_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
-                raise ValueError(f"semi-global matching needs {self.sgm_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
-                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
-        self.bp_params = self.bp_cost = self.bp_ws = None
-        self.bp_ws_bytes = 0
-        if bp:
-            if self.s_begin != 0 or self.s_end != self.size_d:
-                raise ValueError("belief propagation needs a pixel's whole disparity range: no slice sub-range")
-            self.bp_params = bp_params if bp_params is not None else _lib.default_bp_params()
-            q = self.bp_params
-            if not (0 <= q.step <= 4095 and 0 <= q.trunc <= 4095 and 0 <= q.iterations <= 64 and 1 <= q.levels <= 8 and
-                    0 < q.data_scale < float("inf")):
-                raise ValueError("belief propagation needs 0 <= step, trunc <= 4095, 0 <= iterations <= 64, 1 <= levels <= 8 and a "
-                                 "finite data_scale > 0")
-            self.bp_ws_bytes = int(self.lib.smx_bp_workspace_bytes(self.w, self.h, self.size_d, q.levels, 2))
-            if self.bp_ws_bytes == 0:
-                raise ValueError(f"belief propagation does not take {self.w} x {self.h} x {self.size_d} "
-                                 "(w*h < 2^31, size_d <= 256)")
-            if self.bp_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
-                raise ValueError(f"belief propagation needs {self.bp_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
-                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
-        self.so_params = self.so_cost = self.so_ws = self._so_chunk = None
-        self.so_ws_bytes = 0
-        if so:
-            if self.s_begin != 0 or self.s_end != self.size_d:
-                raise ValueError("the scan-line optimiser needs a pixel's whole disparity range: no slice sub-range")
-            self.so_params = scanline_params if scanline_params is not None else _lib.default_scanline_params()
-            self.so_ws_bytes = int(self.lib.smx_scanline_workspace_bytes(self.w, self.h, self.size_d, 2))
-            if self.so_ws_bytes == 0:
-                raise ValueError(f"the scan-line optimiser does not take {self.w} x {self.h} x {self.size_d} "
-                                 "(w*h < 2^31, size_d <= 256)")
-            if self.so_ws_bytes + 2 * self.size_d * self.n * 4 > max_ws_bytes:
-                raise ValueError(f"the scan-line optimiser needs {self.so_ws_bytes + 2 * self.size_d * self.n * 4} bytes for "
-                                 f"its workspace and the two whole cost volumes: more than max_ws_bytes = {max_ws_bytes}")
-            max_ws_bytes -= self.so_ws_bytes + 2 * self.size_d * self.n * 4       # what is left for the chain's cross stage
-        local = max(1, self.s_end - self.s_begin)
-        sif = local if slices_in_flight is None else max(1, min(local, int(slices_in_flight)))
-        # workspace of the path these parameters run (smx_agg_workspace_bytes_for follows the library's choice: a fused
-        # walker, one plane per slice in flight, or the multi-kernel path); a forced multi-kernel path
-        # (smx_set_agg_path(1)) needs the parameter-agnostic bound
-        need = (lambda n: self.lib.smx_agg_workspace_bytes(self.w, self.h, n)) if multi_kernel else \
-               (lambda n: self.lib.smx_agg_workspace_bytes_for(C.byref(self.params), self.w, self.h, n))
-        self.guidance = guidance
-        self.cgf_ws = self.cgf_cost = None
-        self.cgf_ws_bytes = 0
-        if guidance:
-            if self.lib.smx_cgf_workspace_bytes(self.w, self.h, 1, 2) == 0:
-                raise ValueError(f"the colour-guided filter does not take {self.w} x {self.h} (h <= 65535, w*h < 2^31)")
-            # both views in one workspace, and the reference cost goes through a chunk buffer like the census cost
-            need = lambda n: (self.lib.smx_cgf_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4)) // 2
-        self.cross_params = self.cross_ws = self.cross_cost = None
-        self.cross_ws_bytes = 0
-        if cross:
-            self.cross_params = cross_params if cross_params is not None else _lib.default_cross_params()
-            if self.lib.smx_cross_workspace_bytes(self.w, self.h, 1, 2) == 0:
-                raise ValueError(f"cross-based aggregation does not take {self.w} x {self.h} (w*h < 2^31)")
-            # (the chain also holds a chunk of q on its way into the whole volumes)
-            need = lambda n: (self.lib.smx_cross_workspace_bytes(self.w, self.h, n, 2) + (0 if cost else 2 * n * self.n * 4) +
-                              (2 * n * self.n * 4 if so and n < local else 0)) // 2
-        self.cost = cost
-        self.adcensus_params = self.adcensus_table = self._rgb = None
-        if cost == "adcensus":
-            self.adcensus_params = adcensus_params if adcensus_params is not None else _lib.default_adcensus_params()
-            self.census_params = self.adcensus_params.census          # (the codes are those of its census part)
-        elif cost == "mi":
-            self.census_params = None
-        else:
-            self.census_params = (census_params if census_params is not None else _lib.default_census_params()) if cost else None
-        self.mi_params = self.mi_hist = self.mi_table = None
-        if cost == "mi":
-            self.mi_params = mi_params if mi_params is not None else _lib.default_mi_params()
-            if not (1 <= self.mi_params.iterations <= 16 and self.mi_params.init in _lib.MI_INITS.values()):
-                raise ValueError("the mutual-information cost needs 1 <= iterations <= 16 and init 0 (random) or 1 (reference)")
-        chunk_cost = (lambda n: 2 * n * self.n * 4) if cost else (lambda n: 0)     # both views' cost slices of a chunk
-        while sif > 1 and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
-            sif = (sif + 1) // 2
-        if so and cross and 2 * need(sif) + chunk_cost(sif) > max_ws_bytes:
-            raise ValueError("the chain of cross-based aggregation and the scan-line optimiser does not fit max_ws_bytes")
-        self.slices_in_flight = sif
-        # pair calls (both views per launch) need twice the single-view workspace (SGM does not use it)
-        self.ws_bytes = 0 if aggregation or guidance else 2 * int(need(sif))
-        dev = self.device
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        # keys[0] = left view, keys[1] = right view: one buffer so the shard merge is ONE all-reduce
-        self.keys = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev)
-        f = dict(dtype=torch.float32, device=dev)
-        self.best = torch.empty((2, self.h, self.w), **f)
-        self.dmap = torch.empty((2, self.h, self.w), **f)
-        self.mean = (torch.zeros if aggregation or guidance else torch.empty)((2, self.h, self.w), dtype=torch.uint8, device=dev)
-        self.occlusion = torch.empty((self.h, self.w), **f)
-        self.filled = torch.empty((self.h, self.w), **f)
-        self.agg = (torch.empty((2, local, self.h, self.w), **f) if want_agg else None)
-        self.wmf = wmf
-        self.wmf_params = (wmf_params if wmf_params is not None else _lib.default_wmf_params()) if wmf else None
-        self.refined = torch.empty((self.h, self.w), **f) if wmf else None
+        # (the constructor's own arguments, by name: everything but the device is the plan's)
+        args = {k: v for k, v in locals().items() if k not in ("self", "device")}
+        self._build(plan_pipeline(_lib.lib(), **args), device)
+
+    @classmethod
+    def _from_plan(cls, plan, device):
+        self = cls.__new__(cls)
+        self._build(plan, device)
+        return self
+
+    def _build(self, plan, device):
+        """The pipeline of a plan (pipeline_plan.plan_pipeline): its options and byte counts onto the attributes, its buffers
+        allocated, the AD-Census table uploaded, and the cross-scale levels built from its sub-plans."""
+        self.lib, self.plan, self.device = _lib.lib(), plan, torch.device(device)
+        for name, value in {**plan.options, **plan.bytes}.items():
+            setattr(self, name, value)
         self._guide = None            # left image of the last aggregation: the guide of the refinement
-        self.subpixel = subpixel
-        self.nbr = torch.empty((2, 3, self.h, self.w), **f) if subpixel else None
-        self.sub = torch.empty((2, self.h, self.w), **f) if subpixel else None
-        self.sub_filled = torch.empty((self.h, self.w), **f) if subpixel else None
-        self.uniqueness = uniqueness
-        self.uq = torch.empty((2, 3, self.h, self.w), **f) if uniqueness else None
-        self.unique = torch.empty((self.h, self.w), **f) if uniqueness else None
-        self.margin = torch.empty((self.h, self.w), **f) if uniqueness else None
-        self.speckle = _lib.default_speckle_params() if speckle is True else speckle
-        self.despeckled = torch.empty((self.h, self.w), **f) if self.speckle else None
-        self.speckle_ws_bytes = int(self.lib.smx_speckle_workspace_bytes(self.w, self.h)) if self.speckle else 0
-        self.speckle_ws = torch.empty(self.speckle_ws_bytes, dtype=torch.uint8, device=dev) if self.speckle else None
-        self.vote = _lib.default_vote_params() if vote is True else vote
-        self.vote_arms = self.voted = self.vote_arms_plane = self.vote_ws = None
-        self.vote_ws_bytes = 0
-        if self.vote:
-            self.vote_arms = _lib.CrossParams.from_buffer_copy(vote_arms) if vote_arms is not None else _lib.default_cross_params()
-            self.vote_arms.iterations = 1              # (not read by the arms)
-            self.vote_ws_bytes = int(self.lib.smx_vote_workspace_bytes(self.w, self.h))
-            if self.vote_ws_bytes == 0 or not 1 <= self.size_d <= 512:
-                raise ValueError(f"region voting does not take {self.w} x {self.h} x {self.size_d} (w*h < 2^31, size_d <= 512)")
-            self.voted = torch.empty((self.h, self.w), **f)
-            self.vote_arms_plane = torch.empty((self.h, self.w), dtype=torch.int32, device=dev)
-            self.vote_ws = torch.empty(self.vote_ws_bytes, dtype=torch.uint8, device=dev)
-        if self.adjust:
-            self.adjusted = torch.empty((self.h, self.w), **f)
-            self.adjust_ws = torch.empty(self.adjust_ws_bytes, dtype=torch.uint8, device=dev)
-        self.codes = torch.empty((2, self.h, self.w), dtype=torch.int64, device=dev) if cost in ("census", "adcensus") else None
-        if cost == "mi":
-            self.mi_hist = torch.empty((_lib.MI_LEVELS, _lib.MI_LEVELS), dtype=torch.int32, device=dev)
-            self.mi_table = torch.empty((_lib.MI_LEVELS, _lib.MI_LEVELS), dtype=torch.uint8, device=dev)
-        self.census_cost = torch.empty((2, sif, self.h, self.w), **f) if cost and not sgm and not bp and aggregation != "scanline" else None
-        if cost == "adcensus":
-            self.adcensus_table = torch.empty(_lib.ADCENSUS_TABLE_FLOATS, **f)
+        self._rgb = None
+        new = lambda shape, dtype, zeroed=False: (torch.zeros if zeroed else torch.empty)(shape, dtype=getattr(torch, dtype),
+                                                                                         device=self.device)
+        for name in BUFFERS:
+            setattr(self, name, None)
+        for name, shape, dtype, zeroed in plan.buffers:
+            setattr(self, name, new(shape, dtype, zeroed))
+        if self.adcensus_table is not None:
             with self._on_device():     # a set-up call: it waits for its copy, and stays outside any graph capture
                 _lib.check(self.lib.smx_dev_adcensus_tables(C.byref(self.adcensus_params), _dp(self.adcensus_table),
                                                             self._stream()))
-        if sgm:
-            self.sgm_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
-            self.sgm_ws = torch.empty(self.sgm_ws_bytes, dtype=torch.uint8, device=dev)
-        if bp:
-            self.bp_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
-            self.bp_ws = torch.empty(self.bp_ws_bytes, dtype=torch.uint8, device=dev)
-        if so:
-            self.so_cost = torch.empty((2, self.size_d, self.h, self.w), **f)
-            self.so_ws = torch.empty(self.so_ws_bytes, dtype=torch.uint8, device=dev)
-            self._so_chunk = torch.empty((2, sif, self.h, self.w), **f) if cross and sif < local else None
-        if guidance:
-            self.cgf_ws_bytes = int(self.lib.smx_cgf_workspace_bytes(self.w, self.h, sif, 2))
-            self.cgf_ws = torch.empty(self.cgf_ws_bytes, dtype=torch.uint8, device=dev)
-            self.cgf_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
-        if cross:
-            self.cross_ws_bytes = int(self.lib.smx_cross_workspace_bytes(self.w, self.h, sif, 2))
-            self.cross_ws = torch.empty(self.cross_ws_bytes, dtype=torch.uint8, device=dev)
-            self.cross_cost = None if cost else torch.empty((2, sif, self.h, self.w), **f)
-        self.pm_params = self.pm_planes = self.pm_disp = self.pm_ws = None
-        self.pm_ws_bytes = 0
-        if pm:
-            self.pm_params = pm_params if pm_params is not None else _lib.default_pm_params()
-            self.pm_ws_bytes = int(self.lib.smx_pm_workspace_bytes(self.w, self.h))
-            if self.pm_ws_bytes == 0 or not (1 <= self.size_d <= 1 << 20 and abs(self.dminl) <= 1 << 20 and abs(self.dminr) <= 1 << 20):
-                raise ValueError(f"PatchMatch stereo does not take {self.w} x {self.h} x {self.size_d} from {self.dminl} / "
-                                 f"{self.dminr} (w < 2^24, w*h < 2^31, size_d and |dmin| <= 2^20)")
-            if self.pm_ws_bytes + 8 * self.n * 4 > max_ws_bytes:
-                raise ValueError(f"PatchMatch stereo needs {self.pm_ws_bytes + 8 * self.n * 4} bytes for its planes and workspace: "
-                                 f"more than max_ws_bytes = {max_ws_bytes}")
-            self.pm_planes = torch.empty((2, 3, self.h, self.w), **f)
-            self.pm_disp = torch.empty((2, self.h, self.w), **f)
-            self.pm_ws = torch.empty(self.pm_ws_bytes, dtype=torch.uint8, device=dev)
-            self.sub_filled = torch.empty((self.h, self.w), **f)
-        self.permeability = _lib.default_perm_params() if permeability is True else permeability
-        self.perm_ws, self.perm_ws_bytes = None, 0
-        if self.permeability:
-            if self.lib.smx_perm_workspace_bytes(self.w, self.h, self.size_d, 2) == 0:
-                raise ValueError(f"the permeability filter does not take {self.w} x {self.h} x {self.size_d} "
-                                 "(w*h < 2^31, size_d <= 2^20)")
-            # both views: two weight planes and a scratch plane per slice in flight, every slice at once within ~1 GiB
-            per = 2 * self.n * 4
-            self.perm_ws_bytes = per * (2 + min(self.size_d, max(1, (1 << 30) // per - 2)))
-            self.perm_ws = torch.empty(self.perm_ws_bytes, dtype=torch.uint8, device=dev)
-        self.cross_scale = _lib.default_cscale_params() if cross_scale is True else cross_scale
-        self.cs_levels, self.cs_gray, self.cs_rgb = [], [], []
-        if self.cross_scale:
-            colour = bool(guidance) or (cost == "adcensus" and bool(self.adcensus_params.colour))
-            for s in range(1, self.cross_scale.scales):
-                ws, hs, dl, sl = _lib.cscale_level(self.w, self.h, self.dminl, self.size_d, s)
-                _, _, dr, sr = _lib.cscale_level(self.w, self.h, self.dminr, self.size_d, s)
-                if ws < 2:
-                    raise ValueError(f"cross-scale level {s} of a {self.w} x {self.h} pair is narrower than 2 pixels")
-                self.cs_levels.append(PairPipeline(ws, hs, max(sl, sr), dminl=dl, dminr=dr, device=device, want_agg=True,
-                                                   params=self.params, max_ws_bytes=max_ws_bytes, multi_kernel=multi_kernel,
-                                                   cost=cost, census_params=census_params, guidance=guidance,
-                                                   adcensus_params=adcensus_params))
-                self.cs_levels[-1].mi_table = self.mi_table      # (the levels take the table of level 0)
-                self.cs_gray.append(torch.empty((2, hs, ws), dtype=torch.uint8, device=dev))
-                self.cs_rgb.append(torch.empty(2 * hs * ws * 4, dtype=torch.uint8, device=dev) if colour else None)
-        # a chunk's aggregated slices of both views, copied into self.agg (whose views are `local` slices apart)
-        self._agg_chunk = torch.empty((2, sif, self.h, self.w), **f) \
-            if (cost or guidance or cross) and want_agg and sif < local and not sgm and not bp and not so else None
+        self.cs_levels = [PairPipeline._from_plan(sub, device) for _, sub, _, _ in plan.levels]
+        for k in self.cs_levels:        # (the levels take the table of level 0)
+            for name in LEVEL_SHARES:
+                setattr(k, name, getattr(self, name))
+        self.cs_gray = [new(gray, "uint8") for _, _, gray, _ in plan.levels]
+        self.cs_rgb = [new(rgb, "uint8") if rgb else None for _, _, _, rgb in plan.levels]
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -480,10 +194,17 @@ class PairPipeline:
         if self.permeability:
             self._permeability(gray_l, gray_r)
 
+    def _guides(self, gray_l, gray_r, colour=True):
+        """(guide_l, guide_r, channels): the colour pair of this aggregation if it took one (and `colour` lets it guide), else the
+        gray pair."""
+        if colour and self._rgb is not None:
+            return self._rgb[0], self._rgb[1], int(self._rgb[0].shape[2])
+        return gray_l, gray_r, 1
+
     def _permeability(self, gray_l, gray_r):
         """smx_dev_permeability_wta_pair in place over self.agg: the filtered volumes, and self.keys (self.nbr, self.uq) their
         winners (and states).  Guide: the colour pair of this aggregation under guidance="rgb", else the gray images."""
-        gl, gr, ch = (self._rgb[0], self._rgb[1], int(self._rgb[0].shape[2])) if self.guidance else (gray_l, gray_r, 1)
+        gl, gr, ch = self._guides(gray_l, gray_r, colour=bool(self.guidance))     # (the colour images of a cost are no guide)
         with self._on_device():
             _lib.check(self.lib.smx_dev_permeability_wta_pair(C.byref(self.permeability), _dp(self.agg[0]), _dp(self.agg[1]),
                                                               _dp(gl), _dp(gr), ch, self.w, self.h, self.dminl, self.dminr,
@@ -654,7 +375,7 @@ class PairPipeline:
     def _aggregate_cross(self, gray_l, gray_r, rgb_l, rgb_r, cost_l=None, cost_r=None):
         """The cross-based flow: that of the colour guide with smx_dev_cross_wta_pair; the guide is the colour pair where it is
         given, else the gray pair."""
-        gl, gr, ch = (rgb_l, rgb_r, int(rgb_l.shape[2])) if rgb_l is not None else (gray_l, gray_r, 1)
+        gl, gr, ch = self._guides(gray_l, gray_r)
         chain = self.aggregation == "cross-scanline"
         self._aggregate_chunks(gray_l, gray_r, cost_l, cost_r, self.cross_cost, self.lib.smx_dev_cross_wta_pair,
                                C.byref(self.cross_params), gl, gr, ch, self.cross_ws, self.cross_ws_bytes,
@@ -666,24 +387,33 @@ class PairPipeline:
     def _aggregate_scanline(self, gray_l, gray_r, rgb_l, rgb_r, cost_l=None, cost_r=None):
         """The scan-line flow: both whole cost volumes (the caller's, census / AD-Census, or the reference's cost), as for SGM,
         and the one smx_dev_scanline_wta_pair call; the guide is the colour pair where it is given, else the gray pair."""
+        cl, cr = self._whole_costs(gray_l, gray_r, cost_l, cost_r, self.so_cost)
+        self._scanline(*self._guides(gray_l, gray_r), cl, cr)
+
+    def _check_costs(self, cost_l, cost_r):
         if (cost_l is None) != (cost_r is None):
             raise ValueError("pass both cost volumes or neither")
         if self.cost and cost_l is not None:
             raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
+
+    def _whole_costs(self, gray_l, gray_r, cost_l, cost_r, own):
+        """Both whole cost volumes of an aggregation that reads them in one call: the caller's, or built into `own` (2, size_d,
+        h, w) -- the codes and then the cost of this pipeline over 0 .. size_d, or the reference's cost.  -> (left, right)."""
+        self._check_costs(cost_l, cost_r)
         self._guide = gray_l
+        if cost_l is not None:
+            return cost_l, cost_r
         L, w, h = self.lib, self.w, self.h
-        cl, cr = (cost_l, cost_r) if cost_l is not None else (self.so_cost[0], self.so_cost[1])
         with self._on_device():
             st = self._stream()
             if self.cost:
                 self._census_codes(gray_l, gray_r, st)
-                self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
-            elif cost_l is None:
+                self._code_cost(gray_l, gray_r, own[0], own[1], 0, self.size_d, st)
+            else:
                 P = C.byref(self.params)
-                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
-                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
-        gl, gr, ch = (rgb_l, rgb_r, int(rgb_l.shape[2])) if rgb_l is not None else (gray_l, gray_r, 1)
-        self._scanline(gl, gr, ch, cl, cr)
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(own[0]), w, w, h, self.dminl, 0, self.size_d, st))
+                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(own[1]), w, w, h, self.dminr, 0, self.size_d, st))
+        return own[0], own[1]
 
     def _scanline(self, guide_l, guide_r, ch, cl, cr):
         with self._on_device():
@@ -699,10 +429,7 @@ class PairPipeline:
         Fresh keys, then per chunk of `slices_in_flight` slices the cost slices of both views (the caller's volumes, census /
         AD-Census into self.census_cost, or the reference's cost into own_cost) and `entry` -- smx_dev_cgf_wta_pair or
         smx_dev_cross_wta_pair -- from them, which accumulates into the keys (and the neighbour / second-best states)."""
-        if (cost_l is None) != (cost_r is None):
-            raise ValueError("pass both cost volumes or neither")
-        if self.cost and cost_l is not None:
-            raise ValueError("a census pipeline builds its own cost volumes: pass the images only")
+        self._check_costs(cost_l, cost_r)
         self._guide = gray_l
         L, w, h = self.lib, self.w, self.h
         self.init_keys()
@@ -745,21 +472,10 @@ class PairPipeline:
         """The SGM flow: both whole cost volumes (the caller's, census, or the reference's cost) and the one
         smx_dev_sgm_wta_pair call, which writes the keys (and S, the neighbour state) of both views.  aggregation="bp" runs the
         same flow with smx_dev_bp_wta_pair in that call's place."""
-        if (cost_l is None) != (cost_r is None):
-            raise ValueError("pass both cost volumes or neither")
-        self._guide = gray_l
         L, w, h = self.lib, self.w, self.h
-        whole = self.bp_cost if self.aggregation == "bp" else self.sgm_cost
-        cl, cr = (cost_l, cost_r) if cost_l is not None else (whole[0], whole[1])
+        cl, cr = self._whole_costs(gray_l, gray_r, cost_l, cost_r, self.bp_cost if self.aggregation == "bp" else self.sgm_cost)
         with self._on_device():
             st = self._stream()
-            if self.cost:
-                self._census_codes(gray_l, gray_r, st)
-                self._code_cost(gray_l, gray_r, cl, cr, 0, self.size_d, st)
-            elif cost_l is None:
-                P = C.byref(self.params)
-                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_l), _dp(gray_r), _dp(cl), w, w, h, self.dminl, 0, self.size_d, st))
-                _lib.check(L.smx_dev_cost_volume(P, _dp(gray_r), _dp(gray_l), _dp(cr), w, w, h, self.dminr, 0, self.size_d, st))
             if self.aggregation == "bp":
                 _lib.check(L.smx_dev_bp_wta_pair(C.byref(self.bp_params), _dp(cl), _dp(cr), w, h, self.size_d, _dp(self.keys),
                                                  _dp(self.agg), _dp(self.nbr), _dp(self.uq) if self.uniqueness else None,
@@ -865,12 +581,16 @@ class PairPipeline:
             if self.aggregation == "patchmatch":
                 self.occlusion.copy_(self.dmap[0])
                 _lib.check(L.smx_dev_detect_occlusion(P, _dp(self.occlusion), _dp(self.dmap[1]), self.dminl - 100, self.w, self.h, st))
-                self.filled.copy_(self.occlusion)
-                _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+                self._fill_from(self.occlusion, st)
             else:
                 _lib.check(L.smx_dev_finish_pair(P, _dp(self.keys), self.w, self.h, self.dminl, self.dminr,
                                                  self.dminl - 100, float(self.dminl), _dp(self.best), _dp(self.dmap),
                                                  _dp(self.occlusion), _dp(self.filled), st))
+
+    def _fill_from(self, src, st):
+        """self.filled = the fill of the map `src` (main.cu:153-155)."""
+        self.filled.copy_(src)
+        _lib.check(self.lib.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
 
     def _finish_stages(self):
         """The opt-in stages of finish() behind the LR check and the fill."""
@@ -908,8 +628,7 @@ class PairPipeline:
                                             _dp(self.unique), _dp(self.margin), self.w, self.h, float(self.dminl),
                                             float(self.dminl - 100), st))
             if not self.speckle:
-                self.filled.copy_(self.unique)
-                _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+                self._fill_from(self.unique, st)
 
     def despeckle(self):
         """self.despeckled = the LR-checked (and, with uniqueness on, uniqueness-filtered) left map without its small connected
@@ -920,8 +639,7 @@ class PairPipeline:
             _lib.check(L.smx_dev_speckle_filter(C.byref(self.speckle), _dp(src), _dp(self.despeckled), self.w,
                                                 self.h, float(self.dminl), float(self.dminl - 100), _dp(self.speckle_ws),
                                                 self.speckle_ws_bytes, st))
-            self.filled.copy_(self.despeckled)
-            _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+            self._fill_from(self.despeckled, st)
 
     def region_vote(self):
         """self.voted = the last of the LR-checked / uniqueness-filtered / despeckled left maps with its outliers voted on by
@@ -929,7 +647,7 @@ class PairPipeline:
         aggregate(), then smx_dev_region_vote), and self.filled rewritten as the fill of that map."""
         if self._guide is None:
             raise RuntimeError("region_vote() needs the left image: run an aggregation first")
-        guide, ch = (self._rgb[0], int(self._rgb[0].shape[2])) if self._rgb is not None else (self._guide, 1)
+        guide, _, ch = self._guides(self._guide, None)
         with self._on_device():
             L, st = self.lib, self._stream()
             _lib.check(L.smx_dev_cross_arms(C.byref(self.vote_arms), _dp(guide), None, ch, self.w, self.h, _dp(self.vote_arms_plane),
@@ -937,8 +655,7 @@ class PairPipeline:
             _lib.check(L.smx_dev_region_vote(C.byref(self.vote), _dp(self.vote_arms_plane), _dp(guide), ch, _dp(self._kept()),
                                              _dp(self.dmap[1]), _dp(self.voted), self.w, self.h, self.dminl, self.size_d,
                                              int(self.params.d_lr), _dp(self.vote_ws), self.vote_ws_bytes, st))
-            self.filled.copy_(self.voted)
-            _lib.check(L.smx_dev_fill_occlusion(_dp(self.filled), self.w, self.h, float(self.dminl), st))
+            self._fill_from(self.voted, st)
 
     def _kept(self):
         """The map whose validity test tells which pixels the fill replaced."""
@@ -1041,7 +758,7 @@ class PairPipeline:
         torch.cuda.synchronize(self.device)
         for k in self.cs_levels:
             k.check_status()
-        if self.aggregation or self.guidance:            # (the SGM, colour-guided and cross-based kernels wait for nothing)
+        if self.plan.no_walker:                          # (the SGM, colour-guided and cross-based kernels wait for nothing)
             return
         with self._on_device():
             _lib.check(self.lib.smx_dev_agg_status(_dp(self.ws)))

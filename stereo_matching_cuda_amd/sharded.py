@@ -43,43 +43,20 @@ def merge_keys_host(key_arrays):
 class ShardedPair:
     """D-sharded stereo pair: local aggregation of this rank's slices, ONE all-reduce of both
     views' keys, then decode + LR check + filling (replicated on every rank: n-sized, microseconds).
-    The census and AD-Census matching costs (PairPipeline(cost="census" / "adcensus")) are not part of the sharded driver:
-    cost=... raises ValueError.  Neither is speckle removal (PairPipeline(speckle=...)): speckle=... raises ValueError, and so
-    do region voting (PairPipeline(vote=...)) and the depth-discontinuity adjustment (PairPipeline(adjust=...)).  Nor is semi-global matching, which needs a pixel's whole disparity range on
-    one rank: aggregation="sgm" and aggregation="bp" raise ValueError, and so do the scan-line optimiser's "scanline" / "cross-scanline"."""
+    Of PairPipeline's opt-in stages the driver takes those whose row of pipeline_plan.STAGES says `sharded`: the colour guide,
+    the uniqueness test, the sub-pixel fit (world == 1), the weighted median and want_agg.  Every other one raises ValueError: the
+    matching costs (cost=...), every aggregation= (semi-global matching, belief propagation, the scan-line optimiser and
+    PatchMatch stereo need a pixel's whole disparity range on one rank), cross_scale=, permeability= and adjust= (whole
+    aggregated volumes), speckle= and vote=."""
 
     def __init__(self, w, h, size_d, rank=0, world=1, group=None, **kw):
         from .device import PairPipeline
-        if world > 1 and kw.get("subpixel") is not None:
-            # the neighbours of a winner at a shard boundary were aggregated on another rank
-            raise ValueError("subpixel needs the whole slice range on one rank (world == 1)")
-        if kw.get("cost") is not None:
-            raise ValueError("the census and AD-Census costs are not part of the sharded driver: use "
-                             f"PairPipeline(cost={kw['cost']!r})")
-        if kw.get("speckle") is not None:
-            raise ValueError("speckle removal is not part of the sharded driver: use PairPipeline(speckle=...)")
-        if kw.get("vote") is not None or kw.get("vote_arms") is not None:
-            raise ValueError("region voting is not part of the sharded driver: use PairPipeline(vote=...)")
-        if kw.get("adjust") is not None:
-            # (a D-shard holds no whole aggregated volume)
-            raise ValueError("the depth-discontinuity adjustment is not part of the sharded driver: use PairPipeline(adjust=...)")
-        if kw.get("permeability") is not None:
-            # (the filter runs over whole aggregated volumes)
-            raise ValueError("the permeability filter is not part of the sharded driver: use PairPipeline(permeability=...)")
-        if kw.get("cross_scale") is not None:
-            # (the combination reads whole volumes of every level)
-            raise ValueError("cross-scale aggregation is not part of the sharded driver: use PairPipeline(cross_scale=...)")
-        if kw.get("aggregation") in ("scanline", "cross-scanline") or kw.get("scanline_params") is not None:
-            raise ValueError("the scan-line optimiser is not part of the sharded driver: use "
-                             f"PairPipeline(aggregation={kw.get('aggregation')!r})")
-        if kw.get("aggregation") == "patchmatch" or kw.get("pm_params") is not None:
-            # (there are no slices to shard: the search has no cost volume)
-            raise ValueError("PatchMatch stereo is not part of the sharded driver: use PairPipeline(aggregation='patchmatch')")
-        if kw.get("aggregation") == "bp" or kw.get("bp_params") is not None:
-            # (a message needs every label of a pixel: there are no slices to shard)
-            raise ValueError("belief propagation is not part of the sharded driver: use PairPipeline(aggregation='bp')")
-        if kw.get("aggregation") is not None:
-            raise ValueError("semi-global matching is not part of the sharded driver: use PairPipeline(aggregation='sgm')")
+        from .pipeline_plan import sharded_refusal
+        # (what needs whole volumes, a pixel's whole disparity range or a stage of its own on one rank is no part of this
+        # driver: the rows of pipeline_plan.STAGES say which)
+        refusal = sharded_refusal(world, kw)
+        if refusal:
+            raise ValueError(refusal)
         self.rank, self.world, self.group = rank, world, group
         s0, s1 = shard_range(size_d, rank, world)
         self.pipe = PairPipeline(w, h, size_d, s_begin=s0, s_end=s1, **kw)
