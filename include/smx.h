@@ -860,6 +860,61 @@ int smx_ctx_set_mi(smx_ctx* ctx, const smx_mi_params* p);
 int smx_ctx_mi_table(smx_ctx* ctx, uint8_t* table, uint32_t* hist);
 
 /* ------------------------------------------------------------------------------------
+ * ZNCC window matching cost: zero-mean normalised cross-correlation (not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The reference's cost and the AD term need equal gray values, census keeps no magnitudes, mutual information learns ONE global
+ * relation between the gray values of the two views.  Zero-mean normalised cross-correlation over a window (among the core
+ * costs of Hirschmueller & Scharstein, PAMI 2009) is invariant to a LOCAL affine change a*I + b, a > 0 -- vignetting, an
+ * exposure gradient, a light that moved between the exposures -- and keeps the magnitudes inside the window.
+ * tests/zncc_ref.py is this definition in numpy; moments and volumes equal it bit for bit.
+ *   window  (2 rx + 1) x (2 ry + 1), N pixels, 1 <= rx, ry <= 4 (N <= 81); images replicate-clamped as for census:
+ *         A_ext[y][x] = A[clamp(y, 0, h-1)][clamp(x, 0, w-1)].  An image smaller than the window is legal.
+ *   moments of an image I at (y, x), exact integers: S = sum of I_ext over the window, Q = sum of I_ext^2,
+ *         V = N Q - S^2, 0 <= V <= 81 * 81 * 65025 < 2^31.  One 8-byte word a pixel: S | (uint64_t)V << 32.
+ *   cost  of view v, slice z, A the view's own image and B the other's: d = dmin_v + z, xx = x + d.
+ *         xx < 0 or xx >= w:                  cost = 255.0f
+ *         else P = sum over the window of A_ext[y+dy][x+dx] * B_ext[y+dy][xx+dx]      (each image clamped on its own)
+ *              num = N P - S_A(y, x) S_B(y, xx)   (|num| < 2^31),   Va = V_A(y, x), Vb = V_B(y, xx)
+ *         Va == 0 or Vb == 0 (a flat window): cost = 128.0f
+ *         else, in f32, every operation rounded on its own (no contraction), int -> float to nearest-even:
+ *              nf = (float)|num|;  s = min((nf * nf) / ((float)Va * (float)Vb), 1.0f)
+ *              cost = rintf(num >= 0 ? 127.5f * (1.0f - s) : 127.5f * (1.0f + s))                       (ties to even)
+ *         That is 127.5 (1 - rho |rho|) with rho the ZNCC: the signed square is monotone in rho and needs no square root, only
+ *         the correctly rounded f32 multiply and divide.  Costs are integers 0 .. 255: the value set of the comb walker's
+ *         exactness argument (no fall-back) and of SGM's clamp.
+ *   Layout [z][y][x], slice placement and [s_begin, s_end) as for smx_dev_census_cost_pair. */
+typedef struct smx_zncc_params {
+    int rx, ry;       /* window radii, default 3, 3; 1 .. 4 each */
+} smx_zncc_params;
+void smx_default_zncc_params(smx_zncc_params* p);
+/* N of the window, or SMX_E_ARG (negative) for invalid parameters.  Host only: works without a GPU. */
+int smx_zncc_window(const smx_zncc_params* p);
+/* Columns and rows of a workgroup's tile of smx_dev_zncc_cost_pair (for tests that put sizes at a tile seam). */
+int smx_zncc_geometry(int* cols, int* rows);
+/* The moments of `nimages` planes of w x h that lie back to back at d_img into d_mom (nimages * w * h words, 8-byte aligned):
+ * one launch, no allocation, no synchronisation (graph-capturable).  w, h >= 1. */
+int smx_dev_zncc_moments(const smx_zncc_params* p, const uint8_t* d_img, uint64_t* d_mom, int w, int h, int nimages,
+                         void* stream);
+/* Slices [s_begin, s_end) of the left volume (labels dminl + z) into d_cost_l and of the right volume (labels dminr + z) into
+ * d_cost_r from d_mom ([2][h][w]: the left image's moments, then the right one's, of the same parameters) and the two images,
+ * both in one launch; either cost pointer may be NULL (not both).  No allocation, no synchronisation (graph-capturable). */
+int smx_dev_zncc_cost_pair(const smx_zncc_params* p, const uint64_t* d_mom, const uint8_t* d_img_l, const uint8_t* d_img_r,
+                           float* d_cost_l, float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end,
+                           void* stream);
+/* Host pointers, synchronous; mirrors smx_census_cost: the volume of i1 against i2, size_d*w*h floats, labels dmin + z. */
+int smx_zncc_cost(const smx_zncc_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h, int size_d,
+                  int dmin);
+
+#define SMX_COST_ZNCC 3   /* what smx_ctx_set_zncc selects; smx_ctx_set_cost does not take it */
+/* The ZNCC cost of this context.  Non-NULL switches it on and replaces whatever smx_ctx_set_cost, smx_ctx_set_adcensus or
+ * smx_ctx_set_mi chose; NULL switches it off again (the reference's cost), and so does a later call of one of those setters.
+ * A pair with it on runs the moments of both images once, then cost chunk -> aggregation in every flow the census cost runs in
+ * (not with PatchMatch stereo); cost_l / cost_r of smx_pair_out receive the ZNCC volumes.  smx_ctx_stereo_pair_async returns
+ * SMX_E_ARG while it is on.  The moments live in the buffer of the census codes, allocated on first use. */
+int smx_ctx_set_zncc(smx_ctx* ctx, const smx_zncc_params* p);
+
+/* ------------------------------------------------------------------------------------
  * Cross-based aggregation: colour-adaptive support regions (not a stage of the reference; opt-in)
  * ---------------------------------------------------------------------------------- */
 

@@ -61,6 +61,11 @@ MI_LEVELS = 256                       # smx.h SMX_MI_LEVELS
 MI_INITS = {"random": 0, "reference": 1}
 
 
+class ZnccParams(C.Structure):
+    """smx_zncc_params: the ZNCC window matching cost (not a stage of the reference)."""
+    _fields_ = [("rx", C.c_int), ("ry", C.c_int)]
+
+
 class SpeckleParams(C.Structure):
     """smx_speckle_params: the connected-component speckle filter (not a stage of the reference)."""
     _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
@@ -138,6 +143,7 @@ _WP = C.POINTER(WmfParams)
 _CP = C.POINTER(CensusParams)
 _AP = C.POINTER(AdCensusParams)
 _IP = C.POINTER(MiParams)
+_ZP = C.POINTER(ZnccParams)
 _SP = C.POINTER(SpeckleParams)
 _GP = C.POINTER(SgmParams)
 _BP = C.POINTER(BpParams)
@@ -231,6 +237,13 @@ SIGNATURES = {
     "smx_mi_cost": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
     "smx_ctx_set_mi": (_i, [_vp, _IP]),
     "smx_ctx_mi_table": (_i, [_vp, _vp, _vp]),
+    "smx_default_zncc_params": (None, [_ZP]),
+    "smx_zncc_window": (_i, [_ZP]),
+    "smx_zncc_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "smx_dev_zncc_moments": (_i, [_ZP, _vp, _vp, _i, _i, _i, _vp]),
+    "smx_dev_zncc_cost_pair": (_i, [_ZP, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "smx_zncc_cost": (_i, [_ZP, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "smx_ctx_set_zncc": (_i, [_vp, _ZP]),
     "smx_default_speckle_params": (None, [_SP]),
     "smx_speckle_workspace_bytes": (_sz, [_i, _i]),
     "smx_dev_speckle_filter": (_i, [_SP, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
@@ -398,6 +411,12 @@ def default_census_params():
 def default_mi_params():
     p = MiParams()
     lib().smx_default_mi_params(C.byref(p))
+    return p
+
+
+def default_zncc_params():
+    p = ZnccParams()
+    lib().smx_default_zncc_params(C.byref(p))
     return p
 
 

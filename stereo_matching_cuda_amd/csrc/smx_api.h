@@ -44,6 +44,8 @@ bool wmf_params_ok(const smx_wmf_params* p);
 // (the shape limits, shape_ok and the *_SHAPES texts: smx_ctx_plan.h)
 bool census_params_ok(const smx_census_params* p);
 constexpr const char* CENSUS_RANGES = "census needs 1 <= rx <= 4, 1 <= ry <= 3, th >= 1";
+bool zncc_params_ok(const smx_zncc_params* p);
+constexpr const char* ZNCC_RANGES = "ZNCC needs 1 <= rx <= 4 and 1 <= ry <= 4";
 bool adcensus_params_ok(const smx_adcensus_params* p);
 constexpr const char* ADCENSUS_RANGES = "needs a valid census window, 0 < lambda <= 1e6, 2^-20 <= scale <= 2^20 and colour 0 or 1";
 bool speckle_params_ok(const smx_speckle_params* p);

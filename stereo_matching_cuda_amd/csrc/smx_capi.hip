@@ -102,6 +102,7 @@ bool wmf_params_ok(const smx_wmf_params* p) {
            p->sigma_c > 0;
 }
 bool census_params_ok(const smx_census_params* p) { return p && p->rx >= 1 && p->rx <= 4 && p->ry >= 1 && p->ry <= 3 && p->th >= 1; }
+bool zncc_params_ok(const smx_zncc_params* p) { return p && p->rx >= 1 && p->rx <= 4 && p->ry >= 1 && p->ry <= 4; }
 bool adcensus_params_ok(const smx_adcensus_params* p) {
     return p && census_params_ok(&p->census) && isfinite(p->lambda_census) && p->lambda_census > 0 && p->lambda_census <= 1e6 &&
            isfinite(p->lambda_ad) && p->lambda_ad > 0 && p->lambda_ad <= 1e6 && isfinite(p->scale) && p->scale >= 0x1p-20 &&
@@ -689,6 +690,39 @@ int smx_dev_mi_cost_pair(const uint8_t* d_table, const uint8_t* d_img_l, const u
     SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
     return launch_mi_cost_pair(d_table, d_img_l, d_img_r, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end,
                                (hipStream_t)stream);
+}
+
+// ---- ZNCC window matching cost (not in the reference; smx_zncc.hip) -------------------------------------
+void smx_default_zncc_params(smx_zncc_params* p) {
+    if (!p) return;
+    p->rx = 3; p->ry = 3;
+}
+
+int smx_zncc_window(const smx_zncc_params* p) {
+    SMX_ARG(zncc_params_ok(p));
+    return (2 * p->rx + 1) * (2 * p->ry + 1);
+}
+
+int smx_zncc_geometry(int* cols, int* rows) {
+    SMX_ARG(cols && rows);
+    zncc_geometry(cols, rows);
+    return SMX_OK;
+}
+
+int smx_dev_zncc_moments(const smx_zncc_params* p, const uint8_t* d_img, uint64_t* d_mom, int w, int h, int nimages, void* stream) {
+    if (!zncc_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_zncc_moments: %s", ZNCC_RANGES);
+    SMX_ARG(d_img && d_mom && ((uintptr_t)d_mom & 7) == 0 && w >= 1 && h >= 1 && nimages >= 1);
+    return launch_zncc_moments(p->rx, p->ry, d_img, d_mom, w, h, nimages, (hipStream_t)stream);
+}
+
+int smx_dev_zncc_cost_pair(const smx_zncc_params* p, const uint64_t* d_mom, const uint8_t* d_img_l, const uint8_t* d_img_r,
+                           float* d_cost_l, float* d_cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end,
+                           void* stream) {
+    if (!zncc_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_zncc_cost_pair: %s", ZNCC_RANGES);
+    SMX_ARG(d_mom && ((uintptr_t)d_mom & 7) == 0 && d_img_l && d_img_r && (d_cost_l || d_cost_r));
+    SMX_ARG(w >= 1 && h >= 1 && s_begin >= 0 && s_end >= s_begin);
+    return launch_zncc_cost_pair(p->rx, p->ry, d_mom, d_img_l, d_img_r, d_cost_l, d_cost_r, w, h, dminl, dminr, s_begin, s_end,
+                                 (hipStream_t)stream);
 }
 
 // ---- semi-global matching (not in the reference; smx_sgm.hip) -----------------------------------------

@@ -26,7 +26,7 @@ struct smx_ctx {
     CtxSettings s;
     PairPlan done;
     DevBuf nbr, sub, subf;      // sub-pixel: neighbour state [2][3][h][w], maps [2][h][w] and [h][w]
-    DevBuf codes;               // census cost, AD-Census: the codes [2][h][w]
+    DevBuf codes;               // census cost, AD-Census: the codes [2][h][w]; the ZNCC cost: the moments [2][h][w], as large
     bool adc_tab_valid = false; // the device table holds the tables of s.adc
     DevBuf adc_tab;
     // the mutual-information cost: the histogram [256][256] u32 and the table [256][256] u8 of the pass in hand; mi_table is
@@ -152,9 +152,16 @@ static int ctx_reserve(smx_ctx* c, const PairPlan& need) {
     return SMX_OK;
 }
 
-// The census codes of both images of `call`: one launch where they lie back to back, else one per image
+// The census codes of both images of `call`: one launch where they lie back to back, else one per image.  With the ZNCC cost
+// the window moments, in the same buffer and the same way.
 static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
     uint64_t* codes = c->codes.as<uint64_t>();
+    if (c->s.cost_mode == SMX_COST_ZNCC) {
+        if (call.guide[1] == call.guide[0] + c->n) return smx_dev_zncc_moments(&c->s.zncc, call.guide[0], codes, c->w, c->h, 2, call.st);
+        int rc = SMX_OK;
+        for (int v = 0; v < 2 && !rc; ++v) rc = smx_dev_zncc_moments(&c->s.zncc, call.guide[v], codes + v * c->n, c->w, c->h, 1, call.st);
+        return rc;
+    }
     const smx_census_params* cp = c->s.adcensus ? &c->s.adc.census : &c->s.census;
     if (call.guide[1] == call.guide[0] + c->n) return smx_dev_census(cp, call.guide[0], codes, c->w, c->h, 2, call.st);
     int rc = SMX_OK;
@@ -163,8 +170,11 @@ static int ctx_census_codes(smx_ctx* c, const AggCall& call) {
 }
 
 // Slices [s0, s1) of both views' cost from the codes: the census cost, or AD-Census with its AD term from the gray images or
-// from the colour images of the pair; or, without codes, the mutual-information cost from the table of the pass in hand
+// from the colour images of the pair; or, without codes, the mutual-information cost from the table of the pass in hand; or
+// the ZNCC cost from the moments and the gray images
 static int ctx_code_cost(smx_ctx* c, const PairIn& in, float* cl, float* cr, int s0, int s1, hipStream_t st) {
+    if (c->s.cost_mode == SMX_COST_ZNCC)
+        return smx_dev_zncc_cost_pair(&c->s.zncc, c->codes.as<uint64_t>(), in.left, in.right, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
     if (c->s.cost_mode == SMX_COST_MI)
         return smx_dev_mi_cost_pair(c->mi_table, in.left, in.right, cl, cr, c->w, c->h, in.dminl, in.dminr, s0, s1, st);
     const uint64_t* codes = c->codes.as<uint64_t>();
@@ -415,6 +425,7 @@ static int ctx_cscale_levels(smx_ctx* c, const char* who, const PairIn& in, cons
         k->agg_path = c->agg_path;
         k->s.cost_mode = c->s.cost_mode;
         k->s.census = c->s.census;
+        k->s.zncc = c->s.zncc;
         k->s.guide_mode = c->s.guide_mode;
         if (c->s.adcensus && (!k->s.adcensus || memcmp(&k->s.adc, &c->s.adc, sizeof(k->s.adc)) != 0)) { k->s.adc = c->s.adc; k->adc_tab_valid = false; }
         k->s.adcensus = c->s.adcensus;
@@ -745,6 +756,17 @@ int smx_ctx_set_mi(smx_ctx* c, const smx_mi_params* p) {
         c->s.cost_mode = SMX_COST_MI;                   // (it replaces whatever smx_ctx_set_cost or smx_ctx_set_adcensus chose)
         c->s.adcensus = false;
     } else if (c->s.cost_mode == SMX_COST_MI) c->s.cost_mode = SMX_COST_REFERENCE;
+    return SMX_OK;
+}
+
+int smx_ctx_set_zncc(smx_ctx* c, const smx_zncc_params* p) {
+    SMX_ARG(c);
+    if (p) {
+        if (!zncc_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_zncc: %s", ZNCC_RANGES);
+        c->s.zncc = *p;
+        c->s.cost_mode = SMX_COST_ZNCC;                 // (it replaces whatever the other cost setters chose)
+        c->s.adcensus = false;
+    } else if (c->s.cost_mode == SMX_COST_ZNCC) c->s.cost_mode = SMX_COST_REFERENCE;
     return SMX_OK;
 }
 

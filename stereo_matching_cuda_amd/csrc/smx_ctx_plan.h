@@ -40,6 +40,7 @@ struct CtxSettings {
     bool adcensus = false;                  // smx_ctx_set_adcensus: it takes the place of the census cost in every flow
     smx_adcensus_params adc;
     smx_mi_params mi;                       // smx_ctx_set_mi: cost_mode SMX_COST_MI, the third value, which only that setter writes
+    smx_zncc_params zncc = {3, 3};          // smx_ctx_set_zncc: cost_mode SMX_COST_ZNCC, the fourth value, likewise
     int agg_mode = SMX_AGG_GUIDED;          // smx_ctx_set_aggregation
     smx_sgm_params sgm;
     int guide_mode = SMX_GUIDE_GRAY;        // smx_ctx_set_guidance
@@ -60,7 +61,7 @@ struct CtxSettings {
 
 // What one pair asks of the context beyond the eight result planes, decided once per pair by plan_pair.  cost / agg: the whole
 // volumes, because the caller wants them or a stage reads them; census: a cost materialised chunk by chunk (the census cost,
-// AD-Census, or the mutual-information cost, which needs no codes); the rest: the stage runs and its buffers are reserved.  cscale / perm / bp / sgm / so / cross / cgf say where the
+// AD-Census, the mutual-information cost, which needs no codes, or the ZNCC cost, whose moments take the codes' place); the rest: the stage runs and its buffers are reserved.  cscale / perm / bp / sgm / so / cross / cgf say where the
 // winners come from, pm that PatchMatch takes the place of cost, aggregation and winners.  level: this pair is a level of
 // another context's pyramid, which wants its aggregated volumes and nothing behind them (ctx_cscale_levels sets it).
 // walker_status: the pair ran the fused aggregation, whose status word the entry reads afterwards.
@@ -144,7 +145,7 @@ static_assert(excludes_are_symmetric(), "STAGES: A must list B exactly when B li
 // The stages that `s` has on, as bits of CtxStage
 inline uint32_t stages_on(const CtxSettings& s) {
     const bool on[N_STAGES] = {s.agg_mode == SMX_AGG_SGM, s.guide_mode == SMX_GUIDE_RGB, s.cross, s.so, s.cscale, s.perm, s.bp, s.pm,
-                               s.adjust, s.uniq > 0.0f, s.subpix != 0, s.speckle, s.vote, s.cost_mode == SMX_COST_CENSUS || s.cost_mode == SMX_COST_MI,
+                               s.adjust, s.uniq > 0.0f, s.subpix != 0, s.speckle, s.vote, s.cost_mode == SMX_COST_CENSUS || s.cost_mode == SMX_COST_MI || s.cost_mode == SMX_COST_ZNCC,
                                s.adcensus};
     uint32_t m = 0;
     for (int i = 0; i < N_STAGES; ++i) m |= on[i] ? bit(i) : 0;
@@ -167,10 +168,11 @@ inline int plan_pair(const CtxSettings& s, int w, int h, int size_d, PairEntry e
     const uint32_t on = stages_on(s);
     auto is_on = [on](int i) { return (on >> i & 1) != 0; };
     auto refuse = [&](const char* fmt, auto... a) { snprintf(err, errlen, fmt, who, a...); return SMX_E_ARG; };
-    // the mutual-information cost is a mode of the census cost's row: the same flows and exclusions under its own name
-    const bool mi = s.cost_mode == SMX_COST_MI;
-    auto noun = [mi](int i) { return mi && i == S_CENSUS ? "the mutual-information cost" : STAGES[i].noun; };
-    auto setter = [mi](int i) { return mi && i == S_CENSUS ? "smx_ctx_set_mi" : STAGES[i].setter; };
+    // the mutual-information cost and the ZNCC cost are modes of the census cost's row: the same flows and exclusions under
+    // their own names
+    const bool mi = s.cost_mode == SMX_COST_MI, zncc = s.cost_mode == SMX_COST_ZNCC;
+    auto noun = [mi, zncc](int i) { return i != S_CENSUS ? STAGES[i].noun : mi ? "the mutual-information cost" : zncc ? "the ZNCC cost" : STAGES[i].noun; };
+    auto setter = [mi, zncc](int i) { return i != S_CENSUS ? STAGES[i].setter : mi ? "smx_ctx_set_mi" : zncc ? "smx_ctx_set_zncc" : STAGES[i].setter; };
     *plan = PairPlan{};
     plan->walker_status = true;
     // the pipelined entry stages the eight planes only: it takes the state with every opt-in off

@@ -205,6 +205,27 @@ int smx_census_cost(const smx_census_params* p, const uint8_t* i1, const uint8_t
     return SMX_OK;
 }
 
+int smx_zncc_cost(const smx_zncc_params* p, const uint8_t* i1, const uint8_t* i2, float* cost, int w, int h, int size_d,
+                  int dmin) {
+    if (!zncc_params_ok(p)) return fail(SMX_E_ARG, "smx_zncc_cost: %s", ZNCC_RANGES);
+    SMX_ARG(i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);
+    const size_t n = (size_t)w * h;
+    DevBuf img, mom, dc;
+    SMX_HIP(img.ensure(2 * n));
+    SMX_HIP(mom.ensure(2 * n * sizeof(uint64_t)));
+    SMX_HIP(dc.ensure(n * size_d * sizeof(float)));
+    SMX_HIP(hipMemcpy(img.p, i1, n, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(img.as<uint8_t>() + n, i2, n, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = smx_dev_zncc_moments(p, img.as<uint8_t>(), mom.as<uint64_t>(), w, h, 2, nullptr))) return rc;
+    if ((rc = smx_dev_zncc_cost_pair(p, mom.as<uint64_t>(), img.as<uint8_t>(), img.as<uint8_t>() + n, dc.as<float>(), nullptr, w, h, dmin, 0, 0,
+                                     size_d, nullptr)))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    SMX_HIP(dc.download(cost, n * size_d * sizeof(float)));
+    return SMX_OK;
+}
+
 int smx_adcensus_cost(const smx_adcensus_params* p, const uint8_t* i1, const uint8_t* i2, int channels, float* cost, int w,
                       int h, int size_d, int dmin) {
     SMX_ARG(adcensus_params_ok(p) && i1 && i2 && cost && w >= 1 && h >= 1 && size_d >= 1);

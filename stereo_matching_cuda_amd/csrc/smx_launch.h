@@ -54,6 +54,12 @@ void mi_table(const uint32_t* hist, uint8_t* table);
 int launch_mi_random_map(float* map, int w, int h, int dmin, int size_d, uint32_t seed, hipStream_t st);
 int launch_mi_cost_pair(const uint8_t* table, const uint8_t* img_l, const uint8_t* img_r, float* cost_l, float* cost_r, int w,
                         int h, int dminl, int dminr, int s_begin, int s_end, hipStream_t st);
+// smx_zncc.hip: the ZNCC window cost -- the window moments {S, V} of nimages planes (8 bytes a pixel) and the cost slices
+// [s_begin, s_end) of one or both views from them and the images; zncc_geometry: columns and rows of a cost workgroup
+void zncc_geometry(int* cols, int* rows);
+int launch_zncc_moments(int rx, int ry, const uint8_t* img, uint64_t* mom, int w, int h, int nimages, hipStream_t st);
+int launch_zncc_cost_pair(int rx, int ry, const uint64_t* mom, const uint8_t* img_l, const uint8_t* img_r, float* cost_l,
+                          float* cost_r, int w, int h, int dminl, int dminr, int s_begin, int s_end, hipStream_t st);
 // smx_speckle.hip: the connected-component filter (smx_dev_speckle_filter); ws: speckle_workspace_bytes(w, h) bytes
 size_t speckle_workspace_bytes(int w, int h);
 int launch_speckle_filter(int max_size, float max_diff, const float* disp, float* out, int w, int h, float vmin,

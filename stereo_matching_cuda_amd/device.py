@@ -788,3 +788,30 @@ class PairPipeline:
             r["pm_planes"] = c(self.pm_planes)
             r["subpixl"], r["subpixr"], r["subpix_filled"] = c(self.pm_disp[0]), c(self.pm_disp[1]), c(self.sub_filled)
         return r
+
+
+def zncc_cost_volumes(gray_l, gray_r, size_d, dminl, dminr=0, params=None, s_begin=0, s_end=None):
+    """The ZNCC window cost of a pair on the device (include/smx.h smx_dev_zncc_moments, smx_dev_zncc_cost_pair): two launches
+    on torch's current stream, the moments of both images and slices [s_begin, s_end) of both views' volumes.  gray_l, gray_r:
+    (h, w) uint8 tensors on one GPU.  Returns (cost_l, cost_r), float32 (s_end - s_begin, h, w) with labels dminl + z and
+    dminr + z: what PairPipeline.aggregate(gray_l, gray_r, cost_l=..., cost_r=...) takes in every flow."""
+    if gray_l.dtype != torch.uint8 or gray_l.dim() != 2 or gray_r.shape != gray_l.shape or gray_r.dtype != torch.uint8:
+        raise ValueError("zncc_cost_volumes expects two (h, w) uint8 tensors of one shape")
+    if not gray_l.is_cuda or gray_r.device != gray_l.device:
+        raise ValueError("zncc_cost_volumes expects both images on one GPU")
+    s_end = int(size_d) if s_end is None else int(s_end)
+    if not 0 <= s_begin <= s_end <= size_d:
+        raise ValueError("zncc_cost_volumes needs 0 <= s_begin <= s_end <= size_d")
+    p = params if params is not None else _lib.default_zncc_params()
+    L = _lib.lib()
+    h, w = gray_l.shape
+    dev = gray_l.device
+    pair = torch.stack((gray_l, gray_r)).contiguous()
+    mom = torch.empty((2, h, w), dtype=torch.int64, device=dev)
+    cost = torch.empty((2, s_end - s_begin, h, w), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(L.smx_dev_zncc_moments(C.byref(p), _dp(pair), _dp(mom), w, h, 2, st))
+        _lib.check(L.smx_dev_zncc_cost_pair(C.byref(p), _dp(mom), _dp(pair[0]), _dp(pair[1]), _dp(cost[0]), _dp(cost[1]), w, h,
+                                            int(dminl), int(dminr), int(s_begin), s_end, st))
+    return cost[0], cost[1]

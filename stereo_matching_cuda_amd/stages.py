@@ -452,6 +452,20 @@ def mi_cost(table, i1, i2, size_d, dmin, right=False):
     return cost
 
 
+def zncc_cost(i1, i2, size_d, dmin, params=None):
+    """ZNCC window cost volume of i1 against i2, [z][y][x], slice z has label dmin + z (smx_zncc_cost; include/smx.h has the
+    definition): 127.5 (1 - rho |rho|) rounded, rho the zero-mean normalised cross-correlation of the two windows; 128 where a
+    window is flat, 255 where the partner lies outside the image."""
+    i1, i2 = _c(i1, np.uint8), _c(i2, np.uint8)
+    if i1.ndim != 2 or i2.shape != i1.shape:
+        raise ValueError("zncc_cost expects two (h, w) uint8 images of one shape")
+    h, w = i1.shape
+    p = params if params is not None else _lib.default_zncc_params()
+    cost = np.empty((max(size_d, 0), h, w), np.float32)
+    _lib.check(_lib.lib().smx_zncc_cost(C.byref(p), _ptr(i1), _ptr(i2), _ptr(cost), w, h, size_d, dmin))
+    return cost
+
+
 def sgm_aggregate(cost, dmin=0, params=None, want_agg=True):
     """Semi-global matching of one (size_d, h, w) float32 cost volume (smx_sgm_aggregate; include/smx.h has the
     definition).  Returns (agg, best, disp_map): S as float32 [z][y][x] (None without want_agg), the winner's S and
