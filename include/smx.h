@@ -1472,6 +1472,104 @@ int smx_ctx_set_permeability(smx_ctx* ctx, const smx_perm_params* p);
  * whose pairs never ran with it on. */
 int smx_ctx_perm_held(const smx_ctx* ctx, size_t* bytes);
 
+/* ------------------------------------------------------------------------------------
+ * Non-local cost aggregation on a minimum spanning tree (Yang, CVPR 2012; not a stage of the reference; opt-in)
+ * ---------------------------------------------------------------------------------- */
+
+/* The support of a pixel is the whole image, as with the permeability filter, but the weight between two pixels is
+ * exp(-dist / sigma) with dist the distance ALONG THE MINIMUM SPANNING TREE of the guide: the path between two pixels is the
+ * most similar one that exists, of any shape, where the permeability filter knows L-shaped paths only.  Two sweeps over the
+ * tree, leaves to root and root to leaves, give every pixel its exact sum at O(1) per cell.  tests/tree_ref.py is this
+ * definition in numpy; the results equal it bit for bit.
+ *
+ * Parameters.  sigma: finite and > 0; anything else is SMX_E_ARG before any device call.  The default 25.5 is the paper's 0.1 on
+ * a [0, 1] scale: a starting point, not measured on real data.
+ *
+ * Guide.  u8 [h][w][channels], channels 1, 3 or 4, interleaved.  diff of two 4-neighbours as in the permeability filter: |dI|
+ * for one channel, the maximum of |dI| over R, G, B for 3 or 4 channels (alpha is ignored).
+ *
+ * Graph.  Pixel p = y*w + x.  Edge (p, p+1) exists for x < w-1 and has id 2p; edge (p, p+w) exists for y < h-1 and has id 2p+1.
+ * The weight of an edge is diff of its two pixels, 0 .. 255.
+ *
+ * Tree.  Kruskal over the edges in ascending (weight, id) order: an edge joins the tree when its ends are not connected yet.
+ * The total order makes the tree unique whatever union-find is used.  Pixel 0 is the root.  The nodes are numbered breadth
+ * first; a node's children are visited in ascending pixel index (up, left, right, down), so the children of a node are
+ * consecutive numbers and a level is a contiguous run.  `levels` is the number of levels (the root alone is level 0).
+ *
+ * The blob.  smx_tree_bytes(w, h) bytes, position independent -- it holds indices only -- so it is copied to the device as it
+ * is.  n = w*h; every multi-byte value in the host's (little-endian) byte order:
+ *   offset 0            u32 n
+ *   offset 4            u32 levels
+ *   offset 8            u32 order[n]           the pixel index of node i
+ *   offset 8 + 4n       u32 parent[n]          the node number of i's parent; 0 for the root
+ *   offset 8 + 8n       u32 child_first[n]     the node number of i's first child: the number of nodes that were numbered when i
+ *                                              was visited, also where i has no child (so it never decreases, and may be n)
+ *   offset 8 + 12n      u32 level_start[n+1]   level l is the nodes level_start[l] .. level_start[l+1]-1; entries 0 .. levels
+ *                                              are used (level_start[levels] == n), the rest is 0
+ *   offset 12 + 16n     u8  child_count[n]     0 .. 4
+ *   offset 12 + 17n     u8  wt[n]              the weight of the edge from i to its parent; 0 for the root
+ *   then 0 .. 3 bytes of 0 up to a multiple of 4: smx_tree_bytes(w, h) = (12 + 18n + 3) & ~3.
+ * smx_tree_build writes every byte of it, on the host in plain C++ (a counting sort over the 256 weights, a union-find, a
+ * queue): deterministic, no device call, about 13 bytes a pixel of temporary host memory.  blob: 4-byte aligned.  smx_tree_bytes
+ * is 0 for w or h < 1 or w*h >= 2^31.
+ *
+ * Tables.  t[k] = (float)exp(-(double)k / sigma) and u[k] = (float)(1.0 - exp(-2.0 * (double)k / sigma)), k = 0 .. 255, computed
+ * on the host in double (smx_tree_tables); t[0] == 1, u[0] == 0.  The kernels hold no transcendental and no division.
+ *
+ * Filter.  Per slice C [h][w] of an f32 volume [size_d][h][w], every product and every sum rounded to f32 on its own, no fused
+ * multiply-add; NaN, infinities and subnormals as IEEE 754 says.  With i a node number:
+ *   up, the levels descending:   U[i] = C[order[i]];  then for every child c of i, c ascending:  U[i] = U[i] + t[wt[c]] * U[c]
+ *   down, the levels ascending:  A[0] = U[0];  A[i] = t[wt[i]] * A[parent[i]] + u[wt[i]] * U[i]
+ *   out[order[i]] = A[i]
+ * (U[i] is the weighted sum over i's subtree; the second line adds what lies outside it: A[p] - t U[i] seen through the edge,
+ * t (A[p] - t U[i]) + U[i].)  A NaN or an infinity anywhere in a slice reaches every pixel of that slice and no other slice.
+ *
+ * The output is NOT normalised, as in the paper and as with the permeability filter: a pixel's total weight depends on the guide
+ * only and is the same for every label, so the winners, the sub-pixel fits, the uniqueness ratio and the comparisons of the
+ * depth-discontinuity adjustment are what they would be on the normalised volume.  The filtered costs are weighted SUMS.
+ *
+ * Winners.  From out by the packed key's rule with the slices ascending, as smx_dev_permeability_wta_pair takes them.
+ *
+ * smx_tree_workspace_bytes: the workspace with which a call on nviews views of size_d slices runs as one chunk whatever its
+ * outputs (0 for w, h or size_d < 1, w*h >= 2^31, size_d > 2^20 or nviews not 1 or 2): per view and slice the breadth-first
+ * plane of U and A and a plane of the filtered slice, which a call with d_out == NULL keeps there.  A smaller workspace makes
+ * the call go in chunks of slices, with the same bits; one that does not hold one slice -- nviews * w * h * 4 bytes with d_out,
+ * twice that without -- is SMX_E_WS before anything is launched.
+ *
+ * smx_dev_tree_wta_pair: on `stream`; no allocation, no synchronisation (graph-capturable); per chunk one filter launch -- a
+ * workgroup per (slice, view), which walks the levels with a workgroup barrier a level -- and the winner-take-all pass.
+ * d_tree_l / d_tree_r: the views' blobs on the device, 4-byte aligned, built from the views' guides at this w and h; they are
+ * read only.  The call cannot check them: a blob of another shape gives wrong numbers (the kernel skips every index past the
+ * tree, so it never leaves the buffers of the call).  d_vol_r and d_tree_r may both be NULL for a one-view call (or d_vol_l and
+ * d_tree_l).  d_out, d_keys, d_nbr, d_uq, dminl, dminr, the limits and the alignment as in smx_dev_permeability_wta_pair; d_out
+ * may be the input volumes (in place).  smx_set_max_slices_per_launch of the calling thread bounds the chunk too.
+ *
+ * smx_tree_filter: host pointers, one view, synchronous; it builds the tree itself.  out (the filtered volume), best (the
+ * winners' costs) and disp_map (dmin + winning slice) may each be NULL. */
+typedef struct smx_tree_params { double sigma; } smx_tree_params;
+void smx_default_tree_params(smx_tree_params* p);
+size_t smx_tree_bytes(int w, int h);
+int smx_tree_build(const uint8_t* guide, int channels, int w, int h, void* blob);
+int smx_tree_tables(const smx_tree_params* p, float* t /* [256] */, float* u /* [256] */);
+size_t smx_tree_workspace_bytes(int w, int h, int size_d, int nviews);
+int smx_dev_tree_wta_pair(const smx_tree_params* p, const float* d_vol_l, const float* d_vol_r, const void* d_tree_l,
+                          const void* d_tree_r, int w, int h, int dminl, int dminr, int size_d, int64_t* d_keys, float* d_out,
+                          float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream);
+int smx_tree_filter(const smx_tree_params* p, const float* volume, const uint8_t* guide, int channels, int w, int h, int dmin,
+                    int size_d, float* out, float* best, float* disp_map);
+/* The tree filter of this context: a second mode of the permeability filter's place in a pair.  NULL switches it off (the
+ * default: nothing is allocated or launched).  While it is on, smx_ctx_stereo_pair / _rgb keeps the aggregated volumes, builds
+ * the two trees on the host from the images it was handed -- the gray images, or the colour pair under SMX_GUIDE_RGB --, uploads
+ * them and runs smx_dev_tree_wta_pair in place where the permeability pass would run; everything behind runs unchanged, and
+ * what is supported and refused is what smx_ctx_set_permeability lists, under this mode's own name.  The two modes exclude each
+ * other: smx_ctx_set_tree while the permeability filter is on is SMX_E_ARG, and so is smx_ctx_set_permeability while this mode
+ * is on; switch the other off first.  smx_ctx_stereo_pair_async refuses while the mode is on.  The host build costs more than
+ * the kernels. */
+int smx_ctx_set_tree(smx_ctx* ctx, const smx_tree_params* p);
+/* Test hook, NOT part of the stable contract: the device bytes the context holds for the tree filter (workspace and blobs).  0
+ * for a context whose pairs never ran with it on. */
+int smx_ctx_tree_held(const smx_ctx* ctx, size_t* bytes);
+
 /* Host-side helpers for the packed key (same encoding as the kernels). */
 int64_t smx_pack_key(float cost, uint32_t slice);
 void smx_unpack_key(int64_t key, float* cost, uint32_t* slice);

@@ -117,6 +117,11 @@ class PermParams(C.Structure):
     _fields_ = [("sigma", C.c_double)]
 
 
+class TreeParams(C.Structure):
+    """smx_tree_params: non-local aggregation on the guide's minimum spanning tree (not a stage of the reference)."""
+    _fields_ = [("sigma", C.c_double)]
+
+
 class StageMs(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("upload", "guidance", "aggregation", "wta", "finish", "download", "total")] + \
                [("calls", C.c_int), ("dropped", C.c_int)]
@@ -155,6 +160,7 @@ _JP = C.POINTER(AdjustParams)
 _KP = C.POINTER(CScaleParams)
 _ip = C.POINTER(C.c_int)
 _EP = C.POINTER(PermParams)
+_TP = C.POINTER(TreeParams)
 
 # name -> (restype, argtypes).  Mirrors include/smx.h one to one (tests/test_capi.py checks it).
 SIGNATURES = {
@@ -328,6 +334,15 @@ SIGNATURES = {
     "smx_permeability_filter": (_i, [_EP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "smx_ctx_set_permeability": (_i, [_vp, _EP]),
     "smx_ctx_perm_held": (_i, [_vp, C.POINTER(_sz)]),
+    "smx_default_tree_params": (None, [_TP]),
+    "smx_tree_bytes": (_sz, [_i, _i]),
+    "smx_tree_build": (_i, [_vp, _i, _i, _i, _vp]),
+    "smx_tree_tables": (_i, [_TP, _vp, _vp]),
+    "smx_tree_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smx_dev_tree_wta_pair": (_i, [_TP, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "smx_tree_filter": (_i, [_TP, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "smx_ctx_set_tree": (_i, [_vp, _TP]),
+    "smx_ctx_tree_held": (_i, [_vp, C.POINTER(_sz)]),
 }
 
 # smx.h SMX_AGG_*: the aggregations by name
@@ -491,6 +506,20 @@ def perm_table(params):
     t = (C.c_float * 256)()
     check(lib().smx_perm_table(C.byref(params), t))
     return list(t)
+
+
+def default_tree_params():
+    p = TreeParams()
+    lib().smx_default_tree_params(C.byref(p))
+    return p
+
+
+def tree_tables(params):
+    """The two tables of the tree filter (smx_tree_tables): (t, u) with t[k] = exp(-k / sigma) and u[k] = 1 - exp(-2 k / sigma),
+    each a list of 256 floats."""
+    t, u = (C.c_float * 256)(), (C.c_float * 256)()
+    check(lib().smx_tree_tables(C.byref(params), t, u))
+    return list(t), list(u)
 
 
 def pm_weights(params):

@@ -5,6 +5,7 @@
 #include "smx_cscale_host.h"
 #include "smx_ctx_plan.h"
 #include "smx_perm_host.h"
+#include "smx_tree_host.h"
 
 namespace smx {
 
@@ -67,6 +68,7 @@ constexpr const char* CSCALE_RANGES = "needs 1 <= scales <= 5 and a finite lambd
 bool pm_params_ok(const smx_pm_params* p);             // (smx_patchmatch.hip, beside the limits of its kernels)
 constexpr const char* PM_RANGES = "needs 0 <= radius <= 17, a finite gamma > 0, 1 <= iterations <= 16 and 0 <= max_slope <= 8";
 constexpr const char* PERM_RANGES = "needs a finite sigma > 0";
+constexpr const char* TREE_RANGES = "needs a finite sigma > 0";
 size_t pick_ws_bytes(int w, int h, int size_d);   // workspace of ONE view for the host-pointer entries (smx_host.hip)
 
 }  // namespace smx

@@ -1073,6 +1073,61 @@ int smx_dev_permeability_wta_pair(const smx_perm_params* p, const float* d_vol_l
                                 d_ws, chunk, (hipStream_t)stream);
 }
 
+// ---- the non-local tree filter (not in the reference; smx_tree.hip, smx_tree_host.h) --------------------------------------
+void smx_default_tree_params(smx_tree_params* p) {
+    if (!p) return;
+    p->sigma = 25.5;
+}
+
+static bool tree_shape_ok(int w, int h) { return w >= 1 && h >= 1 && (long long)w * h < (1ll << 31); }
+
+size_t smx_tree_bytes(int w, int h) { return tree_shape_ok(w, h) ? tree_layout((size_t)w * h).bytes : 0; }
+
+int smx_tree_build(const uint8_t* guide, int channels, int w, int h, void* blob) {
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!tree_shape_ok(w, h)) return fail(SMX_E_ARG, "smx_tree_build: %s", PLANE_SHAPES);
+    SMX_ARG(guide && blob);
+    if (((uintptr_t)blob & 3) != 0) return fail(SMX_E_ARG, "smx_tree_build: the blob is not 4-byte aligned");
+    try {
+        tree_build(guide, channels, w, h, (uint8_t*)blob);
+    } catch (const std::bad_alloc&) {
+        return fail(SMX_E_HIP, "smx_tree_build: out of host memory");
+    }
+    return SMX_OK;
+}
+
+int smx_tree_tables(const smx_tree_params* p, float* t, float* u) {
+    if (!tree_params_ok(p)) return fail(SMX_E_ARG, "smx_tree_tables: %s", TREE_RANGES);
+    SMX_ARG(t != nullptr && u != nullptr);
+    tree_tables(p, t, u);
+    return SMX_OK;
+}
+
+size_t smx_tree_workspace_bytes(int w, int h, int size_d, int nviews) {
+    return shape_ok(w, h, size_d, WIDE_MAX_D) && (nviews == 1 || nviews == 2) ? tree_workspace_bytes(w, h, size_d, nviews) : 0;
+}
+
+int smx_dev_tree_wta_pair(const smx_tree_params* p, const float* d_vol_l, const float* d_vol_r, const void* d_tree_l,
+                          const void* d_tree_r, int w, int h, int dminl, int dminr, int size_d, int64_t* d_keys, float* d_out,
+                          float* d_nbr, float* d_uq, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!tree_params_ok(p)) return fail(SMX_E_ARG, "smx_dev_tree_wta_pair: %s", TREE_RANGES);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_dev_tree_wta_pair: %s", PERM_SHAPES);
+    SMX_ARG((d_vol_l || d_vol_r) && !d_tree_l == !d_vol_l && !d_tree_r == !d_vol_r);
+    SMX_ARG(d_keys || (!d_nbr && !d_uq));
+    SMX_ARG(dminl >= -(1 << 29) && dminl <= (1 << 29) && dminr >= -(1 << 29) && dminr <= (1 << 29));
+    if ((((uintptr_t)d_vol_l | (uintptr_t)d_vol_r | (uintptr_t)d_out | (uintptr_t)d_ws | (uintptr_t)d_tree_l | (uintptr_t)d_tree_r) & 3) != 0)
+        return fail(SMX_E_ARG, "smx_dev_tree_wta_pair: a volume, a tree or the workspace is not 4-byte aligned");
+    const int nviews = d_vol_l && d_vol_r ? 2 : 1;
+    const int chunk = d_ws ? tree_chunk(w, h, nviews, ws_bytes, size_d, d_out == nullptr, g_max_chunk) : 0;
+    if (chunk < 1)
+        return fail(SMX_E_WS, "smx_dev_tree_wta_pair: workspace of %zu bytes, %zu needed for one slice in flight",
+                    d_ws ? ws_bytes : (size_t)0, (size_t)nviews * w * h * sizeof(float) * (d_out ? 1 : 2));
+    float t[256], u[256];
+    tree_tables(p, t, u);
+    return launch_tree_wta_pair(t, u, d_vol_l, d_vol_r, (const uint8_t*)d_tree_l, (const uint8_t*)d_tree_r, w, h, size_d, d_keys,
+                                d_out, d_nbr, d_uq, d_ws, chunk, (hipStream_t)stream);
+}
+
 // Test hook (not in include/smx.h): the natural-order winner-take-all pass of the aggregations (wta_launch, smx_wta.h) over one
 // materialised volume d_q [count][h][w], fresh keys out -- what tests/test_gpu_cscale.py holds the one-scale combination to.
 __attribute__((visibility("default"))) int smx_debug_wta_natural(const float* d_q, int w, int h, int count, int64_t* d_keys,

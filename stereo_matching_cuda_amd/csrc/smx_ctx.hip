@@ -49,6 +49,11 @@ struct smx_ctx {
     // PatchMatch stereo: the planes [2][3][h][w], disp [2][h][w] and the search's workspace; its sub-pixel filled map lies in subf
     DevBuf pm_planes, pm_disp, pm_ws;
     DevBuf perm_ws;             // the permeability filter runs in place over both volumes of aggLR; its workspace
+    // the tree filter, the second mode of the permeability filter's place: its workspace, the two blobs [2][smx_tree_bytes] on
+    // the device and, on the host, the blobs as they are built and the gray guides of a colour pair under the gray guide
+    DevBuf tree_ws, tree_dev;
+    std::vector<uint32_t> tree_host;
+    std::vector<uint8_t> tree_gray;
     DevBuf bp_ws;               // belief propagation reads the whole volumes costL / costR, as SGM does; its workspace
     // What the pair in hand takes of the buffers that the opt-in flows share (ctx_reserve sets them per pair).  mode_ws: the
     // workspace for both views of SGM, the colour-guided filter or cross-based aggregation -- a pair runs at most one of them --
@@ -90,6 +95,13 @@ static size_t ctx_perm_ws_bytes(const smx_ctx* c) {
     if (k > (size_t)c->size_d) k = (size_t)c->size_d;
     return per * (2 + k);
 }
+// The tree filter's workspace for both views under the same rule: a breadth-first plane per view and slice in flight
+static size_t ctx_tree_ws_bytes(const smx_ctx* c) {
+    const size_t cap = (size_t)1 << 30, per = 2 * c->n * sizeof(float);
+    size_t k = cap / per > 1 ? cap / per : 1;
+    if (k > (size_t)c->size_d) k = (size_t)c->size_d;
+    return per * k;
+}
 struct PairIn { const uint8_t* left; const uint8_t* right; int dminl, dminr; const uint8_t* rgb_l; const uint8_t* rgb_r; int channels; };
 struct PairPlanes { float* best; float* map; uint8_t* mean; float* occ; float* fil; };
 
@@ -127,7 +139,11 @@ static int ctx_reserve(smx_ctx* c, const PairPlan& need) {
         SMX_HIP(c->vote_ws.ensure(vote_workspace_bytes(c->w, c->h)));
     }
     if (need.adjust) SMX_HIP(c->adj_ws.ensure(adjust_workspace_bytes(c->w, c->h)));
-    if (need.perm) SMX_HIP(c->perm_ws.ensure(ctx_perm_ws_bytes(c)));
+    if (need.perm && !c->s.tree) SMX_HIP(c->perm_ws.ensure(ctx_perm_ws_bytes(c)));
+    if (need.perm && c->s.tree) {
+        SMX_HIP(c->tree_ws.ensure(ctx_tree_ws_bytes(c)));
+        SMX_HIP(c->tree_dev.ensure(2 * smx_tree_bytes(c->w, c->h)));
+    }
     if (need.bp) SMX_HIP(c->bp_ws.ensure(bp_workspace_bytes(c->w, c->h, c->size_d, c->s.bp_params.levels, 2)));
     if (need.pm) {
         SMX_HIP(c->pm_planes.ensure(6 * fb));
@@ -377,7 +393,13 @@ static int ctx_enqueue(smx_ctx* c, const PairIn& in, const PairPlan& need, const
         if ((rc = smx_dev_cscale_wta_pair(&c->s.cs_params, al, ar, w, h, in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, st)))
             return rc;
     }
-    if (need.perm) {
+    if (need.perm && c->s.tree) {
+        // the tree filter in the same place, over the two trees that ctx_pair built from the pair's guides and uploaded
+        const uint8_t* trees = c->tree_dev.as<uint8_t>();
+        if ((rc = smx_dev_tree_wta_pair(&c->s.tree_params, aggL, aggL + (size_t)size_d * n, trees, trees + smx_tree_bytes(w, h), w, h,
+                                        in.dminl, in.dminr, size_d, keysL, aggL, nbrL, uqL, c->tree_ws.p, ctx_tree_ws_bytes(c), st)))
+            return rc;
+    } else if (need.perm) {
         // the filter goes over both aggregated volumes in place; its winners and states take the place of the plain ones
         const bool colour = need.cgf;
         if ((rc = smx_dev_permeability_wta_pair(&c->s.perm_params, aggL, aggL + (size_t)size_d * n, colour ? in.rgb_l : in.left,
@@ -568,6 +590,30 @@ static int ctx_pair(smx_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int 
         SMX_HIP(hipMemcpyAsync(dL, img_l, n, hipMemcpyHostToDevice, st));
         SMX_HIP(hipMemcpyAsync(dR, img_r, n, hipMemcpyHostToDevice, st));
     }
+    if (need.perm && c->s.tree) {
+        // the two trees, on the host from the pair's guides -- the images as they came, or the device's gray images of a colour
+        // pair under the gray guide, fetched for it -- then up behind the images
+        const size_t tb = smx_tree_bytes(c->w, c->h);
+        const uint8_t* gl = img_l;
+        const uint8_t* gr = img_r;
+        int gch = channels ? channels : 1;
+        try {
+            c->tree_host.resize(2 * (tb / 4));
+            if (channels && !need.cgf) c->tree_gray.resize(2 * n);
+        } catch (const std::bad_alloc&) {
+            return fail(SMX_E_HIP, "%s: out of host memory for the trees", who);
+        }
+        if (channels && !need.cgf) {
+            SMX_HIP(hipMemcpyAsync(c->tree_gray.data(), dL, n, hipMemcpyDeviceToHost, st));
+            SMX_HIP(hipMemcpyAsync(c->tree_gray.data() + n, dR, n, hipMemcpyDeviceToHost, st));
+            SMX_HIP(hipStreamSynchronize(st));
+            gl = c->tree_gray.data(); gr = gl + n; gch = 1;
+        }
+        uint32_t* blobs = c->tree_host.data();
+        if ((rc = smx_tree_build(gl, gch, c->w, c->h, blobs))) return rc;
+        if ((rc = smx_tree_build(gr, gch, c->w, c->h, blobs + tb / 4))) return rc;
+        SMX_HIP(hipMemcpyAsync(c->tree_dev.p, blobs, 2 * tb, hipMemcpyHostToDevice, st));
+    }
     stage_mark(ST_UPLOAD, st);
     float* best = c->best.as<float>(); float* map = c->map.as<float>(); float* agg = c->aggLR.as<float>();
     uint8_t* mean = c->mean.as<uint8_t>();
@@ -655,8 +701,17 @@ static int ctx_set_stage(smx_ctx* c, CtxStage id, bool CtxSettings::*on, P CtxSe
 
 extern "C" {
 
+// (the permeability filter and the tree filter are the two modes of one row: a setter refuses to switch its mode on over the other)
 int smx_ctx_set_permeability(smx_ctx* c, const smx_perm_params* p) {
+    SMX_ARG(c);
+    if (const char* why = p ? row_mode_conflict(c->s, false) : nullptr) return fail(SMX_E_ARG, "%s", why);
     return ctx_set_stage(c, S_PERM, &CtxSettings::perm, &CtxSettings::perm_params, p, perm_params_ok, PERM_RANGES);
+}
+int smx_ctx_set_tree(smx_ctx* c, const smx_tree_params* p) {
+    SMX_ARG(c);
+    if (p && !tree_params_ok(p)) return fail(SMX_E_ARG, "smx_ctx_set_tree: %s", TREE_RANGES);
+    if (const char* why = p ? row_mode_conflict(c->s, true) : nullptr) return fail(SMX_E_ARG, "%s", why);
+    return ctx_set_stage(c, S_PERM, &CtxSettings::tree, &CtxSettings::tree_params, p, tree_params_ok, TREE_RANGES);
 }
 int smx_ctx_set_bp(smx_ctx* c, const smx_bp_params* p) {
     return ctx_set_stage(c, S_BP, &CtxSettings::bp, &CtxSettings::bp_params, p, bp_params_ok, BP_RANGES);
@@ -858,6 +913,13 @@ int smx_ctx_bp_held(const smx_ctx* c, size_t* bytes) {
 int smx_ctx_perm_held(const smx_ctx* c, size_t* bytes) {
     SMX_ARG(c && bytes);
     *bytes = c->perm_ws.p ? c->perm_ws.bytes : 0;
+    return SMX_OK;
+}
+
+int smx_ctx_tree_held(const smx_ctx* c, size_t* bytes) {
+    SMX_ARG(c && bytes);
+    *bytes = 0;
+    for (const DevBuf* b : {&c->tree_ws, &c->tree_dev}) *bytes += b->p ? b->bytes : 0;
     return SMX_OK;
 }
 

@@ -49,6 +49,8 @@ struct CtxSettings {
     smx_scanline_params so_params;
     smx_cscale_params cs_params;
     smx_perm_params perm_params;
+    bool tree = false;                      // smx_ctx_set_tree: the second mode of the permeability filter's row; never on with perm
+    smx_tree_params tree_params = {25.5};
     smx_bp_params bp_params;
     smx_pm_params pm_params;
     smx_adjust_params adj_params;
@@ -144,12 +146,22 @@ static_assert(excludes_are_symmetric(), "STAGES: A must list B exactly when B li
 
 // The stages that `s` has on, as bits of CtxStage
 inline uint32_t stages_on(const CtxSettings& s) {
-    const bool on[N_STAGES] = {s.agg_mode == SMX_AGG_SGM, s.guide_mode == SMX_GUIDE_RGB, s.cross, s.so, s.cscale, s.perm, s.bp, s.pm,
+    const bool on[N_STAGES] = {s.agg_mode == SMX_AGG_SGM, s.guide_mode == SMX_GUIDE_RGB, s.cross, s.so, s.cscale, s.perm || s.tree, s.bp, s.pm,
                                s.adjust, s.uniq > 0.0f, s.subpix != 0, s.speckle, s.vote, s.cost_mode == SMX_COST_CENSUS || s.cost_mode == SMX_COST_MI || s.cost_mode == SMX_COST_ZNCC,
                                s.adcensus};
     uint32_t m = 0;
     for (int i = 0; i < N_STAGES; ++i) m |= on[i] ? bit(i) : 0;
     return m;
+}
+
+// The permeability filter and the tree filter are the two modes of one row and exclude each other at the setters: nullptr where
+// the setter of the tree filter (tree) or of the permeability filter (!tree) may switch its mode on under `s`, else the refusal
+inline const char* row_mode_conflict(const CtxSettings& s, bool tree) {
+    if (tree && s.perm)
+        return "smx_ctx_set_tree: the permeability filter is on (smx_ctx_set_permeability): switch it off first, the two do not run together";
+    if (!tree && s.tree)
+        return "smx_ctx_set_permeability: the tree filter is on (smx_ctx_set_tree): switch it off first, the two do not run together";
+    return nullptr;
 }
 
 inline bool stage_shape_ok(const StageRow& r, int w, int h, int size_d, int dminl, int dminr) {
@@ -171,8 +183,16 @@ inline int plan_pair(const CtxSettings& s, int w, int h, int size_d, PairEntry e
     // the mutual-information cost and the ZNCC cost are modes of the census cost's row: the same flows and exclusions under
     // their own names
     const bool mi = s.cost_mode == SMX_COST_MI, zncc = s.cost_mode == SMX_COST_ZNCC;
-    auto noun = [mi, zncc](int i) { return i != S_CENSUS ? STAGES[i].noun : mi ? "the mutual-information cost" : zncc ? "the ZNCC cost" : STAGES[i].noun; };
-    auto setter = [mi, zncc](int i) { return i != S_CENSUS ? STAGES[i].setter : mi ? "smx_ctx_set_mi" : zncc ? "smx_ctx_set_zncc" : STAGES[i].setter; };
+    // and the tree filter is a mode of the permeability filter's row in the same way (the plan's `perm` says that the pass runs,
+    // the settings which of the two it is)
+    const bool tree = s.tree;
+    auto noun = [mi, zncc, tree](int i) {
+        return i == S_CENSUS && mi ? "the mutual-information cost" : i == S_CENSUS && zncc ? "the ZNCC cost" : i == S_PERM && tree ? "the tree filter" : STAGES[i].noun;
+    };
+    auto setter = [mi, zncc, tree](int i) {
+        return i == S_CENSUS && mi ? "smx_ctx_set_mi" : i == S_CENSUS && zncc ? "smx_ctx_set_zncc" : i == S_PERM && tree ? "smx_ctx_set_tree" : STAGES[i].setter;
+    };
+    auto reason = [tree](int i) { return i == S_PERM && tree ? "the tree filter runs over the guided filter's volumes of one scale" : STAGES[i].why; };
     *plan = PairPlan{};
     plan->walker_status = true;
     // the pipelined entry stages the eight planes only: it takes the state with every opt-in off
@@ -180,9 +200,8 @@ inline int plan_pair(const CtxSettings& s, int w, int h, int size_d, PairEntry e
         if (is_on(i)) return refuse("%s: %s is on (%s): use %s", noun(i), setter(i), ENTRY_NAMES[i == S_CGF ? ENTRY_RGB : ENTRY_GRAY]);
     for (int a = 0; a < N_STAGES; ++a)
         for (int b = a + 1; b < N_STAGES; ++b) {
-            const StageRow &A = STAGES[a], &B = STAGES[b];
-            if (!is_on(a) || !is_on(b) || !(A.excludes >> b & 1)) continue;
-            const char* why = B.why ? B.why : A.why;
+            if (!is_on(a) || !is_on(b) || !(STAGES[a].excludes >> b & 1)) continue;
+            const char* why = reason(b) ? reason(b) : reason(a);
             return refuse("%s: %s (%s) and %s (%s) do not run together%s%s", noun(a), setter(a), noun(b), setter(b), why ? ": " : "", why ? why : "");
         }
     if (is_on(S_PM) && (wants_cost || wants_agg))

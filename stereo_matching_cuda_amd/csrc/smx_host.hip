@@ -591,6 +591,47 @@ int smx_permeability_filter(const smx_perm_params* p, const float* volume, const
     return SMX_OK;
 }
 
+int smx_tree_filter(const smx_tree_params* p, const float* volume, const uint8_t* guide, int channels, int w, int h, int dmin,
+                    int size_d, float* out, float* best, float* disp_map) {
+    if (!tree_params_ok(p)) return fail(SMX_E_ARG, "smx_tree_filter: %s", TREE_RANGES);
+    SMX_ARG(channels == 1 || channels == 3 || channels == 4);
+    if (!shape_ok(w, h, size_d, WIDE_MAX_D)) return fail(SMX_E_ARG, "smx_tree_filter: %s", PERM_SHAPES);
+    SMX_ARG(volume && guide);
+    const size_t n = (size_t)w * h, vb = n * size_d * sizeof(float), tb = smx_tree_bytes(w, h);
+    // (the filtered volume goes over the uploaded one; the workspace: every slice at once up to ~1 GiB, one slice at least)
+    size_t wsb = tree_workspace_bytes(w, h, size_d, 1) / 2;
+    const size_t cap = (size_t)1 << 30, least = n * sizeof(float);
+    if (wsb > cap) wsb = cap / least > 1 ? cap / least * least : least;
+    std::vector<uint32_t> blob;
+    try {
+        blob.resize(tb / 4);
+    } catch (const std::bad_alloc&) {
+        return fail(SMX_E_HIP, "smx_tree_filter: out of host memory");
+    }
+    if (int rc = smx_tree_build(guide, channels, w, h, blob.data())) return rc;
+    DevBuf dV, dT, dK, dW;
+    SMX_HIP(dV.upload(volume, vb));
+    SMX_HIP(dT.upload(blob.data(), tb));
+    SMX_HIP(dK.ensure(n * sizeof(int64_t)));
+    SMX_HIP(dW.ensure(wsb));
+    if (int rc = smx_dev_tree_wta_pair(p, dV.as<float>(), nullptr, dT.p, nullptr, w, h, dmin, 0, size_d, dK.as<int64_t>(), dV.as<float>(),
+                                       nullptr, nullptr, dW.p, wsb, nullptr))
+        return rc;
+    SMX_HIP(hipDeviceSynchronize());
+    if (out) SMX_HIP(dV.download(out, vb));
+    if (best || disp_map) {
+        std::vector<int64_t> keys(n);
+        SMX_HIP(dK.download(keys.data(), n * sizeof(int64_t)));
+        for (size_t i = 0; i < n; ++i) {
+            float c; uint32_t z;
+            unpack_key(keys[i], &c, &z);
+            if (best) best[i] = c;
+            if (disp_map) disp_map[i] = (float)(dmin + (int)z);
+        }
+    }
+    return SMX_OK;
+}
+
 int smx_filter(const smx_params* p, const uint8_t* image, int w, int h, uint8_t* mean, float* var) {
     SMX_ARG(p && image && mean && var && w >= 1 && h >= 1 && p->radius >= 0);
     const size_t n = (size_t)w * h;

@@ -137,4 +137,12 @@ int perm_chunk(int w, int h, int nviews, size_t ws_bytes, int count, bool own_ou
 int launch_perm_wta_pair(const float* table, const float* vol_l, const float* vol_r, const uint8_t* guide_l, const uint8_t* guide_r,
                          int ch, int w, int h, int size_d, int64_t* keys, float* out, float* nbr, float* uq, void* ws, int chunk,
                          hipStream_t st);
+// smx_tree.hip: the non-local tree filter and the winner-take-all pass over it (smx_dev_tree_wta_pair); t, u: the two tables of
+// 256 weights on the host (smx_tree_host.h); tree_l / tree_r: the views' tree blobs on the device; ws: tree_workspace_bytes
+// bytes for the slices in flight, chunk: tree_chunk of that workspace (>= 1; own_out as in perm_chunk)
+size_t tree_workspace_bytes(int w, int h, int nslices, int nviews);
+int tree_chunk(int w, int h, int nviews, size_t ws_bytes, int count, bool own_out, int max_chunk);
+int launch_tree_wta_pair(const float* t, const float* u, const float* vol_l, const float* vol_r, const uint8_t* tree_l,
+                         const uint8_t* tree_r, int w, int h, int size_d, int64_t* keys, float* out, float* nbr, float* uq, void* ws,
+                         int chunk, hipStream_t st);
 }  // namespace smx

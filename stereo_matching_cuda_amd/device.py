@@ -815,3 +815,42 @@ def zncc_cost_volumes(gray_l, gray_r, size_d, dminl, dminr=0, params=None, s_beg
         _lib.check(L.smx_dev_zncc_cost_pair(C.byref(p), _dp(mom), _dp(pair[0]), _dp(pair[1]), _dp(cost[0]), _dp(cost[1]), w, h,
                                             int(dminl), int(dminr), int(s_begin), s_end, st))
     return cost[0], cost[1]
+
+
+def tree_filter_pair(vol_l, vol_r, guide_l, guide_r, sigma=None, dminl=0, dminr=0, want_states=False):
+    """Non-local aggregation of a pair's volumes on the minimum spanning trees of their guides, on the device (include/smx.h
+    smx_dev_tree_wta_pair; Yang 2012; not a stage of the reference).  vol_l, vol_r: (size_d, h, w) float32 tensors on one GPU --
+    aggregated volumes, or raw cost volumes for the paper's own form; guide_l, guide_r: HOST arrays, (h, w) or
+    (h, w, 1 | 3 | 4) uint8: the trees are built on the host (stages.tree_build) and uploaded, which costs more than the
+    kernels.  sigma: None (the default 25.5), a float or TreeParams.  The inputs are left as they are: the filter runs in place
+    over one copy of both.  Returns (out_l, out_r, keys) -- keys (2, h, w) int64, the packed winners of both views -- and with want_states also the
+    neighbour state and the second-best state, (2, 3, h, w) float32 each.  Everything runs on torch's current stream."""
+    from . import stages
+    if vol_l.dtype != torch.float32 or vol_l.dim() != 3 or vol_r.shape != vol_l.shape or vol_r.dtype != torch.float32:
+        raise ValueError("tree_filter_pair expects two (size_d, h, w) float32 tensors of one shape")
+    if not vol_l.is_cuda or vol_r.device != vol_l.device or not vol_l.is_contiguous() or not vol_r.is_contiguous():
+        raise ValueError("tree_filter_pair expects both volumes contiguous on one GPU")
+    p = stages._tree_params(sigma, "tree_filter_pair")
+    size_d, h, w = vol_l.shape
+    L = _lib.lib()
+    dev = vol_l.device
+    blobs = []
+    for g in (guide_l, guide_r):
+        g, _ = stages._tree_guide(g, h, w)
+        blobs.append(torch.from_numpy(stages.tree_build(g)))
+    ws_bytes = L.smx_tree_workspace_bytes(w, h, size_d, 2) // 2
+    if ws_bytes == 0:
+        raise ValueError("tree_filter_pair needs w*h < 2^31 and size_d <= 2^20")
+    per = 2 * w * h * 4
+    ws_bytes = min(ws_bytes, max(per, (1 << 30) // per * per))
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        trees = torch.stack(blobs).to(dev)
+        out = torch.stack((vol_l, vol_r))
+        keys = torch.empty((2, h, w), dtype=torch.int64, device=dev)
+        nbr = torch.empty((2, 3, h, w), dtype=torch.float32, device=dev) if want_states else None
+        uq = torch.empty((2, 3, h, w), dtype=torch.float32, device=dev) if want_states else None
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.smx_dev_tree_wta_pair(C.byref(p), _dp(out[0]), _dp(out[1]), _dp(trees[0]), _dp(trees[1]), w, h, int(dminl),
+                                           int(dminr), size_d, _dp(keys), _dp(out), _dp(nbr), _dp(uq), _dp(ws), ws_bytes, st))
+    return (out[0], out[1], keys, nbr, uq) if want_states else (out[0], out[1], keys)

@@ -330,6 +330,59 @@ def permeability_filter(volume, guide, sigma=None, dmin=0):
     return out, best, disp
 
 
+def _tree_params(sigma, who):
+    p = _lib.default_tree_params()
+    if isinstance(sigma, _lib.TreeParams):
+        p.sigma = sigma.sigma
+    elif sigma is not None:
+        p.sigma = float(sigma)
+    if not (0.0 < p.sigma < float("inf")):
+        raise ValueError(f"{who} needs a finite sigma > 0, not {p.sigma!r}")
+    return p
+
+
+def _tree_guide(guide, h=None, w=None):
+    g = _c(guide, np.uint8)
+    if g.ndim not in (2, 3) or g.size == 0 or (g.ndim == 3 and g.shape[2] not in (1, 3, 4)) or (h is not None and g.shape[:2] != (h, w)):
+        hw = "h, w" if h is None else f"{h}, {w}"
+        raise ValueError(f"the guide must be ({hw}) or ({hw}, 1 | 3 | 4) uint8, not {g.shape}")
+    return g, 1 if g.ndim == 2 else g.shape[2]
+
+
+def tree_build(guide):
+    """The minimum spanning tree of a guide as the blob of include/smx.h (smx_tree_build: host only, no device call).  guide:
+    (h, w) or (h, w, 1 | 3 | 4) uint8.  Returns a uint8 array of smx_tree_bytes(w, h) bytes, 4-byte aligned, which is copied to
+    the device as it is."""
+    g, ch = _tree_guide(guide)
+    h, w = g.shape[:2]
+    nbytes = _lib.lib().smx_tree_bytes(w, h)
+    if nbytes == 0:
+        raise ValueError("tree_build needs w*h < 2^31")
+    blob = np.zeros(nbytes // 4, np.uint32)
+    _lib.check(_lib.lib().smx_tree_build(_ptr(g), ch, w, h, _ptr(blob)))
+    return blob.view(np.uint8)
+
+
+def tree_filter(volume, guide, sigma=None, dmin=0):
+    """Non-local aggregation of one f32 volume on the guide's minimum spanning tree, and its winners (include/smx.h
+    smx_tree_filter; Yang 2012; not a stage of the reference).  volume: (size_d, h, w) float32 -- any volume: an aggregated one, or
+    a raw cost volume for the paper's own form; guide: (h, w) or (h, w, 1 | 3 | 4) uint8; sigma: None (the default 25.5, the
+    paper's 0.1 of the gray range: a starting point), a float or TreeParams.  Returns (filtered (size_d, h, w) float32 -- weighted
+    sums, not means --, best (h, w) float32, label map (h, w) float32 = dmin + winning slice)."""
+    p = _tree_params(sigma, "tree_filter")
+    v = _c(volume, np.float32)
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError("tree_filter expects a (size_d, h, w) float32 volume")
+    size_d, h, w = v.shape
+    g, ch = _tree_guide(guide, h, w)
+    out = np.empty((size_d, h, w), np.float32)
+    best = np.empty((h, w), np.float32)
+    disp = np.empty((h, w), np.float32)
+    _lib.check(_lib.lib().smx_tree_filter(C.byref(p), _ptr(v), _ptr(g), ch, w, h, int(dmin), size_d, _ptr(out), _ptr(best),
+                                          _ptr(disp)))
+    return out, best, disp
+
+
 def uniqueness_filter(keys, sec, disparity, ratio, vmin, new_val, want_margin=False):
     """The uniqueness (peak-ratio) test on a disparity map (include/smx.h smx_uniqueness_filter; not a stage of the
     reference).  keys: (h, w) int64 packed WTA keys of the view; sec: (h, w) float32, the winners' second-best cost (plane 0
